@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the fusion hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--precision bf16|f32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--precision bf16|f32] [--dump-outputs DIR] [--full]
 
 N>1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 (one rank per GPU, RCCL).  A "step" is one optimizer step of the training path on one packed
@@ -14,10 +14,18 @@ reference has no RGB+D image encoder; one "image" is one sample = (RG node embed
 Nr drawn from the real 303..530 histogram, 13 KG category embeddings [13,128]); batch 16 per GPU,
 bf16 MFMA operands with fp32 accumulation/activations.  Weak scaling: 16 samples per GPU.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant node-level kernel (in bf16 mode one of the fused row-tile
-kernels of csrc/fused_rows.hip; in f32 mode the grouped MFMA GEMM) with HIP events recorded on its launch stream, and lists
-every kernel family of the step under `roofline.kernels`; `forward`, `sweep` and `f32` are the inference rate, the batch
-sweep and the exact-f32 step; `cpu_baseline` times the CPU restatements of the reference path on the same workload.
+Prints ONE JSON line (rank 0).  A plain run does W untimed steps, then times exactly K steps between device synchronisations
+(`ms_per_step` = their time / K).  `--dump-outputs DIR` writes what the last timed step returned and left behind: its loss
+terms, its predictions, its gradient norm (before clipping) and the parameters, as DIR/<name>.npy (float32; rank 0's).
+The optimizer runs with lr = 0, so every step starts from the seeded parameters and the same arguments give the same
+outputs up to the rounding of the fp32 atomics.
+
+`--full` adds the diagnostic legs below, each run after the timed steps.  `roofline` prices the dominant node-level kernel
+(in bf16 mode one of the fused row-tile kernels of csrc/fused_rows.hip; in f32 mode the grouped MFMA GEMM) with HIP events
+recorded on its launch stream, and lists every kernel family of the step under `roofline.kernels`; `forward`, `sweep` and
+`f32` are the inference rate, the batch sweep and the exact-f32 step; `cpu_baseline` times the CPU restatements of the
+reference path on the same workload; with N>1, `ddp` times the gradient all-reduce.  The --no-* options drop single legs
+of a --full run.
 """
 import argparse
 import ctypes as C
@@ -133,15 +141,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=16, help="samples per GPU per step")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the HIP-event roofline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward / batch-sweep / f32 legs (single-GPU runs only)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the diagnostic legs: roofline, forward, "
+                    "batch sweep, config3, epoch and f32 legs, CPU baseline, and the all-reduce diagnostics with N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss terms, predictions, gradient "
+                    "norm and the parameters as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the HIP-event roofline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the forward / batch-sweep / f32 legs (single-GPU runs only)")
     ap.add_argument("--allreduce", default="bucketed", choices=["bucketed", "single", "oneshot"],
                     help="gradient all-reduce for --gpus N > 1: two buckets, the first overlapped with the node-level backward "
                          "(default), one flat all-reduce after it, or all_to_all + local sum + all_gather (one exchange step per direction)")
     ap.add_argument("--backend", default="nccl", help="process-group backend for --gpus N > 1 (nccl = RCCL; gloo lets a "
                     "one-GPU box rehearse the multi-rank path with every rank on the same device)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -169,7 +183,11 @@ def main():
     model = build_multimodal_model({}).to(dev).set_precision(args.precision).train()   # reference defaults, dropout 0.3
     if world > 1:
         broadcast_parameters(model._engine)
-    trainer = NativeTrainer(model, lr=5e-4, weight_decay=1e-4, grad_allreduce={"bucketed": BucketedGradAllReducer, "single": GradAllReducer, "oneshot": OneShotGradAllReducer}[args.allreduce]() if world > 1 else None)
+    # lr = 0: every step runs the whole AdamW kernel, but the parameters stay the seeded ones, so each step's inputs are fixed by
+    # the arguments (batch i % 8, dropout seed i).  With a moving state the gradients' fp32 atomics, which sum in a different order
+    # on every run, reach the parameters through AdamW's sign-like first steps and grow into percent-level differences within a
+    # few hundred steps.  The kernels' work does not depend on the values.
+    trainer = NativeTrainer(model, lr=0.0, weight_decay=1e-4, grad_allreduce={"bucketed": BucketedGradAllReducer, "single": GradAllReducer, "oneshot": OneShotGradAllReducer}[args.allreduce]() if world > 1 else None)
 
     if world > 1:
         # weak scaling: global minibatches of world x batch samples, the same on every rank (common seed), each rank taking the share
@@ -212,17 +230,26 @@ def main():
             if sum(times) >= min_seconds or len(times) >= max_blocks:
                 return times
 
-    def train_step(i):
-        trainer.step(*batches[i % len(batches)])
+    last = {}
 
-    blocks = timed_blocks(train_step, args.steps, args.warmup)
-    elapsed = float(np.median(blocks))
+    def train_step(i):
+        last["terms"], last["pred"] = trainer.step(*batches[i % len(batches)])
+
+    # the headline: exactly args.steps timed steps in one block (same inputs, same dropout seeds on every run)
+    elapsed = timed_blocks(train_step, args.steps, args.warmup, min_seconds=0.0)[0]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outs = {"loss_terms": last["terms"], "pred": last["pred"], "grad_norm": trainer.opt.grad_norm(),
+                "params": model._engine.flat_params}
+        for name, t in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
+    kernel_timing = args.full and not args.no_kernel_timing
 
     # ---- multi-GPU diagnostics (every rank runs the steps; rank 0 reports): what the communicator says the world is, event-timed
     # all-reduce per bucket, how much of the overlapped bucket hid behind the backward kernels, and the same steps with ONE plain
     # all-reduce behind the backward for comparison
     ddp_info = None
-    if world > 1:
+    if world > 1 and args.full:
         ar = trainer.grad_allreduce
         ar.enable_timing(True)
         for i in range(args.warmup, args.warmup + min(args.steps, 30)):
@@ -252,11 +279,11 @@ def main():
     # (every rank runs these steps -- they contain the gradient all-reduce -- only rank 0 records events)
     roof = None
     alg_step = float(np.mean([algorithmic_flops(b[1]) for b in host]))
-    if world > 1:                                               # (whole job: the shares of all ranks)
+    if world > 1 and args.full:                                 # (whole job: the shares of all ranks)
         t = torch.tensor([alg_step], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         alg_step = float(t.item()) / world                      # per-rank mean, as the single-GPU figure
-    if not args.no_kernel_timing:
+    if kernel_timing:
         L = _lib.lib()
         k = min(args.steps, 50)
         if rank == 0:
@@ -266,7 +293,7 @@ def main():
             train_step(i)
         torch.cuda.synchronize()
         t_prof = time.perf_counter() - t1
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and kernel_timing:
         ms, n, fl = C.c_double(), C.c_int32(), C.c_double()
         _lib.check(L.camo_prof_end(C.byref(ms), C.byref(n), C.byref(fl)), "camo_prof_end")
         # An event pair also times its own marker packets: an EMPTY pair on the same stream is reported next to the
@@ -333,7 +360,7 @@ def main():
 
     # ---- single-GPU extras: forward-only rate, batch sweep, exact-f32 step
     extras = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         peak = PEAK_TFLOPS[args.precision]
         L = _lib.lib()
         # (a) inference: eval-mode forward of the same packed minibatches (no attention maps), like validate_fixed
@@ -489,9 +516,8 @@ def main():
             "data": "synthetic",
             "health": {"tail_timeouts": _lib.tail_timeouts(),
                        "note": "arrival waits of the one-launch tail kernel that gave up during this process (0 = every step valid)"},
-            "timing": {"blocks": len(blocks), "steps_per_block": args.steps, "timed_seconds": round(sum(blocks), 3),
-                       "reported": "median block", "min_ms_per_step": round(min(blocks) / args.steps * 1e3, 4),
-                       "max_ms_per_step": round(max(blocks) / args.steps * 1e3, 4)},
+            "timing": {"timed_steps": args.steps, "timed_seconds": round(elapsed, 4),
+                       "reported": "one block of --steps steps between device synchronisations (max over ranks)"},
             "config": {"workload": "BASELINE configs[1] on the path that exists (SURVEY 8d): cross-attention fusion "
                                    "model, packed variable-Nr minibatch (Nr ~ real 303..530 histogram, mean %.0f), "
                                    "Nk=13 real KG rows, train mode dropout 0.3, random-init weights" % nr_mean,
@@ -507,7 +533,7 @@ def main():
         if ddp_info is not None:
             line["ddp"] = ddp_info
         line.update(extras)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(host)
         print(json.dumps(line))
     if world > 1:

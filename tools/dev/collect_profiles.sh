@@ -1,10 +1,10 @@
 #!/bin/bash
-# Developer aid (build container): copies the closing sequence's records from gpurun_out/ (scratch) into profiles/ under the round's name
+# Developer aid (build container): copies the closing sequence's records from $OUT (scratch, default dev_out/) into profiles/ under the round's name
 # and regenerates the derived tables.   ROUND=r04 bash tools/dev/collect_profiles.sh
 set -e
 R=$(cd "$(dirname "$0")/../.." && pwd); cd $R
 ROUND=${ROUND:-r04}
-G=gpurun_out
+G=${OUT:-dev_out}
 cp $G/bench_${ROUND}.json profiles/${ROUND}_bench_bf16.json
 grep -h '^{"metric"' $G/${ROUND}_bench_b16.out | tail -1 > profiles/${ROUND}_bench_bf16_under_rocprof.json
 for n in bench_b16 train_b64 fwd_b256 train_b256 train_b1024; do cp $G/${ROUND}_${n}_kernel_stats.csv profiles/${ROUND}_${n}_kernel_stats.csv; done
