@@ -70,8 +70,8 @@ struct BackArgs {
   DropCfg drop; int save; int exp;
   unsigned long long* stamps;                  // developer timeline (null in product calls)
 };
-extern thread_local int g_back_lead_mode;                   // developer A/B: 0 = KG split blocks always first
-int launch_fused_back(BackArgs& a, int variant, hipStream_t stream);
+// lead_mode: developer A/B (camo_options_t back_lead), 0 = KG split blocks always first
+int launch_fused_back(BackArgs& a, int variant, int lead_mode, hipStream_t stream);
 
 // ---- backward, first half (see fused_rows.hip)
 struct Bwd1Stream {

@@ -1476,8 +1476,7 @@ int launch_fused_front(FrontArgs& a, int variant, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-thread_local int g_back_lead_mode = 1;
-int launch_fused_back(BackArgs& a, int variant, hipStream_t stream) {
+int launch_fused_back(BackArgs& a, int variant, int lead_mode, hipStream_t stream) {
   if (a.B < 1 || a.Nk < 1 || a.Nk > 16 || a.rg_tiles_max < 1 || !a.Q16 || !a.KV16 || !a.Q2_16 || !a.KV2_16 || !a.off || !a.tile_off || !a.tile_desc || !a.inv_nr ||
       !a.part || !a.tickets || a.max_splits < 1 || a.max_splits > FUSED_MAX_SPLITS)
     return (int)hipErrorInvalidValue;
@@ -1496,7 +1495,7 @@ int launch_fused_back(BackArgs& a, int variant, hipStream_t stream) {
   }();
   (void)attr;
   const dim3 grid(a.B * a.max_splits + a.rg_tiles_max);
-  a.lead_tiles = (g_back_lead_mode != 0 && a.rows_rg / 32 >= 256 && (int)grid.x > 512) ? 256 : 0;      // (rows / 32 <= number of real tiles)
+  a.lead_tiles = (lead_mode != 0 && a.rows_rg / 32 >= 256 && (int)grid.x > 512) ? 256 : 0;      // (rows / 32 <= number of real tiles)
   // executed FLOPs per row: out-projection 256 -> 256, FFN layer 0 256 -> 512, both attention directions (2 x 2 x Nk x 256)
   const double rows = (double)a.rows_rg + (double)a.B * a.Nk;
   const int prof = gemm_prof_open(stream, 2.0 * rows * (256.0 * 256.0 + 256.0 * 512.0) + 8.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BACK);

@@ -33,39 +33,32 @@
 namespace {
 
 thread_local std::string g_err;
-// Schedule options: the CALLER's (camo_options_t behind camo_dims_t::options), bound for the duration of one entry-point call.  No
-// option state lives in the library: two engines in one process cannot change each other's schedule.
+// Schedule options are the CALLER's (camo_options_t behind camo_dims_t::options); these are the defaults (options == NULL)
 constexpr camo_options_t k_default_options = {/*sched16*/ -1, /*fused*/ -1, /*tail17*/ -1, /*fused_rt*/ -1, /*wide2*/ -1, /*fused_one*/ 1, /*wide_front_rt*/ 0,
                                               /*tailw*/ -1, /*tailw_bwd*/ -1, /*param_space*/ -1, /*tn_big*/ -1, /*fused_variant*/ 1, /*back_lead*/ 1,
                                               /*tn_balance*/ 1, /*tn_kcap*/ 0, /*tn_exp*/ 0, /*exp*/ 0, /*fused_save*/ 0, /*tail_skip_arrival*/ 0, /*wide2_bwd*/ -1};
-static thread_local const camo_options_t* t_opt = &k_default_options;
-struct OptScope {                     // binds the caller's options (and the other translation units' per-call copies) for one entry-point call
-  const camo_options_t* prev;
-  explicit OptScope(const camo_dims_t* d) : prev(t_opt) {
-    t_opt = (d && d->options) ? d->options : &k_default_options;
-    g_back_lead_mode = t_opt->back_lead; g_gemm16_balance = t_opt->tn_balance; g_gemm16_tn_kcap = t_opt->tn_kcap; g_gemm16_exp = t_opt->tn_exp;
-    g_gemm16_tn_big = t_opt->tn_big;
-    if (d && d->options && d->options->tail_skip_arrival) { g_tail_debug_skip = d->options->tail_skip_arrival; d->options->tail_skip_arrival = 0; }
-  }
-  ~OptScope() { t_opt = prev; }
-};
-#define g_opt_sched16 (t_opt->sched16)
-#define g_opt_fused (t_opt->fused)
-#define g_opt_param_space (t_opt->param_space)
-#define g_opt_tail17 (t_opt->tail17)
-#define g_opt_fused_variant (t_opt->fused_variant)
-#define g_opt_fused_rt (t_opt->fused_rt)
-#define g_opt_wide2 (t_opt->wide2)
-#define g_opt_wide2_bwd (t_opt->wide2_bwd)
-#define g_opt_fused_one (t_opt->fused_one)
-#define g_opt_wide_front_rt (t_opt->wide_front_rt)
-#define g_opt_tailw_bwd (t_opt->tailw_bwd)
-#define g_opt_tailw (t_opt->tailw)
-#define g_opt_exp (t_opt->exp)
-#define g_opt_fused_save (t_opt->fused_save)
 unsigned long long* g_dbg_stamps = nullptr;   // developer timeline buffer of the fused kernels (camo_debug_set_stamps; like camo_prof_*: a profiling facility, not a schedule option)
 int g_dbg_stamp_blocks = 0;
-static thread_local bool t_tailw_bwd_planes = false;   // set by a training forward that built the tail's transposed planes (this call's workspace)
+
+// What one entry-point call needs below the entry point: built there, on its stack, and passed down by reference.  No option or per-call
+// state lives in the library, so two engines in one process (or two threads) cannot change each other's schedule or hand-offs.
+struct Call {
+  const camo_options_t& opt;          // the caller's options (dims->options), or k_default_options
+  // camo_forward_cached / camo_forward_loss_backward: caller-owned weight shadows (camo_shadow_bytes), null otherwise.  The 14
+  // fragment-order bf16 copies the fused kernels stream live there instead of in the per-batch workspace, so that the optimizer call
+  // can leave them ready for the next step (camo_clip_adamw_shadows) and the forward need not rebuild them (shadows_valid).
+  void* shadows = nullptr;
+  bool shadows_valid = false;
+  bool fold_missing = false;          // camo_forward_cached(shadows_valid = 2): valid shadows that lack the inference calls' folded in-projection
+  int shadows_state = 0;              // what the fused forward left in them: 0 untouched, 1 forward set, 2 forward + transposed
+  // clears that a forward without a shadow launch leaves to the first backward kernel (forward_nodes17 -> backward_nodes17)
+  void* zero_bwd1_ptr[FUSED_BWD1_MAXZ]; unsigned zero_bwd1_bytes[FUSED_BWD1_MAXZ]; int nzero_bwd1 = 0;
+  bool tailw_bwd_planes = false;      // the training forward built the two-plane tail's transposed planes (this call's workspace)
+  hipEvent_t tail_event = nullptr;    // camo_forward_loss_backward's optional event (record_tail_event)
+  int tail_skip = 0;                  // the caller's one-shot tail_skip_arrival: read by the entry points that can launch the one-launch tail,
+  bool tail_skip_taken = false;       // which write 0 back to the caller's options once that launch took it
+  explicit Call(const camo_dims_t* d) : opt(*(d && d->options ? d->options : &k_default_options)) {}
+};
 
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 int fail_hip(int e, const char* where) {
@@ -319,8 +312,11 @@ void set_bcast(GemmProb& p, const float* v, int ldv, const int* row_sample, cons
 
 // ---- the bf16 schedule's GEMM batch (gemm16.h) ------------------------------------------------
 struct GB16 {
-  Gemm16Batch b; hipStream_t st;
-  GB16(const DropCfg& d, hipStream_t st_) : st(st_) { std::memset(&b, 0, sizeof(b)); b.drop = d; }
+  Gemm16Batch b; Gemm16Knobs kn; hipStream_t st;
+  GB16(const DropCfg& d, const camo_options_t& o, hipStream_t st_) : st(st_) {
+    std::memset(&b, 0, sizeof(b)); b.drop = d;
+    kn.tn_big = o.tn_big; kn.balance = o.tn_balance; kn.tn_kcap = o.tn_kcap; kn.exp = o.tn_exp;
+  }
   Gemm16Prob& add() { Gemm16Prob& p = b.p[b.n++]; std::memset(&p, 0, sizeof(p)); p.aux_scale = 1.f; return p; }
   // y = x.W^T (+bias): x16 [M,K], W16 [N,K]; fp32 result y and/or bf16 result y16 (either may be null)
   Gemm16Prob& nt(const us* x, int ldx, const us* W, int ldw, const float* bias, float* y, int ldy, us* y16, int ldy16,
@@ -339,7 +335,7 @@ struct GB16 {
   }
   int run() {
     if (b.n == 0) return 0;
-    int e = launch_gemm16_batch(b, st);
+    int e = launch_gemm16_batch(b, kn, st);
     b.n = 0;
     return e;
   }
@@ -352,9 +348,9 @@ void set_bcast(Gemm16Prob& p, const float* v, int ldv, const int* row_sample, co
 
 // The bf16 schedule runs when the operands can live in HBM as bf16 tiles the gemm16 kernel takes whole:
 // cross-attention fusion with both input projections, every width a multiple of 64, head_dim 32 attention
-// on the MFMA kernels.  Anything else (and CAMO_SCHED16=0) takes the general fp32-operand schedule.
-bool sched16_ok(const camo_dims_t& d, const float* const* P, int precision, int T, int Nk, int max_nr) {
-  if (g_opt_sched16 == 0 || precision != CAMO_PREC_BF16 || d.fusion_type != CAMO_FUSION_CROSS_ATTENTION) return false;
+// on the MFMA kernels.  Anything else (and option sched16 = 0) takes the general fp32-operand schedule.
+bool sched16_ok(const camo_options_t& o, const camo_dims_t& d, const float* const* P, int precision, int T, int Nk, int max_nr) {
+  if (o.sched16 == 0 || precision != CAMO_PREC_BF16 || d.fusion_type != CAMO_FUSION_CROSS_ATTENTION) return false;
   if (!P[CAMO_P_RG_PROJ_W] || !P[CAMO_P_KG_PROJ_W]) return false;
   if ((d.hidden_dim % 64) || (d.rg_dim % 64) || (d.kg_dim % 64)) return false;
   if (!attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, false) || !attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, true))
@@ -420,7 +416,7 @@ int heads_backward(const camo_dims_t& d, const float* const* hp, float* const* h
 
 
 // ---- node-level forward of the bf16 schedule: CrossAttentionFusion.forward, fusion_model.py:75-135 ----
-int forward_nodes16(const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets,
+int forward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets,
                     const int32_t* row_sample, const float* inv_nr, const float* kg,
                     int B, int T, int Nk, int max_nr, const Ws& w, float* attn_rg2kg, float* attn_kg2rg, const DropCfg& drop,
                     hipStream_t st) {
@@ -456,7 +452,7 @@ int forward_nodes16(const camo_dims_t& d, const float* const* P, const float* rg
     pad(h.dU2, tk, w.TKp, H); pad(h.dQKVkg, tk, w.TKp, 3 * H); pad(h.dG, tk, w.TKp, H); pad(h.H2, tk, w.TKp, 2 * H);
     CK(launch_prep(pb, st), "prep (clear + bf16 casts)");
   }
-  GB16 g(drop, st);
+  GB16 g(drop, c.opt, st);
   // input projections: fp32 for the residual stream, bf16 for the GEMMs that read them
   g.nt(h.KG, Dk, h.Wkg, Dk, P[CAMO_P_KG_PROJ_B], w.G, H, h.G, H, TK, H, Dk);
   g.nt(h.X, D, h.Wrg, D, P[CAMO_P_RG_PROJ_B], w.R, H, h.R, H, T, H, D);
@@ -509,22 +505,12 @@ int forward_nodes16(const camo_dims_t& d, const float* const* P, const float* rg
 }
 
 // ---- node-level forward of the fused row-tile schedule: the same function in 3 launches (fused_rows.h) ----
-bool fused17_ok(const camo_dims_t& d, const float* const* P, int precision, int Nk, int max_nr) {
-  return g_opt_fused != 0 && precision == CAMO_PREC_BF16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS &&
+bool fused17_ok(const camo_options_t& o, const camo_dims_t& d, const float* const* P, int precision, int Nk, int max_nr) {
+  return o.fused != 0 && precision == CAMO_PREC_BF16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS &&
          P[CAMO_P_RG_PROJ_W] && P[CAMO_P_KG_PROJ_W];
 }
 
-// camo_forward_loss_backward's optional caller-owned weight shadows (camo_shadow_bytes): the 14 fragment-order bf16 copies the
-// fused kernels stream live there instead of in the per-batch workspace, so that the optimizer call can leave them ready for
-// the next step (camo_clip_adamw_shadows) and the forward need not rebuild them (CAMO_FLAG_SHADOWS_VALID).
-static thread_local void* t_zero_front_ptr[FUSED_FRONT_MAXZ]; static thread_local unsigned t_zero_front_bytes[FUSED_FRONT_MAXZ];
-static thread_local int t_nzero_front = 0;
-static thread_local void* t_zero_bwd1_ptr[FUSED_BWD1_MAXZ]; static thread_local unsigned t_zero_bwd1_bytes[FUSED_BWD1_MAXZ];
-static thread_local int t_nzero_bwd1 = 0;
-static thread_local void* t_shadows = nullptr;
-static thread_local bool t_shadows_valid = false;
-static thread_local bool t_fold_missing = false;  // camo_forward_cached(shadows_valid = 2): valid shadows that lack the inference calls' folded in-projection
-static thread_local int t_shadows_state = 0;    // what the fused forward left in external shadows: 0 untouched, 1 forward set, 2 forward + transposed
+// the caller-owned weight shadows (Call::shadows)
 struct ShadowSet { us16 *Wrg, *Wkg, *Wqkv_rg, *Wqkv_kg, *Wo1, *Wo2, *W1, *W2, *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT, *Wf_rg; float* bf_rg; size_t bytes; };
 static ShadowSet shadow_carve(void* base) {
   ShadowSet x{};
@@ -538,9 +524,9 @@ static ShadowSet shadow_carve(void* base) {
   x.bytes = (c.off + 255) & ~size_t(255);
   return x;
 }
-static void bind_shadows(Ws& w) {                 // (after every carve() of a call that was handed external shadows)
-  if (!t_shadows) return;
-  const ShadowSet x = shadow_carve(t_shadows);
+static void bind_shadows(const Call& c, Ws& w) {   // (after every carve() of a call that was handed external shadows)
+  if (!c.shadows) return;
+  const ShadowSet x = shadow_carve(c.shadows);
   Ws::F17& f = w.f;
   f.Wrg = x.Wrg; f.Wkg = x.Wkg; f.Wqkv_rg = x.Wqkv_rg; f.Wqkv_kg = x.Wqkv_kg; f.Wo1 = x.Wo1; f.Wo2 = x.Wo2; f.W1 = x.W1; f.W2 = x.W2;
   f.W1T = x.W1T; f.W2T = x.W2T; f.Wo1T = x.Wo1T; f.Wo2T = x.Wo2T; f.WcRgT = x.WcRgT; f.WcKgT = x.WcKgT;
@@ -549,8 +535,8 @@ static void bind_shadows(Ws& w) {                 // (after every carve() of a c
 
 // Which tile family a fused forward takes (fused_rows.h): 0 = 32-row tiles, one per block of 4 waves (small batches: one tile
 // per CU is all there is); 2 / 4 = that many tiles per block of 8 waves (fused_wide.hip), chosen so that the blocks still fill the chip.
-static int wide_rt(int T, int max_nr, bool save = false) {
-  int rt = g_opt_fused_rt;
+static int wide_rt(const camo_options_t& o, int T, int max_nr, bool save = false) {
+  int rt = o.fused_rt;
   // by size: inference calls from about half a 128-row block per CU on (64-row blocks below that).  Calls that save for a backward stay on the 32-row kernels:
   // the saved-tensor stores of the one-launch kernel are not tuned yet (measured slower: B = 64 step 0.53 vs 0.40 ms)
   // (measured eval forward, us: B = 32 [13.5 k rows] 87 / 85 / 103 for 32-row / 2 / 4 tiles per block; B = 48 [20 k] 116 / 103 / 106; B = 56 [24 k] 131 / 112 / 108)
@@ -563,39 +549,49 @@ static int wide_rt(int T, int max_nr, bool save = false) {
 // The RG rows' whole forward in one launch of 64-row half-blocks, two independent blocks per CU, + the KG rows' launch behind it
 // (fused_wide2.hip).  By size for inference AND training calls (the saving / dropout variants write the backward's saved set); a forced
 // fused_rt selects the 8-wave / 32-row kernels.
-static bool wide2_taken(int T, int max_nr, bool save, bool dropping) {
+static bool wide2_taken(const camo_options_t& o, int T, int max_nr, bool save, bool dropping) {
   (void)dropping;
-  if (g_opt_wide2 == 0 || g_opt_fused_one == 0 || max_nr > wide2_max_rows()) return false;
-  if (g_opt_wide2 > 0) return true;
+  if (o.wide2 == 0 || o.fused_one == 0 || max_nr > wide2_max_rows()) return false;
+  if (o.wide2 > 0) return true;
   // training calls from 57 344 rows: their blocks are twice as long (the saved set, the dropout hashes), so the second round of blocks
   // must be nearly full before they beat the 32-row back half (measured, ms per step without / with: B = 96 0.517 / 0.540, B = 128
   // 0.637 / 0.621, B = 192 0.864 / 0.804, B = 256 1.076 / 0.979)
   // inference calls from 10 240 rows (eval forward, us without / with: B = 16 59 / 66, B = 24 72.5 / 69.8, B = 32 77 / 71, B = 48 101 / 82)
-  return g_opt_fused_rt < 0 && g_opt_wide_front_rt == 0 && T >= (save ? 57344 : 10240);
+  return o.fused_rt < 0 && o.wide_front_rt == 0 && T >= (save ? 57344 : 10240);
 }
 
 // Training calls (save): the front half alone on wide blocks -- 64-row blocks from 10 240 packed rows (front 21 -> 17 us at B = 24,
 // 31 -> 26 at B = 48, 37 -> 28 at B = 56), 128-row blocks from 28 672.  -> sub-tiles per block, 0 = the 32-row front kernel.
 // ONE predicate for everything that rides on that launch (the two-plane tail's weight planes are built by its extra blocks).
-static int wide_train_front_rt(int T, int max_nr, bool save) {
-  if (!save || wide_rt(T, max_nr, save) || g_opt_fused_rt >= 0 || g_opt_wide_front_rt < 0) return 0;
-  if (T < 10240 && g_opt_wide_front_rt <= 0) return 0;
-  const int wf_rt = g_opt_wide_front_rt > 0 ? g_opt_wide_front_rt : (T >= 4 * 32 * 224 ? 4 : 2);
+static int wide_train_front_rt(const camo_options_t& o, int T, int max_nr, bool save) {
+  if (!save || wide_rt(o, T, max_nr, save) || o.fused_rt >= 0 || o.wide_front_rt < 0) return 0;
+  if (T < 10240 && o.wide_front_rt <= 0) return 0;
+  const int wf_rt = o.wide_front_rt > 0 ? o.wide_front_rt : (T >= 4 * 32 * 224 ? 4 : 2);
   if (wf_rt != 1 && wf_rt != 2 && wf_rt != 4) return 0;
   return max_nr <= wide_max_rows(wf_rt) - 64 * wf_rt ? wf_rt : 0;
 }
 
-static bool tailw_taken(const camo_dims_t& d, int B, int T, int max_nr, bool save, bool dropping) {
+static bool tailw_taken(const camo_options_t& o, const camo_dims_t& d, int B, int T, int max_nr, bool save, bool dropping) {
   // (B <= 32: the grouped fp32 tail, forward only, is the shorter one: 29.8 vs 33.5 us at B = 32; equal at 48)
-  return g_opt_tailw != 0 && g_opt_fused_one != 0 && (wide_rt(T, max_nr, save) >= 2 || wide2_taken(T, max_nr, save, dropping)) && tail_wide_ok(B, d.num_classes) &&
-         (g_opt_tailw > 0 || B > 32 || !tail_fused_ok(B, d.num_classes));
+  return o.tailw != 0 && o.fused_one != 0 && (wide_rt(o, T, max_nr, save) >= 2 || wide2_taken(o, T, max_nr, save, dropping)) && tail_wide_ok(B, d.num_classes) &&
+         (o.tailw > 0 || B > 32 || !tail_fused_ok(B, d.num_classes));
 }
 
-int forward_nodes17(const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets, const Desc& bd,
+// The per-sample tail of the fused schedule as one launch (tail17), where a caller of the fused schedule asks for it
+static bool tail17_taken(const camo_options_t& o, const camo_dims_t& d, int B) { return o.tail17 != 0 && tail_fused_ok(B, d.num_classes); }
+
+// The projections' and in-projections' weight gradients in parameter space (no dR / dG product in the second backward kernel, 131 k
+// instead of 427 k MACs per row, one small launch behind the weight gradients): from ~10 k packed rows on -- below that the extra launch
+// (~10 us) costs what the second kernel saves (measured: B = 16 +10 us, B = 64 -22 us, B = 256 -105 us per step).  The forward reads it
+// too: R16 is an operand of the row-space form only.
+static bool param_space_bwd(const camo_options_t& o, int T) { return o.param_space < 0 ? T >= 10240 : o.param_space > 0; }
+
+int forward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets, const Desc& bd,
                     const float* kg, int B, int T, int Nk, int max_nr, const Ws& w, const DropCfg& drop, bool save, hipStream_t st, int want_tailw = 0) {
   const int H = 256, D = 128, TK = B * Nk;
   const size_t HH = (size_t)H * H;
   const Ws::F17& f = w.f;
+  FrontArgs fa; std::memset(&fa, 0, sizeof(fa));
   {   // weight shadows (bf16, fragment order) + the clear of the step's atomics block
     ShadowBatch sb; std::memset(&sb, 0, sizeof(sb));
     auto job = [&](us* dst, int N, int K, const float* s0, int r0, const float* s1 = nullptr, int r1 = 0) {
@@ -603,8 +599,8 @@ int forward_nodes17(const camo_dims_t& d, const float* const* P, const float* rg
       J.dst = dst; J.N = N; J.K = K; J.transposed = 0; J.nsrc = s1 ? 2 : 1;
       J.src[0] = s0; J.rows[0] = r0; J.ld[0] = K; J.src[1] = s1; J.rows[1] = r1; J.ld[1] = K;
     };
-    const bool build = !t_shadows_valid;        // (valid: camo_clip_adamw_shadows left them ready; only the clears ride in this launch)
-    if (t_shadows) t_shadows_state = save ? 2 : 1;
+    const bool build = !c.shadows_valid;        // (valid: camo_clip_adamw_shadows left them ready; only the clears ride in this launch)
+    if (c.shadows) c.shadows_state = save ? 2 : 1;
     if (build) {
     job(f.Wrg, H, D, P[CAMO_P_RG_PROJ_W], H); job(f.Wkg, H, D, P[CAMO_P_KG_PROJ_W], H);
     job(f.Wqkv_rg, 3 * H, H, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);       // [Wq1; Wk2; Wv2]: what RG rows are projected with
@@ -642,44 +638,38 @@ int forward_nodes17(const camo_dims_t& d, const float* const* P, const float* rg
     }
     // inference calls: the RG rows' folded in-projection rides with every rebuild of the forward set, and alone when the caller's valid
     // shadows come from the optimizer call, which does not build it (camo_forward_cached, shadows_valid = 2)
-    const bool fold = !save && (build || t_fold_missing);
+    const bool fold = !save && (build || c.fold_missing);
     if (build) {
       CK(launch_weight_shadows(sb, st), "weight shadows");
       if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
                                    f.Wf_rg, f.bf_rg, st), "folded in-projection");
-      t_nzero_front = t_nzero_bwd1 = 0;
     } else {
       if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
                                   f.Wf_rg, f.bf_rg, st), "folded in-projection");
       // no shadow launch this step: the clears ride elsewhere -- the atomics block and d(mean H) at the end of the front
       // kernel's blocks (first use: the back kernel's pooled sums), the operand pad rows in extra blocks of the first backward
       // kernel (first use: the weight-gradient launch)
-      t_nzero_front = t_nzero_bwd1 = 0;
       for (int i = 0; i < sb.nzero; ++i) {
         const bool early = sb.zero_ptr[i] == (void*)w.zero_base || sb.zero_ptr[i] == (void*)w.dHm1 || sb.zero_ptr[i] == (void*)w.dHm2 || sb.zero_ptr[i] == (void*)w.tailsum;
         if (sb.zero_bytes[i] > 0xFFFFFFF0ull) return fail(CAMO_E_ARG, "clear range too large");
         if (early) {
-          if (t_nzero_front >= FUSED_FRONT_MAXZ) return fail(CAMO_E_ARG, "too many early clear ranges");
-          t_zero_front_ptr[t_nzero_front] = sb.zero_ptr[i]; t_zero_front_bytes[t_nzero_front++] = (unsigned)sb.zero_bytes[i];
+          if (fa.nzero >= FUSED_FRONT_MAXZ) return fail(CAMO_E_ARG, "too many early clear ranges");
+          fa.zero_ptr[fa.nzero] = sb.zero_ptr[i]; fa.zero_bytes[fa.nzero++] = (unsigned)sb.zero_bytes[i];
         } else {
-          if (t_nzero_bwd1 >= FUSED_BWD1_MAXZ) return fail(CAMO_E_ARG, "too many late clear ranges");
-          t_zero_bwd1_ptr[t_nzero_bwd1] = sb.zero_ptr[i]; t_zero_bwd1_bytes[t_nzero_bwd1++] = (unsigned)sb.zero_bytes[i];
+          if (c.nzero_bwd1 >= FUSED_BWD1_MAXZ) return fail(CAMO_E_ARG, "too many late clear ranges");
+          c.zero_bwd1_ptr[c.nzero_bwd1] = sb.zero_ptr[i]; c.zero_bwd1_bytes[c.nzero_bwd1++] = (unsigned)sb.zero_bytes[i];
         }
       }
     }
   }
-  FrontArgs fa; std::memset(&fa, 0, sizeof(fa));
   fa.qscale = 1.0f / sqrtf(32.0f); fa.save = save ? 1 : 0;
   fa.s[0] = FrontStream{rg, T, f.Wrg, P[CAMO_P_RG_PROJ_B], f.Wqkv_rg, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, f.X16, f.R16, f.Q16, f.KV2_16, 0};
   fa.s[1] = FrontStream{kg, TK, f.Wkg, P[CAMO_P_KG_PROJ_B], f.Wqkv_kg, P[CAMO_P_A2_IN_B], P[CAMO_P_A1_IN_B] + H, f.KG16, f.G16, f.Q2_16, f.KV16, 0};
-  fa.stamps = g_dbg_stamps; fa.exp = g_opt_exp;
-  fa.nzero = t_nzero_front;
-  for (int i = 0; i < t_nzero_front; ++i) { fa.zero_ptr[i] = t_zero_front_ptr[i]; fa.zero_bytes[i] = t_zero_front_bytes[i]; }
-  t_nzero_front = 0;
-  const bool w2 = wide2_taken(T, max_nr, save, drop.p > 0.f);
-  const int rt = w2 ? 0 : wide_rt(T, max_nr, save);
-  const bool one = w2 || (rt >= 2 && g_opt_fused_one != 0);
-  const int wf_rt = wide_train_front_rt(T, max_nr, save);
+  fa.stamps = g_dbg_stamps; fa.exp = c.opt.exp;
+  const bool w2 = wide2_taken(c.opt, T, max_nr, save, drop.p > 0.f);
+  const int rt = w2 ? 0 : wide_rt(c.opt, T, max_nr, save);
+  const bool one = w2 || (rt >= 2 && c.opt.fused_one != 0);
+  const int wf_rt = wide_train_front_rt(c.opt, T, max_nr, save);
   const bool wide_train_front = wf_rt != 0;
   if (want_tailw && !(one || wide_train_front)) return fail(CAMO_E_ARG, "two-plane tail asked for on a call whose front launch cannot build its weight planes");
   if ((one || wide_train_front) && want_tailw) {
@@ -725,7 +715,7 @@ int forward_nodes17(const camo_dims_t& d, const float* const* P, const float* rg
   // (the back half of training calls stays on the 32-row kernel, whose saving + dropout variant is the faster one: 77 vs 94 us at B = 64)
   else if (wide_train_front)
     CK(launch_wide_front(fa, wf_rt, st, 0), "fused forward, front half (wide tiles)");
-  else CK(launch_fused_front(fa, g_opt_fused_variant, st), "fused forward, front half");
+  else CK(launch_fused_front(fa, c.opt.fused_variant, st), "fused forward, front half");
   BackArgs ba; std::memset(&ba, 0, sizeof(ba));
   ba.s[0] = BackStream{f.Wo1, P[CAMO_P_A1_OUT_B], f.W1, P[CAMO_P_F1_B0], P[CAMO_P_LN1_W], P[CAMO_P_LN1_B], f.R16,
                        f.O16, f.Y16, f.XH16, f.rstd1, f.mask1, w.Ymean, w.H1mean, SITE_FFN_RG};
@@ -735,27 +725,23 @@ int forward_nodes17(const camo_dims_t& d, const float* const* P, const float* rg
   ba.off = rg_offsets; ba.tile_off = bd.tile_off; ba.tile_desc = bd.tile_desc; ba.inv_nr = bd.inv_nr; ba.lse2 = f.lse2;
   ba.B = B; ba.Nk = Nk; ba.rows_rg = T; ba.rg_tiles_max = T / 32 + B;          // >= sum of ceil(Nr / 32); surplus blocks exit at once
   ba.part = f.part; ba.tickets = w.tickets; ba.max_splits = (max_nr + 63) / 64;
-  ba.drop = drop; ba.save = save ? 1 : 0; ba.exp = g_opt_exp;
+  ba.drop = drop; ba.save = save ? 1 : 0; ba.exp = c.opt.exp;
   ba.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)g_dbg_stamp_blocks * 8 : nullptr;
-  // (R16 is read by the row-space form of the projections' weight gradients only: the same predicate as backward_nodes17's; tests that
-  // read it back run an inference call with fused_save)
-  const bool param_space_bwd = g_opt_param_space < 0 ? T >= 10240 : g_opt_param_space > 0;
-  if (w2) CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, (!param_space_bwd || g_opt_fused_save != 0) ? 1 : 0, st),
+  // (R16 is read by the row-space form of the projections' weight gradients only; tests that read it back run an inference call with fused_save)
+  if (w2) CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, (!param_space_bwd(c.opt, T) || c.opt.fused_save != 0) ? 1 : 0, st),
              "fused forward, RG rows in one launch (64-row half-blocks)");
   else if (one) CK(launch_wide_rgfwd(fa.s[0], fa.qscale, ba, rt, max_nr, st), "fused forward, RG rows in one launch (wide tiles)");
   else if (rt) CK(launch_wide_back(ba, rt, max_nr, st), "fused forward, back half (wide tiles)");
-  else CK(launch_fused_back(ba, g_opt_fused_variant, st), "fused forward, back half");
+  else CK(launch_fused_back(ba, c.opt.fused_variant, c.opt.back_lead, st), "fused forward, back half");
   return 0;
 }
 
 // ---- node-level backward of the fused row-tile schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
-int backward_nodes17(const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
+int backward_nodes17(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
                      int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st);
-int tail17(const camo_dims_t& d, const float* const* P, float* const* Gr, const Ws& w, int B, float* outs, const FusedLoss* fl,
-           const DropCfg& drop, hipStream_t st);
 
 // ---- node-level backward of the bf16 schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
-int backward_nodes16(const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets,
+int backward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets,
                      const int32_t* row_sample, const float* inv_nr, int B, int T, int Nk, int max_nr, const Ws& w,
                      const DropCfg& drop, hipStream_t st) {
   const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, TK = B * Nk, nh = d.num_heads;
@@ -775,7 +761,7 @@ int backward_nodes16(const camo_dims_t& d, const float* const* P, float* const* 
     if (rg_side) { p.row_sample = row_sample; p.inv_nr = inv_nr; p.uniform_n = 0; } else { p.row_sample = nullptr; p.inv_nr = nullptr; p.uniform_n = Nk; }
     if (p.flags & GF_A_KMAJOR) p.ldc16 = B;               // (sample count of a weight-gradient problem)
   };
-  GB16 g(drop, st);
+  GB16 g(drop, c.opt, st);
   // first FFN layer: dY = bcast(dpool)/n + dH1.W1 ; dW1 += dH1^T.Y -- and, at hidden_dim 256, the LayerNorm backward
   // dY -> dU (+ dgamma, dbeta) as the epilogue of the dY product (whole-row tiles)
   if (H == 256) {
@@ -835,7 +821,7 @@ int backward_nodes16(const camo_dims_t& d, const float* const* P, float* const* 
 }
 
 // the per-sample tail of the fused schedule as one launch (misc.hip, tail_fused_kernel); fl == null: forward only
-int tail17(const camo_dims_t& d, const float* const* P, float* const* Gr, const Ws& w, int B, float* outs, const FusedLoss* fl,
+int tail17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const Ws& w, int B, float* outs, const FusedLoss* fl,
            const DropCfg& drop, hipStream_t st) {
   const int H = 256;
   TailFusedArgs a; std::memset(&a, 0, sizeof(a));
@@ -859,9 +845,11 @@ int tail17(const camo_dims_t& d, const float* const* P, float* const* Gr, const 
   a.counters = reinterpret_cast<unsigned int*>(w.tailsum + (size_t)B * 4 * H);
   a.B = B; a.C = d.num_classes; a.mode = fl ? 1 : 0; a.drop = drop;
   a.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)4 * g_dbg_stamp_blocks * 8 : nullptr;
+  a.debug_skip = c.tail_skip;
   const bool groups = fl && B > 16;
   if (groups) { a.comb_out = w.comb; a.F1_out = w.F1; a.fused_out = w.fused; a.dhid_out = w.dhid; a.dfused_out = w.dfused; a.dF1_out = w.dF1; }
   CK(launch_tail_fused(a, st), "per-sample tail (one launch)");
+  c.tail_skip_taken = a.debug_skip != 0;
   if (groups) {
     // more than one group of 16 samples: the big weight gradients of the tail are sums over every group -- one batched launch
     // (contraction over the B samples), operands = the copies the tail kernel left in the workspace
@@ -877,15 +865,12 @@ int tail17(const camo_dims_t& d, const float* const* P, float* const* Gr, const 
   return 0;
 }
 
-int backward_nodes17(const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
+int backward_nodes17(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
                      int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st) {
   const int H = 256, D = 128, TK = B * Nk;
   const size_t HH = (size_t)H * H;
   const Ws::F17& f = w.f;
-  // The projections' and in-projections' weight gradients in parameter space (no dR / dG product in the second kernel, 131 k instead
-  // of 427 k MACs per row, one small launch behind the weight gradients): from ~10 k packed rows on -- below that the extra launch
-  // (~10 us) costs what the second kernel saves (measured: B = 16 +10 us, B = 64 -22 us, B = 256 -105 us per step)
-  const bool param_space = g_opt_param_space < 0 ? T >= 10240 : g_opt_param_space > 0;
+  const bool param_space = param_space_bwd(c.opt, T);
   Bwd1Args a1; std::memset(&a1, 0, sizeof(a1));
   a1.s[0] = Bwd1Stream{f.W1T, f.Wo1T, f.mask1, f.XH16, f.rstd1, P[CAMO_P_LN1_W], w.dHm1, 2 * H, w.dcomb, 2 * H, f.dH16, f.dU16,
                        Gr[CAMO_P_LN1_W], Gr[CAMO_P_LN1_B]};
@@ -896,15 +881,14 @@ int backward_nodes17(const camo_dims_t& d, const float* const* P, float* const* 
   a1.off = rg_offsets; a1.tile_off = bd.tile_off; a1.tile_desc = bd.tile_desc; a1.inv_nr = bd.inv_nr; a1.row_sample = bd.row_sample;
   a1.B = B; a1.Nk = Nk; a1.rows_rg = T; a1.rg_tiles_max = T / 32 + B; a1.qscale = 1.0f / sqrtf(32.0f); a1.drop = drop;
   a1.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)2 * g_dbg_stamp_blocks * 8 : nullptr;
-  a1.nzero = t_nzero_bwd1; a1.exp = g_opt_exp;
-  for (int i = 0; i < t_nzero_bwd1; ++i) { a1.zero_ptr[i] = t_zero_bwd1_ptr[i]; a1.zero_bytes[i] = t_zero_bwd1_bytes[i]; }
-  t_nzero_bwd1 = 0;
+  a1.nzero = c.nzero_bwd1; a1.exp = c.opt.exp;
+  for (int i = 0; i < c.nzero_bwd1; ++i) { a1.zero_ptr[i] = c.zero_bwd1_ptr[i]; a1.zero_bytes[i] = c.zero_bwd1_bytes[i]; }
   // the RG rows of the first half on 64-row half-blocks (bwd_wide2.hip) from 16 384 packed rows (training step, ms without / with:
   // B = 24 0.209 / 0.217, B = 32 0.2395 / 0.237, B = 48 0.307 / 0.301, B = 64 0.355 / 0.349, B = 128 0.632 / 0.615, B = 256 1.007 / 0.944,
   // B = 1024 3.215 / 2.815) -- behind either forward: the saved set is the same
-  const bool bwd1w = g_opt_wide2_bwd != 0 && (g_opt_wide2_bwd > 0 || (g_opt_fused_rt < 0 && T >= 16384));
-  if (bwd1w) CK(launch_wide2_bwd1(a1, g_opt_fused_variant, st), "fused backward, first half (64-row half-blocks)");
-  else       CK(launch_fused_bwd1(a1, g_opt_fused_variant, st), "fused backward, first half");
+  const bool bwd1w = c.opt.wide2_bwd != 0 && (c.opt.wide2_bwd > 0 || (c.opt.fused_rt < 0 && T >= 16384));
+  if (bwd1w) CK(launch_wide2_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half (64-row half-blocks)");
+  else       CK(launch_fused_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half");
   Bwd2Args a2; std::memset(&a2, 0, sizeof(a2));
   a2.Q2_16 = f.Q2_16; a2.dO2_16 = f.dO2_16; a2.lse2 = f.lse2; a2.delta2 = f.delta2; a2.KV2_16 = f.KV2_16; a2.dQKV16 = f.dQKV16;
   a2.dU16 = f.dU16; a2.WcRgT = f.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
@@ -915,11 +899,11 @@ int backward_nodes17(const camo_dims_t& d, const float* const* P, float* const* 
   a2.param_space = param_space ? 1 : 0;
   a2.split_finish = (param_space && bwd1w) ? 1 : 0;        // (by the size rule of the wide first half: the extra launch costs ~2 us)
   // (wide2_bwd == 2: developer A/B, bwd2p_kernel + bwd2_finish_kernel behind the wide first half)
-  if (a2.split_finish && g_opt_wide2_bwd != 2) CK(launch_wide2_bwd2(a2, st), "fused backward, second half (64-row blocks)");
-  else CK(launch_fused_bwd2(a2, g_opt_fused_variant, st), "fused backward, second half");
+  if (a2.split_finish && c.opt.wide2_bwd != 2) CK(launch_wide2_bwd2(a2, st), "fused backward, second half (64-row blocks)");
+  else CK(launch_fused_bwd2(a2, c.opt.fused_variant, st), "fused backward, second half");
   // every node-level weight gradient: dW += dy^T . x over the rows of a stream (bf16 operands the fused kernels wrote)
   if (!param_space) {
-    GB16 g(drop, st);
+    GB16 g(drop, c.opt, st);
     g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
     g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
     g.tn(f.dQKV16, 3 * H, f.R16, H, Gr[CAMO_P_A1_IN_W], H, Gr[CAMO_P_A1_IN_B], H, H, T);
@@ -940,7 +924,7 @@ int backward_nodes17(const camo_dims_t& d, const float* const* P, float* const* 
   // -- 131 k MACs per row (M, dU^T x) instead of 427 k (dR, dQKV^T R, dR^T x), and one small fp32 launch behind them (misc.hip, unfold_kernel).
   float* const Mrg = w.parM; float* const Mkg = Mrg + (size_t)3 * H * D;
   float* const dbrg = Mkg + (size_t)3 * H * D; float* const dbkg = dbrg + 3 * H;
-  GB16 g(drop, st);
+  GB16 g(drop, c.opt, st);
   g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
   g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
   g.tn(f.dQKV16, 3 * H, f.X16, D, Mrg, D, dbrg, H, D, T).bias_grad2 = Gr[CAMO_P_A1_IN_B];
@@ -970,7 +954,6 @@ int camo_abi_version(void) { return CAMO_ABI_VERSION; }
 const char* camo_last_error(void) { return g_err.c_str(); }
 
 size_t camo_workspace_bytes(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk) {
-  OptScope opt_scope(dims);
   if (check_dims(dims, B, T, Nk)) return 0;
   return carve(*dims, B, T, Nk, nullptr).bytes;
 }
@@ -1002,13 +985,12 @@ int camo_gather_batch(const float* rg_all, const int64_t* sample_offsets, const 
   return 0;
 }
 
-static int forward_impl(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
+static int forward_impl(Call& c, const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
                         const void* desc,
                         const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
                         size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
                         uint64_t seed, int32_t precision, int32_t flags, void* stream, const FusedLoss* fl,
                         const FusedLoss* fl17 = nullptr /* given: loss + the whole tail backward ride in the one-launch tail */) {
-  t_tailw_bwd_planes = false;
   if (int e = check_dims(dims, B, T, Nk)) return e;
   if (!params || !rg || !rg_offsets || !desc || !kg || !workspace || !outs)
     return fail(CAMO_E_ARG, "null pointer argument");
@@ -1018,7 +1000,7 @@ static int forward_impl(const camo_dims_t* dims, const float* const* params, con
   if (precision != CAMO_PREC_F32 && precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
   const camo_dims_t& d = *dims;
   Ws w = carve(d, B, T, Nk, workspace);
-  bind_shadows(w);
+  bind_shadows(c, w);
   if (workspace_bytes < w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DropCfg drop = make_drop(training, d.dropout, seed);
@@ -1029,9 +1011,9 @@ static int forward_impl(const camo_dims_t* dims, const float* const* params, con
   // one clear of everything this step accumulates into with atomics (means now, dfused/dKV in backward);
   // the bf16 schedule's prep launch does it along with its casts
   // calls at the reference configuration that do not ask for attention maps take the fused row-tile schedule
-  const bool use17 = !attn_rg2kg && !attn_kg2rg && !(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(d, P, precision, Nk, max_nr);
-  const bool save17 = !(flags & CAMO_FWD_INFERENCE) || g_opt_fused_save != 0;
-  const bool use16 = !use17 && sched16_ok(d, P, precision, T, Nk, max_nr);
+  const bool use17 = !attn_rg2kg && !attn_kg2rg && !(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(c.opt, d, P, precision, Nk, max_nr);
+  const bool save17 = !(flags & CAMO_FWD_INFERENCE) || c.opt.fused_save != 0;
+  const bool use16 = !use17 && sched16_ok(c.opt, d, P, precision, T, Nk, max_nr);
   if (!use16 && !use17) CK((int)hipMemsetAsync(w.zero_base, 0, w.zero_bytes, st), "memset zero block");
 
   if (d.fusion_type == CAMO_FUSION_LATE) {
@@ -1054,15 +1036,15 @@ static int forward_impl(const camo_dims_t* dims, const float* const* params, con
   if (!P[CAMO_P_KG_PROJ_W] && Dk != H) return fail(CAMO_E_ARG, "kg_proj weight missing but kg_dim != hidden_dim");
   const size_t HH2 = (size_t)H * H;
   if (use17) {
-    const bool tailw = (flags & CAMO_FWD_INFERENCE) && !fl && !fl17 && tailw_taken(d, B, T, max_nr, save17, drop.p > 0.f);
+    const bool tailw = (flags & CAMO_FWD_INFERENCE) && !fl && !fl17 && tailw_taken(c.opt, d, B, T, max_nr, save17, drop.p > 0.f);
     // training calls on the wide front half with more than 64 samples: the tail's FORWARD as the one two-plane launch (with fp32
     // copies of what the backward launches read) instead of four fp32 GEMM launches (B = 256: 4 x 27 us -> 34 us); the loss launch
     // and the backward launches follow as before
     // (its weight planes are built by extra blocks of the wide front launch: the same predicate as forward_nodes17's)
-    const bool tailw_train = !tailw && fl && !fl17 && save17 && B > 64 && g_opt_tailw != 0 && T >= 4 * 32 * 224 && wide_train_front_rt(T, max_nr, save17) != 0 &&
+    const bool tailw_train = !tailw && fl && !fl17 && save17 && B > 64 && c.opt.tailw != 0 && T >= 4 * 32 * 224 && wide_train_front_rt(c.opt, T, max_nr, save17) != 0 &&
                              tail_wide_ok(B, d.num_classes) && heads_loss_ok(B, d.num_classes);
-    if (int e = forward_nodes17(d, P, rg, rg_offsets, bd, kg, B, T, Nk, max_nr, w, drop, save17, st, tailw_train ? 2 : (tailw ? 1 : 0))) return e;
-    t_tailw_bwd_planes = tailw_train;        // (the backward half of this training call may take the two-plane launch too)
+    if (int e = forward_nodes17(c, d, P, rg, rg_offsets, bd, kg, B, T, Nk, max_nr, w, drop, save17, st, tailw_train ? 2 : (tailw ? 1 : 0))) return e;
+    c.tailw_bwd_planes = tailw_train;        // (the backward half of this training call may take the two-plane launch too)
     if (tailw || tailw_train) {
       TailWideArgs ta; std::memset(&ta, 0, sizeof(ta));
       ta.Ymean = w.Ymean; ta.H1mean = w.H1mean; ta.Y2mean = w.Y2mean; ta.H2mean = w.H2mean;
@@ -1075,10 +1057,10 @@ static int forward_impl(const camo_dims_t* dims, const float* const* params, con
       CK(launch_tail_wide(ta, st), "per-sample tail (wide, one launch)");
       if (!tailw_train) return 0;
       // (the output layers' weight gradients ride in the tail's weight-gradient launch of the backward half, when that half takes it)
-      return heads_forward(d, P + CAMO_P_HEADS, w, B, H, outs, gt, fl, /*hidden_done=*/true, /*defer_out_grads=*/g_opt_tailw_bwd != 0);
+      return heads_forward(d, P + CAMO_P_HEADS, w, B, H, outs, gt, fl, /*hidden_done=*/true, /*defer_out_grads=*/c.opt.tailw_bwd != 0);
     }
   } else if (use16) {
-    if (int e = forward_nodes16(d, P, rg, rg_offsets, row_sample, inv_nr, kg, B, T, Nk, max_nr, w, attn_rg2kg, attn_kg2rg, drop, st)) return e;
+    if (int e = forward_nodes16(c, d, P, rg, rg_offsets, row_sample, inv_nr, kg, B, T, Nk, max_nr, w, attn_rg2kg, attn_kg2rg, drop, st)) return e;
   } else {
   if (P[CAMO_P_KG_PROJ_W]) { g.nt(kg, Dk, P[CAMO_P_KG_PROJ_W], Dk, P[CAMO_P_KG_PROJ_B], w.G, H, TK, H, Dk); G = w.G; }
   if (P[CAMO_P_RG_PROJ_W]) { g.nt(rg, D, P[CAMO_P_RG_PROJ_W], D, P[CAMO_P_RG_PROJ_B], w.R, H, T, H, D); R = w.R; }
@@ -1107,8 +1089,8 @@ static int forward_impl(const camo_dims_t* dims, const float* const* params, con
   CK(g.run(), "ffn layer 0");
   }
   // per-sample means of Y and H1d, then the second FFN layer on the means (mean-pool linearity)
-  if (use17 && g_opt_tail17 != 0 && (fl17 || ((flags & CAMO_FWD_INFERENCE) && !fl)) && tail_fused_ok(B, d.num_classes))
-    return tail17(d, P, fl17 ? fl17->head_grads - CAMO_P_HEADS : nullptr, w, B, outs, fl17, drop, st);
+  if (use17 && (fl17 || ((flags & CAMO_FWD_INFERENCE) && !fl)) && tail17_taken(c.opt, d, B))
+    return tail17(c, d, P, fl17 ? fl17->head_grads - CAMO_P_HEADS : nullptr, w, B, outs, fl17, drop, st);
   if (use16 || use17) {
     // accumulated by the kernels that produce the pooled tensors
   } else {
@@ -1132,9 +1114,12 @@ int camo_forward(const camo_dims_t* dims, const float* const* params, const floa
                  const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
                  size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
                  uint64_t seed, int32_t precision, int32_t flags, void* stream) {
-  OptScope opt_scope(dims);
-  return forward_impl(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                      attn_rg2kg, attn_kg2rg, training, seed, precision, flags, stream, nullptr);
+  Call c(dims);
+  c.tail_skip = c.opt.tail_skip_arrival;
+  const int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+                              attn_rg2kg, attn_kg2rg, training, seed, precision, flags, stream, nullptr);
+  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
+  return rc;
 }
 
 int camo_forward_cached(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
@@ -1142,34 +1127,34 @@ int camo_forward_cached(const camo_dims_t* dims, const float* const* params, con
                         size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
                         uint64_t seed, int32_t precision, int32_t flags, void* shadows, int32_t shadows_valid, int32_t* shadows_state,
                         void* stream) {
-  OptScope opt_scope(dims);
+  Call c(dims);
   if (shadows_state) *shadows_state = 0;
   if (shadows_valid && !shadows) return fail(CAMO_E_ARG, "shadows_valid without a shadow buffer");
   // A call that saves for camo_backward would leave the backward's transposed shadows in the caller's buffer, where camo_backward
-  // (which takes no shadow argument) cannot find them, and its deferred clears in thread-local state that any other forward call
-  // drops: the training pair is camo_forward_loss_backward, which owns both halves.
+  // (which takes no shadow argument) cannot find them, and the clears it defers to the first backward kernel would end with this
+  // call: the training pair is camo_forward_loss_backward, which owns both halves.
   if (shadows && !(flags & CAMO_FWD_INFERENCE))
     return fail(CAMO_E_UNSUPPORTED, "camo_forward_cached with a shadow buffer serves inference calls only (flags must contain CAMO_FWD_INFERENCE)");
   if (shadows && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
-  t_shadows = shadows; t_shadows_valid = shadows && shadows_valid != 0; t_fold_missing = shadows && shadows_valid == 2; t_shadows_state = 0;
-  const int rc = forward_impl(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+  c.shadows = shadows; c.shadows_valid = shadows && shadows_valid != 0; c.fold_missing = shadows && shadows_valid == 2;
+  c.tail_skip = c.opt.tail_skip_arrival;
+  const int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
                               attn_rg2kg, attn_kg2rg, training, seed, precision, flags, stream, nullptr);
-  t_shadows = nullptr; t_shadows_valid = false; t_fold_missing = false;
-  if (rc == 0 && shadows_state) *shadows_state = t_shadows_state;
+  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
+  if (rc == 0 && shadows_state) *shadows_state = c.shadows_state;
   return rc;
 }
 
 // camo_forward_loss_backward's optional event: recorded on the stream as soon as the gradients of the per-sample tail (pooled
 // FFN layers, fusion layer, heads: parameters CAMO_P_F2_W3 .. end of the table, and CAMO_P_F1_W3/B3) are final, so that a
 // data-parallel caller can start reducing that part of the flat buffer while the node-level backward runs.
-static thread_local hipEvent_t t_tail_event = nullptr;
-static int record_tail_event(hipStream_t st) {
-  if (!t_tail_event) return 0;
-  const hipEvent_t ev = t_tail_event; t_tail_event = nullptr;
+static int record_tail_event(Call& c, hipStream_t st) {      // (once per call: the first point that reaches it)
+  if (!c.tail_event) return 0;
+  const hipEvent_t ev = c.tail_event; c.tail_event = nullptr;
   return (int)hipEventRecord(ev, st);
 }
 
-static int backward_impl(const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
+static int backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                          const int32_t* rg_offsets, const void* desc, const float* kg, int32_t B,
                          int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes, const float* outs,
                          const float* d_outs, int32_t d_outs_pre_activation, int32_t training, uint64_t seed, int32_t precision,
@@ -1183,7 +1168,7 @@ static int backward_impl(const camo_dims_t* dims, const float* const* params, fl
   if (precision != CAMO_PREC_F32 && precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
   const camo_dims_t& d = *dims;
   Ws w = carve(d, B, T, Nk, workspace);
-  bind_shadows(w);
+  bind_shadows(c, w);
   if (workspace_bytes < w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DropCfg drop = make_drop(training, d.dropout, seed);
@@ -1210,8 +1195,7 @@ static int backward_impl(const camo_dims_t* dims, const float* const* params, fl
   const bool has_rgp = P[CAMO_P_RG_PROJ_W] != nullptr, has_kgp = P[CAMO_P_KG_PROJ_W] != nullptr;
   const float* R = has_rgp ? w.R : rg;
   const float* G = has_kgp ? w.G : kg;
-  const bool tailw_bwd = t_tailw_bwd_planes && heads_out_done && g_opt_tailw_bwd != 0;
-  t_tailw_bwd_planes = false;
+  const bool tailw_bwd = c.tailw_bwd_planes && heads_out_done && c.opt.tailw_bwd != 0;
   if (tailw_bwd) {
     // the tail's input-gradient chain as ONE two-plane launch (tail_wide.h) + ONE launch for its weight gradients, instead of four
     // fp32 GEMM launches that each pair an input gradient with a weight gradient (B = 256: 108 us)
@@ -1251,11 +1235,11 @@ static int backward_impl(const camo_dims_t* dims, const float* const* params, fl
   gt.tn(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], 2 * H, Gr[CAMO_P_F2_B3], H, 2 * H, B);
   CK(gt.run(), "ffn layer 3 bwd (pooled)");
   }
-  CK(record_tail_event(st), "tail event");
-  if (!(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(d, P, precision, Nk, max_nr))
-    return backward_nodes17(d, P, Gr, rg_offsets, bd, B, T, Nk, w, drop, st);
-  if (sched16_ok(d, P, precision, T, Nk, max_nr))
-    return backward_nodes16(d, P, Gr, rg_offsets, row_sample, inv_nr, B, T, Nk, max_nr, w, drop, st);
+  CK(record_tail_event(c, st), "tail event");
+  if (!(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(c.opt, d, P, precision, Nk, max_nr))
+    return backward_nodes17(c, d, P, Gr, rg_offsets, bd, B, T, Nk, w, drop, st);
+  if (sched16_ok(c.opt, d, P, precision, T, Nk, max_nr))
+    return backward_nodes16(c, d, P, Gr, rg_offsets, row_sample, inv_nr, B, T, Nk, max_nr, w, drop, st);
   {
     BcastSeg s0{w.H1, w.dHm1, 2 * H, row_sample, inv_nr, 0, w.dH1, T};
     BcastSeg s1{w.H2, w.dHm2, 2 * H, nullptr, nullptr, Nk, w.dH2, TK};
@@ -1303,12 +1287,12 @@ int camo_backward(const camo_dims_t* dims, const float* const* params, float* co
                   int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes, const float* outs,
                   const float* d_outs, int32_t d_outs_pre_activation, int32_t training, uint64_t seed, int32_t precision,
                   int32_t flags, void* stream) {
-  OptScope opt_scope(dims);
-  return backward_impl(dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+  Call c(dims);
+  return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
                        d_outs, d_outs_pre_activation, training, seed, precision, flags, stream, false);
 }
 
-static int forward_loss_backward_impl(const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
+static int forward_loss_backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                                const int32_t* rg_offsets, const void* batch_desc, const float* kg,
                                int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes,
                                const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
@@ -1320,58 +1304,57 @@ int camo_forward_loss_backward(const camo_dims_t* dims, const float* const* para
                                const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
                                int32_t training, uint64_t seed, int32_t precision, void* tail_event, void* shadows,
                                int32_t shadows_valid, void* stream) {
-  OptScope opt_scope(dims);
+  Call c(dims);
   if (!dims || !grads || !y || !e || !s || !outs || !loss_terms) return fail(CAMO_E_ARG, "null pointer argument");
   if (shadows_valid && !shadows) return fail(CAMO_E_ARG, "shadows_valid without a shadow buffer");
   // external shadows are used by the fused schedule only; whether the call takes it is known from its arguments
-  const bool ext = shadows && params && !check_dims(dims, B, T, Nk) && fused17_ok(*dims, params, precision, Nk, max_nr);
+  const bool ext = shadows && params && !check_dims(dims, B, T, Nk) && fused17_ok(c.opt, *dims, params, precision, Nk, max_nr);
   // (a call that takes another schedule -- Nk > 16, a 5000-node sample, ... -- builds what it needs in its workspace and leaves the
   // external shadows alone: the promise is simply not used)
   if (ext && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
-  t_shadows = ext ? shadows : nullptr; t_shadows_valid = ext && shadows_valid != 0;
-  t_tail_event = static_cast<hipEvent_t>(tail_event);
-  const int rc = forward_loss_backward_impl(dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace,
+  c.shadows = ext ? shadows : nullptr; c.shadows_valid = ext && shadows_valid != 0;
+  c.tail_event = static_cast<hipEvent_t>(tail_event);
+  c.tail_skip = c.opt.tail_skip_arrival;
+  const int rc = forward_loss_backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace,
                                             workspace_bytes, y, e, s, outs, loss_terms, pred, training, seed, precision, stream);
-  t_shadows = nullptr; t_shadows_valid = false;
-  if (rc == 0) { CK(record_tail_event(static_cast<hipStream_t>(stream)), "tail event"); }   // (schedules without an early point)
-  t_tail_event = nullptr;
+  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
+  if (rc == 0) { CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event"); }   // (schedules without an early point)
   return rc;
 }
 
-static int forward_loss_backward_impl(const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
+static int forward_loss_backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                                const int32_t* rg_offsets, const void* batch_desc, const float* kg,
                                int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes,
                                const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
                                int32_t training, uint64_t seed, int32_t precision, void* stream) {
   const int head0 = dims->fusion_type == CAMO_FUSION_LATE ? CAMO_PL_HEADS : CAMO_P_HEADS;
   const bool fuse = heads_loss_ok(B, dims->num_classes);
-  if (g_opt_tail17 != 0 && params && !check_dims(dims, B, T, Nk) && fused17_ok(*dims, params, precision, Nk, max_nr) &&
-      tail_fused_ok(B, dims->num_classes)) {
+  if (params && !check_dims(dims, B, T, Nk) && fused17_ok(c.opt, *dims, params, precision, Nk, max_nr) && tail17_taken(c.opt, *dims, B)) {
     // fused schedule + one-launch tail: node-level forward, [tail forward + loss + tail backward], node-level backward
     const FusedLoss fl{y, e, s, loss_terms, pred, grads + head0};
-    if (int rc = forward_impl(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+    if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
                               nullptr, nullptr, training, seed, precision, 0, stream, nullptr, &fl)) return rc;
     Ws w = carve(*dims, B, T, Nk, workspace);
-    bind_shadows(w);
+    bind_shadows(c, w);
     const Desc bd = desc_carve(B, T, const_cast<void*>(batch_desc));
-    CK(record_tail_event(static_cast<hipStream_t>(stream)), "tail event");
-    return backward_nodes17(*dims, params, grads, rg_offsets, bd, B, T, Nk, w, make_drop(training, dims->dropout, seed),
+    CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event");
+    return backward_nodes17(c, *dims, params, grads, rg_offsets, bd, B, T, Nk, w, make_drop(training, dims->dropout, seed),
                             static_cast<hipStream_t>(stream));
   }
   if (fuse) {
     const FusedLoss fl{y, e, s, loss_terms, pred, grads + head0};
-    if (int rc = forward_impl(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+    if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
                               nullptr, nullptr, training, seed, precision, 0, stream, &fl)) return rc;
-    return backward_impl(dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
+    return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
                          outs, nullptr, 1, training, seed, precision, 0, stream, true);
   }
   // large batches / many classes: the three steps as separate launches, d(loss)/d(pre-activation) staged in the workspace
-  if (int rc = forward_impl(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
+  if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
                             nullptr, nullptr, training, seed, precision, 0, stream, nullptr)) return rc;
   const Ws w = carve(*dims, B, T, Nk, workspace);
   CK(launch_loss(outs, reinterpret_cast<const long long*>(y), e, s, B, dims->num_classes, loss_terms, nullptr, w.dlog, pred,
                  static_cast<hipStream_t>(stream)), "loss");
-  return backward_impl(dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
+  return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
                        outs, w.dlog, 1, training, seed, precision, 0, stream, false);
 }
 
@@ -1391,7 +1374,6 @@ int camo_grad_sumsq(const float* g, size_t n, float* sumsq, void* stream) {
 }
 
 size_t camo_shadow_bytes(const camo_dims_t* dims) {
-  OptScope opt_scope(dims);
   if (!dims || !fused17_dims(*dims)) return 0;
   return shadow_carve(nullptr).bytes;
 }
@@ -1399,7 +1381,6 @@ size_t camo_shadow_bytes(const camo_dims_t* dims) {
 int camo_clip_adamw_shadows(const camo_dims_t* dims, const float* const* params, float* p, float* g, float* m, float* v, size_t n,
                             float* sumsq, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                             int32_t step, int32_t zero_grads, void* shadows, void* stream) {
-  OptScope opt_scope(dims);
   if (!dims || !params || !p || !g || !m || !v || !sumsq || !shadows || n == 0) return fail(CAMO_E_ARG, "null pointer or empty buffer");
   if (step < 1) return fail(CAMO_E_ARG, "step is 1-based");
   if (!fused17_dims(*dims)) return fail(CAMO_E_UNSUPPORTED, "weight shadows exist for the fused schedule's configuration only");
@@ -1480,7 +1461,7 @@ int camo_debug_gemm16(const void* A16, int32_t lda, const void* B16, int32_t ldb
   p.A = static_cast<const unsigned short*>(A16); p.lda = lda; p.B = static_cast<const unsigned short*>(B16); p.ldb = ldb;
   p.C = C; p.ldc = ldc; p.C16 = static_cast<unsigned short*>(C16); p.ldc16 = ldc16;
   p.bias = bias; p.res = res; p.ldr = ldr; p.bias_grad = bias_grad; p.M = M; p.N = N; p.K = K; p.flags = flags; p.aux_scale = 1.f;
-  CK(launch_gemm16_batch(gb, static_cast<hipStream_t>(stream)), "debug gemm16");
+  CK(launch_gemm16_batch(gb, Gemm16Knobs{}, static_cast<hipStream_t>(stream)), "debug gemm16");
   return 0;
 }
 
@@ -1544,7 +1525,6 @@ int camo_prof_end(double* gemm_ms, int32_t* gemm_launches, double* gemm_flops) {
 }
 
 int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk, const char* name) {
-  OptScope opt_scope(dims);
   if (check_dims(dims, B, T, Nk) || !name) return -1;
   char* base = reinterpret_cast<char*>(4096);
   const Ws w = carve(*dims, B, T, Nk, base);

@@ -59,9 +59,13 @@ struct Gemm16Batch {
   int n_heavy;       // (filled by the launcher) > 0: tiles [0, n_heavy) are split-K blocks with long K loops, the rest short ones
 };
 
+// Developer A/Bs of the launcher (the caller's camo_options_t tn_big, tn_balance, tn_kcap, tn_exp); the defaults are the product's.
+struct Gemm16Knobs {
+  int tn_big = -1;       // -1 by size, 0 never, 1 always (weight-gradient-only launches)
+  int balance = 1;       // 0 = plain contiguous XCD remap
+  int tn_kcap = 0;       // > 0 pins the split-K depth (64-row tiles per block) of weight-gradient problems
+  int exp = 0;           // -> Gemm16Batch::exp
+};
+
 // Returns hipError_t as int; hipErrorInvalidValue for an unsupported problem.
-extern thread_local int g_gemm16_exp;
-extern thread_local int g_gemm16_tn_big;          // developer A/B: -1 by size, 0 never, 1 always (weight-gradient-only launches)
-extern thread_local int g_gemm16_balance;         // developer A/B: 0 = plain contiguous XCD remap
-extern thread_local int g_gemm16_tn_kcap;         // developer A/B: > 0 pins the split-K depth (64-row tiles per block) of weight-gradient problems
-int launch_gemm16_batch(Gemm16Batch& gb, hipStream_t stream);
+int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stream);

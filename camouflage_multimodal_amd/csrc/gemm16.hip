@@ -751,13 +751,11 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-thread_local int g_gemm16_exp = 0;
-thread_local int g_gemm16_tn_big = -1;             // developer A/B ("tn_big"): -1 by size, 0 never, 1 whenever the launch is weight gradients only
-static int launch_tnbig(Gemm16Batch& gb, hipStream_t stream) {
+static int launch_tnbig(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stream) {
   int total = 0;
   static const int kcaps[] = {512, 384, 256, 192, 128, 96, 64, 48, 32, 24, 16, 12, 8, 6, 4};
   for (int ci = 0;; ++ci) {
-    const int kcap = g_gemm16_tn_kcap > 0 ? g_gemm16_tn_kcap : kcaps[ci];
+    const int kcap = kn.tn_kcap > 0 ? kn.tn_kcap : kcaps[ci];
     total = 0;
     for (int i = 0; i < gb.n; ++i) {
       Gemm16Prob& p = gb.p[i];
@@ -773,9 +771,9 @@ static int launch_tnbig(Gemm16Batch& gb, hipStream_t stream) {
       p.tile_begin = total;
       total += tiles * p.ksplit;
     }
-    if (g_gemm16_tn_kcap > 0 || total >= 224 || kcap <= 4) break;         // ~ one block per CU
+    if (kn.tn_kcap > 0 || total >= 224 || kcap <= 4) break;         // ~ one block per CU
   }
-  gb.n_heavy = 0; gb.exp = g_gemm16_exp;
+  gb.n_heavy = 0; gb.exp = kn.exp;
   static const bool attr_ok = [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_tnbig_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GBUF_BYTES);
     return true;
@@ -790,9 +788,7 @@ static int launch_tnbig(Gemm16Batch& gb, hipStream_t stream) {
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
-thread_local int g_gemm16_balance = 1;             // developer A/B ("tn_balance")
-thread_local int g_gemm16_tn_kcap = 0;             // developer A/B (camo_debug_set_option "tn_kcap"): > 0 pins the split-K depth
-int launch_gemm16_batch(Gemm16Batch& gb, hipStream_t stream) {
+int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stream) {
   if (gb.n <= 0) return 0;
   if (gb.n > GEMM16_MAXP) return (int)hipErrorInvalidValue;
   // Split-K depth of the weight-gradient problems, in 64-row tiles per block: the longest of a short ladder that still gives
@@ -808,13 +804,13 @@ int launch_gemm16_batch(Gemm16Batch& gb, hipStream_t stream) {
       all_tn = all_tn && (p.flags & GF_A_KMAJOR) && (p.flags & GF_B_KMAJOR) && !(p.flags & GF_A_VIRT) && !p.ln_mode && (p.M % 8) == 0 && (p.N % 8) == 0;
       kmax = p.K > kmax ? p.K : kmax;
     }
-    const bool big = g_gemm16_tn_big < 0 ? kmax >= 40000 : g_gemm16_tn_big > 0;    // (measured: B = 64 [27 k rows] +8 %, B = 128 [55 k] -7 %, B = 256 [125 k] -15 %)
-    if (all_tn && big) return launch_tnbig(gb, stream);
+    const bool big = kn.tn_big < 0 ? kmax >= 40000 : kn.tn_big > 0;    // (measured: B = 64 [27 k rows] +8 %, B = 128 [55 k] -7 %, B = 256 [125 k] -15 %)
+    if (all_tn && big) return launch_tnbig(gb, kn, stream);
   }
   int total = 0, kcap_used = 0;
   static const int kcaps[] = {512, 384, 256, 192, 128, 96, 64, 48, 32, 24, 16, 8};
   for (int ci = 0;; ++ci) {
-    const int kcap = g_gemm16_tn_kcap > 0 ? g_gemm16_tn_kcap : kcaps[ci];
+    const int kcap = kn.tn_kcap > 0 ? kn.tn_kcap : kcaps[ci];
     total = 0; kcap_used = kcap;
     for (int i = 0; i < gb.n; ++i) {
       Gemm16Prob& p = gb.p[i];
@@ -856,12 +852,12 @@ int launch_gemm16_batch(Gemm16Batch& gb, hipStream_t stream) {
       p.tile_begin = total;
       total += tiles * p.ksplit;
     }
-    if (g_gemm16_tn_kcap > 0 || (kcap > 16 ? total >= 440 : total >= 200) || kcap <= KCAP_MIN) break;
+    if (kn.tn_kcap > 0 || (kcap > 16 ? total >= 440 : total >= 200) || kcap <= KCAP_MIN) break;
   }
-  gb.n_heavy = 0; gb.exp = g_gemm16_exp;
+  gb.n_heavy = 0; gb.exp = kn.exp;
   // (measured on the training step: B = 4 -2.8 us, B = 16 +-0, B = 64 +0.7 us -- with long chunks the short blocks no longer
   // matter and the plain runs keep a K slice's tiles together; hence only up to 16-tile chunks)
-  if (g_gemm16_balance && kcap_used <= 16) {                  // a prefix of split-K problems followed by single-slice ones only
+  if (kn.balance && kcap_used <= 16) {                  // a prefix of split-K problems followed by single-slice ones only
     int i = 0;
     while (i < gb.n && (gb.p[i].flags & GF_A_KMAJOR) && gb.p[i].ksplit > 1) ++i;
     const int first_light = i;

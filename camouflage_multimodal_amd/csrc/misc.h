@@ -71,9 +71,10 @@ struct TailFusedArgs {
   float *comb_out, *F1_out, *fused_out, *dhid_out, *dfused_out, *dF1_out;       // [B][512], [B][256], [B][256], [B][512], [B][256], [B][256]
   int B, C, mode; DropCfg drop;
   unsigned long long* stamps;                               // developer timeline (null in product calls)
-  int debug_skip;                                           // (launcher) developer hook: block id + 1 that skips its first arrival
+  int debug_skip;                                           // developer hook (camo_options_t tail_skip_arrival): block id + 1 that skips its
+                                                            // first arrival, so the others' wait times out deterministically -- the only way
+                                                            // to test the give-up path without sharing the GPU.  0 in product calls
 };
-extern thread_local int g_tail_debug_skip;      // (set per call from the caller's camo_options_t: fusion_abi.hip, OptScope)
 int tail_fused_ok(int B, int C);
 int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream);
 int tail_timeouts(unsigned int* out);

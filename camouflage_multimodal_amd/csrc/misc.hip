@@ -1529,10 +1529,6 @@ int launch_heads_loss(const float* hid, const HeadsOut& hp, const long long* y, 
   return (int)hipGetLastError();
 }
 
-// developer hook (camo_debug_set_option "tail_skip_arrival" = block id + 1): that block of the NEXT one-launch tail skips its first
-// arrival, so the others' wait times out deterministically -- the only way to test the give-up path without sharing the GPU
-thread_local int g_tail_debug_skip = 0;
-
 int tail_fused_ok(int B, int C) {
   // every block of the launch waits for the other 63: all of them must be resident at once, one per CU (1024 threads, 148 KB of
   // LDS), so the device (or the partition this process sees) must have at least that many CUs
@@ -1546,10 +1542,8 @@ int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream) {
     return true;
   }();
   (void)attr;
-  TailFusedArgs aa = a;
-  aa.debug_skip = g_tail_debug_skip; g_tail_debug_skip = 0;
   const int prof = gemm_prof_open(stream, 0.0, PROF_TAIL);
-  hipLaunchKernelGGL(tail_fused_kernel, dim3(TG * ((a.B + TF_MAXB - 1) / TF_MAXB)), dim3(TF_THREADS), TF_LDS_FLOATS * 4, stream, aa);
+  hipLaunchKernelGGL(tail_fused_kernel, dim3(TG * ((a.B + TF_MAXB - 1) / TF_MAXB)), dim3(TF_THREADS), TF_LDS_FLOATS * 4, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }

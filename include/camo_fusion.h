@@ -16,10 +16,11 @@
  *    one [T, rg_dim] matrix (variable Nr per sample, no padding), the KG rows
  *    are [B*Nk, kg_dim];
  *  - calls only ENQUEUE work on `stream` (a hipStream_t passed as void*); no
- *    allocation, no synchronisation, and the environment is never read.  The only
- *    process-global state is the two testing/measurement hooks at the end of this
- *    file (camo_options_t, camo_prof_begin/end); without them the calls are
- *    graph-capturable and thread-compatible;
+ *    allocation, no synchronisation, and the environment is never read.  Schedule
+ *    options are per caller (camo_options_t behind camo_dims_t::options).  The only
+ *    process-global state is the two developer / measurement facilities at the end
+ *    of this file (camo_debug_set_stamps, camo_prof_begin/end): while either is on,
+ *    calls are neither graph-capturable nor thread-compatible; otherwise they are both;
  *  - return value: 0 on success, a negative CAMO_E_* code otherwise; no C++
  *    exception crosses the boundary; camo_last_error() gives a thread-local
  *    message for the last failing call.
@@ -67,7 +68,8 @@ enum { CAMO_PREC_F32 = 0,  /* f32-input MFMA: bit-faithful fp32 FMA chains      
  *            camo_debug_ws_offset: R16 G16 Q16 Q2_16 KV16 KV2_16 O16 O2_16 Y16 Y2_16 XH16 XH2_16 rstd1 rstd2 mask1 mask2 lse2 X16
  *            Wqkv_rg W1s Ymean H1mean Y2mean H2mean)
  *   tail_skip_arrival  block id + 1 of the NEXT one-launch tail that skips its first arrival (the give-up path's test); one shot:
- *            the call that consumes it writes 0 back. */
+ *            read by camo_forward, camo_forward_cached and camo_forward_loss_backward, and the call whose one-launch tail took it
+ *            writes 0 back. */
 typedef struct camo_options {
   int32_t sched16, fused, tail17, fused_rt, wide2, fused_one, wide_front_rt, tailw, tailw_bwd, param_space, tn_big, fused_variant,
           back_lead, tn_balance, tn_kcap, tn_exp, exp, fused_save, tail_skip_arrival, wide2_bwd;
@@ -284,14 +286,15 @@ int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int3
 int camo_options_init(camo_options_t* options);
 int camo_options_set(camo_options_t* options, const char* name, int32_t value);
 /* camo_debug_set_stamps: developer timeline of the fused kernels.  buf = device buffer of 2 * blocks_per_kernel * 8 uint64
- * (or NULL to switch it off): wave 0 of every block stores the 100 MHz wall clock at its phase boundaries. */
+ * (or NULL to switch it off): wave 0 of every block stores the 100 MHz wall clock at its phase boundaries.  Process-global:
+ * every later call of every thread writes there until it is switched off. */
 int camo_debug_set_stamps(void* buf, int32_t blocks_per_kernel);
 
 /* Opt-in launch timing for bench.py's roofline leg: between camo_prof_begin and camo_prof_end every
  * launch of the path's kernels (the grouped GEMMs, the fused row-tile kernels, the tail GEMMs, weight shadows) is bracketed
  * by two HIP events recorded on the launch stream.  camo_prof_end synchronises on them and returns
- * the summed kernel time, the number of launches and the FLOPs those launches executed.  This is the
- * one piece of process-global state in the library: single-threaded use, not for production loops. */
+ * the summed kernel time, the number of launches and the FLOPs those launches executed.  Process-global state, like
+ * camo_debug_set_stamps: single-threaded use, not for production loops. */
 int camo_prof_begin(int32_t max_launches);
 int camo_prof_end(double* gemm_ms, int32_t* gemm_launches, double* gemm_flops);
 /* After camo_prof_end: the same three figures per kernel family.  kind: 0 grouped GEMMs (weight gradients in the fused

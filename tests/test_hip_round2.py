@@ -363,6 +363,7 @@ def test_tail_timeout_is_not_applied(kg_real):
     terms, _ = tr.step(rg, nrs, kg, y, e, s)
     torch.cuda.synchronize()
     assert _lib.tail_timeouts() > t0
+    assert m._engine.options.tail_skip_arrival == 0                  # (the step's tail launch took the hook)
     assert torch.isnan(terms).all()
     assert not np.isfinite(t2n(tr.opt.grad_norm())[0])
     assert torch.equal(m._engine.flat_params, before), "a timed-out step changed the parameters"

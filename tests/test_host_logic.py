@@ -353,3 +353,23 @@ def test_schedule_options_are_per_engine_state():
     assert L.camo_options_set(C.byref(o), b"no_such_option", 1) != 0
     with pytest.raises(_lib.CamoError):
         engine.set_option_all("no_such_option", 1)
+
+
+def test_calls_that_launch_no_tail_leave_the_callers_options_alone():
+    """The library reads the caller's options and writes back only the one-shot tail_skip_arrival, once a one-launch tail took it.
+    Size queries, the workspace-offset lookup and a forward refused before any launch leave every field as it was."""
+    import ctypes as C
+    from camouflage_multimodal_amd import _lib
+    L = _lib.lib()
+    o = _lib.CamoOptions()
+    want = {n: v + 2 for n, v in _lib.OPTION_DEFAULTS.items()}
+    want["tail_skip_arrival"] = 6
+    for n, v in want.items():
+        setattr(o, n, v)
+    d = _lib.CamoDims(128, 128, 256, 8, 2, _lib.FUSION_CROSS_ATTENTION, 0.3, C.pointer(o))
+    assert L.camo_workspace_bytes(C.byref(d), 16, 7700, 13) > 0
+    assert L.camo_shadow_bytes(C.byref(d)) > 0
+    assert L.camo_debug_ws_offset(C.byref(d), 16, 7700, 13, b"R16") >= 0
+    assert L.camo_forward(C.byref(d), None, None, None, None, None, 4, 100, 13, 50, None, 0, None, None, None,
+                          0, 0, 0, 0, None) == -1
+    assert {n: getattr(o, n) for n in _lib.OPTION_NAMES} == want
