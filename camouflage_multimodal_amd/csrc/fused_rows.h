@@ -82,6 +82,13 @@ struct Bwd1Stream {
   us16* dH16; us16* dU16;                      // out: [rows][512] FFN pre-activation gradient, [rows][256] LayerNorm input gradient
   float* dgamma; float* dbeta;                 // += (atomics)
 };
+// The one-launch tail's weight gradients (misc.hip, tail_fused_kernel, one group of B <= 16 samples): nothing of this launch waits
+// for them, so they ride as extra blocks at the end of its grid instead of sitting on the tail's dependent chain.  Product p:
+// dW[r][c] += sum_b dy[b][r] x[b][c], db[r] += sum_b dy[b][r] (fp32, b in order, plain stores: every element has one writer), on
+// tiles of 16 rows x 256 columns (rows % 16 == 0, cols % 256 == 0, dW row-major with ld = cols)
+struct TailWgProd { const float* dy; const float* x; float* dW; float* db; int ld_dy, ld_x, rows, cols; int tile_begin; };
+#define TAIL_WG_MAXP 8
+struct TailWgArgs { TailWgProd p[TAIL_WG_MAXP]; int n, B, tiles; };   // n == 0: none (tile_begin, tiles: filled by the launcher)
 struct Bwd1Args {
   Bwd1Stream s[2];                             // 0: RG rows, 1: KG rows
   const us16* Q16; const us16* KV16;           // RG queries (pre-scaled) [T][256]; KG keys|values [B*Nk][512]
@@ -94,6 +101,7 @@ struct Bwd1Args {
   int writer_blocks, writer_first_row;         // (filled by the launcher) dH16 writer blocks and the first row of [RG rows | KG rows] they cover
   // clears for the weight-gradient launch (pad rows of its operands) when no shadow launch did them: one extra block each
   void* zero_ptr[FUSED_BWD1_MAXZ]; unsigned zero_bytes[FUSED_BWD1_MAXZ]; int nzero;
+  TailWgArgs twg;                              // the tail's weight gradients: twg.tiles blocks behind the clearing blocks
 };
 int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only = 0);   // kg_only: the KG rows' blocks alone (launch_wide2_bwd1)
 // the RG rows on 64-row half-blocks (bwd_wide2.hip) + the KG rows through launch_fused_bwd1(kg_only); same arguments, outputs and saved set

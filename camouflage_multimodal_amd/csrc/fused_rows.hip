@@ -704,6 +704,47 @@ constexpr int W_GTAB = 0, W_BUFDU = 1024, W_KS = W_BUFDU + 32 * PR, W_VS = W_KS 
               W_IMGS = W_BUFDO + 32 * PR, W_RED = W_IMGS + 16384, W_LDS = W_RED + 1024;          // 69120 bytes
 static_assert(32 * PR + 16384 == 32 * PT * 4, "the fp32 column-sum tile aliases [bufdO | images]");
 
+// One tile of the tail's weight gradients (TailWgArgs): 16 rows x 256 columns of one product, thread t = column c0 + t, all 16 rows.
+// Every global read (the thread's x column, the tile's dy, the old values) is issued at once; dy is shared through LDS.  Same
+// arithmetic as the tail kernel did in place: old value, then fmaf over the samples in order -- the result is bit-identical.
+__device__ __forceinline__ void tail_wg_tile(const TailWgArgs& g, int tile, float* dys, unsigned long long* stamps) {
+  stamp(stamps, 0);
+  int pi = 0;
+  for (int i = 1; i < g.n; ++i) if (tile >= g.p[i].tile_begin) pi = i;
+  const TailWgProd& P = g.p[pi];
+  const int tid = threadIdx.x, B = g.B, ncb = P.cols >> 8, lt = tile - P.tile_begin, rb = lt / ncb;
+  const int r0 = 16 * rb, c = 256 * (lt - rb * ncb) + tid;
+  float xv[16], acc[16];
+#pragma unroll
+  for (int b = 0; b < 16; ++b) xv[b] = b < B ? P.x[(size_t)b * P.ld_x + c] : 0.f;
+  const float dv = tid < B * 16 ? P.dy[(size_t)(tid >> 4) * P.ld_dy + r0 + (tid & 15)] : 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = P.dW[(size_t)(r0 + r) * P.cols + c];
+  const bool bias = c < 16;                                  // (the tile of column block 0: its first 16 threads take the row biases)
+  float bacc = bias ? P.db[r0 + tid] : 0.f;
+  if (tid < B * 16) dys[tid] = dv;
+  __syncthreads();
+  stamp(stamps, 1);
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    if (b < B) {
+      const float4* d4 = reinterpret_cast<const float4*>(dys + 16 * b);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float4 d = d4[k];
+        acc[4 * k] = fmaf(d.x, xv[b], acc[4 * k]); acc[4 * k + 1] = fmaf(d.y, xv[b], acc[4 * k + 1]);
+        acc[4 * k + 2] = fmaf(d.z, xv[b], acc[4 * k + 2]); acc[4 * k + 3] = fmaf(d.w, xv[b], acc[4 * k + 3]);
+      }
+      if (bias) bacc += dys[16 * b + tid];
+    }
+  }
+  stamp(stamps, 2);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) P.dW[(size_t)(r0 + r) * P.cols + c] = acc[r];
+  if (bias) P.db[r0 + tid] = bacc;
+  stamp(stamps, 3);
+}
+
 template <int DEPTH, bool ROT>
 __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -714,6 +755,10 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
   // blocks (15 us) than RG tiles (18-22 us), which then ended the kernel
   const bool kg = (int)blockIdx.x >= a.rg_tiles_max && (int)blockIdx.x < a.rg_tiles_max + a.B;
   const int rot = ROT ? (int)(blockIdx.x >> 3) : 0;
+  if ((int)blockIdx.x >= a.B + a.rg_tiles_max + a.writer_blocks + a.nzero) {   // the tail's weight gradients (see TailWgArgs)
+    tail_wg_tile(a.twg, (int)blockIdx.x - a.B - a.rg_tiles_max - a.writer_blocks - a.nzero, reinterpret_cast<float*>(smem), a.stamps);
+    return;
+  }
   if ((int)blockIdx.x >= a.B + a.rg_tiles_max + a.writer_blocks) {       // one clearing block per range (see Bwd1Args)
     const int zi = (int)blockIdx.x - a.B - a.rg_tiles_max - a.writer_blocks;
     u32x4* z = static_cast<u32x4*>(a.zero_ptr[zi]);
@@ -1533,9 +1578,19 @@ int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only)
   if (a.nzero < 0 || a.nzero > FUSED_BWD1_MAXZ) return (int)hipErrorInvalidValue;
   for (int i = 0; i < a.nzero; ++i)
     if (!a.zero_ptr[i] || !al16(a.zero_ptr[i]) || (a.zero_bytes[i] & 15)) return (int)hipErrorInvalidValue;
+  TailWgArgs& t = a.twg;
+  if (t.n < 0 || t.n > TAIL_WG_MAXP || (t.n && (t.B < 1 || t.B > 16))) return (int)hipErrorInvalidValue;
+  t.tiles = 0;
+  for (int i = 0; i < t.n; ++i) {
+    TailWgProd& p = t.p[i];
+    if (!p.dy || !p.x || !p.dW || !p.db || p.rows < 16 || (p.rows & 15) || p.cols < 256 || (p.cols & 255) || p.ld_dy < p.rows || p.ld_x < p.cols)
+      return (int)hipErrorInvalidValue;
+    p.tile_begin = t.tiles;
+    t.tiles += (p.rows / 16) * (p.cols / 256);
+  }
   Bwd1Args k = a;                                                    // (the kernel decodes a block's role from rg_tiles_max)
   if (kg_only) { k.rg_tiles_max = 0; k.stamps = nullptr; }           // (the timeline region belongs to the RG rows' launch then)
-  const dim3 grid(k.B + k.rg_tiles_max + k.writer_blocks + k.nzero);
+  const dim3 grid(k.B + k.rg_tiles_max + k.writer_blocks + k.nzero + k.twg.tiles);
   // executed FLOPs per row: dY (512 -> 256), dO (256 -> 256); RG rows: the RG->KG attention backward (5 products of Nk x 256)
   const double rows = (kg_only ? 0.0 : (double)a.rows_rg) + (double)a.B * a.Nk;
   const int prof = gemm_prof_open(stream, 2.0 * rows * (512.0 * 256.0 + 256.0 * 256.0) + (kg_only ? 0.0 : 10.0 * (double)a.rows_rg * a.Nk * 256.0), PROF_BWD1);

@@ -55,6 +55,7 @@ struct Call {
   void* zero_bwd1_ptr[FUSED_BWD1_MAXZ]; unsigned zero_bwd1_bytes[FUSED_BWD1_MAXZ]; int nzero_bwd1 = 0;
   bool tailw_bwd_planes = false;      // the training forward built the two-plane tail's transposed planes (this call's workspace)
   hipEvent_t tail_event = nullptr;    // camo_forward_loss_backward's optional event (record_tail_event)
+  bool tail_wg_bwd1 = false;          // the one-launch tail (one group, training) left its eight big weight gradients to backward_nodes17's first launch
   int tail_skip = 0;                  // the caller's one-shot tail_skip_arrival: read by the entry points that can launch the one-launch tail,
   bool tail_skip_taken = false;       // which write 0 back to the caller's options once that launch took it
   explicit Call(const camo_dims_t* d) : opt(*(d && d->options ? d->options : &k_default_options)) {}
@@ -737,8 +738,17 @@ int forward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, const 
 }
 
 // ---- node-level backward of the fused row-tile schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
-int backward_nodes17(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
+int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
                      int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st);
+
+// camo_forward_loss_backward's optional event: recorded on the stream as soon as the gradients of the per-sample tail (pooled
+// FFN layers, fusion layer, heads: parameters CAMO_P_F2_W3 .. end of the table, and CAMO_P_F1_W3/B3) are final, so that a
+// data-parallel caller can start reducing that part of the flat buffer while the node-level backward runs.
+int record_tail_event(Call& c, hipStream_t st) {      // (once per call: the first point that reaches it)
+  if (!c.tail_event) return 0;
+  const hipEvent_t ev = c.tail_event; c.tail_event = nullptr;
+  return (int)hipEventRecord(ev, st);
+}
 
 // ---- node-level backward of the bf16 schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
 int backward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets,
@@ -846,10 +856,16 @@ int tail17(Call& c, const camo_dims_t& d, const float* const* P, float* const* G
   a.B = B; a.C = d.num_classes; a.mode = fl ? 1 : 0; a.drop = drop;
   a.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)4 * g_dbg_stamp_blocks * 8 : nullptr;
   a.debug_skip = c.tail_skip;
+  // training: the kernel leaves copies of the operands of the eight big weight gradients (the heads' hidden layers, fusion layers 3
+  // and 0, the pooled FFN layers), and these gradients to the launches behind it: nothing on the chain to the node-level backward
+  // waits for them
   const bool groups = fl && B > 16;
-  if (groups) { a.comb_out = w.comb; a.F1_out = w.F1; a.fused_out = w.fused; a.dhid_out = w.dhid; a.dfused_out = w.dfused; a.dF1_out = w.dF1; }
+  if (fl) { a.comb_out = w.comb; a.F1_out = w.F1; a.fused_out = w.fused; a.dhid_out = w.dhid; a.dfused_out = w.dfused; a.dF1_out = w.dF1; }
   CK(launch_tail_fused(a, st), "per-sample tail (one launch)");
   c.tail_skip_taken = a.debug_skip != 0;
+  // one group: extra blocks at the end of the node-level backward's first launch, which always follows (forward_loss_backward_impl
+  // -> backward_nodes17), run them on CUs that its row tiles leave idle (a launch of their own would cost ~5 us of floor)
+  c.tail_wg_bwd1 = fl && !groups;
   if (groups) {
     // more than one group of 16 samples: the big weight gradients of the tail are sums over every group -- one batched launch
     // (contraction over the B samples), operands = the copies the tail kernel left in the workspace
@@ -865,7 +881,7 @@ int tail17(Call& c, const camo_dims_t& d, const float* const* P, float* const* G
   return 0;
 }
 
-int backward_nodes17(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
+int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
                      int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st) {
   const int H = 256, D = 128, TK = B * Nk;
   const size_t HH = (size_t)H * H;
@@ -883,12 +899,28 @@ int backward_nodes17(const Call& c, const camo_dims_t& d, const float* const* P,
   a1.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)2 * g_dbg_stamp_blocks * 8 : nullptr;
   a1.nzero = c.nzero_bwd1; a1.exp = c.opt.exp;
   for (int i = 0; i < c.nzero_bwd1; ++i) { a1.zero_ptr[i] = c.zero_bwd1_ptr[i]; a1.zero_bytes[i] = c.zero_bwd1_bytes[i]; }
+  if (c.tail_wg_bwd1) {
+    // the one-launch tail's eight big weight gradients (tail17), from the operand copies it left: dW += dy^T x over the B samples
+    TailWgArgs& t = a1.twg;
+    auto prod = [&](const float* dy, int ld_dy, const float* x, int ld_x, float* dW, float* db, int rows, int cols) {
+      t.p[t.n++] = TailWgProd{dy, x, dW, db, ld_dy, ld_x, rows, cols, 0};
+    };
+    const int Fh = H / 2;
+    for (int x = 0; x < 4; ++x) prod(w.dhid + x * Fh, 4 * Fh, w.fused, H, Gr[CAMO_P_HEADS + 4 * x], Gr[CAMO_P_HEADS + 4 * x + 1], Fh, H);
+    prod(w.dfused, H, w.F1, H, Gr[CAMO_P_FU_W3], Gr[CAMO_P_FU_B3], H, H);
+    prod(w.dF1, H, w.comb, 2 * H, Gr[CAMO_P_FU_W0], Gr[CAMO_P_FU_B0], H, 2 * H);
+    prod(w.dcomb, 2 * H, w.H1mean, 2 * H, Gr[CAMO_P_F1_W3], Gr[CAMO_P_F1_B3], H, 2 * H);
+    prod(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], Gr[CAMO_P_F2_B3], H, 2 * H);
+    t.B = B;
+    c.tail_wg_bwd1 = false;
+  }
   // the RG rows of the first half on 64-row half-blocks (bwd_wide2.hip) from 16 384 packed rows (training step, ms without / with:
   // B = 24 0.209 / 0.217, B = 32 0.2395 / 0.237, B = 48 0.307 / 0.301, B = 64 0.355 / 0.349, B = 128 0.632 / 0.615, B = 256 1.007 / 0.944,
   // B = 1024 3.215 / 2.815) -- behind either forward: the saved set is the same
   const bool bwd1w = c.opt.wide2_bwd != 0 && (c.opt.wide2_bwd > 0 || (c.opt.fused_rt < 0 && T >= 16384));
   if (bwd1w) CK(launch_wide2_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half (64-row half-blocks)");
   else       CK(launch_fused_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half");
+  CK(record_tail_event(c, st), "tail event");      // (the one-launch tail's weight gradients are final behind the launch above)
   Bwd2Args a2; std::memset(&a2, 0, sizeof(a2));
   a2.Q2_16 = f.Q2_16; a2.dO2_16 = f.dO2_16; a2.lse2 = f.lse2; a2.delta2 = f.delta2; a2.KV2_16 = f.KV2_16; a2.dQKV16 = f.dQKV16;
   a2.dU16 = f.dU16; a2.WcRgT = f.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
@@ -1145,15 +1177,6 @@ int camo_forward_cached(const camo_dims_t* dims, const float* const* params, con
   return rc;
 }
 
-// camo_forward_loss_backward's optional event: recorded on the stream as soon as the gradients of the per-sample tail (pooled
-// FFN layers, fusion layer, heads: parameters CAMO_P_F2_W3 .. end of the table, and CAMO_P_F1_W3/B3) are final, so that a
-// data-parallel caller can start reducing that part of the flat buffer while the node-level backward runs.
-static int record_tail_event(Call& c, hipStream_t st) {      // (once per call: the first point that reaches it)
-  if (!c.tail_event) return 0;
-  const hipEvent_t ev = c.tail_event; c.tail_event = nullptr;
-  return (int)hipEventRecord(ev, st);
-}
-
 static int backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                          const int32_t* rg_offsets, const void* desc, const float* kg, int32_t B,
                          int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes, const float* outs,
@@ -1337,7 +1360,8 @@ static int forward_loss_backward_impl(Call& c, const camo_dims_t* dims, const fl
     Ws w = carve(*dims, B, T, Nk, workspace);
     bind_shadows(c, w);
     const Desc bd = desc_carve(B, T, const_cast<void*>(batch_desc));
-    CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event");
+    // the tail event; with one group of samples, behind backward_nodes17's first launch, which finishes the tail's weight gradients
+    if (!c.tail_wg_bwd1) CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event");
     return backward_nodes17(c, *dims, params, grads, rg_offsets, bd, B, T, Nk, w, make_drop(training, dims->dropout, seed),
                             static_cast<hipStream_t>(stream));
   }

@@ -61,13 +61,13 @@ int launch_clip_adamw(float* p, float* g, float* m, float* v, size_t n, float* s
 struct TailFusedArgs {
   const float *Ymean, *H1mean, *Y2mean, *H2mean;            // pooled node-level outputs [B][256], [B][512] x 2 streams
   const float *W13, *b13, *W23, *b23, *Wfu0, *bfu0, *Wfu3, *bfu3; const float* Wh0[4]; const float* bh0[4]; const float* Wh3[4]; const float* bh3[4];
-  float *gW13, *gb13, *gW23, *gb23, *gWfu0, *gbfu0, *gWfu3, *gbfu3; float* gWh0[4]; float* gbh0[4]; float* gWh3[4]; float* gbh3[4];   // += (mode 1)
+  float *gW13, *gb13, *gW23, *gb23, *gWfu0, *gbfu0, *gWfu3, *gbfu3; float* gWh0[4]; float* gbh0[4]; float* gWh3[4]; float* gbh3[4];   // mode 1: the kernel += gWh3, gbh3
   const long long* y; const float* e; const float* s;       // labels (mode 1)
   float* outs; float* terms; int* pred;                     // [B][2C+2]; mode 1: [B][4], [B] (may be null)
   float *F1sum, *hidsum, *dF1sum; unsigned int* counters;   // ZEROED exchange buffers [B][256], [B][512], [B][256]; 4 words (3 arrival counters + timeout flag)
   float *dcomb, *dHm1, *dHm2;                               // mode 1 out: d(mean Z) [B][512]; d(mean H) [B][512] x 2, ZEROED (accumulated with atomics)
-  // B > 16 (more than one group of samples), mode 1: the four big weight gradients are sums over ALL groups -- left to ONE batched
-  // GEMM launch behind this one (fusion_abi.hip, tail17), which reads these copies of the per-sample operands
+  // mode 1: copies of the per-sample operands of the eight big weight gradients, which the kernel leaves to the launches behind it
+  // (fusion_abi.hip, tail17: extra blocks of the node-level backward's first launch for one group, one batched GEMM launch for more)
   float *comb_out, *F1_out, *fused_out, *dhid_out, *dfused_out, *dF1_out;       // [B][512], [B][256], [B][256], [B][512], [B][256], [B][256]
   int B, C, mode; DropCfg drop;
   unsigned long long* stamps;                               // developer timeline (null in product calls)

@@ -647,7 +647,8 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(const float* __restrict
 //   outputs, all-reduced with fp32 atomics;  L3 (fusion layer 3) by output column, L4 (heads' hidden layers) by input
 //   column -> partial sums of their 512 outputs, all-reduced;  the head output layers and the loss are small enough
 //   to be recomputed by every block.  Backward mirrors it: one all-reduce (d F1), and the last partial sums
-//   (d mean H) are simply complete when the kernel ends.  Every weight gradient element has exactly one writer.
+//   (d mean H) are simply complete when the kernel ends.  The weight gradients are not on this chain: the kernel leaves copies of
+//   their per-sample operands, and the launch behind it computes them (only the output layer's are summed here).
 // An all-reduce = every block's atomics acknowledged, an arrival counter, a BOUNDED spin on it by one lane per block (the
 // grid is 64 blocks of 256 threads: co-resident on any MI355X partition of >= 64 CUs; on timeout the kernel raises
 // counters[3] and finishes with wrong numbers instead of hanging), an agent-scope acquire, then plain loads: float atomics
@@ -696,8 +697,7 @@ constexpr int TF_LDS_FLOATS = 2 * TF_MAXB * 512 + 2 * TF_MAXB * 256 + 2048 + 204
 
 // The kernel runs once per step on 64 CUs that have just run other code, one block per CU: what it costs is latency, not
 // throughput.  So: 1024 threads -- four "quarters" of 256 threads, quarter q walking samples 4q..4q+3 through every
-// per-sample phase (four independent chains per thread hide the LDS latency, four waves per SIMD hide each other's), and
-// the sums over the batch (weight gradients) split by output column between the quarters instead; every global read whose
+// per-sample phase (four independent chains per thread hide the LDS latency, four waves per SIMD hide each other's); every global read whose
 // address is known early is issued early (one memory round trip at the start, a second one hidden behind the first
 // all-reduce), and the passes that fetch an all-reduce's result have all their loads in flight together.  The LDS images
 // are padded with zero rows to a multiple of 4 samples.
@@ -715,9 +715,10 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   // Sample groups: block (g, sg) = column slice g of samples [16 sg, 16 sg + 16).  Groups never wait for each other (their own
   // arrival counters), so a batch of up to 16 * groups samples costs one group's latency while the chip has 64 CUs per group;
   // blocks are numbered group by group, so the blocks a group waits for are never queued behind blocks that wait for them.
-  // With more than one group the four big weight gradients (sums over every group's samples) are left to one batched GEMM launch
-  // behind this kernel, which gets the per-sample operands from the *_out copies; the small output-layer gradients use atomics.
-  const bool wg = a.mode && gridDim.x > TG;               // (write the copies, skip the big weight gradients)
+  // The eight big weight gradients (the heads' hidden layers, fusion layers 3 and 0, the two pooled FFN layers) are left to the
+  // launches behind this kernel, which get the per-sample operands from the *_out copies: nothing on the chain from here to the
+  // node-level backward waits for them (fusion_abi.hip, tail17).  The small output-layer gradients stay here (atomics with more than one group).
+  const bool wg = a.mode != 0;                              // (write the copies)
   const int tid = threadIdx.x, lane = tid & 63, g = blockIdx.x & (TG - 1), sg = blockIdx.x >> 6, C = a.C, Wd = 2 * C + 2;
   const bool multi = gridDim.x > TG;
   const int sb = TF_MAXB * sg, B = min(TF_MAXB, a.B - sb);
@@ -737,11 +738,10 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   unsigned int* const cnt = a.counters + 4 * sg;            // arrivals: words 4 sg .. 4 sg + 2 (word 3: the launch's gave-up flag)
   unsigned int* const gaveup = a.counters + 3;
   auto put = [&](float* p, float v) { if (multi) atomicAdd(p, v); else *p = v; };
-  auto put2 = [&](float2* p, float2 v) { if (multi) { atomicAdd(&p->x, v.x); atomicAdd(&p->y, v.y); } else *p = v; };
   const int q = __builtin_amdgcn_readfirstlane(tid >> 8), t = tid & 255, wv = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int b0 = 4 * q, B4 = (B + 3) & ~3;
   const bool active = b0 < B;                               // (wave-uniform)
-  float* R1 = sm;                       // [16][512] pooled FFN activations of this block's stream (kept to the end)
+  float* R1 = sm;                       // [16][512] pooled FFN activations of this block's stream
   float* R2 = R1 + TF_MAXB * 512;       // [16][512] the heads' hidden activations, then (in place) the gradient of their pre-activations
   float* F1 = R2 + TF_MAXB * 512;       // [16][256] fusion layer 0 activations (after ReLU and dropout)
   float* DF = F1 + TF_MAXB * 256;       // [16][256] gradient of fusion layer 0's pre-activations
@@ -756,15 +756,13 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   const int c0 = 8 * (g & 31), ccol = (kgs ? 256 : 0) + c0;
   const float* Hmean = kgs ? gH2mean : gH1mean; const float* Ymean = kgs ? gY2mean : gYmean;
   const float* W3s = kgs ? a.W23 : a.W13; const float* b3s = kgs ? a.b23 : a.b13;
-  float* gW3s = kgs ? a.gW23 : a.gW13; float* gb3s = kgs ? a.gb23 : a.gb13; float* dHm = kgs ? gdHm2 : gdHm1;
+  float* dHm = kgs ? gdHm2 : gdHm1;
   const bool dodrop = a.drop.p > 0.f;
   const float dscale = a.drop.scale;
   auto headW0 = [&](int x) { return x == 0 ? a.Wh0[0] : (x == 1 ? a.Wh0[1] : (x == 2 ? a.Wh0[2] : a.Wh0[3])); };
   auto headB0 = [&](int x) { return x == 0 ? a.bh0[0] : (x == 1 ? a.bh0[1] : (x == 2 ? a.bh0[2] : a.bh0[3])); };
   auto headW3 = [&](int x) { return x == 0 ? a.Wh3[0] : (x == 1 ? a.Wh3[1] : (x == 2 ? a.Wh3[2] : a.Wh3[3])); };
   auto headB3 = [&](int x) { return x == 0 ? a.bh3[0] : (x == 1 ? a.bh3[1] : (x == 2 ? a.bh3[2] : a.bh3[3])); };
-  auto gheadW0 = [&](int x) { return x == 0 ? a.gWh0[0] : (x == 1 ? a.gWh0[1] : (x == 2 ? a.gWh0[2] : a.gWh0[3])); };
-  auto gheadB0 = [&](int x) { return x == 0 ? a.gbh0[0] : (x == 1 ? a.gbh0[1] : (x == 2 ? a.gbh0[2] : a.gbh0[3])); };
   auto gheadW3 = [&](int x) { return x == 0 ? a.gWh3[0] : (x == 1 ? a.gWh3[1] : (x == 2 ? a.gWh3[2] : a.gWh3[3])); };
   auto gheadB3 = [&](int x) { return x == 0 ? a.gbh3[0] : (x == 1 ? a.gbh3[1] : (x == 2 ? a.gbh3[2] : a.gbh3[3])); };
   auto head_of = [&](int o, int& x, int& oo) {              // output column o of [mask C | instance C | edge | score]
@@ -803,26 +801,14 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   const float bias2 = g == 0 ? a.bfu0[t] : 0.f;
   const float bias3 = a.bfu3[4 * g + wv];
   const float bias4a = g == 0 ? headB0(t >> 7)[t & 127] : 0.f, bias4b = g == 0 ? headB0(2 + (t >> 7))[t & 127] : 0.f;
-  // operands of the backward and the old values of every gradient this block adds to: issued behind the forward's
-  // reads (loads return in order: the forward never waits for these), so that no += later waits for its read.  The sums over the batch are split between the quarters by column:
-  //   hidden-layer weights [512 m][4 c]: m = t + 256 (q & 1), columns 2 (q >> 1), +1;  fusion layer 3 [256 n][4 c]: column q;
-  //   fusion layer 0 [256 n][8 c]: columns 2q, 2q + 1;  pooled FFN layer [512 k][8 c]: k = t + 256 (q & 1), columns 4 (q >> 1)..+3
-  const int qm = t + 256 * (q & 1), qh = q >> 1;
+  // the old values of the output-layer gradients this block adds to (one group: plain stores), issued behind the forward's
+  // reads (loads return in order: the forward never waits for these)
   const int hx = (8 * g) >> 7, hmm0 = (8 * g) & 127, hnout = hx < 2 ? C : 1, hcoff = hx == 0 ? 0 : (hx == 1 ? C : (hx == 2 ? 2 * C : 2 * C + 1));
   float* dW3h = gheadW3(hx) + (size_t)(tid >> 3) * 128 + hmm0 + (tid & 7);
-  float2* dstW0 = reinterpret_cast<float2*>(gheadW0(qm >> 7) + (size_t)(qm & 127) * 256 + 4 * g + 2 * qh);
-  float* dstfu3 = a.gWfu3 + (size_t)(4 * g + q) * 256 + t;
-  float2* dstfu0 = reinterpret_cast<float2*>(a.gWfu0 + (size_t)t * 512 + ccol + 2 * q);
-  float oW3h = 0.f, ob3h = 0.f, ob0h = 0.f, obfu3 = 0.f, obfu0 = 0.f, ob3s = 0.f, ofu3 = 0.f, ogw3[4] = {0.f, 0.f, 0.f, 0.f};
-  float2 oW0 = make_float2(0.f, 0.f), ofu0 = make_float2(0.f, 0.f);
+  float oW3h = 0.f, ob3h = 0.f;
   if (a.mode && !multi) {
     if (tid < hnout * 8) oW3h = *dW3h;
     if (g == 0 && tid >= 128 && tid < 128 + Wd) { int xx, oo; head_of(tid - 128, xx, oo); ob3h = gheadB3(xx)[oo]; }
-    oW0 = *dstW0; ofu3 = *dstfu3; ofu0 = *dstfu0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ogw3[c] = gW3s[(size_t)(c0 + 4 * qh + c) * 512 + qm];
-    if (tid < 8) { ob0h = gheadB0((8 * g + tid) >> 7)[(8 * g + tid) & 127]; ob3s = gb3s[c0 + tid]; }
-    if (tid < 4) { obfu3 = a.gbfu3[4 * g + tid]; obfu0 = a.gbfu0[4 * g + tid]; }
   }
 #pragma unroll
   for (int it = 0; it < 2; ++it) { const int i = tid + TF_THREADS * it; if (i < B4 * 128) reinterpret_cast<float4*>(R1)[i] = hv[it]; }
@@ -1026,8 +1012,7 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   }
   __syncthreads();
   tstamp(a.stamps, 13);
-  // ---- d fused for this block's 4 columns (wave wv: column wv): sum over the 512 hidden units; the hidden-layer weight
-  // gradients of those 4 columns (2 per quarter pair); hidden-layer bias gradients of units [8g, 8g+8)
+  // ---- d fused for this block's 4 columns (wave wv: column wv): sum over the 512 hidden units
   if (active) {
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1045,47 +1030,14 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
       }
     }
   }
-  if (!wg) {
-    float2 gacc = oW0;
-#pragma unroll 1
-    for (int bb = 0; bb < B; bb += 4)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = R2[(bb + j) * 512 + qm];
-        const float2 f = reinterpret_cast<const float2*>(fusedS)[(bb + j) * 2 + qh];
-        gacc.x = fmaf(d, f.x, gacc.x); gacc.y = fmaf(d, f.y, gacc.y);
-      }
-    put2(dstW0, gacc);
-    if (tid < 8) {
-      const int m = 8 * g + tid;
-      float s = ob0h;
-#pragma unroll 1
-      for (int b = 0; b < B; ++b) s += R2[b * 512 + m];
-      put(gheadB0(m >> 7) + (m & 127), s);
-    }
-  }
   __syncthreads();
   tstamp(a.stamps, 14);
-  // ---- partial sums of d F1 (fusion layer 3 by its output rows 4g..4g+3); its weight and bias gradients
+  // ---- partial sums of d F1 (fusion layer 3 by its output rows 4g..4g+3)
   if (active) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float4 df = reinterpret_cast<const float4*>(dfusedS)[b0 + j];
       if (b0 + j < B) atomicAdd(gdF1sum + (b0 + j) * 256 + t, df.x * WfL[t] + df.y * WfL[256 + t] + df.z * WfL[512 + t] + df.w * WfL[768 + t]);
-    }
-  }
-  if (!wg) {
-    float gw = ofu3;
-#pragma unroll 1
-    for (int bb = 0; bb < B; bb += 4)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) gw = fmaf(dfusedS[(bb + j) * 4 + q], F1[(bb + j) * 256 + t], gw);
-    put(dstfu3, gw);
-    if (tid < 4) {
-      float s = obfu3;
-#pragma unroll 1
-      for (int b = 0; b < B; ++b) s += dfusedS[b * 4 + tid];
-      put(a.gbfu3 + 4 * g + tid, s);
     }
   }
   tstamp(a.stamps, 15);
@@ -1103,8 +1055,7 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
   }
   __syncthreads();
   tstamp(a.stamps, 17);
-  // ---- d comb for this block's 8 columns (wave wv: columns 2wv, 2wv+1); fusion layer 0's weight gradients of those columns,
-  // its bias gradients of units [4g, 4g+4)
+  // ---- d comb for this block's 8 columns (wave wv: columns 2wv, 2wv+1)
   if (active) {
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
@@ -1127,27 +1078,9 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
     }
   }
   tstamp(a.stamps, 18);
-  if (!wg) {
-    float2 gw = ofu0;
-#pragma unroll 1
-    for (int bb = 0; bb < B; bb += 4)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = DF[(bb + j) * 256 + t];
-        const float2 cv = reinterpret_cast<const float2*>(combS)[(bb + j) * 4 + q];
-        gw.x = fmaf(d, cv.x, gw.x); gw.y = fmaf(d, cv.y, gw.y);
-      }
-    put2(dstfu0, gw);
-    if (tid < 4) {
-      float s = obfu0;
-#pragma unroll 1
-      for (int b = 0; b < B; ++b) s += DF[b * 256 + 4 * g + tid];
-      put(a.gbfu0 + 4 * g + tid, s);
-    }
-  }
   __syncthreads();
   tstamp(a.stamps, 19);
-  // ---- partial sums of d(mean H) of this block's stream (complete when the kernel ends); the pooled FFN layer's weight gradients
+  // ---- partial sums of d(mean H) of this block's stream (complete when the kernel ends)
   if (active) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1160,25 +1093,6 @@ __global__ __launch_bounds__(TF_THREADS) void tail_fused_kernel(const TailFusedA
         if (b0 + j < B) atomicAdd(dHm + (b0 + j) * 512 + t + 256 * kk, acc);
       }
     }
-  }
-  if (!wg) {
-    float gw[4] = {ogw3[0], ogw3[1], ogw3[2], ogw3[3]};
-#pragma unroll 1
-    for (int bb = 0; bb < B; bb += 4)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float4 dc = reinterpret_cast<const float4*>(dcombS)[(bb + j) * 2 + qh];
-        const float hm = R1[(bb + j) * 512 + qm];
-        gw[0] = fmaf(dc.x, hm, gw[0]); gw[1] = fmaf(dc.y, hm, gw[1]); gw[2] = fmaf(dc.z, hm, gw[2]); gw[3] = fmaf(dc.w, hm, gw[3]);
-      }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) put(gW3s + (size_t)(c0 + 4 * qh + c) * 512 + qm, gw[c]);
-  }
-  if (!wg && tid < 8) {
-    float s = ob3s;
-#pragma unroll 1
-    for (int b = 0; b < B; ++b) s += dcombS[b * 8 + tid];
-    put(gb3s + c0 + tid, s);
   }
   tstamp(a.stamps, 20);
 }
@@ -1537,6 +1451,7 @@ int tail_fused_ok(int B, int C) {
 }
 int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream) {
   if (!tail_fused_ok(a.B, a.C)) return (int)hipErrorInvalidValue;
+  if (a.mode && (!a.comb_out || !a.F1_out || !a.fused_out || !a.dhid_out || !a.dfused_out || !a.dF1_out)) return (int)hipErrorInvalidValue;
   static const bool attr = [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TF_LDS_FLOATS * 4);
     return true;

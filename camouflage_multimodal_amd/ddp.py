@@ -69,8 +69,9 @@ class BucketedGradAllReducer(GradAllReducer):
     """Two buckets instead of one, the first overlapped with the node-level backward.
 
     The gradients of the per-sample tail (pooled KG FFN layer, fusion layer, heads: ``engine.tail_grad_offset()`` .. end of
-    the flat buffer, ~1/3 of it) are final before the four node-level backward launches start.  The native training call
-    records an event at that point (``camo_forward_loss_backward(tail_event=...)``); bucket A's all-reduce is issued on a
+    the flat buffer, ~1/3 of it) are final when the first node-level backward launch ends (at B <= 16 its last blocks compute
+    the tail's big weight gradients; at larger B they are final even before it starts).  The native training call records an
+    event at that point (``camo_forward_loss_backward(tail_event=...)``); bucket A's all-reduce is issued on a
     side stream behind that event and runs beside the backward kernels, bucket B (everything in front of the offset) is
     issued behind the whole call.  Both land before the clip: ``wait()`` orders the launch stream behind them.  The sum
     is the same as the single all-reduce's (a different partition of the same element-wise SUM)."""

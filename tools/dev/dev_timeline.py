@@ -40,8 +40,8 @@ if train:
     if t[:, 0].min() > 0:
         t0 = t[:, 0].min()
         names = {0: "start", 1: "staged", 2: "L1 done", 3: "L2 issued", 4: "AR1 done", 5: "F1 staged", 6: "L3 done", 7: "L4 issued", 8: "AR2 done",
-                 9: "hid staged", 10: "head outputs", 11: "loss", 12: "output-layer grads", 13: "d hidden", 14: "d fused + hidden-layer grads",
-                 15: "d F1 issued", 16: "AR3 done", 17: "dF staged", 18: "d comb", 19: "fusion layer 0 grads", 20: "end"}
+                 9: "hid staged", 10: "head outputs", 11: "loss", 12: "output-layer grads", 13: "d hidden", 14: "d fused",
+                 15: "d F1 issued", 16: "AR3 done", 17: "dF staged", 18: "d comb", 19: "d comb shared", 20: "end"}
         print("--- tail (one launch): stamp (median / max over the 64 blocks, us from first block start; delta to previous)")
         prev = 0.0
         for k in range(21):
@@ -74,9 +74,13 @@ for k, name in enumerate(("front", "back", "bwd1", "bwd2") if train else ("front
     idx = np.nonzero(act)[0]
     if name == "back":
         groups = [("KG splits", idx < nkg), ("RG tiles", idx >= nkg)]
-    elif name == "bwd1":                      # grid order: RG tiles, KG blocks, (writer blocks: no stamps)
+    elif name == "bwd1":                      # grid order: RG tiles, KG blocks, (writer and clearing blocks: no stamps), the tail's dW tiles
         rgmax = sum(nrs) // 32 + B
-        groups = [("KG blocks", (idx >= rgmax) & (idx < rgmax + B)), ("RG tiles", idx < rgmax)]
+        tw = idx >= rgmax + B
+        groups = [("KG blocks", (idx >= rgmax) & (idx < rgmax + B)), ("RG tiles", idx < rgmax), ("tail dW", tw)]
+        if tw.any():
+            print(f"    tail dW tiles: start {(s[tw, 0].min() - t0) / 100:.2f}..{(s[tw, 0].max() - t0) / 100:.2f} us, last ends at "
+                  f"{(s[tw, 3].max() - t0) / 100:.2f} us; the RG tiles and KG blocks end by {(s[~tw, 3].max() - t0) / 100:.2f} us")
     elif name == "bwd2":
         groups = [("KG blocks", idx < B), ("RG tiles", idx >= B)]
     else:
