@@ -140,6 +140,11 @@ class FusionOracle:
         self.near = None
         self.near_eps = 2e-4
         self.relu_flip = frozenset()
+        # The node-level FFN ReLUs (sites SITE_FFN_RG / SITE_FFN_KG) the same way, one (row, unit) at a time: when ``node_near`` is
+        # a list, every decision within ``node_eps`` of zero is recorded there as (site, sample, (row, unit), value);
+        # ``relu_flip`` entries (site, sample, (row, unit)) invert such a decision.
+        self.node_near = None
+        self.node_eps = 1e-6
 
     def _relu_tail(self, x, site, b_index):
         pos = x > 0
@@ -152,6 +157,17 @@ class FusionOracle:
         return np.where(pos, x, f32(0)), pos
         if self.cfg["fusion_type"] not in ("cross_attention", "late"):
             raise ValueError(f"Unknown fusion_type: {self.cfg['fusion_type']}")
+
+    def _relu_node(self, x, site, b_index):
+        h = np.maximum(x, 0)
+        if self.node_near is not None:
+            for t, u in np.argwhere(np.abs(x) < self.node_eps):
+                self.node_near.append((site, b_index, (int(t), int(u)), float(x[t, u])))
+        for (s_, b_, u) in self.relu_flip:
+            if s_ == site and b_ == b_index and isinstance(u, tuple):
+                t, j = u                                  # (the other side of zero, within |x| of the plain value)
+                h[t, j] = f32(0) if x[t, j] > 0 else max(abs(x[t, j]), f32(1e-30))
+        return h
 
     # ------------------------------------------------------------------ fwd
     def forward_sample(self, rg, kg, training=False, seed=0, row_base=0, b_index=0, kg_row_base=None):
@@ -192,7 +208,7 @@ class FusionOracle:
         A = _linear(O, W("fusion.cross_attn_rg2kg.out_proj.weight"), P["fusion.cross_attn_rg2kg.out_proj.bias"])
         # fusion_model.py:119-120  (the mean pool of Z uses the fp32 LayerNorm output; the first FFN layer its bf16 copy)
         Y, xh1, rstd1 = _layernorm(R + A, P["fusion.ln_rg.weight"], P["fusion.ln_rg.bias"])
-        H1 = np.maximum(_linear(q(Y), W("fusion.ffn_rg.0.weight"), P["fusion.ffn_rg.0.bias"]), 0)
+        H1 = self._relu_node(_linear(q(Y), W("fusion.ffn_rg.0.weight"), P["fusion.ffn_rg.0.bias"]), SITE_FFN_RG, b_index)
         H1d, m_f1 = _drop(H1, seed, SITE_FFN_RG, row_base * 2 * H, pd, training)
         Z = Y + _linear(H1d, P["fusion.ffn_rg.3.weight"], P["fusion.ffn_rg.3.bias"])
         # fusion_model.py:123-129 -- MHA, query=kg, key=value=rg_proj
@@ -228,7 +244,7 @@ class FusionOracle:
         A2 = _linear(O2, W("fusion.cross_attn_kg2rg.out_proj.weight"), P["fusion.cross_attn_kg2rg.out_proj.bias"])
         # fusion_model.py:130-131
         Y2, xh2, rstd2 = _layernorm(G + A2, P["fusion.ln_kg.weight"], P["fusion.ln_kg.bias"])
-        H2 = np.maximum(_linear(q(Y2), W("fusion.ffn_kg.0.weight"), P["fusion.ffn_kg.0.bias"]), 0)
+        H2 = self._relu_node(_linear(q(Y2), W("fusion.ffn_kg.0.weight"), P["fusion.ffn_kg.0.bias"]), SITE_FFN_KG, b_index)
         H2d, m_f2 = _drop(H2, seed, SITE_FFN_KG, kg_row_base * 2 * H, pd, training)
         Zk = Y2 + _linear(H2d, P["fusion.ffn_kg.3.weight"], P["fusion.ffn_kg.3.bias"])
         # fusion_model.py:134-139

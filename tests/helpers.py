@@ -93,13 +93,22 @@ def oracle_step_at_relu_thresholds(make_oracle, step, got_grads, max_near=6, max
     return best, list(orc.near), flips
 
 
-def oracle_batch_step(make_oracle, rg_list, kg, y, e, s, seed, got_grads=None, training=True, near_eps=5e-5, max_near=None, max_flips=None):
+def oracle_batch_step(make_oracle, rg_list, kg, y, e, s, seed, got_grads=None, training=True, near_eps=5e-5, max_near=None, max_flips=None,
+                      node_off=None, node_eps=1e-6, max_node_near=None, max_node_flips=None):
     """The reference-semantics gradient of a LARGE minibatch (train_multimodal.py:238-279: per-sample forward / backward, gradients
     summed) from the oracle, one sample at a time and without keeping the samples' caches: -> dict(outs [B, 6 ...] as the
     oracle's forward_list gives them, loss_terms [B, 4], raw_grads, near, flips).  Samples are independent, so the ReLU-threshold
     treatment of ``oracle_step_at_relu_thresholds`` costs one sample's step per candidate unit here instead of a whole batch's:
     a unit of sample b is tried flipped by replacing that sample's gradient contribution.  Bounds on the candidates and on the
-    flips taken scale with the batch (about one unit per 15 samples sits within 5e-5 of the threshold)."""
+    flips taken scale with the batch (about one unit per 15 samples sits within 5e-5 of the threshold).
+    ``node_off(raw_grads)`` -> {site: units} extends this to the node-level FFN ReLUs (FusionOracle._relu_node).  Past ~10^7
+    node-level pre-activations, a few sit within the f32 kernels' rounding (~1e-7) of zero; one such row moves its unit's gradient
+    row in the first FFN layer by a percent of the tensor's RMS.  The first pass records every node-level decision within
+    ``node_eps`` of zero; after the tail units are settled, ``node_off`` names the units whose gradient rows are still off, and
+    only those units' recorded decisions are tried, so the door stays narrow: ``max_node_near`` candidates and ``max_node_flips``
+    flips at most (default 4 x and 1 x the number of units named).
+    A flip replaces the sample's gradient contribution only: ``outs`` and ``loss_terms`` stay those of the first pass (a decision
+    within ``near_eps`` / ``node_eps`` of zero moves them by about that much)."""
     from oracle import fusion_oracle as FO
     B = len(rg_list)
     max_near = max(6, B // 6) if max_near is None else max_near
@@ -107,6 +116,8 @@ def oracle_batch_step(make_oracle, rg_list, kg, y, e, s, seed, got_grads=None, t
     orc = make_oracle()
     orc.near = []
     orc.near_eps = near_eps
+    if node_off is not None:
+        orc.node_near, orc.node_eps = [], node_eps
     g = orc.zero_grads()
     outs, terms, bases = [], [], []
     base = 0
@@ -123,25 +134,44 @@ def oracle_batch_step(make_oracle, rg_list, kg, y, e, s, seed, got_grads=None, t
         outs.append(ob); terms.append(t)
         base += len(rg_list[b])
     res = dict(outs={k: np.stack([o[k] for o in outs]) for k in ("mask", "instance", "edge", "score")}, loss_terms=np.stack(terms),
-               raw_grads=g, near=list(orc.near), flips=[])
-    if got_grads is None or not orc.near:
+               raw_grads=g, near=list(orc.near), node_near=[], flips=[])
+    if got_grads is None:
         return res
     assert len(orc.near) <= max_near, f"{len(orc.near)} tail units within {near_eps} of the ReLU threshold (allowed {max_near}): {orc.near}"
     best_err = _grad_err(got_grads, g)
     taken = {}                                   # sample -> flips kept so far
-    for (site, b, u, _) in orc.near:
-        plain, flipped = make_oracle(), make_oracle()
-        plain.relu_flip = frozenset(taken.get(b, []))
-        flipped.relu_flip = frozenset(taken.get(b, []) + [(site, b, u)])
-        g0, g1 = plain.zero_grads(), flipped.zero_grads()
-        sample_grad(plain, b, g0); sample_grad(flipped, b, g1)
-        trial = {k: g[k] + (g1[k] - g0[k]) for k in g}
-        err = _grad_err(got_grads, trial)
-        if err < best_err:
-            g, best_err = trial, err
-            taken.setdefault(b, []).append((site, b, u))
-            res["flips"].append((site, b, u))
+
+    def try_flips(cands):
+        nonlocal g, best_err
+        kept = []
+        for (site, b, u, _) in cands:
+            plain, flipped = make_oracle(), make_oracle()
+            plain.relu_flip = frozenset(taken.get(b, []))
+            flipped.relu_flip = frozenset(taken.get(b, []) + [(site, b, u)])
+            g0, g1 = plain.zero_grads(), flipped.zero_grads()
+            sample_grad(plain, b, g0); sample_grad(flipped, b, g1)
+            trial = {k: g[k] + (g1[k] - g0[k]) for k in g}
+            err = _grad_err(got_grads, trial)
+            if err < best_err:
+                g, best_err = trial, err
+                taken.setdefault(b, []).append((site, b, u))
+                kept.append((site, b, u))
+        return kept
+    res["flips"] = try_flips(orc.near)
     assert len(res["flips"]) <= max_flips, f"{len(res['flips'])} ReLU decisions taken flipped (allowed {max_flips}): {res['flips']}"
+    if node_off is not None:
+        off = node_off(g)
+        n_units = sum(len(v) for v in off.values())
+        max_node_near = 4 * n_units if max_node_near is None else max_node_near
+        max_node_flips = n_units if max_node_flips is None else max_node_flips
+        cands = [c for c in orc.node_near if c[2][1] in off.get(c[0], ())]
+        res["node_near"] = cands
+        assert len(cands) <= max_node_near, \
+            f"{len(cands)} node-level FFN decisions within {node_eps} of the ReLU threshold in units {off} (allowed {max_node_near}): {cands}"
+        node_flips = try_flips(cands)
+        assert len(node_flips) <= max_node_flips, \
+            f"{len(node_flips)} node-level FFN decisions taken flipped (allowed {max_node_flips}): {node_flips}"
+        res["flips"] += node_flips
     res["raw_grads"] = g
     return res
 

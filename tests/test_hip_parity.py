@@ -22,12 +22,14 @@ pytestmark = pytest.mark.gpu
 OUT_KEYS = ("mask", "instance", "edge", "score")
 
 
-def make_model(cfg, seed, precision="f32"):
+def make_model(cfg, seed, precision="f32", params=None):
+    """``params``: load these instead of OP.make_params(cfg, seed)."""
     from camouflage_multimodal_amd import build_multimodal_model
     from camouflage_multimodal_amd import _lib
     assert _lib.lib() is not None
     m = build_multimodal_model(cfg)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in OP.make_params(cfg, seed).items()}, strict=True)
+    prm = OP.make_params(cfg, seed) if params is None else params
+    m.load_state_dict({k: torch.from_numpy(np.array(v, np.float32)) for k, v in prm.items()}, strict=True)
     return m.to("cuda").set_precision(precision)
 
 
