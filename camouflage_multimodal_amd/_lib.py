@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcamo_fusion.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 FWD_INFERENCE = 1
 FLAG_ATTN_MAPS = 2
 SUMSQ_FLOATS = 257
@@ -22,7 +22,7 @@ NPARAMS_CROSS, NPARAMS_LATE = 44, 22
 
 # every symbol include/camo_fusion.h declares
 SYMBOLS = ("camo_abi_version", "camo_last_error", "camo_workspace_bytes", "camo_batch_desc_bytes", "camo_prepare_batch", "camo_gather_batch", "camo_forward", "camo_forward_cached", "camo_backward", "camo_forward_loss_backward",
-           "camo_loss", "camo_grad_sumsq", "camo_clip_adamw", "camo_shadow_bytes", "camo_clip_adamw_shadows", "camo_debug_gemm", "camo_debug_gemm16", "camo_debug_ws_offset",
+           "camo_loss", "camo_grad_sumsq", "camo_clip_adamw", "camo_shadow_bytes", "camo_clip_adamw_shadows", "camo_debug_gemm", "camo_debug_gemm16", "camo_debug_ws_offset", "camo_debug_plan",
            "camo_options_init", "camo_options_set", "camo_debug_set_stamps", "camo_prof_begin", "camo_prof_end", "camo_prof_kind", "camo_tail_timeouts", "camo_tail_poison_to_grads")
 
 
@@ -62,6 +62,15 @@ def default_options():
 class CamoDims(C.Structure):
     _fields_ = [("rg_dim", C.c_int32), ("kg_dim", C.c_int32), ("hidden_dim", C.c_int32), ("num_heads", C.c_int32),
                 ("num_classes", C.c_int32), ("fusion_type", C.c_int32), ("dropout", C.c_float), ("options", C.POINTER(CamoOptions))]
+
+
+CALL_FORWARD, CALL_BACKWARD, CALL_TRAIN = 0, 1, 2
+PLAN_FIELDS = ("nodes", "shadows", "save", "front", "front_rt", "back", "back_rt", "save_r16", "tail", "tail_wg", "loss", "tail_event", "param_space", "bwd1", "bwd2")
+
+
+class CamoPlan(C.Structure):
+    """camo_plan_t (include/camo_fusion.h): the launch schedule of one call, as camo_debug_plan reports it."""
+    _fields_ = [(n, C.c_int32) for n in PLAN_FIELDS]
 
 
 class CamoError(RuntimeError):
@@ -138,6 +147,8 @@ def lib():
     L.camo_debug_gemm16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]
     L.camo_debug_ws_offset.restype = C.c_int64
     L.camo_debug_ws_offset.argtypes = [C.POINTER(CamoDims), i32, i32, i32, C.c_char_p]
+    L.camo_debug_plan.restype = C.c_int
+    L.camo_debug_plan.argtypes = [C.POINTER(CamoDims), i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(CamoPlan)]
     L.camo_options_init.restype = C.c_int
     L.camo_options_init.argtypes = [C.POINTER(CamoOptions)]
     L.camo_options_set.restype = C.c_int

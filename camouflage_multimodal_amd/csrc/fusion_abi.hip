@@ -40,10 +40,11 @@ constexpr camo_options_t k_default_options = {/*sched16*/ -1, /*fused*/ -1, /*ta
 unsigned long long* g_dbg_stamps = nullptr;   // developer timeline buffer of the fused kernels (camo_debug_set_stamps; like camo_prof_*: a profiling facility, not a schedule option)
 int g_dbg_stamp_blocks = 0;
 
-// What one entry-point call needs below the entry point: built there, on its stack, and passed down by reference.  No option or per-call
-// state lives in the library, so two engines in one process (or two threads) cannot change each other's schedule or hand-offs.
+
+// The hand-offs of one entry-point call: state that one launch sequence leaves for a later one of the same call.  Built on the entry
+// point's stack and passed down by reference.  No option or per-call state lives in the library, so two engines in one process (or two
+// threads) cannot change each other's schedule or hand-offs.  (Decisions are not hand-offs: they are in the plan.)
 struct Call {
-  const camo_options_t& opt;          // the caller's options (dims->options), or k_default_options
   // camo_forward_cached / camo_forward_loss_backward: caller-owned weight shadows (camo_shadow_bytes), null otherwise.  The 14
   // fragment-order bf16 copies the fused kernels stream live there instead of in the per-batch workspace, so that the optimizer call
   // can leave them ready for the next step (camo_clip_adamw_shadows) and the forward need not rebuild them (shadows_valid).
@@ -53,13 +54,11 @@ struct Call {
   int shadows_state = 0;              // what the fused forward left in them: 0 untouched, 1 forward set, 2 forward + transposed
   // clears that a forward without a shadow launch leaves to the first backward kernel (forward_nodes17 -> backward_nodes17)
   void* zero_bwd1_ptr[FUSED_BWD1_MAXZ]; unsigned zero_bwd1_bytes[FUSED_BWD1_MAXZ]; int nzero_bwd1 = 0;
-  bool tailw_bwd_planes = false;      // the training forward built the two-plane tail's transposed planes (this call's workspace)
   hipEvent_t tail_event = nullptr;    // camo_forward_loss_backward's optional event (record_tail_event)
-  bool tail_wg_bwd1 = false;          // the one-launch tail (one group, training) left its eight big weight gradients to backward_nodes17's first launch
   int tail_skip = 0;                  // the caller's one-shot tail_skip_arrival: read by the entry points that can launch the one-launch tail,
   bool tail_skip_taken = false;       // which write 0 back to the caller's options once that launch took it
-  explicit Call(const camo_dims_t* d) : opt(*(d && d->options ? d->options : &k_default_options)) {}
 };
+const camo_options_t& options_of(const camo_dims_t* d) { return *(d && d->options ? d->options : &k_default_options); }
 
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 int fail_hip(int e, const char* where) {
@@ -347,80 +346,281 @@ void set_bcast(Gemm16Prob& p, const float* v, int ldv, const int* row_sample, co
   p.flags |= GF_RES_BCAST; p.res = v; p.ldr = ldv; p.row_sample = row_sample; p.inv_nr = inv_nr; p.uniform_n = uniform_n;
 }
 
-// The bf16 schedule runs when the operands can live in HBM as bf16 tiles the gemm16 kernel takes whole:
-// cross-attention fusion with both input projections, every width a multiple of 64, head_dim 32 attention
-// on the MFMA kernels.  Anything else (and option sched16 = 0) takes the general fp32-operand schedule.
-bool sched16_ok(const camo_options_t& o, const camo_dims_t& d, const float* const* P, int precision, int T, int Nk, int max_nr) {
-  if (o.sched16 == 0 || precision != CAMO_PREC_BF16 || d.fusion_type != CAMO_FUSION_CROSS_ATTENTION) return false;
-  if (!P[CAMO_P_RG_PROJ_W] || !P[CAMO_P_KG_PROJ_W]) return false;
-  if ((d.hidden_dim % 64) || (d.rg_dim % 64) || (d.kg_dim % 64)) return false;
-  if (!attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, false) || !attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, true))
-    return false;
-  return ((double)T + 128.0) * 3.0 * d.hidden_dim * 2.0 < 4.0e9;
+// the caller-owned weight shadows (Call::shadows)
+struct ShadowSet { us16 *Wrg, *Wkg, *Wqkv_rg, *Wqkv_kg, *Wo1, *Wo2, *W1, *W2, *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT, *Wf_rg; float* bf_rg; size_t bytes; };
+static ShadowSet shadow_carve(void* base) {
+  ShadowSet x{};
+  Carver c(base);
+  const size_t H = 256, D = 128, HH = H * H;
+  x.Wrg = c.take<us16>(H * D); x.Wkg = c.take<us16>(H * D); x.Wqkv_rg = c.take<us16>(3 * HH); x.Wqkv_kg = c.take<us16>(3 * HH);
+  x.Wo1 = c.take<us16>(HH); x.Wo2 = c.take<us16>(HH); x.W1 = c.take<us16>(2 * HH); x.W2 = c.take<us16>(2 * HH);
+  x.W1T = c.take<us16>(2 * HH); x.W2T = c.take<us16>(2 * HH); x.Wo1T = c.take<us16>(HH); x.Wo2T = c.take<us16>(HH);
+  x.WcRgT = c.take<us16>(3 * HH); x.WcKgT = c.take<us16>(3 * HH);
+  x.Wf_rg = c.take<us16>(3 * H * D); x.bf_rg = c.take<float>(3 * H);      // (inference calls only: launch_fold_rg)
+  x.bytes = (c.off + 255) & ~size_t(255);
+  return x;
+}
+void bind_shadows(void* shadows, Ws& w) {   // (a call that was handed external shadows keeps the fused schedule's weight shadows there)
+  const ShadowSet x = shadow_carve(shadows);
+  Ws::F17& f = w.f;
+  f.Wrg = x.Wrg; f.Wkg = x.Wkg; f.Wqkv_rg = x.Wqkv_rg; f.Wqkv_kg = x.Wqkv_kg; f.Wo1 = x.Wo1; f.Wo2 = x.Wo2; f.W1 = x.W1; f.W2 = x.W2;
+  f.W1T = x.W1T; f.W2T = x.W2T; f.Wo1T = x.Wo1T; f.Wo2T = x.Wo2T; f.WcRgT = x.WcRgT; f.WcKgT = x.WcKgT;
+  f.Wf_rg = x.Wf_rg; f.bf_rg = x.bf_rg;
+}
+
+// ---- the launch schedule of one call ----------------------------------------------------------------------
+// Which kernels a call runs follows from its arguments.  make_plan() is the one place that rule lives: a pure
+// function of the caller's options, the dims and the call's arguments (PlanIn), evaluated once per entry-point call; everything
+// below it takes its decisions from the camo_plan_t it returns (include/camo_fusion.h documents the fields; camo_debug_plan shows
+// it to the tests, tests/test_schedule_plan.py pins the table).
+enum CallKind { CALL_INFERENCE, CALL_FORWARD_SAVE /* a camo_backward follows */, CALL_BACKWARD, CALL_TRAIN /* camo_forward_loss_backward: labels ride along */ };
+struct PlanIn {
+  const camo_options_t& o; const camo_dims_t& d;
+  bool rg_proj, kg_proj;        // the projection weights are present
+  int precision, B, T, Nk, max_nr;
+  CallKind kind;
+  bool attn_maps;               // attention maps are wanted: pointers given, or CAMO_FLAG_ATTN_MAPS
+  int cus;                      // compute units of the device (the one-launch tail's blocks must be co-resident)
+};
+
+// the fused row-tile kernels' forward launches (fused_rows.h) of a call that takes that schedule
+static void plan_fused_forward(const PlanIn& in, bool save, bool param_space, camo_plan_t& p) {
+  const camo_options_t& o = in.o;
+  const int B = in.B, T = in.T, max_nr = in.max_nr, C = in.d.num_classes;
+  const bool infer = in.kind == CALL_INFERENCE, train = in.kind == CALL_TRAIN;
+  // Which tile family the two halves take: 0 = 32-row tiles, one per block of 4 waves (small batches: one tile per CU is all there
+  // is); 2 / 4 = that many tiles per block of 8 waves (fused_wide.hip), chosen so that the blocks still fill the chip.
+  int rt = o.fused_rt;
+  // by size: inference calls from about half a 128-row block per CU on (64-row blocks below that).  Calls that save for a backward stay on the 32-row kernels:
+  // the saved-tensor stores of the one-launch kernel are not tuned yet (measured slower: B = 64 step 0.53 vs 0.40 ms)
+  // (measured eval forward, us: B = 32 [13.5 k rows] 87 / 85 / 103 for 32-row / 2 / 4 tiles per block; B = 48 [20 k] 116 / 103 / 106; B = 56 [24 k] 131 / 112 / 108)
+  if (rt < 0) rt = save ? 0 : (T >= 22528 ? 4 : (T >= 13312 ? 2 : 0));
+  if (rt != 0 && rt != 1 && rt != 2 && rt != 4) rt = 0;
+  if (rt && max_nr > wide_max_rows(rt) - 64 * rt) rt = 0;
+  // The RG rows' whole forward in one launch of 64-row half-blocks, two independent blocks per CU, + the KG rows' launch behind it
+  // (fused_wide2.hip).  By size for inference AND training calls (the saving / dropout variants write the backward's saved set); a
+  // forced fused_rt selects the 8-wave / 32-row kernels.
+  bool rg64 = o.wide2 != 0 && o.fused_one != 0 && max_nr <= wide2_max_rows();
+  // training calls from 57 344 rows: their blocks are twice as long (the saved set, the dropout hashes), so the second round of blocks
+  // must be nearly full before they beat the 32-row back half (measured, ms per step without / with: B = 96 0.517 / 0.540, B = 128
+  // 0.637 / 0.621, B = 192 0.864 / 0.804, B = 256 1.076 / 0.979)
+  // inference calls from 10 240 rows (eval forward, us without / with: B = 16 59 / 66, B = 24 72.5 / 69.8, B = 32 77 / 71, B = 48 101 / 82)
+  if (rg64 && o.wide2 < 0) rg64 = o.fused_rt < 0 && o.wide_front_rt == 0 && T >= (save ? 57344 : 10240);
+  // the RG rows in one launch: the 64-row kernel, or the wide tiles' (rt >= 2)
+  const bool rg_one = rg64 || (rt >= 2 && o.fused_one != 0);
+  // Training calls (save): the front half alone on wide blocks -- 64-row blocks from 10 240 packed rows (front 21 -> 17 us at B = 24,
+  // 31 -> 26 at B = 48, 37 -> 28 at B = 56), 128-row blocks from 28 672.  -> sub-tiles per block, 0 = the 32-row front kernel.
+  // (the back half of training calls stays on the 32-row kernel, whose saving + dropout variant is the faster one: 77 vs 94 us at B = 64)
+  const bool rows128 = T >= 4 * 32 * 224;
+  int wf_rt = 0;
+  if (save && rt == 0 && o.fused_rt < 0 && o.wide_front_rt >= 0 && (T >= 10240 || o.wide_front_rt > 0)) {
+    wf_rt = o.wide_front_rt > 0 ? o.wide_front_rt : (rows128 ? 4 : 2);
+    if ((wf_rt != 1 && wf_rt != 2 && wf_rt != 4) || max_nr > wide_max_rows(wf_rt) - 64 * wf_rt) wf_rt = 0;
+  }
+  p.save = save;
+  if (rg_one) p.front = CAMO_FRONT_KG;
+  else if (rt || wf_rt) { p.front = CAMO_FRONT_WIDE; p.front_rt = rt ? rt : wf_rt; }
+  else p.front = CAMO_FRONT_ROWS32;
+  if (rg64) {
+    p.back = CAMO_BACK_RG_64;
+    // (R16 is read by the row-space form of the projections' weight gradients only; tests that read it back run an inference call with fused_save)
+    p.save_r16 = !param_space || o.fused_save != 0;
+  } else if (rt) { p.back = rg_one ? CAMO_BACK_RG_WIDE : CAMO_BACK_WIDE; p.back_rt = rt; }
+  else p.back = CAMO_BACK_ROWS32;
+
+  // The per-sample tail.  The two-plane launch's weight planes are built by extra blocks of a wide front launch (CAMO_FRONT_KG or
+  // CAMO_FRONT_WIDE), so both two-plane rules below are written on top of the front launch's.
+  const bool one_launch = o.tail17 != 0 && tail_fused_ok(B, C, in.cus);
+  // inference calls behind the RG rows' one-launch forward
+  // (B <= 32: the grouped fp32 tail, forward only, is the shorter one: 29.8 vs 33.5 us at B = 32; equal at 48)
+  const bool planes_infer = infer && o.tailw != 0 && rg_one && tail_wide_ok(B, C) && (o.tailw > 0 || B > 32 || !tail_fused_ok(B, C, in.cus));
+  // training calls from the 128-row front half's size on (wf_rt: also behind the RG rows' one-launch forward) with more than 64 samples: the tail's FORWARD as the one two-plane launch (with fp32
+  // copies of what the backward launches read) instead of four fp32 GEMM launches (B = 256: 4 x 27 us -> 34 us); the loss launch
+  // (heads_loss_kernel) and the backward follow -- the backward as ONE two-plane launch for the tail's input-gradient chain + ONE
+  // launch for its weight gradients, instead of four fp32 GEMM launches that each pair an input gradient with a weight gradient
+  // (B = 256: 108 us), unless tailw_bwd = 0
+  const bool planes_train = train && heads_loss_ok(B, C) && B > 64 && o.tailw != 0 && rows128 && wf_rt != 0 && tail_wide_ok(B, C);
+  if (planes_infer) p.tail = CAMO_TAIL_PLANES;
+  else if ((infer || train) && one_launch) p.tail = CAMO_TAIL_ONE_LAUNCH;
+  else if (planes_train) p.tail = o.tailw_bwd != 0 ? CAMO_TAIL_PLANES_TRAIN : CAMO_TAIL_PLANES_TRAIN_FWD;
+  else p.tail = CAMO_TAIL_GEMMS;
+  if (train && p.tail == CAMO_TAIL_ONE_LAUNCH) {
+    p.loss = CAMO_LOSS_TAIL;
+    // The kernel leaves copies of the operands of its eight big weight gradients, and these gradients to a launch behind it.  One
+    // group of 16 samples: extra blocks at the end of the node-level backward's first launch, which always follows, run them on CUs
+    // that its row tiles leave idle (a launch of their own would cost ~5 us of floor).  More groups: the gradients are sums over
+    // every group -- one batched launch (contraction over the B samples).
+    p.tail_wg = B > 16 ? CAMO_TAIL_WG_LAUNCH : CAMO_TAIL_WG_BWD1;
+    // the tail event: behind the launch that finishes the tail's weight gradients
+    p.tail_event = p.tail_wg == CAMO_TAIL_WG_BWD1 ? CAMO_EVENT_AFTER_BWD1 : CAMO_EVENT_BEFORE_NODES;
+  }
+}
+
+// the fused row-tile kernels' backward launches
+static void plan_fused_backward(const PlanIn& in, bool param_space, camo_plan_t& p) {
+  const camo_options_t& o = in.o;
+  p.param_space = param_space;
+  // the RG rows of the first half on 64-row half-blocks (bwd_wide2.hip) from 16 384 packed rows (training step, ms without / with:
+  // B = 24 0.209 / 0.217, B = 32 0.2395 / 0.237, B = 48 0.307 / 0.301, B = 64 0.355 / 0.349, B = 128 0.632 / 0.615, B = 256 1.007 / 0.944,
+  // B = 1024 3.215 / 2.815) -- behind either forward: the saved set is the same
+  const bool bwd1w = o.wide2_bwd != 0 && (o.wide2_bwd > 0 || (o.fused_rt < 0 && in.T >= 16384));
+  p.bwd1 = bwd1w ? CAMO_BWD1_64 : CAMO_BWD1_ROWS32;
+  // the second half without an arrival protocol (the KG rows' dQ2 sums become bf16 in a second, B-block launch): parameter-space
+  // form only, by the size rule of the wide first half: the extra launch costs ~2 us
+  // (wide2_bwd == 2: developer A/B, bwd2p_kernel + bwd2_finish_kernel behind the wide first half)
+  p.bwd2 = !(param_space && bwd1w) ? CAMO_BWD2_ROWS32 : (o.wide2_bwd != 2 ? CAMO_BWD2_64 : CAMO_BWD2_ROWS32_SPLIT);
+}
+
+camo_plan_t make_plan(const PlanIn& in) {
+  const camo_options_t& o = in.o; const camo_dims_t& d = in.d;
+  const int B = in.B, T = in.T, Nk = in.Nk, max_nr = in.max_nr;
+  const bool train = in.kind == CALL_TRAIN;
+  camo_plan_t p; std::memset(&p, 0, sizeof(p));
+  // the training call's loss, unless the one-launch tail takes it: the head output layer, the loss and the head output layer's backward
+  // as one kernel (misc.hip, heads_loss_kernel); large batches / many classes: the three steps as separate launches
+  if (train) p.loss = heads_loss_ok(B, d.num_classes) ? CAMO_LOSS_HEADS : CAMO_LOSS_LAUNCH;
+  if (d.fusion_type == CAMO_FUSION_LATE) {
+    p.nodes = CAMO_NODES_LATE;
+    if (train) p.tail_event = CAMO_EVENT_END;      // (a schedule without an earlier point)
+    return p;
+  }
+  if (train) p.tail_event = CAMO_EVENT_BEFORE_NODES;
+  const bool proj = in.rg_proj && in.kg_proj, bf16 = in.precision == CAMO_PREC_BF16;
+  // calls at the reference configuration that do not ask for attention maps take the fused row-tile schedule
+  if (!in.attn_maps && o.fused != 0 && bf16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS && proj) {
+    p.nodes = CAMO_NODES_FUSED;
+    p.shadows = in.kind != CALL_BACKWARD;      // (camo_backward takes no shadow argument)
+    // The projections' and in-projections' weight gradients in parameter space (no dR / dG product in the second backward kernel, 131 k
+    // instead of 427 k MACs per row, one small launch behind the weight gradients): from ~10 k packed rows on -- below that the extra launch
+    // (~10 us) costs what the second kernel saves (measured: B = 16 +10 us, B = 64 -22 us, B = 256 -105 us per step).  The forward reads it
+    // too: R16 is an operand of the row-space form only.
+    const bool param_space = o.param_space < 0 ? T >= 10240 : o.param_space > 0;
+    if (in.kind != CALL_BACKWARD) plan_fused_forward(in, in.kind != CALL_INFERENCE || o.fused_save != 0, param_space, p);
+    if (in.kind == CALL_BACKWARD || train) plan_fused_backward(in, param_space, p);
+    return p;
+  }
+  // The bf16 schedule runs when the operands can live in HBM as bf16 tiles the gemm16 kernel takes whole:
+  // cross-attention fusion with both input projections, every width a multiple of 64, head_dim 32 attention
+  // on the MFMA kernels.  Anything else (and option sched16 = 0) takes the general fp32-operand schedule.
+  const bool use16 = o.sched16 != 0 && bf16 && proj && !(d.hidden_dim % 64) && !(d.rg_dim % 64) && !(d.kg_dim % 64) &&
+                     attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, false) && attn_mfma_ok(d.hidden_dim, d.num_heads, Nk, max_nr, true) &&
+                     ((double)T + 128.0) * 3.0 * d.hidden_dim * 2.0 < 4.0e9;
+  p.nodes = use16 ? CAMO_NODES_BF16 : CAMO_NODES_GENERAL;
+  return p;
+}
+
+// What every function below an entry point needs: the call's arguments, and -- filled by open_batch() once they are validated -- the
+// caller's options, the plan, the carved descriptor and workspace (external shadows bound) and the dropout configuration.
+struct Batch {
+  const camo_dims_t* dims; const float* const* P; float* const* Gr; const float* rg; const int32_t* rg_offsets; const void* desc; const float* kg;
+  int B, T, Nk, max_nr; void* workspace; size_t workspace_bytes; int training; uint64_t seed; int precision; hipStream_t st;
+  const camo_options_t* opt; camo_plan_t plan; Desc bd; Ws w; DropCfg drop;
+};
+
+// the plan of an entry point's call (behind check_dims; params == null: left empty, open_batch refuses the call)
+void plan_batch(Batch& x, CallKind kind, bool attn_maps) {
+  x.opt = &options_of(x.dims);
+  if (x.P) x.plan = make_plan(PlanIn{*x.opt, *x.dims, x.P[CAMO_P_RG_PROJ_W] != nullptr, x.P[CAMO_P_KG_PROJ_W] != nullptr, x.precision, x.B, x.T, x.Nk, x.max_nr,
+                                     kind, attn_maps, device_cus()});
+}
+
+// (validated arguments -> the rest of the bundle; `ptrs_ok`: the entry point's own pointer arguments are there)
+int open_batch(Batch& x, const Call& c, bool ptrs_ok) {
+  if (!x.P || !x.rg || !x.rg_offsets || !x.desc || !x.kg || !x.workspace || !ptrs_ok) return fail(CAMO_E_ARG, "null pointer argument");
+  x.bd = desc_carve(x.B, x.T, const_cast<void*>(x.desc));
+  if (x.max_nr < 1 || x.max_nr > x.T) return fail(CAMO_E_ARG, "max_nr out of range");
+  if (x.precision != CAMO_PREC_F32 && x.precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
+  x.w = carve(*x.dims, x.B, x.T, x.Nk, x.workspace);
+  if (c.shadows) bind_shadows(c.shadows, x.w);
+  if (x.workspace_bytes < x.w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
+  x.drop = make_drop(x.training, x.dims->dropout, x.seed);
+  return 0;
 }
 
 // ---- the four heads (fusion_model.py:208-235), shared by both fusion types -------------------
 // The per-sample ("tail") GEMMs have M = B rows and a negligible FLOP share, so they always run
 // on the exact f32 MFMA; `precision` selects the MFMA type of the node-level (T-row) GEMMs only.
-// labels + outputs of the native training call: when given, the head output layer, the loss and the head output
-// layer's backward run as one kernel (misc.hip, heads_loss_kernel) instead of three launches
-struct FusedLoss { const int64_t* y; const float* e; const float* s; float* terms; int32_t* pred; float* const* head_grads; };
+// labels + outputs of the native training call: where the plan puts the loss (camo_plan_t::loss)
+struct FusedLoss { const int64_t* y; const float* e; const float* s; float* terms; int32_t* pred; };
+GB tail_gemms(const Batch& x) { return GB(x.drop, CAMO_PREC_F32, x.st); }     // per-sample (B-row) GEMMs
 
-int heads_forward(const camo_dims_t& d, const float* const* hp /*16 pointers*/, const Ws& w, int B, int F,
-                  float* outs, GB& g, const FusedLoss* fl = nullptr, bool hidden_done = false, bool defer_out_grads = false) {
-  const int Fh = F / 2, C = d.num_classes, Wd = 2 * C + 2;
+// fl given: the head output layer, the loss and the head output layer's backward run as one kernel (misc.hip, heads_loss_kernel)
+// instead of three launches
+int heads_forward(const Batch& x, int head0, int F, float* outs, const FusedLoss* fl, bool hidden_done = false, bool defer_out_grads = false) {
+  const camo_dims_t& d = *x.dims; const Ws& w = x.w;
+  const float* const* hp = x.P + head0;
+  const int B = x.B, Fh = F / 2, C = d.num_classes, Wd = 2 * C + 2;
   const int nout[4] = {C, C, 1, 1}, coff[4] = {0, C, 2 * C, 2 * C + 1};
+  GB g = tail_gemms(x);
   if (!hidden_done) {                      // (else w.hid came out of the two-plane tail launch)
-    for (int x = 0; x < 4; ++x) {
-      GemmProb& p = g.nt(w.fused, F, hp[4 * x], F, hp[4 * x + 1], w.hid + x * Fh, 4 * Fh, B, Fh, F, GF_RELU);
-      set_drop(p, SITE_HEAD0 + x);
+    for (int h = 0; h < 4; ++h) {
+      GemmProb& p = g.nt(w.fused, F, hp[4 * h], F, hp[4 * h + 1], w.hid + h * Fh, 4 * Fh, B, Fh, F, GF_RELU);
+      set_drop(p, SITE_HEAD0 + h);
     }
     CK(g.run(), "heads hidden");
   }
   if (fl) {
+    float* const* hg = x.Gr + head0;
     HeadsOut ho;
-    for (int x = 0; x < 4; ++x) { ho.W[x] = hp[4 * x + 2]; ho.b[x] = hp[4 * x + 3]; ho.gW[x] = fl->head_grads[4 * x + 2]; ho.gb[x] = fl->head_grads[4 * x + 3]; }
-    CK(launch_heads_loss(w.hid, ho, reinterpret_cast<const long long*>(fl->y), fl->e, fl->s, B, C, Fh, g.b.drop.scale, outs, fl->terms,
-                         fl->pred, w.dhid, g.st, defer_out_grads ? w.dlog : nullptr), "heads out + loss + heads out bwd");
+    for (int h = 0; h < 4; ++h) { ho.W[h] = hp[4 * h + 2]; ho.b[h] = hp[4 * h + 3]; ho.gW[h] = hg[4 * h + 2]; ho.gb[h] = hg[4 * h + 3]; }
+    CK(launch_heads_loss(w.hid, ho, reinterpret_cast<const long long*>(fl->y), fl->e, fl->s, B, C, Fh, x.drop.scale, outs, fl->terms,
+                         fl->pred, w.dhid, x.st, defer_out_grads ? w.dlog : nullptr), "heads out + loss + heads out bwd");
     return 0;
   }
-  for (int x = 0; x < 4; ++x)
-    g.nt(w.hid + x * Fh, 4 * Fh, hp[4 * x + 2], Fh, hp[4 * x + 3], outs + coff[x], Wd, B, nout[x], Fh, x == 3 ? GF_SIGMOID : 0);
+  for (int h = 0; h < 4; ++h)
+    g.nt(w.hid + h * Fh, 4 * Fh, hp[4 * h + 2], Fh, hp[4 * h + 3], outs + coff[h], Wd, B, nout[h], Fh, h == 3 ? GF_SIGMOID : 0);
   CK(g.run(), "heads out");
   return 0;
 }
 
-// d_outs -> dfused (w.dfused, zeroed here) and the 16 head-parameter gradients
-int heads_backward(const camo_dims_t& d, const float* const* hp, float* const* hg, const Ws& w, int B, int F,
-                   const float* outs, const float* d_outs, int pre_activation, const DropCfg& drop, hipStream_t st, GB& g,
-                   bool heads_out_done = false) {
-  const int Fh = F / 2, C = d.num_classes, Wd = 2 * C + 2;
+// d_outs -> dfused (w.dfused, zeroed by the forward) and the 16 head-parameter gradients
+int heads_backward(const Batch& x, int head0, int F, const float* outs, const float* d_outs, int pre_activation, bool heads_out_done) {
+  const camo_dims_t& d = *x.dims; const Ws& w = x.w;
+  const float* const* hp = x.P + head0; float* const* hg = x.Gr + head0;
+  const int B = x.B, Fh = F / 2, C = d.num_classes, Wd = 2 * C + 2;
   const int nout[4] = {C, C, 1, 1}, coff[4] = {0, C, 2 * C, 2 * C + 1};
+  GB g = tail_gemms(x);
   // (w.dfused was zeroed by the forward's memset of the workspace's zero block)
   if (!heads_out_done) {      // else w.dhid and the output-layer gradients came out of heads_loss_kernel
     const float* dlog = d_outs;
-    if (!pre_activation) { CK(launch_head_out_grad(outs, d_outs, w.dlog, B, Wd, st), "head_out_grad"); dlog = w.dlog; }
-    for (int x = 0; x < 4; ++x) {
-      GemmProb& p = g.nn(dlog + coff[x], Wd, hp[4 * x + 2], Fh, w.dhid + x * Fh, 4 * Fh, B, Fh, nout[x]);
-      set_relu_bwd(p, w.hid + x * Fh, 4 * Fh, drop.scale);
-      g.tn(dlog + coff[x], Wd, w.hid + x * Fh, 4 * Fh, hg[4 * x + 2], Fh, hg[4 * x + 3], nout[x], Fh, B);
+    if (!pre_activation) { CK(launch_head_out_grad(outs, d_outs, w.dlog, B, Wd, x.st), "head_out_grad"); dlog = w.dlog; }
+    for (int h = 0; h < 4; ++h) {
+      GemmProb& p = g.nn(dlog + coff[h], Wd, hp[4 * h + 2], Fh, w.dhid + h * Fh, 4 * Fh, B, Fh, nout[h]);
+      set_relu_bwd(p, w.hid + h * Fh, 4 * Fh, x.drop.scale);
+      g.tn(dlog + coff[h], Wd, w.hid + h * Fh, 4 * Fh, hg[4 * h + 2], Fh, hg[4 * h + 3], nout[h], Fh, B);
     }
     CK(g.run(), "heads out bwd");
   }
-  for (int x = 0; x < 4; ++x) {
-    g.nn(w.dhid + x * Fh, 4 * Fh, hp[4 * x], F, w.dfused, F, B, F, Fh, GF_ATOMIC);
-    g.tn(w.dhid + x * Fh, 4 * Fh, w.fused, F, hg[4 * x], F, hg[4 * x + 1], Fh, F, B);
+  for (int h = 0; h < 4; ++h) {
+    g.nn(w.dhid + h * Fh, 4 * Fh, hp[4 * h], F, w.dfused, F, B, F, Fh, GF_ATOMIC);
+    g.tn(w.dhid + h * Fh, 4 * Fh, w.fused, F, hg[4 * h], F, hg[4 * h + 1], Fh, F, B);
   }
   CK(g.run(), "heads hidden bwd");
   return 0;
 }
 
+// The eight big weight gradients of the cross-attention tail, dW [rows][cols] += dy^T x over the B samples (db += colsum(dy)): the
+// heads' hidden layers, fusion layers 3 and 0, the pooled FFN layers.  f(dy, ld_dy, x, ld_x, dW, db, rows, cols), in the order every
+// launch that sums them keeps (fp32 sums, some with atomics: the order is part of the result).
+template <typename F> void for_tail_wg(const Batch& b, F&& f) {
+  const Ws& w = b.w; float* const* Gr = b.Gr;
+  const int H = b.dims->hidden_dim, Fh = H / 2;
+  for (int h = 0; h < 4; ++h) f(w.dhid + h * Fh, 4 * Fh, w.fused, H, Gr[CAMO_P_HEADS + 4 * h], Gr[CAMO_P_HEADS + 4 * h + 1], Fh, H);
+  f(w.dfused, H, w.F1, H, Gr[CAMO_P_FU_W3], Gr[CAMO_P_FU_B3], H, H);
+  f(w.dF1, H, w.comb, 2 * H, Gr[CAMO_P_FU_W0], Gr[CAMO_P_FU_B0], H, 2 * H);
+  f(w.dcomb, 2 * H, w.H1mean, 2 * H, Gr[CAMO_P_F1_W3], Gr[CAMO_P_F1_B3], H, 2 * H);
+  f(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], Gr[CAMO_P_F2_B3], H, 2 * H);
+}
+void add_tail_wg(const Batch& b, GB& g) {
+  for_tail_wg(b, [&](const float* dy, int ld_dy, const float* x, int ld_x, float* dW, float* db, int rows, int cols) { g.tn(dy, ld_dy, x, ld_x, dW, cols, db, rows, cols, b.B); });
+}
 
 // ---- node-level forward of the bf16 schedule: CrossAttentionFusion.forward, fusion_model.py:75-135 ----
-int forward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets,
-                    const int32_t* row_sample, const float* inv_nr, const float* kg,
-                    int B, int T, int Nk, int max_nr, const Ws& w, float* attn_rg2kg, float* attn_kg2rg, const DropCfg& drop,
-                    hipStream_t st) {
+int forward_nodes16(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; const Ws& w = x.w; const DropCfg& drop = x.drop; hipStream_t st = x.st;
+  const float* rg = x.rg; const float* kg = x.kg; const int32_t* rg_offsets = x.rg_offsets;
+  const int32_t* row_sample = x.bd.row_sample; const float* inv_nr = x.bd.inv_nr;
+  const int B = x.B, T = x.T, Nk = x.Nk, max_nr = x.max_nr;
   const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, TK = B * Nk, nh = d.num_heads;
   const size_t HH = (size_t)H * H;
   const Ws::H16& h = w.h;
@@ -453,7 +653,7 @@ int forward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, 
     pad(h.dU2, tk, w.TKp, H); pad(h.dQKVkg, tk, w.TKp, 3 * H); pad(h.dG, tk, w.TKp, H); pad(h.H2, tk, w.TKp, 2 * H);
     CK(launch_prep(pb, st), "prep (clear + bf16 casts)");
   }
-  GB16 g(drop, c.opt, st);
+  GB16 g(drop, *x.opt, st);
   // input projections: fp32 for the residual stream, bf16 for the GEMMs that read them
   g.nt(h.KG, Dk, h.Wkg, Dk, P[CAMO_P_KG_PROJ_B], w.G, H, h.G, H, TK, H, Dk);
   g.nt(h.X, D, h.Wrg, D, P[CAMO_P_RG_PROJ_B], w.R, H, h.R, H, T, H, D);
@@ -506,122 +706,39 @@ int forward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, 
 }
 
 // ---- node-level forward of the fused row-tile schedule: the same function in 3 launches (fused_rows.h) ----
-bool fused17_ok(const camo_options_t& o, const camo_dims_t& d, const float* const* P, int precision, int Nk, int max_nr) {
-  return o.fused != 0 && precision == CAMO_PREC_BF16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS &&
-         P[CAMO_P_RG_PROJ_W] && P[CAMO_P_KG_PROJ_W];
-}
-
-// the caller-owned weight shadows (Call::shadows)
-struct ShadowSet { us16 *Wrg, *Wkg, *Wqkv_rg, *Wqkv_kg, *Wo1, *Wo2, *W1, *W2, *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT, *Wf_rg; float* bf_rg; size_t bytes; };
-static ShadowSet shadow_carve(void* base) {
-  ShadowSet x{};
-  Carver c(base);
-  const size_t H = 256, D = 128, HH = H * H;
-  x.Wrg = c.take<us16>(H * D); x.Wkg = c.take<us16>(H * D); x.Wqkv_rg = c.take<us16>(3 * HH); x.Wqkv_kg = c.take<us16>(3 * HH);
-  x.Wo1 = c.take<us16>(HH); x.Wo2 = c.take<us16>(HH); x.W1 = c.take<us16>(2 * HH); x.W2 = c.take<us16>(2 * HH);
-  x.W1T = c.take<us16>(2 * HH); x.W2T = c.take<us16>(2 * HH); x.Wo1T = c.take<us16>(HH); x.Wo2T = c.take<us16>(HH);
-  x.WcRgT = c.take<us16>(3 * HH); x.WcKgT = c.take<us16>(3 * HH);
-  x.Wf_rg = c.take<us16>(3 * H * D); x.bf_rg = c.take<float>(3 * H);      // (inference calls only: launch_fold_rg)
-  x.bytes = (c.off + 255) & ~size_t(255);
-  return x;
-}
-static void bind_shadows(const Call& c, Ws& w) {   // (after every carve() of a call that was handed external shadows)
-  if (!c.shadows) return;
-  const ShadowSet x = shadow_carve(c.shadows);
-  Ws::F17& f = w.f;
-  f.Wrg = x.Wrg; f.Wkg = x.Wkg; f.Wqkv_rg = x.Wqkv_rg; f.Wqkv_kg = x.Wqkv_kg; f.Wo1 = x.Wo1; f.Wo2 = x.Wo2; f.W1 = x.W1; f.W2 = x.W2;
-  f.W1T = x.W1T; f.W2T = x.W2T; f.Wo1T = x.Wo1T; f.Wo2T = x.Wo2T; f.WcRgT = x.WcRgT; f.WcKgT = x.WcKgT;
-  f.Wf_rg = x.Wf_rg; f.bf_rg = x.bf_rg;
-}
-
-// Which tile family a fused forward takes (fused_rows.h): 0 = 32-row tiles, one per block of 4 waves (small batches: one tile
-// per CU is all there is); 2 / 4 = that many tiles per block of 8 waves (fused_wide.hip), chosen so that the blocks still fill the chip.
-static int wide_rt(const camo_options_t& o, int T, int max_nr, bool save = false) {
-  int rt = o.fused_rt;
-  // by size: inference calls from about half a 128-row block per CU on (64-row blocks below that).  Calls that save for a backward stay on the 32-row kernels:
-  // the saved-tensor stores of the one-launch kernel are not tuned yet (measured slower: B = 64 step 0.53 vs 0.40 ms)
-  // (measured eval forward, us: B = 32 [13.5 k rows] 87 / 85 / 103 for 32-row / 2 / 4 tiles per block; B = 48 [20 k] 116 / 103 / 106; B = 56 [24 k] 131 / 112 / 108)
-  if (rt < 0) rt = save ? 0 : (T >= 22528 ? 4 : (T >= 13312 ? 2 : 0));
-  if (rt != 0 && rt != 1 && rt != 2 && rt != 4) rt = 0;
-  if (rt && max_nr > wide_max_rows(rt) - 64 * rt) rt = 0;
-  return rt;
-}
-
-// The RG rows' whole forward in one launch of 64-row half-blocks, two independent blocks per CU, + the KG rows' launch behind it
-// (fused_wide2.hip).  By size for inference AND training calls (the saving / dropout variants write the backward's saved set); a forced
-// fused_rt selects the 8-wave / 32-row kernels.
-static bool wide2_taken(const camo_options_t& o, int T, int max_nr, bool save, bool dropping) {
-  (void)dropping;
-  if (o.wide2 == 0 || o.fused_one == 0 || max_nr > wide2_max_rows()) return false;
-  if (o.wide2 > 0) return true;
-  // training calls from 57 344 rows: their blocks are twice as long (the saved set, the dropout hashes), so the second round of blocks
-  // must be nearly full before they beat the 32-row back half (measured, ms per step without / with: B = 96 0.517 / 0.540, B = 128
-  // 0.637 / 0.621, B = 192 0.864 / 0.804, B = 256 1.076 / 0.979)
-  // inference calls from 10 240 rows (eval forward, us without / with: B = 16 59 / 66, B = 24 72.5 / 69.8, B = 32 77 / 71, B = 48 101 / 82)
-  return o.fused_rt < 0 && o.wide_front_rt == 0 && T >= (save ? 57344 : 10240);
-}
-
-// Training calls (save): the front half alone on wide blocks -- 64-row blocks from 10 240 packed rows (front 21 -> 17 us at B = 24,
-// 31 -> 26 at B = 48, 37 -> 28 at B = 56), 128-row blocks from 28 672.  -> sub-tiles per block, 0 = the 32-row front kernel.
-// ONE predicate for everything that rides on that launch (the two-plane tail's weight planes are built by its extra blocks).
-static int wide_train_front_rt(const camo_options_t& o, int T, int max_nr, bool save) {
-  if (!save || wide_rt(o, T, max_nr, save) || o.fused_rt >= 0 || o.wide_front_rt < 0) return 0;
-  if (T < 10240 && o.wide_front_rt <= 0) return 0;
-  const int wf_rt = o.wide_front_rt > 0 ? o.wide_front_rt : (T >= 4 * 32 * 224 ? 4 : 2);
-  if (wf_rt != 1 && wf_rt != 2 && wf_rt != 4) return 0;
-  return max_nr <= wide_max_rows(wf_rt) - 64 * wf_rt ? wf_rt : 0;
-}
-
-static bool tailw_taken(const camo_options_t& o, const camo_dims_t& d, int B, int T, int max_nr, bool save, bool dropping) {
-  // (B <= 32: the grouped fp32 tail, forward only, is the shorter one: 29.8 vs 33.5 us at B = 32; equal at 48)
-  return o.tailw != 0 && o.fused_one != 0 && (wide_rt(o, T, max_nr, save) >= 2 || wide2_taken(o, T, max_nr, save, dropping)) && tail_wide_ok(B, d.num_classes) &&
-         (o.tailw > 0 || B > 32 || !tail_fused_ok(B, d.num_classes));
-}
-
-// The per-sample tail of the fused schedule as one launch (tail17), where a caller of the fused schedule asks for it
-static bool tail17_taken(const camo_options_t& o, const camo_dims_t& d, int B) { return o.tail17 != 0 && tail_fused_ok(B, d.num_classes); }
-
-// The projections' and in-projections' weight gradients in parameter space (no dR / dG product in the second backward kernel, 131 k
-// instead of 427 k MACs per row, one small launch behind the weight gradients): from ~10 k packed rows on -- below that the extra launch
-// (~10 us) costs what the second kernel saves (measured: B = 16 +10 us, B = 64 -22 us, B = 256 -105 us per step).  The forward reads it
-// too: R16 is an operand of the row-space form only.
-static bool param_space_bwd(const camo_options_t& o, int T) { return o.param_space < 0 ? T >= 10240 : o.param_space > 0; }
-
-int forward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, const float* rg, const int32_t* rg_offsets, const Desc& bd,
-                    const float* kg, int B, int T, int Nk, int max_nr, const Ws& w, const DropCfg& drop, bool save, hipStream_t st, int want_tailw = 0) {
-  const int H = 256, D = 128, TK = B * Nk;
+int forward_nodes17(Call& c, const Batch& x) {
+  const camo_plan_t& pl = x.plan; const float* const* P = x.P; const Ws& w = x.w; hipStream_t st = x.st;
+  const int H = 256, D = 128, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, max_nr = x.max_nr;
   const size_t HH = (size_t)H * H;
+  const bool save = pl.save != 0;
   const Ws::F17& f = w.f;
   FrontArgs fa; std::memset(&fa, 0, sizeof(fa));
   {   // weight shadows (bf16, fragment order) + the clear of the step's atomics block
     ShadowBatch sb; std::memset(&sb, 0, sizeof(sb));
-    auto job = [&](us* dst, int N, int K, const float* s0, int r0, const float* s1 = nullptr, int r1 = 0) {
+    // shadow of [s0; s1] (N rows of K columns), or of its transpose (transposed: the sources have K rows of N columns)
+    auto job = [&](us* dst, int N, int K, int transposed, const float* s0, int r0, const float* s1 = nullptr, int r1 = 0) {
       ShadowJob& J = sb.j[sb.n++];
-      J.dst = dst; J.N = N; J.K = K; J.transposed = 0; J.nsrc = s1 ? 2 : 1;
-      J.src[0] = s0; J.rows[0] = r0; J.ld[0] = K; J.src[1] = s1; J.rows[1] = r1; J.ld[1] = K;
+      const int ld = transposed ? N : K;
+      J.dst = dst; J.N = N; J.K = K; J.transposed = transposed; J.nsrc = s1 ? 2 : 1;
+      J.src[0] = s0; J.rows[0] = r0; J.ld[0] = ld; J.src[1] = s1; J.rows[1] = r1; J.ld[1] = ld;
     };
     const bool build = !c.shadows_valid;        // (valid: camo_clip_adamw_shadows left them ready; only the clears ride in this launch)
     if (c.shadows) c.shadows_state = save ? 2 : 1;
     if (build) {
-    job(f.Wrg, H, D, P[CAMO_P_RG_PROJ_W], H); job(f.Wkg, H, D, P[CAMO_P_KG_PROJ_W], H);
-    job(f.Wqkv_rg, 3 * H, H, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);       // [Wq1; Wk2; Wv2]: what RG rows are projected with
-    job(f.Wqkv_kg, 3 * H, H, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);       // [Wq2; Wk1; Wv1]
-    job(f.Wo1, H, H, P[CAMO_P_A1_OUT_W], H); job(f.Wo2, H, H, P[CAMO_P_A2_OUT_W], H);
-    job(f.W1, 2 * H, H, P[CAMO_P_F1_W0], 2 * H); job(f.W2, 2 * H, H, P[CAMO_P_F2_W0], 2 * H);
+      job(f.Wrg, H, D, 0, P[CAMO_P_RG_PROJ_W], H); job(f.Wkg, H, D, 0, P[CAMO_P_KG_PROJ_W], H);
+      job(f.Wqkv_rg, 3 * H, H, 0, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);       // [Wq1; Wk2; Wv2]: what RG rows are projected with
+      job(f.Wqkv_kg, 3 * H, H, 0, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);       // [Wq2; Wk1; Wv1]
+      job(f.Wo1, H, H, 0, P[CAMO_P_A1_OUT_W], H); job(f.Wo2, H, H, 0, P[CAMO_P_A2_OUT_W], H);
+      job(f.W1, 2 * H, H, 0, P[CAMO_P_F1_W0], 2 * H); job(f.W2, 2 * H, H, 0, P[CAMO_P_F2_W0], 2 * H);
     }
     auto zero = [&](void* ptr, size_t bytes) { if (bytes) { sb.zero_ptr[sb.nzero] = ptr; sb.zero_bytes[sb.nzero++] = (bytes + 15) & ~size_t(15); } };
     if (save) {
       // transposed shadows of the backward's dy . W products; K-concatenated where one product serves three in-projections
-      auto jobT = [&](us* dst, int N, int K, const float* s0, int r0, const float* s1 = nullptr, int r1 = 0) {
-        ShadowJob& J = sb.j[sb.n++];
-        J.dst = dst; J.N = N; J.K = K; J.transposed = 1; J.nsrc = s1 ? 2 : 1;
-        J.src[0] = s0; J.rows[0] = r0; J.ld[0] = N; J.src[1] = s1; J.rows[1] = r1; J.ld[1] = N;
-      };
       if (build) {
-      jobT(f.W1T, H, 2 * H, P[CAMO_P_F1_W0], 2 * H); jobT(f.W2T, H, 2 * H, P[CAMO_P_F2_W0], 2 * H);
-      jobT(f.Wo1T, H, H, P[CAMO_P_A1_OUT_W], H); jobT(f.Wo2T, H, H, P[CAMO_P_A2_OUT_W], H);
-      jobT(f.WcRgT, H, 3 * H, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);      // dR = [dQ | dK2 | dV2] . [Wq1; Wk2; Wv2]
-      jobT(f.WcKgT, H, 3 * H, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);      // dG = [dQ2 | dK | dV] . [Wq2; Wk1; Wv1]
+        job(f.W1T, H, 2 * H, 1, P[CAMO_P_F1_W0], 2 * H); job(f.W2T, H, 2 * H, 1, P[CAMO_P_F2_W0], 2 * H);
+        job(f.Wo1T, H, H, 1, P[CAMO_P_A1_OUT_W], H); job(f.Wo2T, H, H, 1, P[CAMO_P_A2_OUT_W], H);
+        job(f.WcRgT, H, 3 * H, 1, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);      // dR = [dQ | dK2 | dV2] . [Wq1; Wk2; Wv2]
+        job(f.WcKgT, H, 3 * H, 1, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);      // dG = [dQ2 | dK | dV] . [Wq2; Wk1; Wv1]
       }
       zero(w.zero_base, w.zero_bytes);                       // means, dfused, arrival counters, dK|dV and dQ2 sums
       // pad rows (row count rounded up to 128) of every weight-gradient operand: the contraction runs over whole 64-row tiles
@@ -640,13 +757,10 @@ int forward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, const 
     // inference calls: the RG rows' folded in-projection rides with every rebuild of the forward set, and alone when the caller's valid
     // shadows come from the optimizer call, which does not build it (camo_forward_cached, shadows_valid = 2)
     const bool fold = !save && (build || c.fold_missing);
-    if (build) {
-      CK(launch_weight_shadows(sb, st), "weight shadows");
-      if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
-                                   f.Wf_rg, f.bf_rg, st), "folded in-projection");
-    } else {
-      if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
-                                  f.Wf_rg, f.bf_rg, st), "folded in-projection");
+    if (build) CK(launch_weight_shadows(sb, st), "weight shadows");
+    if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
+                                f.Wf_rg, f.bf_rg, st), "folded in-projection");
+    if (!build) {
       // no shadow launch this step: the clears ride elsewhere -- the atomics block and d(mean H) at the end of the front
       // kernel's blocks (first use: the back kernel's pooled sums), the operand pad rows in extra blocks of the first backward
       // kernel (first use: the weight-gradient launch)
@@ -664,96 +778,73 @@ int forward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, const 
     }
   }
   fa.qscale = 1.0f / sqrtf(32.0f); fa.save = save ? 1 : 0;
-  fa.s[0] = FrontStream{rg, T, f.Wrg, P[CAMO_P_RG_PROJ_B], f.Wqkv_rg, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, f.X16, f.R16, f.Q16, f.KV2_16, 0};
-  fa.s[1] = FrontStream{kg, TK, f.Wkg, P[CAMO_P_KG_PROJ_B], f.Wqkv_kg, P[CAMO_P_A2_IN_B], P[CAMO_P_A1_IN_B] + H, f.KG16, f.G16, f.Q2_16, f.KV16, 0};
-  fa.stamps = g_dbg_stamps; fa.exp = c.opt.exp;
-  const bool w2 = wide2_taken(c.opt, T, max_nr, save, drop.p > 0.f);
-  const int rt = w2 ? 0 : wide_rt(c.opt, T, max_nr, save);
-  const bool one = w2 || (rt >= 2 && c.opt.fused_one != 0);
-  const int wf_rt = wide_train_front_rt(c.opt, T, max_nr, save);
-  const bool wide_train_front = wf_rt != 0;
-  if (want_tailw && !(one || wide_train_front)) return fail(CAMO_E_ARG, "two-plane tail asked for on a call whose front launch cannot build its weight planes");
-  if ((one || wide_train_front) && want_tailw) {
+  fa.s[0] = FrontStream{x.rg, T, f.Wrg, P[CAMO_P_RG_PROJ_B], f.Wqkv_rg, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, f.X16, f.R16, f.Q16, f.KV2_16, 0};
+  fa.s[1] = FrontStream{x.kg, TK, f.Wkg, P[CAMO_P_KG_PROJ_B], f.Wqkv_kg, P[CAMO_P_A2_IN_B], P[CAMO_P_A1_IN_B] + H, f.KG16, f.G16, f.Q2_16, f.KV16, 0};
+  fa.stamps = g_dbg_stamps; fa.exp = x.opt->exp;
+  if (pl.tail >= CAMO_TAIL_PLANES) {
     // the per-sample tail's weights as hi / lo bf16 planes in fragment order: extra blocks of the (KG rows') wide front launch
-    const size_t HH = (size_t)H * H;
     const float* hsrc[4] = {P[CAMO_P_HEADS], P[CAMO_P_HEADS + 4], P[CAMO_P_HEADS + 8], P[CAMO_P_HEADS + 12]};
-    auto xj = [&](us* dst, int N, int K, const float* src, int lo) {
+    // plane of src (N rows of K columns), or of src^T (transposed: src has K rows of N columns)
+    auto xj = [&](us* dst, int N, int K, int transposed, const float* src, int lo) {
       ShadowJob& J = fa.xjob[fa.nxjob++];
       std::memset(&J, 0, sizeof(J));
-      J.dst = dst; J.N = N; J.K = K; J.nsrc = 1; J.src[0] = src; J.rows[0] = N; J.ld[0] = K; J.lo = lo;
+      J.dst = dst; J.N = N; J.K = K; J.transposed = transposed; J.nsrc = 1; J.src[0] = src; J.rows[0] = transposed ? K : N; J.ld[0] = transposed ? N : K; J.lo = lo;
     };
-    (void)HH;
-    for (int lo = 0; lo < 2; ++lo) {
-      xj(w.f.tailw[0 + lo], H, 2 * H, P[CAMO_P_F1_W3], lo); xj(w.f.tailw[2 + lo], H, 2 * H, P[CAMO_P_F2_W3], lo);
-      xj(w.f.tailw[4 + lo], H, 2 * H, P[CAMO_P_FU_W0], lo); xj(w.f.tailw[6 + lo], H, H, P[CAMO_P_FU_W3], lo);
-    }
-    for (int lo = 0; lo < 2; ++lo) {      // the four heads' first layers [128 x 256] each, stacked
+    // ... of the four heads' first layers [128 x 256] each, stacked: [Wh0_0; ..; Wh0_3] or its transpose (512 source rows of 256 columns)
+    auto xheads = [&](us* dst, int N, int K, int transposed, int lo) {
       ShadowJob& J = fa.xjob[fa.nxjob++];
       std::memset(&J, 0, sizeof(J));
-      J.dst = w.f.tailw[8 + lo]; J.N = 2 * H; J.K = H; J.nsrc = 4; J.lo = lo;
-      for (int x = 0; x < 4; ++x) { J.src[x] = hsrc[x]; J.rows[x] = H / 2; J.ld[x] = H; }
+      J.dst = dst; J.N = N; J.K = K; J.transposed = transposed; J.nsrc = 4; J.lo = lo;
+      for (int h = 0; h < 4; ++h) { J.src[h] = hsrc[h]; J.rows[h] = H / 2; J.ld[h] = H; }
+    };
+    for (int lo = 0; lo < 2; ++lo) {
+      xj(f.tailw[0 + lo], H, 2 * H, 0, P[CAMO_P_F1_W3], lo); xj(f.tailw[2 + lo], H, 2 * H, 0, P[CAMO_P_F2_W3], lo);
+      xj(f.tailw[4 + lo], H, 2 * H, 0, P[CAMO_P_FU_W0], lo); xj(f.tailw[6 + lo], H, H, 0, P[CAMO_P_FU_W3], lo);
     }
-    if (want_tailw > 1) {                   // the transposed planes of the tail's backward (tail_wide.h, TailWideBwdArgs)
-      auto xjT = [&](us* dst, int N, int K, const float* src, int ld, int lo) {      // shadow of src^T: src has K rows of >= N columns
-        ShadowJob& J = fa.xjob[fa.nxjob++];
-        std::memset(&J, 0, sizeof(J));
-        J.dst = dst; J.N = N; J.K = K; J.transposed = 1; J.nsrc = 1; J.src[0] = src; J.rows[0] = K; J.ld[0] = ld; J.lo = lo;
-      };
+    for (int lo = 0; lo < 2; ++lo) xheads(f.tailw[8 + lo], 2 * H, H, 0, lo);
+    if (pl.tail != CAMO_TAIL_PLANES)        // training calls: the transposed planes of the tail's backward (tail_wide.h, TailWideBwdArgs)
       for (int lo = 0; lo < 2; ++lo) {
-        ShadowJob& J = fa.xjob[fa.nxjob++];   // [Wh0_0; ..; Wh0_3]^T: 512 source rows (4 x 128) of 256 columns
-        std::memset(&J, 0, sizeof(J));
-        J.dst = w.f.tailw[10 + lo]; J.N = H; J.K = 2 * H; J.transposed = 1; J.nsrc = 4; J.lo = lo;
-        for (int x = 0; x < 4; ++x) { J.src[x] = hsrc[x]; J.rows[x] = H / 2; J.ld[x] = H; }
-        xjT(w.f.tailw[12 + lo], H, H, P[CAMO_P_FU_W3], H, lo);
-        xjT(w.f.tailw[14 + lo], 2 * H, H, P[CAMO_P_FU_W0], 2 * H, lo);
-        xjT(w.f.tailw[16 + lo], 2 * H, H, P[CAMO_P_F1_W3], 2 * H, lo);
-        xjT(w.f.tailw[18 + lo], 2 * H, H, P[CAMO_P_F2_W3], 2 * H, lo);
+        xheads(f.tailw[10 + lo], H, 2 * H, 1, lo);
+        xj(f.tailw[12 + lo], H, H, 1, P[CAMO_P_FU_W3], lo);
+        xj(f.tailw[14 + lo], 2 * H, H, 1, P[CAMO_P_FU_W0], lo);
+        xj(f.tailw[16 + lo], 2 * H, H, 1, P[CAMO_P_F1_W3], lo);
+        xj(f.tailw[18 + lo], 2 * H, H, 1, P[CAMO_P_F2_W3], lo);
       }
-    }
   }
-  if (one) { fa.split3 = 1; CK(launch_wide_front(fa, 1, st, 1), "fused forward, KG rows' front half (32-row tiles, one in-projection pass per block)"); }
-  else if (rt) CK(launch_wide_front(fa, rt, st, 0), "fused forward, front half (wide tiles)");
-  // (the back half of training calls stays on the 32-row kernel, whose saving + dropout variant is the faster one: 77 vs 94 us at B = 64)
-  else if (wide_train_front)
-    CK(launch_wide_front(fa, wf_rt, st, 0), "fused forward, front half (wide tiles)");
-  else CK(launch_fused_front(fa, c.opt.fused_variant, st), "fused forward, front half");
+  if (pl.front == CAMO_FRONT_KG) { fa.split3 = 1; CK(launch_wide_front(fa, 1, st, 1), "fused forward, KG rows' front half (32-row tiles, one in-projection pass per block)"); }
+  else if (pl.front == CAMO_FRONT_WIDE) CK(launch_wide_front(fa, pl.front_rt, st, 0), "fused forward, front half (wide tiles)");
+  else CK(launch_fused_front(fa, x.opt->fused_variant, st), "fused forward, front half");
   BackArgs ba; std::memset(&ba, 0, sizeof(ba));
   ba.s[0] = BackStream{f.Wo1, P[CAMO_P_A1_OUT_B], f.W1, P[CAMO_P_F1_B0], P[CAMO_P_LN1_W], P[CAMO_P_LN1_B], f.R16,
                        f.O16, f.Y16, f.XH16, f.rstd1, f.mask1, w.Ymean, w.H1mean, SITE_FFN_RG};
   ba.s[1] = BackStream{f.Wo2, P[CAMO_P_A2_OUT_B], f.W2, P[CAMO_P_F2_B0], P[CAMO_P_LN2_W], P[CAMO_P_LN2_B], f.G16,
                        f.O2_16, f.Y2_16, f.XH2_16, f.rstd2, f.mask2, w.Y2mean, w.H2mean, SITE_FFN_KG};
   ba.Q16 = f.Q16; ba.KV16 = f.KV16; ba.Q2_16 = f.Q2_16; ba.KV2_16 = f.KV2_16;
-  ba.off = rg_offsets; ba.tile_off = bd.tile_off; ba.tile_desc = bd.tile_desc; ba.inv_nr = bd.inv_nr; ba.lse2 = f.lse2;
+  ba.off = x.rg_offsets; ba.tile_off = x.bd.tile_off; ba.tile_desc = x.bd.tile_desc; ba.inv_nr = x.bd.inv_nr; ba.lse2 = f.lse2;
   ba.B = B; ba.Nk = Nk; ba.rows_rg = T; ba.rg_tiles_max = T / 32 + B;          // >= sum of ceil(Nr / 32); surplus blocks exit at once
   ba.part = f.part; ba.tickets = w.tickets; ba.max_splits = (max_nr + 63) / 64;
-  ba.drop = drop; ba.save = save ? 1 : 0; ba.exp = c.opt.exp;
+  ba.drop = x.drop; ba.save = save ? 1 : 0; ba.exp = x.opt->exp;
   ba.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)g_dbg_stamp_blocks * 8 : nullptr;
-  // (R16 is read by the row-space form of the projections' weight gradients only; tests that read it back run an inference call with fused_save)
-  if (w2) CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, (!param_space_bwd(c.opt, T) || c.opt.fused_save != 0) ? 1 : 0, st),
-             "fused forward, RG rows in one launch (64-row half-blocks)");
-  else if (one) CK(launch_wide_rgfwd(fa.s[0], fa.qscale, ba, rt, max_nr, st), "fused forward, RG rows in one launch (wide tiles)");
-  else if (rt) CK(launch_wide_back(ba, rt, max_nr, st), "fused forward, back half (wide tiles)");
-  else CK(launch_fused_back(ba, c.opt.fused_variant, c.opt.back_lead, st), "fused forward, back half");
+  switch (pl.back) {
+    case CAMO_BACK_RG_64: CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, pl.save_r16, st), "fused forward, RG rows in one launch (64-row half-blocks)"); break;
+    case CAMO_BACK_RG_WIDE: CK(launch_wide_rgfwd(fa.s[0], fa.qscale, ba, pl.back_rt, max_nr, st), "fused forward, RG rows in one launch (wide tiles)"); break;
+    case CAMO_BACK_WIDE: CK(launch_wide_back(ba, pl.back_rt, max_nr, st), "fused forward, back half (wide tiles)"); break;
+    default: CK(launch_fused_back(ba, x.opt->fused_variant, x.opt->back_lead, st), "fused forward, back half");
+  }
   return 0;
 }
 
-// ---- node-level backward of the fused row-tile schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
-int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
-                     int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st);
-
 // camo_forward_loss_backward's optional event: recorded on the stream as soon as the gradients of the per-sample tail (pooled
 // FFN layers, fusion layer, heads: parameters CAMO_P_F2_W3 .. end of the table, and CAMO_P_F1_W3/B3) are final, so that a
-// data-parallel caller can start reducing that part of the flat buffer while the node-level backward runs.
-int record_tail_event(Call& c, hipStream_t st) {      // (once per call: the first point that reaches it)
-  if (!c.tail_event) return 0;
-  const hipEvent_t ev = c.tail_event; c.tail_event = nullptr;
-  return (int)hipEventRecord(ev, st);
-}
+// data-parallel caller can start reducing that part of the flat buffer while the node-level backward runs.  (camo_plan_t::tail_event
+// names the one point of a call that records it.)
+int record_tail_event(const Call& c, hipStream_t st) { return c.tail_event ? (int)hipEventRecord(c.tail_event, st) : 0; }
 
 // ---- node-level backward of the bf16 schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
-int backward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets,
-                     const int32_t* row_sample, const float* inv_nr, int B, int T, int Nk, int max_nr, const Ws& w,
-                     const DropCfg& drop, hipStream_t st) {
+int backward_nodes16(const Batch& x) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; const DropCfg& drop = x.drop; hipStream_t st = x.st;
+  const int32_t* rg_offsets = x.rg_offsets; const int32_t* row_sample = x.bd.row_sample; const float* inv_nr = x.bd.inv_nr;
+  const int B = x.B, T = x.T, Nk = x.Nk;
   const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, TK = B * Nk, nh = d.num_heads;
   const size_t HH = (size_t)H * H;
   const Ws::H16& h = w.h;
@@ -771,7 +862,7 @@ int backward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P,
     if (rg_side) { p.row_sample = row_sample; p.inv_nr = inv_nr; p.uniform_n = 0; } else { p.row_sample = nullptr; p.inv_nr = nullptr; p.uniform_n = Nk; }
     if (p.flags & GF_A_KMAJOR) p.ldc16 = B;               // (sample count of a weight-gradient problem)
   };
-  GB16 g(drop, c.opt, st);
+  GB16 g(drop, *x.opt, st);
   // first FFN layer: dY = bcast(dpool)/n + dH1.W1 ; dW1 += dH1^T.Y -- and, at hidden_dim 256, the LayerNorm backward
   // dY -> dU (+ dgamma, dbeta) as the epilogue of the dY product (whole-row tiles)
   if (H == 256) {
@@ -831,9 +922,9 @@ int backward_nodes16(const Call& c, const camo_dims_t& d, const float* const* P,
 }
 
 // the per-sample tail of the fused schedule as one launch (misc.hip, tail_fused_kernel); fl == null: forward only
-int tail17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const Ws& w, int B, float* outs, const FusedLoss* fl,
-           const DropCfg& drop, hipStream_t st) {
-  const int H = 256;
+int tail17(Call& c, const Batch& x, float* outs, const FusedLoss* fl) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; hipStream_t st = x.st;
+  const int H = 256, B = x.B;
   TailFusedArgs a; std::memset(&a, 0, sizeof(a));
   a.Ymean = w.Ymean; a.H1mean = w.H1mean; a.Y2mean = w.Y2mean; a.H2mean = w.H2mean;
   a.W13 = P[CAMO_P_F1_W3]; a.b13 = P[CAMO_P_F1_B3]; a.W23 = P[CAMO_P_F2_W3]; a.b23 = P[CAMO_P_F2_B3];
@@ -853,40 +944,68 @@ int tail17(Call& c, const camo_dims_t& d, const float* const* P, float* const* G
   a.outs = outs;
   a.F1sum = w.tailsum; a.hidsum = w.tailsum + (size_t)B * H; a.dF1sum = w.tailsum + (size_t)B * 3 * H;
   a.counters = reinterpret_cast<unsigned int*>(w.tailsum + (size_t)B * 4 * H);
-  a.B = B; a.C = d.num_classes; a.mode = fl ? 1 : 0; a.drop = drop;
+  a.B = B; a.C = d.num_classes; a.mode = fl ? 1 : 0; a.drop = x.drop;
   a.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)4 * g_dbg_stamp_blocks * 8 : nullptr;
   a.debug_skip = c.tail_skip;
-  // training: the kernel leaves copies of the operands of the eight big weight gradients (the heads' hidden layers, fusion layers 3
-  // and 0, the pooled FFN layers), and these gradients to the launches behind it: nothing on the chain to the node-level backward
-  // waits for them
-  const bool groups = fl && B > 16;
+  // training: the kernel leaves copies of the operands of the eight big weight gradients (for_tail_wg), and these gradients to the
+  // launches behind it: nothing on the chain to the node-level backward waits for them
   if (fl) { a.comb_out = w.comb; a.F1_out = w.F1; a.fused_out = w.fused; a.dhid_out = w.dhid; a.dfused_out = w.dfused; a.dF1_out = w.dF1; }
   CK(launch_tail_fused(a, st), "per-sample tail (one launch)");
   c.tail_skip_taken = a.debug_skip != 0;
-  // one group: extra blocks at the end of the node-level backward's first launch, which always follows (forward_loss_backward_impl
-  // -> backward_nodes17), run them on CUs that its row tiles leave idle (a launch of their own would cost ~5 us of floor)
-  c.tail_wg_bwd1 = fl && !groups;
-  if (groups) {
-    // more than one group of 16 samples: the big weight gradients of the tail are sums over every group -- one batched launch
-    // (contraction over the B samples), operands = the copies the tail kernel left in the workspace
-    const int Fh = H / 2;
-    GB g(drop, 0, st);
-    for (int x = 0; x < 4; ++x) g.tn(w.dhid + x * Fh, 4 * Fh, w.fused, H, a.gWh0[x], H, a.gbh0[x], Fh, H, B);
-    g.tn(w.dfused, H, w.F1, H, a.gWfu3, H, a.gbfu3, H, H, B);
-    g.tn(w.dF1, H, w.comb, 2 * H, a.gWfu0, 2 * H, a.gbfu0, H, 2 * H, B);
-    g.tn(w.dcomb, 2 * H, w.H1mean, 2 * H, a.gW13, 2 * H, a.gb13, H, 2 * H, B);
-    g.tn(w.dcomb + H, 2 * H, w.H2mean, 2 * H, a.gW23, 2 * H, a.gb23, H, 2 * H, B);
+  if (x.plan.tail_wg == CAMO_TAIL_WG_LAUNCH) {      // (operands = the copies the tail kernel left in the workspace)
+    GB g(x.drop, 0, st);
+    add_tail_wg(x, g);
     CK(g.run(), "per-sample tail, weight gradients");
   }
   return 0;
 }
 
-int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float* const* Gr, const int32_t* rg_offsets, const Desc& bd,
-                     int B, int T, int Nk, const Ws& w, const DropCfg& drop, hipStream_t st) {
-  const int H = 256, D = 128, TK = B * Nk;
+// the per-sample tail's forward as the one two-plane launch (tail_wide.h), behind a front launch that built its weight planes
+int tail_planes_forward(const Batch& x, float* outs, const FusedLoss* fl) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; const Ws& w = x.w;
+  const bool train = x.plan.tail != CAMO_TAIL_PLANES;
+  TailWideArgs ta; std::memset(&ta, 0, sizeof(ta));
+  ta.Ymean = w.Ymean; ta.H1mean = w.H1mean; ta.Y2mean = w.Y2mean; ta.H2mean = w.H2mean;
+  const us* const* tw = w.f.tailw;
+  ta.T13h = tw[0]; ta.T13l = tw[1]; ta.T23h = tw[2]; ta.T23l = tw[3]; ta.Tfu0h = tw[4]; ta.Tfu0l = tw[5]; ta.Tfu3h = tw[6]; ta.Tfu3l = tw[7]; ta.Th0h = tw[8]; ta.Th0l = tw[9];
+  ta.b13 = P[CAMO_P_F1_B3]; ta.b23 = P[CAMO_P_F2_B3]; ta.bfu0 = P[CAMO_P_FU_B0]; ta.bfu3 = P[CAMO_P_FU_B3];
+  for (int x = 0; x < 4; ++x) { ta.bh0[x] = P[CAMO_P_HEADS + 4 * x + 1]; ta.Wh3[x] = P[CAMO_P_HEADS + 4 * x + 2]; ta.bh3[x] = P[CAMO_P_HEADS + 4 * x + 3]; }
+  ta.outs = outs; ta.B = x.B; ta.C = d.num_classes; ta.drop = x.drop;
+  if (train) { ta.comb_out = w.comb; ta.F1_out = w.F1; ta.fused_out = w.fused; ta.hid_out = w.hid; }
+  CK(launch_tail_wide(ta, x.st), "per-sample tail (wide, one launch)");
+  if (!train) return 0;
+  // (the output layers' weight gradients ride in the tail's weight-gradient launch of the backward half, when that half takes it)
+  return heads_forward(x, CAMO_P_HEADS, d.hidden_dim, outs, fl, /*hidden_done=*/true, /*defer_out_grads=*/x.plan.tail == CAMO_TAIL_PLANES_TRAIN);
+}
+
+// ... and its backward: the tail's input-gradient chain as ONE two-plane launch + ONE launch for its weight gradients
+int tail_planes_backward(const Batch& x) {
+  const camo_dims_t& d = *x.dims; float* const* Gr = x.Gr; const Ws& w = x.w;
+  const int H = d.hidden_dim, B = x.B;
+  TailWideBwdArgs ta; std::memset(&ta, 0, sizeof(ta));
+  const us* const* tw = w.f.tailw;
+  ta.dhid = w.dhid; ta.F1 = w.F1;
+  ta.Th0h = tw[10]; ta.Th0l = tw[11]; ta.Tfu3h = tw[12]; ta.Tfu3l = tw[13]; ta.Tfu0h = tw[14]; ta.Tfu0l = tw[15];
+  ta.T13h = tw[16]; ta.T13l = tw[17]; ta.T23h = tw[18]; ta.T23l = tw[19];
+  ta.dfused = w.dfused; ta.dF1 = w.dF1; ta.dcomb = w.dcomb; ta.dHm1 = w.dHm1; ta.dHm2 = w.dHm2;
+  ta.B = B; ta.scale = x.drop.scale;
+  CK(launch_tail_wide_bwd(ta, x.st), "per-sample tail, input gradients (wide, one launch)");
+  const int Fh = H / 2, C = d.num_classes, Wd = 2 * C + 2, nout[4] = {C, C, 1, 1}, coff[4] = {0, C, 2 * C, 2 * C + 1};
+  float* const* hg = Gr + CAMO_P_HEADS;
+  GB gt = tail_gemms(x);
+  for (int h = 0; h < 4; ++h) gt.tn(w.dlog + coff[h], Wd, w.hid + h * Fh, 4 * Fh, hg[4 * h + 2], Fh, hg[4 * h + 3], nout[h], Fh, B);   // (left by the loss launch)
+  add_tail_wg(x, gt);
+  CK(gt.run(), "per-sample tail, weight gradients");
+  return 0;
+}
+
+// ---- node-level backward of the fused row-tile schedule (w.dcomb, w.dHm1, w.dHm2 hold the pooled gradients) ----
+int backward_nodes17(Call& c, const Batch& x) {
+  const camo_plan_t& pl = x.plan; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; const DropCfg& drop = x.drop; hipStream_t st = x.st;
+  const int32_t* rg_offsets = x.rg_offsets; const Desc& bd = x.bd;
+  const int H = 256, D = 128, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk;
   const size_t HH = (size_t)H * H;
   const Ws::F17& f = w.f;
-  const bool param_space = param_space_bwd(c.opt, T);
   Bwd1Args a1; std::memset(&a1, 0, sizeof(a1));
   a1.s[0] = Bwd1Stream{f.W1T, f.Wo1T, f.mask1, f.XH16, f.rstd1, P[CAMO_P_LN1_W], w.dHm1, 2 * H, w.dcomb, 2 * H, f.dH16, f.dU16,
                        Gr[CAMO_P_LN1_W], Gr[CAMO_P_LN1_B]};
@@ -897,30 +1016,19 @@ int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float
   a1.off = rg_offsets; a1.tile_off = bd.tile_off; a1.tile_desc = bd.tile_desc; a1.inv_nr = bd.inv_nr; a1.row_sample = bd.row_sample;
   a1.B = B; a1.Nk = Nk; a1.rows_rg = T; a1.rg_tiles_max = T / 32 + B; a1.qscale = 1.0f / sqrtf(32.0f); a1.drop = drop;
   a1.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)2 * g_dbg_stamp_blocks * 8 : nullptr;
-  a1.nzero = c.nzero_bwd1; a1.exp = c.opt.exp;
+  a1.nzero = c.nzero_bwd1; a1.exp = x.opt->exp;
   for (int i = 0; i < c.nzero_bwd1; ++i) { a1.zero_ptr[i] = c.zero_bwd1_ptr[i]; a1.zero_bytes[i] = c.zero_bwd1_bytes[i]; }
-  if (c.tail_wg_bwd1) {
-    // the one-launch tail's eight big weight gradients (tail17), from the operand copies it left: dW += dy^T x over the B samples
+  if (pl.tail_wg == CAMO_TAIL_WG_BWD1) {
+    // the one-launch tail's eight big weight gradients (tail17), from the operand copies it left
     TailWgArgs& t = a1.twg;
-    auto prod = [&](const float* dy, int ld_dy, const float* x, int ld_x, float* dW, float* db, int rows, int cols) {
-      t.p[t.n++] = TailWgProd{dy, x, dW, db, ld_dy, ld_x, rows, cols, 0};
-    };
-    const int Fh = H / 2;
-    for (int x = 0; x < 4; ++x) prod(w.dhid + x * Fh, 4 * Fh, w.fused, H, Gr[CAMO_P_HEADS + 4 * x], Gr[CAMO_P_HEADS + 4 * x + 1], Fh, H);
-    prod(w.dfused, H, w.F1, H, Gr[CAMO_P_FU_W3], Gr[CAMO_P_FU_B3], H, H);
-    prod(w.dF1, H, w.comb, 2 * H, Gr[CAMO_P_FU_W0], Gr[CAMO_P_FU_B0], H, 2 * H);
-    prod(w.dcomb, 2 * H, w.H1mean, 2 * H, Gr[CAMO_P_F1_W3], Gr[CAMO_P_F1_B3], H, 2 * H);
-    prod(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], Gr[CAMO_P_F2_B3], H, 2 * H);
+    for_tail_wg(x, [&](const float* dy, int ld_dy, const float* xin, int ld_x, float* dW, float* db, int rows, int cols) {
+      t.p[t.n++] = TailWgProd{dy, xin, dW, db, ld_dy, ld_x, rows, cols, 0};
+    });
     t.B = B;
-    c.tail_wg_bwd1 = false;
   }
-  // the RG rows of the first half on 64-row half-blocks (bwd_wide2.hip) from 16 384 packed rows (training step, ms without / with:
-  // B = 24 0.209 / 0.217, B = 32 0.2395 / 0.237, B = 48 0.307 / 0.301, B = 64 0.355 / 0.349, B = 128 0.632 / 0.615, B = 256 1.007 / 0.944,
-  // B = 1024 3.215 / 2.815) -- behind either forward: the saved set is the same
-  const bool bwd1w = c.opt.wide2_bwd != 0 && (c.opt.wide2_bwd > 0 || (c.opt.fused_rt < 0 && T >= 16384));
-  if (bwd1w) CK(launch_wide2_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half (64-row half-blocks)");
-  else       CK(launch_fused_bwd1(a1, c.opt.fused_variant, st), "fused backward, first half");
-  CK(record_tail_event(c, st), "tail event");      // (the one-launch tail's weight gradients are final behind the launch above)
+  if (pl.bwd1 == CAMO_BWD1_64) CK(launch_wide2_bwd1(a1, x.opt->fused_variant, st), "fused backward, first half (64-row half-blocks)");
+  else                         CK(launch_fused_bwd1(a1, x.opt->fused_variant, st), "fused backward, first half");
+  if (pl.tail_event == CAMO_EVENT_AFTER_BWD1) CK(record_tail_event(c, st), "tail event");      // (the one-launch tail's weight gradients are final behind the launch above)
   Bwd2Args a2; std::memset(&a2, 0, sizeof(a2));
   a2.Q2_16 = f.Q2_16; a2.dO2_16 = f.dO2_16; a2.lse2 = f.lse2; a2.delta2 = f.delta2; a2.KV2_16 = f.KV2_16; a2.dQKV16 = f.dQKV16;
   a2.dU16 = f.dU16; a2.WcRgT = f.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
@@ -928,14 +1036,14 @@ int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float
   a2.tickets = w.tickets + B; a2.off = rg_offsets; a2.tile_off = bd.tile_off; a2.tile_desc = bd.tile_desc;
   a2.B = B; a2.Nk = Nk; a2.rows_rg = T; a2.rg_tiles_max = T / 32 + B; a2.qscale = a1.qscale; a2.drop = drop;
   a2.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)3 * g_dbg_stamp_blocks * 8 : nullptr;
+  const bool param_space = pl.param_space != 0;
   a2.param_space = param_space ? 1 : 0;
-  a2.split_finish = (param_space && bwd1w) ? 1 : 0;        // (by the size rule of the wide first half: the extra launch costs ~2 us)
-  // (wide2_bwd == 2: developer A/B, bwd2p_kernel + bwd2_finish_kernel behind the wide first half)
-  if (a2.split_finish && c.opt.wide2_bwd != 2) CK(launch_wide2_bwd2(a2, st), "fused backward, second half (64-row blocks)");
-  else CK(launch_fused_bwd2(a2, c.opt.fused_variant, st), "fused backward, second half");
+  a2.split_finish = pl.bwd2 != CAMO_BWD2_ROWS32 ? 1 : 0;
+  if (pl.bwd2 == CAMO_BWD2_64) CK(launch_wide2_bwd2(a2, st), "fused backward, second half (64-row blocks)");
+  else CK(launch_fused_bwd2(a2, x.opt->fused_variant, st), "fused backward, second half");
   // every node-level weight gradient: dW += dy^T . x over the rows of a stream (bf16 operands the fused kernels wrote)
   if (!param_space) {
-    GB16 g(drop, c.opt, st);
+    GB16 g(drop, *x.opt, st);
     g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
     g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
     g.tn(f.dQKV16, 3 * H, f.R16, H, Gr[CAMO_P_A1_IN_W], H, Gr[CAMO_P_A1_IN_B], H, H, T);
@@ -956,7 +1064,7 @@ int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float
   // -- 131 k MACs per row (M, dU^T x) instead of 427 k (dR, dQKV^T R, dR^T x), and one small fp32 launch behind them (misc.hip, unfold_kernel).
   float* const Mrg = w.parM; float* const Mkg = Mrg + (size_t)3 * H * D;
   float* const dbrg = Mkg + (size_t)3 * H * D; float* const dbkg = dbrg + 3 * H;
-  GB16 g(drop, c.opt, st);
+  GB16 g(drop, *x.opt, st);
   g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
   g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
   g.tn(f.dQKV16, 3 * H, f.X16, D, Mrg, D, dbrg, H, D, T).bias_grad2 = Gr[CAMO_P_A1_IN_B];
@@ -978,122 +1086,50 @@ int backward_nodes17(Call& c, const camo_dims_t& d, const float* const* P, float
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int camo_abi_version(void) { return CAMO_ABI_VERSION; }
-const char* camo_last_error(void) { return g_err.c_str(); }
-
-size_t camo_workspace_bytes(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk) {
-  if (check_dims(dims, B, T, Nk)) return 0;
-  return carve(*dims, B, T, Nk, nullptr).bytes;
+// ---- LateFusion.forward, fusion_model.py:164-171
+int forward_late(const Batch& x, float* outs, const FusedLoss* fl) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; const Ws& w = x.w; hipStream_t st = x.st;
+  const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, B = x.B, Nk = x.Nk, F = H / 2, Dc = D + Dk;
+  CK((int)hipMemsetAsync(w.zero_base, 0, w.zero_bytes, st), "memset zero block");
+  GB gt = tail_gemms(x);
+  SegMean sm[2] = {{x.rg, D, D, x.rg_offsets, 0, w.comb, Dc}, {x.kg, Dk, Dk, nullptr, Nk, w.comb + D, Dc}};
+  CK(launch_seg_mean(sm, 2, B, x.max_nr > Nk ? x.max_nr : Nk, st), "late means");
+  set_drop(gt.nt(w.comb, Dc, P[CAMO_PL_W0], Dc, P[CAMO_PL_B0], w.F1, H, B, H, Dc, GF_RELU), SITE_LATE0);
+  CK(gt.run(), "late fc0");
+  set_drop(gt.nt(w.F1, H, P[CAMO_PL_W3], H, P[CAMO_PL_B3], w.a2, F, B, F, H, GF_RELU), SITE_LATE0 + 1);
+  CK(gt.run(), "late fc3");
+  gt.nt(w.a2, F, P[CAMO_PL_W6], F, P[CAMO_PL_B6], w.fused, F, B, F, F);
+  CK(gt.run(), "late fc6");
+  return heads_forward(x, CAMO_PL_HEADS, F, outs, fl);
 }
 
-size_t camo_batch_desc_bytes(int32_t B, int32_t T) {
-  if (B < 1 || T < B) { fail(CAMO_E_ARG, "need B >= 1 and T >= B"); return 0; }
-  return desc_carve(B, T, nullptr).bytes;
-}
-
-int camo_prepare_batch(const int32_t* rg_offsets, int32_t B, int32_t T, int32_t max_nr, void* desc, size_t desc_bytes, void* stream) {
-  if (!rg_offsets || !desc || B < 1 || T < B || max_nr < 1 || max_nr > T) return fail(CAMO_E_ARG, "bad prepare_batch arguments");
-  const Desc d = desc_carve(B, T, desc);
-  if (desc_bytes < d.bytes) return fail(CAMO_E_WORKSPACE, "descriptor buffer smaller than camo_batch_desc_bytes()");
-  CK(launch_rowmap(rg_offsets, d.row_sample, d.inv_nr, d.tile_off, d.tile_desc, B, T / 32 + B, max_nr, static_cast<hipStream_t>(stream)), "rowmap");
+int backward_late(const Batch& x, const float* outs, const float* d_outs, int pre_activation, bool heads_out_done) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; const DropCfg& drop = x.drop;
+  const int H = d.hidden_dim, B = x.B, F = H / 2, Dc = d.rg_dim + d.kg_dim;
+  if (int e = heads_backward(x, CAMO_PL_HEADS, F, outs, d_outs, pre_activation, heads_out_done)) return e;
+  GB gt = tail_gemms(x);
+  set_relu_bwd(gt.nn(w.dfused, F, P[CAMO_PL_W6], F, w.da2, F, B, F, F), w.a2, F, drop.scale);
+  gt.tn(w.dfused, F, w.a2, F, Gr[CAMO_PL_W6], F, Gr[CAMO_PL_B6], F, F, B);
+  CK(gt.run(), "late fc6 bwd");
+  set_relu_bwd(gt.nn(w.da2, F, P[CAMO_PL_W3], H, w.dF1, H, B, H, F), w.F1, H, drop.scale);
+  gt.tn(w.da2, F, w.F1, H, Gr[CAMO_PL_W3], H, Gr[CAMO_PL_B3], F, H, B);
+  CK(gt.run(), "late fc3 bwd");
+  gt.tn(w.dF1, H, w.comb, Dc, Gr[CAMO_PL_W0], Dc, Gr[CAMO_PL_B0], H, Dc, B);
+  CK(gt.run(), "late fc0 bwd");
   return 0;
 }
 
-int camo_gather_batch(const float* rg_all, const int64_t* sample_offsets, const float* kg_all, const int64_t* y_all, const float* e_all, const float* s_all,
-                      const int64_t* idx, int32_t B, int32_t T, int32_t rg_dim, int32_t kg_floats, float* rg_out, float* kg_out, int32_t* offsets_out,
-                      int64_t* y_out, float* e_out, float* s_out, float noise_std, uint64_t seed, void* stream) {
-  if (!rg_all || !sample_offsets || !kg_all || !y_all || !e_all || !s_all || !idx || !rg_out || !kg_out || !offsets_out || !y_out || !e_out || !s_out)
-    return fail(CAMO_E_ARG, "null pointer argument");
-  if (B < 1 || T < B) return fail(CAMO_E_ARG, "need B >= 1 and T >= B");
-  if (B > 4096 || rg_dim < 4 || (rg_dim & 3) || rg_dim > 1024 || kg_floats < 2 || (kg_floats & 1) || noise_std < 0.f)
-    return fail(CAMO_E_UNSUPPORTED, "camo_gather_batch: B <= 4096, rg_dim a multiple of 4 (<= 1024), an even number of KG floats per sample");
-  CK(launch_gather_batch(rg_all, reinterpret_cast<const long long*>(sample_offsets), kg_all, reinterpret_cast<const long long*>(y_all), e_all, s_all,
-                         reinterpret_cast<const long long*>(idx), B, T, rg_dim, kg_floats, rg_out, kg_out, offsets_out, reinterpret_cast<long long*>(y_out),
-                         e_out, s_out, noise_std, seed, static_cast<hipStream_t>(stream)), "gather batch");
-  return 0;
-}
-
-static int forward_impl(Call& c, const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
-                        const void* desc,
-                        const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
-                        size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
-                        uint64_t seed, int32_t precision, int32_t flags, void* stream, const FusedLoss* fl,
-                        const FusedLoss* fl17 = nullptr /* given: loss + the whole tail backward ride in the one-launch tail */) {
-  if (int e = check_dims(dims, B, T, Nk)) return e;
-  if (!params || !rg || !rg_offsets || !desc || !kg || !workspace || !outs)
-    return fail(CAMO_E_ARG, "null pointer argument");
-  const Desc bd = desc_carve(B, T, const_cast<void*>(desc));
-  const int32_t* row_sample = bd.row_sample; const float* inv_nr = bd.inv_nr;
-  if (max_nr < 1 || max_nr > T) return fail(CAMO_E_ARG, "max_nr out of range");
-  if (precision != CAMO_PREC_F32 && precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
-  const camo_dims_t& d = *dims;
-  Ws w = carve(d, B, T, Nk, workspace);
-  bind_shadows(c, w);
-  if (workspace_bytes < w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const DropCfg drop = make_drop(training, d.dropout, seed);
-  const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, TK = B * Nk, nh = d.num_heads;
-  const float* const* P = params;
-  GB g(drop, precision, st);
-  GB gt(drop, CAMO_PREC_F32, st);   // per-sample (B-row) GEMMs
-  // one clear of everything this step accumulates into with atomics (means now, dfused/dKV in backward);
-  // the bf16 schedule's prep launch does it along with its casts
-  // calls at the reference configuration that do not ask for attention maps take the fused row-tile schedule
-  const bool use17 = !attn_rg2kg && !attn_kg2rg && !(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(c.opt, d, P, precision, Nk, max_nr);
-  const bool save17 = !(flags & CAMO_FWD_INFERENCE) || c.opt.fused_save != 0;
-  const bool use16 = !use17 && sched16_ok(c.opt, d, P, precision, T, Nk, max_nr);
-  if (!use16 && !use17) CK((int)hipMemsetAsync(w.zero_base, 0, w.zero_bytes, st), "memset zero block");
-
-  if (d.fusion_type == CAMO_FUSION_LATE) {
-    // LateFusion.forward, fusion_model.py:164-171
-    const int F = H / 2, Dc = D + Dk;
-    SegMean sm[2] = {{rg, D, D, rg_offsets, 0, w.comb, Dc}, {kg, Dk, Dk, nullptr, Nk, w.comb + D, Dc}};
-    CK(launch_seg_mean(sm, 2, B, max_nr > Nk ? max_nr : Nk, st), "late means");
-    set_drop(gt.nt(w.comb, Dc, P[CAMO_PL_W0], Dc, P[CAMO_PL_B0], w.F1, H, B, H, Dc, GF_RELU), SITE_LATE0);
-    CK(gt.run(), "late fc0");
-    set_drop(gt.nt(w.F1, H, P[CAMO_PL_W3], H, P[CAMO_PL_B3], w.a2, F, B, F, H, GF_RELU), SITE_LATE0 + 1);
-    CK(gt.run(), "late fc3");
-    gt.nt(w.a2, F, P[CAMO_PL_W6], F, P[CAMO_PL_B6], w.fused, F, B, F, F);
-    CK(gt.run(), "late fc6");
-    return heads_forward(d, P + CAMO_PL_HEADS, w, B, F, outs, gt, fl);
-  }
-
-  // ---- CrossAttentionFusion.forward, fusion_model.py:75-146
-  const float* R = rg; const float* G = kg;
-  if (!P[CAMO_P_RG_PROJ_W] && D != H) return fail(CAMO_E_ARG, "rg_proj weight missing but rg_dim != hidden_dim");
-  if (!P[CAMO_P_KG_PROJ_W] && Dk != H) return fail(CAMO_E_ARG, "kg_proj weight missing but kg_dim != hidden_dim");
+// ---- node-level forward of the general schedule (fp32 operands, any configuration): CrossAttentionFusion.forward, fusion_model.py:75-135
+int forward_nodes_general(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; const Ws& w = x.w; const DropCfg& drop = x.drop; hipStream_t st = x.st;
+  const float* rg = x.rg; const float* kg = x.kg; const int32_t* rg_offsets = x.rg_offsets;
+  const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, nh = d.num_heads, max_nr = x.max_nr;
   const size_t HH2 = (size_t)H * H;
-  if (use17) {
-    const bool tailw = (flags & CAMO_FWD_INFERENCE) && !fl && !fl17 && tailw_taken(c.opt, d, B, T, max_nr, save17, drop.p > 0.f);
-    // training calls on the wide front half with more than 64 samples: the tail's FORWARD as the one two-plane launch (with fp32
-    // copies of what the backward launches read) instead of four fp32 GEMM launches (B = 256: 4 x 27 us -> 34 us); the loss launch
-    // and the backward launches follow as before
-    // (its weight planes are built by extra blocks of the wide front launch: the same predicate as forward_nodes17's)
-    const bool tailw_train = !tailw && fl && !fl17 && save17 && B > 64 && c.opt.tailw != 0 && T >= 4 * 32 * 224 && wide_train_front_rt(c.opt, T, max_nr, save17) != 0 &&
-                             tail_wide_ok(B, d.num_classes) && heads_loss_ok(B, d.num_classes);
-    if (int e = forward_nodes17(c, d, P, rg, rg_offsets, bd, kg, B, T, Nk, max_nr, w, drop, save17, st, tailw_train ? 2 : (tailw ? 1 : 0))) return e;
-    c.tailw_bwd_planes = tailw_train;        // (the backward half of this training call may take the two-plane launch too)
-    if (tailw || tailw_train) {
-      TailWideArgs ta; std::memset(&ta, 0, sizeof(ta));
-      ta.Ymean = w.Ymean; ta.H1mean = w.H1mean; ta.Y2mean = w.Y2mean; ta.H2mean = w.H2mean;
-      const us* const* tw = w.f.tailw;
-      ta.T13h = tw[0]; ta.T13l = tw[1]; ta.T23h = tw[2]; ta.T23l = tw[3]; ta.Tfu0h = tw[4]; ta.Tfu0l = tw[5]; ta.Tfu3h = tw[6]; ta.Tfu3l = tw[7]; ta.Th0h = tw[8]; ta.Th0l = tw[9];
-      ta.b13 = P[CAMO_P_F1_B3]; ta.b23 = P[CAMO_P_F2_B3]; ta.bfu0 = P[CAMO_P_FU_B0]; ta.bfu3 = P[CAMO_P_FU_B3];
-      for (int x = 0; x < 4; ++x) { ta.bh0[x] = P[CAMO_P_HEADS + 4 * x + 1]; ta.Wh3[x] = P[CAMO_P_HEADS + 4 * x + 2]; ta.bh3[x] = P[CAMO_P_HEADS + 4 * x + 3]; }
-      ta.outs = outs; ta.B = B; ta.C = d.num_classes; ta.drop = drop;
-      if (tailw_train) { ta.comb_out = w.comb; ta.F1_out = w.F1; ta.fused_out = w.fused; ta.hid_out = w.hid; }
-      CK(launch_tail_wide(ta, st), "per-sample tail (wide, one launch)");
-      if (!tailw_train) return 0;
-      // (the output layers' weight gradients ride in the tail's weight-gradient launch of the backward half, when that half takes it)
-      return heads_forward(d, P + CAMO_P_HEADS, w, B, H, outs, gt, fl, /*hidden_done=*/true, /*defer_out_grads=*/c.opt.tailw_bwd != 0);
-    }
-  } else if (use16) {
-    if (int e = forward_nodes16(c, d, P, rg, rg_offsets, row_sample, inv_nr, kg, B, T, Nk, max_nr, w, attn_rg2kg, attn_kg2rg, drop, st)) return e;
-  } else {
+  // one clear of everything this step accumulates into with atomics (means now, dfused/dKV in backward);
+  // the other schedules' first launch does it along with its casts / shadows
+  CK((int)hipMemsetAsync(w.zero_base, 0, w.zero_bytes, st), "memset zero block");
+  GB g(drop, x.precision, st);
+  const float* R = rg; const float* G = kg;
   if (P[CAMO_P_KG_PROJ_W]) { g.nt(kg, Dk, P[CAMO_P_KG_PROJ_W], Dk, P[CAMO_P_KG_PROJ_B], w.G, H, TK, H, Dk); G = w.G; }
   if (P[CAMO_P_RG_PROJ_W]) { g.nt(rg, D, P[CAMO_P_RG_PROJ_W], D, P[CAMO_P_RG_PROJ_B], w.R, H, T, H, D); R = w.R; }
   CK(g.run(), "input projections");
@@ -1103,7 +1139,7 @@ static int forward_impl(Call& c, const camo_dims_t* dims, const float* const* pa
   g.nt(G, H, P[CAMO_P_A1_IN_W] + HH2, H, P[CAMO_P_A1_IN_B] + H, w.KV, 2 * H, TK, 2 * H, H);
   g.nt(G, H, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A2_IN_B], w.Q2, H, TK, H, H);
   CK(g.run(), "attention in-projections");
-      CK(launch_attn_rg2kg_fwd(w.Q, w.KV, rg_offsets, w.P, w.O, attn_rg2kg, B, T, max_nr, H, nh, Nk, drop, st), "attn rg2kg fwd");
+  CK(launch_attn_rg2kg_fwd(w.Q, w.KV, rg_offsets, w.P, w.O, attn_rg2kg, B, T, max_nr, H, nh, Nk, drop, st), "attn rg2kg fwd");
   CK(launch_attn_kg2rg_fwd(w.Q2, w.KV2, rg_offsets, w.P2, w.O2, B, max_nr, H, nh, Nk, drop, st), "attn kg2rg fwd");
   if (attn_kg2rg) CK(launch_attn_avg(w.P2, attn_kg2rg, T, nh, Nk, drop, st), "attn avg");
   // out-projection + residual (fusion_model.py:119,130), then LayerNorm
@@ -1119,17 +1155,18 @@ static int forward_impl(Call& c, const camo_dims_t* dims, const float* const* pa
   set_drop(g.nt(w.Y, H, P[CAMO_P_F1_W0], H, P[CAMO_P_F1_B0], w.H1, 2 * H, T, 2 * H, H, GF_RELU), SITE_FFN_RG);
   set_drop(g.nt(w.Y2, H, P[CAMO_P_F2_W0], H, P[CAMO_P_F2_B0], w.H2, 2 * H, TK, 2 * H, H, GF_RELU), SITE_FFN_KG);
   CK(g.run(), "ffn layer 0");
-  }
-  // per-sample means of Y and H1d, then the second FFN layer on the means (mean-pool linearity)
-  if (use17 && (fl17 || ((flags & CAMO_FWD_INFERENCE) && !fl)) && tail17_taken(c.opt, d, B))
-    return tail17(c, d, P, fl17 ? fl17->head_grads - CAMO_P_HEADS : nullptr, w, B, outs, fl17, drop, st);
-  if (use16 || use17) {
-    // accumulated by the kernels that produce the pooled tensors
-  } else {
-    SegMean sm[4] = {{w.Y, H, H, rg_offsets, 0, w.Ymean, H}, {w.H1, 2 * H, 2 * H, rg_offsets, 0, w.H1mean, 2 * H},
-                     {w.Y2, H, H, nullptr, Nk, w.Y2mean, H}, {w.H2, 2 * H, 2 * H, nullptr, Nk, w.H2mean, 2 * H}};
-    CK(launch_seg_mean(sm, 4, B, max_nr > Nk ? max_nr : Nk, st), "pool");
-  }
+  // per-sample means of Y and H1d (the other schedules' kernels accumulate them as they produce the pooled tensors)
+  SegMean sm[4] = {{w.Y, H, H, rg_offsets, 0, w.Ymean, H}, {w.H1, 2 * H, 2 * H, rg_offsets, 0, w.H1mean, 2 * H},
+                   {w.Y2, H, H, nullptr, Nk, w.Y2mean, H}, {w.H2, 2 * H, 2 * H, nullptr, Nk, w.H2mean, 2 * H}};
+  CK(launch_seg_mean(sm, 4, B, max_nr > Nk ? max_nr : Nk, st), "pool");
+  return 0;
+}
+
+// the per-sample tail as fp32 GEMM launches: the second FFN layer on the means (mean-pool linearity), the fusion layer, the heads
+int forward_tail_gemms(const Batch& x, float* outs, const FusedLoss* fl) {
+  const float* const* P = x.P; const Ws& w = x.w;
+  const int H = x.dims->hidden_dim, B = x.B;
+  GB gt = tail_gemms(x);
   set_res(gt.nt(w.H1mean, 2 * H, P[CAMO_P_F1_W3], 2 * H, P[CAMO_P_F1_B3], w.comb, 2 * H, B, H, 2 * H), w.Ymean, H);
   set_res(gt.nt(w.H2mean, 2 * H, P[CAMO_P_F2_W3], 2 * H, P[CAMO_P_F2_B3], w.comb + H, 2 * H, B, H, 2 * H), w.Y2mean, H);
   CK(gt.run(), "ffn layer 3 on pooled rows");
@@ -1138,112 +1175,33 @@ static int forward_impl(Call& c, const camo_dims_t* dims, const float* const* pa
   CK(gt.run(), "fusion layer 0");
   gt.nt(w.F1, H, P[CAMO_P_FU_W3], H, P[CAMO_P_FU_B3], w.fused, H, B, H, H);
   CK(gt.run(), "fusion layer 3");
-  return heads_forward(d, P + CAMO_P_HEADS, w, B, H, outs, gt, fl);
+  return heads_forward(x, CAMO_P_HEADS, H, outs, fl);
 }
 
-int camo_forward(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
-                 const void* batch_desc,
-                 const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
-                 size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
-                 uint64_t seed, int32_t precision, int32_t flags, void* stream) {
-  Call c(dims);
-  c.tail_skip = c.opt.tail_skip_arrival;
-  const int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                              attn_rg2kg, attn_kg2rg, training, seed, precision, flags, stream, nullptr);
-  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
-  return rc;
-}
-
-int camo_forward_cached(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
-                        const void* batch_desc, const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
-                        size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
-                        uint64_t seed, int32_t precision, int32_t flags, void* shadows, int32_t shadows_valid, int32_t* shadows_state,
-                        void* stream) {
-  Call c(dims);
-  if (shadows_state) *shadows_state = 0;
-  if (shadows_valid && !shadows) return fail(CAMO_E_ARG, "shadows_valid without a shadow buffer");
-  // A call that saves for camo_backward would leave the backward's transposed shadows in the caller's buffer, where camo_backward
-  // (which takes no shadow argument) cannot find them, and the clears it defers to the first backward kernel would end with this
-  // call: the training pair is camo_forward_loss_backward, which owns both halves.
-  if (shadows && !(flags & CAMO_FWD_INFERENCE))
-    return fail(CAMO_E_UNSUPPORTED, "camo_forward_cached with a shadow buffer serves inference calls only (flags must contain CAMO_FWD_INFERENCE)");
-  if (shadows && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
-  c.shadows = shadows; c.shadows_valid = shadows && shadows_valid != 0; c.fold_missing = shadows && shadows_valid == 2;
-  c.tail_skip = c.opt.tail_skip_arrival;
-  const int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                              attn_rg2kg, attn_kg2rg, training, seed, precision, flags, stream, nullptr);
-  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
-  if (rc == 0 && shadows_state) *shadows_state = c.shadows_state;
-  return rc;
-}
-
-static int backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
-                         const int32_t* rg_offsets, const void* desc, const float* kg, int32_t B,
-                         int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes, const float* outs,
-                         const float* d_outs, int32_t d_outs_pre_activation, int32_t training, uint64_t seed, int32_t precision,
-                         int32_t flags, void* stream, bool heads_out_done) {
-  if (int e = check_dims(dims, B, T, Nk)) return e;
-  if (!params || !grads || !rg || !rg_offsets || !desc || !kg || !workspace || !outs || (!d_outs && !heads_out_done))
-    return fail(CAMO_E_ARG, "null pointer argument");
-  const Desc bd = desc_carve(B, T, const_cast<void*>(desc));
-  const int32_t* row_sample = bd.row_sample; const float* inv_nr = bd.inv_nr;
-  if (max_nr < 1 || max_nr > T) return fail(CAMO_E_ARG, "max_nr out of range");
-  if (precision != CAMO_PREC_F32 && precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
-  const camo_dims_t& d = *dims;
-  Ws w = carve(d, B, T, Nk, workspace);
-  bind_shadows(c, w);
-  if (workspace_bytes < w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const DropCfg drop = make_drop(training, d.dropout, seed);
-  const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, TK = B * Nk, nh = d.num_heads;
-  const float* const* P = params;
-  float* const* Gr = grads;
-  GB g(drop, precision, st);
-  GB gt(drop, CAMO_PREC_F32, st);   // per-sample (B-row) GEMMs
-
-  if (d.fusion_type == CAMO_FUSION_LATE) {
-    const int F = H / 2, Dc = D + Dk;
-    if (int e = heads_backward(d, P + CAMO_PL_HEADS, Gr + CAMO_PL_HEADS, w, B, F, outs, d_outs, d_outs_pre_activation, drop, st, gt, heads_out_done)) return e;
-    set_relu_bwd(gt.nn(w.dfused, F, P[CAMO_PL_W6], F, w.da2, F, B, F, F), w.a2, F, drop.scale);
-    gt.tn(w.dfused, F, w.a2, F, Gr[CAMO_PL_W6], F, Gr[CAMO_PL_B6], F, F, B);
-    CK(gt.run(), "late fc6 bwd");
-    set_relu_bwd(gt.nn(w.da2, F, P[CAMO_PL_W3], H, w.dF1, H, B, H, F), w.F1, H, drop.scale);
-    gt.tn(w.da2, F, w.F1, H, Gr[CAMO_PL_W3], H, Gr[CAMO_PL_B3], F, H, B);
-    CK(gt.run(), "late fc3 bwd");
-    gt.tn(w.dF1, H, w.comb, Dc, Gr[CAMO_PL_W0], Dc, Gr[CAMO_PL_B0], H, Dc, B);
-    CK(gt.run(), "late fc0 bwd");
-    return 0;
-  }
-
-  const bool has_rgp = P[CAMO_P_RG_PROJ_W] != nullptr, has_kgp = P[CAMO_P_KG_PROJ_W] != nullptr;
-  const float* R = has_rgp ? w.R : rg;
-  const float* G = has_kgp ? w.G : kg;
-  const bool tailw_bwd = c.tailw_bwd_planes && heads_out_done && c.opt.tailw_bwd != 0;
-  if (tailw_bwd) {
-    // the tail's input-gradient chain as ONE two-plane launch (tail_wide.h) + ONE launch for its weight gradients, instead of four
-    // fp32 GEMM launches that each pair an input gradient with a weight gradient (B = 256: 108 us)
-    TailWideBwdArgs ta; std::memset(&ta, 0, sizeof(ta));
-    const us* const* tw = w.f.tailw;
-    ta.dhid = w.dhid; ta.F1 = w.F1;
-    ta.Th0h = tw[10]; ta.Th0l = tw[11]; ta.Tfu3h = tw[12]; ta.Tfu3l = tw[13]; ta.Tfu0h = tw[14]; ta.Tfu0l = tw[15];
-    ta.T13h = tw[16]; ta.T13l = tw[17]; ta.T23h = tw[18]; ta.T23l = tw[19];
-    ta.dfused = w.dfused; ta.dF1 = w.dF1; ta.dcomb = w.dcomb; ta.dHm1 = w.dHm1; ta.dHm2 = w.dHm2;
-    ta.B = B; ta.scale = drop.scale;
-    CK(launch_tail_wide_bwd(ta, st), "per-sample tail, input gradients (wide, one launch)");
-    const int Fh = H / 2;
-    float* const* hg = Gr + CAMO_P_HEADS;
-    {
-      const int C = d.num_classes, Wd = 2 * C + 2, nout[4] = {C, C, 1, 1}, coff[4] = {0, C, 2 * C, 2 * C + 1};
-      for (int x = 0; x < 4; ++x) gt.tn(w.dlog + coff[x], Wd, w.hid + x * Fh, 4 * Fh, hg[4 * x + 2], Fh, hg[4 * x + 3], nout[x], Fh, B);   // (left by the loss launch)
-    }
-    for (int x = 0; x < 4; ++x) gt.tn(w.dhid + x * Fh, 4 * Fh, w.fused, H, hg[4 * x], H, hg[4 * x + 1], Fh, H, B);
-    gt.tn(w.dfused, H, w.F1, H, Gr[CAMO_P_FU_W3], H, Gr[CAMO_P_FU_B3], H, H, B);
-    gt.tn(w.dF1, H, w.comb, 2 * H, Gr[CAMO_P_FU_W0], 2 * H, Gr[CAMO_P_FU_B0], H, 2 * H, B);
-    gt.tn(w.dcomb, 2 * H, w.H1mean, 2 * H, Gr[CAMO_P_F1_W3], 2 * H, Gr[CAMO_P_F1_B3], H, 2 * H, B);
-    gt.tn(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], 2 * H, Gr[CAMO_P_F2_B3], H, 2 * H, B);
-    CK(gt.run(), "per-sample tail, weight gradients");
+// fl: the training call's labels, for the launch that camo_plan_t::loss names (null: no loss in this forward)
+int forward_impl(Call& c, const Batch& x, float* outs, float* attn_rg2kg, float* attn_kg2rg, const FusedLoss* fl) {
+  const camo_dims_t& d = *x.dims;
+  if (x.plan.nodes == CAMO_NODES_LATE) return forward_late(x, outs, fl);
+  if (!x.P[CAMO_P_RG_PROJ_W] && d.rg_dim != d.hidden_dim) return fail(CAMO_E_ARG, "rg_proj weight missing but rg_dim != hidden_dim");
+  if (!x.P[CAMO_P_KG_PROJ_W] && d.kg_dim != d.hidden_dim) return fail(CAMO_E_ARG, "kg_proj weight missing but kg_dim != hidden_dim");
+  if (x.plan.nodes == CAMO_NODES_FUSED) {
+    if (int e = forward_nodes17(c, x)) return e;
+    if (x.plan.tail >= CAMO_TAIL_PLANES) return tail_planes_forward(x, outs, fl);
+    if (x.plan.tail == CAMO_TAIL_ONE_LAUNCH) return tail17(c, x, outs, fl);
+  } else if (x.plan.nodes == CAMO_NODES_BF16) {
+    if (int e = forward_nodes16(x, attn_rg2kg, attn_kg2rg)) return e;
   } else {
-  if (int e = heads_backward(d, P + CAMO_P_HEADS, Gr + CAMO_P_HEADS, w, B, H, outs, d_outs, d_outs_pre_activation, drop, st, gt, heads_out_done)) return e;
+    if (int e = forward_nodes_general(x, attn_rg2kg, attn_kg2rg)) return e;
+  }
+  return forward_tail_gemms(x, outs, fl);
+}
+
+// the per-sample tail's backward as fp32 GEMM launches: heads, fusion layer, pooled second FFN layer
+int backward_tail_gemms(const Batch& x, const float* outs, const float* d_outs, int pre_activation, bool heads_out_done) {
+  const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; const DropCfg& drop = x.drop;
+  const int H = x.dims->hidden_dim, B = x.B;
+  if (int e = heads_backward(x, CAMO_P_HEADS, H, outs, d_outs, pre_activation, heads_out_done)) return e;
+  GB gt = tail_gemms(x);
   // fusion layer
   set_relu_bwd(gt.nn(w.dfused, H, P[CAMO_P_FU_W3], H, w.dF1, H, B, H, H), w.F1, H, drop.scale);
   gt.tn(w.dfused, H, w.F1, H, Gr[CAMO_P_FU_W3], H, Gr[CAMO_P_FU_B3], H, H, B);
@@ -1257,12 +1215,18 @@ static int backward_impl(Call& c, const camo_dims_t* dims, const float* const* p
   gt.tn(w.dcomb, 2 * H, w.H1mean, 2 * H, Gr[CAMO_P_F1_W3], 2 * H, Gr[CAMO_P_F1_B3], H, 2 * H, B);
   gt.tn(w.dcomb + H, 2 * H, w.H2mean, 2 * H, Gr[CAMO_P_F2_W3], 2 * H, Gr[CAMO_P_F2_B3], H, 2 * H, B);
   CK(gt.run(), "ffn layer 3 bwd (pooled)");
-  }
-  CK(record_tail_event(c, st), "tail event");
-  if (!(flags & CAMO_FLAG_ATTN_MAPS) && fused17_ok(c.opt, d, P, precision, Nk, max_nr))
-    return backward_nodes17(c, d, P, Gr, rg_offsets, bd, B, T, Nk, w, drop, st);
-  if (sched16_ok(c.opt, d, P, precision, T, Nk, max_nr))
-    return backward_nodes16(c, d, P, Gr, rg_offsets, row_sample, inv_nr, B, T, Nk, max_nr, w, drop, st);
+  return 0;
+}
+
+// ---- node-level backward of the general schedule
+int backward_nodes_general(const Batch& x) {
+  const camo_dims_t& d = *x.dims; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; const DropCfg& drop = x.drop; hipStream_t st = x.st;
+  const float* rg = x.rg; const float* kg = x.kg; const int32_t* rg_offsets = x.rg_offsets; const int32_t* row_sample = x.bd.row_sample; const float* inv_nr = x.bd.inv_nr;
+  const int H = d.hidden_dim, D = d.rg_dim, Dk = d.kg_dim, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, nh = d.num_heads, max_nr = x.max_nr;
+  const bool has_rgp = P[CAMO_P_RG_PROJ_W] != nullptr, has_kgp = P[CAMO_P_KG_PROJ_W] != nullptr;
+  const float* R = has_rgp ? w.R : rg;
+  const float* G = has_kgp ? w.G : kg;
+  GB g(drop, x.precision, st);
   {
     BcastSeg s0{w.H1, w.dHm1, 2 * H, row_sample, inv_nr, 0, w.dH1, T};
     BcastSeg s1{w.H2, w.dHm2, 2 * H, nullptr, nullptr, Nk, w.dH2, TK};
@@ -1305,21 +1269,103 @@ static int backward_impl(Call& c, const camo_dims_t* dims, const float* const* p
   return 0;
 }
 
+int backward_impl(Call& c, const Batch& x, const float* outs, const float* d_outs, int pre_activation, bool heads_out_done) {
+  if (x.plan.nodes == CAMO_NODES_LATE) return backward_late(x, outs, d_outs, pre_activation, heads_out_done);
+  if (x.plan.tail == CAMO_TAIL_PLANES_TRAIN) { if (int e = tail_planes_backward(x)) return e; }
+  else if (int e = backward_tail_gemms(x, outs, d_outs, pre_activation, heads_out_done)) return e;
+  if (x.plan.tail_event == CAMO_EVENT_BEFORE_NODES) CK(record_tail_event(c, x.st), "tail event");
+  if (x.plan.nodes == CAMO_NODES_FUSED) return backward_nodes17(c, x);
+  if (x.plan.nodes == CAMO_NODES_BF16) return backward_nodes16(x);
+  return backward_nodes_general(x);
+}
+
+}  // namespace
+
+extern "C" {
+
+int camo_abi_version(void) { return CAMO_ABI_VERSION; }
+const char* camo_last_error(void) { return g_err.c_str(); }
+
+size_t camo_workspace_bytes(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk) {
+  if (check_dims(dims, B, T, Nk)) return 0;
+  return carve(*dims, B, T, Nk, nullptr).bytes;
+}
+
+size_t camo_batch_desc_bytes(int32_t B, int32_t T) {
+  if (B < 1 || T < B) { fail(CAMO_E_ARG, "need B >= 1 and T >= B"); return 0; }
+  return desc_carve(B, T, nullptr).bytes;
+}
+
+int camo_prepare_batch(const int32_t* rg_offsets, int32_t B, int32_t T, int32_t max_nr, void* desc, size_t desc_bytes, void* stream) {
+  if (!rg_offsets || !desc || B < 1 || T < B || max_nr < 1 || max_nr > T) return fail(CAMO_E_ARG, "bad prepare_batch arguments");
+  const Desc d = desc_carve(B, T, desc);
+  if (desc_bytes < d.bytes) return fail(CAMO_E_WORKSPACE, "descriptor buffer smaller than camo_batch_desc_bytes()");
+  CK(launch_rowmap(rg_offsets, d.row_sample, d.inv_nr, d.tile_off, d.tile_desc, B, T / 32 + B, max_nr, static_cast<hipStream_t>(stream)), "rowmap");
+  return 0;
+}
+
+int camo_gather_batch(const float* rg_all, const int64_t* sample_offsets, const float* kg_all, const int64_t* y_all, const float* e_all, const float* s_all,
+                      const int64_t* idx, int32_t B, int32_t T, int32_t rg_dim, int32_t kg_floats, float* rg_out, float* kg_out, int32_t* offsets_out,
+                      int64_t* y_out, float* e_out, float* s_out, float noise_std, uint64_t seed, void* stream) {
+  if (!rg_all || !sample_offsets || !kg_all || !y_all || !e_all || !s_all || !idx || !rg_out || !kg_out || !offsets_out || !y_out || !e_out || !s_out)
+    return fail(CAMO_E_ARG, "null pointer argument");
+  if (B < 1 || T < B) return fail(CAMO_E_ARG, "need B >= 1 and T >= B");
+  if (B > 4096 || rg_dim < 4 || (rg_dim & 3) || rg_dim > 1024 || kg_floats < 2 || (kg_floats & 1) || noise_std < 0.f)
+    return fail(CAMO_E_UNSUPPORTED, "camo_gather_batch: B <= 4096, rg_dim a multiple of 4 (<= 1024), an even number of KG floats per sample");
+  CK(launch_gather_batch(rg_all, reinterpret_cast<const long long*>(sample_offsets), kg_all, reinterpret_cast<const long long*>(y_all), e_all, s_all,
+                         reinterpret_cast<const long long*>(idx), B, T, rg_dim, kg_floats, rg_out, kg_out, offsets_out, reinterpret_cast<long long*>(y_out),
+                         e_out, s_out, noise_std, seed, static_cast<hipStream_t>(stream)), "gather batch");
+  return 0;
+}
+
+int camo_forward(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
+                 const void* batch_desc,
+                 const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
+                 size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
+                 uint64_t seed, int32_t precision, int32_t flags, void* stream) {
+  return camo_forward_cached(dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs, attn_rg2kg, attn_kg2rg,
+                             training, seed, precision, flags, nullptr, 0, nullptr, stream);
+}
+
+int camo_forward_cached(const camo_dims_t* dims, const float* const* params, const float* rg, const int32_t* rg_offsets,
+                        const void* batch_desc, const float* kg, int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace,
+                        size_t workspace_bytes, float* outs, float* attn_rg2kg, float* attn_kg2rg, int32_t training,
+                        uint64_t seed, int32_t precision, int32_t flags, void* shadows, int32_t shadows_valid, int32_t* shadows_state,
+                        void* stream) {
+  Call c;
+  if (shadows_state) *shadows_state = 0;
+  if (shadows_valid && !shadows) return fail(CAMO_E_ARG, "shadows_valid without a shadow buffer");
+  // A call that saves for camo_backward would leave the backward's transposed shadows in the caller's buffer, where camo_backward
+  // (which takes no shadow argument) cannot find them, and the clears it defers to the first backward kernel would end with this
+  // call: the training pair is camo_forward_loss_backward, which owns both halves.
+  if (shadows && !(flags & CAMO_FWD_INFERENCE))
+    return fail(CAMO_E_UNSUPPORTED, "camo_forward_cached with a shadow buffer serves inference calls only (flags must contain CAMO_FWD_INFERENCE)");
+  if (shadows && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
+  if (int e = check_dims(dims, B, T, Nk)) return e;
+  Batch x{dims, params, nullptr, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, training, seed, precision, static_cast<hipStream_t>(stream)};
+  plan_batch(x, (flags & CAMO_FWD_INFERENCE) ? CALL_INFERENCE : CALL_FORWARD_SAVE, attn_rg2kg || attn_kg2rg || (flags & CAMO_FLAG_ATTN_MAPS));
+  // (a call that takes a schedule without shadows leaves the caller's buffer alone: a promise is then simply not used)
+  if (x.plan.shadows) { c.shadows = shadows; c.shadows_valid = shadows && shadows_valid != 0; c.fold_missing = shadows && shadows_valid == 2; }
+  if (int e = open_batch(x, c, outs != nullptr)) return e;
+  c.tail_skip = x.opt->tail_skip_arrival;
+  const int rc = forward_impl(c, x, outs, attn_rg2kg, attn_kg2rg, nullptr);
+  if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
+  if (rc == 0 && shadows_state) *shadows_state = c.shadows_state;
+  return rc;
+}
+
 int camo_backward(const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                   const int32_t* rg_offsets, const void* batch_desc, const float* kg, int32_t B,
                   int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes, const float* outs,
                   const float* d_outs, int32_t d_outs_pre_activation, int32_t training, uint64_t seed, int32_t precision,
                   int32_t flags, void* stream) {
-  Call c(dims);
-  return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                       d_outs, d_outs_pre_activation, training, seed, precision, flags, stream, false);
+  Call c;
+  if (int e = check_dims(dims, B, T, Nk)) return e;
+  Batch x{dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, training, seed, precision, static_cast<hipStream_t>(stream)};
+  plan_batch(x, CALL_BACKWARD, (flags & CAMO_FLAG_ATTN_MAPS) != 0);
+  if (int e = open_batch(x, c, grads && outs && d_outs)) return e;
+  return backward_impl(c, x, outs, d_outs, d_outs_pre_activation, false);
 }
-
-static int forward_loss_backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
-                               const int32_t* rg_offsets, const void* batch_desc, const float* kg,
-                               int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes,
-                               const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
-                               int32_t training, uint64_t seed, int32_t precision, void* stream);
 
 int camo_forward_loss_backward(const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
                                const int32_t* rg_offsets, const void* batch_desc, const float* kg,
@@ -1327,59 +1373,40 @@ int camo_forward_loss_backward(const camo_dims_t* dims, const float* const* para
                                const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
                                int32_t training, uint64_t seed, int32_t precision, void* tail_event, void* shadows,
                                int32_t shadows_valid, void* stream) {
-  Call c(dims);
+  Call c;
   if (!dims || !grads || !y || !e || !s || !outs || !loss_terms) return fail(CAMO_E_ARG, "null pointer argument");
   if (shadows_valid && !shadows) return fail(CAMO_E_ARG, "shadows_valid without a shadow buffer");
+  if (int rc = check_dims(dims, B, T, Nk)) return rc;
+  Batch x{dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, training, seed, precision, static_cast<hipStream_t>(stream)};
+  plan_batch(x, CALL_TRAIN, false);
   // external shadows are used by the fused schedule only; whether the call takes it is known from its arguments
-  const bool ext = shadows && params && !check_dims(dims, B, T, Nk) && fused17_ok(c.opt, *dims, params, precision, Nk, max_nr);
   // (a call that takes another schedule -- Nk > 16, a 5000-node sample, ... -- builds what it needs in its workspace and leaves the
   // external shadows alone: the promise is simply not used)
-  if (ext && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
-  c.shadows = ext ? shadows : nullptr; c.shadows_valid = ext && shadows_valid != 0;
+  if (shadows && x.plan.shadows) {
+    if (reinterpret_cast<uintptr_t>(shadows) & 255) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
+    c.shadows = shadows; c.shadows_valid = shadows_valid != 0;
+  }
+  if (int rc = open_batch(x, c, true)) return rc;
   c.tail_event = static_cast<hipEvent_t>(tail_event);
-  c.tail_skip = c.opt.tail_skip_arrival;
-  const int rc = forward_loss_backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace,
-                                            workspace_bytes, y, e, s, outs, loss_terms, pred, training, seed, precision, stream);
+  c.tail_skip = x.opt->tail_skip_arrival;
+  const camo_plan_t& pl = x.plan;
+  const FusedLoss fl{y, e, s, loss_terms, pred};
+  int rc = forward_impl(c, x, outs, nullptr, nullptr, pl.loss == CAMO_LOSS_LAUNCH ? nullptr : &fl);
   if (c.tail_skip_taken) dims->options->tail_skip_arrival = 0;
-  if (rc == 0) { CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event"); }   // (schedules without an early point)
-  return rc;
-}
-
-static int forward_loss_backward_impl(Call& c, const camo_dims_t* dims, const float* const* params, float* const* grads, const float* rg,
-                               const int32_t* rg_offsets, const void* batch_desc, const float* kg,
-                               int32_t B, int32_t T, int32_t Nk, int32_t max_nr, void* workspace, size_t workspace_bytes,
-                               const int64_t* y, const float* e, const float* s, float* outs, float* loss_terms, int32_t* pred,
-                               int32_t training, uint64_t seed, int32_t precision, void* stream) {
-  const int head0 = dims->fusion_type == CAMO_FUSION_LATE ? CAMO_PL_HEADS : CAMO_P_HEADS;
-  const bool fuse = heads_loss_ok(B, dims->num_classes);
-  if (params && !check_dims(dims, B, T, Nk) && fused17_ok(c.opt, *dims, params, precision, Nk, max_nr) && tail17_taken(c.opt, *dims, B)) {
+  if (rc) return rc;
+  if (pl.loss == CAMO_LOSS_TAIL) {
     // fused schedule + one-launch tail: node-level forward, [tail forward + loss + tail backward], node-level backward
-    const FusedLoss fl{y, e, s, loss_terms, pred, grads + head0};
-    if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                              nullptr, nullptr, training, seed, precision, 0, stream, nullptr, &fl)) return rc;
-    Ws w = carve(*dims, B, T, Nk, workspace);
-    bind_shadows(c, w);
-    const Desc bd = desc_carve(B, T, const_cast<void*>(batch_desc));
-    // the tail event; with one group of samples, behind backward_nodes17's first launch, which finishes the tail's weight gradients
-    if (!c.tail_wg_bwd1) CK(record_tail_event(c, static_cast<hipStream_t>(stream)), "tail event");
-    return backward_nodes17(c, *dims, params, grads, rg_offsets, bd, B, T, Nk, w, make_drop(training, dims->dropout, seed),
-                            static_cast<hipStream_t>(stream));
+    if (pl.tail_event == CAMO_EVENT_BEFORE_NODES) CK(record_tail_event(c, x.st), "tail event");
+    rc = backward_nodes17(c, x);
+  } else if (pl.loss == CAMO_LOSS_HEADS) {
+    rc = backward_impl(c, x, outs, nullptr, 1, true);
+  } else {
+    // large batches / many classes: the three steps as separate launches, d(loss)/d(pre-activation) staged in the workspace
+    CK(launch_loss(outs, reinterpret_cast<const long long*>(y), e, s, B, dims->num_classes, loss_terms, nullptr, x.w.dlog, pred, x.st), "loss");
+    rc = backward_impl(c, x, outs, x.w.dlog, 1, false);
   }
-  if (fuse) {
-    const FusedLoss fl{y, e, s, loss_terms, pred, grads + head0};
-    if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                              nullptr, nullptr, training, seed, precision, 0, stream, &fl)) return rc;
-    return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
-                         outs, nullptr, 1, training, seed, precision, 0, stream, true);
-  }
-  // large batches / many classes: the three steps as separate launches, d(loss)/d(pre-activation) staged in the workspace
-  if (int rc = forward_impl(c, dims, params, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, outs,
-                            nullptr, nullptr, training, seed, precision, 0, stream, nullptr)) return rc;
-  const Ws w = carve(*dims, B, T, Nk, workspace);
-  CK(launch_loss(outs, reinterpret_cast<const long long*>(y), e, s, B, dims->num_classes, loss_terms, nullptr, w.dlog, pred,
-                 static_cast<hipStream_t>(stream)), "loss");
-  return backward_impl(c, dims, params, grads, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes,
-                       outs, w.dlog, 1, training, seed, precision, 0, stream, false);
+  if (rc == 0 && pl.tail_event == CAMO_EVENT_END) CK(record_tail_event(c, x.st), "tail event");   // (schedules without an early point)
+  return rc;
 }
 
 int camo_loss(const float* outs, const int64_t* y, const float* e, const float* s, int32_t B, int32_t num_classes,
@@ -1566,6 +1593,19 @@ int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int3
   for (const auto& e : tab)
     if (std::strcmp(e.n, name) == 0 && e.p) return static_cast<const char*>(e.p) - base;
   return -1;
+}
+
+int camo_debug_plan(const camo_dims_t* dims, int32_t has_projections, int32_t B, int32_t T, int32_t Nk, int32_t max_nr,
+                    int32_t precision, int32_t flags, int32_t call_kind, int32_t cus, camo_plan_t* out) {
+  if (int e = check_dims(dims, B, T, Nk)) return e;
+  if (!out) return fail(CAMO_E_ARG, "null pointer argument");
+  if (max_nr < 1 || max_nr > T) return fail(CAMO_E_ARG, "max_nr out of range");
+  if (precision != CAMO_PREC_F32 && precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
+  if (call_kind != CAMO_CALL_FORWARD && call_kind != CAMO_CALL_BACKWARD && call_kind != CAMO_CALL_TRAIN) return fail(CAMO_E_ARG, "unknown call kind");
+  const CallKind kind = call_kind == CAMO_CALL_TRAIN ? CALL_TRAIN : (call_kind == CAMO_CALL_BACKWARD ? CALL_BACKWARD : ((flags & CAMO_FWD_INFERENCE) ? CALL_INFERENCE : CALL_FORWARD_SAVE));
+  *out = make_plan(PlanIn{options_of(dims), *dims, (has_projections & 1) != 0, (has_projections & 2) != 0, precision, B, T, Nk, max_nr, kind,
+                          kind != CALL_TRAIN && (flags & CAMO_FLAG_ATTN_MAPS) != 0, cus < 0 ? device_cus() : cus});
+  return 0;
 }
 
 

@@ -75,7 +75,9 @@ struct TailFusedArgs {
                                                             // first arrival, so the others' wait times out deterministically -- the only way
                                                             // to test the give-up path without sharing the GPU.  0 in product calls
 };
-int tail_fused_ok(int B, int C);
+int tail_fused_ok(int B, int C);             // on this device: tail_fused_ok(B, C, device_cus())
+int tail_fused_ok(int B, int C, int cus);    // the same rule for a device of `cus` compute units (touches no device)
+int device_cus();                            // compute units of the device (or partition) this process sees; queried once
 int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream);
 int tail_timeouts(unsigned int* out);
 int launch_tail_poison_to_grads(float* g, hipStream_t stream);      // data parallel: a pending tail timeout -> NaN in g[0] (misc.hip)

@@ -1443,12 +1443,16 @@ int launch_heads_loss(const float* hid, const HeadsOut& hp, const long long* y, 
   return (int)hipGetLastError();
 }
 
-int tail_fused_ok(int B, int C) {
+int device_cus() {
+  static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
+  return cus;
+}
+int tail_fused_ok(int B, int C, int cus) {
   // every block of the launch waits for the other 63: all of them must be resident at once, one per CU (1024 threads, 148 KB of
   // LDS), so the device (or the partition this process sees) must have at least that many CUs
-  static const int cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   return B >= 1 && B <= TF_MAXGROUPS * TF_MAXB && C >= 1 && 2 * C + 2 <= TF_MAXW && cus >= TG * ((B + TF_MAXB - 1) / TF_MAXB);
 }
+int tail_fused_ok(int B, int C) { return tail_fused_ok(B, C, device_cus()); }
 int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream) {
   if (!tail_fused_ok(a.B, a.C)) return (int)hipErrorInvalidValue;
   if (a.mode && (!a.comb_out || !a.F1_out || !a.fused_out || !a.dhid_out || !a.dfused_out || !a.dF1_out)) return (int)hipErrorInvalidValue;

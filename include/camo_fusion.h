@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CAMO_ABI_VERSION 10
+#define CAMO_ABI_VERSION 11
 
 enum {
   CAMO_OK = 0,
@@ -282,6 +282,65 @@ int camo_debug_gemm16(const void* A16, int32_t lda, const void* B16, int32_t ldb
                       void* C16, int32_t ldc16, const float* bias, const float* res, int32_t ldr, float* bias_grad,
                       int32_t M, int32_t N, int32_t K, int32_t flags, void* stream);
 int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk, const char* name);
+/* camo_debug_plan: the launch schedule a call with these arguments takes, without launching anything: the
+ * library decides it once per call, in one function of the caller's options (dims->options), the dims and the arguments below, and
+ * this entry runs that function.  tests/test_schedule_plan.py pins its table.
+ *   has_projections  bit 0: the rg_proj weight is present (params[CAMO_P_RG_PROJ_W] != NULL), bit 1: the kg_proj weight
+ *   flags            CAMO_FWD_INFERENCE as on camo_forward; CAMO_FLAG_ATTN_MAPS: attention maps are wanted (a forward that is
+ *                    given attention-map pointers, or camo_backward with that flag)
+ *                    (ignored for CAMO_CALL_TRAIN: camo_forward_loss_backward has no such argument)
+ *   call_kind        CAMO_CALL_*: which entry point
+ *   cus              compute units of the device (the one-launch tail needs 64 co-resident blocks per group of 16 samples);
+ *                    < 0: ask the current device.  With cus >= 0 the call touches no device and needs none.
+ * Validates like camo_forward.  Fields that describe launches the call does not make are 0; every field but `nodes` is 0
+ * unless nodes == CAMO_NODES_FUSED, except `loss` and `tail_event`, which every camo_forward_loss_backward has. */
+enum { CAMO_CALL_FORWARD = 0,      /* camo_forward / camo_forward_cached                                   */
+       CAMO_CALL_BACKWARD = 1,     /* camo_backward                                                          */
+       CAMO_CALL_TRAIN = 2         /* camo_forward_loss_backward                                             */ };
+enum { CAMO_NODES_LATE = 0,        /* late fusion: no node-level kernels                                     */
+       CAMO_NODES_GENERAL = 1,     /* fp32-operand GEMMs + attention kernels (any configuration)             */
+       CAMO_NODES_BF16 = 2,        /* bf16-resident GEMM schedule (csrc/gemm16.h)                            */
+       CAMO_NODES_FUSED = 3        /* fused row-tile schedule (csrc/fused_rows.h), reference configuration  */ };
+enum { CAMO_FRONT_ROWS32 = 0,      /* front_kernel: 32-row tiles                                             */
+       CAMO_FRONT_WIDE = 1,        /* wide front half, front_rt x 32 rows per block (csrc/fused_wide.hip)    */
+       CAMO_FRONT_KG = 2           /* the KG rows' front half alone; the RG rows' is part of the back launch */ };
+enum { CAMO_BACK_ROWS32 = 0,       /* back_kernel: 32-row tiles                                              */
+       CAMO_BACK_WIDE = 1,         /* wide back half, back_rt x 32 rows per block                            */
+       CAMO_BACK_RG_WIDE = 2,      /* the RG rows' whole forward in one launch of wide tiles (back_rt)       */
+       CAMO_BACK_RG_64 = 3         /* ... of 64-row half-blocks (csrc/fused_wide2.hip)                       */ };
+enum { CAMO_TAIL_GEMMS = 0,        /* the per-sample tail as fp32 GEMM launches                              */
+       CAMO_TAIL_ONE_LAUNCH = 1,   /* tail_fused_kernel (training calls: with the loss and the tail's backward) */
+       CAMO_TAIL_PLANES = 2,       /* inference: the two-plane launch (csrc/tail_wide.h)                     */
+       CAMO_TAIL_PLANES_TRAIN_FWD = 3, /* training: two-plane forward, GEMM backward (option tailw_bwd = 0) */
+       CAMO_TAIL_PLANES_TRAIN = 4  /* training: two-plane forward and backward                               */ };
+enum { CAMO_TAIL_WG_NONE = 0,      /* the one-launch tail's eight big weight gradients (training calls):     */
+       CAMO_TAIL_WG_BWD1 = 1,      /* extra blocks of the node-level backward's first launch (one group)     */
+       CAMO_TAIL_WG_LAUNCH = 2     /* one batched GEMM launch behind the tail (several groups of 16 samples) */ };
+enum { CAMO_LOSS_NONE = 0,         /* not a training call                                                    */
+       CAMO_LOSS_TAIL = 1,         /* inside the one-launch tail                                             */
+       CAMO_LOSS_HEADS = 2,        /* heads_loss_kernel: head output layer + loss + its backward             */
+       CAMO_LOSS_LAUNCH = 3        /* loss_kernel, between forward and backward                              */ };
+enum { CAMO_EVENT_NONE = 0,        /* where camo_forward_loss_backward records tail_event:                   */
+       CAMO_EVENT_BEFORE_NODES = 1,/* behind the tail's backward, in front of the node-level backward        */
+       CAMO_EVENT_AFTER_BWD1 = 2,  /* behind the node-level backward's first launch (CAMO_TAIL_WG_BWD1)      */
+       CAMO_EVENT_END = 3          /* at the end of the call (late fusion)                                   */ };
+enum { CAMO_BWD1_ROWS32 = 0, CAMO_BWD1_64 = 1 };           /* bwd1_kernel / bwd1w_kernel (csrc/bwd_wide2.hip)  */
+enum { CAMO_BWD2_ROWS32 = 0,       /* bwd2_kernel (row space) or bwd2p_kernel (parameter space)              */
+       CAMO_BWD2_ROWS32_SPLIT = 1, /* bwd2p_kernel + bwd2_finish_kernel (option wide2_bwd = 2)               */
+       CAMO_BWD2_64 = 2            /* bwd2w_kernel + bwd2_finish_kernel                                      */ };
+typedef struct camo_plan {
+  int32_t nodes;        /* CAMO_NODES_*                                                                       */
+  int32_t shadows;      /* 1: the call keeps its weight shadows in the caller's shadow buffer when given one  */
+  int32_t save;         /* 1: the fused forward writes what a backward reads                                  */
+  int32_t front, front_rt;  /* CAMO_FRONT_*, 32-row sub-tiles per block (CAMO_FRONT_WIDE)                     */
+  int32_t back, back_rt;    /* CAMO_BACK_*, 32-row sub-tiles per block (CAMO_BACK_WIDE, CAMO_BACK_RG_WIDE)    */
+  int32_t save_r16;     /* CAMO_BACK_RG_64: 1 = it stores R16 (operand of the row-space weight gradients)     */
+  int32_t tail, tail_wg, loss, tail_event;   /* CAMO_TAIL_*, CAMO_TAIL_WG_*, CAMO_LOSS_*, CAMO_EVENT_*        */
+  int32_t param_space;  /* backward: 1 = projection / in-projection weight gradients in parameter space      */
+  int32_t bwd1, bwd2;   /* CAMO_BWD1_*, CAMO_BWD2_*                                                           */
+} camo_plan_t;
+int camo_debug_plan(const camo_dims_t* dims, int32_t has_projections, int32_t B, int32_t T, int32_t Nk, int32_t max_nr,
+                    int32_t precision, int32_t flags, int32_t call_kind, int32_t cus, camo_plan_t* out);
 /* camo_options_init: every field to its default.  camo_options_set: one field by name (CAMO_E_ARG for an unknown name). */
 int camo_options_init(camo_options_t* options);
 int camo_options_set(camo_options_t* options, const char* name, int32_t value);

@@ -235,7 +235,7 @@ def _long_plus(n_long, n_short, at, base=440):
 @pytest.mark.parametrize("max_nr", [2944, 2945])
 def test_bf16_training_wide_front_max_nr_limit(max_nr, kg_real):
     """Training at 16 384 <= T < 28 672 (31 samples: one long, 30 of ~450 rows): the front half runs on 64-row blocks
-    (wide_train_front_rt: 2 sub-tiles from 10 240 rows) while max_nr <= wide_max_rows(2) - 64 * 2 = 32 * 2 * 48 - 128 = 2944;
+    (make_plan's wide front: 2 sub-tiles from 10 240 rows) while max_nr <= wide_max_rows(2) - 64 * 2 = 32 * 2 * 48 - 128 = 2944;
     at 2945 it falls back to the 32-row front_kernel.  From 16 384 rows the first backward half is bwd1w_kernel / bwd2w_kernel on
     64-row half-blocks, where the long sample spans ~46 of them."""
     nrs = _long_plus(max_nr, 30, 0 if max_nr == 2944 else 30)
@@ -245,7 +245,7 @@ def test_bf16_training_wide_front_max_nr_limit(max_nr, kg_real):
 
 def test_bf16_training_128row_front_4096_row_sample(kg_real):
     """Training at 28 672 <= T < 57 344 with B = 60 and one 4 096-row sample (the fused schedule's limit, 64 x FUSED_MAX_SPLITS):
-    the 128-row front (wide_train_front_rt: 4 sub-tiles from 4 x 32 x 224 rows; 4096 <= wide_max_rows(4) - 256) and, at
+    the 128-row front (make_plan's wide front: 4 sub-tiles from 4 x 32 x 224 rows; 4096 <= wide_max_rows(4) - 256) and, at
     49 <= B <= 64 with no wide forward to build the two-plane tail's weight planes, the nine-launch tail."""
     nrs = _long_plus(4096, 59, 17)
     assert 28672 <= sum(nrs) < 57344 and 49 <= len(nrs) <= 64
@@ -254,7 +254,7 @@ def test_bf16_training_128row_front_4096_row_sample(kg_real):
 
 def test_bf16_training_64row_forward_4096_row_sample(kg_real):
     """Training at T >= 57 344 (120 samples of the real histogram + one of 4 096 rows): the saving + dropout variants of
-    rgfwd2_kernel / kgchain_kernel (wide2_taken: max_nr <= wide2_max_rows() = 4096) with the long sample across 64 half-blocks,
+    rgfwd2_kernel / kgchain_kernel (make_plan: max_nr <= wide2_max_rows() = 4096) with the long sample across 64 half-blocks,
     the two-plane tail, bwd1w_kernel / bwd2w_kernel -- against the oracle with the 64-row forward's flash-block partition."""
     nrs, _, _ = _histogram_batch(120, 17, kg_real)
     nrs.insert(61, 4096)
@@ -264,8 +264,8 @@ def test_bf16_training_64row_forward_4096_row_sample(kg_real):
 
 @pytest.mark.parametrize("max_nr", [4096, 4097])
 def test_bf16_inference_fused_schedule_max_nr_limit(max_nr, kg_real):
-    """Eval forward at T >= 10 240: with max_nr = 4096 the fused schedule's 64-row inference forward (rgfwd2_kernel, wide2_taken);
-    at 4097 both fused17_ok (max_nr <= 64 x FUSED_MAX_SPLITS) and sched16_ok (the MFMA KG->RG kernels' max_nr <= 768) refuse the
+    """Eval forward at T >= 10 240: with max_nr = 4096 the fused schedule's 64-row inference forward (rgfwd2_kernel, CAMO_BACK_RG_64);
+    at 4097 both make_plan's fused rule (max_nr <= 64 x FUSED_MAX_SPLITS) and its bf16 rule (the MFMA KG->RG kernels' max_nr <= 768) refuse the
     call, which then runs the general bf16-operand path, KG->RG attention on the general forward attn_kg2rg_fwd_kernel<16>.
     Logits of the long sample, its neighbours and the first and last samples against the f32 oracle at north_star's 1e-3, and
     packed == one-by-one at the bound of the B = 256 case."""
