@@ -12,8 +12,10 @@ from .fusion_model import (CrossAttentionFusion, LateFusion, MultimodalCamouflag
                            build_multimodal_model)
 from .losses import AggressiveFocalLoss, multitask_loss  # noqa: F401
 from .optim import FusedClipAdamW, cosine_warm_restarts_lr  # noqa: F401
-from .test_multimodal import (build_ordered_kg_tensor, load_multimodal_model, predict_embedding_directory,  # noqa: F401
-                              predict_from_embeddings, predict_from_region_graph)
+from .test_multimodal import (build_ordered_kg_tensor, load_multimodal_model, predict_from_embeddings,  # noqa: F401
+                              predict_from_region_graph)
+# (the package's predict_embedding_directory is test_multimodal's with a group size: batch_size=1, the default, calls that one)
+from .predict_batch import predict_batch_from_embeddings, predict_embedding_directory  # noqa: F401
 from .train_multimodal import (NativeTrainer, SmartMultimodalDataset, calculate_f1_score, collate_fn,  # noqa: F401
                                extract_label_from_mask, fit, pack_samples, train_epoch_fixed, train_multimodal_fixed,
                                validate_fixed)
@@ -25,4 +27,4 @@ __all__ = ["RegionGraphGNN", "RegionGraphData", "create_region_graph", "create_r
            "AggressiveFocalLoss", "multitask_loss", "FusedClipAdamW", "cosine_warm_restarts_lr", "NativeTrainer",
            "calculate_f1_score", "collate_fn", "fit", "pack_samples", "train_epoch_fixed", "validate_fixed",
            "EmbeddingMatcher", "DeviceResidentDataset", "SmartMultimodalDataset", "extract_label_from_mask", "train_multimodal_fixed", "load_multimodal_model", "build_ordered_kg_tensor",
-           "predict_from_embeddings", "predict_from_region_graph", "predict_embedding_directory"]
+           "predict_from_embeddings", "predict_batch_from_embeddings", "predict_from_region_graph", "predict_embedding_directory"]

@@ -12,9 +12,10 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcamo_fusion.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 FWD_INFERENCE = 1
 FLAG_ATTN_MAPS = 2
+FWD_FUSED_MAPS = 4
 SUMSQ_FLOATS = 257
 FUSION_CROSS_ATTENTION, FUSION_LATE = 0, 1
 PREC_F32, PREC_BF16 = 0, 1
@@ -65,7 +66,7 @@ class CamoDims(C.Structure):
 
 
 CALL_FORWARD, CALL_BACKWARD, CALL_TRAIN = 0, 1, 2
-PLAN_FIELDS = ("nodes", "shadows", "save", "front", "front_rt", "back", "back_rt", "save_r16", "tail", "tail_wg", "loss", "tail_event", "param_space", "bwd1", "bwd2")
+PLAN_FIELDS = ("nodes", "shadows", "save", "front", "front_rt", "back", "back_rt", "save_r16", "tail", "tail_wg", "loss", "tail_event", "param_space", "bwd1", "bwd2", "maps")
 
 
 class CamoPlan(C.Structure):

@@ -69,6 +69,7 @@ struct BackArgs {
   int B, Nk, rg_tiles_max, rows_rg;             // rows_rg = T (launch-timing bookkeeping only)
   DropCfg drop; int save; int exp;
   unsigned long long* stamps;                  // developer timeline (null in product calls)
+  int save_lse2;                               // 32-row back half: store lse2 although save == 0 (a call whose maps launch reads it, attn_maps.h)
 };
 // lead_mode: developer A/B (camo_options_t back_lead), 0 = KG split blocks always first
 int launch_fused_back(BackArgs& a, int variant, int lead_mode, hipStream_t stream);

@@ -460,7 +460,7 @@ __device__ __forceinline__ void attn_kg_combine(const BackArgs& a, char* smem, c
       }
     }
     invL[tid] = 1.0f / L;
-    if (a.save && a.lse2 && j < Nk) { float* o = a.lse2 + (((size_t)b * 8 + hd) * 16 + j) * 2; o[0] = M; o[1] = L; }
+    if ((a.save | a.save_lse2) && a.lse2 && j < Nk) { float* o = a.lse2 + (((size_t)b * 8 + hd) * 16 + j) * 2; o[0] = M; o[1] = L; }
   }
   __syncthreads();
   f32x4 acc[4];

@@ -23,6 +23,7 @@
 #include "gemm.h"
 #include "fused_rows.h"
 #include "tail_wide.h"
+#include "attn_maps.h"
 #include "gemm16.h"
 #include "misc.h"
 #include "rg_gnn.h"
@@ -380,6 +381,7 @@ struct PlanIn {
   int precision, B, T, Nk, max_nr;
   CallKind kind;
   bool attn_maps;               // attention maps are wanted: pointers given, or CAMO_FLAG_ATTN_MAPS
+  bool fused_maps;              // CAMO_FWD_FUSED_MAPS: an inference call that wants maps may take the fused schedule + the maps launch
   int cus;                      // compute units of the device (the one-launch tail's blocks must be co-resident)
 };
 
@@ -397,10 +399,15 @@ static void plan_fused_forward(const PlanIn& in, bool save, bool param_space, ca
   if (rt < 0) rt = save ? 0 : (T >= 22528 ? 4 : (T >= 13312 ? 2 : 0));
   if (rt != 0 && rt != 1 && rt != 2 && rt != 4) rt = 0;
   if (rt && max_nr > wide_max_rows(rt) - 64 * rt) rt = 0;
+  // A call that produces its maps behind the forward (p.maps, csrc/attn_maps.hip) needs q, k2 | v2 in the workspace: the one-launch
+  // kernels of the RG rows keep them in registers, so it takes the two-launch combinations the saving forwards run -- the 32-row
+  // front half below 10 240 packed rows, the wide front half from there on, and the 32-row back half (the one that stores lse2).
+  const bool maps = p.maps != 0;
+  if (maps) rt = 0;
   // The RG rows' whole forward in one launch of 64-row half-blocks, two independent blocks per CU, + the KG rows' launch behind it
   // (fused_wide2.hip).  By size for inference AND training calls (the saving / dropout variants write the backward's saved set); a
   // forced fused_rt selects the 8-wave / 32-row kernels.
-  bool rg64 = o.wide2 != 0 && o.fused_one != 0 && max_nr <= wide2_max_rows();
+  bool rg64 = !maps && o.wide2 != 0 && o.fused_one != 0 && max_nr <= wide2_max_rows();
   // training calls from 57 344 rows: their blocks are twice as long (the saved set, the dropout hashes), so the second round of blocks
   // must be nearly full before they beat the 32-row back half (measured, ms per step without / with: B = 96 0.517 / 0.540, B = 128
   // 0.637 / 0.621, B = 192 0.864 / 0.804, B = 256 1.076 / 0.979)
@@ -413,7 +420,7 @@ static void plan_fused_forward(const PlanIn& in, bool save, bool param_space, ca
   // (the back half of training calls stays on the 32-row kernel, whose saving + dropout variant is the faster one: 77 vs 94 us at B = 64)
   const bool rows128 = T >= 4 * 32 * 224;
   int wf_rt = 0;
-  if (save && rt == 0 && o.fused_rt < 0 && o.wide_front_rt >= 0 && (T >= 10240 || o.wide_front_rt > 0)) {
+  if ((save || maps) && rt == 0 && o.fused_rt < 0 && o.wide_front_rt >= 0 && (T >= 10240 || o.wide_front_rt > 0)) {
     wf_rt = o.wide_front_rt > 0 ? o.wide_front_rt : (rows128 ? 4 : 2);
     if ((wf_rt != 1 && wf_rt != 2 && wf_rt != 4) || max_nr > wide_max_rows(wf_rt) - 64 * wf_rt) wf_rt = 0;
   }
@@ -486,9 +493,12 @@ camo_plan_t make_plan(const PlanIn& in) {
   }
   if (train) p.tail_event = CAMO_EVENT_BEFORE_NODES;
   const bool proj = in.rg_proj && in.kg_proj, bf16 = in.precision == CAMO_PREC_BF16;
-  // calls at the reference configuration that do not ask for attention maps take the fused row-tile schedule
-  if (!in.attn_maps && o.fused != 0 && bf16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS && proj) {
+  // calls at the reference configuration that do not ask for attention maps take the fused row-tile schedule -- and inference calls
+  // that ask for them and allow it (CAMO_FWD_FUSED_MAPS): the maps then come out of one launch behind the back half
+  const bool maps = in.attn_maps && in.fused_maps && in.kind == CALL_INFERENCE;
+  if ((!in.attn_maps || maps) && o.fused != 0 && bf16 && fused17_dims(d) && Nk <= 16 && max_nr <= 64 * FUSED_MAX_SPLITS && proj) {
     p.nodes = CAMO_NODES_FUSED;
+    p.maps = maps;
     p.shadows = in.kind != CALL_BACKWARD;      // (camo_backward takes no shadow argument)
     // The projections' and in-projections' weight gradients in parameter space (no dR / dG product in the second backward kernel, 131 k
     // instead of 427 k MACs per row, one small launch behind the weight gradients): from ~10 k packed rows on -- below that the extra launch
@@ -518,10 +528,10 @@ struct Batch {
 };
 
 // the plan of an entry point's call (behind check_dims; params == null: left empty, open_batch refuses the call)
-void plan_batch(Batch& x, CallKind kind, bool attn_maps) {
+void plan_batch(Batch& x, CallKind kind, bool attn_maps, bool fused_maps = false) {
   x.opt = &options_of(x.dims);
   if (x.P) x.plan = make_plan(PlanIn{*x.opt, *x.dims, x.P[CAMO_P_RG_PROJ_W] != nullptr, x.P[CAMO_P_KG_PROJ_W] != nullptr, x.precision, x.B, x.T, x.Nk, x.max_nr,
-                                     kind, attn_maps, device_cus()});
+                                     kind, attn_maps, fused_maps, device_cus()});
 }
 
 // (validated arguments -> the rest of the bundle; `ptrs_ok`: the entry point's own pointer arguments are there)
@@ -706,7 +716,7 @@ int forward_nodes16(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
 }
 
 // ---- node-level forward of the fused row-tile schedule: the same function in 3 launches (fused_rows.h) ----
-int forward_nodes17(Call& c, const Batch& x) {
+int forward_nodes17(Call& c, const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
   const camo_plan_t& pl = x.plan; const float* const* P = x.P; const Ws& w = x.w; hipStream_t st = x.st;
   const int H = 256, D = 128, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, max_nr = x.max_nr;
   const size_t HH = (size_t)H * H;
@@ -823,13 +833,21 @@ int forward_nodes17(Call& c, const Batch& x) {
   ba.off = x.rg_offsets; ba.tile_off = x.bd.tile_off; ba.tile_desc = x.bd.tile_desc; ba.inv_nr = x.bd.inv_nr; ba.lse2 = f.lse2;
   ba.B = B; ba.Nk = Nk; ba.rows_rg = T; ba.rg_tiles_max = T / 32 + B;          // >= sum of ceil(Nr / 32); surplus blocks exit at once
   ba.part = f.part; ba.tickets = w.tickets; ba.max_splits = (max_nr + 63) / 64;
-  ba.drop = x.drop; ba.save = save ? 1 : 0; ba.exp = x.opt->exp;
+  ba.drop = x.drop; ba.save = save ? 1 : 0; ba.save_lse2 = pl.maps; ba.exp = x.opt->exp;
   ba.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)g_dbg_stamp_blocks * 8 : nullptr;
   switch (pl.back) {
     case CAMO_BACK_RG_64: CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, pl.save_r16, st), "fused forward, RG rows in one launch (64-row half-blocks)"); break;
     case CAMO_BACK_RG_WIDE: CK(launch_wide_rgfwd(fa.s[0], fa.qscale, ba, pl.back_rt, max_nr, st), "fused forward, RG rows in one launch (wide tiles)"); break;
     case CAMO_BACK_WIDE: CK(launch_wide_back(ba, pl.back_rt, max_nr, st), "fused forward, back half (wide tiles)"); break;
     default: CK(launch_fused_back(ba, x.opt->fused_variant, x.opt->back_lead, st), "fused forward, back half");
+  }
+  if (pl.maps) {
+    // both head-averaged maps from what the two halves left in the workspace: one launch over the batch descriptor's tile table,
+    // behind the back half (lse2) and independent of the per-sample tail
+    AttnMapsArgs ma; std::memset(&ma, 0, sizeof(ma));
+    ma.Q16 = f.Q16; ma.KV16 = f.KV16; ma.Q2_16 = f.Q2_16; ma.KV2_16 = f.KV2_16; ma.lse2 = f.lse2; ma.tile_desc = x.bd.tile_desc;
+    ma.rg2kg = attn_rg2kg; ma.kg2rg = attn_kg2rg; ma.Nk = Nk; ma.tiles = T / 32 + B; ma.rows_rg = T;
+    CK(launch_attn_maps(ma, st), "attention maps of the fused forward");
   }
   return 0;
 }
@@ -1185,7 +1203,7 @@ int forward_impl(Call& c, const Batch& x, float* outs, float* attn_rg2kg, float*
   if (!x.P[CAMO_P_RG_PROJ_W] && d.rg_dim != d.hidden_dim) return fail(CAMO_E_ARG, "rg_proj weight missing but rg_dim != hidden_dim");
   if (!x.P[CAMO_P_KG_PROJ_W] && d.kg_dim != d.hidden_dim) return fail(CAMO_E_ARG, "kg_proj weight missing but kg_dim != hidden_dim");
   if (x.plan.nodes == CAMO_NODES_FUSED) {
-    if (int e = forward_nodes17(c, x)) return e;
+    if (int e = forward_nodes17(c, x, attn_rg2kg, attn_kg2rg)) return e;
     if (x.plan.tail >= CAMO_TAIL_PLANES) return tail_planes_forward(x, outs, fl);
     if (x.plan.tail == CAMO_TAIL_ONE_LAUNCH) return tail17(c, x, outs, fl);
   } else if (x.plan.nodes == CAMO_NODES_BF16) {
@@ -1342,8 +1360,11 @@ int camo_forward_cached(const camo_dims_t* dims, const float* const* params, con
     return fail(CAMO_E_UNSUPPORTED, "camo_forward_cached with a shadow buffer serves inference calls only (flags must contain CAMO_FWD_INFERENCE)");
   if (shadows && (reinterpret_cast<uintptr_t>(shadows) & 255)) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
   if (int e = check_dims(dims, B, T, Nk)) return e;
+  // (training mode with dropout: the reference's maps are the probabilities after attention dropout -- today's schedules model that)
+  if (training && dims->dropout > 0.f) flags &= ~CAMO_FWD_FUSED_MAPS;
   Batch x{dims, params, nullptr, rg, rg_offsets, batch_desc, kg, B, T, Nk, max_nr, workspace, workspace_bytes, training, seed, precision, static_cast<hipStream_t>(stream)};
-  plan_batch(x, (flags & CAMO_FWD_INFERENCE) ? CALL_INFERENCE : CALL_FORWARD_SAVE, attn_rg2kg || attn_kg2rg || (flags & CAMO_FLAG_ATTN_MAPS));
+  plan_batch(x, (flags & CAMO_FWD_INFERENCE) ? CALL_INFERENCE : CALL_FORWARD_SAVE, attn_rg2kg || attn_kg2rg || (flags & CAMO_FLAG_ATTN_MAPS),
+             (attn_rg2kg || attn_kg2rg) && (flags & CAMO_FWD_FUSED_MAPS) != 0);
   // (a call that takes a schedule without shadows leaves the caller's buffer alone: a promise is then simply not used)
   if (x.plan.shadows) { c.shadows = shadows; c.shadows_valid = shadows && shadows_valid != 0; c.fold_missing = shadows && shadows_valid == 2; }
   if (int e = open_batch(x, c, outs != nullptr)) return e;
@@ -1604,7 +1625,7 @@ int camo_debug_plan(const camo_dims_t* dims, int32_t has_projections, int32_t B,
   if (call_kind != CAMO_CALL_FORWARD && call_kind != CAMO_CALL_BACKWARD && call_kind != CAMO_CALL_TRAIN) return fail(CAMO_E_ARG, "unknown call kind");
   const CallKind kind = call_kind == CAMO_CALL_TRAIN ? CALL_TRAIN : (call_kind == CAMO_CALL_BACKWARD ? CALL_BACKWARD : ((flags & CAMO_FWD_INFERENCE) ? CALL_INFERENCE : CALL_FORWARD_SAVE));
   *out = make_plan(PlanIn{options_of(dims), *dims, (has_projections & 1) != 0, (has_projections & 2) != 0, precision, B, T, Nk, max_nr, kind,
-                          kind != CALL_TRAIN && (flags & CAMO_FLAG_ATTN_MAPS) != 0, cus < 0 ? device_cus() : cus});
+                          kind != CALL_TRAIN && (flags & CAMO_FLAG_ATTN_MAPS) != 0, (flags & CAMO_FWD_FUSED_MAPS) != 0, cus < 0 ? device_cus() : cus});
   return 0;
 }
 

@@ -344,9 +344,11 @@ class FusionEngine:
         return (self._seed_base + 0x9E3779B97F4A7C15 * self._calls) & 0xFFFFFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ raw calls
-    def forward_raw(self, batch, ws, training, seed, want_attention=False, outs=None, inference=False, cache_shadows=True):
+    def forward_raw(self, batch, ws, training, seed, want_attention=False, outs=None, inference=False, cache_shadows=True, fused_maps=False):
         """``inference``: no backward_raw will follow on this workspace (lets the library skip what it would save).
-        ``cache_shadows=False``: an inference call that keeps its weight shadows in ``ws`` like any other call (tests read them there)."""
+        ``cache_shadows=False``: an inference call that keeps its weight shadows in ``ws`` like any other call (tests read them there).
+        ``fused_maps``: allow an inference call that wants attention maps to take the fused row-tile schedule and produce the maps with
+        one launch behind it (CAMO_FWD_FUSED_MAPS: a permission -- where the fused schedule does not apply the call runs as without it)."""
         mod = self.module()
         if outs is None:
             outs = torch.empty(batch.B, self.out_width, dtype=torch.float32, device=batch.rg.device)
@@ -356,7 +358,10 @@ class FusionEngine:
             a2 = torch.empty(batch.T, batch.Nk, dtype=torch.float32, device=batch.rg.device)
         # inference calls keep the fused schedule's weight shadows in the engine's persistent buffer: a validation / prediction
         # loop builds them once per parameter change instead of once per call (the library says what it left there)
-        sh = self.shadow_buffer() if (inference and cache_shadows and a1 is None) else None
+        # (the permission takes effect in bf16 mode only: elsewhere the call runs, and allocates, exactly as without it)
+        fused_maps = bool(fused_maps and inference and a1 is not None and mod.precision == "bf16")
+        flags = (_lib.FWD_INFERENCE if inference else 0) | (_lib.FWD_FUSED_MAPS if fused_maps else 0)
+        sh = self.shadow_buffer() if (inference and cache_shadows and (a1 is None or fused_maps)) else None
         with _on(self.device):
             if sh is not None:
                 # (1 = current including the folded in-projection, which only inference calls build; 2 = current but left by the
@@ -365,8 +370,8 @@ class FusionEngine:
                 state = C.c_int32(0)
                 rc = _lib.lib().camo_forward_cached(C.byref(self.dims), self._ptab, _ptr(batch.rg), _ptr(batch.offsets),
                                                     _ptr(batch.desc), _ptr(batch.kg), batch.B, batch.T, batch.Nk, batch.max_nr, _ptr(ws), ws.numel(),
-                                                    _ptr(outs), None, None, int(bool(training)), seed, _PREC[mod.precision],
-                                                    _lib.FWD_INFERENCE, _ptr(sh), valid, C.byref(state), _stream_ptr(self.device))
+                                                    _ptr(outs), _ptr(a1), _ptr(a2), int(bool(training)), seed, _PREC[mod.precision],
+                                                    flags, _ptr(sh), valid, C.byref(state), _stream_ptr(self.device))
                 if rc == 0 and state.value:
                     self._shadows_full = state.value == 2 or bool(valid and self._shadows_full)
                     self._shadows_version = self.param_version()
@@ -375,7 +380,7 @@ class FusionEngine:
                 rc = _lib.lib().camo_forward(C.byref(self.dims), self._ptab, _ptr(batch.rg), _ptr(batch.offsets),
                                              _ptr(batch.desc), _ptr(batch.kg), batch.B, batch.T, batch.Nk, batch.max_nr, _ptr(ws), ws.numel(), _ptr(outs),
                                              _ptr(a1), _ptr(a2), int(bool(training)), seed, _PREC[mod.precision],
-                                             _lib.FWD_INFERENCE if inference else 0, _stream_ptr(self.device))
+                                             flags, _stream_ptr(self.device))
         _lib.check(rc, "camo_forward")
         return outs, ((a1, a2) if a1 is not None else None)
 
@@ -421,7 +426,7 @@ class FusionEngine:
         return outs, terms, pred
 
     # ------------------------------------------------------------------ autograd (drop-in) mode
-    def forward_autograd(self, rg_packed, nrs, kg, want_attention=False):
+    def forward_autograd(self, rg_packed, nrs, kg, want_attention=False, fused_attention=False):
         mod = self.module()
         batch = self.make_batch(rg_packed, nrs, kg)
         named = dict(mod.named_parameters())
@@ -429,7 +434,8 @@ class FusionEngine:
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         seed = self.next_seed()
         if not needs_grad:
-            return self.forward_raw(batch, self.workspace(batch), mod.training, seed, want_attention, inference=True)
+            return self.forward_raw(batch, self.workspace(batch), mod.training, seed, want_attention, inference=True,
+                                    fused_maps=fused_attention and want_attention)
         ws = self.workspace(batch, private=True)   # saved activations live until this call's backward
         res = _FusionFn.apply(self, batch, ws, mod.training, seed, want_attention and self.cross, *params)
         if want_attention and self.cross:

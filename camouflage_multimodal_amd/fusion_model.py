@@ -156,14 +156,18 @@ class MultimodalCamouflageDetector(nn.Module):
         self.precision = precision
         return self
 
-    def forward(self, rg_embeddings, kg_embeddings, return_attention=False):
+    def forward(self, rg_embeddings, kg_embeddings, return_attention=False, *, fused_attention=False):
+        """``fused_attention`` (with ``return_attention``, calls without autograd): in bf16 mode at the reference configuration the
+        call may run the fused inference schedule and take its head-averaged maps from one extra launch over the tensors that
+        schedule leaves behind, instead of the schedule that materialises every head's probabilities.  Eval mode (or dropout 0)
+        only; anywhere else, and in f32 mode, it has no effect.  Default: off."""
         rg = _collapse_to_3d(rg_embeddings, "rg_embeddings")
         kg = _collapse_to_3d(kg_embeddings, "kg_embeddings")
         if rg.shape[0] != kg.shape[0]:
             raise RuntimeError(f"batch sizes differ: rg {tuple(rg.shape)} vs kg {tuple(kg.shape)}")
         B, Nr, _ = rg.shape
         outs, attn = self._engine.forward_autograd(rg.reshape(B * Nr, rg.shape[2]), [Nr] * B, kg,
-                                                   want_attention=return_attention)
+                                                   want_attention=return_attention, fused_attention=fused_attention)
         res = self._split(outs)
         if not return_attention:
             return res
@@ -172,12 +176,13 @@ class MultimodalCamouflageDetector(nn.Module):
         Nk = kg.shape[1]
         return res + ({"rg2kg": attn[0].view(B, Nr, Nk), "kg2rg": attn[1].view(B, Nr, Nk).transpose(1, 2)},)
 
-    def forward_packed(self, rg_packed, nr_per_sample, kg_embeddings, return_attention=False):
+    def forward_packed(self, rg_packed, nr_per_sample, kg_embeddings, return_attention=False, *, fused_attention=False):
         """Variable-Nr minibatch: ``rg_packed`` [sum(Nr), rg_dim] holds the samples' node rows back
         to back, ``nr_per_sample`` their lengths (host ints), ``kg_embeddings`` [B, Nk, kg_dim].
-        Attention maps come back as per-sample lists."""
+        Attention maps come back as per-sample lists.  ``fused_attention``: as in ``forward``."""
         kg = _collapse_to_3d(kg_embeddings, "kg_embeddings")
-        outs, attn = self._engine.forward_autograd(rg_packed, list(nr_per_sample), kg, want_attention=return_attention)
+        outs, attn = self._engine.forward_autograd(rg_packed, list(nr_per_sample), kg, want_attention=return_attention,
+                                                   fused_attention=fused_attention)
         res = self._split(outs)
         if not return_attention:
             return res

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CAMO_ABI_VERSION 11
+#define CAMO_ABI_VERSION 12
 
 enum {
   CAMO_OK = 0,
@@ -134,9 +134,18 @@ size_t camo_workspace_bytes(const camo_dims_t* dims, int32_t B, int32_t T, int32
  *               counter-based mask of (seed, site, element index)
  *   flags       CAMO_FWD_* bits.  CAMO_FWD_INFERENCE: no camo_backward will follow this call (validation,
  *               prediction): nothing is saved for it and the workspace contents are undefined afterwards.
+ *               CAMO_FWD_FUSED_MAPS: a PERMISSION, never an error -- an inference call that is given at least one map pointer may
+ *               take the fused row-tile schedule and produce its maps with one extra launch behind the forward's back half
+ *               (csrc/attn_maps.hip) instead of the bf16-resident / general schedule that materialises the probabilities.  It takes
+ *               effect only together with CAMO_FWD_INFERENCE, with training == 0 or dims->dropout == 0 (in training mode the
+ *               reference returns the maps after attention dropout: that stays on the schedules that model the site masks), and
+ *               when every other condition of the fused schedule holds (bf16, reference dims, both projections, Nk <= 16,
+ *               max_nr <= 4096); otherwise the call plans exactly as it does without the flag.  The maps are the probabilities the
+ *               fused forward's PV products used (fp32 softmax of the bf16 queries and keys), head-averaged.
  */
 #define CAMO_FWD_INFERENCE 1
 #define CAMO_FLAG_ATTN_MAPS 2   /* camo_backward only: the forward call of this workspace was given attention-map pointers */
+#define CAMO_FWD_FUSED_MAPS 4   /* camo_forward / camo_forward_cached / camo_debug_plan: see above */
 size_t camo_batch_desc_bytes(int32_t B, int32_t T);
 int camo_prepare_batch(const int32_t* rg_offsets, int32_t B, int32_t T, int32_t max_nr,
                        void* batch_desc, size_t batch_desc_bytes, void* stream);
@@ -172,7 +181,7 @@ int camo_forward(const camo_dims_t* dims, const float* const* params,
  * per inference call).  shadows_valid == 2: valid, but left by camo_clip_adamw_shadows, whose set lacks the one piece only
  * inference calls build -- the RG rows' folded in-projection Wf = [Wq; Wk'; Wv'] Wrg (csrc/fused_wide2.hip) -- which this call
  * then builds alone (one small launch); afterwards the caller may pass 1.  *shadows_state (may be null) reports what the buffer holds after the call: 0 = untouched (the call
- * took a schedule without shadows: Nk > 16, attention maps, f32 ...; a promise is then simply not used), 1 = the forward
+ * took a schedule without shadows: Nk > 16, attention maps without CAMO_FWD_FUSED_MAPS, f32 ...; a promise is then simply not used), 1 = the forward
  * shadows (an inference call built them, or used valid ones); 2 is reported by camo_forward_loss_backward only (forward and
  * transposed shadows).  With a shadow buffer the call must be an inference call (flags contain CAMO_FWD_INFERENCE), else
  * CAMO_E_UNSUPPORTED: camo_backward takes no shadow argument, so a saving call's transposed shadows would be out of its reach --
@@ -288,7 +297,9 @@ int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int3
  *   has_projections  bit 0: the rg_proj weight is present (params[CAMO_P_RG_PROJ_W] != NULL), bit 1: the kg_proj weight
  *   flags            CAMO_FWD_INFERENCE as on camo_forward; CAMO_FLAG_ATTN_MAPS: attention maps are wanted (a forward that is
  *                    given attention-map pointers, or camo_backward with that flag)
- *                    (ignored for CAMO_CALL_TRAIN: camo_forward_loss_backward has no such argument)
+ *                    (ignored for CAMO_CALL_TRAIN: camo_forward_loss_backward has no such argument);
+ *                    CAMO_FWD_FUSED_MAPS as on camo_forward (CAMO_CALL_FORWARD only; this entry has no `training` argument: the
+ *                    entry points drop the flag from training-mode calls with dropout before they plan)
  *   call_kind        CAMO_CALL_*: which entry point
  *   cus              compute units of the device (the one-launch tail needs 64 co-resident blocks per group of 16 samples);
  *                    < 0: ask the current device.  With cus >= 0 the call touches no device and needs none.
@@ -338,6 +349,8 @@ typedef struct camo_plan {
   int32_t tail, tail_wg, loss, tail_event;   /* CAMO_TAIL_*, CAMO_TAIL_WG_*, CAMO_LOSS_*, CAMO_EVENT_*        */
   int32_t param_space;  /* backward: 1 = projection / in-projection weight gradients in parameter space      */
   int32_t bwd1, bwd2;   /* CAMO_BWD1_*, CAMO_BWD2_*                                                           */
+  int32_t maps;         /* 1: CAMO_FWD_FUSED_MAPS took effect -- the front half is one that writes Q16 / Q2_16 / KV16 /   */
+                        /* KV2_16, the 32-row back half also stores lse2, and the maps launch follows it                */
 } camo_plan_t;
 int camo_debug_plan(const camo_dims_t* dims, int32_t has_projections, int32_t B, int32_t T, int32_t Nk, int32_t max_nr,
                     int32_t precision, int32_t flags, int32_t call_kind, int32_t cus, camo_plan_t* out);
