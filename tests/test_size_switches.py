@@ -58,16 +58,18 @@ def _log_spread(maps):
     return float(np.concatenate([x.max(1) - x.min(1) for x in lp]).mean())
 
 
-def _f32_case(cfg, pseed, nrs, nk):
+def _f32_case(cfg, pseed, nrs, nk, y=None):
     """One f32 training step (dropout as in ``cfg``) through NativeTrainer against FO.train_step with the same seed, at the bounds of
     test_train_mode_dropout_matches_oracle_masks; before it, an eval forward with attention maps against the oracle's: logits and
     both maps at the bounds of test_long_sequence_config_nr2048 / test_eval_forward_golden_real_kg, every map row summing to 1.
-    Parameters from _sharp_params, so that the attention maps are far from uniform (checked on the oracle's maps)."""
+    Parameters from _sharp_params, so that the attention maps are far from uniform (checked on the oracle's maps).
+    ``y``: mask labels instead of OP.make_labels' (which are 0 / 1 whatever num_classes is)."""
     from camouflage_multimodal_amd import NativeTrainer
     B = len(nrs)
     rg = [OP.make_rg(n, cfg["rg_dim"], seed=700 + 3 * pseed + i) for i, n in enumerate(nrs)]
     kg = np.stack([OP.make_kg(nk, cfg["kg_dim"], seed=800 + 3 * pseed + i) for i in range(B)])
-    y, e, s = OP.make_labels(B, seed=40 + pseed)
+    y0, e, s = OP.make_labels(B, seed=40 + pseed)
+    y = y0 if y is None else np.asarray(y, np.int64)
     rgp, kgt = torch.from_numpy(np.concatenate(rg)).cuda(), torch.from_numpy(kg).cuda()
     prm = _sharp_params(cfg, pseed)
     m = make_model(cfg, pseed, params=prm).eval()
