@@ -15,10 +15,10 @@
 // tile's [rows][Nk] outputs leave as one contiguous run of dword stores.  Rows past the tile's end and keys past Nk are never read.
 #include "attn_maps.h"
 #include "gemm.h"
+#include "mfma_inl.h"   // u32x4
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // c + a.lo * b.lo + a.hi * b.hi on two packed bf16 pairs, fp32 accumulate

@@ -18,11 +18,11 @@
 // Numerics: fp32 FMA chains in k order, same math as attn.hip; dropout masks from the shared
 // counter hash.  Conditions: head_dim == 32, Nk <= 16; kg2rg additionally Nr <= 16*4*MAXT.
 #include "attn.h"
+#include "mfma_inl.h"   // f32x4
 
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int DH = 32;
 constexpr int NW = 8;      // waves per block in the kg2rg kernels
 constexpr int MAXT = 6;    // key tiles per wave there (8 waves x 6 tiles x 16 keys => Nr <= 768)
@@ -42,7 +42,7 @@ __device__ __forceinline__ Frag8 scale8(Frag8 f, float s) {
 }
 
 // C += A.B^T, K = 32: a = row fragment of A (lane x = row of C), b = row fragment of B (lane x = col of C)
-__device__ __forceinline__ f4 mma_nt32(const Frag8& a, const Frag8& b, f4 c) {
+__device__ __forceinline__ f32x4 mma_nt32(const Frag8& a, const Frag8& b, f32x4 c) {
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo.x, b.lo.x, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo.y, b.lo.y, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo.z, b.lo.z, c, 0, 0, 0);
@@ -55,7 +55,7 @@ __device__ __forceinline__ f4 mma_nt32(const Frag8& a, const Frag8& b, f4 c) {
 }
 // C += A.B, K = 16: a = an accumulator tile whose ROWS are the contraction index (a[e] <-> k = 4q+e),
 // b[e] = B[4q+e][col x]
-__device__ __forceinline__ f4 mma_acc16(const f4& a, const f4& b, f4 c) {
+__device__ __forceinline__ f32x4 mma_acc16(const f32x4& a, const f32x4& b, f32x4 c) {
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
@@ -64,8 +64,8 @@ __device__ __forceinline__ f4 mma_acc16(const f4& a, const f4& b, f4 c) {
 }
 // b[e] = X[(row0 + 4q + e) * ld + col] for e = 0..3, rows clamped to [.., row_max] (finite filler;
 // the matching A entries are zero there)
-__device__ __forceinline__ f4 load_col4(const float* __restrict__ X, size_t ld, int row0, int q, int row_max, int col) {
-  f4 b;
+__device__ __forceinline__ f32x4 load_col4(const float* __restrict__ X, size_t ld, int row0, int q, int row_max, int col) {
+  f32x4 b;
 #pragma unroll
   for (int e = 0; e < 4; ++e) b[e] = X[(size_t)min(row0 + 4 * q + e, row_max) * ld + col];
   return b;
@@ -90,10 +90,10 @@ __device__ __forceinline__ void rg2kg_fwd_body(
   const float* kvb = KV + (size_t)b * Nk * 2 * H;
   const Frag8 qf = load_row8(Q + (size_t)node * H + h * DH, q, true);
   const Frag8 kf = load_row8(kvb + (size_t)min(x, Nk - 1) * 2 * H + h * DH, q, x < Nk);
-  f4 vb[2];
+  f32x4 vb[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n) vb[n] = load_col4(kvb + H + h * DH + 16 * n, (size_t)2 * H, 0, q, Nk - 1, x);
-  f4 s = mma_nt32(kf, qf, f4{0.f, 0.f, 0.f, 0.f});       // S^T: rows = keys 4q+r, col = node x
+  f32x4 s = mma_nt32(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f});       // S^T: rows = keys 4q+r, col = node x
   float m = -INFINITY;
 #pragma unroll
   for (int r = 0; r < 4; ++r) { s[r] = (4 * q + r < Nk) ? s[r] * scale : -INFINITY; m = fmaxf(m, s[r]); }
@@ -116,7 +116,7 @@ __device__ __forceinline__ void rg2kg_fwd_body(
   }
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
-    const f4 o = mma_acc16(s, vb[n], f4{0.f, 0.f, 0.f, 0.f});   // rows = nodes 4q+r, col = 16n + x
+    const f32x4 o = mma_acc16(s, vb[n], f32x4{0.f, 0.f, 0.f, 0.f});   // rows = nodes 4q+r, col = 16n + x
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (t0 + 4 * q + r < nr) {
@@ -157,11 +157,11 @@ constexpr int TPW = 2;
 __device__ __forceinline__ void rg2kg_bwd_tiles(
     const float* __restrict__ Q, const float* __restrict__ P, const float* __restrict__ dO,
     float* __restrict__ dQ, Bf16Dst dq16, int H, int nh, int Nk, float scale, const DropCfg& drop,
-    int r0, int nr, int h, const int (&t0s)[TPW], const Frag8& vf, const f4 (&kb)[2], f4 (&dKa)[2], f4 (&dVa)[2]) {
+    int r0, int nr, int h, const int (&t0s)[TPW], const Frag8& vf, const f32x4 (&kb)[2], f32x4 (&dKa)[2], f32x4 (&dVa)[2]) {
   const int lane = threadIdx.x & 63, x = lane & 15, q = lane >> 4;
   // all loads of the tiles first, unconditionally, from rows clamped into the sample (see kg2rg forward)
   Frag8 gfv[TPW];
-  f4 pTv[TPW], pNv[TPW], qbv[TPW][2], gbv[TPW][2];
+  f32x4 pTv[TPW], pNv[TPW], qbv[TPW][2], gbv[TPW][2];
 #pragma unroll
   for (int tt = 0; tt < TPW; ++tt) {
     const int t0 = min(t0s[tt], nr - 1);
@@ -187,9 +187,9 @@ __device__ __forceinline__ void rg2kg_bwd_tiles(
     const bool node_ok = t0 + x < nr;
     const Frag8 gf = gfv[tt];
     // ---- orientation T: rows = keys 4q+r, col = node x
-    f4 dpT = mma_nt32(vf, gf, f4{0.f, 0.f, 0.f, 0.f});
+    f32x4 dpT = mma_nt32(vf, gf, f32x4{0.f, 0.f, 0.f, 0.f});
     const size_t pbase = ((size_t)node * nh + h) * Nk;
-    f4 pT;
+    f32x4 pT;
     float dot = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -201,12 +201,12 @@ __device__ __forceinline__ void rg2kg_bwd_tiles(
       dot = fmaf(pT[r], dpT[r], dot);
     }
     dot = group_sum(dot);                                  // row-dot of node x
-    f4 dsT;
+    f32x4 dsT;
 #pragma unroll
     for (int r = 0; r < 4; ++r) dsT[r] = pT[r] * (dpT[r] - dot) * scale;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const f4 dq = mma_acc16(dsT, kb[n], f4{0.f, 0.f, 0.f, 0.f});     // rows = nodes 4q+r, col = 16n + x
+      const f32x4 dq = mma_acc16(dsT, kb[n], f32x4{0.f, 0.f, 0.f, 0.f});     // rows = nodes 4q+r, col = 16n + x
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (t0 + 4 * q + r < nr) {
@@ -215,8 +215,8 @@ __device__ __forceinline__ void rg2kg_bwd_tiles(
         }
     }
     // ---- orientation N: rows = nodes 4q+r, col = key x
-    f4 dpN = mma_nt32(gf, vf, f4{0.f, 0.f, 0.f, 0.f});
-    f4 dsN, pdN;
+    f32x4 dpN = mma_nt32(gf, vf, f32x4{0.f, 0.f, 0.f, 0.f});
+    f32x4 dsN, pdN;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int nd = t0 + 4 * q + r;
@@ -251,11 +251,11 @@ __global__ __launch_bounds__(256) void rg2kg_bwd_mfma_kernel(
   const int tfirst = (blockIdx.x * 4 + wave) * TPW;
   const float* kvb = KV + (size_t)b * Nk * 2 * H;
   const Frag8 vf = load_row8(kvb + (size_t)min(x, Nk - 1) * 2 * H + H + h * DH, q, x < Nk);
-  f4 kb[2], dKa[2], dVa[2];
+  f32x4 kb[2], dKa[2], dVa[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     kb[n] = load_col4(kvb + h * DH + 16 * n, (size_t)2 * H, 0, q, Nk - 1, x);   // K_h[key 4q+e][16n + x]
-    dKa[n] = f4{0.f, 0.f, 0.f, 0.f}; dVa[n] = f4{0.f, 0.f, 0.f, 0.f};
+    dKa[n] = f32x4{0.f, 0.f, 0.f, 0.f}; dVa[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int t0s[TPW] = {tfirst * 16, (tfirst + 1) * 16};
   rg2kg_bwd_tiles(Q, P, dO, dQ, dq16, H, nh, Nk, scale, drop, r0, nr, h, t0s, vf, kb, dKa, dVa);
@@ -297,7 +297,7 @@ __device__ __forceinline__ void kg2rg_fwd_body(
   // (tiles past the end re-read its last row and are masked below): with the loads inside "if (tile valid)" the
   // compiler kept each tile's load -> wait -> MFMA chain separate, one memory round trip per tile.
   Frag8 kf[MAXT];
-  f4 vb[MAXT][2];
+  f32x4 vb[MAXT][2];
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     const int t0 = (wave + NW * i) * 16;
@@ -309,12 +309,12 @@ __device__ __forceinline__ void kg2rg_fwd_body(
 #pragma unroll
     for (int n = 0; n < 2; ++n) vb[i][n] = load_col4(kv + H + h * DH + 16 * n, (size_t)2 * H, min(t0, nr - 1), q, nr - 1, x);
   }
-  f4 s[MAXT];
+  f32x4 s[MAXT];
   float m = -INFINITY;
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     const int t0 = (wave + NW * i) * 16;
-    s[i] = mma_nt32(kf[i], q2f, f4{0.f, 0.f, 0.f, 0.f});
+    s[i] = mma_nt32(kf[i], q2f, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
     for (int r = 0; r < 4; ++r) { if (t0 + 4 * q + r >= nr) s[i][r] = -INFINITY; m = fmaxf(m, s[i][r]); }
   }
@@ -338,7 +338,7 @@ __device__ __forceinline__ void kg2rg_fwd_body(
 #pragma unroll
   for (int w = 1; w < NW; ++w) tot += red[w][x];
   const float inv = 1.0f / tot;
-  f4 o[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
+  f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     const int t0 = (wave + NW * i) * 16;
@@ -427,7 +427,7 @@ __device__ __forceinline__ void kg2rg_bwd_body(
   // ---- orientation T (rows = keys 4q+r, col = query x): dP, dS, dQ2.  All loads of the kernel are issued up front,
   // unconditionally, from clamped rows (see kg2rg forward)
   Frag8 vf[MAXT];
-  f4 pld[MAXT], pl2[MAXT], kb[MAXT][2];
+  f32x4 pld[MAXT], pl2[MAXT], kb[MAXT][2];
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     const int t0 = (wave + NW * i) * 16;
@@ -443,12 +443,12 @@ __device__ __forceinline__ void kg2rg_bwd_body(
 #pragma unroll
     for (int n = 0; n < 2; ++n) kb[i][n] = load_col4(kv + h * DH + 16 * n, (size_t)2 * H, min(t0, nr - 1), q, nr - 1, x);
   }
-  f4 dq[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
+  f32x4 dq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
     const int t0 = (wave + NW * i) * 16;
     if (wave + NW * i >= ntiles) continue;                   // wave-uniform; nothing below loads
-    f4 ds = mma_nt32(vf[i], g2f, f4{0.f, 0.f, 0.f, 0.f});
+    f32x4 ds = mma_nt32(vf[i], g2f, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int t = t0 + 4 * q + r;
@@ -483,7 +483,7 @@ __device__ __forceinline__ void kg2rg_bwd_body(
       }
   }
   // ---- phase 2, orientation N (rows = queries 4q+r, col = key x): dK2, dV2 of every key tile
-  f4 q2b[2], g2b[2];
+  f32x4 q2b[2], g2b[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     q2b[n] = load_col4(q2p + 16 * n, (size_t)H, 0, q, Nk - 1, x);   // Q2_h[query 4q+e][16n + x]
@@ -498,9 +498,9 @@ __device__ __forceinline__ void kg2rg_bwd_body(
     if (wave + NW * i >= ntiles) continue;                   // wave-uniform; nothing below loads
     const int key = min(t0 + x, nr - 1);
     const bool key_ok = t0 + x < nr;
-    const f4 dpN = mma_nt32(g2f, vf[i], f4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 dpN = mma_nt32(g2f, vf[i], f32x4{0.f, 0.f, 0.f, 0.f});
     const size_t pb = ((size_t)(r0 + key) * nh + h) * Nk;
-    f4 dsN, pdN;
+    f32x4 dsN, pdN;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int qi = 4 * q + r;
@@ -512,8 +512,8 @@ __device__ __forceinline__ void kg2rg_bwd_body(
     }
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const f4 dk = mma_acc16(dsN, q2b[n], f4{0.f, 0.f, 0.f, 0.f});  // rows = keys 4q+r, col = 16n + x
-      const f4 dv = mma_acc16(pdN, g2b[n], f4{0.f, 0.f, 0.f, 0.f});
+      const f32x4 dk = mma_acc16(dsN, q2b[n], f32x4{0.f, 0.f, 0.f, 0.f});  // rows = keys 4q+r, col = 16n + x
+      const f32x4 dv = mma_acc16(pdN, g2b[n], f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int t = t0 + 4 * q + r;
@@ -557,11 +557,11 @@ __device__ __forceinline__ void rg2kg_bwd_owner_body(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, x = lane & 15, q = lane >> 4;
   const float* kvb = KV + (size_t)b * Nk * 2 * H;
   const Frag8 vf = load_row8(kvb + (size_t)min(x, Nk - 1) * 2 * H + H + h * DH, q, x < Nk);
-  f4 kb[2], dKa[2], dVa[2];
+  f32x4 kb[2], dKa[2], dVa[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     kb[n] = load_col4(kvb + h * DH + 16 * n, (size_t)2 * H, 0, q, Nk - 1, x);   // K_h[key 4q+e][16n + x]
-    dKa[n] = f4{0.f, 0.f, 0.f, 0.f}; dVa[n] = f4{0.f, 0.f, 0.f, 0.f};
+    dKa[n] = f32x4{0.f, 0.f, 0.f, 0.f}; dVa[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   static_assert(MAXT % TPW == 0, "tile groups");
 #pragma unroll 1

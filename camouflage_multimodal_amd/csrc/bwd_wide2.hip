@@ -48,21 +48,6 @@ struct CfgB {
   static_assert(LDS <= 81920, "two blocks per CU");
 };
 
-// Softmax over the <= 16 keys of one RG row -- the code of fused_rows.hip (rg_softmax), which the saved probabilities' consumers share
-__device__ __forceinline__ void rg_softmax(const f32x16& Sc, int h, int Nk, float (&p)[8]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = acc_row(i, h) < Nk ? Sc[i] : -INFINITY; m = fmaxf(m, p[i]); }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - m); sum += p[i]; }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) p[i] *= inv;
-}
-
 template <int DEPTH, bool DROP, int NT>
 __global__ __launch_bounds__(CfgB<NT>::NTHB, CfgB<NT>::NWB / 2) void bwd1w_kernel(const Bwd1Args a) {      // (HIP: threads per block, min WAVES PER SIMD -- two blocks per CU)
   using C = CfgB<NT>;
@@ -467,12 +452,7 @@ __global__ __launch_bounds__(CfgB<NT>::NTHB, CfgB<NT>::NWB / 2) void bwd1w_kerne
 
 template <int DEPTH, bool DROP, int NT>
 int bwd1w_launch(const Bwd1Args& a, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd1w_kernel<DEPTH, DROP, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, CfgB<NT>::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((bwd1w_kernel<DEPTH, DROP, NT>), dim3((a.rg_tiles_max + RT - 1) / RT), dim3(CfgB<NT>::NTHB), CfgB<NT>::LDS, stream, a);
+  launch_lds<bwd1w_kernel<DEPTH, DROP, NT>>(dim3((a.rg_tiles_max + RT - 1) / RT), dim3(CfgB<NT>::NTHB), CfgB<NT>::LDS, stream, a);
   return (int)hipGetLastError();
 }
 
@@ -652,16 +632,10 @@ int launch_wide2_bwd2(Bwd2Args& a, hipStream_t stream) {
   if (a.B < 1 || a.Nk < 1 || a.Nk > 16 || a.rg_tiles_max < 1 || !a.Q2_16 || !a.dO2_16 || !a.lse2 || !a.delta2 || !a.KV2_16 || !a.dQKV16 || !a.dQ2acc || !a.dKV ||
       !a.dQKVkg16 || !a.tile_desc)
     return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd2w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, CfgC::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd2w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CfgC::LDS);
-    return true;
-  }();
-  (void)attr;
   const int prof = gemm_prof_open(stream, 10.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BWD2);
   const dim3 grid((a.rg_tiles_max + RT - 1) / RT);
-  if (a.drop.p > 0.f) hipLaunchKernelGGL(bwd2w_kernel<true>, grid, dim3(512), CfgC::LDS, stream, a);
-  else                hipLaunchKernelGGL(bwd2w_kernel<false>, grid, dim3(512), CfgC::LDS, stream, a);
+  if (a.drop.p > 0.f) launch_lds<bwd2w_kernel<true>>(grid, dim3(512), CfgC::LDS, stream, a);
+  else                launch_lds<bwd2w_kernel<false>>(grid, dim3(512), CfgC::LDS, stream, a);
   hipLaunchKernelGGL(bwd2w_finish_kernel, dim3(a.B), dim3(256), 0, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();

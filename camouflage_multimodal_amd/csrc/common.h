@@ -98,3 +98,17 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
+
+// Launch of a kernel that asks for more dynamic LDS than a kernel gets without opting in: the opt-in attribute is set once per
+// process for each kernel instantiation, before its first launch, and never again (the call takes a driver lock; per launch it
+// would sit on the host's critical path).  `lds` is a constant of the instantiation.  Argument checks and the profiling brackets
+// stay with the caller.
+template <auto Kernel, class... A>
+void launch_lds(dim3 grid, dim3 block, int lds, hipStream_t stream, const A&... args) {
+  static const bool attr = [lds] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    return true;
+  }();
+  (void)attr;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+}

@@ -17,31 +17,9 @@
 #include "fused_rows.h"
 #include "shadow_inl.h"
 #include "gemm.h"      // launch timing hooks (gemm_prof_open / close)
+#include "mfma_inl.h"  // fragment types and helpers, acc_row, store16_wt, rg_softmax, tile pitches
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) { return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}; }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __uint_as_float(v & 0xFFFF0000u); }
-// accumulator register r of lane half h holds row (r & 3) + 8 (r >> 2) + 4 h of the 32x32 tile
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- one linear layer of a tile: acc[t] (+)= sum over KS k steps.  `wp` = the wave's fragment stream + lane (16-byte
 // units: fragment i of the stream is wp[64 i]); `act` = LDS address of this lane's first activation fragment (row
@@ -96,12 +74,6 @@ __device__ __forceinline__ void stamp(unsigned long long* stamps, int k) {
 }
 
 // rows [0, nrows) of a bf16 LDS tile -> global, 16 bytes per thread, whole rows contiguous (LOG2C: log2 of 16-byte chunks per row)
-// 16-byte write-through store (sc0 sc1): the bytes go to memory as they are issued instead of staying dirty in this XCD's L2
-// until the end-of-kernel write-back, which then has that much less to do before the next launch may start
-// (tile outputs of one training step: ~60 MB; measured -2.5 us per step at B = 16)
-__device__ __forceinline__ void store16_wt(void* p, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");   // (s_nop: the data registers may be rewritten right behind an asm store)
-}
 template <int LOG2C>
 __device__ __forceinline__ void copy_out(const char* lds, int pitch, int col_byte0, us16* dst, int ld, size_t row0, int nrows) {
   for (int c = threadIdx.x; c < (32 << LOG2C); c += 256) {
@@ -128,9 +100,6 @@ __global__ __launch_bounds__(256) void shadow_kernel(const ShadowBatch sb, int t
 }
 
 // ------------------------------------------------------------------------------------------------ forward, front half
-constexpr int PX = 272;     // row pitch (bytes) of the [32][128] bf16 input tile: 256 + 16
-constexpr int PR = 528;     // ... of a [32][256] bf16 tile: a ds_read_b128 lane group's 16 rows land on 16 distinct bank quads
-constexpr int PQ = 1552;    // ... of the [32][768] bf16 [q | k' | v'] tile
 constexpr int F_BUFR = 32 * PX, F_BUFQ = F_BUFR + 32 * PR, F_LDS = F_BUFQ + 32 * PQ;      // 8704, 25600, 75264
 
 template <int DEPTH, bool ROT>
@@ -213,7 +182,6 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
 // LDS map (bytes).  Region A is the attention scratch and, once the attention and the out-projection are done with it, the
 // fp32 tile of the LayerNorm output whose columns are summed for the mean pool.
 constexpr int PK = 528;      // RG tile: the sample's 16 key rows [16][256] (ds_read_b128 fragments: rows 4 banks apart)
-constexpr int PV = 576;      // RG tile: the sample's 16 value rows [16][256] (transposing reads: rows 16 banks apart)
 constexpr int PVC = 192;     // KG block: a wave's 32-row x 64-feature value chunk (transposing reads)
 constexpr int PT = 260;      // fp32 tile pitch (floats)
 constexpr int B_VS = 16 * PK;                       // 8448
@@ -228,22 +196,6 @@ template <> struct BackL<2> { static constexpr int XH = 0, O = 32 * PT * 4, Y = 
 template <> struct BackL<3> { static constexpr int Y = 0, XH = 32 * PR, O = 2 * 32 * PR, RED = O + 32 * PR, LDS = RED + 1024; };             // 0, 16896, 33792, 50688, 51712
 constexpr int B_LDS = BackL<2>::LDS;
 static_assert(BackL<3>::O >= 4 * 32 * 192 && BackL<3>::O >= 8448 + 9216 && BackL<2>::O >= 4 * 32 * 192, "attention scratch inside region A");
-
-// Softmax over the <= 16 keys of one RG row: S holds the (pre-scaled) scores of keys acc_row(i, h), i < 8, in this lane
-// and the other 8 keys in lane ^ 32.  p = probabilities (0 for keys >= Nk).  Forward and backward run this same code.
-__device__ __forceinline__ void rg_softmax(const f32x16& S, int h, int Nk, float (&p)[8]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = acc_row(i, h) < Nk ? S[i] : -INFINITY; m = fmaxf(m, p[i]); }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - m); sum += p[i]; }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) p[i] *= inv;
-}
 
 // RG tile: rows [row0, row0 + nrows) of sample b against its Nk keys; wave w owns heads 2w, 2w+1.  Leaves the attention
 // output (bf16) in bufO.
@@ -1505,18 +1457,11 @@ int launch_fused_front(FrontArgs& a, int variant, hipStream_t stream) {
   if (a.nzero < 0 || a.nzero > FUSED_FRONT_MAXZ) return (int)hipErrorInvalidValue;
   for (int i = 0; i < a.nzero; ++i)
     if (!a.zero_ptr[i] || !al16(a.zero_ptr[i]) || (a.zero_bytes[i] & 15)) return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&front_kernel<12, false>), hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&front_kernel<12, true>), hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&front_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-    return true;
-  }();
-  (void)attr;
   // executed FLOPs: per row 128 -> 256 and 256 -> 768
   const int prof = gemm_prof_open(stream, 2.0 * ((double)a.s[0].M + a.s[1].M) * (128.0 * 256.0 + 256.0 * 768.0), PROF_FRONT);
-  if (variant == 0)      hipLaunchKernelGGL((front_kernel<12, false>), dim3(total), dim3(256), F_LDS, stream, a);
-  else if (variant == 2) hipLaunchKernelGGL((front_kernel<16, true>), dim3(total), dim3(256), F_LDS, stream, a);
-  else                   hipLaunchKernelGGL((front_kernel<12, true>), dim3(total), dim3(256), F_LDS, stream, a);
+  if (variant == 0)      launch_lds<front_kernel<12, false>>(dim3(total), dim3(256), F_LDS, stream, a);
+  else if (variant != 2) launch_lds<front_kernel<12, true>>(dim3(total), dim3(256), F_LDS, stream, a);
+  else                   launch_lds<front_kernel<16, true>>(dim3(total), dim3(256), F_LDS, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
@@ -1531,23 +1476,16 @@ int launch_fused_back(BackArgs& a, int variant, int lead_mode, hipStream_t strea
     if (a.save && (!S.O16 || !S.Y16 || !S.XH16 || !S.rstd || !S.mask)) return (int)hipErrorInvalidValue;
     if (!al16(S.bo) || !al16(S.ln_g) || !al16(S.ln_b) || !al16(S.Wo) || !al16(S.W1) || !al16(S.R16)) return (int)hipErrorInvalidValue;
   }
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&back_kernel<12, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, BackL<2>::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&back_kernel<12, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, BackL<2>::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&back_kernel<12, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BackL<3>::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&back_kernel<16, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, BackL<2>::LDS);
-    return true;
-  }();
-  (void)attr;
   const dim3 grid(a.B * a.max_splits + a.rg_tiles_max);
   a.lead_tiles = (lead_mode != 0 && a.rows_rg / 32 >= 256 && (int)grid.x > 512) ? 256 : 0;      // (rows / 32 <= number of real tiles)
   // executed FLOPs per row: out-projection 256 -> 256, FFN layer 0 256 -> 512, both attention directions (2 x 2 x Nk x 256)
   const double rows = (double)a.rows_rg + (double)a.B * a.Nk;
   const int prof = gemm_prof_open(stream, 2.0 * rows * (256.0 * 256.0 + 256.0 * 512.0) + 8.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BACK);
-  if (variant == 0)        hipLaunchKernelGGL((back_kernel<12, false, 2>), grid, dim3(256), BackL<2>::LDS, stream, a);
-  else if (variant == 2)   hipLaunchKernelGGL((back_kernel<16, true, 2>), grid, dim3(256), BackL<2>::LDS, stream, a);
-  else if (grid.x > 512u)  hipLaunchKernelGGL((back_kernel<12, true, 3>), grid, dim3(256), BackL<3>::LDS, stream, a);
-  else                     hipLaunchKernelGGL((back_kernel<12, true, 2>), grid, dim3(256), BackL<2>::LDS, stream, a);
+  if (variant == 0)        launch_lds<back_kernel<12, false, 2>>(grid, dim3(256), BackL<2>::LDS, stream, a);
+  else if (variant != 2) {
+    if (grid.x <= 512u)    launch_lds<back_kernel<12, true, 2>>(grid, dim3(256), BackL<2>::LDS, stream, a);
+    else                   launch_lds<back_kernel<12, true, 3>>(grid, dim3(256), BackL<3>::LDS, stream, a);
+  } else                   launch_lds<back_kernel<16, true, 2>>(grid, dim3(256), BackL<2>::LDS, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
@@ -1565,12 +1503,6 @@ int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only)
     if (!al16(S.W1T) || !al16(S.WoT) || !al16(S.mask) || !al16(S.ln_g) || !al16(S.dcomb) || (S.ld_dcomb & 3) || !al16(S.dH16) || !al16(S.dU16))
       return (int)hipErrorInvalidValue;
   }
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd1_kernel<12, false>), hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd1_kernel<12, true>), hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS);
-    return true;
-  }();
-  (void)attr;
   // kg_only (launch_wide2_bwd1 takes the RG rows, their dH16 included): no RG tile blocks, writer blocks for the KG stream's rows only
   a.writer_first_row = kg_only ? a.rows_rg : 0;
   a.writer_blocks = (a.rows_rg + a.B * a.Nk - a.writer_first_row + 15) / 16;   // four rows per wave per pass (see the kernel; eight: the same at B = 64, -5 us at B = 256)
@@ -1594,8 +1526,8 @@ int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only)
   // executed FLOPs per row: dY (512 -> 256), dO (256 -> 256); RG rows: the RG->KG attention backward (5 products of Nk x 256)
   const double rows = (kg_only ? 0.0 : (double)a.rows_rg) + (double)a.B * a.Nk;
   const int prof = gemm_prof_open(stream, 2.0 * rows * (512.0 * 256.0 + 256.0 * 256.0) + (kg_only ? 0.0 : 10.0 * (double)a.rows_rg * a.Nk * 256.0), PROF_BWD1);
-  if (variant == 0) hipLaunchKernelGGL((bwd1_kernel<12, false>), grid, dim3(256), W_LDS, stream, k);
-  else              hipLaunchKernelGGL((bwd1_kernel<12, true>), grid, dim3(256), W_LDS, stream, k);
+  if (variant == 0) launch_lds<bwd1_kernel<12, false>>(grid, dim3(256), W_LDS, stream, k);
+  else              launch_lds<bwd1_kernel<12, true>>(grid, dim3(256), W_LDS, stream, k);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
@@ -1608,19 +1540,13 @@ int launch_fused_bwd2(Bwd2Args& a, int variant, hipStream_t stream) {
       !a.dU16 || !a.WcRgT || !a.dR16 || !a.dQ2acc || !a.dKV || !a.dU2_16 || !a.WcKgT || !a.dQKVkg16 || !a.dG16 || !a.dGpart || !a.tickets || !a.off || !a.tile_off || !a.tile_desc)
     return (int)hipErrorInvalidValue;
   if (!al16(a.dQKV16) || !al16(a.dQKVkg16) || !al16(a.WcRgT) || !al16(a.WcKgT) || !al16(a.dQ2acc) || !al16(a.dKV)) return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd2_kernel<12, false>), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd2p_kernel<12, false>), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS);
-    return true;
-  }();
-  (void)attr;
   // executed FLOPs per row: dR / dG (768 -> 256) unless the caller takes those gradients in parameter space; RG rows: the KG->RG
   // attention backward (5 products of Nk x 256)
   const double rows = (double)a.rows_rg + (double)a.B * a.Nk;
   const int prof = gemm_prof_open(stream, (a.param_space ? 0.0 : 2.0 * rows * 768.0 * 256.0) + 10.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BWD2);
   if (!a.param_space) a.split_finish = 0;
-  if (a.param_space) hipLaunchKernelGGL((bwd2p_kernel<12, false>), dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
-  else               hipLaunchKernelGGL((bwd2_kernel<12, false>), dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
+  if (!a.param_space) launch_lds<bwd2_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
+  else                launch_lds<bwd2p_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
   if (a.split_finish) hipLaunchKernelGGL(bwd2_finish_kernel, dim3(a.B), dim3(256), 0, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();

@@ -21,31 +21,10 @@
 #include "fused_rows.h"
 #include "shadow_inl.h"
 #include "gemm.h"      // launch timing hooks
+#include "mfma_inl.h"  // fragment types and helpers, acc_row, store16_wt, rg_softmax, tile pitches
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) { return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}; }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __uint_as_float(v & 0xFFFF0000u); }
-// accumulator register r of lane half h holds row (r & 3) + 8 (r >> 2) + 4 h of the 32x32 tile
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 // Developer timeline (testing hook "stamps"): lane 0 of every wave records the 100 MHz wall clock at phase boundaries:
 // stamps[(block * 8 + wave) * 16 + k].  Product calls pass null and execute none of it.
 __device__ __forceinline__ void stamp(unsigned long long* stamps, int k) {
@@ -56,16 +35,9 @@ __device__ __forceinline__ void stamp(unsigned long long* stamps, int k) {
     if (k == 12) p[15] = __builtin_amdgcn_s_memtime();       // the clock the CU actually ran at = their difference / the wall-clock interval
   }
 }
-__device__ __forceinline__ void store16_wt(void* p, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");   // (s_nop: the data registers may be rewritten right behind an asm store)
-}
 
 constexpr int NW = 8;        // waves per block
 constexpr int NTH = 64 * NW;
-constexpr int PX = 272;      // row pitch (bytes) of a [rows][128] bf16 tile
-constexpr int PR = 528;      // ... of a [rows][256] bf16 tile (a ds_read_b128 lane group's 16 rows land on 16 distinct bank quads)
-constexpr int PQ = 1552;     // ... of a [rows][768] bf16 tile
-constexpr int PV = 576;      // the 16 value rows of a sample [16][256] (transposing reads: rows 16 banks apart)
 
 // ---- one linear layer over RT sub-tiles: acc[s][t] (+)= sum over KS k steps.  `wp` = this wave's first fragment + lane (16-byte
 // units); fragment (ks, t) is wp[64 (ks KST + t)] (KST = tiles per k step in the shadow's 4-wave layout).  frag(s, ks) = this
@@ -279,22 +251,6 @@ __global__ __launch_bounds__(NTH, 2) void front8_kernel(const FrontArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward, back half
-// Softmax over the <= 16 keys of one RG row: S holds the (pre-scaled) scores of keys acc_row(i, h), i < 8, in this lane
-// and the other 8 keys in lane ^ 32.  (The same code as fused_rows.hip: backward recomputes these probabilities.)
-__device__ __forceinline__ void rg_softmax(const f32x16& S, int h, int Nk, float (&p)[8]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = acc_row(i, h) < Nk ? S[i] : -INFINITY; m = fmaxf(m, p[i]); }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { p[i] = __expf(p[i] - m); sum += p[i]; }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) p[i] *= inv;
-}
-
 constexpr int PART_FLOATS = 16 + 16 + 16 * 32;      // per (segment, head): max[16], sum[16], Z[16][32]
 static_assert(PART_FLOATS == FUSED_PART_FLOATS, "fused_rows.h");
 
@@ -1159,22 +1115,12 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int RT>
 int front8_launch(FrontArgs& a, int total, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&front8_kernel<RT, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, FrontCfg<RT>::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((front8_kernel<RT, 12>), dim3(total), dim3(NTH), FrontCfg<RT>::LDS, stream, a);
+  launch_lds<front8_kernel<RT, 12>>(dim3(total), dim3(NTH), FrontCfg<RT>::LDS, stream, a);
   return 0;
 }
 template <int RT, bool DROP, bool SAVE>
 int back8_launch2(BackArgs& a, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&back8_kernel<RT, 8, DROP, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, BackCfg<RT>::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((back8_kernel<RT, 8, DROP, SAVE>), dim3((a.rg_tiles_max + RT - 1) / RT), dim3(NTH), BackCfg<RT>::LDS, stream, a);
+  launch_lds<back8_kernel<RT, 8, DROP, SAVE>>(dim3((a.rg_tiles_max + RT - 1) / RT), dim3(NTH), BackCfg<RT>::LDS, stream, a);
   return 0;
 }
 // dropout and the saved-for-backward set are compile-time variants: as run-time flags they were two branches per ELEMENT of every epilogue
@@ -1187,12 +1133,7 @@ int back8_launch(BackArgs& a, hipStream_t stream) {
 
 template <int RT, bool DROP, bool SAVE>
 int rgfwd_launch2(RgFwdArgs& g, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rgfwd_kernel<RT, DROP, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, RgCfg<RT>::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((rgfwd_kernel<RT, DROP, SAVE>), dim3((g.b.rg_tiles_max + RT - 1) / RT), dim3(NTH), RgCfg<RT>::LDS, stream, g);
+  launch_lds<rgfwd_kernel<RT, DROP, SAVE>>(dim3((g.b.rg_tiles_max + RT - 1) / RT), dim3(NTH), RgCfg<RT>::LDS, stream, g);
   return 0;
 }
 template <int RT>

@@ -850,21 +850,11 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int DEPTH, bool FOLD, bool DROP, bool SAVE>
 void wide2_launch(const RgFwd2Args& g, dim3 grid, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rgfwd2_kernel<DEPTH, FOLD, DROP, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((rgfwd2_kernel<DEPTH, FOLD, DROP, SAVE>), grid, dim3(NTH), Cfg::LDS, stream, g);
+  launch_lds<rgfwd2_kernel<DEPTH, FOLD, DROP, SAVE>>(grid, dim3(NTH), Cfg::LDS, stream, g);
 }
 template <int DEPTH, bool DROP, bool SAVE>
 void kgchain_launch(const KgChainArgs& k, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kgchain_kernel<DEPTH, DROP, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((kgchain_kernel<DEPTH, DROP, SAVE>), dim3((k.b.B + 1) / 2), dim3(NTH), Cfg::LDS, stream, k);
+  launch_lds<kgchain_kernel<DEPTH, DROP, SAVE>>(dim3((k.b.B + 1) / 2), dim3(NTH), Cfg::LDS, stream, k);
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 // The MFMA k-slot a lane half feeds is arbitrary as long as A and B agree: lane half h of
 // step s takes k = 16h + s (f32) or the 8 k's [16*step + 8h, +8) (bf16).
 #include "gemm.h"
+#include "mfma_inl.h"   // f32x16, bf16x8, f32x4
 
 #include <vector>
 
@@ -34,9 +35,6 @@ constexpr int B_F32 = (BN * LDM > BK * LDKB) ? BN * LDM : BK * LDKB;   // 4608 f
 constexpr int LDH = BK + 8;    // bf16 row stride (elements): 40 -> 80 B
 constexpr int A_BF16 = BM * LDH;   // elements (ushort)
 constexpr int B_BF16 = BN * LDH;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 // Guarded loads, branch-free BY CONSTRUCTION.  hipcc turns "cond ? load : 0" into a branch around
 // the load plus a vmcnt(0) wait per element (one memory round trip each; the first version of this
@@ -531,7 +529,6 @@ __global__ __launch_bounds__(256, (PIPE <= 2 ? 2 : 1)) void gemm_grouped_kernel(
 //   * dW += dy^T.x      (K <= 64): one wave per tile, 4 tiles per block.
 // Lane (x = lane & 15, q = lane >> 4) of MFMA step e within a 16-deep k block feeds k = 4q + e for
 // both operands, so a lane's four steps come from one 16-B load where the source is k-contiguous.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One 16x16 tile (or, for dW problems, NW tiles: one per wave) of skinny problem P; `local` = tile index within
 // the problem.  Every thread returns normally.

@@ -19,6 +19,7 @@
 // one output row -> 16-byte fp32 stores and 8-byte bf16 stores; TN keeps C orientation for its fp32 atomics
 // (a wave-instruction covers 128 contiguous bytes of two rows).
 #include "gemm16.h"
+#include "mfma_inl.h"   // fragment types, lds_tr16
 
 
 namespace {
@@ -31,11 +32,6 @@ constexpr int A_TN_BYTES = BK * PKA;    // 12288
 constexpr int NT_BUF_BYTES = (BM + BN) * PM;   // 24576: two stages = 48 KB, three blocks per CU
 constexpr int BUF_BYTES = 32768;        // TN stage: 12288 + 64*320
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 struct Stage { u32x4 a[2], b[4]; };
 
 // act chunk (8 bf16) + 8 gradient values -> 8 bf16 of (act > 0 ? g * scale : 0)
@@ -47,10 +43,6 @@ __device__ __forceinline__ u32x4 virt_chunk(u32x4 act, float4 g0, float4 g1, flo
   o.z = pack2(sel(act.z << 16, g1.x), sel(act.z & 0xFFFF0000u, g1.y));
   o.w = pack2(sel(act.w << 16, g1.z), sel(act.w & 0xFFFF0000u, g1.w));
   return o;
-}
-
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
 // The staged-K loop shared by both layouts.  Straight-line on purpose (see gemm.hip, PIPELINE_LOOP): every
@@ -774,17 +766,12 @@ static int launch_tnbig(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
     if (kn.tn_kcap > 0 || total >= 224 || kcap <= 4) break;         // ~ one block per CU
   }
   gb.n_heavy = 0; gb.exp = kn.exp;
-  static const bool attr_ok = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_tnbig_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GBUF_BYTES);
-    return true;
-  }();
-  (void)attr_ok;
   double fl = 0.0;
   for (int i = 0; i < gb.n; ++i) fl += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
   const int prof = gemm_prof_open(stream, fl);
   // (four register stages measured the same as two: the K loop is bound by its LDS transposing reads -- SQ_ACTIVE_INST_LDS 80 % of
   // the kernel's busy cycles, no bank conflicts -- not by load latency)
-  hipLaunchKernelGGL((gemm16_tnbig_kernel<2>), dim3(total), dim3(512), 2 * GBUF_BYTES, stream, gb, total);
+  launch_lds<gemm16_tnbig_kernel<2>>(dim3(total), dim3(512), 2 * GBUF_BYTES, stream, gb, total);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
@@ -872,20 +859,15 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
       return (int)hipErrorInvalidValue;
   }
   if (has_virt && !has_rows) return (int)hipErrorInvalidValue;      // the virtual operand lives in the whole-row kernel only
-  const size_t lds = has_rows ? 2 * ROW_BUF_BYTES : (has_tn ? 2 * BUF_BYTES : 2 * NT_BUF_BYTES);     // 72 / 64 / 48 KB
-  static const bool attr_ok = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ROW_BUF_BYTES);
-    return true;
-  }();
-  (void)attr_ok;
   double fl = 0.0;
   for (int i = 0; i < gb.n; ++i) fl += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
   const int prof = gemm_prof_open(stream, fl);
   // two register stages (four measured slower on every launch of the step; round 2: a weight-gradient-only kernel with four
   // stages at two blocks per CU, 184 VGPRs, no spills: +1 us on the fused schedule's weight-gradient launch)
-  if (has_rows) hipLaunchKernelGGL((gemm16_kernel<2, true>), dim3(total), dim3(256), lds, stream, gb, total);
-  else          hipLaunchKernelGGL((gemm16_kernel<2, false>), dim3(total), dim3(256), lds, stream, gb, total);
+  // dynamic LDS: whole-row problems 72 KB, k-major (TN) ones 64 KB, the rest 48 KB (which needs no opt-in)
+  if (!has_rows && !has_tn) hipLaunchKernelGGL((gemm16_kernel<2, false>), dim3(total), dim3(256), 2 * NT_BUF_BYTES, stream, gb, total);
+  else if (!has_rows)       launch_lds<gemm16_kernel<2, false>>(dim3(total), dim3(256), 2 * BUF_BYTES, stream, gb, total);
+  else                      launch_lds<gemm16_kernel<2, true>>(dim3(total), dim3(256), 2 * ROW_BUF_BYTES, stream, gb, total);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }

@@ -1456,13 +1456,8 @@ int tail_fused_ok(int B, int C) { return tail_fused_ok(B, C, device_cus()); }
 int launch_tail_fused(const TailFusedArgs& a, hipStream_t stream) {
   if (!tail_fused_ok(a.B, a.C)) return (int)hipErrorInvalidValue;
   if (a.mode && (!a.comb_out || !a.F1_out || !a.fused_out || !a.dhid_out || !a.dfused_out || !a.dF1_out)) return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TF_LDS_FLOATS * 4);
-    return true;
-  }();
-  (void)attr;
   const int prof = gemm_prof_open(stream, 0.0, PROF_TAIL);
-  hipLaunchKernelGGL(tail_fused_kernel, dim3(TG * ((a.B + TF_MAXB - 1) / TF_MAXB)), dim3(TF_THREADS), TF_LDS_FLOATS * 4, stream, a);
+  launch_lds<tail_fused_kernel>(dim3(TG * ((a.B + TF_MAXB - 1) / TF_MAXB)), dim3(TF_THREADS), TF_LDS_FLOATS * 4, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }

@@ -10,28 +10,15 @@
 // accumulation -- the dropped x_lo W_lo term is 2^-18 relative.
 #include "tail_wide.h"
 #include "gemm.h"      // launch timing hooks
+#include "mfma_inl.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-__device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
 // two values -> their packed hi and lo planes
 struct HiLo { uint32_t hi, lo; };
 __device__ __forceinline__ HiLo split2(float a, float b) {
   const uint32_t ha = f2bf(a), hb = f2bf(b);
-  return HiLo{ha | (hb << 16), pack2(a - bf2f(ha), b - bf2f(hb))};
+  return HiLo{ha | (hb << 16), pack2(a - bf_lo(ha), b - bf_lo(hb))};
 }
 
 constexpr int NW = 8, NTH = 64 * NW, TS = 32;
@@ -376,16 +363,10 @@ int launch_tail_wide(const TailWideArgs& a, hipStream_t stream) {
       !a.Tfu0h || !a.Tfu0l || !a.Tfu3h || !a.Tfu3l || !a.Th0h || !a.Th0l || !a.b13 || !a.b23 || !a.bfu0 || !a.bfu3)
     return (int)hipErrorInvalidValue;
   for (int x = 0; x < 4; ++x) if (!a.bh0[x] || !a.Wh3[x] || !a.bh3[x]) return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tailw_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tailw_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    return true;
-  }();
-  (void)attr;
   const int prof = gemm_prof_open(stream, 2.0 * a.B * (2.0 * 512 * 256 + 512 * 256 + 256 * 256 + 256 * 512) * 3.0, PROF_TAIL);
   const dim3 grid((a.B + TS - 1) / TS);
-  if (a.drop.p > 0.f) hipLaunchKernelGGL((tailw_fwd_kernel<true>), grid, dim3(NTH), LDS_BYTES, stream, a);
-  else                hipLaunchKernelGGL((tailw_fwd_kernel<false>), grid, dim3(NTH), LDS_BYTES, stream, a);
+  if (!(a.drop.p > 0.f)) launch_lds<tailw_fwd_kernel<false>>(grid, dim3(NTH), LDS_BYTES, stream, a);
+  else                   launch_lds<tailw_fwd_kernel<true>>(grid, dim3(NTH), LDS_BYTES, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }
@@ -394,13 +375,8 @@ int launch_tail_wide_bwd(const TailWideBwdArgs& a, hipStream_t stream) {
   if (a.B < 1 || !a.dhid || !a.F1 || !a.Th0h || !a.Th0l || !a.Tfu3h || !a.Tfu3l || !a.Tfu0h || !a.Tfu0l || !a.T13h || !a.T13l || !a.T23h || !a.T23l ||
       !a.dfused || !a.dF1 || !a.dcomb || !a.dHm1 || !a.dHm2)
     return (int)hipErrorInvalidValue;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tailw_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF);
-    return true;
-  }();
-  (void)attr;
   const int prof = gemm_prof_open(stream, 2.0 * a.B * (512.0 * 256 + 256.0 * 256 + 3.0 * 256 * 512) * 3.0, PROF_TAIL);
-  hipLaunchKernelGGL(tailw_bwd_kernel, dim3((a.B + TS - 1) / TS), dim3(NTH), 2 * BUF, stream, a);
+  launch_lds<tailw_bwd_kernel>(dim3((a.B + TS - 1) / TS), dim3(NTH), 2 * BUF, stream, a);
   gemm_prof_close(prof, stream);
   return (int)hipGetLastError();
 }

@@ -1,38 +1,15 @@
-// Shared device helpers of the 64-row half-block kernels (fused_wide2.hip: forward; bwd_wide2.hip: backward, first half): MFMA fragment
-// types, the weight-stream stage (buffer loads with scalar offsets), per-register constant vectors, the developer timeline stamp and
-// the late kernel-argument pointer loads.  Everything sits in an anonymous namespace: include once per translation unit.
+// Shared device helpers of the 64-row half-block kernels (fused_wide2.hip: forward; bwd_wide2.hip: backward, first half): the
+// weight-stream stage (buffer loads with scalar offsets), per-register constant vectors, the developer timeline stamp and the late
+// kernel-argument pointer loads, on top of the fragment vocabulary of mfma_inl.h.  Everything sits in an anonymous namespace: include
+// once per translation unit.
 #pragma once
 #include "fused_rows.h"
+#include "mfma_inl.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 join(s16x4 lo, s16x4 hi) { return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}; }
-__device__ __forceinline__ f32x16 splat16(float v) {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = v;
-  return z;
-}
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __uint_as_float(v & 0xFFFF0000u); }
-// accumulator register r of lane half h holds row (r & 3) + 8 (r >> 2) + 4 h of the 32x32 tile
-__device__ __forceinline__ constexpr int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 __device__ __forceinline__ u32x4 pack8(const f32x16& a, int k) {
   return u32x4{pack2(a[8 * k], a[8 * k + 1]), pack2(a[8 * k + 2], a[8 * k + 3]), pack2(a[8 * k + 4], a[8 * k + 5]), pack2(a[8 * k + 6], a[8 * k + 7])};
-}
-__device__ __forceinline__ void store16_wt(void* p, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 // Developer timeline (testing hook "stamps"): lane 0 of every wave records the 100 MHz wall clock at phase boundaries:
 // stamps[(block * 8 + wave) * 16 + k] (the 8-wave kernels' layout: waves 4..7 of a block stay empty here).
@@ -51,8 +28,6 @@ constexpr int NW = 4;        // waves per block
 constexpr int NTH = 64 * NW;
 constexpr int RT = 2;        // 32-row sub-tiles per block
 constexpr int ROWS = 32 * RT;
-constexpr int PX = 272;      // row pitch (bytes) of a [rows][128] bf16 tile
-constexpr int PR = 528;      // ... of a [rows][256] bf16 tile (a ds_read_b128 lane group's 16 rows land on 16 distinct bank quads)
 constexpr int PS = 144;      // row pitch (bytes) of a strip [rows][64]: 16 rows of a ds_read_b128 lane group land on 16 distinct 16-byte slots
 // KG->RG partial of one (segment, head), this file's layout inside the workspace's partial buffer (sized for the other kernels'
 // FUSED_PART_FLOATS = 544 floats per slot): max[16] fp32 (log2 units) | sum[16] fp32 | Z[16 queries][32 features] BF16 -- the partials
@@ -95,36 +70,8 @@ struct Stage {
     for (int i = 0; i < D; ++i) buf[i] = load(i);
   }
   // W_IS_A: the weights are the A operand (accumulator: lane = tile row, registers = features) -- else the B operand (lane = feature,
-  // registers = tile rows).  init[t]: the first k step's C operand (a bias vector, or zeros).
-  template <bool W_IS_A, class F>
-  __device__ __forceinline__ void run_f(F&& frag, const f32x16 (&init)[NT], f32x16 (&acc)[RS][NT]) {
-    bf16x8 x[RS], xn[RS];
-#pragma unroll
-    for (int s = 0; s < RS; ++s) xn[s] = frag(s, 0);
-#pragma unroll
-    for (int i = 0; i < TOTAL; ++i) {
-      const int ks = i / NT, t = i % NT;
-      const bf16x8 wf = as_frag(buf[i % D]);
-      if (i + D < TOTAL) buf[i % D] = load(i + D);
-      if (t == 0) {
-#pragma unroll
-        for (int s = 0; s < RS; ++s) x[s] = xn[s];
-        if (ks + 1 < KS) {
-#pragma unroll
-          for (int s = 0; s < RS; ++s) xn[s] = frag(s, ks + 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int s = 0; s < RS; ++s) {
-        const f32x16 c = ks == 0 ? init[t] : acc[s][t];
-        if constexpr (W_IS_A) acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, x[s], c, 0, 0, 0);
-        else                  acc[s][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[s], wf, c, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // run_f with a C operand per (sub-tile, feature tile): initf(s, t) (the backward's first product starts from a per-sample vector)
+  // registers = tile rows).  frag(s, ks): this lane's activation fragment of sub-tile s, k step ks.  initf(s, t): the first k step's
+  // C operand per (sub-tile, feature tile) (the backward's first product starts from a per-sample vector).
   template <bool W_IS_A, class F, class I>
   __device__ __forceinline__ void run_fi(F&& frag, I&& initf, f32x16 (&acc)[RS][NT]) {
     bf16x8 x[RS], xn[RS];
@@ -152,6 +99,11 @@ struct Stage {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
+  // the same with one C operand per feature tile: init[t] (a bias vector, or zeros)
+  template <bool W_IS_A, class F>
+  __device__ __forceinline__ void run_f(F&& frag, const f32x16 (&init)[NT], f32x16 (&acc)[RS][NT]) {
+    run_fi<W_IS_A>(frag, [&](int, int t) { return init[t]; }, acc);
   }
   // activation tiles in LDS: `act` = address of this lane's first fragment of sub-tile 0 (row lane & 31, byte 16 (lane >> 5)),
   // sub-tile s is `sub` bytes further, k step ks 32 bytes further

@@ -1,4 +1,5 @@
-"""Executable statement of the data layouts the fused row-tile kernels (csrc/fused_rows.hip) rely on, checked on the CPU
+"""Executable statement of the data layouts the fused row-tile kernels (csrc/fused_rows.hip and the other families; the shared
+fragment helpers, ``acc_row`` and ``rg_softmax`` among them, are defined once in csrc/mfma_inl.h) rely on, checked on the CPU
 against plain matrix arithmetic with a lane-level model of the gfx950 MFMA / transposing-LDS-read semantics
 (cdna_hip_programming.md section 3: A[i = l&31][k = 8(l>>5)+j], B[k = 8(l>>5)+j][col = l&31], C/D row = (r&3)+8(r>>2)+4(l>>5),
 col = l&31; T10: ds_read_b64_tr_b16).
