@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcamo_fusion.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 FWD_INFERENCE = 1
 FLAG_ATTN_MAPS = 2
 FWD_FUSED_MAPS = 4
@@ -31,6 +31,8 @@ SYMBOLS = ("camo_abi_version", "camo_last_error", "camo_workspace_bytes", "camo_
 RG_SYMBOLS = ("camo_rg_workspace_bytes", "camo_rg_node_embeddings", "camo_rg_build_csr")
 # every symbol include/camo_rg_features.h declares
 RGF_SYMBOLS = ("camo_rg_graph_workspace_bytes", "camo_rg_region_graph")
+# every symbol include/camo_canny.h declares
+CANNY_SYMBOLS = ("camo_canny_workspace_bytes", "camo_canny", "camo_canny_hysteresis")
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -142,6 +144,12 @@ def lib():
     L.camo_rg_graph_workspace_bytes.argtypes = [i32]
     L.camo_rg_region_graph.restype = C.c_int
     L.camo_rg_region_graph.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, i32, vp, vp]
+    L.camo_canny_workspace_bytes.restype = sz
+    L.camo_canny_workspace_bytes.argtypes = [i32, i32, i32]
+    L.camo_canny.restype = C.c_int
+    L.camo_canny.argtypes = [vp, i32, i32, i32, f32, f32, f32, vp, sz, vp, vp, vp]
+    L.camo_canny_hysteresis.restype = C.c_int
+    L.camo_canny_hysteresis.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
     L.camo_debug_gemm.restype = C.c_int
     L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.camo_debug_gemm16.restype = C.c_int

@@ -28,8 +28,10 @@
 #include "misc.h"
 #include "rg_gnn.h"
 #include "rg_features.h"
+#include "canny.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
+#include "../../include/camo_canny.h"
 
 namespace {
 
@@ -1717,6 +1719,49 @@ int camo_rg_region_graph(const float* image, const int32_t* segments, const uint
   if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_rg_graph_workspace_bytes()");
   CK(launch_region_graph(image, segments, canny, H, W, n_labels, ws, x, region_map, reinterpret_cast<long long*>(edge_index), edge_attr,
                          edge_capacity, counts, static_cast<hipStream_t>(stream)), "region graph");
+  return 0;
+}
+
+static int canny_check(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if ((long long)N * H * W > CAMO_CANNY_MAX_PIXELS) return fail(CAMO_E_UNSUPPORTED, "N * H * W exceeds CAMO_CANNY_MAX_PIXELS (32-bit pixel indices)");
+  return 0;
+}
+
+size_t camo_canny_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+  if (canny_check(N, H, W)) return 0;
+  return canny_carve((size_t)N * H * W, nullptr).bytes;
+}
+
+int camo_canny(const float* images, int32_t N, int32_t H, int32_t W, float sigma, float low, float high, void* workspace,
+               size_t workspace_bytes, uint8_t* edges, float* grad, void* stream) {
+  if (int e = canny_check(N, H, W)) return e;
+  if (!(sigma > 0.f)) return fail(CAMO_E_ARG, "sigma must be > 0");
+  if (!(low > 0.f && low <= high)) return fail(CAMO_E_ARG, "need 0 < low <= high");
+  if (!images || !workspace || !edges) return fail(CAMO_E_ARG, "null pointer argument");
+  const double radius = 4.0 * (double)sigma + 0.5;
+  if (!(radius < CAMO_CANNY_MAX_RADIUS + 1)) return fail(CAMO_E_UNSUPPORTED, "the blur radius int(4 sigma + 0.5) must be <= 32");
+  const CannyWs ws = canny_carve((size_t)N * H * W, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_canny_workspace_bytes()");
+  CannyTaps taps{};
+  taps.radius = (int)radius;
+  double phi[2 * CANNY_MAX_RADIUS + 1], sum = 0.0;
+  for (int k = -taps.radius; k <= taps.radius; ++k) sum += phi[k + taps.radius] = std::exp(-0.5 / ((double)sigma * sigma) * k * k);
+  for (int k = 0; k <= 2 * taps.radius; ++k) taps.w[k] = (float)(phi[k] / sum);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* g = grad ? grad : ws.grad;
+  CK(launch_canny_gradients(images, N, H, W, taps, g, st), "canny gradients");
+  CK(launch_canny_hysteresis(g, nullptr, low, high, N, H, W, ws, edges, st), "canny hysteresis");
+  return 0;
+}
+
+int camo_canny_hysteresis(const uint8_t* cls, int32_t N, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, uint8_t* edges,
+                          void* stream) {
+  if (int e = canny_check(N, H, W)) return e;
+  if (!cls || !workspace || !edges) return fail(CAMO_E_ARG, "null pointer argument");
+  const CannyWs ws = canny_carve((size_t)N * H * W, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_canny_workspace_bytes()");
+  CK(launch_canny_hysteresis(nullptr, cls, 0.f, 0.f, N, H, W, ws, edges, static_cast<hipStream_t>(stream)), "canny hysteresis");
   return 0;
 }
 }  // extern "C"

@@ -69,18 +69,56 @@ class RegionGraphData:
     cpu = lambda self: self.to("cpu")  # noqa: E731
 
 
-def create_region_graph_from_segments(image, segments, edges_canny, device="cuda", edge_capacity=None):
+def canny_edges(images, sigma=2.0, low_threshold=0.1, high_threshold=0.2, device="cuda", return_gradients=False):
+    """``skimage.feature.canny(gray, sigma=2)`` of the reference (extract_rg_embeddings.py:151-152, luma :151 included) on the
+    device (``camo_canny``, include/camo_canny.h): ``images`` [H, W, 3] or [N, H, W, 3] float in [0, 1] -> bool tensor [H, W]
+    or [N, H, W] on the device; with ``return_gradients`` also the fp32 gradients [N, 3, H, W] = gi, gj, magnitude ([3, H, W]
+    for one image).  A tensor is used where it is (``device`` places other inputs) and must be on a HIP device.  PARITY UNPINNED,
+    see the header."""
+    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
+    _lib.require_device(img, "images")
+    img = img.to(torch.float32).contiguous()
+    single = img.dim() == 3
+    if single:
+        img = img.unsqueeze(0)
+    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
+        raise ValueError(f"need images [H, W, 3] or [N, H, W, 3], got {tuple(img.shape)}")
+    dev = img.device
+    N, H, W = img.shape[:3]
+    L = _lib.lib()
+    need = L.camo_canny_workspace_bytes(N, H, W)
+    if need == 0:
+        _lib.check(-1, "camo_canny_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    edges = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+    grad = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev) if return_gradients else None
+    with torch.cuda.device(dev):
+        rc = L.camo_canny(_ptr(img), N, H, W, float(sigma), float(low_threshold), float(high_threshold), _ptr(ws), ws.numel(),
+                          _ptr(edges), _ptr(grad), _stream_ptr(dev))
+    _lib.check(rc, "camo_canny")
+    edges = edges.to(torch.bool)
+    if single:
+        edges, grad = edges[0], (None if grad is None else grad[0])
+    return (edges, grad) if return_gradients else edges
+
+
+def create_region_graph_from_segments(image, segments, edges_canny=None, device="cuda", edge_capacity=None):
     """The body of ``create_region_graph`` (extract_rg_embeddings.py:146-246) between its skimage calls, on the device
     (``camo_rg_region_graph``, include/camo_rg_features.h): ``image`` [H, W, 3] float in [0, 1], ``segments`` [H, W] integer
-    superpixel labels (what ``slic`` returned, :144), ``edges_canny`` [H, W] bool (what ``canny`` returned, :152) ->
+    superpixel labels (what ``slic`` returned, :144), ``edges_canny`` [H, W] bool (what ``canny`` returned, :152; ``None``: computed
+    from ``image`` on the device by ``canny_edges``) ->
     (RegionGraphData on the device, region_map int32 [labels] = new index of each label or -1).  Regions are renumbered in
     increasing label order with empty labels dropped; edges come sorted by (i, j) with each followed by its reverse (the
     reference's order is networkx's iteration order: a permutation).  PARITY UNPINNED, see the header."""
     dev = torch.device(device)
     img = torch.as_tensor(image).to(device=dev, dtype=torch.float32).contiguous()
     seg = torch.as_tensor(segments).to(device=dev, dtype=torch.int32).contiguous()
-    can = torch.as_tensor(edges_canny).to(device=dev).to(torch.uint8).contiguous()
     _lib.require_device(img, "image")
+    if edges_canny is None:
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
+        edges_canny = canny_edges(img)
+    can = torch.as_tensor(edges_canny).to(device=dev).to(torch.uint8).contiguous()
     if img.dim() != 3 or img.shape[2] != 3 or seg.shape != img.shape[:2] or can.shape != img.shape[:2]:
         raise ValueError(f"need image [H, W, 3], segments [H, W], edges_canny [H, W]; got {tuple(img.shape)}, {tuple(seg.shape)}, {tuple(can.shape)}")
     H, W = seg.shape

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CAMO_ABI_VERSION 12
+#define CAMO_ABI_VERSION 13
 
 enum {
   CAMO_OK = 0,
