@@ -33,6 +33,8 @@ RG_SYMBOLS = ("camo_rg_workspace_bytes", "camo_rg_node_embeddings", "camo_rg_bui
 RGF_SYMBOLS = ("camo_rg_graph_workspace_bytes", "camo_rg_region_graph")
 # every symbol include/camo_canny.h declares
 CANNY_SYMBOLS = ("camo_canny_workspace_bytes", "camo_canny", "camo_canny_hysteresis")
+# every symbol include/camo_slic.h declares
+SLIC_SYMBOLS = ("camo_slic_grid", "camo_slic_workspace_bytes", "camo_slic", "camo_slic_preprocess", "camo_slic_assign", "camo_slic_update", "camo_slic_connect")
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -150,6 +152,20 @@ def lib():
     L.camo_canny.argtypes = [vp, i32, i32, i32, f32, f32, f32, vp, sz, vp, vp, vp]
     L.camo_canny_hysteresis.restype = C.c_int
     L.camo_canny_hysteresis.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
+    L.camo_slic_grid.restype = C.c_int
+    L.camo_slic_grid.argtypes = [i32, i32, i32, C.POINTER(i32)]
+    L.camo_slic_workspace_bytes.restype = sz
+    L.camo_slic_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.camo_slic.restype = C.c_int
+    L.camo_slic.argtypes = [vp, i32, i32, i32, i32, f32, f32, vp, sz, vp, vp, vp]
+    L.camo_slic_preprocess.restype = C.c_int
+    L.camo_slic_preprocess.argtypes = [vp, i32, i32, i32, f32, f32, vp, vp]
+    L.camo_slic_assign.restype = C.c_int
+    L.camo_slic_assign.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.camo_slic_update.restype = C.c_int
+    L.camo_slic_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.camo_slic_connect.restype = C.c_int
+    L.camo_slic_connect.argtypes = [vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
     L.camo_debug_gemm.restype = C.c_int
     L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.camo_debug_gemm16.restype = C.c_int

@@ -29,9 +29,11 @@
 #include "rg_gnn.h"
 #include "rg_features.h"
 #include "canny.h"
+#include "slic.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_canny.h"
+#include "../../include/camo_slic.h"
 
 namespace {
 
@@ -1762,6 +1764,131 @@ int camo_canny_hysteresis(const uint8_t* cls, int32_t N, int32_t H, int32_t W, v
   const CannyWs ws = canny_carve((size_t)N * H * W, workspace);
   if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_canny_workspace_bytes()");
   CK(launch_canny_hysteresis(nullptr, cls, 0.f, 0.f, N, H, W, ws, edges, static_cast<hipStream_t>(stream)), "canny hysteresis");
+  return 0;
+}
+
+// include/camo_slic.h step 4
+static int slic_grid(int H, int W, int n_segments, SlicGrid* g) {
+  if (H < 1 || W < 1 || n_segments < 1) return fail(CAMO_E_ARG, "need H >= 1, W >= 1, n_segments >= 1");
+  const long long hw = (long long)H * W;
+  if (hw > CAMO_SLIC_MAX_IMAGE_PIXELS) return fail(CAMO_E_UNSUPPORTED, "H * W exceeds CAMO_SLIC_MAX_IMAGE_PIXELS");
+  if (hw <= n_segments) return fail(CAMO_E_UNSUPPORTED, "need H * W > n_segments");
+  const double s = std::sqrt((double)hw / n_segments);
+  if ((double)std::min(H, W) < s) return fail(CAMO_E_UNSUPPORTED, "need min(H, W) >= sqrt(H * W / n_segments)");
+  g->step = (int)std::nearbyint(s);                                         // (round-half-even in the default rounding mode)
+  g->start = (int)std::floor(s / 2);
+  g->ny = (H - g->start + g->step - 1) / g->step;
+  g->nx = (W - g->start + g->step - 1) / g->step;
+  const long long K = (long long)g->ny * g->nx;
+  if (K > CAMO_RG_MAX_LABELS - 1) return fail(CAMO_E_UNSUPPORTED, "the grid has more than CAMO_RG_MAX_LABELS - 1 centroids");
+  g->K = (int)K;
+  return 0;
+}
+
+static int slic_check(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if (N > CAMO_SLIC_MAX_IMAGES) return fail(CAMO_E_UNSUPPORTED, "N exceeds CAMO_SLIC_MAX_IMAGES");
+  if ((long long)H * W > CAMO_SLIC_MAX_IMAGE_PIXELS) return fail(CAMO_E_UNSUPPORTED, "H * W exceeds CAMO_SLIC_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_SLIC_MAX_PIXELS) return fail(CAMO_E_UNSUPPORTED, "N * H * W exceeds CAMO_SLIC_MAX_PIXELS (32-bit pixel indices)");
+  return 0;
+}
+
+static int slic_taps(float compactness, float sigma, CannyTaps* taps) {
+  if (!(compactness >= CAMO_SLIC_MIN_COMPACTNESS) || !std::isfinite(compactness))
+    return fail(compactness > 0.f ? CAMO_E_UNSUPPORTED : CAMO_E_ARG, "compactness must be finite and >= CAMO_SLIC_MIN_COMPACTNESS");
+  if (!(sigma >= 0.f)) return fail(CAMO_E_ARG, "sigma must be >= 0");
+  const double radius = 4.0 * (double)sigma + 0.5;
+  if (!(radius < CAMO_SLIC_MAX_RADIUS + 1)) return fail(CAMO_E_UNSUPPORTED, "the blur radius int(4 sigma + 0.5) must be <= 32");
+  *taps = CannyTaps{};
+  taps->radius = (int)radius;
+  if (taps->radius == 0) { taps->w[0] = 1.f; return 0; }
+  double phi[2 * CANNY_MAX_RADIUS + 1], sum = 0.0;
+  for (int k = -taps->radius; k <= taps->radius; ++k) sum += phi[k + taps->radius] = std::exp(-0.5 / ((double)sigma * sigma) * k * k);
+  for (int k = 0; k <= 2 * taps->radius; ++k) taps->w[k] = (float)(phi[k] / sum);
+  return 0;
+}
+
+int camo_slic_grid(int32_t H, int32_t W, int32_t n_segments, int32_t* out) {
+  if (!out) return fail(CAMO_E_ARG, "null pointer argument");
+  SlicGrid g{};
+  if (int e = slic_grid(H, W, n_segments, &g)) return e;
+  out[0] = g.K; out[1] = g.step; out[2] = g.start; out[3] = g.ny; out[4] = g.nx;
+  return 0;
+}
+
+size_t camo_slic_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t n_segments) {
+  if (slic_check(N, H, W)) return 0;
+  if (n_segments == 0) return slic_conn_carve(N, H, W, nullptr).bytes;
+  SlicGrid g{};
+  if (slic_grid(H, W, n_segments, &g)) return 0;
+  return slic_carve(N, H, W, g.K, nullptr).bytes;
+}
+
+int camo_slic(const float* images, int32_t N, int32_t H, int32_t W, int32_t n_segments, float compactness, float sigma, void* workspace,
+              size_t workspace_bytes, int32_t* labels, int32_t* counts, void* stream) {
+  if (int e = slic_check(N, H, W)) return e;
+  SlicGrid g{};
+  if (int e = slic_grid(H, W, n_segments, &g)) return e;
+  CannyTaps taps;
+  if (int e = slic_taps(compactness, sigma, &taps)) return e;
+  if (!images || !workspace || !labels || !counts) return fail(CAMO_E_ARG, "null pointer argument");
+  const SlicWs ws = slic_carve(N, H, W, g.K, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_slic_workspace_bytes()");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CK(launch_slic_preprocess(images, N, H, W, taps, 1.0f / compactness, ws.lab, st), "slic preprocess");
+  CK(launch_slic_init(g, N, ws.cent, ws.sums, st), "slic init");
+  for (int it = 0; it < SLIC_ITERATIONS; ++it) {
+    CK(launch_slic_assign(ws.lab, ws.cent, N, H, W, g.K, g.step, ws.nearest, nullptr, st), "slic assign");
+    if (it + 1 < SLIC_ITERATIONS) CK(launch_slic_update(ws.lab, ws.nearest, N, H, W, g.K, ws.sums, ws.cent, false, st), "slic update");
+  }
+  // (connected components of equal labels: the "+ 1" of step 7 changes none of them)
+  const double segment = (double)H * W / g.K;
+  CK(launch_slic_connect(ws.nearest, N, H, W, (int)(0.5 * segment), (int)(3.0 * segment), ws.conn, labels, counts, st), "slic connect");
+  return 0;
+}
+
+int camo_slic_preprocess(const float* images, int32_t N, int32_t H, int32_t W, float compactness, float sigma, float* lab, void* stream) {
+  if (int e = slic_check(N, H, W)) return e;
+  CannyTaps taps;
+  if (int e = slic_taps(compactness, sigma, &taps)) return e;
+  if (!images || !lab) return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_slic_preprocess(images, N, H, W, taps, 1.0f / compactness, lab, static_cast<hipStream_t>(stream)), "slic preprocess");
+  return 0;
+}
+
+static int slic_k_check(int K, int step) {
+  if (K < 1 || K > CAMO_RG_MAX_LABELS - 1) return fail(CAMO_E_ARG, "K must be in [1, CAMO_RG_MAX_LABELS - 1]");
+  if (step < 1 || step > 4096) return fail(CAMO_E_ARG, "step must be in [1, 4096]");
+  return 0;
+}
+
+int camo_slic_assign(const float* lab, const float* centroids, int32_t N, int32_t H, int32_t W, int32_t K, int32_t step, int32_t* nearest,
+                     float* dist, void* stream) {
+  if (int e = slic_check(N, H, W)) return e;
+  if (int e = slic_k_check(K, step)) return e;
+  if (!lab || !centroids || !nearest || !dist) return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_slic_assign(lab, centroids, N, H, W, K, step, nearest, dist, static_cast<hipStream_t>(stream)), "slic assign");
+  return 0;
+}
+
+int camo_slic_update(const float* lab, const int32_t* nearest, int32_t N, int32_t H, int32_t W, int32_t K, int64_t* sums, float* centroids,
+                     void* stream) {
+  if (int e = slic_check(N, H, W)) return e;
+  if (int e = slic_k_check(K, 1)) return e;
+  if (!lab || !nearest || !sums || !centroids) return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_slic_update(lab, nearest, N, H, W, K, reinterpret_cast<long long*>(sums), centroids, true, static_cast<hipStream_t>(stream)),
+     "slic update");
+  return 0;
+}
+
+int camo_slic_connect(const int32_t* labels_in, int32_t N, int32_t H, int32_t W, int32_t min_size, int32_t max_size, void* workspace,
+                      size_t workspace_bytes, int32_t* labels, int32_t* counts, void* stream) {
+  if (int e = slic_check(N, H, W)) return e;
+  if (min_size < 0 || max_size < 1) return fail(CAMO_E_ARG, "need min_size >= 0 and max_size >= 1");
+  if (!labels_in || !workspace || !labels || !counts) return fail(CAMO_E_ARG, "null pointer argument");
+  const SlicConnWs ws = slic_conn_carve(N, H, W, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_slic_workspace_bytes(N, H, W, 0)");
+  CK(launch_slic_connect(labels_in, N, H, W, min_size, max_size, ws, labels, counts, static_cast<hipStream_t>(stream)), "slic connect");
   return 0;
 }
 }  // extern "C"

@@ -146,6 +146,61 @@ def create_region_graph_from_segments(image, segments, edges_canny=None, device=
     return RegionGraphData(x[:n], ei[:, :e], ea[:e].unsqueeze(1)), rmap
 
 
+def slic_segments(images, n_segments=500, compactness=10.0, sigma=1.0, device="cuda", return_counts=False):
+    """``skimage.segmentation.slic((image * 255).astype(np.uint8), n_segments, compactness=10, sigma=1)`` of the reference
+    (extract_rg_embeddings.py:143-144, the quantisation included) on the device (``camo_slic``, include/camo_slic.h): ``images``
+    [H, W, 3] or [N, H, W, 3] float in [0, 1] -> int32 labels [H, W] or [N, H, W] on the device; with ``return_counts`` also int32
+    [N, 2] ([2] for one image) = (largest label + 1, components of max_size pixels or more, which the device leaves whole).  A tensor
+    is used where it is (``device`` places other inputs) and must be on a HIP device.  PARITY UNPINNED, see the header."""
+    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
+    _lib.require_device(img, "images")
+    img = img.to(torch.float32).contiguous()
+    single = img.dim() == 3
+    if single:
+        img = img.unsqueeze(0)
+    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
+        raise ValueError(f"need images [H, W, 3] or [N, H, W, 3], got {tuple(img.shape)}")
+    dev = img.device
+    N, H, W = img.shape[:3]
+    L = _lib.lib()
+    need = L.camo_slic_workspace_bytes(N, H, W, int(n_segments))
+    if need == 0:
+        _lib.check(-1, "camo_slic_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    labels = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+    counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.camo_slic(_ptr(img), N, H, W, int(n_segments), float(compactness), float(sigma), _ptr(ws), ws.numel(), _ptr(labels),
+                         _ptr(counts), _stream_ptr(dev))
+    _lib.check(rc, "camo_slic")
+    if single:
+        labels, counts = labels[0], counts[0]
+    return (labels, counts) if return_counts else labels
+
+
+def region_graph_from_image(image, n_segments=500, device="cuda"):
+    """``create_region_graph(image, n_segments)`` of the reference (extract_rg_embeddings.py:138) with nothing on the host:
+    ``slic_segments`` then ``create_region_graph_from_segments`` (which computes the Canny edge map on the device).  ``image``
+    [H, W, 3] float in [0, 1].  Returns (RegionGraphData on the device, segments int32 [H, W] on the device)."""
+    img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
+    _lib.require_device(img, "image")
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
+    img = img.to(torch.float32).contiguous()
+    segments = slic_segments(img, n_segments)
+    data, _ = create_region_graph_from_segments(img, segments, device=img.device)
+    return data, segments
+
+
+def predict_from_image(multimodal_model, rg_model, image, kg_embeddings_dict, device, n_segments=500):
+    """The reference's ``predict_single_image`` from the image on, with no host-side image processing: superpixels, edge map and
+    region graph on the device (``region_graph_from_image``), then ``predict_from_region_graph`` (test_multimodal.py, which stays
+    the reference's per-image surface unchanged).  ``image`` [H, W, 3] float in [0, 1].  Returns what that function returns."""
+    from .test_multimodal import predict_from_region_graph
+    graph_data, _ = region_graph_from_image(image, n_segments, device)
+    return predict_from_region_graph(multimodal_model, rg_model, graph_data, kg_embeddings_dict, device)
+
+
 def create_region_graph(image, n_segments=500, device="cuda"):
     """``create_region_graph(image, n_segments)`` of the reference (extract_rg_embeddings.py:138): slic and canny are
     skimage's and stay on the host when skimage is installed; everything after them runs on the device.  Returns
@@ -155,7 +210,8 @@ def create_region_graph(image, n_segments=500, device="cuda"):
         from skimage.segmentation import slic
     except ImportError as err:
         raise _lib.CamoError("create_region_graph needs scikit-image for slic / canny (models/region_graph/extract_rg_embeddings.py:144,152); "
-                             "pass their results to create_region_graph_from_segments instead") from err
+                             "pass their results to create_region_graph_from_segments instead, or call region_graph_from_image, which "
+                             "computes both on the device") from err
     import numpy as np
     image = np.asarray(image)
     segments = slic((image * 255).astype(np.uint8), n_segments=n_segments, compactness=10, sigma=1)       # :143-144
