@@ -15,15 +15,16 @@ from .optim import FusedClipAdamW, cosine_warm_restarts_lr  # noqa: F401
 from .test_multimodal import (build_ordered_kg_tensor, load_multimodal_model, predict_from_embeddings,  # noqa: F401
                               predict_from_region_graph)
 # (the package's predict_embedding_directory is test_multimodal's with a group size: batch_size=1, the default, calls that one)
-from .predict_batch import predict_batch_from_embeddings, predict_embedding_directory  # noqa: F401
+from .predict_batch import predict_batch_from_embeddings, predict_batch_from_images, predict_embedding_directory  # noqa: F401
 from .train_multimodal import (NativeTrainer, SmartMultimodalDataset, calculate_f1_score, collate_fn,  # noqa: F401
                                extract_label_from_mask, fit, pack_samples, train_epoch_fixed, train_multimodal_fixed,
                                validate_fixed)
 
-from .region_graph import (RegionGraphData, RegionGraphGNN, build_target_csr, canny_edges, create_region_graph,  # noqa: F401,E402
-                           create_region_graph_from_segments, predict_from_image, region_graph_from_image, slic_segments)
+from .region_graph import (RegionGraphBatch, RegionGraphData, RegionGraphGNN, build_target_csr, canny_edges, create_region_graph,  # noqa: F401,E402
+                           create_region_graph_from_segments, create_region_graphs_from_segments, predict_from_image,
+                           region_graph_from_image, region_graphs_from_images, slic_label_bound, slic_segments)
 
-__all__ = ["RegionGraphGNN", "RegionGraphData", "create_region_graph", "create_region_graph_from_segments", "canny_edges", "slic_segments", "region_graph_from_image", "predict_from_image", "build_target_csr", "build_multimodal_model", "MultimodalCamouflageDetector", "CrossAttentionFusion", "LateFusion",
+__all__ = ["RegionGraphGNN", "RegionGraphData", "RegionGraphBatch", "create_region_graphs_from_segments", "region_graphs_from_images", "slic_label_bound", "predict_batch_from_images", "create_region_graph", "create_region_graph_from_segments", "canny_edges", "slic_segments", "region_graph_from_image", "predict_from_image", "build_target_csr", "build_multimodal_model", "MultimodalCamouflageDetector", "CrossAttentionFusion", "LateFusion",
            "AggressiveFocalLoss", "multitask_loss", "FusedClipAdamW", "cosine_warm_restarts_lr", "NativeTrainer",
            "calculate_f1_score", "collate_fn", "fit", "pack_samples", "train_epoch_fixed", "validate_fixed",
            "EmbeddingMatcher", "DeviceResidentDataset", "SmartMultimodalDataset", "extract_label_from_mask", "train_multimodal_fixed", "load_multimodal_model", "build_ordered_kg_tensor",

@@ -31,6 +31,10 @@ SYMBOLS = ("camo_abi_version", "camo_last_error", "camo_workspace_bytes", "camo_
 RG_SYMBOLS = ("camo_rg_workspace_bytes", "camo_rg_node_embeddings", "camo_rg_build_csr")
 # every symbol include/camo_rg_features.h declares
 RGF_SYMBOLS = ("camo_rg_graph_workspace_bytes", "camo_rg_region_graph")
+# every symbol include/camo_rg_batch.h declares
+RGB_SYMBOLS = ("camo_rg_batch_workspace_bytes", "camo_rg_region_graph_batch")
+RGB_TILE_SLOTS = 64                 # CAMO_RGB_TILE_SLOTS
+RGB_VAR_BOUND = 3.0 * 2.0 ** -37    # CAMO_RGB_VAR_BOUND
 # every symbol include/camo_canny.h declares
 CANNY_SYMBOLS = ("camo_canny_workspace_bytes", "camo_canny", "camo_canny_hysteresis")
 # every symbol include/camo_slic.h declares
@@ -146,6 +150,10 @@ def lib():
     L.camo_rg_graph_workspace_bytes.argtypes = [i32]
     L.camo_rg_region_graph.restype = C.c_int
     L.camo_rg_region_graph.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, i32, vp, vp]
+    L.camo_rg_batch_workspace_bytes.restype = sz
+    L.camo_rg_batch_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.camo_rg_region_graph_batch.restype = C.c_int
+    L.camo_rg_region_graph_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.camo_canny_workspace_bytes.restype = sz
     L.camo_canny_workspace_bytes.argtypes = [i32, i32, i32]
     L.camo_canny.restype = C.c_int

@@ -28,10 +28,12 @@
 #include "misc.h"
 #include "rg_gnn.h"
 #include "rg_features.h"
+#include "rg_batch.h"
 #include "canny.h"
 #include "slic.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
+#include "../../include/camo_rg_batch.h"
 #include "../../include/camo_canny.h"
 #include "../../include/camo_slic.h"
 
@@ -1721,6 +1723,40 @@ int camo_rg_region_graph(const float* image, const int32_t* segments, const uint
   if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_rg_graph_workspace_bytes()");
   CK(launch_region_graph(image, segments, canny, H, W, n_labels, ws, x, region_map, reinterpret_cast<long long*>(edge_index), edge_attr,
                          edge_capacity, counts, static_cast<hipStream_t>(stream)), "region graph");
+  return 0;
+}
+
+static_assert(RGB_SLOTS == CAMO_RGB_TILE_SLOTS && RGB_FIX_BITS == CAMO_RGB_FIX_BITS, "include/camo_rg_batch.h states the kernel's constants");
+
+static int rg_batch_check(int N, int H, int W, int label_bound) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if (N > CAMO_RGB_MAX_IMAGES) return fail(CAMO_E_UNSUPPORTED, "N exceeds CAMO_RGB_MAX_IMAGES");
+  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS)
+    return fail(CAMO_E_UNSUPPORTED, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS (the 64-bit fixed-point sums hold 2^26 pixels)");
+  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_UNSUPPORTED, "N * H * W exceeds CAMO_RGB_MAX_PIXELS (32-bit edge offsets)");
+  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, 4096]");
+  return 0;
+}
+
+size_t camo_rg_batch_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t label_bound) {
+  if (rg_batch_check(N, H, W, label_bound)) return 0;
+  return rg_batch_carve(N, label_bound, nullptr).bytes;
+}
+
+int camo_rg_region_graph_batch(const float* images, const int32_t* segments, const uint8_t* canny, int32_t N, int32_t H, int32_t W,
+                               int32_t label_bound, void* workspace, size_t workspace_bytes, float* x, int32_t node_capacity,
+                               int32_t* region_map, int64_t* edge_index, float* edge_attr, int32_t edge_capacity, int32_t* node_off,
+                               int32_t* edge_off, int32_t* batch, int32_t* status, void* stream) {
+  if (int e = rg_batch_check(N, H, W, label_bound)) return e;
+  if ((long long)node_capacity < (long long)N * label_bound) return fail(CAMO_E_ARG, "node_capacity must be >= N * label_bound");
+  if (edge_capacity < 2) return fail(CAMO_E_ARG, "edge_capacity must be >= 2");
+  const RgBatchWs ws = rg_batch_carve(N, label_bound, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_rg_batch_workspace_bytes()");
+  if (!images || !segments || !canny || !workspace || !x || !region_map || !edge_index || !edge_attr || !node_off || !edge_off || !batch || !status)
+    return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_region_graph_batch(images, segments, canny, N, H, W, label_bound, ws, x, region_map, reinterpret_cast<long long*>(edge_index),
+                               edge_attr, edge_capacity, node_off, edge_off, batch, status, static_cast<hipStream_t>(stream)),
+     "region graph batch");
   return 0;
 }
 

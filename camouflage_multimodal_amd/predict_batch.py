@@ -52,6 +52,21 @@ def predict_batch_from_embeddings(multimodal_model, rg_list, kg_embeddings_dict,
     return predictions, attn, kg_ordered
 
 
+@torch.no_grad()
+def predict_batch_from_images(multimodal_model, rg_model, images, kg_embeddings_dict, device, n_segments=500, return_attention=True):
+    """``predict_from_image`` for a batch with no per-image step before the fusion model: superpixels, edge maps and region graphs
+    of ``images`` [N, H, W, 3] float in [0, 1] in batched device calls (``region_graphs_from_images``), ONE
+    ``extract_node_embeddings`` call on the block-diagonal graph, and the embeddings split by ``node_offsets`` (views) into
+    ``predict_batch_from_embeddings``, whose result this returns.  Host synchronisations of the whole call: the graph sizes
+    read-back and the final [N, 6] copy."""
+    from .region_graph import region_graphs_from_images
+    graphs, _ = region_graphs_from_images(images, n_segments, device)
+    emb = rg_model.extract_node_embeddings(graphs)
+    no = graphs.node_offsets
+    return predict_batch_from_embeddings(multimodal_model, [emb[no[k]:no[k + 1]] for k in range(graphs.num_graphs)], kg_embeddings_dict, device,
+                                         return_attention=return_attention)
+
+
 def predict_embedding_directory(multimodal_model, rg_embeddings, kg_embeddings_dict, output_dir, device, max_images=None, batch_size=1):
     """``test_multimodal.predict_embedding_directory`` with a group size.  ``batch_size=1`` (default) IS that function: the
     per-image loop.  ``batch_size`` > 1: that many images per model call through ``predict_batch_from_embeddings`` (the attention

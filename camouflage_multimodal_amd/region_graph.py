@@ -69,6 +69,31 @@ class RegionGraphData:
     cpu = lambda self: self.to("cpu")  # noqa: E731
 
 
+class RegionGraphBatch:
+    """The region graphs of N images as ONE block-diagonal graph (torch_geometric's ``Batch``): ``x`` [n, 15] with the regions of
+    image k in rows ``node_offsets[k] : node_offsets[k + 1]``, ``edge_index`` [2, E] int64 with global node indices (image k's edges
+    in columns ``edge_offsets[k] : edge_offsets[k + 1]``), ``edge_attr`` [E, 1], ``batch`` [n] int32 image index of every node,
+    ``num_graphs``.  The offsets are host lists of N + 1 integers.  Duck-typed for ``extract_node_embeddings`` /
+    ``extract_graph_embedding``."""
+
+    def __init__(self, x, edge_index, edge_attr, batch, node_offsets, edge_offsets):
+        self.x, self.edge_index, self.edge_attr, self.batch = x, edge_index, edge_attr, batch
+        self.node_offsets, self.edge_offsets = list(node_offsets), list(edge_offsets)
+        self.num_graphs = len(self.node_offsets) - 1
+
+    def to(self, device):
+        return RegionGraphBatch(self.x.to(device), self.edge_index.to(device), self.edge_attr.to(device), self.batch.to(device),
+                                self.node_offsets, self.edge_offsets)
+
+    cpu = lambda self: self.to("cpu")  # noqa: E731
+
+    def graphs(self):
+        """Per-image ``RegionGraphData`` (rows of ``x`` and ``edge_attr`` are views; edge indices are local to the image)."""
+        no, eo = self.node_offsets, self.edge_offsets
+        return [RegionGraphData(self.x[no[k]:no[k + 1]], self.edge_index[:, eo[k]:eo[k + 1]] - no[k], self.edge_attr[eo[k]:eo[k + 1]])
+                for k in range(self.num_graphs)]
+
+
 def canny_edges(images, sigma=2.0, low_threshold=0.1, high_threshold=0.2, device="cuda", return_gradients=False):
     """``skimage.feature.canny(gray, sigma=2)`` of the reference (extract_rg_embeddings.py:151-152, luma :151 included) on the
     device (``camo_canny``, include/camo_canny.h): ``images`` [H, W, 3] or [N, H, W, 3] float in [0, 1] -> bool tensor [H, W]
@@ -144,6 +169,92 @@ def create_region_graph_from_segments(image, segments, edges_canny=None, device=
             break
         cap = e                                                          # the library reported the capacity needed: once more
     return RegionGraphData(x[:n], ei[:, :e], ea[:e].unsqueeze(1)), rmap
+
+
+def create_region_graphs_from_segments(images, segments, edges_canny=None, device="cuda", label_bound=None, edge_capacity=None):
+    """``create_region_graph_from_segments`` for a batch in one library call (``camo_rg_region_graph_batch``,
+    include/camo_rg_batch.h): ``images`` [N, H, W, 3] float in [0, 1], ``segments`` [N, H, W] integer labels, ``edges_canny``
+    [N, H, W] bool (``None``: one batched ``canny_edges`` call) -> (RegionGraphBatch on the device, region_map int32
+    [N, label_bound] = index of each label within its image or -1).  Per image the graph is the single-image function's, up to
+    the arithmetic: the sums are integers here (the header derives the bounds), so the result does not depend on the order the
+    additions arrive in -- two calls give the same bytes and a batch the bytes of its images one by one.  ``label_bound``: every label
+    must lie in [0, label_bound); ``None`` reads ``segments.max()`` back (one synchronisation more).  After the launch ONE
+    device -> host copy brings the offsets and the status; a label out of range raises ``ValueError``, more edges than
+    ``edge_capacity`` (default 16 N label_bound) run the call once more with the capacity it reported."""
+    dev = torch.device(device)
+    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(dev)
+    seg = segments if isinstance(segments, torch.Tensor) else torch.as_tensor(segments).to(dev)
+    can = None if edges_canny is None else (edges_canny if isinstance(edges_canny, torch.Tensor) else torch.as_tensor(edges_canny).to(dev))
+    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0 or seg.shape != img.shape[:3] or (can is not None and can.shape != img.shape[:3]):
+        raise ValueError(f"need images [N, H, W, 3], segments [N, H, W], edges_canny [N, H, W]; got {tuple(img.shape)}, {tuple(seg.shape)}"
+                         + ("" if can is None else f", {tuple(can.shape)}"))
+    _lib.require_device(img, "images")
+    dev = img.device
+    img = img.to(torch.float32).contiguous()
+    seg = seg.to(device=dev, dtype=torch.int32).contiguous()
+    if can is None:
+        can = canny_edges(img)
+    can = can.to(device=dev).to(torch.uint8).contiguous()
+    N, H, W = seg.shape
+    if label_bound is None:
+        label_bound = max(int(seg.max()), 0) + 1                          # (a negative label is the range check's, on the device)
+    label_bound = int(label_bound)
+    if label_bound < 1 or label_bound > _lib.RG_MAX_LABELS:
+        raise ValueError(f"label_bound must lie in [1, {_lib.RG_MAX_LABELS}], got {label_bound}")
+    nodes = N * label_bound
+    cap = int(edge_capacity) if edge_capacity else 16 * nodes             # (a planar adjacency has < 3 n pairs; 8-connectivity adds corner contacts)
+    L = _lib.lib()
+    need = L.camo_rg_batch_workspace_bytes(N, H, W, label_bound)
+    if need == 0:
+        _lib.check(-1, "camo_rg_batch_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    x = torch.empty(nodes, 15, dtype=torch.float32, device=dev)
+    rmap = torch.empty(N, label_bound, dtype=torch.int32, device=dev)
+    batch = torch.empty(nodes, dtype=torch.int32, device=dev)
+    sizes = torch.empty(2 * (N + 1) + 2, dtype=torch.int32, device=dev)   # node_off, edge_off, status: one copy brings all three
+    node_off, edge_off, status = sizes[:N + 1], sizes[N + 1:2 * (N + 1)], sizes[2 * (N + 1):]
+    while True:
+        ei = torch.empty(2, cap, dtype=torch.int64, device=dev)
+        ea = torch.empty(cap, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = L.camo_rg_region_graph_batch(_ptr(img), _ptr(seg), _ptr(can), N, H, W, label_bound, _ptr(ws), ws.numel(), _ptr(x), nodes,
+                                              _ptr(rmap), _ptr(ei), _ptr(ea), cap, _ptr(node_off), _ptr(edge_off), _ptr(batch), _ptr(status),
+                                              _stream_ptr(dev))
+        _lib.check(rc, "camo_rg_region_graph_batch")
+        host = sizes.tolist()                                             # (the one synchronisation: the sizes of what was built)
+        no, eo, (bad, e) = host[:N + 1], host[N + 1:2 * (N + 1)], host[2 * (N + 1):]
+        if bad:
+            raise ValueError(f"{bad} pixel{'s' if bad != 1 else ''} with a segment label outside [0, {label_bound})")
+        if e <= cap:
+            break
+        cap = e                                                           # the library reported the capacity needed: once more
+    n = no[N]
+    return RegionGraphBatch(x[:n], ei[:, :e], ea[:e].unsqueeze(1), batch[:n], no, eo), rmap
+
+
+def slic_label_bound(H, W, n_segments):
+    """A bound on ``slic_segments``' labels that needs no look at them: labels < bound.  The connectivity step (include/camo_slic.h
+    step 8) gives a new label only to a component of at least ``min_size = int(0.5 H W / K)`` pixels (K centroids,
+    ``camo_slic_grid``), the components are disjoint, and labels start at 1 with 0 for pixels that adopt none: at most
+    ``H W // max(min_size, 1)`` labels above 0.  Capped at ``RG_MAX_LABELS``; the device-side range check covers the rest."""
+    out = (C.c_int32 * 5)()
+    _lib.check(_lib.lib().camo_slic_grid(int(H), int(W), int(n_segments), out), "camo_slic_grid")
+    min_size = int(0.5 * H * W / out[0])
+    return min(H * W // max(min_size, 1) + 2, _lib.RG_MAX_LABELS)
+
+
+def region_graphs_from_images(images, n_segments=500, device="cuda"):
+    """``region_graph_from_image`` for a batch: ``slic_segments`` on ``images`` [N, H, W, 3] float in [0, 1], then
+    ``create_region_graphs_from_segments`` (one batched Canny call inside) with ``slic_label_bound`` as the label bound, so the
+    only synchronisation is the sizes read-back.  Returns (RegionGraphBatch on the device, segments int32 [N, H, W] on the device)."""
+    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
+    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
+        raise ValueError(f"need images [N, H, W, 3], got {tuple(img.shape)}")
+    _lib.require_device(img, "images")
+    img = img.to(torch.float32).contiguous()
+    segments = slic_segments(img, n_segments)
+    graphs, _ = create_region_graphs_from_segments(img, segments, device=img.device, label_bound=slic_label_bound(img.shape[1], img.shape[2], n_segments))
+    return graphs, segments
 
 
 def slic_segments(images, n_segments=500, compactness=10.0, sigma=1.0, device="cuda", return_counts=False):
@@ -315,7 +426,9 @@ class RegionGraphGNN(nn.Module):
         batch = getattr(data, "batch", None)
         if batch is None:
             return emb.mean(dim=0, keepdim=True)
-        g = int(batch.max().item()) + 1
+        g = getattr(data, "num_graphs", None)                              # (a RegionGraphBatch knows it: no read-back)
+        if g is None:
+            g = int(batch.max().item()) + 1
         out = torch.zeros(g, emb.shape[1], dtype=emb.dtype, device=emb.device).index_add_(0, batch.long(), emb)
         return out / torch.bincount(batch.long(), minlength=g).clamp(min=1).unsqueeze(1).to(emb.dtype)
 
