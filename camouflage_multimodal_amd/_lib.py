@@ -39,6 +39,11 @@ RGB_VAR_BOUND = 3.0 * 2.0 ** -37    # CAMO_RGB_VAR_BOUND
 CANNY_SYMBOLS = ("camo_canny_workspace_bytes", "camo_canny", "camo_canny_hysteresis")
 # every symbol include/camo_slic.h declares
 SLIC_SYMBOLS = ("camo_slic_grid", "camo_slic_workspace_bytes", "camo_slic", "camo_slic_preprocess", "camo_slic_assign", "camo_slic_update", "camo_slic_connect")
+# every symbol include/camo_rg_detect.h declares
+RGD_SYMBOLS = ("camo_rg_node_heads", "camo_rg_paint", "camo_seg_counts")
+RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
+RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
+RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -174,6 +179,12 @@ def lib():
     L.camo_slic_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.camo_slic_connect.restype = C.c_int
     L.camo_slic_connect.argtypes = [vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
+    L.camo_rg_node_heads.restype = C.c_int
+    L.camo_rg_node_heads.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, i32, vp, vp, vp]
+    L.camo_rg_paint.restype = C.c_int
+    L.camo_rg_paint.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]
+    L.camo_seg_counts.restype = C.c_int
+    L.camo_seg_counts.argtypes = [vp, C.c_int64, vp, f32, i32, i32, i32, vp, vp]
     L.camo_debug_gemm.restype = C.c_int
     L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.camo_debug_gemm16.restype = C.c_int

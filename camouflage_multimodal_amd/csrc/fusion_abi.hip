@@ -31,11 +31,13 @@
 #include "rg_batch.h"
 #include "canny.h"
 #include "slic.h"
+#include "rg_detect.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
 #include "../../include/camo_canny.h"
 #include "../../include/camo_slic.h"
+#include "../../include/camo_rg_detect.h"
 
 namespace {
 
@@ -1925,6 +1927,49 @@ int camo_slic_connect(const int32_t* labels_in, int32_t N, int32_t H, int32_t W,
   const SlicConnWs ws = slic_conn_carve(N, H, W, workspace);
   if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_slic_workspace_bytes(N, H, W, 0)");
   CK(launch_slic_connect(labels_in, N, H, W, min_size, max_size, ws, labels, counts, static_cast<hipStream_t>(stream)), "slic connect");
+  return 0;
+}
+
+static_assert(CAMO_RGD_NPARAMS == 12 && CAMO_RGD_MAX_CLASSES == 8, "rg_detect.h sizes its parameter table and its logit rows by these");
+
+int camo_rg_node_heads(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* head_params, const float* emb, int32_t n,
+                       float* logits, float* probs, void* stream) {
+  if (!dims) return fail(CAMO_E_ARG, "dims is null");
+  if (dims->hidden < 2 || dims->hidden > CAMO_RGD_MAX_HIDDEN || (dims->hidden & 1))
+    return fail(CAMO_E_ARG, "hidden must be even and in [2, CAMO_RGD_MAX_HIDDEN]");
+  if (num_classes < 2 || num_classes > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_ARG, "num_classes must be in [2, CAMO_RGD_MAX_CLASSES]");
+  if (n < 1) return fail(CAMO_E_ARG, "need n >= 1");
+  if (!head_params || !emb || !logits || !probs) return fail(CAMO_E_ARG, "null pointer argument");
+  RgdHeads P{};
+  for (int i = 0; i < CAMO_RGD_NPARAMS; ++i) {
+    if (!head_params[i]) return fail(CAMO_E_ARG, "null pointer in the head parameter table");
+    P.p[i] = head_params[i];
+  }
+  CK(launch_rgd_heads(P, emb, n, dims->hidden, num_classes, logits, probs, static_cast<hipStream_t>(stream)), "rg node heads");
+  return 0;
+}
+
+int camo_rg_paint(const float* values, int32_t n_nodes, int32_t C, const int32_t* segments, const int32_t* region_map,
+                  const int32_t* node_off, int32_t N, int32_t H, int32_t W, int32_t label_bound, float fill, float* maps, void* stream) {
+  if (C < 1 || C > CAMO_RGD_MAX_CHANNELS) return fail(CAMO_E_ARG, "C must be in [1, CAMO_RGD_MAX_CHANNELS]");
+  if (n_nodes < 1 || N < 1 || H < 1 || W < 1 || label_bound < 1) return fail(CAMO_E_ARG, "need n_nodes >= 1, N >= 1, H >= 1, W >= 1, label_bound >= 1");
+  if ((long long)N * H * W > CAMO_RGD_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGD_MAX_PIXELS");
+  if (!values || !segments || !region_map || !node_off || !maps) return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_rgd_paint(values, n_nodes, C, segments, region_map, node_off, N, H, W, label_bound, fill, maps, static_cast<hipStream_t>(stream)),
+     "rg paint");
+  return 0;
+}
+
+int camo_seg_counts(const float* pred, int64_t pred_image_stride, const uint8_t* gt, float threshold, int32_t N, int32_t H, int32_t W,
+                    int64_t* counts, void* stream) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if (N > CAMO_RGD_MAX_IMAGES) return fail(CAMO_E_ARG, "N exceeds CAMO_RGD_MAX_IMAGES");
+  if ((long long)H * W > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGD_MAX_IMAGE_PIXELS (the integer absolute-error sum holds 2^26 pixels)");
+  if (pred_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "pred_image_stride must be >= H * W");
+  if (threshold != threshold) return fail(CAMO_E_ARG, "threshold is NaN");
+  if (!pred || !gt || !counts) return fail(CAMO_E_ARG, "null pointer argument");
+  CK(launch_rgd_counts(pred, pred_image_stride, gt, threshold, N, H, W, reinterpret_cast<unsigned long long*>(counts),
+                       static_cast<hipStream_t>(stream)), "seg counts");
   return 0;
 }
 }  // extern "C"

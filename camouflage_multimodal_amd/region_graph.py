@@ -5,8 +5,9 @@
 (test_multimodal.py:420-423); ``extract_node_embeddings(data)`` (:94-122) -- the call that feeds the fusion model at
 inference -- runs as HIP kernels behind ``camo_rg_node_embeddings`` (include/camo_rg_gnn.h).  The graph layers are
 torch_geometric's in the reference; the published algorithms they are restated from and the CPU checker the kernels are
-tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here, no RG weights or fixtures shipped).  The node-classification ``forward`` (training of the RG model,
-models/region_graph/train.py) is outside the path and raises.
+tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here, no RG weights or fixtures shipped).  The node-classification ``forward``
+runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py); training the RG model
+(models/region_graph/train.py) is outside the path, so ``forward`` in training mode raises.
 """
 from __future__ import annotations
 
@@ -372,11 +373,12 @@ class RegionGraphGNN(nn.Module):
         self.conv3 = _GCNParams(h, h); self.bn3 = nn.BatchNorm1d(h)
         self.conv4 = _GCNParams(h, h); self.bn4 = nn.BatchNorm1d(h)
         self.fc_shared = nn.Linear(h, h)
-        # node-classification heads: parameters kept so that the reference checkpoint loads strictly; not on the path
+        # node-classification heads (forward / node_probabilities, eval mode only)
         self.fc_mask_1 = nn.Linear(h, h // 2); self.fc_mask_2 = nn.Linear(h // 2, num_classes)
         self.fc_instance_1 = nn.Linear(h, h // 2); self.fc_instance_2 = nn.Linear(h // 2, num_classes)
         self.fc_edge_1 = nn.Linear(h, h // 2); self.fc_edge_2 = nn.Linear(h // 2, 1)
         self._dims = _lib.CamoRgDims(in_channels, h, heads)
+        self.num_classes = num_classes
 
     def _param_table(self):
         t = [self.conv1.att_src, self.conv1.att_dst, self.conv1.bias, self.conv1.lin.weight,
@@ -432,6 +434,47 @@ class RegionGraphGNN(nn.Module):
         out = torch.zeros(g, emb.shape[1], dtype=emb.dtype, device=emb.device).index_add_(0, batch.long(), emb)
         return out / torch.bincount(batch.long(), minlength=g).clamp(min=1).unsqueeze(1).to(emb.dtype)
 
+    def _head_table(self):
+        t = []
+        for name in ("fc_mask", "fc_instance", "fc_edge"):
+            for layer in (getattr(self, name + "_1"), getattr(self, name + "_2")):
+                t += [layer.weight, layer.bias]
+        assert len(t) == _lib.RGD_NPARAMS
+        for p in t:
+            _lib.require_device(p, "RegionGraphGNN parameters")
+        keep = [p.detach().to(torch.float32).contiguous() for p in t]
+        tab = (C.c_void_p * len(keep))(*[p.data_ptr() for p in keep])
+        return tab, keep
+
+    @torch.no_grad()
+    def node_heads(self, emb):
+        """The three heads on node embeddings [n, hidden] in one launch (``camo_rg_node_heads``, include/camo_rg_detect.h) ->
+        (logits [n, 2 num_classes + 1] = mask | instance | edge, probs [n, 3] = P(mask = 1), P(instance = 1), sigmoid(edge))."""
+        _lib.require_device(emb, "emb")
+        if emb.dim() != 2 or emb.shape[1] != self._dims.hidden or emb.shape[0] < 1:
+            raise RuntimeError(f"emb of shape {tuple(emb.shape)} does not match hidden {self._dims.hidden}")
+        emb = emb.detach().to(torch.float32).contiguous()
+        n = emb.shape[0]
+        logits = torch.empty(n, 2 * self.num_classes + 1, dtype=torch.float32, device=emb.device)
+        probs = torch.empty(n, 3, dtype=torch.float32, device=emb.device)
+        tab, keep = self._head_table()
+        with torch.cuda.device(emb.device):
+            rc = _lib.lib().camo_rg_node_heads(C.byref(self._dims), self.num_classes, tab, _ptr(emb), n, _ptr(logits), _ptr(probs),
+                                               _stream_ptr(emb.device))
+        _lib.check(rc, "camo_rg_node_heads")
+        return logits, probs
+
+    def node_probabilities(self, data):
+        """[n, 3] per node: P(mask = 1), P(instance = 1), sigmoid(edge logit) -- what the reference's detector paints
+        (models/region_graph/test.py::detect_camouflage).  Eval-mode arithmetic whatever the module's mode."""
+        return self.node_heads(self.extract_node_embeddings(data))[1]
+
     def forward(self, data):
-        raise _lib.CamoError("RegionGraphGNN.forward (node-classification heads, used only to train the RG model) is outside "
-                             "the MI355X path; use extract_node_embeddings()")
+        """Eval mode: (mask_logits [n, c], instance_logits [n, c], edge_logits [n, 1]), views of one tensor.  Training mode raises:
+        training the RG model (train.py: batch statistics, dropout, a backward) is outside the MI355X path."""
+        if self.training:
+            raise _lib.CamoError("RegionGraphGNN.forward in training mode: training the RG model (models/region_graph/train.py) is "
+                                 "outside the MI355X path; call .eval() for the node-classification heads, or use extract_node_embeddings()")
+        logits, _ = self.node_heads(self.extract_node_embeddings(data))
+        c = self.num_classes
+        return logits[:, :c], logits[:, c:2 * c], logits[:, 2 * c:]
