@@ -44,6 +44,9 @@ RGD_SYMBOLS = ("camo_rg_node_heads", "camo_rg_paint", "camo_seg_counts")
 RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
 RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
 RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
+# every symbol include/camo_rg_train.h declares
+RGT_SYMBOLS = ("camo_rg_train_workspace_bytes", "camo_rg_loss_backward")
+RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -185,6 +188,10 @@ def lib():
     L.camo_rg_paint.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]
     L.camo_seg_counts.restype = C.c_int
     L.camo_seg_counts.argtypes = [vp, C.c_int64, vp, f32, i32, i32, i32, vp, vp]
+    L.camo_rg_train_workspace_bytes.restype = sz
+    L.camo_rg_train_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
+    L.camo_rg_loss_backward.restype = C.c_int
+    L.camo_rg_loss_backward.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, vp]
     L.camo_debug_gemm.restype = C.c_int
     L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.camo_debug_gemm16.restype = C.c_int

@@ -12,6 +12,7 @@
 //     H..3H of in_proj_weight; their input gradients as one K=2H GEMM.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -32,12 +33,14 @@
 #include "canny.h"
 #include "slic.h"
 #include "rg_detect.h"
+#include "rg_train.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
 #include "../../include/camo_canny.h"
 #include "../../include/camo_slic.h"
 #include "../../include/camo_rg_detect.h"
+#include "../../include/camo_rg_train.h"
 
 namespace {
 
@@ -1970,6 +1973,153 @@ int camo_seg_counts(const float* pred, int64_t pred_image_stride, const uint8_t*
   if (!pred || !gt || !counts) return fail(CAMO_E_ARG, "null pointer argument");
   CK(launch_rgd_counts(pred, pred_image_stride, gt, threshold, N, H, W, reinterpret_cast<unsigned long long*>(counts),
                        static_cast<hipStream_t>(stream)), "seg counts");
+  return 0;
+}
+
+// ---- Region-graph GNN loss and gradients, batch norm frozen (include/camo_rg_train.h) --------------------------
+static_assert(CAMO_RGT_NGRADS == 32 && CAMO_RGT_FC_B == 19 && CAMO_RGT_HEADS == 20, "the gradient table is the 20 + 12 trainable parameters");
+
+namespace {
+struct RgtWs {
+  float *Hh, *O, *dh, *a_src, *a_dst, *m, *S, *r, *da_src, *da_dst, *dinv, *xw, *h[4], *xhat[4], *emb, *Z, *dZ, *logits, *dlogits, *dA, *dB,
+      *W1, *b1, *partial;
+  size_t bytes;
+};
+size_t rgt_partial_width(const camo_rg_dims_t& d, int nc) {
+  const size_t C = d.hidden, K = d.heads, Hh = C / 2;
+  return std::max(std::max(2 * K * C, 3 * Hh), std::max((size_t)nc * Hh, (size_t)2 * nc + 1));
+}
+RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base) {
+  RgtWs w{};
+  Carver c(base);
+  const size_t n = N, C = d.hidden, K = d.heads, units = 3 * (C / 2), L = 2 * (size_t)nc + 1;
+  w.Hh = c.take<float>(n * K * C); w.O = c.take<float>(n * K * C); w.dh = c.take<float>(n * K * C);
+  w.a_src = c.take<float>(n * K); w.a_dst = c.take<float>(n * K); w.m = c.take<float>(n * K); w.S = c.take<float>(n * K);
+  w.r = c.take<float>(n * K); w.da_src = c.take<float>(n * K); w.da_dst = c.take<float>(n * K); w.dinv = c.take<float>(n);
+  w.xw = c.take<float>(n * C);
+  for (int k = 0; k < 4; ++k) { w.h[k] = c.take<float>(n * C); w.xhat[k] = c.take<float>(n * C); }
+  w.emb = c.take<float>(n * C); w.Z = c.take<float>(n * units); w.dZ = c.take<float>(n * units);
+  w.logits = c.take<float>(n * L); w.dlogits = c.take<float>(n * L); w.dA = c.take<float>(n * C); w.dB = c.take<float>(n * C);
+  w.W1 = c.take<float>(units * C); w.b1 = c.take<float>(units);
+  w.partial = c.take<float>((size_t)rgt_row_blocks(N) * rgt_partial_width(d, nc));
+  c.off = (c.off + 255) & ~size_t(255);
+  w.bytes = c.off;
+  return w;
+}
+int rgt_check(const camo_rg_dims_t* d, int nc, int N, int E) {
+  if (!d) return fail(CAMO_E_ARG, "dims is null");
+  if (N < 1 || E < N || d->in_channels < 1 || d->hidden < 2 || d->hidden > 512 || (d->hidden & 1) || d->heads < 1 || d->heads > 8)
+    return fail(CAMO_E_UNSUPPORTED, "need N >= 1, E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8");
+  if (nc < 2 || nc > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_UNSUPPORTED, "num_classes must be in [2, 8]");
+  return 0;
+}
+}  // namespace
+
+size_t camo_rg_train_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E) {
+  if (rgt_check(dims, num_classes, N, E)) return 0;
+  return rgt_carve(*dims, num_classes, N, nullptr).bytes;
+}
+
+int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                          const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                          const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                          const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                          float* loss, float* const* grads, void* stream) {
+  if (int e = rgt_check(dims, num_classes, N, E)) return e;
+  if (!params || !head_params || !x || !rowptr || !col || !w || !rrowptr || !rcol || !rw || !mask_t || !inst_t || !edge_t || !workspace ||
+      !loss || !grads)
+    return fail(CAMO_E_ARG, "null pointer argument");
+  for (int i = 0; i < CAMO_RG_NPARAMS; ++i)
+    if (!params[i]) return fail(CAMO_E_ARG, "null pointer in the parameter table");
+  for (int i = 0; i < CAMO_RGD_NPARAMS; ++i)
+    if (!head_params[i]) return fail(CAMO_E_ARG, "null pointer in the head parameter table");
+  for (int i = 0; i < CAMO_RGT_NGRADS; ++i)
+    if (!grads[i]) return fail(CAMO_E_ARG, "null pointer in the gradient table");
+  if (!std::isfinite(w_mask) || !std::isfinite(w_instance) || !std::isfinite(w_edge)) return fail(CAMO_E_ARG, "loss weights must be finite");
+  const camo_rg_dims_t& d = *dims;
+  const RgtWs ws = rgt_carve(d, num_classes, N, workspace);
+  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_rg_train_workspace_bytes()");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int C = d.hidden, K = d.heads, In = d.in_channels, nc = num_classes, Hh = C / 2, units = 3 * Hh, L = 2 * nc + 1;
+  const int nb = rgt_row_blocks(N);
+  const float* const* P = params;
+  const float* const* HP = head_params;
+  float* const* G = grads;
+  float* const* GH = grads + CAMO_RGT_HEADS;
+  auto bn = [&](int slot) { return BnEval{P[slot], P[slot + 1], P[slot + 2], P[slot + 3]}; };
+  constexpr int KM = GF_A_KMAJOR | GF_B_KMAJOR;   // dW = dY^T . X without atomics: one block owns an output tile over the whole contraction
+  GB g(make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
+
+  // ---- forward, saving (camo_rg_node_embeddings + camo_rg_node_heads) ----
+  g.nt(x, In, P[CAMO_RG_C1_W], In, nullptr, ws.Hh, K * C, N, K * C, In);
+  CK(g.run(), "gat projection");
+  CK(launch_gat_alpha(ws.Hh, P[CAMO_RG_C1_ATT_SRC], P[CAMO_RG_C1_ATT_DST], ws.a_src, ws.a_dst, N, K, C, st), "gat attention logits");
+  CK(launch_rgt_gat_forward(ws.Hh, ws.a_src, ws.a_dst, rowptr, col, P[CAMO_RG_C1_BIAS], bn(CAMO_RG_BN1), ws.m, ws.S, ws.O, ws.xhat[0], ws.h[0],
+                            N, K, C, st), "gat aggregate");
+  CK(launch_gcn_dinv(rowptr, w, ws.dinv, N, st), "gcn degrees");
+  for (int k = 0; k < 3; ++k) {
+    const int base = CAMO_RG_C2_BIAS + 6 * k;
+    g.nt(ws.h[k], C, P[base + 1], C, nullptr, ws.xw, C, N, C, C);
+    CK(g.run(), "gcn projection");
+    CK(launch_rgt_gcn_forward(ws.xw, rowptr, col, w, ws.dinv, P[base], bn(base + 2), ws.xhat[k + 1], ws.h[k + 1], N, C, st), "gcn aggregate");
+  }
+  CK(launch_rgt_concat_heads(HP, ws.W1, ws.b1, C, st), "head weights");
+  g.nt(ws.h[3], C, P[CAMO_RG_FC_W], C, P[CAMO_RG_FC_B], ws.emb, C, N, C, C, GF_RELU);
+  CK(g.run(), "fc_shared");
+  g.nt(ws.emb, C, ws.W1, C, ws.b1, ws.Z, units, N, units, C, GF_RELU);
+  CK(g.run(), "head first layers");
+  CK(launch_rgt_head_logits(HP, ws.Z, ws.logits, N, C, nc, st), "head logits");
+
+  // ---- loss and dlogits ----
+  CK(launch_rgt_loss(ws.logits, mask_t, inst_t, edge_t, w_mask, w_instance, w_edge, N, nc, loss, ws.dlogits, st), "loss");
+
+  // ---- heads backward ----
+  CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dlogits, L, L, N, ws.partial, st), "head bias sums");
+  CK(launch_rgt_colsum_finish(ws.partial, nb, L, RgtSegs{{GH[CAMO_RGD_MASK_B2], GH[CAMO_RGD_INST_B2], GH[CAMO_RGD_EDGE_B2], nullptr},
+                                                         {0, nc, 2 * nc, L, L}, 3}, st), "head bias sums");
+  for (int h = 0; h < 3; ++h) {
+    const int nch = h < 2 ? nc : 1;
+    CK(launch_rgt_cross_partial(ws.dlogits + h * nc, L, nch, ws.Z + h * Hh, units, Hh, N, ws.partial, st), "head second-layer gradient");
+    CK(launch_rgt_colsum_finish(ws.partial, nb, nch * Hh, RgtSegs{{GH[4 * h + 2], nullptr, nullptr, nullptr}, {0, nch * Hh, 0, 0, 0}, 1}, st),
+       "head second-layer gradient");
+  }
+  CK(launch_rgt_head_dz(HP, ws.Z, ws.dlogits, ws.dZ, N, C, nc, st), "head hidden gradient");
+  CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dZ, units, units, N, ws.partial, st), "head first-layer bias sums");
+  CK(launch_rgt_colsum_finish(ws.partial, nb, units, RgtSegs{{GH[CAMO_RGD_MASK_B1], GH[CAMO_RGD_INST_B1], GH[CAMO_RGD_EDGE_B1], nullptr},
+                                                             {0, Hh, 2 * Hh, units, units}, 3}, st), "head first-layer bias sums");
+  for (int h = 0; h < 3; ++h) g.add(ws.dZ + h * Hh, units, ws.emb, C, GH[4 * h], C, Hh, C, N, KM);
+  set_relu_bwd(g.nn(ws.dZ, units, ws.W1, C, ws.dA, C, N, C, units), ws.emb, C, 1.f);                 // dA = d(fc_shared pre-activation)
+  CK(g.run(), "head first-layer gradients");
+
+  // ---- fc_shared backward ----
+  CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dA, C, C, N, ws.partial, st), "fc_shared bias sums");
+  CK(launch_rgt_colsum_finish(ws.partial, nb, C, RgtSegs{{G[CAMO_RGT_FC_B], nullptr, nullptr, nullptr}, {0, C, 0, 0, 0}, 1}, st), "fc_shared bias sums");
+  g.add(ws.dA, C, ws.h[3], C, G[CAMO_RGT_FC_W], C, C, C, N, KM);
+  set_relu_bwd(g.nn(ws.dA, C, P[CAMO_RG_FC_W], C, ws.dB, C, N, C, C), ws.h[3], C, 1.f);              // dB = dy of bn4 (ReLU-masked)
+  CK(g.run(), "fc_shared gradients");
+
+  // ---- conv4 .. conv2 backward: dB = dy -> dPre (in place) -> dA = dXW -> dB = dy of the layer below ----
+  for (int k = 2; k >= 0; --k) {
+    const int base = CAMO_RG_C2_BIAS + 6 * k, gb = CAMO_RGT_C2_BIAS + 4 * k;
+    CK(launch_rgt_bn_backward(ws.dB, ws.xhat[k + 1], bn(base + 2), N, C, ws.partial, st), "bn backward");
+    CK(launch_rgt_bn_finish(ws.partial, nb, bn(base + 2), C, G[gb + 2], G[gb + 3], G[gb], st), "bn gradients");
+    CK(launch_rgt_gcn_backward(ws.dB, rrowptr, rcol, rw, ws.dinv, ws.dA, N, C, st), "gcn aggregate backward");
+    g.add(ws.dA, C, ws.h[k], C, G[gb + 1], C, C, C, N, KM);
+    set_relu_bwd(g.nn(ws.dA, C, P[base + 1], C, ws.dB, C, N, C, C), ws.h[k], C, 1.f);
+    CK(g.run(), "gcn projection gradients");
+  }
+
+  // ---- conv1 (GAT) backward ----
+  CK(launch_rgt_bn_backward(ws.dB, ws.xhat[0], bn(CAMO_RG_BN1), N, C, ws.partial, st), "bn backward");
+  CK(launch_rgt_bn_finish(ws.partial, nb, bn(CAMO_RG_BN1), C, G[CAMO_RGT_BN1_W], G[CAMO_RGT_BN1_B], G[CAMO_RGT_C1_BIAS], st), "bn gradients");
+  CK(launch_rgt_gat_backward_a(ws.dB, ws.Hh, ws.O, ws.a_src, ws.a_dst, ws.m, ws.S, rowptr, col, ws.r, ws.da_dst, N, K, C, st), "gat backward A");
+  CK(launch_rgt_gat_backward_b(ws.dB, ws.Hh, ws.a_src, ws.a_dst, ws.m, ws.S, ws.r, ws.da_dst, P[CAMO_RG_C1_ATT_SRC], P[CAMO_RG_C1_ATT_DST],
+                               rrowptr, rcol, ws.da_src, ws.dh, N, K, C, st), "gat backward B");
+  CK(launch_rgt_att_partial(ws.da_src, ws.da_dst, ws.Hh, N, K, C, ws.partial, st), "attention vector sums");
+  CK(launch_rgt_colsum_finish(ws.partial, nb, 2 * K * C, RgtSegs{{G[CAMO_RGT_C1_ATT_SRC], G[CAMO_RGT_C1_ATT_DST], nullptr, nullptr},
+                                                                 {0, K * C, 2 * K * C, 0, 0}, 2}, st), "attention vector sums");
+  g.add(ws.dh, K * C, x, In, G[CAMO_RGT_C1_W], In, K * C, In, N, KM);
+  CK(g.run(), "gat projection gradient");
   return 0;
 }
 }  // extern "C"

@@ -1,0 +1,478 @@
+// Loss and backward of the region-graph GNN with frozen batch-norm statistics (include/camo_rg_train.h).
+// Like the forward (rg_gnn.hip) the sparse part is latency- and HBM-bound gathers: one wave (GCN) or one block of `heads` waves
+// (GAT) per row of a CSR, source rows read as coalesced pieces, CPL channels per lane.  The backward of an aggregation is the same
+// gather walked over the REVERSED CSR, so every output row has one owner and no scatter is needed; every column sum over the
+// nodes (bias, batch-norm and attention-vector gradients) is per-block partials in row order, then a second stage in block order.
+// No floating-point atomic: the gradients are functions of the inputs alone.
+#include "rg_train.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr float BN_EPS = 1e-5f;
+
+struct HeadPtrs { const float* p[12]; };   // CAMO_RGD_* order
+
+__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
+
+// ---- forward, saving ------------------------------------------------------------------------------------------------------
+// grid N, block 64 * heads.  Two walks over the row: the maximum, then the sums (the saved m and S are what the backward
+// recomputes alpha from, so they are taken the plain way, not online).
+template <int CPL>
+__global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
+                                   const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias, BnEval bn,
+                                   float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O, float* __restrict__ xhat,
+                                   float* __restrict__ out, int heads, int C) {
+  __shared__ float red[8][64 * CPL];
+  const int i = blockIdx.x, k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float ad = a_dst[i * heads + k];
+  const int e0 = rowptr[i], e1 = rowptr[i + 1];
+  float m = -INFINITY;
+  for (int e = e0; e < e1; ++e) m = fmaxf(m, lrelu(a_src[col[e] * heads + k] + ad));
+  float s = 0.f, acc[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) acc[q] = 0.f;
+  for (int e = e0; e < e1; ++e) {
+    const int j = col[e];
+    const float p = expf(lrelu(a_src[j * heads + k] + ad) - m);
+    s += p;
+    const float* h = Hh + ((size_t)j * heads + k) * C;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) acc[q] = fmaf(p, h[c], acc[q]); }
+  }
+  const float inv = s > 0.f ? 1.0f / s : 0.f;
+  float* o = O + ((size_t)i * heads + k) * C;
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;
+    const float v = acc[q] * inv;
+    red[k][c] = v;
+    if (c < C) o[c] = v;
+  }
+  if (lane == 0) { m_out[i * heads + k] = m; S_out[i * heads + k] = s; }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float v = 0.f;
+    for (int kk = 0; kk < heads; ++kk) v += red[kk][c];
+    const float xh = (v / (float)heads + bias[c] - bn.mean[c]) / sqrtf(bn.var[c] + BN_EPS);
+    xhat[(size_t)i * C + c] = xh;
+    out[(size_t)i * C + c] = fmaxf(xh * bn.weight[c] + bn.bias[c], 0.f);
+  }
+}
+
+// one wave per target node, 4 nodes per block
+template <int CPL>
+__global__ void gcn_forward_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                   const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias, BnEval bn,
+                                   float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= N) return;
+  const float di = dinv[i];
+  float acc[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) acc[q] = 0.f;
+  for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+    const int j = col[e];
+    const float nrm = dinv[j] * w[e] * di;
+    const float* h = XW + (size_t)j * C;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) acc[q] = fmaf(nrm, h[c], acc[q]); }
+  }
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;
+    if (c < C) {
+      const float xh = (acc[q] + bias[c] - bn.mean[c]) / sqrtf(bn.var[c] + BN_EPS);
+      xhat[(size_t)i * C + c] = xh;
+      out[(size_t)i * C + c] = fmaxf(xh * bn.weight[c] + bn.bias[c], 0.f);
+    }
+  }
+}
+
+__global__ void concat_heads_kernel(HeadPtrs P, float* __restrict__ W1, float* __restrict__ b1, int H) {
+  const int Hh = H >> 1, units = 3 * Hh;
+  const int idx = blockIdx.x * NT + threadIdx.x;
+  if (idx < units * H) {
+    const int u = idx / H, k = idx - u * H, h = u / Hh;
+    W1[idx] = P.p[4 * h][(size_t)(u - h * Hh) * H + k];
+  } else if (idx < units * (H + 1)) {
+    const int u = idx - units * H, h = u / Hh;
+    b1[u] = P.p[4 * h + 1][u - h * Hh];
+  }
+}
+
+// one wave per node, 4 nodes per block: logit o = <W2_h[c, :], z_h> + b2_h[c], 64 partial sums of stride 64 added in a fixed tree
+__global__ void head_logits_kernel(HeadPtrs P, const float* __restrict__ Z, float* __restrict__ logits, int N, int H, int nc) {
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (n >= N) return;
+  const int Hh = H >> 1, L = 2 * nc + 1;
+  for (int o = 0; o < L; ++o) {
+    const int h = (o >= nc) + (o >= 2 * nc), c = o - h * nc;
+    const float* W2 = P.p[4 * h + 2] + (size_t)c * Hh;
+    const float* z = Z + (size_t)n * 3 * Hh + h * Hh;
+    float s = 0.f;
+    for (int j = lane; j < Hh; j += 64) s = fmaf(W2[j], z[j], s);
+    s = wave_sum(s);
+    if (lane == 0) logits[(size_t)n * L + o] = s + P.p[4 * h + 3][c];
+  }
+}
+
+// ---- loss -------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ONE block of 1024 threads.  First the integer counts of the non-ignored nodes, then per node the three terms and dlogits, already
+// scaled by weight / count; the sums are per-thread doubles in node order, a butterfly per wave, the 16 waves in order.
+__global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ logits, const int* __restrict__ mask_t, const int* __restrict__ inst_t,
+                                                    const float* __restrict__ edge_t, float wm, float wi, float we, int N, int nc,
+                                                    float* __restrict__ loss, float* __restrict__ dlogits) {
+  __shared__ int cnt_w[3][16];
+  __shared__ double sum_w[3][16];
+  __shared__ int cnt[3];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, L = 2 * nc + 1;
+  int c0 = 0, c1 = 0, c2 = 0;
+  for (int n = tid; n < N; n += 1024) {
+    const int a = mask_t[n], b = inst_t[n];
+    c0 += (a >= 0 && a < nc); c1 += (b >= 0 && b < nc); c2 += (edge_t[n] >= 0.f);
+  }
+  c0 = wave_sum_int(c0); c1 = wave_sum_int(c1); c2 = wave_sum_int(c2);
+  if (lane == 0) { cnt_w[0][wave] = c0; cnt_w[1][wave] = c1; cnt_w[2][wave] = c2; }
+  __syncthreads();
+  if (tid < 3) {
+    int s = 0;
+    for (int v = 0; v < 16; ++v) s += cnt_w[tid][v];
+    cnt[tid] = s;
+  }
+  __syncthreads();
+  const int n0 = cnt[0], n1 = cnt[1], n2 = cnt[2];
+  const float sc[3] = {n0 > 0 ? wm / (float)n0 : 0.f, n1 > 0 ? wi / (float)n1 : 0.f, n2 > 0 ? we / (float)n2 : 0.f};
+  double a[3] = {0.0, 0.0, 0.0};
+  for (int n = tid; n < N; n += 1024) {
+    const float* l = logits + (size_t)n * L;
+    float* d = dlogits + (size_t)n * L;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int t = h ? inst_t[n] : mask_t[n];
+      const float* lh = l + h * nc;
+      float* dh = d + h * nc;
+      if (t < 0 || t >= nc) {
+        for (int c = 0; c < nc; ++c) dh[c] = 0.f;
+      } else {
+        float mx = lh[0];
+        for (int c = 1; c < nc; ++c) mx = fmaxf(mx, lh[c]);
+        float den = 0.f;
+        for (int c = 0; c < nc; ++c) den += expf(lh[c] - mx);
+        a[h] += (double)(mx + logf(den) - lh[t]);
+        for (int c = 0; c < nc; ++c) dh[c] = (expf(lh[c] - mx) / den - (c == t ? 1.f : 0.f)) * sc[h];
+      }
+    }
+    const float t = edge_t[n], z = l[2 * nc];
+    if (t >= 0.f) {
+      a[2] += (double)(fmaxf(z, 0.f) - z * t + logf(1.0f + expf(-fabsf(z))));
+      d[2 * nc] = (1.0f / (1.0f + expf(-z)) - t) * sc[2];
+    } else {
+      d[2 * nc] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 3; ++h) {
+    const double v = wave_sum_f64(a[h]);
+    if (lane == 0) sum_w[h][wave] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double term[3];
+    for (int h = 0; h < 3; ++h) {
+      double s = 0.0;
+      for (int v = 0; v < 16; ++v) s += sum_w[h][v];
+      term[h] = cnt[h] > 0 ? s / (double)cnt[h] : 0.0;
+    }
+    loss[0] = (float)((double)wm * term[0] + (double)wi * term[1] + (double)we * term[2]);
+    loss[1] = (float)term[0]; loss[2] = (float)term[1]; loss[3] = (float)term[2];
+  }
+}
+
+// ---- dense pieces that are too thin for the GEMM --------------------------------------------------------------------------
+__global__ void head_dz_kernel(HeadPtrs P, const float* __restrict__ Z, const float* __restrict__ dlogits, float* __restrict__ dZ,
+                               long long total, int H, int nc) {
+  const long long idx = (long long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= total) return;
+  const int Hh = H >> 1, units = 3 * Hh, L = 2 * nc + 1;
+  const long long n = idx / units;
+  const int u = (int)(idx - n * units), h = u / Hh, j = u - h * Hh, nch = h < 2 ? nc : 1;
+  float v = 0.f;
+  if (Z[idx] > 0.f) {
+    const float* dl = dlogits + n * L + h * nc;
+    const float* W2 = P.p[4 * h + 2];
+    for (int c = 0; c < nch; ++c) v = fmaf(dl[c], W2[(size_t)c * Hh + j], v);
+  }
+  dZ[idx] = v;
+}
+
+// grid (row blocks, column blocks): thread = output (m, c), the block's rows in increasing order
+__global__ void cross_partial_kernel(const float* __restrict__ A, int lda, int MA, const float* __restrict__ B, int ldb, int NB, int N,
+                                     float* __restrict__ partial) {
+  const int idx = blockIdx.y * NT + threadIdx.x, W = MA * NB;
+  if (idx >= W) return;
+  const int mi = idx / NB, c = idx - mi * NB;
+  const int r0 = blockIdx.x * RGT_ROWS, r1 = min(N, r0 + RGT_ROWS);
+  float s = 0.f;
+  for (int r = r0; r < r1; ++r) s = fmaf(A ? A[(size_t)r * lda + mi] : 1.0f, B[(size_t)r * ldb + c], s);
+  partial[(size_t)blockIdx.x * W + idx] = s;
+}
+
+__global__ void colsum_finish_kernel(const float* __restrict__ partial, int nb, int width, RgtSegs segs) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= width) return;
+  float s = 0.f;
+  for (int b = 0; b < nb; ++b) s += partial[(size_t)b * width + c];
+  for (int g = 0; g < segs.n; ++g)
+    if (c >= segs.beg[g] && c < segs.beg[g + 1]) segs.out[g][c - segs.beg[g]] = s;
+}
+
+__global__ void bn_backward_kernel(float* __restrict__ d, const float* __restrict__ xhat, BnEval bn, int N, int C, float* __restrict__ partial) {
+  const int c = blockIdx.y * NT + threadIdx.x;
+  if (c >= C) return;
+  const float scale = bn.weight[c] / sqrtf(bn.var[c] + BN_EPS);
+  const int r0 = blockIdx.x * RGT_ROWS, r1 = min(N, r0 + RGT_ROWS);
+  float s0 = 0.f, s1 = 0.f;
+  for (int r = r0; r < r1; ++r) {
+    const size_t at = (size_t)r * C + c;
+    const float dy = d[at];
+    s0 = fmaf(dy, xhat[at], s0);
+    s1 += dy;
+    d[at] = dy * scale;
+  }
+  partial[((size_t)blockIdx.x * 2) * C + c] = s0;
+  partial[((size_t)blockIdx.x * 2 + 1) * C + c] = s1;
+}
+
+__global__ void bn_finish_kernel(const float* __restrict__ partial, int nb, BnEval bn, int C, float* __restrict__ dweight,
+                                 float* __restrict__ dbias_bn, float* __restrict__ dbias_conv) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= C) return;
+  float s0 = 0.f, s1 = 0.f;
+  for (int b = 0; b < nb; ++b) { s0 += partial[((size_t)b * 2) * C + c]; s1 += partial[((size_t)b * 2 + 1) * C + c]; }
+  dweight[c] = s0;
+  dbias_bn[c] = s1;
+  dbias_conv[c] = s1 * (bn.weight[c] / sqrtf(bn.var[c] + BN_EPS));
+}
+
+// ---- sparse backward ------------------------------------------------------------------------------------------------------------
+// one wave per SOURCE node j, 4 nodes per block: the forward's gather over the reversed CSR, with the forward's dinv
+template <int CPL>
+__global__ void gcn_backward_kernel(const float* __restrict__ dPre, const int* __restrict__ rrowptr, const int* __restrict__ rcol,
+                                    const float* __restrict__ rw, const float* __restrict__ dinv, float* __restrict__ dXW, int N, int C) {
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (j >= N) return;
+  const float dj = dinv[j];
+  float acc[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) acc[q] = 0.f;
+  for (int e = rrowptr[j]; e < rrowptr[j + 1]; ++e) {
+    const int i = rcol[e];
+    const float nrm = dj * rw[e] * dinv[i];
+    const float* g = dPre + (size_t)i * C;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) acc[q] = fmaf(nrm, g[c], acc[q]); }
+  }
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) dXW[(size_t)j * C + c] = acc[q]; }
+}
+
+// grid N (target i), block 64 * heads.  (Every lane of a wave walks the same edges: the butterflies are wave-uniform.)
+template <int CPL>
+__global__ void gat_backward_a_kernel(const float* __restrict__ dPre, const float* __restrict__ Hh, const float* __restrict__ O,
+                                      const float* __restrict__ a_src, const float* __restrict__ a_dst, const float* __restrict__ m,
+                                      const float* __restrict__ S, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                      float* __restrict__ r_out, float* __restrict__ da_dst, int heads, int C) {
+  const int i = blockIdx.x, k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float invh = 1.0f / (float)heads;
+  float g[CPL], dot = 0.f;
+  const float* o = O + ((size_t)i * heads + k) * C;
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;
+    g[q] = c < C ? dPre[(size_t)i * C + c] * invh : 0.f;
+    dot = fmaf(g[q], c < C ? o[c] : 0.f, dot);
+  }
+  const float r = wave_sum(dot);
+  const float ad = a_dst[i * heads + k], mm = m[i * heads + k], den = S[i * heads + k];
+  float dd = 0.f;
+  for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+    const int j = col[e];
+    const float s = a_src[j * heads + k] + ad;
+    const float alpha = expf(lrelu(s) - mm) / den;
+    const float* h = Hh + ((size_t)j * heads + k) * C;
+    float da = 0.f;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; da = fmaf(g[q], c < C ? h[c] : 0.f, da); }
+    da = wave_sum(da);
+    dd += alpha * (da - r) * (s > 0.f ? 1.0f : 0.2f);
+  }
+  if (lane == 0) { r_out[i * heads + k] = r; da_dst[i * heads + k] = dd; }
+}
+
+// grid N (source j), block 64 * heads
+template <int CPL>
+__global__ void gat_backward_b_kernel(const float* __restrict__ dPre, const float* __restrict__ Hh, const float* __restrict__ a_src,
+                                      const float* __restrict__ a_dst, const float* __restrict__ m, const float* __restrict__ S,
+                                      const float* __restrict__ r, const float* __restrict__ da_dst, const float* __restrict__ att_src,
+                                      const float* __restrict__ att_dst, const int* __restrict__ rrowptr, const int* __restrict__ rcol,
+                                      float* __restrict__ da_src, float* __restrict__ dh, int heads, int C) {
+  const int j = blockIdx.x, k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float invh = 1.0f / (float)heads;
+  const float* h = Hh + ((size_t)j * heads + k) * C;
+  float hj[CPL], acc[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; hj[q] = c < C ? h[c] : 0.f; acc[q] = 0.f; }
+  const float as = a_src[j * heads + k];
+  float dsum = 0.f;
+  for (int e = rrowptr[j]; e < rrowptr[j + 1]; ++e) {
+    const int i = rcol[e];
+    const float s = as + a_dst[i * heads + k];
+    const float alpha = expf(lrelu(s) - m[i * heads + k]) / S[i * heads + k];
+    float g[CPL], da = 0.f;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+      const int c = lane + 64 * q;
+      g[q] = c < C ? dPre[(size_t)i * C + c] * invh : 0.f;
+      da = fmaf(g[q], hj[q], da);
+    }
+    da = wave_sum(da);
+    dsum += alpha * (da - r[i * heads + k]) * (s > 0.f ? 1.0f : 0.2f);
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) acc[q] = fmaf(alpha, g[q], acc[q]);
+  }
+  const float dd = da_dst[j * heads + k];
+  float* out = dh + ((size_t)j * heads + k) * C;
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;
+    if (c < C) out[c] = acc[q] + dsum * att_src[k * C + c] + dd * att_dst[k * C + c];
+  }
+  if (lane == 0) da_src[j * heads + k] = dsum;
+}
+
+__global__ void att_partial_kernel(const float* __restrict__ da_src, const float* __restrict__ da_dst, const float* __restrict__ Hh, int N,
+                                   int heads, int C, float* __restrict__ partial) {
+  const int idx = blockIdx.y * NT + threadIdx.x, KC = heads * C;
+  if (idx >= KC) return;
+  const int k = idx / C;
+  const int r0 = blockIdx.x * RGT_ROWS, r1 = min(N, r0 + RGT_ROWS);
+  float s0 = 0.f, s1 = 0.f;
+  for (int n = r0; n < r1; ++n) {
+    const float h = Hh[(size_t)n * KC + idx];
+    s0 = fmaf(da_src[n * heads + k], h, s0);
+    s1 = fmaf(da_dst[n * heads + k], h, s1);
+  }
+  partial[((size_t)blockIdx.x * 2) * KC + idx] = s0;
+  partial[((size_t)blockIdx.x * 2 + 1) * KC + idx] = s1;
+}
+
+HeadPtrs head_ptrs(const float* const* hp) {
+  HeadPtrs P;
+  for (int i = 0; i < 12; ++i) P.p[i] = hp[i];
+  return P;
+}
+
+}  // namespace
+
+int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
+                           BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream) {
+  if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
+  if (C <= 128) hipLaunchKernelGGL(gat_forward_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
+  else          hipLaunchKernelGGL(gat_forward_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_gcn_forward(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
+                           BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream) {
+  if (C > 512) return (int)hipErrorInvalidValue;
+  if (C <= 128) hipLaunchKernelGGL(gcn_forward_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
+  else          hipLaunchKernelGGL(gcn_forward_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_concat_heads(const float* const* hp, float* W1, float* b1, int hidden, hipStream_t stream) {
+  const int total = 3 * (hidden / 2) * (hidden + 1);
+  hipLaunchKernelGGL(concat_heads_kernel, dim3((total + NT - 1) / NT), dim3(NT), 0, stream, head_ptrs(hp), W1, b1, hidden);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_head_logits(const float* const* hp, const float* Z, float* logits, int N, int hidden, int nc, hipStream_t stream) {
+  hipLaunchKernelGGL(head_logits_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, head_ptrs(hp), Z, logits, N, hidden, nc);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_loss(const float* logits, const int* mask_t, const int* inst_t, const float* edge_t, float wm, float wi, float we, int N,
+                    int nc, float* loss, float* dlogits, hipStream_t stream) {
+  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(1024), 0, stream, logits, mask_t, inst_t, edge_t, wm, wi, we, N, nc, loss, dlogits);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream) {
+  const long long total = (long long)N * 3 * (hidden / 2);
+  hipLaunchKernelGGL(head_dz_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, stream, head_ptrs(hp), Z, dlogits, dZ, total, hidden, nc);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_cross_partial(const float* A, int lda, int MA, const float* B, int ldb, int NB, int N, float* partial, hipStream_t stream) {
+  hipLaunchKernelGGL(cross_partial_kernel, dim3(rgt_row_blocks(N), (MA * NB + NT - 1) / NT), dim3(NT), 0, stream, A, lda, MA, B, ldb, NB, N, partial);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_colsum_finish(const float* partial, int nb, int width, RgtSegs segs, hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3((width + NT - 1) / NT), dim3(NT), 0, stream, partial, nb, width, segs);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_bn_backward(float* d, const float* xhat, BnEval bn, int N, int C, float* partial, hipStream_t stream) {
+  hipLaunchKernelGGL(bn_backward_kernel, dim3(rgt_row_blocks(N), (C + NT - 1) / NT), dim3(NT), 0, stream, d, xhat, bn, N, C, partial);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* dweight, float* dbias_bn, float* dbias_conv, hipStream_t stream) {
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((C + NT - 1) / NT), dim3(NT), 0, stream, partial, nb, bn, C, dweight, dbias_bn, dbias_conv);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_gcn_backward(const float* dPre, const int* rrowptr, const int* rcol, const float* rw, const float* dinv, float* dXW, int N,
+                            int C, hipStream_t stream) {
+  if (C > 512) return (int)hipErrorInvalidValue;
+  if (C <= 128) hipLaunchKernelGGL(gcn_backward_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, stream, dPre, rrowptr, rcol, rw, dinv, dXW, N, C);
+  else          hipLaunchKernelGGL(gcn_backward_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, stream, dPre, rrowptr, rcol, rw, dinv, dXW, N, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_gat_backward_a(const float* dPre, const float* Hh, const float* O, const float* a_src, const float* a_dst, const float* m,
+                              const float* S, const int* rowptr, const int* col, float* r, float* da_dst, int N, int heads, int C,
+                              hipStream_t stream) {
+  if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
+  if (C <= 128) hipLaunchKernelGGL(gat_backward_a_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, dPre, Hh, O, a_src, a_dst, m, S, rowptr, col, r, da_dst, heads, C);
+  else          hipLaunchKernelGGL(gat_backward_a_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, dPre, Hh, O, a_src, a_dst, m, S, rowptr, col, r, da_dst, heads, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_gat_backward_b(const float* dPre, const float* Hh, const float* a_src, const float* a_dst, const float* m, const float* S,
+                              const float* r, const float* da_dst, const float* att_src, const float* att_dst, const int* rrowptr,
+                              const int* rcol, float* da_src, float* dh, int N, int heads, int C, hipStream_t stream) {
+  if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
+  if (C <= 128) hipLaunchKernelGGL(gat_backward_b_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, dPre, Hh, a_src, a_dst, m, S, r, da_dst, att_src, att_dst, rrowptr, rcol, da_src, dh, heads, C);
+  else          hipLaunchKernelGGL(gat_backward_b_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, dPre, Hh, a_src, a_dst, m, S, r, da_dst, att_src, att_dst, rrowptr, rcol, da_src, dh, heads, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_att_partial(const float* da_src, const float* da_dst, const float* Hh, int N, int heads, int C, float* partial,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(att_partial_kernel, dim3(rgt_row_blocks(N), (heads * C + NT - 1) / NT), dim3(NT), 0, stream, da_src, da_dst, Hh, N, heads, C, partial);
+  return (int)hipGetLastError();
+}

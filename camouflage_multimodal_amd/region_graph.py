@@ -6,8 +6,10 @@
 inference -- runs as HIP kernels behind ``camo_rg_node_embeddings`` (include/camo_rg_gnn.h).  The graph layers are
 torch_geometric's in the reference; the published algorithms they are restated from and the CPU checker the kernels are
 tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here, no RG weights or fixtures shipped).  The node-classification ``forward``
-runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py); training the RG model
-(models/region_graph/train.py) is outside the path, so ``forward`` in training mode raises.
+runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py).  ``loss_and_gradients``
+gives the loss on the heads and every parameter's gradient with the batch-norm statistics frozen (``camo_rg_loss_backward``,
+include/camo_rg_train.h); batch statistics and dropout (models/region_graph/train.py) are outside the path, so ``forward`` in
+training mode raises.
 """
 from __future__ import annotations
 
@@ -469,12 +471,110 @@ class RegionGraphGNN(nn.Module):
         (models/region_graph/test.py::detect_camouflage).  Eval-mode arithmetic whatever the module's mode."""
         return self.node_heads(self.extract_node_embeddings(data))[1]
 
+    def trainable_parameters(self):
+        """The 32 parameters ``loss_and_gradients`` writes a gradient for, in the order of the gradient table of
+        include/camo_rg_train.h: the embedding path's 20 (``_param_table`` without the running statistics), then the heads' 12."""
+        t = [self.conv1.att_src, self.conv1.att_dst, self.conv1.bias, self.conv1.lin.weight, self.bn1.weight, self.bn1.bias]
+        for conv, bn in ((self.conv2, self.bn2), (self.conv3, self.bn3), (self.conv4, self.bn4)):
+            t += [conv.bias, conv.lin.weight, bn.weight, bn.bias]
+        t += [self.fc_shared.weight, self.fc_shared.bias]
+        for name in ("fc_mask", "fc_instance", "fc_edge"):
+            for layer in (getattr(self, name + "_1"), getattr(self, name + "_2")):
+                t += [layer.weight, layer.bias]
+        assert len(t) == _lib.RGT_NGRADS
+        return t
+
+    @torch.no_grad()
+    def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.)):
+        """``loss_and_gradients`` on CSR arrays the caller built: ``csr`` = (rowptr, col, w) by target, ``reversed_csr`` the same
+        for the graph with every edge turned round (both from ``build_target_csr_device``; they must hold the same edges).  One
+        library call (``camo_rg_loss_backward``, include/camo_rg_train.h).  Returns (loss fp32 [4] = total, mask, instance, edge;
+        list of 32 gradient tensors in ``trainable_parameters`` order, views of one buffer).  The result is a function of the
+        arrays alone: two calls on the same arrays give the same bytes."""
+        _lib.require_device(x, "x")
+        if x.dim() != 2 or x.shape[1] != self._dims.in_channels or x.shape[0] < 1:
+            raise RuntimeError(f"x of shape {tuple(x.shape)} does not match in_channels {self._dims.in_channels}")
+        n, dev = x.shape[0], x.device
+        x = x.detach().to(torch.float32).contiguous()
+        graph = []
+        for t, dt in zip(tuple(csr) + tuple(reversed_csr), (torch.int32, torch.int32, torch.float32) * 2):
+            _lib.require_device(t, "csr")
+            graph.append(t.to(dt).contiguous())
+        rowptr, col, w, rrowptr, rcol, rw = graph
+        E = col.shape[0]
+        if rowptr.shape[0] != n + 1 or rrowptr.shape[0] != n + 1 or w.shape[0] != E or rcol.shape[0] != E or rw.shape[0] != E:
+            raise RuntimeError("the two CSRs do not describe the same graph of x.shape[0] nodes")
+        tg = []
+        for t, dt, name in ((mask_target, torch.int32, "mask_target"), (instance_target, torch.int32, "instance_target"),
+                            (edge_target, torch.float32, "edge_target")):
+            _lib.require_device(t, name)
+            t = t.detach().reshape(-1).to(dt).contiguous()
+            if t.shape[0] != n:
+                raise RuntimeError(f"{name} has {t.shape[0]} entries for {n} nodes")
+            tg.append(t)
+        wm, wi, we = (float(v) for v in loss_weights)
+        L = _lib.lib()
+        need = L.camo_rg_train_workspace_bytes(C.byref(self._dims), self.num_classes, n, E)
+        if need == 0:
+            _lib.check(-1, "camo_rg_train_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        params = self.trainable_parameters()
+        flat = torch.empty(sum(-(-p.numel() // 64) * 64 for p in params), dtype=torch.float32, device=dev)    # (256-byte aligned pieces)
+        grads, at = [], 0
+        for p in params:
+            grads.append(flat[at:at + p.numel()].view(p.shape))
+            at += -(-p.numel() // 64) * 64
+        loss = torch.empty(4, dtype=torch.float32, device=dev)
+        tab, keep = self._param_table()
+        htab, hkeep = self._head_table()
+        gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        with torch.cuda.device(dev):
+            rc = L.camo_rg_loss_backward(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w),
+                                         _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi, we,
+                                         _ptr(ws), ws.numel(), _ptr(loss), gtab, _stream_ptr(dev))
+        _lib.check(rc, "camo_rg_loss_backward")
+        return loss, grads
+
+    @torch.no_grad()
+    def loss_and_gradients(self, data, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), accumulate=False, csr=None):
+        """Loss on the three node heads and the gradient of every trainable parameter, with the BatchNorm layers on their running
+        statistics and dropout off: eval-mode arithmetic (like ``node_probabilities``, whatever the module's mode) plus a backward --
+        fine-tuning with frozen statistics (include/camo_rg_train.h).  ``data``: a ``RegionGraphData`` or ``RegionGraphBatch`` (the
+        loss means then run over the whole block-diagonal graph).  Per node: ``mask_target`` / ``instance_target`` integer class or
+        -1 to ignore the node, ``edge_target`` float in [0, 1] or negative to ignore it.
+        ``loss = w_m CE(mask) + w_i CE(instance) + w_e BCEWithLogits(edge)``, each a mean over its non-ignored nodes (0 when there are
+        none).  Sets ``.grad`` of the 32 ``trainable_parameters()`` (adds into an existing ``.grad`` with ``accumulate``); the running
+        statistics are not touched, and any torch optimizer can step on the result.  Returns 0-d device tensors ``loss``,
+        ``mask_loss``, ``instance_loss``, ``edge_loss``.  Both CSRs are built on the device and ONE library call does the rest; no
+        host synchronisation.  ``csr``: the pair (CSR by target, CSR of the reversed graph) of an earlier
+        ``build_target_csr_device`` of this graph, for a graph that is trained on again and again; the builder leaves a row's edges in
+        no particular order, so only calls on the same pair are sure to add in the same order and give the same bytes."""
+        x, edge_index = data.x, data.edge_index
+        edge_attr = getattr(data, "edge_attr", None)
+        _lib.require_device(x, "x")
+        _lib.require_device(edge_index, "edge_index")
+        n = x.shape[0]
+        ew = None if edge_attr is None or edge_attr.numel() == 0 else edge_attr.reshape(-1)
+        if csr is None:
+            csr = (build_target_csr_device(n, edge_index, ew), build_target_csr_device(n, edge_index.flip(0), ew))
+        csr, rcsr = csr
+        loss, grads = self.loss_and_gradients_csr(x, csr, rcsr, mask_target, instance_target, edge_target, loss_weights)
+        for p, g in zip(self.trainable_parameters(), grads):
+            g = g.to(p.dtype)
+            if accumulate and p.grad is not None:
+                p.grad.add_(g)
+            else:
+                p.grad = g
+        return {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
+
     def forward(self, data):
         """Eval mode: (mask_logits [n, c], instance_logits [n, c], edge_logits [n, 1]), views of one tensor.  Training mode raises:
-        training the RG model (train.py: batch statistics, dropout, a backward) is outside the MI355X path."""
+        the forward with batch statistics and dropout (train.py) is outside the MI355X path; ``loss_and_gradients`` gives the loss and
+        the gradients with the statistics frozen."""
         if self.training:
             raise _lib.CamoError("RegionGraphGNN.forward in training mode: training the RG model (models/region_graph/train.py) is "
-                                 "outside the MI355X path; call .eval() for the node-classification heads, or use extract_node_embeddings()")
+                                 "outside the MI355X path; call .eval() for the node-classification heads, or use extract_node_embeddings() "
+                                 "(loss_and_gradients() gives the loss and gradients with the batch-norm statistics frozen)")
         logits, _ = self.node_heads(self.extract_node_embeddings(data))
         c = self.num_classes
         return logits[:, :c], logits[:, c:2 * c], logits[:, 2 * c:]

@@ -1,0 +1,36 @@
+"""Developer aid / measurement of the Region-Graph GNN's loss and gradients with frozen batch norm: one
+loss_and_gradients call against extract_node_embeddings + node_heads on the same graphs, in the same run, at 16 and at 128 graphs of
+~410 nodes.
+  python tools/dev/dev_rg_train_bench.py [graphs_per_batch ...]"""
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np, torch
+from camouflage_multimodal_amd import RegionGraphData, RegionGraphGNN
+from oracle import rg_gnn_oracle as RO
+
+
+def timed(fn, it=30, warm=5):
+    for _ in range(warm): fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(it): fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / it
+
+
+m = RegionGraphGNN().cuda().eval()
+for G in [int(a) for a in sys.argv[1:]] or [16, 128]:
+    gs = [RO.make_graph(int(n), seed=i) for i, n in enumerate(np.random.RandomState(0).randint(303, 518, size=G))]
+    off = np.cumsum([0] + [g[0].shape[0] for g in gs])
+    x = torch.from_numpy(np.concatenate([g[0] for g in gs])).cuda()
+    ei = torch.from_numpy(np.concatenate([g[1] + off[i] for i, g in enumerate(gs)], axis=1)).cuda()
+    ew = torch.from_numpy(np.concatenate([g[2] for g in gs])).cuda()
+    data = RegionGraphData(x, ei, ew[:, None])
+    N = x.shape[0]
+    rs = np.random.RandomState(1)
+    mt, it_ = (torch.from_numpy(rs.randint(0, 2, size=N).astype(np.int32)).cuda() for _ in range(2))
+    et = torch.from_numpy(rs.uniform(0, 1, size=N).astype(np.float32)).cuda()
+    fwd = timed(lambda: m.node_heads(m.extract_node_embeddings(data)))
+    trn = timed(lambda: m.loss_and_gradients(data, mt, it_, et))
+    print(f"{G} graphs / {N} nodes / {ei.shape[1] + N} CSR entries: forward (embeddings + heads) {fwd * 1e6:.1f} us, "
+          f"loss_and_gradients {trn * 1e6:.1f} us = {trn / fwd:.2f} x the forward (both include their CSR builds)")
