@@ -1,0 +1,71 @@
+// Host-side vocabulary of the C ABI files (fusion_abi.hip, rg_abi.hip): the error return, the workspace carver and the builder of
+// an exact-fp32 GEMM batch.  No device code.
+#pragma once
+#include <cstring>
+#include <string>
+
+#include "../../include/camo_fusion.h"
+#include "gemm.h"
+
+namespace camo_abi {
+
+// Set the calling thread's camo_last_error() string and return the code.  Defined once, in fusion_abi.hip, next to the string; hidden:
+// shared between the library's own files, not exported.
+__attribute__((visibility("hidden"))) int fail(int code, const std::string& msg);
+__attribute__((visibility("hidden"))) int fail_hip(int e, const char* where);
+#define CK(x, where)                                   \
+  do {                                                 \
+    int e_ = (x);                                      \
+    if (e_ != 0) return camo_abi::fail_hip(e_, where); \
+  } while (0)
+
+struct Carver {
+  char* base; size_t off;
+  explicit Carver(void* b) : base(static_cast<char*>(b)), off(0) {}
+  template <typename T> T* take(size_t n) {
+    off = (off + 255) & ~size_t(255);
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += n * sizeof(T);
+    return p;
+  }
+};
+
+struct GB {
+  GemmBatch b;
+  int prec; hipStream_t st;
+  GB(const DropCfg& d, int prec_, hipStream_t st_) : prec(prec_), st(st_) { std::memset(&b, 0, sizeof(b)); b.drop = d; }
+  GemmProb& add(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K, int flags) {
+    GemmProb& p = b.p[b.n++];
+    std::memset(&p, 0, sizeof(p));   // slots are reused across launches: no stale res/bias_grad/flags
+    p.A = A; p.lda = lda; p.B = Bm; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.flags = flags;
+    p.aux_scale = 1.f;
+    return p;
+  }
+  // y = x.W^T (+bias): x [M,K], W [N,K]
+  GemmProb& nt(const float* x, int ldx, const float* W, int ldw, const float* bias, float* y, int ldy, int M, int N, int K, int flags = 0) {
+    GemmProb& p = add(x, ldx, W, ldw, y, ldy, M, N, K, flags);
+    p.bias = bias;
+    return p;
+  }
+  // dx = dy.W : dy [M,K=Nout], W [Nout, N=in]
+  GemmProb& nn(const float* dy, int lddy, const float* W, int ldw, float* dx, int lddx, int M, int N, int K, int flags = 0) {
+    return add(dy, lddy, W, ldw, dx, lddx, M, N, K, flags | GF_B_KMAJOR);
+  }
+  // dW [Nout, Nin] += dy^T.x : dy [rows, Nout], x [rows, Nin]; db [Nout] += colsum(dy)
+  GemmProb& tn(const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, float* db, int Nout, int Nin, int rows) {
+    GemmProb& p = add(dy, lddy, x, ldx, dW, lddw, Nout, Nin, rows, GF_A_KMAJOR | GF_B_KMAJOR | GF_ATOMIC);
+    p.bias_grad = db;
+    return p;
+  }
+  int run() {
+    if (b.n == 0) return 0;
+    int e = launch_gemm_batch(b, prec, st);
+    b.n = 0;
+    return e;
+  }
+};
+inline void set_relu_bwd(GemmProb& p, const float* act, int ldr, float scale) {
+  p.flags |= GF_RELU_BWD; p.res = act; p.ldr = ldr; p.aux_scale = scale;
+}
+
+}  // namespace camo_abi

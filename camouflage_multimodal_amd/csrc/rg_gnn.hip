@@ -7,11 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ float bn_relu(float v, const BnEval& bn, int c) {
-  v = (v - bn.mean[c]) / sqrtf(bn.var[c] + 1e-5f) * bn.weight[c] + bn.bias[c];
-  return fmaxf(v, 0.f);
-}
-
 __global__ void gcn_dinv_kernel(const int* __restrict__ rowptr, const float* __restrict__ w, float* __restrict__ dinv, int N) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
@@ -45,8 +40,7 @@ __global__ void gat_aggregate_kernel(const float* __restrict__ Hh, const float* 
   for (int q = 0; q < CPL; ++q) acc[q] = 0.f;
   for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
     const int j = col[e];
-    float v = a_src[j * heads + k] + ad;
-    v = v > 0.f ? v : 0.2f * v;
+    const float v = lrelu(a_src[j * heads + k] + ad);
     const float mn = fmaxf(m, v);
     const float corr = __expf(m - mn), p = __expf(v - mn);       // (m = -inf on the first edge: corr = 0)
     s = s * corr + p;
@@ -62,15 +56,15 @@ __global__ void gat_aggregate_kernel(const float* __restrict__ Hh, const float* 
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float v = 0.f;
     for (int kk = 0; kk < heads; ++kk) v += red[kk][c];
-    out[(size_t)i * C + c] = bn_relu(v / (float)heads + bias[c], bn, c);
+    out[(size_t)i * C + c] = bn_relu(bn_xhat(v / (float)heads + bias[c], bn, c), bn, c);
   }
 }
 
-// one wave per target node, 4 nodes per block
-template <int CPL>
+// one wave per target node, 4 nodes per block.  SAVE: the training forward's instantiation, which also keeps xhat for the backward
+template <int CPL, bool SAVE>
 __global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
                                      const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
-                                     BnEval bn, float* __restrict__ out, int N, int C) {
+                                     BnEval bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= N) return;
   const float di = dinv[i];
@@ -85,7 +79,14 @@ __global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __
     for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) acc[q] = fmaf(nrm, h[c], acc[q]); }
   }
 #pragma unroll
-  for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) out[(size_t)i * C + c] = bn_relu(acc[q] + bias[c], bn, c); }
+  for (int q = 0; q < CPL; ++q) {
+    const int c = lane + 64 * q;
+    if (c < C) {
+      const float xh = bn_xhat(acc[q] + bias[c], bn, c);
+      if constexpr (SAVE) xhat[(size_t)i * C + c] = xh;
+      out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+    }
+  }
 }
 
 // ---- CSR-by-target construction from a COO edge list (counting sort by target; one self-loop per node) ----
@@ -168,10 +169,16 @@ int launch_gat_aggregate(const float* Hh, const float* a_src, const float* a_dst
   return (int)hipGetLastError();
 }
 
+template <int CPL, bool SAVE>
+static void gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias, BnEval bn,
+                          float* xhat, float* out, int N, int C, hipStream_t stream) {
+  hipLaunchKernelGGL((gcn_aggregate_kernel<CPL, SAVE>), dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
+}
+
 int launch_gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                         BnEval bn, float* out, int N, int C, hipStream_t stream) {
+                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream) {
   if (C > 512) return (int)hipErrorInvalidValue;
-  if (C <= 128) hipLaunchKernelGGL(gcn_aggregate_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, out, N, C);
-  else          hipLaunchKernelGGL(gcn_aggregate_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, out, N, C);
+  auto run = C <= 128 ? (xhat ? gcn_aggregate<2, true> : gcn_aggregate<2, false>) : (xhat ? gcn_aggregate<8, true> : gcn_aggregate<8, false>);
+  run(XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, stream);
   return (int)hipGetLastError();
 }

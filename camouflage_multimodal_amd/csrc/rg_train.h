@@ -1,5 +1,5 @@
 // Kernels of the region-graph GNN's loss and backward with frozen batch-norm statistics (rg_train.hip, include/camo_rg_train.h,
-// DESIGN.md 9a): the saving variants of the two sparse aggregations, the loss on the node heads, the backward of the aggregations
+// DESIGN.md 9a): the saving variant of the GAT aggregation, the loss on the node heads, the backward of the aggregations
 // over the reversed CSR, and the fixed-order column sums behind every bias / batch-norm / attention-vector gradient.  No
 // floating-point atomic anywhere: every sum has one owner and a fixed order.  All launchers return hipError_t as int; the callers
 // have checked the arguments.
@@ -13,9 +13,7 @@ inline int rgt_row_blocks(int N) { return (N + RGT_ROWS - 1) / RGT_ROWS; }
 // O [N, heads, C] per-head aggregates, xhat [N, C] = (pre - mean) / sqrt(var + 1e-5), out [N, C] = relu(xhat * weight + bias_bn)
 int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
                            BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream);
-// GCN aggregate that keeps xhat and out (as above)
-int launch_rgt_gcn_forward(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                           BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream);
+// (the GCN aggregate that keeps xhat is rg_gnn.h's launch_gcn_aggregate with a non-null xhat)
 // copies the three heads' first layers into one [3 hidden / 2, hidden] weight and one [3 hidden / 2] bias
 int launch_rgt_concat_heads(const float* const* hp, float* W1, float* b1, int hidden, hipStream_t stream);
 // logits [N, 2 nc + 1] from Z [N, 3 hidden / 2] (the heads' hidden activations): one wave per node

@@ -9,11 +9,8 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr float BN_EPS = 1e-5f;
 
 struct HeadPtrs { const float* p[12]; };   // CAMO_RGD_* order
-
-__device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
 
 // ---- forward, saving ------------------------------------------------------------------------------------------------------
 // grid N, block 64 * heads.  Two walks over the row: the maximum, then the sums (the saved m and S are what the backward
@@ -54,38 +51,9 @@ __global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float v = 0.f;
     for (int kk = 0; kk < heads; ++kk) v += red[kk][c];
-    const float xh = (v / (float)heads + bias[c] - bn.mean[c]) / sqrtf(bn.var[c] + BN_EPS);
+    const float xh = bn_xhat(v / (float)heads + bias[c], bn, c);
     xhat[(size_t)i * C + c] = xh;
-    out[(size_t)i * C + c] = fmaxf(xh * bn.weight[c] + bn.bias[c], 0.f);
-  }
-}
-
-// one wave per target node, 4 nodes per block
-template <int CPL>
-__global__ void gcn_forward_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
-                                   const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias, BnEval bn,
-                                   float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (i >= N) return;
-  const float di = dinv[i];
-  float acc[CPL];
-#pragma unroll
-  for (int q = 0; q < CPL; ++q) acc[q] = 0.f;
-  for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
-    const int j = col[e];
-    const float nrm = dinv[j] * w[e] * di;
-    const float* h = XW + (size_t)j * C;
-#pragma unroll
-    for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < C) acc[q] = fmaf(nrm, h[c], acc[q]); }
-  }
-#pragma unroll
-  for (int q = 0; q < CPL; ++q) {
-    const int c = lane + 64 * q;
-    if (c < C) {
-      const float xh = (acc[q] + bias[c] - bn.mean[c]) / sqrtf(bn.var[c] + BN_EPS);
-      xhat[(size_t)i * C + c] = xh;
-      out[(size_t)i * C + c] = fmaxf(xh * bn.weight[c] + bn.bias[c], 0.f);
-    }
+    out[(size_t)i * C + c] = bn_relu(xh, bn, c);
   }
 }
 
@@ -391,14 +359,6 @@ int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_d
   if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
   if (C <= 128) hipLaunchKernelGGL(gat_forward_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
   else          hipLaunchKernelGGL(gat_forward_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
-  return (int)hipGetLastError();
-}
-
-int launch_rgt_gcn_forward(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                           BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream) {
-  if (C > 512) return (int)hipErrorInvalidValue;
-  if (C <= 128) hipLaunchKernelGGL(gcn_forward_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
-  else          hipLaunchKernelGGL(gcn_forward_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
   return (int)hipGetLastError();
 }
 

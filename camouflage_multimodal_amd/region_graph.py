@@ -22,6 +22,30 @@ from . import _lib
 from .engine import _ptr, _stream_ptr
 
 
+def _as_tensor(value, device):
+    """A tensor is used where it is; anything else is placed on ``device``."""
+    return value if isinstance(value, torch.Tensor) else torch.as_tensor(value).to(torch.device(device))
+
+
+def _image_batch(img, single_ok=False):
+    """A tensor of images as (contiguous fp32 [N, H, W, 3], whether it came as one [H, W, 3] image, which only ``single_ok``
+    allows); any other shape raises.  Where the tensor lives is the caller's check, before or after this one."""
+    single = single_ok and img.dim() == 3
+    if single:
+        img = img.unsqueeze(0)
+    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
+        raise ValueError(f"need images {'[H, W, 3] or ' if single_ok else ''}[N, H, W, 3], got {tuple(img.shape)}")
+    return img.to(torch.float32).contiguous(), single
+
+
+def _workspace(bytes_fn, *args, device):
+    """A device buffer of the size the library's ``bytes_fn(*args)`` states; 0 is its answer to arguments it does not take."""
+    need = getattr(_lib.lib(), bytes_fn)(*args)
+    if need == 0:
+        _lib.check(-1, bytes_fn)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
 def build_target_csr_device(num_nodes, edge_index, edge_weight=None):
     """The same CSR as ``build_target_csr`` built by the library (``camo_rg_build_csr``: counting sort by target, four
     small launches instead of a chain of torch index kernels); a row's edges after its leading self-loop come in no
@@ -103,26 +127,17 @@ def canny_edges(images, sigma=2.0, low_threshold=0.1, high_threshold=0.2, device
     or [N, H, W] on the device; with ``return_gradients`` also the fp32 gradients [N, 3, H, W] = gi, gj, magnitude ([3, H, W]
     for one image).  A tensor is used where it is (``device`` places other inputs) and must be on a HIP device.  PARITY UNPINNED,
     see the header."""
-    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
+    img = _as_tensor(images, device)
     _lib.require_device(img, "images")
-    img = img.to(torch.float32).contiguous()
-    single = img.dim() == 3
-    if single:
-        img = img.unsqueeze(0)
-    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
-        raise ValueError(f"need images [H, W, 3] or [N, H, W, 3], got {tuple(img.shape)}")
+    img, single = _image_batch(img, single_ok=True)
     dev = img.device
     N, H, W = img.shape[:3]
-    L = _lib.lib()
-    need = L.camo_canny_workspace_bytes(N, H, W)
-    if need == 0:
-        _lib.check(-1, "camo_canny_workspace_bytes")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace("camo_canny_workspace_bytes", N, H, W, device=dev)
     edges = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
     grad = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev) if return_gradients else None
     with torch.cuda.device(dev):
-        rc = L.camo_canny(_ptr(img), N, H, W, float(sigma), float(low_threshold), float(high_threshold), _ptr(ws), ws.numel(),
-                          _ptr(edges), _ptr(grad), _stream_ptr(dev))
+        rc = _lib.lib().camo_canny(_ptr(img), N, H, W, float(sigma), float(low_threshold), float(high_threshold), _ptr(ws),
+                                   ws.numel(), _ptr(edges), _ptr(grad), _stream_ptr(dev))
     _lib.check(rc, "camo_canny")
     edges = edges.to(torch.bool)
     if single:
@@ -185,9 +200,8 @@ def create_region_graphs_from_segments(images, segments, edges_canny=None, devic
     device -> host copy brings the offsets and the status; a label out of range raises ``ValueError``, more edges than
     ``edge_capacity`` (default 16 N label_bound) run the call once more with the capacity it reported."""
     dev = torch.device(device)
-    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(dev)
-    seg = segments if isinstance(segments, torch.Tensor) else torch.as_tensor(segments).to(dev)
-    can = None if edges_canny is None else (edges_canny if isinstance(edges_canny, torch.Tensor) else torch.as_tensor(edges_canny).to(dev))
+    img, seg = _as_tensor(images, dev), _as_tensor(segments, dev)
+    can = None if edges_canny is None else _as_tensor(edges_canny, dev)
     if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0 or seg.shape != img.shape[:3] or (can is not None and can.shape != img.shape[:3]):
         raise ValueError(f"need images [N, H, W, 3], segments [N, H, W], edges_canny [N, H, W]; got {tuple(img.shape)}, {tuple(seg.shape)}"
                          + ("" if can is None else f", {tuple(can.shape)}"))
@@ -207,10 +221,7 @@ def create_region_graphs_from_segments(images, segments, edges_canny=None, devic
     nodes = N * label_bound
     cap = int(edge_capacity) if edge_capacity else 16 * nodes             # (a planar adjacency has < 3 n pairs; 8-connectivity adds corner contacts)
     L = _lib.lib()
-    need = L.camo_rg_batch_workspace_bytes(N, H, W, label_bound)
-    if need == 0:
-        _lib.check(-1, "camo_rg_batch_workspace_bytes")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace("camo_rg_batch_workspace_bytes", N, H, W, label_bound, device=dev)
     x = torch.empty(nodes, 15, dtype=torch.float32, device=dev)
     rmap = torch.empty(N, label_bound, dtype=torch.int32, device=dev)
     batch = torch.empty(nodes, dtype=torch.int32, device=dev)
@@ -250,11 +261,8 @@ def region_graphs_from_images(images, n_segments=500, device="cuda"):
     """``region_graph_from_image`` for a batch: ``slic_segments`` on ``images`` [N, H, W, 3] float in [0, 1], then
     ``create_region_graphs_from_segments`` (one batched Canny call inside) with ``slic_label_bound`` as the label bound, so the
     only synchronisation is the sizes read-back.  Returns (RegionGraphBatch on the device, segments int32 [N, H, W] on the device)."""
-    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
-    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
-        raise ValueError(f"need images [N, H, W, 3], got {tuple(img.shape)}")
+    img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
-    img = img.to(torch.float32).contiguous()
     segments = slic_segments(img, n_segments)
     graphs, _ = create_region_graphs_from_segments(img, segments, device=img.device, label_bound=slic_label_bound(img.shape[1], img.shape[2], n_segments))
     return graphs, segments
@@ -266,26 +274,17 @@ def slic_segments(images, n_segments=500, compactness=10.0, sigma=1.0, device="c
     [H, W, 3] or [N, H, W, 3] float in [0, 1] -> int32 labels [H, W] or [N, H, W] on the device; with ``return_counts`` also int32
     [N, 2] ([2] for one image) = (largest label + 1, components of max_size pixels or more, which the device leaves whole).  A tensor
     is used where it is (``device`` places other inputs) and must be on a HIP device.  PARITY UNPINNED, see the header."""
-    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
+    img = _as_tensor(images, device)
     _lib.require_device(img, "images")
-    img = img.to(torch.float32).contiguous()
-    single = img.dim() == 3
-    if single:
-        img = img.unsqueeze(0)
-    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
-        raise ValueError(f"need images [H, W, 3] or [N, H, W, 3], got {tuple(img.shape)}")
+    img, single = _image_batch(img, single_ok=True)
     dev = img.device
     N, H, W = img.shape[:3]
-    L = _lib.lib()
-    need = L.camo_slic_workspace_bytes(N, H, W, int(n_segments))
-    if need == 0:
-        _lib.check(-1, "camo_slic_workspace_bytes")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace("camo_slic_workspace_bytes", N, H, W, int(n_segments), device=dev)
     labels = torch.empty(N, H, W, dtype=torch.int32, device=dev)
     counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = L.camo_slic(_ptr(img), N, H, W, int(n_segments), float(compactness), float(sigma), _ptr(ws), ws.numel(), _ptr(labels),
-                         _ptr(counts), _stream_ptr(dev))
+        rc = _lib.lib().camo_slic(_ptr(img), N, H, W, int(n_segments), float(compactness), float(sigma), _ptr(ws), ws.numel(),
+                                  _ptr(labels), _ptr(counts), _stream_ptr(dev))
     _lib.check(rc, "camo_slic")
     if single:
         labels, counts = labels[0], counts[0]
@@ -296,7 +295,7 @@ def region_graph_from_image(image, n_segments=500, device="cuda"):
     """``create_region_graph(image, n_segments)`` of the reference (extract_rg_embeddings.py:138) with nothing on the host:
     ``slic_segments`` then ``create_region_graph_from_segments`` (which computes the Canny edge map on the device).  ``image``
     [H, W, 3] float in [0, 1].  Returns (RegionGraphData on the device, segments int32 [H, W] on the device)."""
-    img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
+    img = _as_tensor(image, device)
     _lib.require_device(img, "image")
     if img.dim() != 3 or img.shape[2] != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
@@ -382,18 +381,32 @@ class RegionGraphGNN(nn.Module):
         self._dims = _lib.CamoRgDims(in_channels, h, heads)
         self.num_classes = num_classes
 
-    def _param_table(self):
-        t = [self.conv1.att_src, self.conv1.att_dst, self.conv1.bias, self.conv1.lin.weight,
-             self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var]
+    def _abi_order(self):
+        """The one list of what the library reads, in its order: (the embedding path's 28 tensors of include/camo_rg_gnn.h, the
+        heads' 12 of include/camo_rg_detect.h).  The gradient table of include/camo_rg_train.h is the first list without the
+        batch norms' running statistics -- buffers, not parameters -- followed by the second."""
+        bn_all = lambda bn: [bn.weight, bn.bias, bn.running_mean, bn.running_var]  # noqa: E731
+        embed = [self.conv1.att_src, self.conv1.att_dst, self.conv1.bias, self.conv1.lin.weight, *bn_all(self.bn1)]
         for conv, bn in ((self.conv2, self.bn2), (self.conv3, self.bn3), (self.conv4, self.bn4)):
-            t += [conv.bias, conv.lin.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        t += [self.fc_shared.weight, self.fc_shared.bias]
-        assert len(t) == _lib.RG_NPARAMS
+            embed += [conv.bias, conv.lin.weight, *bn_all(bn)]
+        embed += [self.fc_shared.weight, self.fc_shared.bias]
+        heads = []
+        for name in ("fc_mask", "fc_instance", "fc_edge"):
+            for layer in (getattr(self, name + "_1"), getattr(self, name + "_2")):
+                heads += [layer.weight, layer.bias]
+        assert (len(embed), len(heads)) == (_lib.RG_NPARAMS, _lib.RGD_NPARAMS)
+        return embed, heads
+
+    @staticmethod
+    def _pointer_table(t):
         for p in t:
             _lib.require_device(p, "RegionGraphGNN parameters")
         keep = [p.detach().to(torch.float32).contiguous() for p in t]
         tab = (C.c_void_p * len(keep))(*[p.data_ptr() for p in keep])
         return tab, keep
+
+    def _param_table(self):
+        return self._pointer_table(self._abi_order()[0])
 
     @torch.no_grad()
     def extract_node_embeddings(self, data=None, x=None, edge_index=None, edge_attr=None):
@@ -410,15 +423,11 @@ class RegionGraphGNN(nn.Module):
         ew = None if edge_attr is None or edge_attr.numel() == 0 else edge_attr.reshape(-1)     # :98
         rowptr, col, w = build_target_csr_device(n, edge_index, ew)
         x = x.detach().to(torch.float32).contiguous()
-        L = _lib.lib()
-        need = L.camo_rg_workspace_bytes(C.byref(self._dims), n)
-        if need == 0:
-            _lib.check(-1, "camo_rg_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _workspace("camo_rg_workspace_bytes", C.byref(self._dims), n, device=x.device)
         out = torch.empty(n, self._dims.hidden, dtype=torch.float32, device=x.device)
         tab, keep = self._param_table()
-        rc = L.camo_rg_node_embeddings(C.byref(self._dims), tab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w), n, col.shape[0],
-                                       _ptr(ws), ws.numel(), _ptr(out), _stream_ptr())
+        rc = _lib.lib().camo_rg_node_embeddings(C.byref(self._dims), tab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w), n, col.shape[0],
+                                                _ptr(ws), ws.numel(), _ptr(out), _stream_ptr())
         _lib.check(rc, "camo_rg_node_embeddings")
         return out
 
@@ -437,16 +446,7 @@ class RegionGraphGNN(nn.Module):
         return out / torch.bincount(batch.long(), minlength=g).clamp(min=1).unsqueeze(1).to(emb.dtype)
 
     def _head_table(self):
-        t = []
-        for name in ("fc_mask", "fc_instance", "fc_edge"):
-            for layer in (getattr(self, name + "_1"), getattr(self, name + "_2")):
-                t += [layer.weight, layer.bias]
-        assert len(t) == _lib.RGD_NPARAMS
-        for p in t:
-            _lib.require_device(p, "RegionGraphGNN parameters")
-        keep = [p.detach().to(torch.float32).contiguous() for p in t]
-        tab = (C.c_void_p * len(keep))(*[p.data_ptr() for p in keep])
-        return tab, keep
+        return self._pointer_table(self._abi_order()[1])
 
     @torch.no_grad()
     def node_heads(self, emb):
@@ -474,13 +474,9 @@ class RegionGraphGNN(nn.Module):
     def trainable_parameters(self):
         """The 32 parameters ``loss_and_gradients`` writes a gradient for, in the order of the gradient table of
         include/camo_rg_train.h: the embedding path's 20 (``_param_table`` without the running statistics), then the heads' 12."""
-        t = [self.conv1.att_src, self.conv1.att_dst, self.conv1.bias, self.conv1.lin.weight, self.bn1.weight, self.bn1.bias]
-        for conv, bn in ((self.conv2, self.bn2), (self.conv3, self.bn3), (self.conv4, self.bn4)):
-            t += [conv.bias, conv.lin.weight, bn.weight, bn.bias]
-        t += [self.fc_shared.weight, self.fc_shared.bias]
-        for name in ("fc_mask", "fc_instance", "fc_edge"):
-            for layer in (getattr(self, name + "_1"), getattr(self, name + "_2")):
-                t += [layer.weight, layer.bias]
+        embed, heads = self._abi_order()
+        # (the running statistics are the list's only buffers, every layer being affine; the assert holds the result to the table)
+        t = [p for p in embed if isinstance(p, nn.Parameter)] + heads
         assert len(t) == _lib.RGT_NGRADS
         return t
 
@@ -513,11 +509,7 @@ class RegionGraphGNN(nn.Module):
                 raise RuntimeError(f"{name} has {t.shape[0]} entries for {n} nodes")
             tg.append(t)
         wm, wi, we = (float(v) for v in loss_weights)
-        L = _lib.lib()
-        need = L.camo_rg_train_workspace_bytes(C.byref(self._dims), self.num_classes, n, E)
-        if need == 0:
-            _lib.check(-1, "camo_rg_train_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _workspace("camo_rg_train_workspace_bytes", C.byref(self._dims), self.num_classes, n, E, device=dev)
         params = self.trainable_parameters()
         flat = torch.empty(sum(-(-p.numel() // 64) * 64 for p in params), dtype=torch.float32, device=dev)    # (256-byte aligned pieces)
         grads, at = [], 0
@@ -529,9 +521,9 @@ class RegionGraphGNN(nn.Module):
         htab, hkeep = self._head_table()
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         with torch.cuda.device(dev):
-            rc = L.camo_rg_loss_backward(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w),
-                                         _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi, we,
-                                         _ptr(ws), ws.numel(), _ptr(loss), gtab, _stream_ptr(dev))
+            rc = _lib.lib().camo_rg_loss_backward(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w),
+                                                  _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi,
+                                                  we, _ptr(ws), ws.numel(), _ptr(loss), gtab, _stream_ptr(dev))
         _lib.check(rc, "camo_rg_loss_backward")
         return loss, grads
 

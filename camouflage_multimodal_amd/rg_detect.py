@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .engine import _ptr, _stream_ptr
-from .region_graph import create_region_graphs_from_segments, slic_label_bound, slic_segments
+from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 
 
 def _offsets_tensor(node_offsets, device):
@@ -128,11 +128,8 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     "region_map": int32 [N, label_bound]}, all on the device, plus "metrics" (``segmentation_metrics`` of the mask probability
     against ``gt_masks`` [N, H, W] uint8 / bool) when ``gt_masks`` is given.  Host synchronisations: the graph sizes read-back and,
     with ``gt_masks``, one [N, 5] copy."""
-    img = images if isinstance(images, torch.Tensor) else torch.as_tensor(images).to(torch.device(device))
-    if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
-        raise ValueError(f"need images [N, H, W, 3], got {tuple(img.shape)}")
+    img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
-    img = img.to(torch.float32).contiguous()
     N, H, W = img.shape[:3]
     gt = None
     if gt_masks is not None:
