@@ -66,8 +66,9 @@ def forward(P, x, src, dst, w, heads, taps=None):
 
 
 def cross_entropy(l, t):
-    """Mean over the nodes with t >= 0 of logsumexp(l) - l[t]; 0 (with zero gradient) when there is none."""
-    keep = t >= 0
+    """Mean over the nodes with t in [0, classes) of logsumexp(l) - l[t] (the header: any other target is ignored); 0 (with zero
+    gradient) when there is none."""
+    keep = (t >= 0) & (t < l.shape[1])
     if int(keep.sum()) == 0:
         return l.sum() * 0
     lk = l[keep]
@@ -92,9 +93,11 @@ def losses(logits, mask_t, inst_t, edge_t, weights, nc):
     return [weights[0] * lm + weights[1] * li + weights[2] * le, lm, li, le]
 
 
-def loss_and_grads(params, x, edge_index, edge_weight, mask_t, inst_t, edge_t, heads, nc, weights=(1.0, 1.0, 1.0), dtype=torch.float64):
+def loss_and_grads(params, x, edge_index, edge_weight, mask_t, inst_t, edge_t, heads, nc, weights=(1.0, 1.0, 1.0), dtype=torch.float64,
+                   probe=None):
     """params: dict name -> fp32 numpy array (embedding path + heads, running statistics included).  Returns
-    (losses float [4], {name: gradient numpy array} for the 32 trainable parameters, min over the taps of min|t| / max|t|)."""
+    (losses float [4], {name: gradient numpy array} for the 32 trainable parameters, min over the taps of min|t| / max|t|).
+    `probe`: a dict that receives "max_score" = max|s| and "top_score" = max s over the attention scores, and "max_logit" = max|logit|."""
     n = x.shape[0]
     src, dst, w = RO.with_self_loops(n, edge_index, edge_weight)
     P = {k: torch.tensor(np.asarray(v), dtype=dtype) for k, v in params.items()}
@@ -108,4 +111,7 @@ def loss_and_grads(params, x, edge_index, edge_weight, mask_t, inst_t, edge_t, h
     grads = torch.autograd.grad(ls[0], [P[k] for k in names], allow_unused=True)
     grads = {k: (np.zeros(P[k].shape) if g is None else g.numpy()) for k, g in zip(names, grads)}
     margin = min(float(t.abs().min() / t.abs().max()) for t in taps if t.numel())
+    if probe is not None:
+        probe["max_score"], probe["top_score"] = float(taps[0].abs().max()), float(taps[0].max())
+        probe["max_logit"] = float(logits.detach().abs().max())
     return [float(v.detach()) for v in ls], grads, margin

@@ -14,7 +14,11 @@ CPU REFERENCE that no pre-activation (attention scores per edge, the four batch-
 layers) lies within 1e-4 max|tensor| of 0; the seeds below were found by a search on the CPU for that condition and are fixed.  No
 element is ever left out of a comparison.
 
-The case "real" (N = 23, hidden 128, heads 4, classes 2) prints its largest e and e32; DESIGN.md 9a records them.
+The case "real" (N = 23, hidden 128, heads 4, classes 2) prints its largest e and e32, and so do "many" (1049 nodes: a thread of the
+loss kernel owns two nodes, 17 row blocks feed every column sum, the weight-gradient products contract over 1049), "saturated" (its
+logits past 20), "sharp" and "steep" (attention scores down to -128 and up to +126, the second past ln FLT_MAX) and "hub" (a row of 80 edges, repeated edges); DESIGN.md 9a records them.
+Batch norm being frozen, the graphs of a block-diagonal batch do not see each other: a batch of copies of flip-clear graphs is
+flip-clear with the same margin whatever its targets, which is how "many" gets past the sizes a seed search reaches.
 """
 import ctypes
 import functools
@@ -42,8 +46,42 @@ CASES = {
     "directed": ("directed", 12, 128, 4, 2, 110),     # no reverse edges, unequal weights, one explicit self-loop of weight 0.25
     "batch": ("batch", 64, 32, 2, 2, 11),            # 23 + 1 + 40 nodes at hidden 32, heads 2; some ignored targets
     "learn": ("grid", 23, 32, 4, 2, 15283),
+    # 16 copies of the three graphs of "batch" and 23 + 1 + 1 more: 51 graphs, 3728 edges; 1049 > 1024, 1049 % 64 = 25, 1049 % 4 = 1,
+    # 17 row blocks, a one-node graph at the very end; about a tenth of the mask and of the edge targets ignored
+    "many": ("many", 1049, 32, 2, 2, 11),
+    "saturated": ("many", 1049, 32, 2, 2, 11),        # "many" with the heads' last biases far out: |logit| > 20; edge targets of exactly 0 and 1
+    "sharp": ("grid", 23, 32, 2, 2, 4),               # attention vectors x 60: |s| up to 128, all of it below zero (max s = 7): the softmax is nearly one-hot
+    # att_src x 60, att_dst x -60: scores of both signs in a row, up to +126 > ln FLT_MAX, so a softmax without its row maximum
+    # overflows.  (With both vectors x -60 every slope of the leaky ReLU is 1 and d att_dst is 0 but for rounding: nothing to compare;
+    # the seed is the first whose margin exceeds 2e-4, whose top score exceeds 100 and whose 32 float64 gradients all reach 1e-6.)
+    "steep": ("grid", 23, 32, 2, 2, 155),
+    # row 0 and column 0 of 80 entries; 1 -> 0 and 0 -> 2 listed twice with two weights.  The reference keeps repeated edges
+    # (index_add adds both), and so do both CSR builders.
+    "hub": ("hub", 80, 16, 2, 2, 55),
 }
 BATCH_SIZES = (23, 1, 40)
+MANY_ORDER = (0, 1, 2) * 16 + (0, 1, 1)
+HUB_EXTRA = ((1, 0, 0.3), (0, 2, 0.7), (5, 6, 0.11))          # appended: two repeats of hub edges with other weights, and 5 -> 6, a one-way edge (the chords are 1-2, 4-5, 7-8, ...)
+
+
+def _saturate(p):
+    p["fc_mask_2.bias"] = np.array([25, -25], np.float32)
+    p["fc_instance_2.bias"] = np.array([-12, 12], np.float32)
+    p["fc_edge_2.bias"] = np.array([30], np.float32)
+
+
+def _sharpen(p, src=60, dst=60):
+    p["conv1.att_src"] = (p["conv1.att_src"] * np.float32(src)).astype(np.float32)
+    p["conv1.att_dst"] = (p["conv1.att_dst"] * np.float32(dst)).astype(np.float32)
+
+
+# applied to the parameters after make_params and make_head_params
+OVERRIDES = {"saturated": _saturate, "sharp": _sharpen, "steep": functools.partial(_sharpen, dst=-60)}
+
+
+def _sizes(kind):
+    """The node counts of the graphs of a block-diagonal kind, in order; None for a single graph."""
+    return {"batch": BATCH_SIZES, "many": tuple(BATCH_SIZES[k] for k in MANY_ORDER)}.get(kind)
 
 
 def _graph(kind, n, seed):
@@ -63,11 +101,18 @@ def _graph(kind, n, seed):
         w = np.exp(-rs.uniform(0, 3, size=2 * n)).astype(np.float32)
         assert not (set(zip(src, dst)) & set(zip(dst[:-1], src[:-1])))
         return x, np.array([src, dst], np.int64), np.concatenate([w, [np.float32(0.25)]]).astype(np.float32)
-    assert kind == "batch" and n == sum(BATCH_SIZES)
+    if kind == "hub":
+        pairs = [(0, j) for j in range(1, n)] + [(j, j + 1) for j in range(1, n - 1, 3)]
+        w = np.exp(-rs.uniform(0, 3, size=len(pairs))).astype(np.float32)
+        src = [a for a, b in pairs] + [b for a, b in pairs] + [a for a, b, v in HUB_EXTRA]
+        dst = [b for a, b in pairs] + [a for a, b in pairs] + [b for a, b, v in HUB_EXTRA]
+        return x, np.array([src, dst], np.int64), np.concatenate([w, w, [np.float32(v) for a, b, v in HUB_EXTRA]]).astype(np.float32)
+    assert kind in ("batch", "many") and n == sum(_sizes(kind))
+    three = [RO.make_graph(m, seed + 10 * k) for k, m in enumerate(BATCH_SIZES)]
     xs, eis, ews, off = [], [], [], 0
-    for k, m in enumerate(BATCH_SIZES):
-        gx, gei, gew = RO.make_graph(m, seed + 10 * k)
-        xs.append(gx); eis.append(gei + off); ews.append(gew); off += m
+    for k in (range(3) if kind == "batch" else MANY_ORDER):
+        gx, gei, gew = three[k]
+        xs.append(gx); eis.append(gei + off); ews.append(gew); off += gx.shape[0]
     return np.concatenate(xs), np.concatenate(eis, 1), np.concatenate(ews)
 
 
@@ -77,6 +122,8 @@ def _case(name):
     kind, n, hidden, heads, nc, seed = CASES[name]
     p = dict(RO.make_params(seed, 15, hidden, heads))
     p.update(R.make_head_params(seed + 1, hidden, nc))
+    if name in OVERRIDES:
+        OVERRIDES[name](p)
     x, ei, ew = _graph(kind, n, seed)
     rs = np.random.RandomState(seed + 1000)
     mt = rs.randint(0, nc, size=n).astype(np.int32)
@@ -85,12 +132,20 @@ def _case(name):
     if kind == "batch":
         mt[[2, 23, 30]] = -1          # (23: the one-node graph has no mask target at all)
         et[[5, 40, 41, 63]] = -1.0
-    l64, g64, margin = TR.loss_and_grads(p, x, ei, ew, mt, it, et, heads, nc)
+    if kind == "many":                # per node over the whole batch, so the copies of a graph do not have equal gradients
+        mt[rs.uniform(size=n) < 0.1] = -1
+        et[rs.uniform(size=n) < 0.1] = -1.0
+        mt[1030], et[1040] = -1, -1.0   # (and among the nodes that are a thread's second)
+    if name == "saturated":
+        et[[0, 7, 100, 1024]] = 0.0
+        et[[1, 50, 1023, 1048]] = 1.0
+    probe = {}
+    l64, g64, margin = TR.loss_and_grads(p, x, ei, ew, mt, it, et, heads, nc, probe=probe)
     l32, g32, _ = TR.loss_and_grads(p, x, ei, ew, mt, it, et, heads, nc, dtype=torch.float32)
     for a in list(p.values()) + [x, ei, ew, mt, it, et]:
         a.setflags(write=False)
     return dict(p=p, x=x, ei=ei, ew=ew, mt=mt, it=it, et=et, l64=l64, g64=g64, margin=margin, l32=l32, g32=g32,
-                hidden=hidden, heads=heads, nc=nc, n=n)
+                hidden=hidden, heads=heads, nc=nc, n=n, sizes=_sizes(kind), **probe)
 
 
 def _err(g, ref):
@@ -224,6 +279,82 @@ def test_cases_stay_clear_of_a_relu_flip(name):
     assert _case(name)["margin"] > TR.FLIP_MARGIN, (name, _case(name)["margin"])
 
 
+def test_the_edge_cases_are_where_they_claim_to_be():
+    """On the reference alone: the sizes "many" was chosen for, the logits of "saturated", the attention scores of "sharp", the long
+    rows and the repeated edges of "hub"."""
+    c = _case("many")
+    n = c["n"]
+    assert n == c["x"].shape[0] == 1049 > 1024 and n % 64 == 25 and n % 4 == 1 and -(-n // 64) == 17 and c["ei"].shape[1] == 3728
+    assert c["sizes"][-2:] == (1, 1) and len(c["sizes"]) == 51
+    for k, lo, hi in (("mt", 60, 150), ("et", 60, 150)):                                        # about a tenth ignored, in both halves of the loss kernel's stride
+        assert lo < int((c[k] < 0).sum()) < hi and (c[k][:1024] < 0).any() and (c[k][1024:] < 0).any(), k
+    assert not np.array_equal(c["mt"][:64], c["mt"][64:128])                                    # the copies differ in their targets
+    s = _case("saturated")
+    assert s["max_logit"] > 20 and s["margin"] == c["margin"]
+    assert all(np.array_equal(s[k], c[k]) for k in ("x", "ei", "ew", "mt", "it"))
+    assert int((s["et"] == 0.0).sum()) >= 4 and int((s["et"] == 1.0).sum()) >= 4
+    assert c["max_logit"] < 1 and _case("real")["max_score"] < 10                               # what every other case looks like
+    assert _case("sharp")["max_score"] > 100 > np.log(np.finfo(np.float32).max)
+    # (in "sharp" the large scores are negative, and expf(0.2 s) of those overflows nothing; "steep" has them positive)
+    assert _case("sharp")["top_score"] < 10 and _case("steep")["top_score"] > 100
+    assert min(float(np.abs(g).max()) for g in _case("steep")["g64"].values()) > 1e-6                # no gradient of it is rounding alone
+    h = _case("hub")
+    assert int((h["ei"][1] == 0).sum()) == 80 > 64 and int((h["ei"][0] == 0).sum()) == 80       # 79 neighbours and one repeat, each way
+
+
+def test_host_csr_builder_keeps_both_copies_of_a_repeated_edge():
+    from camouflage_multimodal_amd import build_target_csr
+    c = _case("hub")
+    n, ei, ew = c["n"], c["ei"], c["ew"]
+    for flip in (False, True):
+        e = ei[::-1].copy() if flip else ei
+        rowptr, col, w = [t.numpy() for t in build_target_csr(n, torch.from_numpy(e.copy()), torch.from_numpy(ew.copy()))]
+        src, dst, ws = RO.with_self_loops(n, e, ew)
+        assert col.shape[0] == ei.shape[1] + n and np.array_equal(rowptr, np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))]))
+        for i in range(n):                                                                      # the reference's edge multiset, row by row
+            assert sorted(zip(col[rowptr[i]:rowptr[i + 1]].tolist(), w[rowptr[i]:rowptr[i + 1]].tolist())) == \
+                sorted(zip(src[dst == i].tolist(), ws[dst == i].tolist())), i
+    rowptr, col, w = [t.numpy() for t in build_target_csr(n, torch.from_numpy(ei.copy()), torch.from_numpy(ew.copy()))]
+    for a, b, v in HUB_EXTRA[:2]:
+        got = sorted(w[rowptr[b]:rowptr[b + 1]][col[rowptr[b]:rowptr[b + 1]] == a].tolist())
+        first = float(ew[(ei[0] == a) & (ei[1] == b)][0])
+        assert got == sorted([first, float(np.float32(v))]) and first != np.float32(v), (a, b, got)
+
+
+OOR_NODES = (0, 3, 7, 11, 22)
+OOR_VALUES = (None, 7, -5, 2 ** 31 - 1, None)        # None: num_classes, the first value that is out of range
+
+
+@functools.lru_cache(maxsize=None)
+def _oor_case():
+    """"real" with the mask and instance targets of OOR_NODES ignored: as -1 (with both references), and as other values outside
+    [0, num_classes), int64."""
+    c = dict(_case("real"))
+    minus, other = {}, {}
+    for k in ("mt", "it"):
+        minus[k] = c[k].copy(); minus[k][list(OOR_NODES)] = -1
+        other[k] = c[k].astype(np.int64); other[k][list(OOR_NODES)] = [c["nc"] if v is None else v for v in OOR_VALUES]
+    args = (c["p"], c["x"], c["ei"], c["ew"], minus["mt"], minus["it"], c["et"], c["heads"], c["nc"])
+    c["l64"], c["g64"], c["margin"] = TR.loss_and_grads(*args)
+    c["l32"], c["g32"], _ = TR.loss_and_grads(*args, dtype=torch.float32)
+    c.update(mt=minus["mt"], it=minus["it"], other=other)
+    return c
+
+
+def test_a_target_outside_the_classes_means_minus_one_on_the_reference():
+    """include/camo_rg_train.h: any target outside [0, num_classes) is ignored.  The restatement with nc, 7, -5 and 2^31 - 1 gives
+    exactly what it gives with -1, and that is not what it gives with the nodes counted."""
+    l = torch.tensor([[0.3, -1.2], [4.0, -4.0], [-0.5, -0.5], [1.0, 2.0], [0.1, 0.2], [2.0, -1.0]], dtype=torch.float64)
+    t = torch.tensor([1, 2, 0, 7, -5, 2 ** 31 - 1])                                             # torch's own loss, which knows only -1
+    want = torch.nn.functional.cross_entropy(l, torch.tensor([1, -1, 0, -1, -1, -1]), ignore_index=-1)
+    assert abs(float(TR.cross_entropy(l, t)) - float(want)) < 1e-12
+    c, real = _oor_case(), _case("real")
+    ls, g, _ = TR.loss_and_grads(c["p"], c["x"], c["ei"], c["ew"], c["other"]["mt"], c["other"]["it"], c["et"], c["heads"], c["nc"])
+    assert ls == c["l64"] and all(np.array_equal(g[k], c["g64"][k]) for k in NAMES)
+    assert c["l64"][1] != real["l64"][1] and c["l64"][2] != real["l64"][2] and c["l64"][3] == real["l64"][3]
+    assert c["margin"] == real["margin"]                                                        # (targets do not reach the forward)
+
+
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 
 def _model(c):
@@ -237,14 +368,14 @@ def _model(c):
     return m.cuda()
 
 
-def _data(c, name=None):
+def _data(c):
     from camouflage_multimodal_amd import RegionGraphBatch, RegionGraphData
     x, ei, ea = torch.from_numpy(c["x"].copy()).cuda(), torch.from_numpy(c["ei"].copy()).cuda(), torch.from_numpy(c["ew"].copy()).cuda()[:, None]
-    if name != "batch":
+    if c["sizes"] is None:
         return RegionGraphData(x, ei, ea)
-    no = np.concatenate([[0], np.cumsum(BATCH_SIZES)])
+    no = np.concatenate([[0], np.cumsum(c["sizes"])])
     eo = [int((c["ei"][1] < b).sum()) for b in no]                 # (a graph's edges are contiguous and in graph order)
-    batch = torch.from_numpy(np.repeat(np.arange(3), BATCH_SIZES).astype(np.int32)).cuda()
+    batch = torch.from_numpy(np.repeat(np.arange(len(c["sizes"])), c["sizes"]).astype(np.int32)).cuda()
     return RegionGraphBatch(x, ei, ea, batch, [int(v) for v in no], eo)
 
 
@@ -290,23 +421,47 @@ def _hold(c, loss4, grads, tag):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["single", "isolated", "real", "tail", "wide", "directed", "batch"])
+@pytest.mark.parametrize("name", ["single", "isolated", "real", "tail", "wide", "directed", "batch", "many", "saturated", "sharp", "steep", "hub"])
 def test_gradients_match_float64_autograd(name):
     c = _case(name)
     assert c["margin"] > TR.FLIP_MARGIN                       # on the CPU reference, before the device is looked at
-    m = _model(c).train()                                     # (whatever the mode: eval-mode arithmetic)
-    out = m.loss_and_gradients(_data(c, name), *_targets(c))
+    if name == "saturated":
+        assert c["max_logit"] > 20
+    if name in ("sharp", "steep"):
+        assert c["max_score"] > 100
+    if name == "steep":
+        assert c["top_score"] > 100
+    m, d = _model(c).train(), _data(c)                        # (whatever the mode: eval-mode arithmetic)
+    out = m.loss_and_gradients(d, *_targets(c))
     assert set(out) == {"loss", "mask_loss", "instance_loss", "edge_loss"} and all(v.dim() == 0 and v.is_cuda for v in out.values())
-    _hold(c, [float(out[k]) for k in ("loss", "mask_loss", "instance_loss", "edge_loss")], _device_grads(m), name)
+    loss4 = [float(out[k]) for k in ("loss", "mask_loss", "instance_loss", "edge_loss")]
+    assert all(np.isfinite(v) for v in loss4), loss4
+    _hold(c, loss4, _device_grads(m), name)
+    if name in ("sharp", "steep"):
+        # The figure above moves with the order of a row's edges, which the device builder does not fix; at these scores
+        # ds = alpha (da - r) is a difference of nearly equal numbers.  The host-built pair has sorted rows: a second check, held to the
+        # same bound, whose figure is the same from run to run.
+        out = m.loss_and_gradients(d, *_targets(c), csr=_host_csr_pair(c, d))
+        _hold(c, [float(out[k]) for k in ("loss", "mask_loss", "instance_loss", "edge_loss")], _device_grads(m), name + " (sorted rows)")
+
+
+def _host_csr_pair(c, d):
+    from camouflage_multimodal_amd import build_target_csr
+    return (build_target_csr(c["n"], d.edge_index, d.edge_attr.reshape(-1)), build_target_csr(c["n"], d.edge_index.flip(0), d.edge_attr.reshape(-1)))
+
+
+def _csr_pair(c, d):
+    from camouflage_multimodal_amd.region_graph import build_target_csr_device
+    return (build_target_csr_device(c["n"], d.edge_index, d.edge_attr.reshape(-1)),
+            build_target_csr_device(c["n"], d.edge_index.flip(0), d.edge_attr.reshape(-1)))
 
 
 @pytest.mark.gpu
-def test_two_calls_on_the_same_csr_give_the_same_bytes():
-    from camouflage_multimodal_amd.region_graph import build_target_csr_device
-    c = _case("real")
+@pytest.mark.parametrize("name", ["real", "many"])            # "many": the loss kernel's 16-wave sum with two nodes to a thread
+def test_two_calls_on_the_same_csr_give_the_same_bytes(name):
+    c = _case(name)
     m, d, t = _model(c).eval(), _data(c), _targets(c)
-    csr = build_target_csr_device(c["n"], d.edge_index, d.edge_attr.reshape(-1))
-    rcsr = build_target_csr_device(c["n"], d.edge_index.flip(0), d.edge_attr.reshape(-1))
+    csr, rcsr = _csr_pair(c, d)
     l1, g1 = m.loss_and_gradients_csr(d.x, csr, rcsr, *t)
     l2, g2 = m.loss_and_gradients_csr(d.x, csr, rcsr, *t)
     assert np.array_equal(_bits(l1.cpu()), _bits(l2.cpu()))
@@ -315,11 +470,107 @@ def test_two_calls_on_the_same_csr_give_the_same_bytes():
 
 
 @pytest.mark.gpu
+def test_device_csr_builder_keeps_long_rows_and_repeated_edges():
+    """"hub" (a row and a column of 80 entries, two edges listed twice) through the device builder, both ways round, against the host
+    builder row by row (tests/test_rg_gnn.py does the same on make_graph graphs, whose rows have at most about 6 entries)."""
+    from camouflage_multimodal_amd import build_target_csr
+    from camouflage_multimodal_amd.region_graph import build_target_csr_device
+    c = _case("hub")
+    n = c["n"]
+    for ei in (c["ei"], c["ei"][::-1].copy()):
+        eit, ewt = torch.from_numpy(ei.copy()).cuda(), torch.from_numpy(c["ew"].copy()).cuda()
+        r0, c0, w0 = [t.cpu().numpy() for t in build_target_csr(n, eit, ewt)]
+        r1, c1, w1 = [t.cpu().numpy() for t in build_target_csr_device(n, eit, ewt)]
+        assert np.array_equal(r0, r1) and r1[1] - r1[0] == 81 and c1.shape[0] == ei.shape[1] + n
+        for i in range(n):
+            a = sorted(zip(c0[r0[i]:r0[i + 1]].tolist(), w0[r0[i]:r0[i + 1]].tolist()))
+            b = sorted(zip(c1[r1[i]:r1[i + 1]].tolist(), w1[r1[i]:r1[i + 1]].tolist()))
+            assert a == b, i
+            assert c1[r1[i]] == i                                             # the self-loop leads its row
+
+
+@pytest.mark.gpu
+def test_targets_outside_the_classes_are_ignored_like_minus_one():
+    """nc, 7, -5 and 2^31 - 1 at OOR_NODES, as int64 and once through a non-contiguous view, give the bytes that -1 gives there; and
+    those are the float64 reference's figures with -1."""
+    c = _oor_case()
+    assert c["margin"] > TR.FLIP_MARGIN
+    m, d = _model(c).eval(), _data(c)
+    csr, rcsr = _csr_pair(c, d)
+    l1, g1 = m.loss_and_gradients_csr(d.x, csr, rcsr, *_targets(c))
+    _hold(c, l1.cpu().numpy().tolist(), {k: g.cpu().numpy() for k, g in zip(NAMES, g1)}, "out of range as -1")
+    et = torch.from_numpy(c["et"].copy()).cuda()
+    wide = torch.from_numpy(np.stack([c["other"]["mt"], c["other"]["it"]], 1)).cuda()          # int64 [n, 2]: its columns have stride 2
+    assert wide.dtype == torch.int64 and not wide[:, 0].is_contiguous()
+    for mt, it in ((wide[:, 0].contiguous(), wide[:, 1].contiguous()), (wide[:, 0], wide[:, 1])):
+        l2, g2 = m.loss_and_gradients_csr(d.x, csr, rcsr, mt, it, et)
+        assert np.array_equal(_bits(l1.cpu()), _bits(l2.cpu()))
+        for k, a, b in zip(NAMES, g1, g2):
+            assert np.array_equal(_bits(a.cpu()), _bits(b.cpu())), k
+
+
+GUARD = 4096
+
+
+def _guarded(nbytes, fill):
+    """(whole, piece): `piece` is `nbytes` bytes on a 256-byte boundary in the middle of the uint8 device tensor `whole`, which is
+    filled with `fill` and has at least GUARD bytes on either side of the piece."""
+    whole = torch.full((nbytes + 2 * GUARD + 256,), fill, dtype=torch.uint8, device="cuda")
+    at = GUARD + (-(whole.data_ptr() + GUARD)) % 256
+    piece = whole[at:at + nbytes]
+    assert piece.data_ptr() % 256 == 0 and at >= GUARD and whole.numel() - at - nbytes >= GUARD
+    return whole, piece
+
+
+def _guards_intact(whole, piece, fill):
+    at = piece.data_ptr() - whole.data_ptr()
+    return bool((whole[:at] == fill).all()) and bool((whole[at + piece.numel():] == fill).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["many", "tail"])
+def test_the_library_writes_inside_its_workspace_and_its_gradient_buffers(name):
+    """camo_rg_loss_backward called directly, as the wrapper calls it, on a workspace of exactly camo_rg_train_workspace_bytes and
+    on 33 output buffers of exactly their parameters' sizes, each in the middle of a tensor of its own filled with a sentinel: no
+    byte outside a declared extent changes, every output element is written (the outputs' sentinel 0xFF is a NaN in every float),
+    and the bytes are those of loss_and_gradients_csr on the same arrays.  Nothing is overrun: a write past an extent would land in
+    memory this test owns, where it is seen."""
+    from camouflage_multimodal_amd import _lib
+    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
+    c = _case(name)
+    m, d, t = _model(c).eval(), _data(c), _targets(c)
+    csr, rcsr = _csr_pair(c, d)
+    want_loss, want = m.loss_and_gradients_csr(d.x, csr, rcsr, *t)
+    L, n, E = _lib.lib(), c["n"], csr[1].shape[0]
+    need = L.camo_rg_train_workspace_bytes(ctypes.byref(m._dims), c["nc"], n, E)
+    assert need > 0
+    ws_whole, ws = _guarded(need, 0xA5)
+    params = m.trainable_parameters()
+    outs = [_guarded(4 * k, 0xFF) for k in [p.numel() for p in params] + [4]]
+    assert all(bool(torch.isnan(piece.view(torch.float32)).all()) for _, piece in outs)
+    tab, keep = m._param_table()
+    htab, hkeep = m._head_table()
+    gtab = (ctypes.c_void_p * 32)(*[piece.data_ptr() for _, piece in outs[:32]])
+    x = d.x.contiguous()
+    assert all(a.is_contiguous() for a in (x,) + tuple(csr) + tuple(rcsr) + t) and t[0].dtype == t[1].dtype == torch.int32
+    _lib.check(L.camo_rg_loss_backward(ctypes.byref(m._dims), c["nc"], tab, htab, _ptr(x), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]),
+                                       _ptr(rcsr[0]), _ptr(rcsr[1]), _ptr(rcsr[2]), n, E, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), 1.0, 1.0, 1.0,
+                                       _ptr(ws), need, _ptr(outs[32][1]), gtab, _stream_ptr()), "camo_rg_loss_backward")
+    torch.cuda.synchronize()
+    assert _guards_intact(ws_whole, ws, 0xA5), "workspace"
+    for k, (whole, piece), ref in zip(NAMES + ["loss"], outs, list(want) + [want_loss]):
+        assert _guards_intact(whole, piece, 0xFF), k
+        got = piece.view(torch.float32)
+        assert bool(torch.isfinite(got).all()), k                             # every element written: none is the sentinel any more
+        assert np.array_equal(_bits(got.cpu()), _bits(ref.reshape(-1).cpu())), k
+
+
+@pytest.mark.gpu
 def test_batch_is_the_count_weighted_sum_of_its_graphs():
     """Term t of the batch is a mean over cnt_t nodes, cnt_gt of them in graph g: d(batch) = sum_t sum_g cnt_gt / cnt_t d(term t of g)."""
     c = _case("batch")
     assert c["margin"] > TR.FLIP_MARGIN
-    m, d = _model(c).eval(), _data(c, "batch")
+    m, d = _model(c).eval(), _data(c)
     total = {k: np.zeros(c["g64"][k].shape) for k in NAMES}
     cnt = [int((c["mt"] >= 0).sum()), int((c["it"] >= 0).sum()), int((c["et"] >= 0).sum())]
     for g, graph in enumerate(d.graphs()):
