@@ -47,6 +47,8 @@ RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
 # every symbol include/camo_rg_train.h declares
 RGT_SYMBOLS = ("camo_rg_train_workspace_bytes", "camo_rg_loss_backward")
 RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
+# every symbol include/camo_rg_targets.h declares
+RGTG_SYMBOLS = ("camo_rg_node_targets",)
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -192,6 +194,8 @@ def lib():
     L.camo_rg_train_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
     L.camo_rg_loss_backward.restype = C.c_int
     L.camo_rg_loss_backward.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, vp]
+    L.camo_rg_node_targets.restype = C.c_int
+    L.camo_rg_node_targets.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.camo_debug_gemm.restype = C.c_int
     L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.camo_debug_gemm16.restype = C.c_int

@@ -1,6 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
-// heads / painting / metrics, and the GNN's loss and gradients with batch norm frozen.  No device code here.
+// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen, and the node targets from ground-truth masks.
+// No device code here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include "slic.h"
 #include "rg_detect.h"
 #include "rg_train.h"
+#include "rg_targets.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -21,6 +23,7 @@
 #include "../../include/camo_slic.h"
 #include "../../include/camo_rg_detect.h"
 #include "../../include/camo_rg_train.h"
+#include "../../include/camo_rg_targets.h"
 
 using namespace camo_abi;
 
@@ -504,6 +507,35 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
                                                                  {0, K * C, 2 * K * C, 0, 0}, 2}, st), "attention vector sums");
   g.add(ws.dh, K * C, x, In, G[CAMO_RGT_C1_W], In, K * C, In, N, KM);
   CK(g.run(), "gat projection gradient");
+  return 0;
+}
+
+// ---- Node targets from ground-truth masks (include/camo_rg_targets.h) ------------------------------------------
+static_assert(RGTG_TILE == CAMO_RGTG_TILE && RGTG_SLOTS == CAMO_RGTG_TILE_SLOTS, "include/camo_rg_targets.h states the kernel's constants");
+
+int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, const int32_t* node_off, const uint8_t* gt_mask,
+                         const uint8_t* gt_instance, const uint8_t* gt_edge, int32_t N, int32_t H, int32_t W, int32_t label_bound,
+                         int32_t n_nodes, int32_t band_permille, int32_t edge_min_pixels, int32_t* counts, int32_t* mask_t,
+                         int32_t* inst_t, float* edge_t, void* stream) {
+  if (N < 1) return fail(CAMO_E_ARG, "N must be >= 1");
+  if (H < 1) return fail(CAMO_E_ARG, "H must be >= 1");
+  if (W < 1) return fail(CAMO_E_ARG, "W must be >= 1");
+  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, CAMO_RG_MAX_LABELS]");
+  if (n_nodes < 1) return fail(CAMO_E_ARG, "n_nodes must be >= 1");
+  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGB_MAX_PIXELS");
+  if (band_permille < 0 || band_permille >= 500) return fail(CAMO_E_ARG, "band_permille must be in [0, 500)");
+  if (edge_min_pixels < 1) return fail(CAMO_E_ARG, "edge_min_pixels must be >= 1");
+  if (!segments) return fail(CAMO_E_ARG, "segments is null");
+  if (!region_map) return fail(CAMO_E_ARG, "region_map is null");
+  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
+  if (!gt_mask) return fail(CAMO_E_ARG, "gt_mask is null");
+  if (!counts) return fail(CAMO_E_ARG, "counts is null");
+  if (!mask_t) return fail(CAMO_E_ARG, "mask_t is null");
+  if (!inst_t) return fail(CAMO_E_ARG, "inst_t is null");
+  if (!edge_t) return fail(CAMO_E_ARG, "edge_t is null");
+  CK(launch_rg_node_targets(segments, region_map, node_off, gt_mask, gt_instance, gt_edge, N, H, W, label_bound, n_nodes, band_permille,
+                            edge_min_pixels, counts, mask_t, inst_t, edge_t, static_cast<hipStream_t>(stream)), "rg node targets");
   return 0;
 }
 }  // extern "C"

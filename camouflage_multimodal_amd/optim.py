@@ -26,7 +26,49 @@ def cosine_warm_restarts_lr(base_lr, epoch, T_0=10, T_mult=2, eta_min=0.0):
     return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * t / Ti)) / 2
 
 
-class FusedClipAdamW:
+class AdamWStateMixin:
+    """What a clip + AdamW optimizer over flat buffers shares whatever model it steps: the epoch's learning rate, the last gradient
+    norm and the checkpoint interchange with ``torch.optim.AdamW``.  The class that uses it has ``lr``, ``base_lr``, ``betas``,
+    ``eps``, ``weight_decay``, ``step_count``, ``_state()`` -> (m, v, sumsq) flat buffers and ``_layout()`` -> one
+    (parameter, name, offset, numel, shape) per parameter in ``param_groups`` order."""
+
+    def set_epoch(self, epoch, T_0=10, T_mult=2):
+        self.lr = cosine_warm_restarts_lr(self.base_lr, epoch, T_0, T_mult)
+        return self.lr
+
+    def grad_norm(self):
+        """Pre-clip global gradient norm of the last step (device tensor)."""
+        return self._state()[2][:1].sqrt()
+
+    # ---- checkpoint interchange with torch.optim.AdamW (train_multimodal.py:467) -------------------
+    def state_dict(self):
+        m, v, _ = self._state()
+        layout = self._layout()
+        state = {}
+        for idx, (_, name, o, n, shape) in enumerate(layout):
+            state[idx] = {"step": torch.tensor(float(self.step_count)),
+                          "exp_avg": m[o:o + n].view(shape).clone(), "exp_avg_sq": v[o:o + n].view(shape).clone()}
+        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False,
+                     maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                     decoupled_weight_decay=True, initial_lr=self.base_lr, params=list(range(len(layout))))
+        return {"state": state if self.step_count else {}, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        m, v, _ = self._state()
+        grp = sd["param_groups"][0]
+        self.lr = float(grp["lr"]); self.base_lr = float(grp.get("initial_lr", grp["lr"]))
+        self.betas = tuple(grp["betas"]); self.eps = float(grp["eps"]); self.weight_decay = float(grp["weight_decay"])
+        steps = 0
+        for idx, (_, name, o, n, shape) in enumerate(self._layout()):
+            st = sd["state"].get(idx)
+            if st is None:
+                continue
+            m[o:o + n].copy_(st["exp_avg"].reshape(-1)); v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+            steps = int(float(st["step"]))
+        self.step_count = steps
+
+
+class FusedClipAdamW(AdamWStateMixin):
     def __init__(self, model, lr=5e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0):
         self.engine = model._engine
         self.base_lr = self.lr = float(lr)
@@ -42,12 +84,11 @@ class FusedClipAdamW:
             self._sumsq = torch.zeros(_lib.SUMSQ_FLOATS, dtype=torch.float32, device=p.device)
         return self._m, self._v, self._sumsq
 
+    def _layout(self):
+        return self.engine._layout
+
     def zero_grad(self):
         self.engine.ensure_flat_grads().zero_()
-
-    def set_epoch(self, epoch, T_0=10, T_mult=2):
-        self.lr = cosine_warm_restarts_lr(self.base_lr, epoch, T_0, T_mult)
-        return self.lr
 
     def step(self, allreduce=None, zero_grads=False, shadows=False):
         """``allreduce``: optional callable applied to the flat gradient buffer before the norm
@@ -80,33 +121,3 @@ class FusedClipAdamW:
             _lib.check(L.camo_clip_adamw(_ptr(eng.flat_params), _ptr(g), _ptr(m), _ptr(v), g.numel(), _ptr(ss),
                                          self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps,
                                          self.weight_decay, self.step_count, int(bool(zero_grads)), st), "camo_clip_adamw")
-
-    def grad_norm(self):
-        """Pre-clip global gradient norm of the last step (device tensor)."""
-        return self._state()[2][:1].sqrt()
-
-    # ---- checkpoint interchange with torch.optim.AdamW (train_multimodal.py:467) -------------------
-    def state_dict(self):
-        m, v, _ = self._state()
-        state = {}
-        for idx, (_, name, o, n, shape) in enumerate(self.engine._layout):
-            state[idx] = {"step": torch.tensor(float(self.step_count)),
-                          "exp_avg": m[o:o + n].view(shape).clone(), "exp_avg_sq": v[o:o + n].view(shape).clone()}
-        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False,
-                     maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
-                     decoupled_weight_decay=True, initial_lr=self.base_lr, params=list(range(len(self.engine._layout))))
-        return {"state": state if self.step_count else {}, "param_groups": [group]}
-
-    def load_state_dict(self, sd):
-        m, v, _ = self._state()
-        grp = sd["param_groups"][0]
-        self.lr = float(grp["lr"]); self.base_lr = float(grp.get("initial_lr", grp["lr"]))
-        self.betas = tuple(grp["betas"]); self.eps = float(grp["eps"]); self.weight_decay = float(grp["weight_decay"])
-        steps = 0
-        for idx, (_, name, o, n, shape) in enumerate(self.engine._layout):
-            st = sd["state"].get(idx)
-            if st is None:
-                continue
-            m[o:o + n].copy_(st["exp_avg"].reshape(-1)); v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-            steps = int(float(st["step"]))
-        self.step_count = steps

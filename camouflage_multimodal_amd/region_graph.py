@@ -481,12 +481,14 @@ class RegionGraphGNN(nn.Module):
         return t
 
     @torch.no_grad()
-    def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.)):
+    def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None):
         """``loss_and_gradients`` on CSR arrays the caller built: ``csr`` = (rowptr, col, w) by target, ``reversed_csr`` the same
         for the graph with every edge turned round (both from ``build_target_csr_device``; they must hold the same edges).  One
         library call (``camo_rg_loss_backward``, include/camo_rg_train.h).  Returns (loss fp32 [4] = total, mask, instance, edge;
         list of 32 gradient tensors in ``trainable_parameters`` order, views of one buffer).  The result is a function of the
-        arrays alone: two calls on the same arrays give the same bytes."""
+        arrays alone: two calls on the same arrays give the same bytes.  ``out``: a contiguous fp32 device buffer of exactly the
+        flat layout's size (every piece rounded up to 64 floats) that receives the gradients instead of a new one; its padding is
+        not written."""
         _lib.require_device(x, "x")
         if x.dim() != 2 or x.shape[1] != self._dims.in_channels or x.shape[0] < 1:
             raise RuntimeError(f"x of shape {tuple(x.shape)} does not match in_channels {self._dims.in_channels}")
@@ -511,7 +513,14 @@ class RegionGraphGNN(nn.Module):
         wm, wi, we = (float(v) for v in loss_weights)
         ws = _workspace("camo_rg_train_workspace_bytes", C.byref(self._dims), self.num_classes, n, E, device=dev)
         params = self.trainable_parameters()
-        flat = torch.empty(sum(-(-p.numel() // 64) * 64 for p in params), dtype=torch.float32, device=dev)    # (256-byte aligned pieces)
+        total = sum(-(-p.numel() // 64) * 64 for p in params)                                                # (256-byte aligned pieces)
+        if out is None:
+            flat = torch.empty(total, dtype=torch.float32, device=dev)
+        else:
+            _lib.require_device(out, "out")
+            if out.dtype != torch.float32 or out.dim() != 1 or out.numel() != total or not out.is_contiguous() or out.device != dev:
+                raise RuntimeError(f"out must be a contiguous fp32 buffer of {total} floats on {dev}")
+            flat = out
         grads, at = [], 0
         for p in params:
             grads.append(flat[at:at + p.numel()].view(p.shape))

@@ -1,0 +1,207 @@
+"""Fine-tuning the region-graph detector from images and ground-truth masks on MI355X (include/camo_rg_targets.h).
+
+What models/region_graph/train.py does around its forward and backward, with the batch-norm statistics frozen and dropout off (the
+path of ``RegionGraphGNN.loss_and_gradients``): ``node_targets_from_masks`` turns ground-truth masks into one target per superpixel
+for the three node heads (``camo_rg_node_targets``, three launches), ``prepare_finetune_batch`` builds everything a step reads from
+a batch of images once, and ``RegionGraphFineTuner`` holds the 32 trainable parameters in one flat buffer and takes a step as one
+``camo_rg_loss_backward`` plus the two launches of the clip + AdamW pair of optim.py.  PARITY UNPINNED: the reference's CODDataset
+cannot be read here, so the header's text defines the targets.  There is no CPU path: tensors that are not on a HIP device raise.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from .engine import _on, _ptr, _stream_ptr
+from .optim import AdamWStateMixin
+from .region_graph import (_as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments, slic_label_bound,
+                           slic_segments)
+from .rg_detect import _offsets_tensor, detect_camouflage_batch
+
+PIECE = 64      # floats: every parameter starts on a 256-byte boundary of the flat buffers, as in loss_and_gradients_csr
+
+
+def flat_layout(shapes):
+    """The flat layout of tensors of ``shapes`` in order: ([(offset, numel), ...], total floats).  Every piece is rounded up to 64
+    floats -- the layout ``RegionGraphGNN.loss_and_gradients_csr`` gives its gradients."""
+    pieces, at = [], 0
+    for shape in shapes:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        pieces.append((at, n))
+        at += -(-n // PIECE) * PIECE
+    return pieces, at
+
+
+def _mask_bytes(mask, name, shape, dev):
+    """A uint8 [N, H, W] device mask (positive above 127) from uint8 or bool, as ``segmentation_counts`` takes them."""
+    if mask is None:
+        return None
+    m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+    _lib.require_device(m, name)
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"need {name} [N, H, W] = {tuple(shape)}, got {tuple(m.shape)}")
+    m = m.to(device=dev)
+    return (m.to(torch.uint8) * 255 if m.dtype == torch.bool else m.to(torch.uint8)).contiguous()
+
+
+@torch.no_grad()
+def node_targets_from_masks(segments, region_map, node_offsets, gt_masks, instance_masks=None, edge_masks=None, band_permille=0,
+                            edge_min_pixels=1, n_nodes=None):
+    """One target per node of a block-diagonal batch of region graphs from ground-truth masks (``camo_rg_node_targets``,
+    include/camo_rg_targets.h): ``segments`` [N, H, W] integer labels, ``region_map`` [N, label_bound] and ``node_offsets`` (N + 1
+    integers, list or tensor) as ``create_region_graphs_from_segments`` returns them (what ``paint_regions`` takes; one image
+    [H, W] with ``region_map`` [labels] is N = 1); ``gt_masks`` and the optional ``instance_masks`` / ``edge_masks`` [N, H, W] uint8
+    (positive above 127) or bool.  Returns (mask_target int32 [n], instance_target int32 [n], edge_target fp32 [n], counts int32
+    [n, 4] = pixels, mask-positive, instance-positive and edge pixels of every node) on the device, ready for
+    ``loss_and_gradients``: a node is 1 when more than ``500 + band_permille`` thousandths of its pixels are positive, 0 at
+    ``500 - band_permille`` or fewer, -1 (ignored) between; its edge target is 1 with ``edge_min_pixels`` edge pixels or more.
+    Without ``instance_masks`` the mask stands in; without ``edge_masks`` the mask's boundary does.  Integer sums: two calls give
+    the same bytes.  ``n`` is the last of ``node_offsets`` (a device tensor is read back for it unless ``n_nodes`` is given)."""
+    _lib.require_device(segments, "segments")
+    _lib.require_device(region_map, "region_map")
+    dev = segments.device
+    if segments.dim() == 2:
+        segments, region_map = segments.unsqueeze(0), region_map.reshape(1, -1)
+    if segments.dim() != 3 or region_map.dim() != 2 or region_map.shape[0] != segments.shape[0] or segments.numel() == 0 \
+            or region_map.numel() == 0:
+        raise ValueError(f"need segments [N, H, W] and region_map [N, label_bound]; got {tuple(segments.shape)}, {tuple(region_map.shape)}")
+    N, H, W = segments.shape
+    if n_nodes is None:
+        n_nodes = int(node_offsets[-1])
+    off = _offsets_tensor(node_offsets, dev)
+    if off.numel() != N + 1:
+        raise ValueError(f"node_offsets must hold N + 1 = {N + 1} integers, got {off.numel()}")
+    gt = _mask_bytes(gt_masks, "gt_masks", (N, H, W), dev)
+    if gt is None:
+        raise ValueError("gt_masks is required")
+    inst = _mask_bytes(instance_masks, "instance_masks", (N, H, W), dev)
+    edge = _mask_bytes(edge_masks, "edge_masks", (N, H, W), dev)
+    seg = segments.to(dtype=torch.int32).contiguous()
+    rmap = region_map.to(device=dev, dtype=torch.int32).contiguous()
+    n = int(n_nodes)
+    counts = torch.empty(max(n, 0), 4, dtype=torch.int32, device=dev)
+    mask_t = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    inst_t = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    edge_t = torch.empty(max(n, 0), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().camo_rg_node_targets(_ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), _ptr(inst), _ptr(edge), N, H, W, rmap.shape[1], n,
+                                             int(band_permille), int(edge_min_pixels), _ptr(counts), _ptr(mask_t), _ptr(inst_t),
+                                             _ptr(edge_t), _stream_ptr(dev))
+    _lib.check(rc, "camo_rg_node_targets")
+    return mask_t, inst_t, edge_t, counts
+
+
+class FineTuneBatch:
+    """What a fine-tuning step reads, built once and kept on the device: ``graphs`` (RegionGraphBatch), ``segments`` int32
+    [N, H, W], ``region_map`` int32 [N, label_bound], ``mask_target`` / ``instance_target`` / ``edge_target`` / ``counts`` of
+    ``node_targets_from_masks``, and ``csr`` / ``reversed_csr`` (by target, and of the graph with every edge turned round)."""
+
+    def __init__(self, graphs, segments, region_map, mask_target, instance_target, edge_target, counts, csr, reversed_csr):
+        self.graphs, self.segments, self.region_map = graphs, segments, region_map
+        self.mask_target, self.instance_target, self.edge_target, self.counts = mask_target, instance_target, edge_target, counts
+        self.csr, self.reversed_csr = csr, reversed_csr
+
+
+@torch.no_grad()
+def prepare_finetune_batch(images, gt_masks, instance_masks=None, edge_masks=None, n_segments=500, band_permille=0, device="cuda",
+                           edge_min_pixels=1):
+    """``images`` [N, H, W, 3] float in [0, 1] and their ground-truth masks [N, H, W] -> ``FineTuneBatch``: superpixels, edge maps
+    and region graphs on the device (region_graph.py), the node targets, and both CSRs built once with ``build_target_csr_device``,
+    so that a resident dataset is trained on epoch after epoch through the ``csr=`` path of ``loss_and_gradients`` with nothing
+    rebuilt.  The only host synchronisation is the sizes read-back of ``create_region_graphs_from_segments``."""
+    img, _ = _image_batch(_as_tensor(images, device))
+    _lib.require_device(img, "images")
+    N, H, W = img.shape[:3]
+    segments = slic_segments(img, n_segments)
+    graphs, region_map = create_region_graphs_from_segments(img, segments, device=img.device, label_bound=slic_label_bound(H, W, n_segments))
+    gt = _as_tensor(gt_masks, img.device)
+    inst = None if instance_masks is None else _as_tensor(instance_masks, img.device)
+    edge = None if edge_masks is None else _as_tensor(edge_masks, img.device)
+    mask_t, inst_t, edge_t, counts = node_targets_from_masks(segments, region_map, graphs.node_offsets, gt, inst, edge, band_permille,
+                                                             edge_min_pixels)
+    n, ew = graphs.x.shape[0], graphs.edge_attr.reshape(-1)
+    csr = build_target_csr_device(n, graphs.edge_index, ew)
+    rcsr = build_target_csr_device(n, graphs.edge_index.flip(0), ew)
+    return FineTuneBatch(graphs, segments, region_map, mask_t, inst_t, edge_t, counts, csr, rcsr)
+
+
+class RegionGraphFineTuner(AdamWStateMixin):
+    """Clip + AdamW fine-tuning of a ``RegionGraphGNN`` with its batch-norm statistics frozen.  At construction the model's 32
+    ``trainable_parameters()`` become views of ONE flat fp32 buffer (``flat_layout``: pieces rounded up to 64 floats, padding zero),
+    so ``state_dict``, ``load_state_dict`` and every method of the model keep working; the flat gradient, first- and second-moment
+    buffers are allocated once.  ``step`` is ``camo_rg_loss_backward`` into the flat gradient buffer, then ``camo_grad_sumsq`` and
+    ``camo_clip_adamw`` over the flat buffers: ``torch.nn.utils.clip_grad_norm_(max_norm)`` followed by ``torch.optim.AdamW`` on the
+    32 parameters, with no host synchronisation.  The running statistics are buffers of the model and are never written."""
+
+    def __init__(self, rg_model, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, loss_weights=(1.0, 1.0, 1.0)):
+        self.model = rg_model
+        self.base_lr = self.lr = float(lr)
+        self.weight_decay, self.betas, self.eps, self.max_norm = float(weight_decay), tuple(betas), float(eps), float(max_norm)
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self.step_count = 0
+        params = rg_model.trainable_parameters()
+        names = {id(p): k for k, p in rg_model.named_parameters()}
+        dev = params[0].device
+        if any(p.device != dev or p.dtype != torch.float32 for p in params):
+            raise ValueError("RegionGraphFineTuner needs every trainable parameter in fp32 on one device")
+        pieces, total = flat_layout([p.shape for p in params])
+        self.flat_params = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._entries = []                                          # (parameter, name, offset, numel, shape): the layout of engine.py
+        with torch.no_grad():
+            for p, (o, n) in zip(params, pieces):
+                view = self.flat_params[o:o + n].view(p.shape)
+                view.copy_(p.data)
+                p.data = view
+                self._entries.append((p, names[id(p)], o, n, tuple(p.shape)))
+        self.flat_grads = torch.zeros_like(self.flat_params)
+        self.grads = [self.flat_grads[o:o + n].view(shape) for _, _, o, n, shape in self._entries]
+        self._m = torch.zeros_like(self.flat_params)
+        self._v = torch.zeros_like(self.flat_params)
+        self._sumsq = torch.zeros(_lib.SUMSQ_FLOATS, dtype=torch.float32, device=dev)
+
+    def _layout(self):
+        return self._entries
+
+    def _state(self):
+        return self._m, self._v, self._sumsq
+
+    def _check_resident(self):
+        base, dev = self.flat_params.data_ptr(), self.flat_params.device
+        for p, name, o, n, shape in self._entries:
+            if p.device != dev or p.data_ptr() != base + 4 * o or tuple(p.shape) != shape or not p.is_contiguous():
+                raise _lib.CamoError(f"parameter {name} no longer lives in the fine-tuner's flat buffer (the model was moved or its "
+                                     "parameters were replaced after the tuner was built): build a new RegionGraphFineTuner for the model "
+                                     "as it is now; this one would train a copy")
+
+    @torch.no_grad()
+    def step(self, batch):
+        """One clip + AdamW step on a ``FineTuneBatch``.  Returns 0-d device tensors ``loss``, ``mask_loss``, ``instance_loss``,
+        ``edge_loss`` of the parameters BEFORE the update.  No host synchronisation; the gradient buffer is the tuner's own."""
+        _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        self._check_resident()
+        loss, _ = self.model.loss_and_gradients_csr(batch.graphs.x, batch.csr, batch.reversed_csr, batch.mask_target, batch.instance_target,
+                                                    batch.edge_target, self.loss_weights, out=self.flat_grads)
+        p, g, (m, v, ss) = self.flat_params, self.flat_grads, self._state()
+        self.step_count += 1
+        L = _lib.lib()
+        with _on(p.device):
+            st = _stream_ptr(p.device)
+            _lib.check(L.camo_grad_sumsq(_ptr(g), g.numel(), _ptr(ss), st), "camo_grad_sumsq")
+            _lib.check(L.camo_clip_adamw(_ptr(p), _ptr(g), _ptr(m), _ptr(v), g.numel(), _ptr(ss), self.max_norm, self.lr, self.betas[0],
+                                         self.betas[1], self.eps, self.weight_decay, self.step_count, 0, st), "camo_clip_adamw")
+        return {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
+
+    def step_from_images(self, images, gt_masks, instance_masks=None, edge_masks=None, n_segments=500, band_permille=0, edge_min_pixels=1):
+        """``prepare_finetune_batch`` on the tuner's device, then ``step``."""
+        _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        return self.step(prepare_finetune_batch(images, gt_masks, instance_masks, edge_masks, n_segments, band_permille,
+                                                self.flat_params.device, edge_min_pixels))
+
+    def evaluate(self, images, gt_masks, n_segments=500, threshold=0.5):
+        """``detect_camouflage_batch``'s metrics of the model as it is now: a list of ``segmentation_metrics`` dicts, one per image."""
+        _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        return detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device)["metrics"]
