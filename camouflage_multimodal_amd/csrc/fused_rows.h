@@ -125,7 +125,16 @@ struct Bwd2Args {
   int B, Nk, rg_tiles_max, rows_rg; float qscale; DropCfg drop; unsigned long long* stamps;
   int param_space;                             // 1: no dR / dG products (bwd2p_kernel): the caller takes the projections' weight gradients in parameter space
   int split_finish;                            // (param_space only) 1: no arrival protocol -- the KG rows' dQ2 sums become bf16 in a second, B-block launch
+  int kg_defer;                                // (row space only) 1: no arrival protocol and no finish -- dGpart = dU2 + [dK | dV] . [Wk1; Wv1] goes, as
+                                               // bf16 rows of 256 (pad rows cleared), into the dGpart scratch; dG16 and columns 0..255 of dQKVkg16 stay
+                                               // unwritten: the caller's weight-gradient launch takes what dQ2 adds from the fp32 sums in dQ2acc and
+                                               // writes both (gemm16.h, GF_A_F32 / GF_KGQ).  -1: by size -- the launcher decides
+                                               // (B Nk <= FUSED_BWD2_DEFER_MAX_TK) and leaves 0 or 1 here for the caller
 };
+// A GF_KGQ block of the weight-gradient launch walks all B Nk rows in 64-row steps, then one more step and an ordinary block's atomics; up to
+// this many rows that is half the 16 steps of the launch's long blocks.  Measured with row space forced: B Nk =
+// 208, 312, 416 each -3 % of the step; nothing larger was measured, and by size row space ends near B Nk = 300.
+#define FUSED_BWD2_DEFER_MAX_TK 512
 int launch_fused_bwd2(Bwd2Args& a, int variant, hipStream_t stream);
 // param_space calls of large batches: the RG rows on 64-row blocks, wave = head, no barriers (bwd_wide2.hip); same outputs
 int launch_wide2_bwd2(Bwd2Args& a, hipStream_t stream);

@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   // weight stream ran.  vid = the block's id in the splits-first numbering.
   const int vid = (int)blockIdx.x < a.lead_tiles ? nkg + (int)blockIdx.x : ((int)blockIdx.x < a.lead_tiles + nkg ? (int)blockIdx.x - a.lead_tiles : (int)blockIdx.x);
   const bool kg = vid < nkg;
-  const int rot = ROT ? (int)(blockIdx.x >> 3) : 0;
+  int rot = ROT ? (int)(blockIdx.x >> 3) : 0;
   using L = BackL<OCC>;
   char* bufO = smem + L::O; char* bufY = smem + L::Y;
   float* red = reinterpret_cast<float*>(smem + L::RED);
@@ -467,6 +467,9 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   if (kg) {
     b = vid / a.max_splits;
     const int sp = vid - b * a.max_splits;
+    // the sample's chain runs in whichever split block arrives last: its k order must follow the sample, not that block's id, or the fp32
+    // sums of the out-projection and the FFN -- and with them the odd bf16 rounding of Y2 / XH2 -- change from call to call
+    if (ROT) rot = b;
     const int nsplit = (a.off[b + 1] - a.off[b] + SPLIT_ROWS - 1) / SPLIT_ROWS;
     if (sp >= nsplit) return;
     attn_kg_split(a, smem, b, sp, w, lane);
@@ -1004,7 +1007,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
 // max / sum), i.e. dK2, dV2 per row and the tile's contribution to the sample's dQ2 (fp32 atomics); then the input
 // gradient of the three in-projections in ONE product, dR = dU + [dQ | dK2 | dV2] . [Wq1; Wk2; Wv2]  (K = 768).
 // The last tile of a sample to finish (arrival counter, as in the forward) runs the same product for the sample's KG rows:
-// dG = dU2 + [dQ2 | dK | dV] . [Wq2; Wk1; Wv1].
+// dG = dU2 + [dQ2 | dK | dV] . [Wq2; Wk1; Wv1].  Bwd2Args::kg_defer (small batches): no arrival, no finish -- the early blocks' part of
+// dG is the projection's weight-gradient operand and the weight-gradient launch adds what dQ2 contributes (gemm16.h, GF_KGQ).
 constexpr int X_Q2S = 0, X_DO2S = 16 * PK, X_TABS = 2 * 16 * PK, X_BUFT = X_TABS + 1536, X_IMGS = X_BUFT + 32 * PQ,
               X_RED = X_IMGS + 8192, X_LDS = X_RED + 64;                                        // 76352 bytes
 
@@ -1041,7 +1045,26 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     f32x16 acc[2] = {zero16(), zero16()};
     se.run(bufT + l31 * PQ + 512 + 16 * h, acc);
     copy_out<6>(bufT, PQ, 512, a.dQKVkg16 + 256, 768, krow0, Nk);
-    if (l31 < Nk) {
+    if (a.kg_defer) {
+      // no finish in this launch: dGpart, rounded, IS the projection's weight-gradient operand (in the dGpart scratch, as bf16 rows of 256);
+      // what dQ2 . Wq2 adds to that gradient is taken from the finished dQ2 sums by the weight-gradient launch
+      us16* const dGp16 = reinterpret_cast<us16*>(a.dGpart);
+      if (l31 < Nk) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
+            const u32x2 uv = *reinterpret_cast<const u32x2*>(a.dU2_16 + (krow0 + l31) * 256 + c0);
+            *reinterpret_cast<u32x2*>(dGp16 + (krow0 + l31) * 256 + c0) =
+                u32x2{pack2(acc[t][4 * g] + bf_lo(uv.x), acc[t][4 * g + 1] + bf_hi(uv.x)), pack2(acc[t][4 * g + 2] + bf_lo(uv.y), acc[t][4 * g + 3] + bf_hi(uv.y))};
+          }
+      }
+      if (b == a.B - 1) {                                    // the operand's pad rows (the contraction runs over whole 128-row groups)
+        const size_t tk = (size_t)a.B * Nk, n16 = (((tk + 127) & ~size_t(127)) - tk) * 32;
+        for (size_t c = tid; c < n16; c += 256) *(reinterpret_cast<u32x4*>(dGp16 + tk * 256) + c) = u32x4{0u, 0u, 0u, 0u};
+      }
+    } else if (l31 < Nk) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1178,6 +1201,11 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     }
   }
   stamp(a.stamps, 2);
+  }
+  if (a.kg_defer) {                                          // (block-uniform) the dQ2 sums are read behind the kernel boundary
+    if (early) { stamp(a.stamps, 1); stamp(a.stamps, 2); }
+    stamp(a.stamps, 3);
+    return;
   }
   // ---- arrival: the last block of the sample (its RG tiles and its early block) finishes the KG rows' product.  What it reads from the other
   // tiles are the dQ2 sums, fp32 atomics that execute at the memory side (no L2 line to write back), so a tile only has
@@ -1542,8 +1570,11 @@ int launch_fused_bwd2(Bwd2Args& a, int variant, hipStream_t stream) {
   if (!al16(a.dQKV16) || !al16(a.dQKVkg16) || !al16(a.WcRgT) || !al16(a.WcKgT) || !al16(a.dQ2acc) || !al16(a.dKV)) return (int)hipErrorInvalidValue;
   // executed FLOPs per row: dR / dG (768 -> 256) unless the caller takes those gradients in parameter space; RG rows: the KG->RG
   // attention backward (5 products of Nk x 256)
-  const double rows = (double)a.rows_rg + (double)a.B * a.Nk;
-  const int prof = gemm_prof_open(stream, (a.param_space ? 0.0 : 2.0 * rows * 768.0 * 256.0) + 10.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BWD2);
+  // (kg_defer: the KG rows' product stops at its [dK | dV] columns, K = 512)
+  if (a.param_space) a.kg_defer = 0;
+  else if (a.kg_defer < 0) a.kg_defer = a.B * a.Nk <= FUSED_BWD2_DEFER_MAX_TK ? 1 : 0;
+  const double dr = 2.0 * ((double)a.rows_rg * 768.0 + (double)a.B * a.Nk * (a.kg_defer ? 512.0 : 768.0)) * 256.0;
+  const int prof = gemm_prof_open(stream, (a.param_space ? 0.0 : dr) + 10.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BWD2);
   if (!a.param_space) a.split_finish = 0;
   if (!a.param_space) launch_lds<bwd2_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
   else                launch_lds<bwd2p_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);

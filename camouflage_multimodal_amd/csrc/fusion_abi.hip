@@ -1008,11 +1008,24 @@ int backward_nodes17(Call& c, const Batch& x) {
   const bool param_space = pl.param_space != 0;
   a2.param_space = param_space ? 1 : 0;
   a2.split_finish = pl.bwd2 != CAMO_BWD2_ROWS32 ? 1 : 0;
+  // row space: the KG rows' dQ2 chain finishes in the weight-gradient launch when the launcher finds B Nk small enough (it leaves its
+  // choice in kg_defer).  Developer A/B: exp = 32 keeps the arrival protocol in bwd2, exp = 64 defers at any size.  A forced tn_big keeps
+  // it too: the 128 x 256 weight-gradient kernel takes bf16 operands only, and forcing it is an A/B of the two kernels on one operand set
+  a2.kg_defer = x.opt->exp == 32 ? 0 : (x.opt->exp == 64 ? 1 : (x.opt->tn_big > 0 ? 0 : -1));
   if (pl.bwd2 == CAMO_BWD2_64) CK(launch_wide2_bwd2(a2, st), "fused backward, second half (64-row blocks)");
   else CK(launch_fused_bwd2(a2, x.opt->fused_variant, st), "fused backward, second half");
   // every node-level weight gradient: dW += dy^T . x over the rows of a stream (bf16 operands the fused kernels wrote)
   if (!param_space) {
     GB16 g(drop, *x.opt, st);
+    const bool kgq = a2.kg_defer == 1;
+    if (kgq) {
+      // first in the launch: dW_kgproj += Wq2^T (dQ2^T KG), db_kgproj += Wq2^T colsum(dQ2) -- the part of dG^T KG that bwd2 left out of its operand (dGpart)
+      Gemm16Prob& p = g.tn(nullptr, H, f.KG16, D, Gr[CAMO_P_KG_PROJ_W], D, Gr[CAMO_P_KG_PROJ_B], H, D, TK);
+      p.A = reinterpret_cast<const us*>(w.dQ2acc); p.flags |= GF_A_F32 | GF_KGQ;
+      p.kgq_wT = f.WcKgT; p.kgq_w = P[CAMO_P_A2_IN_W]; p.ldg = H;
+      // (the workspace's record: dG16 and the dQ2 columns of dQKVkg16, which nothing in this launch reads)
+      p.C16 = f.dG16; p.ldc16 = H; p.kgq_part16 = reinterpret_cast<const us*>(f.dGpart); p.kgq_a16 = f.dQKVkg16; p.kgq_lda16 = 3 * H;
+    }
     g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
     g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
     g.tn(f.dQKV16, 3 * H, f.R16, H, Gr[CAMO_P_A1_IN_W], H, Gr[CAMO_P_A1_IN_B], H, H, T);
@@ -1020,9 +1033,14 @@ int backward_nodes17(Call& c, const Batch& x) {
     g.tn(f.dR16, H, f.X16, D, Gr[CAMO_P_RG_PROJ_W], D, Gr[CAMO_P_RG_PROJ_B], H, D, T);
     g.tn(f.dH2_16, 2 * H, f.Y2_16, H, Gr[CAMO_P_F2_W0], H, Gr[CAMO_P_F2_B0], 2 * H, H, TK);
     g.tn(f.dU2_16, H, f.O2_16, H, Gr[CAMO_P_A2_OUT_W], H, Gr[CAMO_P_A2_OUT_B], H, H, TK);
-    g.tn(f.dQKVkg16, 3 * H, f.G16, H, Gr[CAMO_P_A2_IN_W], H, Gr[CAMO_P_A2_IN_B], H, H, TK);
+    if (kgq) {     // the q rows of attn2.in_proj from the fp32 dQ2 sums: their bf16 columns of dQKVkg16 are only being written by this launch
+      Gemm16Prob& p = g.tn(nullptr, H, f.G16, H, Gr[CAMO_P_A2_IN_W], H, Gr[CAMO_P_A2_IN_B], H, H, TK);
+      p.A = reinterpret_cast<const us*>(w.dQ2acc); p.flags |= GF_A_F32;
+    } else {
+      g.tn(f.dQKVkg16, 3 * H, f.G16, H, Gr[CAMO_P_A2_IN_W], H, Gr[CAMO_P_A2_IN_B], H, H, TK);
+    }
     g.tn(f.dQKVkg16 + H, 3 * H, f.G16, H, Gr[CAMO_P_A1_IN_W] + HH, H, Gr[CAMO_P_A1_IN_B] + H, 2 * H, H, TK);
-    g.tn(f.dG16, H, f.KG16, D, Gr[CAMO_P_KG_PROJ_W], D, Gr[CAMO_P_KG_PROJ_B], H, D, TK);
+    g.tn(kgq ? reinterpret_cast<const us*>(f.dGpart) : f.dG16, H, f.KG16, D, Gr[CAMO_P_KG_PROJ_W], D, Gr[CAMO_P_KG_PROJ_B], H, D, TK);
     CK(g.run(), "node-level weight gradients");
     return 0;
   }

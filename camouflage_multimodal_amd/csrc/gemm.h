@@ -14,7 +14,9 @@ enum : int {
   GF_SIGMOID = 32,    // v = 1/(1+exp(-v))                   (last)
   GF_A_KMAJOR = 64,   // A element (m,k) at A[k*lda + m] instead of A[m*lda + k]
   GF_B_KMAJOR = 128,  // B element (k,n) at B[k*ldb + n] instead of B[n*ldb + k]
-  GF_A_VIRT = 256     // gemm16 only: A is the ReLU/dropout mask-broadcast gradient built on the fly (Gemm16Prob::virt_g)
+  GF_A_VIRT = 256,    // gemm16 only: A is the ReLU/dropout mask-broadcast gradient built on the fly (Gemm16Prob::virt_g)
+  GF_A_F32 = 512,     // gemm16 TN only: A holds fp32 sums (lda in floats), rounded to bf16 while staging; rows >= K read as zero
+  GF_KGQ = 1024       // gemm16 TN only, with GF_A_F32: the KG rows' deferred query-gradient chain (Gemm16Prob::kgq_wT)
 };
 
 // C[m,n] (+)= epi( sum_k A(m,k) * B(k,n) + bias[n] ) (+ res[m,n])

@@ -11,6 +11,7 @@
 //   TN : C[M,N] += A[K,M]^T . B[K,N]  (fp32 atomics, split-K)   A, B row-major bf16 with K rows; rows up to
 //        round_up(K, 128) must be readable, and zero in one operand / finite in the other (the workspace
 //        pads and clears them); M % 8 == 0, N % 8 == 0                                    (dW += dy^T.x)
+//        GF_A_F32: A in fp32, rounded while staging; GF_KGQ: a chained product on top of that (see Gemm16Prob)
 // N % 4 == 0, 16-byte aligned pointers and leading dimensions throughout.
 #pragma once
 #include "common.h"
@@ -47,6 +48,19 @@ struct Gemm16Prob {
   // act = the bf16 tensor passed as A (the forward's post-ReLU/dropout activation, rows padded and cleared like any
   // TN operand), rounded to bf16 exactly as relu_bcast_bwd would have written it.  sample(): as for GF_RES_BCAST.
   const float* virt_g; int ldg;
+  // GF_A_F32: A is an fp32 [K][M] array of finished sums (the fused backward's dQ2 atomics), lda in floats; a block rounds it to
+  // bf16 while staging, as the kernel that used to write the bf16 operand did, and reads rows >= K as zero (no pad rows needed).
+  // GF_KGQ (with GF_A_F32; M = 256, N = 128): instead of C += A^T.B, with Mq = A^T.B kept in fp32 and rounded once to bf16,
+  //   C [256][N] += W^T.Mq  and  bias_grad [256] += W^T.colsum(A),   W [M][256]
+  // -- the weight gradient of a layer x -> g = x.Wp^T whose output gradient is dG = dGpart + A.W, taken without forming A.W:
+  // dG^T.x = dGpart^T.x + W^T.(A^T.x).  Sixteen blocks (output rows 64 q.., K slice 64 c.. of W^T.Mq); each computes the 64-row
+  // slice of Mq it multiplies.  kgq_wT: W^T as the transposed weight shadow (fused_rows.h; k steps 0 .. M/16 - 1 of a stream of
+  // 48), kgq_w: W in fp32 (ld = ldg) for the bias term.
+  // Behind the sixteen, ceil(K / 32) row blocks keep the record of what the chain no longer forms, for readers of the workspace (nothing
+  // in the launch reads either):  kgq_a16 [K][kgq_lda16] = bf16(A)  and  C16 [K][ldc16] = bf16(kgq_part16 + A.W),  kgq_part16
+  // [K][ldc16] = dGpart in bf16.
+  const unsigned short* kgq_wT; const float* kgq_w;
+  const unsigned short* kgq_part16; unsigned short* kgq_a16; int kgq_lda16;
   // filled by the launcher
   int tiles_n, ksplit, kchunk, tile_begin;
 };

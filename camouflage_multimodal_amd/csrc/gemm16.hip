@@ -20,6 +20,7 @@
 // (a wave-instruction covers 128 contiguous bytes of two rows).
 #include "gemm16.h"
 #include "mfma_inl.h"   // fragment types, lds_tr16
+#include <type_traits>
 
 
 namespace {
@@ -33,6 +34,7 @@ constexpr int NT_BUF_BYTES = (BM + BN) * PM;   // 24576: two stages = 48 KB, thr
 constexpr int BUF_BYTES = 32768;        // TN stage: 12288 + 64*320
 
 struct Stage { u32x4 a[2], b[4]; };
+struct StageF { float4 a[4]; u32x4 b[4]; int ok; };      // GF_A_F32: the two A chunks as 8 floats each; ok: bit i = chunk i's row < K
 
 // act chunk (8 bf16) + 8 gradient values -> 8 bf16 of (act > 0 ? g * scale : 0)
 __device__ __forceinline__ u32x4 virt_chunk(u32x4 act, float4 g0, float4 g1, float scale) {
@@ -223,8 +225,98 @@ __device__ __forceinline__ void body_nt(const Gemm16Batch& gb, const Gemm16Prob&
 }
 
 // ------------------------------------------------------------------------------------------ TN
-template <int PIPE, bool VIRT>
-__device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int kt0, int nt, char* smem, int exp = 0) {
+// The tail of a GF_KGQ block (gemm16.h): acc = the 64 x 128 slice Mq[m0 .. m0 + 63][:] of A^T.B in body_tn's layout, accb = the
+// slice's column sums of A.  Mq goes to LDS once, as bf16 and transposed ([d][64 j], pitch 144 B: the sixteen rows of a 16-byte lane
+// group land on sixteen bank quads), where it is the B operand of  C[64 q ..][:] += W^T[64 q .., m0 ..] . Mq  (K = 64); the A
+// operand is the weight shadow's fragment stream, read straight from global memory.
+__device__ __forceinline__ void kgq_finish(const Gemm16Prob& P, int m0, int q, const f32x16 (&acc)[2], const f32x16& accb, char* smem) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, h = lane >> 5;
+  constexpr int PT = 144;
+  // W^T rows 64 q + 32 wr + l31, k = m0 + 16 s + 8 h ..: shadow [wave q][k step][tile wr][lane][8], 48 k steps per wave
+  const u32x4* wp = reinterpret_cast<const u32x4*>(P.kgq_wT) + ((size_t)(q * 48 + (m0 >> 4)) * 2 + wr) * 64 + lane;
+  u32x4 wf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) wf[s] = wp[128 * s];
+  float* sv = reinterpret_cast<float*>(smem + 128 * PT);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    char* row = smem + (64 * wc + 32 * j + l31) * PT + 2 * (32 * wr + 4 * h);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      *reinterpret_cast<u32x2*>(row + 16 * g) = u32x2{pack2(acc[j][4 * g], acc[j][4 * g + 1]), pack2(acc[j][4 * g + 2], acc[j][4 * g + 3])};
+  }
+  if (wc == 0 && l31 == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sv[32 * wr + acc_row(r, h)] = accb[r];
+  }
+  __syncthreads();
+  f32x16 o[2] = {zero16(), zero16()};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const char* pb = smem + (64 * wc + l31) * PT + 32 * s + 16 * h;
+    const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(pb), b1 = *reinterpret_cast<const bf16x8*>(pb + 32 * PT);
+    o[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wf[s]), b0, o[0], 0, 0, 0);
+    o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wf[s]), b1, o[1], 0, 0, 0);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float* cp = P.C + 64 * wc + 32 * j + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) atomicAdd(cp + (size_t)(64 * q + 32 * wr + acc_row(r, h)) * P.ldc, o[j][r]);
+  }
+  {   // bias_grad[64 q + i] += sum_j W[m0 + j][64 q + i] * colsum(A)[m0 + j]: thread = (i, 16 of the 64 j)
+    const int i = tid & 63, j0 = 16 * (tid >> 6);
+    const float* w = P.kgq_w + (size_t)(m0 + j0) * P.ldg + 64 * q + i;
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) sum = fmaf(w[(size_t)j * P.ldg], sv[j0 + j], sum);
+    atomicAdd(P.bias_grad + 64 * q + i, sum);
+  }
+}
+
+// A row block of a GF_KGQ problem (gemm16.h): rows r0 .. r0 + 31 of  bf16(A) -> kgq_a16  and  bf16(kgq_part16 + A.W) -> C16.  The
+// rows' 256 A values sit in LDS as bf16 ([32][256], pitch 528); wave w owns output columns 64 w .. + 63 and streams its part of the
+// weight shadow (k steps 0 .. 15) as the MFMA A operand, so a lane ends up with four consecutive columns of one row.
+__device__ __forceinline__ void kgq_rows(const Gemm16Prob& P, int r0, char* smem) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
+  constexpr int PR_ = 528;
+  for (int c = tid; c < 32 * 32; c += 256) {
+    const int j = c >> 5, ch = c & 31, row = r0 + j;
+    u32x4 v = u32x4{0u, 0u, 0u, 0u};
+    if (row < P.K) {
+      const float* src = reinterpret_cast<const float*>(P.A) + (size_t)row * P.lda + 8 * ch;
+      const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
+      v = u32x4{pack2(x0.x, x0.y), pack2(x0.z, x0.w), pack2(x1.x, x1.y), pack2(x1.z, x1.w)};
+      *reinterpret_cast<u32x4*>(P.kgq_a16 + (size_t)row * P.kgq_lda16 + 8 * ch) = v;
+    }
+    *reinterpret_cast<u32x4*>(smem + j * PR_ + 16 * ch) = v;
+  }
+  __syncthreads();
+  const u32x4* wp = reinterpret_cast<const u32x4*>(P.kgq_wT) + (size_t)w * (48 * 2 * 64) + lane;
+  f32x16 acc[2] = {zero16(), zero16()};
+#pragma unroll 4
+  for (int ks = 0; ks < 16; ++ks) {
+    const bf16x8 x = *reinterpret_cast<const bf16x8*>(smem + l31 * PR_ + 32 * ks + 16 * h);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wp[64 * (2 * ks)]), x, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wp[64 * (2 * ks + 1)]), x, acc[1], 0, 0, 0);
+  }
+  const int row = r0 + l31;
+  if (row < P.K) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
+        const u32x2 pv = *reinterpret_cast<const u32x2*>(P.kgq_part16 + (size_t)row * P.ldc16 + c0);
+        *reinterpret_cast<u32x2*>(P.C16 + (size_t)row * P.ldc16 + c0) =
+            u32x2{pack2(acc[t][4 * g] + bf_lo(pv.x), acc[t][4 * g + 1] + bf_hi(pv.x)), pack2(acc[t][4 * g + 2] + bf_lo(pv.y), acc[t][4 * g + 3] + bf_hi(pv.y))};
+      }
+  }
+}
+
+template <int PIPE, bool VIRT, bool F32A = false>
+__device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int kt0, int nt, char* smem, int exp = 0, int rq = 0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, h = lane >> 5;
   const int M = P.M, N = P.N;
@@ -254,7 +346,7 @@ __device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int
   const bool do_bsum = P.bias_grad != nullptr && n0 == 0 && wc == 0;     // wave-uniform
   const short one = (short)0x3F80;
   const bf16x8 ones = {one, one, one, one, one, one, one, one};
-  Stage st[PIPE];
+  std::conditional_t<F32A, StageF, Stage> st[PIPE];
   int sa[PIPE][2];                        // VIRT: sample of each staged A row
   // VIRT: the tile's 64 columns of the scaled per-sample gradient rows live in LDS behind the two stage buffers
   float* gs = reinterpret_cast<float*>(smem + 2 * BUF_BYTES);
@@ -268,12 +360,23 @@ __device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int
     __syncthreads();
   }
 
-  auto gload = [&](Stage& r, int (&srow)[2], int kt) {
+  auto gload = [&](auto& r, int (&srow)[2], int kt) {
     const int k = kt0 + min(kt, nt - 1);                             // wave-uniform
     const char* a = Ab + (size_t)k * astep;
     const char* b = Bb + (size_t)k * bstep;
+    if constexpr (F32A) {
+      r.ok = 0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) r.a[i] = *reinterpret_cast<const u32x4*>(a + goa[i]);
+      for (int i = 0; i < 2; ++i) {                                  // (row clamp: nothing readable is promised behind row K - 1)
+        const int s = tid + 256 * i, row = k * BK + (s >> 3);
+        const float* src = reinterpret_cast<const float*>(P.A) + (size_t)min(row, P.K - 1) * P.lda + min(m0 + 8 * (s & 7), M - 8);
+        r.a[2 * i] = *reinterpret_cast<const float4*>(src); r.a[2 * i + 1] = *reinterpret_cast<const float4*>(src + 4);
+        r.ok |= row < P.K ? 1 << i : 0;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) r.a[i] = *reinterpret_cast<const u32x4*>(a + goa[i]);
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.b[i] = *reinterpret_cast<const u32x4*>(b + gob[i]);
     if constexpr (VIRT) {
@@ -284,11 +387,18 @@ __device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int
       }
     }
   };
-  auto sstore = [&](const Stage& r, const int (&srow)[2], int buf) {
+  auto sstore = [&](const auto& r, const int (&srow)[2], int buf) {
     char* base = smem + buf * BUF_BYTES;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      u32x4 a = r.a[i];
+      u32x4 a;
+      if constexpr (F32A) {
+        const float4 x0 = r.a[2 * i], x1 = r.a[2 * i + 1];
+        a = u32x4{pack2(x0.x, x0.y), pack2(x0.z, x0.w), pack2(x1.x, x1.y), pack2(x1.z, x1.w)};
+        if (!(r.ok >> i & 1)) a = u32x4{0u, 0u, 0u, 0u};
+      } else {
+        a = r.a[i];
+      }
       if constexpr (VIRT) {
         const float* g = gs + srow[i] * 64 + 8 * ((tid + 256 * i) & 7);
         a = virt_chunk(a, *reinterpret_cast<const float4*>(g), *reinterpret_cast<const float4*>(g + 4), 1.0f);
@@ -325,6 +435,9 @@ __device__ __forceinline__ void body_tn(const Gemm16Prob& P, int m0, int n0, int
   G16_PIPELINE_LOOP
 
   // C orientation: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+  if constexpr (F32A) {
+    if (P.flags & GF_KGQ) { kgq_finish(P, m0, rq, acc, accb, smem); return; }
+  }
   const int rowb = m0 + wr * 32 + 4 * h;
   if ((exp & 1) && acc[0][0] != 12345.f) return;            // (experiment: no epilogue)
   if (do_bsum && l31 == 0) {
@@ -595,11 +708,17 @@ __global__ __launch_bounds__(256, ROWS ? 2 : 3) void gemm16_kernel(const Gemm16B
   // ids, i.e. (with ~8 slices) all output tiles of ONE K slice -- the tiles that re-read the same rows of dy and x
   // then share them through that XCD's L2 instead of fetching them 2-8 times from HBM / Infinity Cache.
   const int tiles = ((P.M + BM - 1) / BM) * P.tiles_n;
+  if ((P.flags & GF_KGQ) && t >= tiles * P.ksplit) { kgq_rows(P, (t - tiles * P.ksplit) * 32, smem_raw); return; }
   const int ks = t / tiles; t -= ks * tiles;
   const int tn = t % P.tiles_n, tm = t / P.tiles_n;
   if (P.flags & GF_A_KMAJOR) {
     const int ktiles = (P.K + 127) / 128 * 2;                 // K rounded up to 128 rows, in 64-row tiles
     const int per = P.kchunk / BK, kt0 = ks * per;
+    if (P.flags & GF_A_F32) {
+      if (P.flags & GF_KGQ) body_tn<PIPE, false, true>(P, tm * BM, 0, 0, ktiles, smem_raw, 0, ks);      // (ks: the block's output rows, not a K slice)
+      else                  body_tn<PIPE, false, true>(P, tm * BM, tn * BN, kt0, min(per, ktiles - kt0), smem_raw);
+      return;
+    }
     if constexpr (ROWS) {
       if (P.flags & GF_A_VIRT) { body_tn<PIPE, true>(P, tm * BM, tn * BN, kt0, min(per, ktiles - kt0), smem_raw); return; }
     }
@@ -738,6 +857,7 @@ __global__ __launch_bounds__(512) void gemm16_tnbig_kernel(const Gemm16Batch gb,
   }
 }
 
+static_assert(sizeof(Gemm16Batch) + sizeof(int) <= 4096, "gemm16_kernel's arguments: the kernel-argument segment is 4 KB");
 constexpr int KCAP_MIN = 8;          // shortest split-K chunk (64-row tiles) a sparse launch falls back to
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -788,7 +908,7 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
     bool all_tn = true; int kmax = 0;
     for (int i = 0; i < gb.n; ++i) {
       const Gemm16Prob& p = gb.p[i];
-      all_tn = all_tn && (p.flags & GF_A_KMAJOR) && (p.flags & GF_B_KMAJOR) && !(p.flags & GF_A_VIRT) && !p.ln_mode && (p.M % 8) == 0 && (p.N % 8) == 0;
+      all_tn = all_tn && (p.flags & GF_A_KMAJOR) && (p.flags & GF_B_KMAJOR) && !(p.flags & (GF_A_VIRT | GF_A_F32)) && !p.ln_mode && (p.M % 8) == 0 && (p.N % 8) == 0;
       kmax = p.K > kmax ? p.K : kmax;
     }
     const bool big = kn.tn_big < 0 ? kmax >= 40000 : kn.tn_big > 0;    // (measured: B = 64 [27 k rows] +8 %, B = 128 [55 k] -7 %, B = 256 [125 k] -15 %)
@@ -799,6 +919,7 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
   for (int ci = 0;; ++ci) {
     const int kcap = kn.tn_kcap > 0 ? kn.tn_kcap : kcaps[ci];
     total = 0; kcap_used = kcap;
+    int extra = 0;                                  // GF_KGQ blocks: short, and no part of what the ladder spreads over the chip
     for (int i = 0; i < gb.n; ++i) {
       Gemm16Prob& p = gb.p[i];
       const bool akm = p.flags & GF_A_KMAJOR, bkm = p.flags & GF_B_KMAJOR;
@@ -817,8 +938,13 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
         tiles = (p.M + RM - 1) / RM;
       }
       if (akm) {
-        if ((p.M & 7) || (p.N & 7) || p.M < 8 || p.N < 8 || !p.C || p.C16 || p.bias || p.res ||
-            (p.flags & ~(GF_A_KMAJOR | GF_B_KMAJOR | GF_ATOMIC | GF_A_VIRT)))
+        if ((p.M & 7) || (p.N & 7) || p.M < 8 || p.N < 8 || !p.C || (p.C16 && !(p.flags & GF_KGQ)) || p.bias || p.res ||
+            (p.flags & ~(GF_A_KMAJOR | GF_B_KMAJOR | GF_ATOMIC | GF_A_VIRT | GF_A_F32 | GF_KGQ)))
+          return (int)hipErrorInvalidValue;
+        if ((p.flags & GF_A_F32) && ((p.flags & GF_A_VIRT) || (double)p.K * p.lda * 4.0 >= 4.0e9)) return (int)hipErrorInvalidValue;
+        if ((p.flags & GF_KGQ) && (!(p.flags & GF_A_F32) || p.M != 256 || p.N != BN || !p.kgq_wT || !al16(p.kgq_wT) || !p.kgq_w || p.ldg < 256 || !p.bias_grad ||
+                                   !p.C16 || !p.kgq_part16 || !p.kgq_a16 || (reinterpret_cast<uintptr_t>(p.C16) & 7) || (reinterpret_cast<uintptr_t>(p.kgq_part16) & 7) ||
+                                   !al16(p.kgq_a16) || p.ldc16 < 256 || (p.ldc16 & 3) || p.kgq_lda16 < 256 || (p.kgq_lda16 & 7)))
           return (int)hipErrorInvalidValue;
         if (p.flags & GF_A_VIRT) {     // sample count rides in ldc16 (unused by TN); its gradient slice must fit the LDS spare
           const int ns = p.row_sample ? p.ldc16 : (p.uniform_n > 0 ? (p.K + p.uniform_n - 1) / p.uniform_n : 0);
@@ -829,6 +955,7 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
         const int per = ktiles < kcap ? ktiles : kcap;                       // even
         p.kchunk = per * BK;
         p.ksplit = (ktiles + per - 1) / per;
+        if (p.flags & GF_KGQ) { p.kchunk = ktiles * BK; p.ksplit = 4; extra += tiles * 4 + (p.K + 31) / 32; }   // whole K per block; the "slices" are output row quarters
       } else {
         if ((p.K % BK) || (p.N & 3) || (p.flags & (GF_ATOMIC | GF_SIGMOID)) || p.bias_grad) return (int)hipErrorInvalidValue;
         if ((p.C && (!al16(p.C) || (p.ldc & 3))) || (p.C16 && ((reinterpret_cast<uintptr_t>(p.C16) & 7) || (p.ldc16 & 3))) ||
@@ -837,9 +964,9 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
         p.kchunk = p.K; p.ksplit = 1;
       }
       p.tile_begin = total;
-      total += tiles * p.ksplit;
+      total += tiles * p.ksplit + ((p.flags & GF_KGQ) ? (p.K + 31) / 32 : 0);                // (+ the record's row blocks)
     }
-    if (kn.tn_kcap > 0 || (kcap > 16 ? total >= 440 : total >= 200) || kcap <= KCAP_MIN) break;
+    if (kn.tn_kcap > 0 || (kcap > 16 ? total - extra >= 440 : total - extra >= 200) || kcap <= KCAP_MIN) break;
   }
   gb.n_heavy = 0; gb.exp = kn.exp;
   // (measured on the training step: B = 4 -2.8 us, B = 16 +-0, B = 64 +0.7 us -- with long chunks the short blocks no longer
@@ -860,7 +987,11 @@ int launch_gemm16_batch(Gemm16Batch& gb, const Gemm16Knobs& kn, hipStream_t stre
   }
   if (has_virt && !has_rows) return (int)hipErrorInvalidValue;      // the virtual operand lives in the whole-row kernel only
   double fl = 0.0;
-  for (int i = 0; i < gb.n; ++i) fl += 2.0 * gb.p[i].M * (double)gb.p[i].N * gb.p[i].K;
+  for (int i = 0; i < gb.n; ++i) {
+    const Gemm16Prob& p = gb.p[i];
+    if (p.flags & GF_KGQ) fl += 2.0 * p.M * (double)p.N * (4.0 * p.K + 256.0) + 2.0 * p.K * 256.0 * 256.0;      // Mq four times over, W^T.Mq; the record's A.W
+    else fl += 2.0 * p.M * (double)p.N * p.K;
+  }
   const int prof = gemm_prof_open(stream, fl);
   // two register stages (four measured slower on every launch of the step; round 2: a weight-gradient-only kernel with four
   // stages at two blocks per CU, 184 VGPRs, no spills: +1 us on the fused schedule's weight-gradient launch)
