@@ -47,6 +47,8 @@ RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
 # every symbol include/camo_rg_train.h declares
 RGT_SYMBOLS = ("camo_rg_train_workspace_bytes", "camo_rg_loss_backward")
 RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
+# every symbol include/camo_rg_train_bn.h declares
+RGTBN_SYMBOLS = ("camo_rg_train_bn_workspace_bytes", "camo_rg_loss_backward_bn")
 # every symbol include/camo_rg_targets.h declares
 RGTG_SYMBOLS = ("camo_rg_node_targets",)
 RG_MAX_LABELS = 4096
@@ -194,6 +196,11 @@ def lib():
     L.camo_rg_train_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
     L.camo_rg_loss_backward.restype = C.c_int
     L.camo_rg_loss_backward.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, vp]
+    L.camo_rg_train_bn_workspace_bytes.restype = sz
+    L.camo_rg_train_bn_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
+    L.camo_rg_loss_backward_bn.restype = C.c_int
+    L.camo_rg_loss_backward_bn.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp,
+                                           f32, vp, vp, vp]
     L.camo_rg_node_targets.restype = C.c_int
     L.camo_rg_node_targets.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.camo_debug_gemm.restype = C.c_int

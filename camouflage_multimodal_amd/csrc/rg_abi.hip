@@ -1,6 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
-// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen, and the node targets from ground-truth masks.
+// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, and the node targets from
+// ground-truth masks.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,7 @@
 #include "../../include/camo_slic.h"
 #include "../../include/camo_rg_detect.h"
 #include "../../include/camo_rg_train.h"
+#include "../../include/camo_rg_train_bn.h"
 #include "../../include/camo_rg_targets.h"
 
 using namespace camo_abi;
@@ -32,6 +34,11 @@ namespace {
 // The embedding forward's buffers: h[k] = output of conv(k + 1) after batch norm and ReLU.  xhat (the normalised pre-activations) and the
 // GAT saves m, S, O are the training call's; all null at inference.
 struct RgFwd { float *Hh, *a_src, *a_dst, *dinv, *xw, *h[4], *xhat[4], *m, *S, *O; };
+
+// Batch-statistics mode of the forward (include/camo_rg_train_bn.h): stats [4][2][C] receives mean | rstd of every layer for the
+// backward, partial is the column sums' first-stage buffer; running (8 pointers, or null) is updated in place, batch_stats
+// ([4][2][C] mean | biased var, or null) is the caller's.
+struct RgBatchNorm { float* stats; float* partial; float* const* running; float momentum; float* batch_stats; };
 
 struct RgWs : RgFwd { size_t bytes; };
 RgWs rg_carve(const camo_rg_dims_t& d, int N, void* base) {
@@ -52,11 +59,23 @@ int rg_check(const camo_rg_dims_t* d, int N) {
   return 0;
 }
 
-// x -> h[3] (conv1 .. conv4, each with its batch norm on the running statistics and ReLU), then fc_shared + ReLU -> emb
+// x -> h[3] (conv1 .. conv4, each with its batch norm and ReLU), then fc_shared + ReLU -> emb.  bb null: batch norm on the running
+// statistics, inside the aggregation kernels.  bb given (needs the saving buffers of f): the aggregations write the raw
+// pre-activation z to xhat[k], then the statistics of z over the N rows, then xhat in place and h[k] = relu(xhat weight + bias).
 int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, const int32_t* rowptr, const int32_t* col, const float* w,
-               int N, const RgFwd& f, float* emb, hipStream_t st) {
+               int N, const RgFwd& f, float* emb, hipStream_t st, const RgBatchNorm* bb = nullptr) {
   const int C = d.hidden, K = d.heads, In = d.in_channels;
+  const bool raw = bb != nullptr;
   auto bn = [&](int slot) { return BnEval{P[slot], P[slot + 1], P[slot + 2], P[slot + 3]}; };
+  auto batch_norm = [&](int layer, int slot) -> int {      // slot: the layer's batch-norm weight
+    if (!raw) return 0;
+    float* mean = bb->stats + (size_t)layer * 2 * C;
+    CK(launch_rgt_bn_stats(f.xhat[layer], N, C, bb->momentum, bb->partial, mean, mean + C,
+                           bb->batch_stats ? bb->batch_stats + (size_t)layer * 2 * C : nullptr, bb->running ? bb->running[2 * layer] : nullptr,
+                           bb->running ? bb->running[2 * layer + 1] : nullptr, st), "batch statistics");
+    CK(launch_rgt_bn_apply(f.xhat[layer], mean, mean + C, P[slot], P[slot + 1], f.h[layer], N, C, st), "batch norm");
+    return 0;
+  };
   GB g(make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
   // conv1: GATConv (extract_rg_embeddings.py:104) + bn1 + relu
   g.nt(x, In, P[CAMO_RG_C1_W], In, nullptr, f.Hh, K * C, N, K * C, In);
@@ -65,15 +84,17 @@ int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, c
   // Two GAT kernels on purpose: inference runs an online softmax with __expf, training a two-pass softmax with expf because its
   // backward recomputes alpha from the saved m and S.  One kernel for both would change one path's bits.
   const float* b1 = P[CAMO_RG_C1_BIAS];
-  CK(f.m ? launch_rgt_gat_forward(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.m, f.S, f.O, f.xhat[0], f.h[0], N, K, C, st)
+  CK(f.m ? launch_rgt_gat_forward(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.m, f.S, f.O, f.xhat[0], f.h[0], N, K, C, st, raw)
          : launch_gat_aggregate(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.h[0], N, K, C, st), "gat aggregate");
+  if (int e = batch_norm(0, CAMO_RG_BN1)) return e;
   // conv2..4: GCNConv with edge weights (:108-118) + bn + relu
   CK(launch_gcn_dinv(rowptr, w, f.dinv, N, st), "gcn degrees");
   for (int k = 0; k < 3; ++k) {
     const int base = CAMO_RG_C2_BIAS + 6 * k;
     g.nt(f.h[k], C, P[base + 1], C, nullptr, f.xw, C, N, C, C);
     CK(g.run(), "gcn projection");
-    CK(launch_gcn_aggregate(f.xw, rowptr, col, w, f.dinv, P[base], bn(base + 2), f.xhat[k + 1], f.h[k + 1], N, C, st), "gcn aggregate");
+    CK(launch_gcn_aggregate(f.xw, rowptr, col, w, f.dinv, P[base], bn(base + 2), f.xhat[k + 1], f.h[k + 1], N, C, st, raw), "gcn aggregate");
+    if (int e = batch_norm(k + 1, base + 2)) return e;
   }
   // fc_shared + relu (:121)
   g.nt(f.h[3], C, P[CAMO_RG_FC_W], C, P[CAMO_RG_FC_B], emb, C, N, C, C, GF_RELU);
@@ -81,16 +102,16 @@ int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, c
   return 0;
 }
 
-// camo_rg_loss_backward (include/camo_rg_train.h)
-struct RgtWs : RgFwd {      // the forward's buffers, all saved, and the backward's
-  float *dh, *r, *da_src, *da_dst, *emb, *Z, *dZ, *logits, *dlogits, *dA, *dB, *W1, *b1, *partial;
+// camo_rg_loss_backward (include/camo_rg_train.h), camo_rg_loss_backward_bn (include/camo_rg_train_bn.h)
+struct RgtWs : RgFwd {      // the forward's buffers, all saved, and the backward's; stats [4][2][C] = mean | rstd: batch statistics only
+  float *dh, *r, *da_src, *da_dst, *emb, *Z, *dZ, *logits, *dlogits, *dA, *dB, *W1, *b1, *partial, *stats;
   size_t bytes;
 };
 size_t rgt_partial_width(const camo_rg_dims_t& d, int nc) {
   const size_t C = d.hidden, K = d.heads, Hh = C / 2;
   return std::max(std::max(2 * K * C, 3 * Hh), std::max((size_t)nc * Hh, (size_t)2 * nc + 1));
 }
-RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base) {
+RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base, bool batch_stats = false) {
   RgtWs w{};
   Carver c(base);
   const size_t n = N, C = d.hidden, K = d.heads, units = 3 * (C / 2), L = 2 * (size_t)nc + 1;
@@ -103,6 +124,7 @@ RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base) {
   w.logits = c.take<float>(n * L); w.dlogits = c.take<float>(n * L); w.dA = c.take<float>(n * C); w.dB = c.take<float>(n * C);
   w.W1 = c.take<float>(units * C); w.b1 = c.take<float>(units);
   w.partial = c.take<float>((size_t)rgt_row_blocks(N) * rgt_partial_width(d, nc));
+  if (batch_stats) w.stats = c.take<float>(4 * 2 * C);
   c.off = (c.off + 255) & ~size_t(255);
   w.bytes = c.off;
   return w;
@@ -115,6 +137,19 @@ int rgt_check(const camo_rg_dims_t* d, int nc, int N, int E) {
   if (nc < 2 || nc > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_UNSUPPORTED, "num_classes must be in [2, 8]");
   return 0;
 }
+// (rgt_check's envelope, plus N >= 2: the unbiased variance of the running update divides by N - 1)
+int rgtbn_check(const camo_rg_dims_t* d, int nc, int N, int E) {
+  if (!d) return fail(CAMO_E_ARG, "dims is null");
+  if (rg_check(d, N) || N < 2 || E < N || (d->hidden & 1))
+    return fail(CAMO_E_UNSUPPORTED, "need N >= 2 (batch statistics), E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8");
+  if (nc < 2 || nc > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_UNSUPPORTED, "num_classes must be in [2, 8]");
+  return 0;
+}
+constexpr bool rg_running_slot(int i) {      // the 8 running-statistic slots of camo_rg_gnn.h's table
+  return i == CAMO_RG_BN1 + 2 || i == CAMO_RG_BN1 + 3 || (i >= CAMO_RG_C2_BIAS && i < CAMO_RG_FC_W && (i - CAMO_RG_C2_BIAS) % 6 >= 4);
+}
+static_assert(rg_running_slot(6) && rg_running_slot(7) && rg_running_slot(12) && rg_running_slot(25) && !rg_running_slot(5) && !rg_running_slot(8) &&
+              !rg_running_slot(11) && !rg_running_slot(26), "the running statistics are slots 6, 7, then 12, 13 of every six");
 }  // namespace
 
 extern "C" {
@@ -420,25 +455,36 @@ size_t camo_rg_train_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_cla
   return rgt_carve(*dims, num_classes, N, nullptr).bytes;
 }
 
-int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
-                          const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
-                          const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
-                          const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                          float* loss, float* const* grads, void* stream) {
-  if (int e = rgt_check(dims, num_classes, N, E)) return e;
+// The one launch sequence of both entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
+// (its stats and partial are filled in here from the workspace).
+static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                   const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                   const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                   const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch) {
+  if (int e = batch ? rgtbn_check(dims, num_classes, N, E) : rgt_check(dims, num_classes, N, E)) return e;
   if (!params || !head_params || !x || !rowptr || !col || !w || !rrowptr || !rcol || !rw || !mask_t || !inst_t || !edge_t || !workspace ||
       !loss || !grads)
     return fail(CAMO_E_ARG, "null pointer argument");
   for (int i = 0; i < CAMO_RG_NPARAMS; ++i)
-    if (!params[i]) return fail(CAMO_E_ARG, "null pointer in the parameter table");
+    if (!params[i] && !(batch && rg_running_slot(i))) return fail(CAMO_E_ARG, "null pointer in the parameter table");
   for (int i = 0; i < CAMO_RGD_NPARAMS; ++i)
     if (!head_params[i]) return fail(CAMO_E_ARG, "null pointer in the head parameter table");
   for (int i = 0; i < CAMO_RGT_NGRADS; ++i)
     if (!grads[i]) return fail(CAMO_E_ARG, "null pointer in the gradient table");
   if (!std::isfinite(w_mask) || !std::isfinite(w_instance) || !std::isfinite(w_edge)) return fail(CAMO_E_ARG, "loss weights must be finite");
+  if (batch && batch->running) {
+    for (int i = 0; i < 8; ++i)
+      if (!batch->running[i]) return fail(CAMO_E_ARG, "null pointer in the running-statistics table");
+    if (!std::isfinite(batch->momentum) || !(batch->momentum > 0.f && batch->momentum <= 1.f))
+      return fail(CAMO_E_ARG, "momentum must be finite and in (0, 1] when running is given");
+  }
   const camo_rg_dims_t& d = *dims;
-  const RgtWs ws = rgt_carve(d, num_classes, N, workspace);
-  if (workspace_bytes < ws.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_rg_train_workspace_bytes()");
+  const RgtWs ws = rgt_carve(d, num_classes, N, workspace, batch != nullptr);
+  if (workspace_bytes < ws.bytes)
+    return fail(CAMO_E_WORKSPACE, batch ? "workspace smaller than camo_rg_train_bn_workspace_bytes()" : "workspace smaller than camo_rg_train_workspace_bytes()");
+  if (batch) { batch->stats = ws.stats; batch->partial = ws.partial; }
+  const bool bs = batch != nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int C = d.hidden, K = d.heads, In = d.in_channels, nc = num_classes, Hh = C / 2, units = 3 * Hh, L = 2 * nc + 1;
   const int nb = rgt_row_blocks(N);
@@ -447,11 +493,19 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
   float* const* G = grads;
   float* const* GH = grads + CAMO_RGT_HEADS;
   auto bn = [&](int slot) { return BnEval{P[slot], P[slot + 1], P[slot + 2], P[slot + 3]}; };
+  // dy (ReLU-masked, in dB) -> the layer's batch-norm gradients, its conv-bias gradient, and dPre in place.  Frozen: dPre = dy weight /
+  // sqrt(var + eps), scaled by the first launch.  Batch statistics: the sums first, then dz from the finished sums (a third launch).
+  auto bn_backward = [&](int layer, int slot, float* dweight, float* dbias_bn, float* dbias_conv) -> int {
+    CK(launch_rgt_bn_backward(ws.dB, ws.xhat[layer], bn(slot), N, C, ws.partial, st, bs), "bn backward");
+    CK(launch_rgt_bn_finish(ws.partial, nb, bn(slot), C, dweight, dbias_bn, dbias_conv, st, bs), "bn gradients");
+    if (bs) CK(launch_rgt_bn_dz(ws.dB, ws.xhat[layer], P[slot], ws.stats + (size_t)layer * 2 * C + C, dweight, dbias_bn, N, C, st), "bn input gradient");
+    return 0;
+  };
   constexpr int KM = GF_A_KMAJOR | GF_B_KMAJOR;   // dW = dY^T . X without atomics: one block owns an output tile over the whole contraction
   GB g(make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
 
   // ---- forward, saving (camo_rg_node_embeddings + camo_rg_node_heads) ----
-  if (int e = rg_forward(d, P, x, rowptr, col, w, N, ws, ws.emb, st)) return e;
+  if (int e = rg_forward(d, P, x, rowptr, col, w, N, ws, ws.emb, st, batch)) return e;
   CK(launch_rgt_concat_heads(HP, ws.W1, ws.b1, C, st), "head weights");
   g.nt(ws.emb, C, ws.W1, C, ws.b1, ws.Z, units, N, units, C, GF_RELU);
   CK(g.run(), "head first layers");
@@ -488,8 +542,7 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
   // ---- conv4 .. conv2 backward: dB = dy -> dPre (in place) -> dA = dXW -> dB = dy of the layer below ----
   for (int k = 2; k >= 0; --k) {
     const int base = CAMO_RG_C2_BIAS + 6 * k, gb = CAMO_RGT_C2_BIAS + 4 * k;
-    CK(launch_rgt_bn_backward(ws.dB, ws.xhat[k + 1], bn(base + 2), N, C, ws.partial, st), "bn backward");
-    CK(launch_rgt_bn_finish(ws.partial, nb, bn(base + 2), C, G[gb + 2], G[gb + 3], G[gb], st), "bn gradients");
+    if (int e = bn_backward(k + 1, base + 2, G[gb + 2], G[gb + 3], G[gb])) return e;
     CK(launch_rgt_gcn_backward(ws.dB, rrowptr, rcol, rw, ws.dinv, ws.dA, N, C, st), "gcn aggregate backward");
     g.add(ws.dA, C, ws.h[k], C, G[gb + 1], C, C, C, N, KM);
     set_relu_bwd(g.nn(ws.dA, C, P[base + 1], C, ws.dB, C, N, C, C), ws.h[k], C, 1.f);
@@ -497,8 +550,7 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
   }
 
   // ---- conv1 (GAT) backward ----
-  CK(launch_rgt_bn_backward(ws.dB, ws.xhat[0], bn(CAMO_RG_BN1), N, C, ws.partial, st), "bn backward");
-  CK(launch_rgt_bn_finish(ws.partial, nb, bn(CAMO_RG_BN1), C, G[CAMO_RGT_BN1_W], G[CAMO_RGT_BN1_B], G[CAMO_RGT_C1_BIAS], st), "bn gradients");
+  if (int e = bn_backward(0, CAMO_RG_BN1, G[CAMO_RGT_BN1_W], G[CAMO_RGT_BN1_B], G[CAMO_RGT_C1_BIAS])) return e;
   CK(launch_rgt_gat_backward_a(ws.dB, ws.Hh, ws.O, ws.a_src, ws.a_dst, ws.m, ws.S, rowptr, col, ws.r, ws.da_dst, N, K, C, st), "gat backward A");
   CK(launch_rgt_gat_backward_b(ws.dB, ws.Hh, ws.a_src, ws.a_dst, ws.m, ws.S, ws.r, ws.da_dst, P[CAMO_RG_C1_ATT_SRC], P[CAMO_RG_C1_ATT_DST],
                                rrowptr, rcol, ws.da_src, ws.dh, N, K, C, st), "gat backward B");
@@ -508,6 +560,31 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
   g.add(ws.dh, K * C, x, In, G[CAMO_RGT_C1_W], In, K * C, In, N, KM);
   CK(g.run(), "gat projection gradient");
   return 0;
+}
+
+int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                          const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                          const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                          const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                          float* loss, float* const* grads, void* stream) {
+  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                 w_edge, workspace, workspace_bytes, loss, grads, stream, nullptr);
+}
+
+// ---- The same with batch-statistics batch norm (include/camo_rg_train_bn.h) --------------------------------------
+size_t camo_rg_train_bn_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E) {
+  if (rgtbn_check(dims, num_classes, N, E)) return 0;
+  return rgt_carve(*dims, num_classes, N, nullptr, true).bytes;
+}
+
+int camo_rg_loss_backward_bn(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                             const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                             const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                             const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                             float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats, void* stream) {
+  RgBatchNorm batch{nullptr, nullptr, running, momentum, batch_stats};
+  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                 w_edge, workspace, workspace_bytes, loss, grads, stream, &batch);
 }
 
 // ---- Node targets from ground-truth masks (include/camo_rg_targets.h) ------------------------------------------

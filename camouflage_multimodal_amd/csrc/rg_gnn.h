@@ -27,6 +27,7 @@ int launch_gat_alpha(const float* Hh, const float* att_src, const float* att_dst
 // out[i,:] = relu(bn(mean_k sum_{j->i} softmax_j(leaky_relu(a_src[j,k] + a_dst[i,k], 0.2)) Hh[j,k,:] + bias))
 int launch_gat_aggregate(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
                          BnEval bn, float* out, int N, int heads, int C, hipStream_t stream);
-// out[i,:] = relu(bn(sum_{j->i} dinv[j] w dinv[i] XW[j,:] + bias)); xhat non-null: the instantiation that also keeps xhat [N, C]
+// out[i,:] = relu(bn(sum_{j->i} dinv[j] w dinv[i] XW[j,:] + bias)); xhat non-null: the instantiation that also keeps xhat [N, C].
+// raw (needs xhat): xhat[i,:] = the sum + bias and nothing else -- bn is not read and out is not written (batch-statistics training)
 int launch_gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream);
+                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw = false);

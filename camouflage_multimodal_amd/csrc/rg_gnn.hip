@@ -60,8 +60,9 @@ __global__ void gat_aggregate_kernel(const float* __restrict__ Hh, const float* 
   }
 }
 
-// one wave per target node, 4 nodes per block.  SAVE: the training forward's instantiation, which also keeps xhat for the backward
-template <int CPL, bool SAVE>
+// one wave per target node, 4 nodes per block.  SAVE: the training forward's instantiation, which also keeps xhat for the backward.
+// RAW (batch-statistics training, rg_train.hip): the pre-activation acc + bias goes where xhat goes; no batch norm, no ReLU, out untouched
+template <int CPL, bool SAVE, bool RAW = false>
 __global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
                                      const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
                                      BnEval bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
@@ -82,9 +83,13 @@ __global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __
   for (int q = 0; q < CPL; ++q) {
     const int c = lane + 64 * q;
     if (c < C) {
-      const float xh = bn_xhat(acc[q] + bias[c], bn, c);
-      if constexpr (SAVE) xhat[(size_t)i * C + c] = xh;
-      out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+      if constexpr (RAW) {
+        xhat[(size_t)i * C + c] = acc[q] + bias[c];
+      } else {
+        const float xh = bn_xhat(acc[q] + bias[c], bn, c);
+        if constexpr (SAVE) xhat[(size_t)i * C + c] = xh;
+        out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+      }
     }
   }
 }
@@ -169,16 +174,16 @@ int launch_gat_aggregate(const float* Hh, const float* a_src, const float* a_dst
   return (int)hipGetLastError();
 }
 
-template <int CPL, bool SAVE>
+template <int CPL, bool SAVE, bool RAW = false>
 static void gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias, BnEval bn,
                           float* xhat, float* out, int N, int C, hipStream_t stream) {
-  hipLaunchKernelGGL((gcn_aggregate_kernel<CPL, SAVE>), dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
+  hipLaunchKernelGGL((gcn_aggregate_kernel<CPL, SAVE, RAW>), dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C);
 }
 
 int launch_gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream) {
-  if (C > 512) return (int)hipErrorInvalidValue;
-  auto run = C <= 128 ? (xhat ? gcn_aggregate<2, true> : gcn_aggregate<2, false>) : (xhat ? gcn_aggregate<8, true> : gcn_aggregate<8, false>);
+                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw) {
+  if (C > 512 || (raw && !xhat)) return (int)hipErrorInvalidValue;
+  auto run = raw ? (C <= 128 ? gcn_aggregate<2, true, true> : gcn_aggregate<8, true, true>) : C <= 128 ? (xhat ? gcn_aggregate<2, true> : gcn_aggregate<2, false>) : (xhat ? gcn_aggregate<8, true> : gcn_aggregate<8, false>);
   run(XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, stream);
   return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// Kernels of the region-graph GNN's loss and backward with frozen batch-norm statistics (rg_train.hip, include/camo_rg_train.h,
-// DESIGN.md 9a): the saving variant of the GAT aggregation, the loss on the node heads, the backward of the aggregations
+// Kernels of the region-graph GNN's loss and backward (rg_train.hip) with frozen batch-norm statistics (include/camo_rg_train.h,
+// DESIGN.md 9a) or with batch statistics (include/camo_rg_train_bn.h): the saving variant of the GAT aggregation, the loss on the node heads, the backward of the aggregations
 // over the reversed CSR, and the fixed-order column sums behind every bias / batch-norm / attention-vector gradient.  No
 // floating-point atomic anywhere: every sum has one owner and a fixed order.  All launchers return hipError_t as int; the callers
 // have checked the arguments.
@@ -10,9 +10,11 @@ constexpr int RGT_ROWS = 64;        // node rows per block of the first stage of
 inline int rgt_row_blocks(int N) { return (N + RGT_ROWS - 1) / RGT_ROWS; }
 
 // GAT aggregate that keeps what the backward needs: m, S [N, heads] softmax maximum and denominator per target and head,
-// O [N, heads, C] per-head aggregates, xhat [N, C] = (pre - mean) / sqrt(var + 1e-5), out [N, C] = relu(xhat * weight + bias_bn)
+// O [N, heads, C] per-head aggregates, xhat [N, C] = (pre - mean) / sqrt(var + 1e-5), out [N, C] = relu(xhat * weight + bias_bn).
+// raw: xhat = pre and nothing else -- bn is not read and out is not written (batch statistics; m, S, O are saved all the same)
 int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
-                           BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream);
+                           BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream,
+                           bool raw = false);
 // (the GCN aggregate that keeps xhat is rg_gnn.h's launch_gcn_aggregate with a non-null xhat)
 // copies the three heads' first layers into one [3 hidden / 2, hidden] weight and one [3 hidden / 2] bias
 int launch_rgt_concat_heads(const float* const* hp, float* W1, float* b1, int hidden, hipStream_t stream);
@@ -31,10 +33,26 @@ int launch_rgt_cross_partial(const float* A, int lda, int MA, const float* B, in
 struct RgtSegs { float* out[4]; int beg[5]; int n; };
 int launch_rgt_colsum_finish(const float* partial, int nb, int width, RgtSegs segs, hipStream_t stream);
 
-// in place d = d * weight / sqrt(var + 1e-5) (d arrives ReLU-masked: it is dy); partial[b, 0 | 1, c] = sum dy * xhat | sum dy
-int launch_rgt_bn_backward(float* d, const float* xhat, BnEval bn, int N, int C, float* partial, hipStream_t stream);
-// dweight = sum0, dbias_bn = sum1, dbias_conv = sum1 * weight / sqrt(var + 1e-5)
-int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* dweight, float* dbias_bn, float* dbias_conv, hipStream_t stream);
+// in place d = d * weight / sqrt(var + 1e-5) (d arrives ReLU-masked: it is dy); partial[b, 0 | 1, c] = sum dy * xhat | sum dy.
+// batch: the partial sums only -- d stays dy and bn is not read
+int launch_rgt_bn_backward(float* d, const float* xhat, BnEval bn, int N, int C, float* partial, hipStream_t stream, bool batch = false);
+// dweight = sum0, dbias_bn = sum1, dbias_conv = sum1 * weight / sqrt(var + 1e-5); batch: dbias_conv = +0.0f and bn is not read
+int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* dweight, float* dbias_bn, float* dbias_conv, hipStream_t stream,
+                         bool batch = false);
+
+// Batch statistics of z [N, C], N >= 2, in two launches: per block of RGT_ROWS rows (mean, sum of centred squares) in row order ->
+// partial [row blocks, 2, C]; then per channel 16 contiguous runs of blocks are merged in block order (Chan) and the 16 runs in run
+// order, by one owner, which writes mean[c],
+// rstd[c] = 1 / sqrt(var + 1e-5) (var = M2 / N), batch_stats[0 | 1, c] = mean | var if non-null, and, if running_mean is non-null,
+// running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var N / (N - 1)
+int launch_rgt_bn_stats(const float* z, int N, int C, float momentum, float* partial, float* mean, float* rstd, float* batch_stats,
+                        float* running_mean, float* running_var, hipStream_t stream);
+// in place zx = xhat = (z - mean) rstd; out = relu(xhat weight + bias)
+int launch_rgt_bn_apply(float* zx, const float* mean, const float* rstd, const float* weight, const float* bias, float* out, int N, int C,
+                        hipStream_t stream);
+// in place d = weight rstd (d - dbias / N - xhat dweight / N): dy -> dz once dweight = sum dy xhat and dbias = sum dy are finished
+int launch_rgt_bn_dz(float* d, const float* xhat, const float* weight, const float* rstd, const float* dweight, const float* dbias, int N, int C,
+                     hipStream_t stream);
 
 // dXW[j, :] = sum over the edges j -> i of the REVERSED CSR (row j: targets i, weights w) dinv[j] w dinv[i] dPre[i, :]
 int launch_rgt_gcn_backward(const float* dPre, const int* rrowptr, const int* rcol, const float* rw, const float* dinv, float* dXW, int N,

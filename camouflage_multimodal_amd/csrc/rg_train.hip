@@ -1,4 +1,5 @@
-// Loss and backward of the region-graph GNN with frozen batch-norm statistics (include/camo_rg_train.h).
+// Loss and backward of the region-graph GNN with frozen batch-norm statistics (include/camo_rg_train.h) or with the
+// statistics of the call's own nodes (include/camo_rg_train_bn.h).
 // Like the forward (rg_gnn.hip) the sparse part is latency- and HBM-bound gathers: one wave (GCN) or one block of `heads` waves
 // (GAT) per row of a CSR, source rows read as coalesced pieces, CPL channels per lane.  The backward of an aggregation is the same
 // gather walked over the REVERSED CSR, so every output row has one owner and no scatter is needed; every column sum over the
@@ -14,8 +15,9 @@ struct HeadPtrs { const float* p[12]; };   // CAMO_RGD_* order
 
 // ---- forward, saving ------------------------------------------------------------------------------------------------------
 // grid N, block 64 * heads.  Two walks over the row: the maximum, then the sums (the saved m and S are what the backward
-// recomputes alpha from, so they are taken the plain way, not online).
-template <int CPL>
+// recomputes alpha from, so they are taken the plain way, not online).  RAW (batch statistics): the pre-activation goes where xhat
+// goes; no batch norm, no ReLU, out untouched.
+template <int CPL, bool RAW = false>
 __global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
                                    const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias, BnEval bn,
                                    float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O, float* __restrict__ xhat,
@@ -51,9 +53,13 @@ __global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float v = 0.f;
     for (int kk = 0; kk < heads; ++kk) v += red[kk][c];
-    const float xh = bn_xhat(v / (float)heads + bias[c], bn, c);
-    xhat[(size_t)i * C + c] = xh;
-    out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+    if constexpr (RAW) {
+      xhat[(size_t)i * C + c] = v / (float)heads + bias[c];
+    } else {
+      const float xh = bn_xhat(v / (float)heads + bias[c], bn, c);
+      xhat[(size_t)i * C + c] = xh;
+      out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+    }
   }
 }
 
@@ -206,10 +212,13 @@ __global__ void colsum_finish_kernel(const float* __restrict__ partial, int nb, 
     if (c >= segs.beg[g] && c < segs.beg[g + 1]) segs.out[g][c - segs.beg[g]] = s;
 }
 
+// BATCH (batch statistics): the two partial sums only; d is left as it is, bn is not read (bn_dz_kernel needs the finished sums first)
+template <bool BATCH>
 __global__ void bn_backward_kernel(float* __restrict__ d, const float* __restrict__ xhat, BnEval bn, int N, int C, float* __restrict__ partial) {
   const int c = blockIdx.y * NT + threadIdx.x;
   if (c >= C) return;
-  const float scale = bn.weight[c] / sqrtf(bn.var[c] + BN_EPS);
+  float scale = 0.f;
+  if constexpr (!BATCH) scale = bn.weight[c] / sqrtf(bn.var[c] + BN_EPS);
   const int r0 = blockIdx.x * RGT_ROWS, r1 = min(N, r0 + RGT_ROWS);
   float s0 = 0.f, s1 = 0.f;
   for (int r = r0; r < r1; ++r) {
@@ -217,12 +226,14 @@ __global__ void bn_backward_kernel(float* __restrict__ d, const float* __restric
     const float dy = d[at];
     s0 = fmaf(dy, xhat[at], s0);
     s1 += dy;
-    d[at] = dy * scale;
+    if constexpr (!BATCH) d[at] = dy * scale;
   }
   partial[((size_t)blockIdx.x * 2) * C + c] = s0;
   partial[((size_t)blockIdx.x * 2 + 1) * C + c] = s1;
 }
 
+// BATCH: the conv bias cancels against the batch mean, so its gradient is +0.0f by definition (written as that, not as rounding noise)
+template <bool BATCH>
 __global__ void bn_finish_kernel(const float* __restrict__ partial, int nb, BnEval bn, int C, float* __restrict__ dweight,
                                  float* __restrict__ dbias_bn, float* __restrict__ dbias_conv) {
   const int c = blockIdx.x * NT + threadIdx.x;
@@ -231,7 +242,107 @@ __global__ void bn_finish_kernel(const float* __restrict__ partial, int nb, BnEv
   for (int b = 0; b < nb; ++b) { s0 += partial[((size_t)b * 2) * C + c]; s1 += partial[((size_t)b * 2 + 1) * C + c]; }
   dweight[c] = s0;
   dbias_bn[c] = s1;
-  dbias_conv[c] = s1 * (bn.weight[c] / sqrtf(bn.var[c] + BN_EPS));
+  if constexpr (BATCH) dbias_conv[c] = 0.f;
+  else dbias_conv[c] = s1 * (bn.weight[c] / sqrtf(bn.var[c] + BN_EPS));
+}
+
+// ---- batch statistics (include/camo_rg_train_bn.h) ---------------------------------------------------------------------------
+// Column statistics of z [N, C] in two stages, thread = channel (consecutive lanes on consecutive channels), never E[z^2] - mean^2.
+// Stage 1, grid (row blocks, column blocks): the block's rows in increasing order, twice -- their mean, then the centred squares
+// M2 = sum (z - mean)^2 (the second walk hits the cache).  partial[b, 0 | 1, c] = mean | M2.
+__global__ void bn_stats_partial_kernel(const float* __restrict__ z, int N, int C, float* __restrict__ partial) {
+  const int c = blockIdx.y * NT + threadIdx.x;
+  if (c >= C) return;
+  const int r0 = blockIdx.x * RGT_ROWS, r1 = min(N, r0 + RGT_ROWS);
+  const float z0 = z[(size_t)r0 * C + c];      // the sum is taken about the block's first row: a common offset of z costs no digits
+  float s = 0.f;
+  for (int r = r0 + 1; r < r1; ++r) s += z[(size_t)r * C + c] - z0;
+  const float mean = z0 + s / (float)(r1 - r0);
+  float m2 = 0.f;
+  for (int r = r0; r < r1; ++r) { const float d = z[(size_t)r * C + c] - mean; m2 = fmaf(d, d, m2); }
+  partial[((size_t)blockIdx.x * 2) * C + c] = mean;
+  partial[((size_t)blockIdx.x * 2 + 1) * C + c] = m2;
+}
+
+// Chan's update: (mean, m2) over na rows absorbs (mb, qb) over nbk >= 1 rows
+__device__ __forceinline__ void chan_merge(float& mean, float& m2, int& na, float mb, float qb, int nbk) {
+  const int n = na + nbk;
+  const float delta = mb - mean;
+  mean += delta * ((float)nbk / (float)n);
+  m2 += qb + delta * delta * ((float)na * (float)nbk / (float)n);
+  na = n;
+}
+
+// Stage 2, block = 16 channels x 16 groups: group g merges its contiguous run of ceil(nb / 16) row blocks in block order (Chan's
+// update; the last block may hold fewer rows), then the thread of group 0 merges the 16 runs in group order and owns the channel: a
+// fixed order at both levels, and a chain of nb / 16 + 16 dependent steps in place of nb.  It writes mean and rstd = 1 / sqrt(var +
+// 1e-5) for the kernels below, (mean, biased var) for the caller, and the running update
+// running <- (1 - momentum) running + momentum (mean | var N / (N - 1)).  The three optional outputs may be null.
+constexpr int BN_FIN_CH = 16, BN_FIN_GROUPS = 16;
+__global__ void bn_stats_finish_kernel(const float* __restrict__ partial, int nb, int N, int C, float momentum, float* __restrict__ mean_out,
+                                       float* __restrict__ rstd_out, float* __restrict__ batch_stats, float* __restrict__ running_mean,
+                                       float* __restrict__ running_var) {
+  __shared__ float sh_mean[BN_FIN_GROUPS][BN_FIN_CH], sh_m2[BN_FIN_GROUPS][BN_FIN_CH];
+  const int cl = threadIdx.x % BN_FIN_CH, g = threadIdx.x / BN_FIN_CH, c = blockIdx.x * BN_FIN_CH + cl;
+  const int per = (nb + BN_FIN_GROUPS - 1) / BN_FIN_GROUPS;
+  float mean = 0.f, m2 = 0.f;
+  int na = 0;
+  if (c < C) {
+    for (int b = g * per; b < min(nb, (g + 1) * per); ++b) {
+      const int nbk = min(N - b * RGT_ROWS, RGT_ROWS);
+      const float mb = partial[((size_t)b * 2) * C + c], qb = partial[((size_t)b * 2 + 1) * C + c];
+      if (na == 0) { mean = mb; m2 = qb; na = nbk; }
+      else chan_merge(mean, m2, na, mb, qb, nbk);
+    }
+  }
+  sh_mean[g][cl] = mean; sh_m2[g][cl] = m2;
+  __syncthreads();
+  if (g != 0 || c >= C) return;
+  for (int h = 1; h < BN_FIN_GROUPS && h * per < nb; ++h) {
+    const int rows = min(N, min(nb, (h + 1) * per) * RGT_ROWS) - h * per * RGT_ROWS;
+    chan_merge(mean, m2, na, sh_mean[h][cl], sh_m2[h][cl], rows);
+  }
+  const float var = m2 / (float)N;
+  mean_out[c] = mean;
+  rstd_out[c] = 1.0f / sqrtf(var + BN_EPS);
+  if (batch_stats) { batch_stats[c] = mean; batch_stats[C + c] = var; }
+  if (running_mean) {
+    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
+    running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (var * ((float)N / (float)(N - 1)));
+  }
+}
+
+// The two elementwise passes: grid (blocks of BN_EW_ROWS rows, column blocks), thread = channel, which reads its channel's four
+// constants once and walks the block's rows (no index division; a wave's lanes stay on consecutive channels of one row).
+constexpr int BN_EW_ROWS = 16;
+
+// in place zx = xhat = (z - mean) * rstd, out = relu(xhat * weight + bias)
+__global__ void bn_apply_kernel(float* __restrict__ zx, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out, int N, int C) {
+  const int c = blockIdx.y * NT + threadIdx.x;
+  if (c >= C) return;
+  const float mu = mean[c], rs = rstd[c], g = weight[c], b = bias[c];
+  const int r0 = blockIdx.x * BN_EW_ROWS, r1 = min(N, r0 + BN_EW_ROWS);
+  for (int r = r0; r < r1; ++r) {
+    const size_t at = (size_t)r * C + c;
+    const float xh = (zx[at] - mu) * rs;
+    zx[at] = xh;
+    out[at] = fmaxf(xh * g + b, 0.f);
+  }
+}
+
+// in place d = dz = weight rstd (dy - dbias / N - xhat dweight / N), dweight and dbias being the finished column sums
+__global__ void bn_dz_kernel(float* __restrict__ d, const float* __restrict__ xhat, const float* __restrict__ weight,
+                             const float* __restrict__ rstd, const float* __restrict__ dweight, const float* __restrict__ dbias, int N, int C,
+                             float inv_n) {
+  const int c = blockIdx.y * NT + threadIdx.x;
+  if (c >= C) return;
+  const float scale = weight[c] * rstd[c], mb = dbias[c] * inv_n, mw = dweight[c] * inv_n;
+  const int r0 = blockIdx.x * BN_EW_ROWS, r1 = min(N, r0 + BN_EW_ROWS);
+  for (int r = r0; r < r1; ++r) {
+    const size_t at = (size_t)r * C + c;
+    d[at] = scale * (d[at] - mb - xhat[at] * mw);
+  }
 }
 
 // ---- sparse backward ------------------------------------------------------------------------------------------------------------
@@ -355,8 +466,14 @@ HeadPtrs head_ptrs(const float* const* hp) {
 }  // namespace
 
 int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
-                           BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream) {
+                           BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream,
+                           bool raw) {
   if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
+  if (raw) {
+    if (C <= 128) hipLaunchKernelGGL((gat_forward_kernel<2, true>), dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
+    else          hipLaunchKernelGGL((gat_forward_kernel<8, true>), dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
+    return (int)hipGetLastError();
+  }
   if (C <= 128) hipLaunchKernelGGL(gat_forward_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
   else          hipLaunchKernelGGL(gat_forward_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
   return (int)hipGetLastError();
@@ -395,13 +512,41 @@ int launch_rgt_colsum_finish(const float* partial, int nb, int width, RgtSegs se
   return (int)hipGetLastError();
 }
 
-int launch_rgt_bn_backward(float* d, const float* xhat, BnEval bn, int N, int C, float* partial, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_backward_kernel, dim3(rgt_row_blocks(N), (C + NT - 1) / NT), dim3(NT), 0, stream, d, xhat, bn, N, C, partial);
+int launch_rgt_bn_backward(float* d, const float* xhat, BnEval bn, int N, int C, float* partial, hipStream_t stream, bool batch) {
+  const dim3 grid(rgt_row_blocks(N), (C + NT - 1) / NT);
+  if (batch) hipLaunchKernelGGL(bn_backward_kernel<true>, grid, dim3(NT), 0, stream, d, xhat, bn, N, C, partial);
+  else       hipLaunchKernelGGL(bn_backward_kernel<false>, grid, dim3(NT), 0, stream, d, xhat, bn, N, C, partial);
   return (int)hipGetLastError();
 }
 
-int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* dweight, float* dbias_bn, float* dbias_conv, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_finish_kernel, dim3((C + NT - 1) / NT), dim3(NT), 0, stream, partial, nb, bn, C, dweight, dbias_bn, dbias_conv);
+int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* dweight, float* dbias_bn, float* dbias_conv, hipStream_t stream,
+                         bool batch) {
+  const dim3 grid((C + NT - 1) / NT);
+  if (batch) hipLaunchKernelGGL(bn_finish_kernel<true>, grid, dim3(NT), 0, stream, partial, nb, bn, C, dweight, dbias_bn, dbias_conv);
+  else       hipLaunchKernelGGL(bn_finish_kernel<false>, grid, dim3(NT), 0, stream, partial, nb, bn, C, dweight, dbias_bn, dbias_conv);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_bn_stats(const float* z, int N, int C, float momentum, float* partial, float* mean, float* rstd, float* batch_stats,
+                        float* running_mean, float* running_var, hipStream_t stream) {
+  if (N < 2) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(rgt_row_blocks(N), (C + NT - 1) / NT), dim3(NT), 0, stream, z, N, C, partial);
+  hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((C + BN_FIN_CH - 1) / BN_FIN_CH), dim3(BN_FIN_CH * BN_FIN_GROUPS), 0, stream, partial,
+                     rgt_row_blocks(N), N, C, momentum, mean, rstd, batch_stats, running_mean, running_var);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_bn_apply(float* zx, const float* mean, const float* rstd, const float* weight, const float* bias, float* out, int N, int C,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(bn_apply_kernel, dim3((N + BN_EW_ROWS - 1) / BN_EW_ROWS, (C + NT - 1) / NT), dim3(NT), 0, stream, zx, mean, rstd, weight, bias,
+                     out, N, C);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_bn_dz(float* d, const float* xhat, const float* weight, const float* rstd, const float* dweight, const float* dbias, int N, int C,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL(bn_dz_kernel, dim3((N + BN_EW_ROWS - 1) / BN_EW_ROWS, (C + NT - 1) / NT), dim3(NT), 0, stream, d, xhat, weight, rstd, dweight,
+                     dbias, N, C, 1.0f / (float)N);
   return (int)hipGetLastError();
 }
 

@@ -8,8 +8,9 @@ torch_geometric's in the reference; the published algorithms they are restated f
 tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here, no RG weights or fixtures shipped).  The node-classification ``forward``
 runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py).  ``loss_and_gradients``
 gives the loss on the heads and every parameter's gradient with the batch-norm statistics frozen (``camo_rg_loss_backward``,
-include/camo_rg_train.h); batch statistics and dropout (models/region_graph/train.py) are outside the path, so ``forward`` in
-training mode raises.
+include/camo_rg_train.h) or, with ``batch_stats=True``, on the statistics of the call's own nodes, the running statistics updated
+(``camo_rg_loss_backward_bn``, include/camo_rg_train_bn.h); dropout (models/region_graph/train.py) is outside the path, so
+``forward`` in training mode raises.
 """
 from __future__ import annotations
 
@@ -481,14 +482,43 @@ class RegionGraphGNN(nn.Module):
         return t
 
     @torch.no_grad()
-    def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None):
+    def _batch_norms(self):
+        return [self.bn1, self.bn2, self.bn3, self.bn4]
+
+    def _running_table(self, dev):
+        """The 8 running statistics as the table ``camo_rg_loss_backward_bn`` updates in place (bn1 mean, bn1 var .. bn4 var), and
+        the modules' momentum."""
+        mom = {bn.momentum for bn in self._batch_norms()}
+        if len(mom) != 1:
+            raise _lib.CamoError("batch-statistics batch norm on the MI355X path needs one momentum for the four BatchNorm1d")
+        bufs = []
+        for bn in self._batch_norms():
+            for t in (bn.running_mean, bn.running_var):
+                if t is None:
+                    raise _lib.CamoError("update_running needs BatchNorm1d layers that track running statistics")
+                _lib.require_device(t, "RegionGraphGNN running statistics")
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                    raise _lib.CamoError("the running statistics must be contiguous fp32 buffers on the device of x: they are updated in place")
+                bufs.append(t)
+        return (C.c_void_p * 8)(*[t.data_ptr() for t in bufs]), bufs, float(mom.pop())
+
+    @torch.no_grad()
+    def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None,
+                               batch_stats=False, update_running=True, stats_out=None):
         """``loss_and_gradients`` on CSR arrays the caller built: ``csr`` = (rowptr, col, w) by target, ``reversed_csr`` the same
         for the graph with every edge turned round (both from ``build_target_csr_device``; they must hold the same edges).  One
         library call (``camo_rg_loss_backward``, include/camo_rg_train.h).  Returns (loss fp32 [4] = total, mask, instance, edge;
         list of 32 gradient tensors in ``trainable_parameters`` order, views of one buffer).  The result is a function of the
         arrays alone: two calls on the same arrays give the same bytes.  ``out``: a contiguous fp32 device buffer of exactly the
         flat layout's size (every piece rounded up to 64 floats) that receives the gradients instead of a new one; its padding is
-        not written."""
+        not written.
+
+        ``batch_stats=True``: the four batch norms normalise by the statistics of this call's nodes (``camo_rg_loss_backward_bn``,
+        include/camo_rg_train_bn.h) -- ``model.train()`` arithmetic without dropout; the four conv-bias gradients are then exactly
+        +0.  With ``update_running`` the modules' ``running_mean`` / ``running_var`` are updated in place with the modules'
+        ``momentum`` and ``num_batches_tracked`` goes up by one, on the device.  ``stats_out``: a contiguous fp32 device tensor
+        [4, 2, hidden] that receives the batch mean and biased variance of each layer.  With the default ``batch_stats=False``
+        neither of the two is looked at and nothing changes, whatever the module's mode."""
         _lib.require_device(x, "x")
         if x.dim() != 2 or x.shape[1] != self._dims.in_channels or x.shape[0] < 1:
             raise RuntimeError(f"x of shape {tuple(x.shape)} does not match in_channels {self._dims.in_channels}")
@@ -511,7 +541,22 @@ class RegionGraphGNN(nn.Module):
                 raise RuntimeError(f"{name} has {t.shape[0]} entries for {n} nodes")
             tg.append(t)
         wm, wi, we = (float(v) for v in loss_weights)
-        ws = _workspace("camo_rg_train_workspace_bytes", C.byref(self._dims), self.num_classes, n, E, device=dev)
+        if batch_stats:
+            if any(bn.eps != 1e-5 for bn in self._batch_norms()):
+                raise _lib.CamoError("batch-statistics batch norm on the MI355X path is built for eps = 1e-5 only")
+            if any(bn.momentum is None for bn in self._batch_norms()):
+                raise _lib.CamoError("batch-statistics batch norm on the MI355X path needs a float momentum (momentum=None, the "
+                                     "cumulative average, is not built)")
+            if n < 2:
+                raise _lib.CamoError("batch-statistics batch norm needs at least 2 nodes")
+            rtab, rkeep, momentum = self._running_table(dev) if update_running else (None, None, 0.0)
+            if stats_out is not None:
+                _lib.require_device(stats_out, "stats_out")
+                if stats_out.dtype != torch.float32 or tuple(stats_out.shape) != (4, 2, self._dims.hidden) or not stats_out.is_contiguous() \
+                        or stats_out.device != dev:
+                    raise RuntimeError(f"stats_out must be a contiguous fp32 tensor [4, 2, {self._dims.hidden}] on {dev}")
+        ws = _workspace("camo_rg_train_bn_workspace_bytes" if batch_stats else "camo_rg_train_workspace_bytes", C.byref(self._dims),
+                        self.num_classes, n, E, device=dev)
         params = self.trainable_parameters()
         total = sum(-(-p.numel() // 64) * 64 for p in params)                                                # (256-byte aligned pieces)
         if out is None:
@@ -530,6 +575,17 @@ class RegionGraphGNN(nn.Module):
         htab, hkeep = self._head_table()
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         with torch.cuda.device(dev):
+            if batch_stats:
+                rc = _lib.lib().camo_rg_loss_backward_bn(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
+                                                         _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
+                                                         _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab, momentum, rtab,
+                                                         None if stats_out is None else _ptr(stats_out), _stream_ptr(dev))
+                _lib.check(rc, "camo_rg_loss_backward_bn")
+                if update_running:
+                    for bn in self._batch_norms():
+                        if bn.num_batches_tracked is not None:
+                            bn.num_batches_tracked.add_(1)
+                return loss, grads
             rc = _lib.lib().camo_rg_loss_backward(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w),
                                                   _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi,
                                                   we, _ptr(ws), ws.numel(), _ptr(loss), gtab, _stream_ptr(dev))
@@ -537,7 +593,8 @@ class RegionGraphGNN(nn.Module):
         return loss, grads
 
     @torch.no_grad()
-    def loss_and_gradients(self, data, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), accumulate=False, csr=None):
+    def loss_and_gradients(self, data, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), accumulate=False, csr=None,
+                           batch_stats=False, update_running=True):
         """Loss on the three node heads and the gradient of every trainable parameter, with the BatchNorm layers on their running
         statistics and dropout off: eval-mode arithmetic (like ``node_probabilities``, whatever the module's mode) plus a backward --
         fine-tuning with frozen statistics (include/camo_rg_train.h).  ``data``: a ``RegionGraphData`` or ``RegionGraphBatch`` (the
@@ -549,7 +606,9 @@ class RegionGraphGNN(nn.Module):
         ``mask_loss``, ``instance_loss``, ``edge_loss``.  Both CSRs are built on the device and ONE library call does the rest; no
         host synchronisation.  ``csr``: the pair (CSR by target, CSR of the reversed graph) of an earlier
         ``build_target_csr_device`` of this graph, for a graph that is trained on again and again; the builder leaves a row's edges in
-        no particular order, so only calls on the same pair are sure to add in the same order and give the same bytes."""
+        no particular order, so only calls on the same pair are sure to add in the same order and give the same bytes.
+        ``batch_stats=True``: batch norm on the statistics of the call's nodes, the running statistics updated in place unless
+        ``update_running`` is false (see ``loss_and_gradients_csr``); a block-diagonal batch is one population."""
         x, edge_index = data.x, data.edge_index
         edge_attr = getattr(data, "edge_attr", None)
         _lib.require_device(x, "x")
@@ -559,7 +618,8 @@ class RegionGraphGNN(nn.Module):
         if csr is None:
             csr = (build_target_csr_device(n, edge_index, ew), build_target_csr_device(n, edge_index.flip(0), ew))
         csr, rcsr = csr
-        loss, grads = self.loss_and_gradients_csr(x, csr, rcsr, mask_target, instance_target, edge_target, loss_weights)
+        loss, grads = self.loss_and_gradients_csr(x, csr, rcsr, mask_target, instance_target, edge_target, loss_weights,
+                                                  batch_stats=batch_stats, update_running=update_running)
         for p, g in zip(self.trainable_parameters(), grads):
             g = g.to(p.dtype)
             if accumulate and p.grad is not None:

@@ -135,9 +135,16 @@ class RegionGraphFineTuner(AdamWStateMixin):
     so ``state_dict``, ``load_state_dict`` and every method of the model keep working; the flat gradient, first- and second-moment
     buffers are allocated once.  ``step`` is ``camo_rg_loss_backward`` into the flat gradient buffer, then ``camo_grad_sumsq`` and
     ``camo_clip_adamw`` over the flat buffers: ``torch.nn.utils.clip_grad_norm_(max_norm)`` followed by ``torch.optim.AdamW`` on the
-    32 parameters, with no host synchronisation.  The running statistics are buffers of the model and are never written."""
+    32 parameters, with no host synchronisation.  The running statistics are buffers of the model and are never written --
+    unless ``batch_norm="batch"``: a step is then ``camo_rg_loss_backward_bn`` (batch statistics, include/camo_rg_train_bn.h), which
+    updates the four layers' running statistics in place, the only thing outside the flat buffers that a step writes.
+    ``batch_norm="frozen"`` (the default) is the frozen path; any other value raises."""
 
-    def __init__(self, rg_model, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, loss_weights=(1.0, 1.0, 1.0)):
+    def __init__(self, rg_model, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, loss_weights=(1.0, 1.0, 1.0),
+                 batch_norm="frozen"):
+        if batch_norm not in ("frozen", "batch"):
+            raise ValueError(f'batch_norm must be "frozen" or "batch", got {batch_norm!r}')
+        self.batch_norm = batch_norm
         self.model = rg_model
         self.base_lr = self.lr = float(lr)
         self.weight_decay, self.betas, self.eps, self.max_norm = float(weight_decay), tuple(betas), float(eps), float(max_norm)
@@ -184,7 +191,8 @@ class RegionGraphFineTuner(AdamWStateMixin):
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         self._check_resident()
         loss, _ = self.model.loss_and_gradients_csr(batch.graphs.x, batch.csr, batch.reversed_csr, batch.mask_target, batch.instance_target,
-                                                    batch.edge_target, self.loss_weights, out=self.flat_grads)
+                                                    batch.edge_target, self.loss_weights, out=self.flat_grads,
+                                                    batch_stats=self.batch_norm == "batch")
         p, g, (m, v, ss) = self.flat_params, self.flat_grads, self._state()
         self.step_count += 1
         L = _lib.lib()

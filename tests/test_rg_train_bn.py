@@ -1,0 +1,516 @@
+"""Loss and gradients of the region-graph GNN with BATCH-STATISTICS batch norm (include/camo_rg_train_bn.h) against
+tests/rg_train_bn_ref.py.
+
+PARITY UNPINNED (the reference tree, torch_geometric and an RG checkpoint are absent): the header is the definition, the torch
+restatement the checker.  CPU tests tie the restatement's batch-norm step to torch.nn.functional.batch_norm(training=True), the rest of
+it to tests/rg_train_ref.py, the vanishing conv-bias gradients to float64 autograd, and the library's argument checks to the header.
+GPU tests hold the 28 gradients that are not zero by definition, the four loss figures, batch_stats (mean and biased variance of the
+four layers) and the eight updated running statistics to float64 with the project's rule,
+
+    e = max|g - g64| / max(max|g64|, 1e-12)  <=  8 e32 + 2e-6,
+
+e32 being the same error of torch-CPU float32 autograd of the same restatement, computed in the same test; the four conv-bias gradients
+are compared as bytes against +0.0.  Every case first asserts ON THE CPU REFERENCE that none of the nine pre-activation taps lies
+within 1e-4 max|tensor| of 0.  The seeds were found by a search on the CPU for that condition under batch statistics and are fixed;
+graphs, parameters and targets are drawn from the seed as tests/test_rg_train.py draws them.  No element is left out of a comparison.
+
+Under batch statistics the graphs of a block-diagonal batch DO see each other, but k copies of a set of graphs have the mean and the
+biased variance of one set, so copies keep the margin; "many" is 16 copies of three graphs (23 + 2 + 40 nodes) and a remainder of 40 + 2
+more, 1082 nodes, and its seed was searched with the remainder in place.
+
+Cases: "real" (23 nodes, hidden 128, heads 4), "tail" (70 rows: row blocks of 64 and 6, the unequal-count merge), "wide" (9 nodes,
+hidden 192: the CPL = 8 raw instantiations), "batch" (23 + 2 + 40), "many" (17 row blocks, 1082 % 64 = 58, a tenth of the mask and edge targets
+ignored per node), "offset" (the four conv biases at +32: nothing but running_mean changes in exact arithmetic, and a one-pass
+E[z^2] - mean^2 in float32 misses the bound, which a CPU test shows first) and "two" (N = 2, statistics only: the unbiased factor is 2).
+"""
+import copy
+import ctypes
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import rg_detect_ref as R
+import rg_train_bn_ref as BR
+import rg_train_ref as TR
+from conftest import ROOT
+from oracle import rg_gnn_oracle as RO
+from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _guarded, _guards_intact, _model, _targets
+
+BN_SIZES = (23, 2, 40)
+MANY_ORDER = (0, 1, 2) * 16 + (2, 1)
+OFFSET = 32.0                # "offset": at this value a float32 one-pass variance misses the bound (test_a_one_pass_variance_...)
+BIAS_NAMES = ("conv1.bias", "conv2.bias", "conv3.bias", "conv4.bias")
+STAT_NAMES = tuple(f"bn{k}.running_{s}" for k in (1, 2, 3, 4) for s in ("mean", "var"))       # the order of the `running` table
+
+# name: (graph kind, n, hidden, heads, classes, seed); flip margins on the float64 reference in the comments
+CASES = {
+    "real": ("grid", 23, 128, 4, 2, 45),             # 1.10e-4
+    "tail": ("grid", 70, 32, 1, 2, 720),             # 1.45e-4
+    "wide": ("grid", 9, 192, 2, 2, 224),             # 2.37e-4 (at hidden 192 a 23-node seed is one in thousands; 9 nodes: 3 blocks of the GCN kernel)
+    "batch": ("batch", 65, 32, 2, 2, 874),           # 1.27e-4
+    "many": ("many", 1082, 32, 2, 2, 616),           # 1.20e-4
+    "offset": ("grid", 23, 32, 2, 2, 17),            # 1.79e-4, with or without the offset
+}
+
+
+def _offset(p):
+    for k in BIAS_NAMES:
+        p[k] = np.full_like(p[k], OFFSET)
+
+
+OVERRIDES = {"offset": _offset}
+
+
+def _sizes(kind):
+    return {"batch": BN_SIZES, "many": tuple(BN_SIZES[k] for k in MANY_ORDER)}.get(kind)
+
+
+def _graph(kind, n, seed):
+    if kind == "grid":
+        return RO.make_graph(n, seed)
+    assert n == sum(_sizes(kind))
+    three = [RO.make_graph(m, seed + 10 * k) for k, m in enumerate(BN_SIZES)]
+    xs, eis, ews, off = [], [], [], 0
+    for k in (range(3) if kind == "batch" else MANY_ORDER):
+        gx, gei, gew = three[k]
+        xs.append(gx); eis.append(gei + off); ews.append(gew); off += gx.shape[0]
+    return np.concatenate(xs), np.concatenate(eis, 1), np.concatenate(ews)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """Inputs and both CPU references of a case, computed once; never written to."""
+    kind, n, hidden, heads, nc, seed = CASES[name]
+    p = dict(RO.make_params(seed, 15, hidden, heads))
+    p.update(R.make_head_params(seed + 1, hidden, nc))
+    if name in OVERRIDES:
+        OVERRIDES[name](p)
+    x, ei, ew = _graph(kind, n, seed)
+    rs = np.random.RandomState(seed + 1000)
+    mt = rs.randint(0, nc, size=n).astype(np.int32)
+    it = rs.randint(0, nc, size=n).astype(np.int32)
+    et = rs.uniform(0, 1, size=n).astype(np.float32)
+    if kind == "batch":
+        mt[[2, 23, 30]] = -1
+        et[[5, 40, 41, 63]] = -1.0
+    if kind == "many":                # per node over the whole batch, so the copies of a graph do not have equal gradients
+        mt[rs.uniform(size=n) < 0.1] = -1
+        et[rs.uniform(size=n) < 0.1] = -1.0
+        mt[1030], et[1040] = -1, -1.0   # (and among the nodes that are a thread's second in the loss kernel)
+    args = (p, x, ei, ew, mt, it, et, heads, nc)
+    l64, g64, margin, bs64, run64 = BR.loss_and_grads(*args)
+    l32, g32, _, bs32, run32 = BR.loss_and_grads(*args, dtype=torch.float32)
+    for a in list(p.values()) + [x, ei, ew, mt, it, et]:
+        a.setflags(write=False)
+    return dict(p=p, x=x, ei=ei, ew=ew, mt=mt, it=it, et=et, l64=l64, g64=g64, margin=margin, bs64=bs64, run64=run64, l32=l32, g32=g32,
+                bs32=bs32, run32=run32, hidden=hidden, heads=heads, nc=nc, n=n, sizes=_sizes(kind))
+
+
+@functools.lru_cache(maxsize=None)
+def _two():
+    """N = 2: two nodes joined both ways, hidden 32, heads 2.  Statistics only."""
+    seed, hidden, heads, nc = 5, 32, 2, 2
+    p = dict(RO.make_params(seed, 15, hidden, heads))
+    p.update(R.make_head_params(seed + 1, hidden, nc))
+    rs = np.random.RandomState(seed)
+    x = rs.uniform(0, 1, size=(2, 15)).astype(np.float32)
+    ei, ew = np.array([[0, 1], [1, 0]], np.int64), np.array([0.4, 0.4], np.float32)
+    mt, it, et = np.array([0, 1], np.int32), np.array([1, 1], np.int32), np.array([0.25, 1.0], np.float32)
+    args = (p, x, ei, ew, mt, it, et, heads, nc)
+    _, _, _, bs64, run64 = BR.loss_and_grads(*args, want_grads=False)
+    _, _, _, bs32, run32 = BR.loss_and_grads(*args, dtype=torch.float32, want_grads=False)
+    return dict(p=p, x=x, ei=ei, ew=ew, mt=mt, it=it, et=et, bs64=bs64, run64=run64, bs32=bs32, run32=run32, hidden=hidden, heads=heads,
+                nc=nc, n=2, sizes=None)
+
+
+def _bound(e32):
+    return 8 * e32 + 2e-6
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------------
+
+def test_the_batch_norm_step_is_torchs_training_batch_norm():
+    """(a) outputs and both running tensors equal torch.nn.functional.batch_norm(training=True, momentum=m) to 1e-12."""
+    rs = np.random.RandomState(0)
+    for n, c, m in ((2, 3, 0.1), (70, 32, 0.1), (23, 5, 1.0), (65, 8, 0.37)):
+        z = torch.tensor(rs.standard_normal((n, c)) * 3 + 1.5)
+        w, b = torch.tensor(rs.standard_normal(c)), torch.tensor(rs.standard_normal(c))
+        rm, rv = torch.tensor(rs.standard_normal(c)), torch.tensor(rs.uniform(0.5, 1.5, c))
+        y, mu, var, nm, nv = BR.bn_step(z, w, b, rm, rv, m)
+        tm, tv = rm.clone(), rv.clone()
+        want = torch.nn.functional.batch_norm(z, tm, tv, w, b, training=True, momentum=m, eps=BR.EPS)
+        assert float((y - want).abs().max()) <= 1e-12 and float((nm - tm).abs().max()) <= 1e-12 and float((nv - tv).abs().max()) <= 1e-12
+        assert float((mu - z.mean(0)).abs().max()) <= 1e-12 and float((var - z.var(0, unbiased=False)).abs().max()) <= 1e-12
+
+
+def test_with_its_statistics_in_the_running_slots_the_frozen_restatement_agrees():
+    """(b) rg_train_ref.forward on the float64 mu, var of the batch restatement gives the batch restatement's logits to 1e-12."""
+    for name in ("real", "tail", "batch"):
+        c = _case(name)
+        src, dst, w = RO.with_self_loops(c["n"], c["ei"], c["ew"])
+        P = {k: torch.tensor(v, dtype=torch.float64) for k, v in c["p"].items()}
+        a = (torch.tensor(c["x"], dtype=torch.float64), torch.tensor(src), torch.tensor(dst), torch.tensor(w, dtype=torch.float64), c["heads"])
+        taps, st = [], {}
+        logits = BR.forward(P, *a, taps=taps, stats=st)
+        assert len(taps) == 9                                                            # s, bn1..4, fc_shared, three heads
+        for k in (1, 2, 3, 4):
+            P[f"bn{k}.running_mean"], P[f"bn{k}.running_var"] = st["mu"][k - 1], st["var"][k - 1]
+        frozen = TR.forward(P, *a)
+        assert float((logits - frozen).abs().max()) <= 1e-12, name
+        bs, _ = BR.stats_arrays(st)
+        assert np.array_equal(bs, c["bs64"])
+
+
+def test_the_conv_bias_gradients_vanish_in_float64():
+    """(c) the four conv biases cancel against the batch mean: <= 1e-12 x the largest gradient of the case."""
+    for name in ("real", "tail", "batch", "offset"):
+        g = _case(name)["g64"]
+        top = max(float(np.abs(v).max()) for v in g.values())
+        for k in BIAS_NAMES:
+            assert float(np.abs(g[k]).max()) <= 1e-12 * top, (name, k)
+        assert min(float(np.abs(g[k]).max()) for k in NAMES if k not in BIAS_NAMES) > 1e-6 * top     # the other 28 are gradients
+
+
+def test_header_symbols_binding_and_abi_version():
+    """(d)"""
+    from camouflage_multimodal_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "camo_rg_train_bn.h")).read()
+    declared = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr)) - {"camo_last_error"}
+    assert declared == set(_lib.RGTBN_SYMBOLS), declared ^ set(_lib.RGTBN_SYMBOLS)
+    assert "PARITY UNPINNED" in hdr and "train.py" in hdr and "+0.0f" in hdr
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for s in declared:
+        assert hasattr(raw, s), s
+    assert _lib.RGT_SYMBOLS == ("camo_rg_train_workspace_bytes", "camo_rg_loss_backward")
+    assert _lib.ABI_VERSION == 13 and _lib.lib().camo_abi_version() == 13
+
+
+def test_argument_checks_match_the_header():
+    """(e)"""
+    from camouflage_multimodal_amd import _lib
+    L = _lib.lib()
+    fake = 0x1000                                    # never dereferenced: every check runs on the host before any launch
+    tabs = [(ctypes.c_void_p * n)(*([fake] * n)) for n in (28, 12, 32, 8)]
+    running_slots = (6, 7, 12, 13, 18, 19, 24, 25)
+
+    def call(hidden=128, nc=2, N=23, E=100, ws_bytes=None, null=None, heads=4, momentum=0.1, running=True, table_null=None, stats=True):
+        d = _lib.CamoRgDims(15, hidden, heads)
+        need = L.camo_rg_train_bn_workspace_bytes(ctypes.byref(d), nc, N, E)
+        ptr = {k: fake for k in ("x", "rowptr", "col", "w", "rrowptr", "rcol", "rw", "mt", "it", "et", "ws", "loss")}
+        t = list(tabs)
+        if null in ptr:
+            ptr[null] = None
+        if null in ("params", "heads", "grads"):
+            t[("params", "heads", "grads").index(null)] = None
+        if table_null == "grads":
+            t[2] = (ctypes.c_void_p * 32)(*([fake] * 31 + [None]))
+        if table_null == "running":
+            t[3] = (ctypes.c_void_p * 8)(*([fake] * 7 + [None]))
+        if table_null == "running slots of params":
+            t[0] = (ctypes.c_void_p * 28)(*[None if i in running_slots else fake for i in range(28)])
+        if table_null == "params":
+            t[0] = (ctypes.c_void_p * 28)(*[None if i == 5 else fake for i in range(28)])
+        rc = L.camo_rg_loss_backward_bn(ctypes.byref(d), nc, t[0], t[1], ptr["x"], ptr["rowptr"], ptr["col"], ptr["w"], ptr["rrowptr"],
+                                        ptr["rcol"], ptr["rw"], N, E, ptr["mt"], ptr["it"], ptr["et"], 1.0, 1.0, 1.0, ptr["ws"],
+                                        need if ws_bytes is None else ws_bytes, ptr["loss"], t[2], momentum, t[3] if running else None,
+                                        fake if stats else None, None)
+        return rc, need
+
+    E_ARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
+    assert call(N=1, E=1) == (E_UNSUPPORTED, 0)
+    msg = L.camo_last_error()
+    assert b"N >= 2" in msg and b"E >= N" in msg and b"hidden even" in msg and b"heads" in msg                     # the whole condition
+    assert call(hidden=127) == (E_UNSUPPORTED, 0) and call(hidden=514) == (E_UNSUPPORTED, 0) and call(heads=9) == (E_UNSUPPORTED, 0)
+    assert call(nc=1) == (E_UNSUPPORTED, 0) and call(nc=9) == (E_UNSUPPORTED, 0) and call(N=23, E=22) == (E_UNSUPPORTED, 0)
+    for m in (0.0, 1.5, float("nan"), -0.1, float("inf")):
+        assert call(momentum=m)[0] == E_ARG, m
+        assert b"momentum" in L.camo_last_error()
+        assert call(momentum=m, running=False, ws_bytes=8)[0] == E_WORKSPACE, m           # without `running` momentum is not looked at
+    rc, need = call(ws_bytes=1024)
+    assert rc == E_WORKSPACE and need > 1024 and call(ws_bytes=need - 1)[0] == E_WORKSPACE
+    for name in ("x", "rowptr", "col", "w", "rrowptr", "rcol", "rw", "mt", "it", "et", "ws", "loss", "params", "heads", "grads"):
+        assert call(null=name)[0] == E_ARG, name
+    assert call(table_null="grads")[0] == E_ARG and b"gradient table" in L.camo_last_error()
+    assert call(table_null="running")[0] == E_ARG and b"running" in L.camo_last_error()
+    assert call(table_null="params")[0] == E_ARG and b"parameter table" in L.camo_last_error()
+    assert call(table_null="running slots of params", ws_bytes=8)[0] == E_WORKSPACE      # the running slots of params are not read: null passes
+    assert call(running=False, stats=False, ws_bytes=8)[0] == E_WORKSPACE                  # running and batch_stats may be null
+    d = _lib.CamoRgDims(15, 128, 4)
+    frozen = L.camo_rg_train_workspace_bytes(ctypes.byref(d), 2, 23, 100)
+    assert L.camo_rg_train_bn_workspace_bytes(ctypes.byref(d), 2, 23, 100) == frozen + 256 * -(-4 * 2 * 128 * 4 // 256)   # 4 * 2 * C floats more
+    assert L.camo_rg_train_bn_workspace_bytes(None, 2, 23, 100) == 0 and L.camo_rg_train_bn_workspace_bytes(ctypes.byref(d), 2, 1, 1) == 0
+
+
+def test_cpu_tensors_and_unsupported_modules_raise():
+    from camouflage_multimodal_amd import RegionGraphData, RegionGraphFineTuner, RegionGraphGNN
+    from camouflage_multimodal_amd._lib import CamoError
+    c = _case("batch")
+    m = RegionGraphGNN(hidden_channels=32, num_classes=2, heads=2)
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    data = RegionGraphData(torch.from_numpy(c["x"].copy()), torch.from_numpy(c["ei"].copy()), torch.from_numpy(c["ew"].copy())[:, None])
+    with pytest.raises(CamoError):
+        m.loss_and_gradients(data, torch.from_numpy(c["mt"].copy()), torch.from_numpy(c["it"].copy()), torch.from_numpy(c["et"].copy()),
+                             batch_stats=True)
+    assert all(p.grad is None for p in m.parameters())
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, before[k]), k
+    with pytest.raises(ValueError, match="batch_norm"):
+        RegionGraphFineTuner(m, batch_norm="running")
+    assert RegionGraphFineTuner(m).batch_norm == "frozen" and RegionGraphFineTuner(m, batch_norm="batch").batch_norm == "batch"
+    with pytest.raises(CamoError, match="training mode"):
+        m.train()(data)                                                                   # forward in training mode keeps raising
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_cases_stay_clear_of_a_relu_flip(name):
+    assert _case(name)["margin"] > BR.FLIP_MARGIN, (name, _case(name)["margin"])
+
+
+def test_the_cases_are_where_they_claim_to_be():
+    c = _case("many")
+    n = c["n"]
+    assert n == c["x"].shape[0] == 1082 > 1024 and n % 64 == 58 and -(-n // 64) == 17 and len(c["sizes"]) == 50
+    for k in ("mt", "et"):
+        assert 60 < int((c[k] < 0).sum()) < 160 and (c[k][:1024] < 0).any() and (c[k][1024:] < 0).any(), k
+    assert not np.array_equal(c["mt"][:65], c["mt"][65:130])                                    # the copies differ in their targets
+    assert _case("tail")["n"] == 70 == 64 + 6 and _case("wide")["hidden"] == 192 > 128 and _case("wide")["n"] == 9
+    # 16 copies of a set of graphs have the mean and the biased variance of one set: the margin of the copies is the margin of the set
+    kind, _, hidden, heads, nc, seed = CASES["batch"]
+    b = _case("batch")
+    three = [RO.make_graph(m, seed + 10 * k) for k, m in enumerate(BN_SIZES)]
+    xs, eis, ews, off = [], [], [], 0
+    for k in (0, 1, 2) * 16:
+        gx, gei, gew = three[k]
+        xs.append(gx); eis.append(gei + off); ews.append(gew); off += gx.shape[0]
+    z = np.zeros(off, np.int32)
+    _, _, margin, bs, _ = BR.loss_and_grads(b["p"], np.concatenate(xs), np.concatenate(eis, 1), np.concatenate(ews), z, z, z.astype(np.float32),
+                                            heads, nc, want_grads=False)
+    assert off == 1040 and abs(margin - b["margin"]) <= 1e-9 * b["margin"] and np.abs(bs - b["bs64"]).max() <= 1e-12
+    # "offset" is "the same case" but for running_mean: same margin, same statistics but the mean, same gradients
+    kind, n, hidden, heads, nc, seed = CASES["offset"]
+    p = dict(RO.make_params(seed, 15, hidden, heads)); p.update(R.make_head_params(seed + 1, hidden, nc))
+    o = _case("offset")
+    _, g, margin, bs, _ = BR.loss_and_grads(p, o["x"], o["ei"], o["ew"], o["mt"], o["it"], o["et"], heads, nc)
+    assert abs(margin - o["margin"]) <= 1e-6 * margin and np.abs(bs[:, 1] - o["bs64"][:, 1]).max() <= 1e-9
+    assert np.abs(o["bs64"][:, 0]).min() > OFFSET - 5 and all(_err(o["g64"][k], g[k]) <= 1e-9 for k in NAMES if k not in BIAS_NAMES)
+
+
+def test_a_one_pass_variance_in_float32_misses_the_bound_on_offset():
+    """What "offset" is for: the float32 restatement with var = E[z^2] - mean^2 is outside 8 e32 + 2e-6 at OFFSET = 32 (statistics and
+    gradients), where the float32 restatement with centred squares defines e32.  A kernel that took the one-pass form would fail."""
+    c = _case("offset")
+    _, g1, _, bs1, _ = BR.loss_and_grads(c["p"], c["x"], c["ei"], c["ew"], c["mt"], c["it"], c["et"], c["heads"], c["nc"], dtype=torch.float32,
+                                         one_pass=True)
+    miss = []
+    for k in range(4):
+        e, e32 = _err(bs1[k, 1], c["bs64"][k, 1]), _err(c["bs32"][k, 1], c["bs64"][k, 1])
+        print(f"one-pass var of layer {k + 1}: e {e:.3g} e32 {e32:.3g}")
+        miss.append(e > _bound(e32))
+    gm = [k for k in NAMES if k not in BIAS_NAMES and _err(g1[k], c["g64"][k]) > _bound(_err(c["g32"][k], c["g64"][k]))]
+    print("gradients a one-pass variance puts outside the bound:", len(gm))
+    assert all(miss) and len(gm) >= 1
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------
+
+LOSS_KEYS = ("loss", "mask_loss", "instance_loss", "edge_loss")
+
+
+def _hold_stats(c, bs, running, tag):
+    """batch_stats [4, 2, C] and the 8 updated running statistics within the bound; returns (largest e, largest e32)."""
+    worst, worst32 = 0.0, 0.0
+    for k in range(4):
+        for j, what in enumerate(("mean", "var")):
+            e, e32 = _err(bs[k, j], c["bs64"][k, j]), _err(c["bs32"][k, j], c["bs64"][k, j])
+            print(f"{tag} batch {what} of bn{k + 1}: e {e:.3g} e32 {e32:.3g}")
+            worst, worst32 = max(worst, e), max(worst32, e32)
+            assert e <= _bound(e32), (tag, k, what, e, e32)
+    for k in STAT_NAMES:
+        e, e32 = _err(running[k], c["run64"][k]), _err(c["run32"][k], c["run64"][k])
+        print(f"{tag} {k}: e {e:.3g} e32 {e32:.3g}")
+        worst, worst32 = max(worst, e), max(worst32, e32)
+        assert e <= _bound(e32), (tag, k, e, e32)
+    return worst, worst32
+
+
+def _hold(c, loss4, grads, bs, running, tag):
+    worst, worst32 = _hold_stats(c, bs, running, tag)
+    for i, k in enumerate(LOSS_KEYS):
+        e, e32 = _err(loss4[i], c["l64"][i]), _err(c["l32"][i], c["l64"][i])
+        print(f"{tag} {k}: e {e:.3g} e32 {e32:.3g}")
+        worst, worst32 = max(worst, e), max(worst32, e32)
+        assert e <= _bound(e32), (tag, k, e, e32)
+    for k in NAMES:
+        assert grads[k].shape == c["g64"][k].shape, k
+        if k in BIAS_NAMES:
+            assert not _bits(grads[k]).any(), (tag, k)                                     # every element is +0.0f, bit for bit
+            continue
+        e, e32 = _err(grads[k], c["g64"][k]), _err(c["g32"][k], c["g64"][k])
+        print(f"{tag} {k}: e {e:.3g} e32 {e32:.3g}")
+        worst, worst32 = max(worst, e), max(worst32, e32)
+        assert e <= _bound(e32), (tag, k, e, e32)
+    print(f"{tag}: largest e {worst:.3g}, largest e32 {worst32:.3g}, largest e / e32 over the case {worst / worst32:.3g}")
+
+
+def _running(m):
+    sd = m.state_dict()
+    return {k: sd[k].detach().cpu().numpy() for k in STAT_NAMES}
+
+
+def _call(m, c, d, csr=None, update_running=True):
+    """(loss [4] tensor, list of gradient tensors, batch_stats tensor) of one batch-statistics call on m"""
+    csr, rcsr = csr if csr is not None else _csr_pair(c, d)
+    bs = torch.full((4, 2, c["hidden"]), float("nan"), device="cuda")
+    loss, grads = m.loss_and_gradients_csr(d.x, csr, rcsr, *_targets(c), batch_stats=True, update_running=update_running, stats_out=bs)
+    return loss, grads, bs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["real", "tail", "wide", "batch", "many", "offset"])
+def test_gradients_and_statistics_match_float64(name):
+    c = _case(name)
+    assert c["margin"] > BR.FLIP_MARGIN                       # on the CPU reference, before the device is looked at
+    m, d = _model(c).train(), _data(c)
+    loss, grads, bs = _call(m, c, d)
+    loss4 = loss.cpu().numpy().tolist()
+    assert all(np.isfinite(v) for v in loss4), loss4
+    _hold(c, loss4, {k: g.cpu().numpy() for k, g in zip(NAMES, grads)}, bs.cpu().numpy(), _running(m), name)
+
+
+@pytest.mark.gpu
+def test_two_nodes_statistics():
+    """N = 2: batch_stats and the running update (unbiased factor 2).  They are continuous in the inputs: no flip-clear seed needed."""
+    c = _two()
+    m, d = _model(c).train(), _data(c)
+    loss, grads, bs = _call(m, c, d)
+    assert bool(torch.isfinite(loss).all()) and all(bool(torch.isfinite(g).all()) for g in grads)
+    _hold_stats(c, bs.cpu().numpy(), _running(m), "two")
+    got, before = _running(m), c["p"]
+    for k in (1, 2, 3, 4):                                     # the running variance moved by 0.1 (2 var_biased - old), on the device's own figures
+        want = 0.9 * before[f"bn{k}.running_var"].astype(np.float64) + 0.1 * 2.0 * bs[k - 1, 1].cpu().numpy().astype(np.float64)
+        assert _err(got[f"bn{k}.running_var"], want) <= 1e-6, k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["real", "many"])
+def test_two_calls_on_the_same_csr_give_the_same_bytes(name):
+    c = _case(name)
+    d = _data(c)
+    pair = _csr_pair(c, d)
+    m1, m2 = _model(c).train(), _model(c).train()              # the running statistics are updated on copies
+    l1, g1, b1 = _call(m1, c, d, pair)
+    l2, g2, b2 = _call(m2, c, d, pair)
+    assert np.array_equal(_bits(l1.cpu()), _bits(l2.cpu())) and np.array_equal(_bits(b1.cpu()), _bits(b2.cpu()))
+    for k, a, b in zip(NAMES, g1, g2):
+        assert np.array_equal(_bits(a.cpu()), _bits(b.cpu())), k
+    r1, r2 = _running(m1), _running(m2)
+    for k in STAT_NAMES:
+        assert np.array_equal(_bits(r1[k]), _bits(r2[k])) and not np.array_equal(_bits(r1[k]), _bits(c["p"][k])), k
+
+
+@pytest.mark.gpu
+def test_update_running_and_the_default_leave_what_they_should():
+    c = _case("batch")
+    m, d = _model(c).train(), _data(c)
+    pair = _csr_pair(c, d)
+    state = {k: v.clone() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k}
+    assert len(state) == 12
+
+    def same():
+        return all(np.array_equal(v.cpu().numpy().reshape(-1).view(np.uint8), state[k].cpu().numpy().reshape(-1).view(np.uint8))
+                   for k, v in m.state_dict().items() if k in state)
+
+    l0, g0, _ = _call(m, c, d, pair, update_running=False)
+    assert same()
+    m.loss_and_gradients(d, *_targets(c), csr=pair, batch_stats=True, update_running=False)
+    assert same() and all(np.array_equal(_bits(p.grad.cpu()), _bits(g.cpu())) for p, g in zip(m.trainable_parameters(), g0))
+    # the default is the frozen call, whatever the mode: the bytes of a model that never saw the keyword
+    frozen = _model(c).eval().loss_and_gradients_csr(d.x, *pair, *_targets(c))
+    got = m.loss_and_gradients_csr(d.x, *pair, *_targets(c))
+    assert same() and np.array_equal(_bits(frozen[0].cpu()), _bits(got[0].cpu()))
+    assert all(np.array_equal(_bits(a.cpu()), _bits(b.cpu())) for a, b in zip(frozen[1], got[1]))
+    for step in (1, 2):
+        out = m.loss_and_gradients(d, *_targets(c), csr=pair, batch_stats=True)
+        assert set(out) == set(LOSS_KEYS) and all(v.dim() == 0 and v.is_cuda for v in out.values())
+        sd = m.state_dict()
+        for k in (1, 2, 3, 4):
+            assert int(sd[f"bn{k}.num_batches_tracked"]) == int(state[f"bn{k}.num_batches_tracked"]) + step
+    assert not same()
+    # the limits are named
+    from camouflage_multimodal_amd._lib import CamoError
+    m.bn3.momentum = None
+    with pytest.raises(CamoError, match="momentum"):
+        _call(m, c, d, pair)
+    m.bn3.momentum, m.bn2.eps = 0.1, 1e-3
+    with pytest.raises(CamoError, match="eps"):
+        _call(m, c, d, pair)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["tail", "batch"])
+def test_the_frozen_call_on_the_batch_statistics_gives_the_same_losses(name):
+    """batch_stats (biased variance) copied into the running buffers, then the frozen call on the same inputs: its four loss figures
+    agree with the batch call's within twice the bound, both being within the bound of one float64 number."""
+    c = _case(name)
+    m, d = _model(c).train(), _data(c)
+    pair = _csr_pair(c, d)
+    lb, _, bs = _call(m, c, d, pair, update_running=False)
+    with torch.no_grad():
+        for k, bn in enumerate((m.bn1, m.bn2, m.bn3, m.bn4)):
+            bn.running_mean.copy_(bs[k, 0]); bn.running_var.copy_(bs[k, 1])
+    lf, _ = m.loss_and_gradients_csr(d.x, *pair, *_targets(c))
+    lb, lf = lb.cpu().numpy().astype(np.float64), lf.cpu().numpy().astype(np.float64)
+    for i, k in enumerate(LOSS_KEYS):
+        e32 = _err(c["l32"][i], c["l64"][i])
+        eb, ef = _err(lb[i], c["l64"][i]), _err(lf[i], c["l64"][i])
+        print(f"{name} {k}: batch e {eb:.3g} frozen e {ef:.3g} e32 {e32:.3g}")
+        assert eb <= _bound(e32) and ef <= _bound(e32) and abs(lb[i] - lf[i]) <= 2 * _bound(e32) * abs(c["l64"][i]), (k, eb, ef, e32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["many", "tail"])
+def test_the_library_writes_inside_its_workspace_and_its_output_buffers(name):
+    """camo_rg_loss_backward_bn called directly on a workspace of exactly camo_rg_train_bn_workspace_bytes and on 32 gradient buffers,
+    loss, batch_stats and the 8 running buffers of exactly their sizes, each between two 4 KiB bands of a sentinel: no guard byte
+    changes, every output element is written (the outputs start as NaN; the running buffers start as the model's), and the bytes are
+    the wrapper's."""
+    from camouflage_multimodal_amd import _lib
+    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
+    c = _case(name)
+    m, d, t = _model(c).train(), _data(c), _targets(c)
+    csr, rcsr = _csr_pair(c, d)
+    other = copy.deepcopy(m)
+    want_loss, want, want_bs = _call(other, c, d, (csr, rcsr))
+    want_run = [other.state_dict()[k] for k in STAT_NAMES]
+    L, n, E, C = _lib.lib(), c["n"], csr[1].shape[0], c["hidden"]
+    need = L.camo_rg_train_bn_workspace_bytes(ctypes.byref(m._dims), c["nc"], n, E)
+    assert need > 0
+    ws_whole, ws = _guarded(need, 0xA5)
+    outs = [_guarded(4 * k, 0xFF) for k in [p.numel() for p in m.trainable_parameters()] + [4, 4 * 2 * C]]
+    assert all(bool(torch.isnan(piece.view(torch.float32)).all()) for _, piece in outs)
+    runs = [_guarded(4 * C, 0xFF) for _ in STAT_NAMES]
+    for (_, piece), k in zip(runs, STAT_NAMES):
+        piece.view(torch.float32).copy_(m.state_dict()[k])
+    tab, keep = m._param_table()
+    htab, hkeep = m._head_table()
+    gtab = (ctypes.c_void_p * 32)(*[piece.data_ptr() for _, piece in outs[:32]])
+    rtab = (ctypes.c_void_p * 8)(*[piece.data_ptr() for _, piece in runs])
+    x = d.x.contiguous()
+    _lib.check(L.camo_rg_loss_backward_bn(ctypes.byref(m._dims), c["nc"], tab, htab, _ptr(x), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]),
+                                          _ptr(rcsr[0]), _ptr(rcsr[1]), _ptr(rcsr[2]), n, E, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), 1.0, 1.0, 1.0,
+                                          _ptr(ws), need, _ptr(outs[32][1]), gtab, m.bn1.momentum, rtab, _ptr(outs[33][1]), _stream_ptr()),
+               "camo_rg_loss_backward_bn")
+    torch.cuda.synchronize()
+    assert _guards_intact(ws_whole, ws, 0xA5), "workspace"
+    refs = list(want) + [want_loss, want_bs] + want_run
+    for k, (whole, piece), ref in zip(NAMES + ["loss", "batch_stats"] + list(STAT_NAMES), outs + runs, refs):
+        assert _guards_intact(whole, piece, 0xFF), k
+        got = piece.view(torch.float32)
+        assert bool(torch.isfinite(got).all()), k
+        assert np.array_equal(_bits(got.cpu()), _bits(ref.reshape(-1).cpu())), k
+    for k, v in m.state_dict().items():                       # the model whose tables were passed was not written: `running` was
+        assert torch.equal(v.cpu(), torch.from_numpy(c["p"][k].copy())) if k in c["p"] else int(v) == 0, k

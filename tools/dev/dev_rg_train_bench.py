@@ -1,7 +1,7 @@
 """Developer aid / measurement of the Region-Graph GNN's loss and gradients with frozen batch norm: one
 loss_and_gradients call against extract_node_embeddings + node_heads on the same graphs, in the same run, at 16 and at 128 graphs of
-~410 nodes.
-  python tools/dev/dev_rg_train_bench.py [graphs_per_batch ...]"""
+~410 nodes.  --bn adds the batch-statistics call (running statistics updated) beside the frozen one, in the same run.
+  python tools/dev/dev_rg_train_bench.py [--bn] [graphs_per_batch ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -18,8 +18,9 @@ def timed(fn, it=30, warm=5):
     return (time.perf_counter() - t0) / it
 
 
+BN = "--bn" in sys.argv[1:]
 m = RegionGraphGNN().cuda().eval()
-for G in [int(a) for a in sys.argv[1:]] or [16, 128]:
+for G in [int(a) for a in sys.argv[1:] if a != "--bn"] or [16, 128]:
     gs = [RO.make_graph(int(n), seed=i) for i, n in enumerate(np.random.RandomState(0).randint(303, 518, size=G))]
     off = np.cumsum([0] + [g[0].shape[0] for g in gs])
     x = torch.from_numpy(np.concatenate([g[0] for g in gs])).cuda()
@@ -34,3 +35,6 @@ for G in [int(a) for a in sys.argv[1:]] or [16, 128]:
     trn = timed(lambda: m.loss_and_gradients(data, mt, it_, et))
     print(f"{G} graphs / {N} nodes / {ei.shape[1] + N} CSR entries: forward (embeddings + heads) {fwd * 1e6:.1f} us, "
           f"loss_and_gradients {trn * 1e6:.1f} us = {trn / fwd:.2f} x the forward (both include their CSR builds)")
+    if BN:
+        bn = timed(lambda: m.loss_and_gradients(data, mt, it_, et, batch_stats=True))
+        print(f"    with batch statistics {bn * 1e6:.1f} us = {bn / trn:.2f} x the frozen call, + {(bn - trn) * 1e6:.1f} us")
