@@ -1,4 +1,4 @@
-"""ctypes binding of include/camo_fusion.h.
+"""ctypes binding of the headers under include/.
 
 There is no CPU fallback: if the shared library is missing or the tensors are
 not on a HIP device the callers raise.  Build with
@@ -21,36 +21,12 @@ FUSION_CROSS_ATTENTION, FUSION_LATE = 0, 1
 PREC_F32, PREC_BF16 = 0, 1
 NPARAMS_CROSS, NPARAMS_LATE = 44, 22
 
-# every symbol include/camo_fusion.h declares
-SYMBOLS = ("camo_abi_version", "camo_last_error", "camo_workspace_bytes", "camo_batch_desc_bytes", "camo_prepare_batch", "camo_gather_batch", "camo_forward", "camo_forward_cached", "camo_backward", "camo_forward_loss_backward",
-           "camo_loss", "camo_grad_sumsq", "camo_clip_adamw", "camo_shadow_bytes", "camo_clip_adamw_shadows", "camo_debug_gemm", "camo_debug_gemm16", "camo_debug_ws_offset", "camo_debug_plan",
-           "camo_options_init", "camo_options_set", "camo_debug_set_stamps", "camo_prof_begin", "camo_prof_end", "camo_prof_kind", "camo_tail_timeouts", "camo_tail_poison_to_grads")
-
-
-# every symbol include/camo_rg_gnn.h declares
-RG_SYMBOLS = ("camo_rg_workspace_bytes", "camo_rg_node_embeddings", "camo_rg_build_csr")
-# every symbol include/camo_rg_features.h declares
-RGF_SYMBOLS = ("camo_rg_graph_workspace_bytes", "camo_rg_region_graph")
-# every symbol include/camo_rg_batch.h declares
-RGB_SYMBOLS = ("camo_rg_batch_workspace_bytes", "camo_rg_region_graph_batch")
 RGB_TILE_SLOTS = 64                 # CAMO_RGB_TILE_SLOTS
 RGB_VAR_BOUND = 3.0 * 2.0 ** -37    # CAMO_RGB_VAR_BOUND
-# every symbol include/camo_canny.h declares
-CANNY_SYMBOLS = ("camo_canny_workspace_bytes", "camo_canny", "camo_canny_hysteresis")
-# every symbol include/camo_slic.h declares
-SLIC_SYMBOLS = ("camo_slic_grid", "camo_slic_workspace_bytes", "camo_slic", "camo_slic_preprocess", "camo_slic_assign", "camo_slic_update", "camo_slic_connect")
-# every symbol include/camo_rg_detect.h declares
-RGD_SYMBOLS = ("camo_rg_node_heads", "camo_rg_paint", "camo_seg_counts")
 RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
 RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
 RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
-# every symbol include/camo_rg_train.h declares
-RGT_SYMBOLS = ("camo_rg_train_workspace_bytes", "camo_rg_loss_backward")
 RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
-# every symbol include/camo_rg_train_bn.h declares
-RGTBN_SYMBOLS = ("camo_rg_train_bn_workspace_bytes", "camo_rg_loss_backward_bn")
-# every symbol include/camo_rg_targets.h declares
-RGTG_SYMBOLS = ("camo_rg_node_targets",)
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -94,6 +70,95 @@ class CamoPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in PLAN_FIELDS]
 
 
+vp, i32, i64, u64, f32, f64, sz, P = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t, C.POINTER
+dims, rgdims = P(CamoDims), P(CamoRgDims)
+
+# THE restatement of include/*.h: header -> (name, restype, argtypes) of every function it declares, in the header's order.
+# lib() binds from it and tests/test_abi_binding.py holds it to the headers' text (names, return types, every argument, the structs above).
+PROTOTYPES = {
+    "camo_fusion.h": (
+        ("camo_abi_version", i32, ()),
+        ("camo_last_error", C.c_char_p, ()),
+        ("camo_workspace_bytes", sz, (dims, i32, i32, i32)),
+        ("camo_batch_desc_bytes", sz, (i32, i32)),
+        ("camo_prepare_batch", i32, (vp, i32, i32, i32, vp, sz, vp)),
+        ("camo_gather_batch", i32, (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, u64, vp)),
+        ("camo_forward", i32, (dims, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, i32, u64, i32, i32, vp)),
+        ("camo_forward_cached", i32, (dims, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, i32, u64, i32, i32, vp, i32, P(i32), vp)),
+        ("camo_backward", i32, (dims, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, i32, i32, u64, i32, i32, vp)),
+        ("camo_loss", i32, (vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp)),
+        ("camo_grad_sumsq", i32, (vp, sz, vp, vp)),
+        ("camo_clip_adamw", i32, (vp, vp, vp, vp, sz, vp, f32, f32, f32, f32, f32, f32, i32, i32, vp)),
+        ("camo_shadow_bytes", sz, (dims,)),
+        ("camo_clip_adamw_shadows", i32, (dims, vp, vp, vp, vp, vp, sz, vp, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp)),
+        ("camo_forward_loss_backward", i32, (dims, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp, vp, i32, u64, i32, vp, vp, i32, vp)),
+        ("camo_debug_gemm", i32, (vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp)),
+        ("camo_debug_gemm16", i32, (vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp)),
+        ("camo_debug_ws_offset", i64, (dims, i32, i32, i32, C.c_char_p)),
+        ("camo_debug_plan", i32, (dims, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(CamoPlan))),
+        ("camo_options_init", i32, (P(CamoOptions),)),
+        ("camo_options_set", i32, (P(CamoOptions), C.c_char_p, i32)),
+        ("camo_debug_set_stamps", i32, (vp, i32)),
+        ("camo_prof_begin", i32, (i32,)),
+        ("camo_prof_end", i32, (P(f64), P(i32), P(f64))),
+        ("camo_prof_kind", i32, (i32, P(f64), P(i32), P(f64))),
+        ("camo_tail_timeouts", i32, (vp,)),
+        ("camo_tail_poison_to_grads", i32, (vp, vp)),
+    ),
+    "camo_rg_gnn.h": (
+        ("camo_rg_workspace_bytes", sz, (rgdims, i32)),
+        ("camo_rg_build_csr", i32, (vp, vp, i32, i32, vp, vp, vp, vp, vp)),
+        ("camo_rg_node_embeddings", i32, (rgdims, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp)),
+    ),
+    "camo_rg_features.h": (
+        ("camo_rg_graph_workspace_bytes", sz, (i32,)),
+        ("camo_rg_region_graph", i32, (vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, i32, vp, vp)),
+    ),
+    "camo_rg_batch.h": (
+        ("camo_rg_batch_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_rg_region_graph_batch", i32, (vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp)),
+    ),
+    "camo_canny.h": (
+        ("camo_canny_workspace_bytes", sz, (i32, i32, i32)),
+        ("camo_canny", i32, (vp, i32, i32, i32, f32, f32, f32, vp, sz, vp, vp, vp)),
+        ("camo_canny_hysteresis", i32, (vp, i32, i32, i32, vp, sz, vp, vp)),
+    ),
+    "camo_slic.h": (
+        ("camo_slic_grid", i32, (i32, i32, i32, P(i32))),
+        ("camo_slic_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_slic", i32, (vp, i32, i32, i32, i32, f32, f32, vp, sz, vp, vp, vp)),
+        ("camo_slic_preprocess", i32, (vp, i32, i32, i32, f32, f32, vp, vp)),
+        ("camo_slic_assign", i32, (vp, vp, i32, i32, i32, i32, i32, vp, vp, vp)),
+        ("camo_slic_update", i32, (vp, vp, i32, i32, i32, i32, vp, vp, vp)),
+        ("camo_slic_connect", i32, (vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp)),
+    ),
+    "camo_rg_detect.h": (
+        ("camo_rg_node_heads", i32, (rgdims, i32, vp, vp, i32, vp, vp, vp)),
+        ("camo_rg_paint", i32, (vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp)),
+        ("camo_seg_counts", i32, (vp, i64, vp, f32, i32, i32, i32, vp, vp)),
+    ),
+    "camo_rg_train.h": (
+        ("camo_rg_train_workspace_bytes", sz, (rgdims, i32, i32, i32)),
+        ("camo_rg_loss_backward", i32, (rgdims, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, vp)),
+    ),
+    "camo_rg_train_bn.h": (
+        ("camo_rg_train_bn_workspace_bytes", sz, (rgdims, i32, i32, i32)),
+        ("camo_rg_loss_backward_bn", i32, (rgdims, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, f32, vp, vp, vp)),
+    ),
+    "camo_rg_targets.h": (
+        ("camo_rg_node_targets", i32, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
+    ),
+}
+
+
+def symbols(header):
+    """The names ``include/<header>`` declares, in its order."""
+    return tuple(name for name, _, _ in PROTOTYPES[header])
+
+
+SYMBOLS = symbols("camo_fusion.h")
+
+
 class CamoError(RuntimeError):
     pass
 
@@ -115,117 +180,17 @@ def lib():
         raise CamoError(f"{LIB_PATH} is missing: the HIP extension has not been built and there is no CPU "
                         "fallback. Run `python -m camouflage_multimodal_amd.build` (needs hipcc).")
     L = C.CDLL(LIB_PATH)
-    vp, i32, u64, f32, sz = C.c_void_p, C.c_int32, C.c_uint64, C.c_float, C.c_size_t
-    L.camo_abi_version.restype = C.c_int
-    L.camo_abi_version.argtypes = []
-    L.camo_last_error.restype = C.c_char_p
-    L.camo_last_error.argtypes = []
-    L.camo_workspace_bytes.restype = sz
-    L.camo_workspace_bytes.argtypes = [C.POINTER(CamoDims), i32, i32, i32]
-    L.camo_batch_desc_bytes.restype = sz
-    L.camo_batch_desc_bytes.argtypes = [i32, i32]
-    L.camo_prepare_batch.restype = C.c_int
-    L.camo_prepare_batch.argtypes = [vp, i32, i32, i32, vp, sz, vp]
-    L.camo_gather_batch.restype = C.c_int
-    L.camo_gather_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, u64, vp]
-    L.camo_forward.restype = C.c_int
-    L.camo_forward.argtypes = [C.POINTER(CamoDims), vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, i32, u64, i32, i32, vp]
-    L.camo_backward.restype = C.c_int
-    L.camo_backward.argtypes = [C.POINTER(CamoDims), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, i32, i32, u64, i32, i32, vp]
-    L.camo_loss.restype = C.c_int
-    L.camo_loss.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    L.camo_grad_sumsq.restype = C.c_int
-    L.camo_grad_sumsq.argtypes = [vp, sz, vp, vp]
-    L.camo_clip_adamw.restype = C.c_int
-    L.camo_clip_adamw.argtypes = [vp, vp, vp, vp, sz, vp, f32, f32, f32, f32, f32, f32, i32, i32, vp]
-    L.camo_forward_loss_backward.restype = C.c_int
-    L.camo_forward_loss_backward.argtypes = [C.POINTER(CamoDims), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz,
-                                             vp, vp, vp, vp, vp, vp, i32, C.c_uint64, i32, vp, vp, i32, vp]
-    L.camo_forward_cached.restype = C.c_int
-    L.camo_forward_cached.argtypes = [C.POINTER(CamoDims), vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, i32, u64, i32, i32, vp, i32,
-                                      C.POINTER(C.c_int32), vp]
-    L.camo_shadow_bytes.restype = sz
-    L.camo_shadow_bytes.argtypes = [C.POINTER(CamoDims)]
-    L.camo_clip_adamw_shadows.restype = C.c_int
-    L.camo_clip_adamw_shadows.argtypes = [C.POINTER(CamoDims), vp, vp, vp, vp, vp, sz, vp, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp]
-    L.camo_rg_workspace_bytes.restype = sz
-    L.camo_rg_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32]
-    L.camo_rg_build_csr.restype = C.c_int
-    L.camo_rg_build_csr.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    L.camo_rg_node_embeddings.restype = C.c_int
-    L.camo_rg_node_embeddings.argtypes = [C.POINTER(CamoRgDims), vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]
-    L.camo_tail_timeouts.restype = C.c_int
-    L.camo_tail_timeouts.argtypes = [vp]
-    L.camo_tail_poison_to_grads.restype = C.c_int
-    L.camo_tail_poison_to_grads.argtypes = [vp, vp]
-    L.camo_rg_graph_workspace_bytes.restype = sz
-    L.camo_rg_graph_workspace_bytes.argtypes = [i32]
-    L.camo_rg_region_graph.restype = C.c_int
-    L.camo_rg_region_graph.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, i32, vp, vp]
-    L.camo_rg_batch_workspace_bytes.restype = sz
-    L.camo_rg_batch_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.camo_rg_region_graph_batch.restype = C.c_int
-    L.camo_rg_region_graph_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.camo_canny_workspace_bytes.restype = sz
-    L.camo_canny_workspace_bytes.argtypes = [i32, i32, i32]
-    L.camo_canny.restype = C.c_int
-    L.camo_canny.argtypes = [vp, i32, i32, i32, f32, f32, f32, vp, sz, vp, vp, vp]
-    L.camo_canny_hysteresis.restype = C.c_int
-    L.camo_canny_hysteresis.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp]
-    L.camo_slic_grid.restype = C.c_int
-    L.camo_slic_grid.argtypes = [i32, i32, i32, C.POINTER(i32)]
-    L.camo_slic_workspace_bytes.restype = sz
-    L.camo_slic_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.camo_slic.restype = C.c_int
-    L.camo_slic.argtypes = [vp, i32, i32, i32, i32, f32, f32, vp, sz, vp, vp, vp]
-    L.camo_slic_preprocess.restype = C.c_int
-    L.camo_slic_preprocess.argtypes = [vp, i32, i32, i32, f32, f32, vp, vp]
-    L.camo_slic_assign.restype = C.c_int
-    L.camo_slic_assign.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.camo_slic_update.restype = C.c_int
-    L.camo_slic_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.camo_slic_connect.restype = C.c_int
-    L.camo_slic_connect.argtypes = [vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
-    L.camo_rg_node_heads.restype = C.c_int
-    L.camo_rg_node_heads.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, i32, vp, vp, vp]
-    L.camo_rg_paint.restype = C.c_int
-    L.camo_rg_paint.argtypes = [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]
-    L.camo_seg_counts.restype = C.c_int
-    L.camo_seg_counts.argtypes = [vp, C.c_int64, vp, f32, i32, i32, i32, vp, vp]
-    L.camo_rg_train_workspace_bytes.restype = sz
-    L.camo_rg_train_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
-    L.camo_rg_loss_backward.restype = C.c_int
-    L.camo_rg_loss_backward.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, vp]
-    L.camo_rg_train_bn_workspace_bytes.restype = sz
-    L.camo_rg_train_bn_workspace_bytes.argtypes = [C.POINTER(CamoRgDims), i32, i32, i32]
-    L.camo_rg_loss_backward_bn.restype = C.c_int
-    L.camo_rg_loss_backward_bn.argtypes = [C.POINTER(CamoRgDims), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp,
-                                           f32, vp, vp, vp]
-    L.camo_rg_node_targets.restype = C.c_int
-    L.camo_rg_node_targets.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.camo_debug_gemm.restype = C.c_int
-    L.camo_debug_gemm.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
-    L.camo_debug_gemm16.restype = C.c_int
-    L.camo_debug_gemm16.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]
-    L.camo_debug_ws_offset.restype = C.c_int64
-    L.camo_debug_ws_offset.argtypes = [C.POINTER(CamoDims), i32, i32, i32, C.c_char_p]
-    L.camo_debug_plan.restype = C.c_int
-    L.camo_debug_plan.argtypes = [C.POINTER(CamoDims), i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(CamoPlan)]
-    L.camo_options_init.restype = C.c_int
-    L.camo_options_init.argtypes = [C.POINTER(CamoOptions)]
-    L.camo_options_set.restype = C.c_int
-    L.camo_options_set.argtypes = [C.POINTER(CamoOptions), C.c_char_p, i32]
+    for header, protos in PROTOTYPES.items():
+        for name, restype, argtypes in protos:
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise CamoError(f"{LIB_PATH} does not export {name} (include/{header}): it is older than this package; "
+                                "rebuild it with `python -m camouflage_multimodal_amd.build`") from None
+            fn.restype, fn.argtypes = restype, list(argtypes)
     # tests and developer tools switch schedules "for the process": a Python-side convenience that sets the option on every live
     # engine and on the defaults of engines created later (engine.set_option_all) -- the library itself keeps no option state
     L.camo_debug_set_option = _set_option_everywhere
-    L.camo_debug_set_stamps.restype = C.c_int
-    L.camo_debug_set_stamps.argtypes = [vp, i32]
-    L.camo_prof_begin.restype = C.c_int
-    L.camo_prof_begin.argtypes = [i32]
-    L.camo_prof_end.restype = C.c_int
-    L.camo_prof_end.argtypes = [C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double)]
-    L.camo_prof_kind.restype = C.c_int
-    L.camo_prof_kind.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double)]
     v = L.camo_abi_version()
     if v != ABI_VERSION:
         raise CamoError(f"libcamo_fusion.so has ABI version {v}, this package expects {ABI_VERSION}: rebuild it")

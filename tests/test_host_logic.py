@@ -3,7 +3,6 @@ no CPU fallback and must say so)."""
 import ctypes
 import io
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,29 +13,18 @@ from oracle import params as OP
 
 
 def test_shared_library_exports_every_declared_symbol():
+    """(The declared names, their prototypes and the exports of all ten headers: tests/test_abi_binding.py.)"""
     from camouflage_multimodal_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "camo_fusion.h")).read()
-    declared = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
     assert os.path.exists(_lib.LIB_PATH), "run `python -m camouflage_multimodal_amd.build` first"
     L = ctypes.CDLL(_lib.LIB_PATH)
-    for s in declared:
-        assert hasattr(L, s), s
     L.camo_abi_version.restype = ctypes.c_int
     assert L.camo_abi_version() == _lib.ABI_VERSION
     assert f"#define CAMO_ABI_VERSION {_lib.ABI_VERSION}" in hdr
     assert f"#define CAMO_SUMSQ_FLOATS {_lib.SUMSQ_FLOATS}" in hdr
     hdr2 = open(os.path.join(ROOT, "include", "camo_rg_gnn.h")).read()
-    declared2 = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr2)) - {"camo_last_error"}
-    assert declared2 == set(_lib.RG_SYMBOLS), declared2 ^ set(_lib.RG_SYMBOLS)
-    for s in declared2:
-        assert hasattr(L, s), s
     assert f"CAMO_RG_NPARAMS" in hdr2 and _lib.RG_NPARAMS == 28
     hdr3 = open(os.path.join(ROOT, "include", "camo_rg_features.h")).read()
-    declared3 = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr3)) - {"camo_last_error"}
-    assert declared3 == set(_lib.RGF_SYMBOLS), declared3 ^ set(_lib.RGF_SYMBOLS)
-    for s in declared3:
-        assert hasattr(L, s), s
     assert f"#define CAMO_RG_MAX_LABELS {_lib.RG_MAX_LABELS}" in hdr3
 
 

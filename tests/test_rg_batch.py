@@ -10,7 +10,6 @@ Images to predictions (test 7): predict_batch_from_images in f32 against predict
 packed batch against B x (B = 1) (2e-6 on probabilities and score, 4e-6 on logits: test_predict_batch.py) and the GNN on the
 block-diagonal batch against separate graphs (1e-5 max(|emb|, 1): test_rg_gnn.py) -- and the bound is the sum of the two.
 """
-import ctypes
 import functools
 import os
 import re
@@ -100,12 +99,7 @@ def _check_against_oracle(g, rm, want, what=""):
 def test_binding_and_refusals_without_a_gpu():
     from camouflage_multimodal_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "camo_rg_batch.h")).read()
-    declared = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr)) - {"camo_last_error"}
-    assert declared == set(_lib.RGB_SYMBOLS), declared ^ set(_lib.RGB_SYMBOLS)
     assert "PARITY UNPINNED" in hdr
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for s in declared:
-        assert hasattr(raw, s), s
     assert _lib.ABI_VERSION == 13 and _lib.lib().camo_abi_version() == 13
     assert int(re.search(r"#define CAMO_RGB_TILE_SLOTS (\d+)", hdr).group(1)) == _lib.RGB_TILE_SLOTS
     S = int(re.search(r"#define CAMO_RGB_FIX_BITS (\d+)", hdr).group(1))

@@ -5,9 +5,7 @@ All the arithmetic is integer, so every GPU test compares every element of the f
 tolerance anywhere in this file.  The CPU tests hold the header to the binding, the library's argument checks to the header, and the
 restatement to properties it must have whatever the kernel does.
 """
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -43,12 +41,8 @@ def _blocks(N, H, W, b):
 def test_header_symbols_binding_and_abi_version():
     from camouflage_multimodal_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "camo_rg_targets.h")).read()
-    declared = set(re.findall(r"\b(camo_[a-z_0-9]+)\s*\(", hdr)) - {"camo_last_error"}
-    assert declared == set(_lib.RGTG_SYMBOLS) == {"camo_rg_node_targets"}, declared ^ set(_lib.RGTG_SYMBOLS)
+    assert _lib.symbols("camo_rg_targets.h") == ("camo_rg_node_targets",)
     assert "PARITY UNPINNED" in hdr and "train.py" in hdr and "THREE launches" in hdr and "No workspace" in hdr
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for s in declared:
-        assert hasattr(raw, s), s
     assert _lib.ABI_VERSION == 13 and "#define CAMO_ABI_VERSION 13" in open(os.path.join(ROOT, "include", "camo_fusion.h")).read()
     assert _lib.lib().camo_abi_version() == 13
     assert "camo_rg_targets.h" in open(os.path.join(ROOT, "include", "camo_rg_train.h")).read()
