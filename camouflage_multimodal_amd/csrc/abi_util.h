@@ -1,5 +1,5 @@
-// Host-side vocabulary of the C ABI files (fusion_abi.hip, rg_abi.hip): the error return, the workspace carver and the builder of
-// an exact-fp32 GEMM batch.  No device code.
+// Host-side vocabulary of the C ABI files (fusion_abi.hip with its workspace layout fusion_ws.h, rg_abi.hip): the error return, the
+// workspace carver and the builder of an exact-fp32 GEMM batch.  No device code.
 #pragma once
 #include <cstring>
 #include <string>

@@ -1,5 +1,5 @@
-// C ABI (include/camo_fusion.h): workspace carving and the launch schedules of the fused
-// forward / backward of the fusion model.  No device code here.
+// C ABI (include/camo_fusion.h): the launch schedules of the fused forward / backward of the fusion
+// model, over the workspace that fusion_ws.h lays out.  No device code here.
 //
 // Algebra used (results equal to the reference up to fp32 re-association):
 //   * mean-pool linearity.  The reference computes Z = Y + FFN(Y) for every node and then only
@@ -28,6 +28,7 @@
 #include "gemm16.h"
 #include "misc.h"
 #include "abi_util.h"
+#include "fusion_ws.h"
 
 namespace {
 thread_local std::string g_err;
@@ -40,6 +41,7 @@ int camo_abi::fail_hip(int e, const char* where) {
   return CAMO_E_HIP;
 }
 using namespace camo_abi;
+using namespace camo_ws;
 
 namespace {
 
@@ -71,168 +73,6 @@ struct Call {
 const camo_options_t& options_of(const camo_dims_t* d) { return *(d && d->options ? d->options : &k_default_options); }
 
 typedef unsigned short us;
-
-// The batch descriptor (camo_prepare_batch): [ row -> sample map | 1 / Nr | first 32-row tile of every sample ]
-struct Desc { int* row_sample; float* inv_nr; int* tile_off; int4* tile_desc; size_t bytes; };
-Desc desc_carve(int B, int T, void* base) {
-  Desc d{};
-  Carver c(base);
-  d.row_sample = c.take<int>((size_t)T); d.inv_nr = c.take<float>((size_t)B); d.tile_off = c.take<int>((size_t)B + 1);
-  d.tile_desc = c.take<int4>((size_t)T / 32 + B);       // one entry per block of the fused kernels' RG tile range
-  c.off = (c.off + 255) & ~size_t(255);
-  d.bytes = c.off;
-  return d;
-}
-
-// arrival-counter words of the one-launch tail behind its all-reduce buffers: 4 per group of 16 samples (misc.hip, tail_fused_kernel)
-static inline size_t tail_counter_words(int B) { return (size_t)4 * ((B + 15) / 16 > 0 ? (B + 15) / 16 : 1); }
-
-struct Ws {
-  // zeroed once per forward: [ means | dfused | dKV ] (accumulated into by atomics)
-  float* zero_base; size_t zero_bytes;
-  // forward (saved for backward)
-  float *R, *G, *Q, *KV2, *KV, *Q2, *P, *P2, *O, *O2, *U, *U2, *st1, *st2, *Y, *Y2, *H1, *H2;
-  float *means, *Ymean, *H1mean, *Y2mean, *H2mean; size_t means_n;
-  float *comb, *F1, *fused, *hid, *a2;
-  // backward scratch
-  float *dlog, *dhid, *dfused, *dF1, *dcomb, *dHm1, *dHm2, *da2;
-  float *dH1, *dH2, *dY, *dY2, *dU, *dU2, *dO, *dO2, *dQ, *dKV, *dQ2, *dKV2, *dS2, *dR, *dG;
-  // bf16 schedule ("sched16"): a bf16 copy of every node-level GEMM operand.  Activations have their row
-  // count padded to a multiple of 128 (Tp, TKp; the pad rows are cleared by the prep launch) so the weight-
-  // gradient GEMMs contract over whole 64-row tiles without masks.  Weights: [out][in] copies for x.W^T,
-  // transposed copies for dy.W, and the two in-projection slices that meet at one input concatenated
-  // (WcRgT = [Wq1^T | Wk2^T | Wv2^T], WcKgT = [Wq2^T | Wk1^T | Wv1^T], both [H][3H]).
-  struct H16 {
-    unsigned short *X, *KG, *R, *G, *O, *O2, *Y, *Y2, *dH1, *dH2, *dU, *dU2, *dQKV, *dQKVkg, *dR, *dG;
-    unsigned short *H1, *H2;   // post-ReLU/dropout FFN activations: only their sign pattern is read again (backward mask)
-    unsigned short *Wrg, *Wkg, *Win1, *Win2, *Wo1, *Wo2, *W1, *W2, *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT;
-  } h;
-  size_t Tp, TKp;
-  // fused row-tile schedule (fused_rows.h): weight shadows in MFMA-fragment order and the bf16 activations that cross
-  // its launches / are saved for backward.  Only carved at the reference configuration (fused17_dims).
-  struct F17 {
-    us16 *Wrg, *Wkg, *Wqkv_rg, *Wqkv_kg, *Wo1, *Wo2, *W1, *W2;
-    us16* Wf_rg; float* bf_rg;          // the RG rows' folded in-projection (fused_wide2.hip, launch_fold_rg): shadow of [768 x 128], bias [768]
-    us16 *X16, *KG16, *R16, *G16, *Q16, *Q2_16, *KV16, *KV2_16, *O16, *O2_16, *Y16, *Y2_16, *XH16, *XH2_16;
-    float *rstd1, *rstd2, *lse2, *part; uint32_t *mask1, *mask2;
-    // backward: transposed shadows, the bf16 gradients that are weight-gradient operands, per-sample exchange buffers
-    us16 *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT;
-    us16 *dH16, *dH2_16, *dU16, *dU2_16, *dQKV16, *dQKVkg16, *dR16, *dG16, *dO2_16;
-    float *delta2, *dGpart;
-    us16* tailw[20];      // hi / lo planes of the per-sample tail's weights (tail_wide.h): W13, W23, Wfu0 [256 x 512], Wfu3 [256 x 256], heads [512 x 256];
-                          // 10..19: of their transposes for the tail's backward: heads^T [256 x 512], Wfu3^T [256 x 256], Wfu0^T, W13^T, W23^T [512 x 256]
-  } f;
-  int* tickets;         // [2][B] arrival counters (forward: KG->RG attention splits; backward: a sample's RG tiles), in the zero block
-  float* dQ2acc;        // [TK][H] fp32 sums of the KG->RG query gradient (in the zero block, fused backward)
-  float* parM;          // [2][3H][D] + [2][3H]: dQKV^T x and colsum(dQKV) of the two streams (in the zero block)
-  float* tailsum;       // [B][4H] all-reduce buffers of the one-launch tail (F1 | hidden | dF1) + 4 counter words per 16 samples (in the zero block)
-  size_t bytes;
-};
-
-// the fused row-tile kernels are written for the reference configuration
-bool fused17_dims(const camo_dims_t& d) {
-  return d.fusion_type == CAMO_FUSION_CROSS_ATTENTION && d.hidden_dim == 256 && d.num_heads == 8 && d.rg_dim == 128 && d.kg_dim == 128;
-}
-
-Ws carve(const camo_dims_t& d, int B, int T, int Nk, void* base) {
-  Ws w{};
-  Carver c(base);
-  const size_t H = d.hidden_dim, TK = (size_t)B * Nk, nh = d.num_heads, Wd = 2 * d.num_classes + 2;
-  if (d.fusion_type == CAMO_FUSION_CROSS_ATTENTION) {
-    const size_t Fh = H / 2;
-    w.R = c.take<float>(T * H); w.G = c.take<float>(TK * H);
-    w.Q = c.take<float>(T * H); w.KV2 = c.take<float>(T * 2 * H);
-    w.KV = c.take<float>(TK * 2 * H); w.Q2 = c.take<float>(TK * H);
-    w.P = c.take<float>(T * nh * Nk); w.P2 = c.take<float>(T * nh * Nk);
-    w.O = c.take<float>(T * H); w.O2 = c.take<float>(TK * H);
-    w.U = c.take<float>(T * H); w.U2 = c.take<float>(TK * H);
-    w.st1 = c.take<float>(T * 2); w.st2 = c.take<float>(TK * 2);
-    w.Y = c.take<float>(T * H); w.Y2 = c.take<float>(TK * H);
-    w.H1 = c.take<float>(T * 2 * H); w.H2 = c.take<float>(TK * 2 * H);
-    w.means_n = (size_t)B * 6 * H;
-    {   // one contiguous block so a single memset clears every atomically-accumulated buffer
-      const size_t nzt = ((size_t)2 * B + 3) & ~size_t(3);                   // tickets: padded to 16 bytes
-      const size_t npar = (size_t)2 * (3 * H * d.rg_dim + 3 * H) + 8;        // per stream: dQKV^T x [3H][D] and colsum(dQKV) [3H] (fused backward, parameter space)
-      const size_t nz = w.means_n + (size_t)B * H + nzt + TK * 2 * H + TK * H + (size_t)B * 4 * H + ((tail_counter_words(B) + 3) & ~size_t(3)) + npar;
-      float* z = c.take<float>(nz);
-      w.zero_base = z; w.zero_bytes = nz * sizeof(float);
-      w.means = z; w.dfused = z ? z + w.means_n : nullptr;
-      w.tickets = z ? reinterpret_cast<int*>(w.dfused + (size_t)B * H) : nullptr;
-      w.dKV = z ? w.dfused + (size_t)B * H + nzt : nullptr;
-      w.dQ2acc = z ? w.dKV + TK * 2 * H : nullptr;
-      w.tailsum = z ? w.dQ2acc + TK * H : nullptr;
-      w.parM = z ? w.tailsum + (size_t)B * 4 * H + ((tail_counter_words(B) + 3) & ~size_t(3)) : nullptr;
-    }
-    if (w.means) { w.Ymean = w.means; w.H1mean = w.Ymean + B * H; w.Y2mean = w.H1mean + B * 2 * H; w.H2mean = w.Y2mean + B * H; }
-    w.comb = c.take<float>(B * 2 * H); w.F1 = c.take<float>(B * H); w.fused = c.take<float>(B * H);
-    w.hid = c.take<float>(B * 4 * Fh);
-    w.dlog = c.take<float>(B * Wd); w.dhid = c.take<float>(B * 4 * Fh);
-    w.dF1 = c.take<float>(B * H); w.dcomb = c.take<float>(B * 2 * H);
-    w.dHm1 = c.take<float>(B * 2 * H); w.dHm2 = c.take<float>(B * 2 * H);
-    w.dH1 = c.take<float>(T * 2 * H); w.dH2 = c.take<float>(TK * 2 * H);
-    w.dY = c.take<float>(T * H); w.dY2 = c.take<float>(TK * H);
-    w.dU = c.take<float>(T * H); w.dU2 = c.take<float>(TK * H);
-    w.dO = c.take<float>(T * H); w.dO2 = c.take<float>(TK * H);
-    w.dQ = c.take<float>(T * H);
-    w.dQ2 = c.take<float>(TK * H); w.dKV2 = c.take<float>(T * 2 * H);
-    w.dS2 = c.take<float>(T * nh * Nk);
-    w.dR = c.take<float>(T * H); w.dG = c.take<float>(TK * H);
-    {
-      const size_t Tp = ((size_t)T + 127) / 128 * 128, TKp = (TK + 127) / 128 * 128, D = d.rg_dim, Dk = d.kg_dim;
-      w.Tp = Tp; w.TKp = TKp;
-      Ws::H16& h = w.h;
-      h.X = c.take<us>(Tp * D); h.KG = c.take<us>(TKp * Dk); h.R = c.take<us>(Tp * H); h.G = c.take<us>(TKp * H);
-      h.O = c.take<us>(Tp * H); h.O2 = c.take<us>(TKp * H); h.Y = c.take<us>(Tp * H); h.Y2 = c.take<us>(TKp * H);
-      h.dH1 = c.take<us>(Tp * 2 * H); h.dH2 = c.take<us>(TKp * 2 * H); h.dU = c.take<us>(Tp * H); h.dU2 = c.take<us>(TKp * H);
-      h.dQKV = c.take<us>(Tp * 3 * H); h.dQKVkg = c.take<us>(TKp * 3 * H); h.dR = c.take<us>(Tp * H); h.dG = c.take<us>(TKp * H);
-      h.Wrg = c.take<us>(H * D); h.Wkg = c.take<us>(H * Dk); h.Win1 = c.take<us>(3 * H * H); h.Win2 = c.take<us>(3 * H * H);
-      h.Wo1 = c.take<us>(H * H); h.Wo2 = c.take<us>(H * H); h.W1 = c.take<us>(2 * H * H); h.W2 = c.take<us>(2 * H * H);
-      h.W1T = c.take<us>(2 * H * H); h.W2T = c.take<us>(2 * H * H); h.Wo1T = c.take<us>(H * H); h.Wo2T = c.take<us>(H * H);
-      h.WcRgT = c.take<us>(3 * H * H); h.WcKgT = c.take<us>(3 * H * H);
-      h.H1 = c.take<us>(Tp * 2 * H); h.H2 = c.take<us>(TKp * 2 * H);      // (padded: they double as weight-gradient operands)
-      if (fused17_dims(d)) {
-        Ws::F17& f = w.f;
-        f.Wrg = c.take<us>(H * D); f.Wkg = c.take<us>(H * Dk); f.Wqkv_rg = c.take<us>(3 * H * H); f.Wqkv_kg = c.take<us>(3 * H * H);
-        f.Wo1 = c.take<us>(H * H); f.Wo2 = c.take<us>(H * H); f.W1 = c.take<us>(2 * H * H); f.W2 = c.take<us>(2 * H * H);
-        f.X16 = c.take<us>(Tp * D); f.KG16 = c.take<us>(TKp * Dk); f.R16 = c.take<us>(Tp * H); f.G16 = c.take<us>(TKp * H);
-        f.Q16 = c.take<us>(Tp * H); f.Q2_16 = c.take<us>(TKp * H); f.KV16 = c.take<us>(TKp * 2 * H); f.KV2_16 = c.take<us>(Tp * 2 * H);
-        f.O16 = c.take<us>(Tp * H); f.O2_16 = c.take<us>(TKp * H); f.Y16 = c.take<us>(Tp * H); f.Y2_16 = c.take<us>(TKp * H);
-        f.XH16 = c.take<us>(Tp * H); f.XH2_16 = c.take<us>(TKp * H);
-        f.rstd1 = c.take<float>(Tp); f.rstd2 = c.take<float>(TKp); f.lse2 = c.take<float>((size_t)B * 8 * 16 * 2);
-        f.mask1 = c.take<uint32_t>(Tp * 16); f.mask2 = c.take<uint32_t>(TKp * 16);
-        f.part = c.take<float>(((size_t)T / 32 + B + 2) * 8 * FUSED_PART_FLOATS);
-        f.W1T = c.take<us>(2 * H * H); f.W2T = c.take<us>(2 * H * H); f.Wo1T = c.take<us>(H * H); f.Wo2T = c.take<us>(H * H);
-        f.WcRgT = c.take<us>(3 * H * H); f.WcKgT = c.take<us>(3 * H * H);
-        f.dH16 = c.take<us>(Tp * 2 * H); f.dH2_16 = c.take<us>(TKp * 2 * H); f.dU16 = c.take<us>(Tp * H); f.dU2_16 = c.take<us>(TKp * H);
-        f.dQKV16 = c.take<us>(Tp * 3 * H); f.dQKVkg16 = c.take<us>(TKp * 3 * H); f.dR16 = c.take<us>(Tp * H); f.dG16 = c.take<us>(TKp * H);
-        f.dO2_16 = c.take<us>(TKp * H); f.delta2 = c.take<float>((size_t)B * 8 * 16); f.dGpart = c.take<float>(TKp * H);
-        for (int i = 0; i < 10; ++i) f.tailw[i] = c.take<us>(i < 6 ? 2 * H * H : (i < 8 ? H * H : 2 * H * H));
-        for (int i = 10; i < 20; ++i) f.tailw[i] = c.take<us>((i == 12 || i == 13) ? H * H : 2 * H * H);
-        f.Wf_rg = c.take<us>(3 * H * D); f.bf_rg = c.take<float>(3 * H);
-      }
-    }
-  } else {
-    const size_t F = H / 2, Fh = F / 2, Dc = (size_t)d.rg_dim + d.kg_dim;
-    w.means_n = (size_t)B * Dc;
-    {
-      const size_t nz = w.means_n + (size_t)B * F;
-      float* z = c.take<float>(nz);
-      w.zero_base = z; w.zero_bytes = nz * sizeof(float);
-      w.comb = z;                                // [B, rg_dim+kg_dim] = the two means, zeroed then accumulated
-      w.dfused = z ? z + w.means_n : nullptr;
-    }
-    w.means = w.comb;
-    w.F1 = c.take<float>(B * H);               // a1
-    w.a2 = c.take<float>(B * F);
-    w.fused = c.take<float>(B * F);
-    w.hid = c.take<float>(B * 4 * Fh);
-    w.dlog = c.take<float>(B * Wd); w.dhid = c.take<float>(B * 4 * Fh);
-    w.da2 = c.take<float>(B * F); w.dF1 = c.take<float>(B * H);
-  }
-  c.off = (c.off + 255) & ~size_t(255);
-  w.bytes = c.off;
-  return w;
-}
 
 int check_dims(const camo_dims_t* d, int B, int T, int Nk) {
   if (!d) return fail(CAMO_E_ARG, "dims is null");
@@ -296,28 +136,6 @@ void set_res(Gemm16Prob& p, const float* res, int ldr) { p.res = res; p.ldr = ld
 void set_drop(Gemm16Prob& p, uint32_t site) { p.flags |= GF_DROPOUT; p.drop_site = site; }
 void set_bcast(Gemm16Prob& p, const float* v, int ldv, const int* row_sample, const float* inv_nr, int uniform_n) {
   p.flags |= GF_RES_BCAST; p.res = v; p.ldr = ldv; p.row_sample = row_sample; p.inv_nr = inv_nr; p.uniform_n = uniform_n;
-}
-
-// the caller-owned weight shadows (Call::shadows)
-struct ShadowSet { us16 *Wrg, *Wkg, *Wqkv_rg, *Wqkv_kg, *Wo1, *Wo2, *W1, *W2, *W1T, *W2T, *Wo1T, *Wo2T, *WcRgT, *WcKgT, *Wf_rg; float* bf_rg; size_t bytes; };
-static ShadowSet shadow_carve(void* base) {
-  ShadowSet x{};
-  Carver c(base);
-  const size_t H = 256, D = 128, HH = H * H;
-  x.Wrg = c.take<us16>(H * D); x.Wkg = c.take<us16>(H * D); x.Wqkv_rg = c.take<us16>(3 * HH); x.Wqkv_kg = c.take<us16>(3 * HH);
-  x.Wo1 = c.take<us16>(HH); x.Wo2 = c.take<us16>(HH); x.W1 = c.take<us16>(2 * HH); x.W2 = c.take<us16>(2 * HH);
-  x.W1T = c.take<us16>(2 * HH); x.W2T = c.take<us16>(2 * HH); x.Wo1T = c.take<us16>(HH); x.Wo2T = c.take<us16>(HH);
-  x.WcRgT = c.take<us16>(3 * HH); x.WcKgT = c.take<us16>(3 * HH);
-  x.Wf_rg = c.take<us16>(3 * H * D); x.bf_rg = c.take<float>(3 * H);      // (inference calls only: launch_fold_rg)
-  x.bytes = (c.off + 255) & ~size_t(255);
-  return x;
-}
-void bind_shadows(void* shadows, Ws& w) {   // (a call that was handed external shadows keeps the fused schedule's weight shadows there)
-  const ShadowSet x = shadow_carve(shadows);
-  Ws::F17& f = w.f;
-  f.Wrg = x.Wrg; f.Wkg = x.Wkg; f.Wqkv_rg = x.Wqkv_rg; f.Wqkv_kg = x.Wqkv_kg; f.Wo1 = x.Wo1; f.Wo2 = x.Wo2; f.W1 = x.W1; f.W2 = x.W2;
-  f.W1T = x.W1T; f.W2T = x.W2T; f.Wo1T = x.Wo1T; f.Wo2T = x.Wo2T; f.WcRgT = x.WcRgT; f.WcKgT = x.WcKgT;
-  f.Wf_rg = x.Wf_rg; f.bf_rg = x.bf_rg;
 }
 
 // ---- the launch schedule of one call ----------------------------------------------------------------------
@@ -492,7 +310,7 @@ int open_batch(Batch& x, const Call& c, bool ptrs_ok) {
   if (x.max_nr < 1 || x.max_nr > x.T) return fail(CAMO_E_ARG, "max_nr out of range");
   if (x.precision != CAMO_PREC_F32 && x.precision != CAMO_PREC_BF16) return fail(CAMO_E_ARG, "unknown precision");
   x.w = carve(*x.dims, x.B, x.T, x.Nk, x.workspace);
-  if (c.shadows) bind_shadows(c.shadows, x.w);
+  if (c.shadows) x.w.f.sh = shadow_carve(c.shadows);      // (a call that was handed external shadows keeps the fused schedule's weight shadows there)
   if (x.workspace_bytes < x.w.bytes) return fail(CAMO_E_WORKSPACE, "workspace smaller than camo_workspace_bytes()");
   x.drop = make_drop(x.training, x.dims->dropout, x.seed);
   return 0;
@@ -593,11 +411,8 @@ int forward_nodes16(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
     };
     auto cast = [&](const float* src, us* dst, size_t n) { job(PREP_CAST, src, dst, n, 0, 0, 0, 0); };
     auto castT = [&](const float* src, us* dst, int rows, int cols, int ld, int off) { job(PREP_CAST_T, src, dst, 0, rows, cols, ld, off); };
-    auto pad = [&](us* buf, size_t rows, size_t rows_p, size_t width) {
-      job(PREP_ZERO, nullptr, buf + rows * width, (rows_p - rows) * width * sizeof(us), 0, 0, 0, 0);
-    };
     // the atomics block: pooled means and dfused (this schedule accumulates nothing into dKV)
-    job(PREP_ZERO, nullptr, w.zero_base, (size_t)(reinterpret_cast<char*>(w.dKV) - reinterpret_cast<char*>(w.zero_base)), 0, 0, 0, 0);
+    job(PREP_ZERO, nullptr, w.zero_base, w.zero_fwd_bytes, 0, 0, 0, 0);
     cast(rg, h.X, (size_t)T * D); cast(kg, h.KG, (size_t)TK * Dk);
     cast(P[CAMO_P_RG_PROJ_W], h.Wrg, (size_t)H * D); cast(P[CAMO_P_KG_PROJ_W], h.Wkg, (size_t)H * Dk);
     cast(P[CAMO_P_A1_IN_W], h.Win1, 3 * HH); cast(P[CAMO_P_A2_IN_W], h.Win2, 3 * HH);
@@ -607,11 +422,7 @@ int forward_nodes16(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
     castT(P[CAMO_P_A1_OUT_W], h.Wo1T, H, H, H, 0); castT(P[CAMO_P_A2_OUT_W], h.Wo2T, H, H, H, 0);
     castT(P[CAMO_P_A1_IN_W], h.WcRgT, H, H, 3 * H, 0); castT(P[CAMO_P_A2_IN_W] + HH, h.WcRgT, 2 * H, H, 3 * H, H);
     castT(P[CAMO_P_A2_IN_W], h.WcKgT, H, H, 3 * H, 0); castT(P[CAMO_P_A1_IN_W] + HH, h.WcKgT, 2 * H, H, 3 * H, H);
-    const size_t t = T, tk = TK;
-    pad(h.X, t, w.Tp, D); pad(h.R, t, w.Tp, H); pad(h.O, t, w.Tp, H); pad(h.Y, t, w.Tp, H); pad(h.dH1, t, w.Tp, 2 * H);
-    pad(h.dU, t, w.Tp, H); pad(h.dQKV, t, w.Tp, 3 * H); pad(h.dR, t, w.Tp, H); pad(h.H1, t, w.Tp, 2 * H);
-    pad(h.KG, tk, w.TKp, Dk); pad(h.G, tk, w.TKp, H); pad(h.O2, tk, w.TKp, H); pad(h.Y2, tk, w.TKp, H); pad(h.dH2, tk, w.TKp, 2 * H);
-    pad(h.dU2, tk, w.TKp, H); pad(h.dQKVkg, tk, w.TKp, 3 * H); pad(h.dG, tk, w.TKp, H); pad(h.H2, tk, w.TKp, 2 * H);
+    for (int i = 0; i < h.pad.n; ++i) job(PREP_ZERO, nullptr, h.pad.r[i].ptr, h.pad.r[i].bytes, 0, 0, 0, 0);
     CK(launch_prep(pb, st), "prep (clear + bf16 casts)");
   }
   GB16 g(drop, *x.opt, st);
@@ -669,78 +480,69 @@ int forward_nodes16(const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
 // ---- node-level forward of the fused row-tile schedule: the same function in 3 launches (fused_rows.h) ----
 int forward_nodes17(Call& c, const Batch& x, float* attn_rg2kg, float* attn_kg2rg) {
   const camo_plan_t& pl = x.plan; const float* const* P = x.P; const Ws& w = x.w; hipStream_t st = x.st;
-  const int H = 256, D = 128, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, max_nr = x.max_nr;
+  const int H = 256, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk, max_nr = x.max_nr;
   const size_t HH = (size_t)H * H;
   const bool save = pl.save != 0;
-  const Ws::F17& f = w.f;
+  const Ws::F17& f = w.f; const ShadowSet& sh = f.sh;
   FrontArgs fa; std::memset(&fa, 0, sizeof(fa));
   {   // weight shadows (bf16, fragment order) + the clear of the step's atomics block
     ShadowBatch sb; std::memset(&sb, 0, sizeof(sb));
-    // shadow of [s0; s1] (N rows of K columns), or of its transpose (transposed: the sources have K rows of N columns)
-    auto job = [&](us* dst, int N, int K, int transposed, const float* s0, int r0, const float* s1 = nullptr, int r1 = 0) {
-      ShadowJob& J = sb.j[sb.n++];
-      const int ld = transposed ? N : K;
-      J.dst = dst; J.N = N; J.K = K; J.transposed = transposed; J.nsrc = s1 ? 2 : 1;
-      J.src[0] = s0; J.rows[0] = r0; J.ld[0] = ld; J.src[1] = s1; J.rows[1] = r1; J.ld[1] = ld;
-    };
     const bool build = !c.shadows_valid;        // (valid: camo_clip_adamw_shadows left them ready; only the clears ride in this launch)
     if (c.shadows) c.shadows_state = save ? 2 : 1;
-    if (build) {
-      job(f.Wrg, H, D, 0, P[CAMO_P_RG_PROJ_W], H); job(f.Wkg, H, D, 0, P[CAMO_P_KG_PROJ_W], H);
-      job(f.Wqkv_rg, 3 * H, H, 0, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);       // [Wq1; Wk2; Wv2]: what RG rows are projected with
-      job(f.Wqkv_kg, 3 * H, H, 0, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);       // [Wq2; Wk1; Wv1]
-      job(f.Wo1, H, H, 0, P[CAMO_P_A1_OUT_W], H); job(f.Wo2, H, H, 0, P[CAMO_P_A2_OUT_W], H);
-      job(f.W1, 2 * H, H, 0, P[CAMO_P_F1_W0], 2 * H); job(f.W2, 2 * H, H, 0, P[CAMO_P_F2_W0], 2 * H);
-    }
-    auto zero = [&](void* ptr, size_t bytes) { if (bytes) { sb.zero_ptr[sb.nzero] = ptr; sb.zero_bytes[sb.nzero++] = (bytes + 15) & ~size_t(15); } };
-    if (save) {
-      // transposed shadows of the backward's dy . W products; K-concatenated where one product serves three in-projections
-      if (build) {
-        job(f.W1T, H, 2 * H, 1, P[CAMO_P_F1_W0], 2 * H); job(f.W2T, H, 2 * H, 1, P[CAMO_P_F2_W0], 2 * H);
-        job(f.Wo1T, H, H, 1, P[CAMO_P_A1_OUT_W], H); job(f.Wo2T, H, H, 1, P[CAMO_P_A2_OUT_W], H);
-        job(f.WcRgT, H, 3 * H, 1, P[CAMO_P_A1_IN_W], H, P[CAMO_P_A2_IN_W] + HH, 2 * H);      // dR = [dQ | dK2 | dV2] . [Wq1; Wk2; Wv2]
-        job(f.WcKgT, H, 3 * H, 1, P[CAMO_P_A2_IN_W], H, P[CAMO_P_A1_IN_W] + HH, 2 * H);      // dG = [dQ2 | dK | dV] . [Wq2; Wk1; Wv1]
+    // One job per shadow, its sources the slices k_shadow_slices gives it: the shadow of [s0; s1] (N rows of K columns), or of its
+    // transpose (transposed: the sources have K rows of N columns) -- the backward's dy . W products, K-concatenated where one
+    // product serves three in-projections.  The jobs of a pass run in the order the shadows are carved in.
+    auto jobs = [&](int transposed) {
+      const int first = sb.n;
+      for (const ShadowSlice& s : k_shadow_slices) {
+        if (transposed && !s.trans) continue;
+        us16* const dst = sh.*(transposed ? s.trans : s.plain);
+        if (!sb.n || sb.j[sb.n - 1].dst != dst) {
+          ShadowJob& J = sb.j[sb.n++];
+          J.dst = dst; J.N = transposed ? s.cols : s.pN; J.K = transposed ? s.tK : s.cols; J.transposed = transposed;
+        }
+        ShadowJob& J = sb.j[sb.n - 1];
+        J.src[J.nsrc] = P[s.param] + (size_t)s.r0 * s.cols; J.rows[J.nsrc] = s.rows; J.ld[J.nsrc++] = s.cols;
       }
-      zero(w.zero_base, w.zero_bytes);                       // means, dfused, arrival counters, dK|dV and dQ2 sums
-      // pad rows (row count rounded up to 128) of every weight-gradient operand: the contraction runs over whole 64-row tiles
-      const size_t t = T, tk = TK;
-      auto pad = [&](us* buf, size_t rows, size_t rows_p, size_t width) { zero(buf + rows * width, (rows_p - rows) * width * sizeof(us)); };
-      pad(f.X16, t, w.Tp, D); pad(f.R16, t, w.Tp, H); pad(f.O16, t, w.Tp, H); pad(f.Y16, t, w.Tp, H); pad(f.dH16, t, w.Tp, 2 * H);
-      pad(f.dU16, t, w.Tp, H); pad(f.dQKV16, t, w.Tp, 3 * H); pad(f.dR16, t, w.Tp, H);
-      pad(f.KG16, tk, w.TKp, D); pad(f.G16, tk, w.TKp, H); pad(f.O2_16, tk, w.TKp, H); pad(f.Y2_16, tk, w.TKp, H); pad(f.dH2_16, tk, w.TKp, 2 * H);
-      pad(f.dU2_16, tk, w.TKp, H); pad(f.dQKVkg16, tk, w.TKp, 3 * H); pad(f.dG16, tk, w.TKp, H);
-      zero(w.dHm1, (size_t)B * 2 * H * sizeof(float)); zero(w.dHm2, (size_t)B * 2 * H * sizeof(float));   // atomically summed by the one-launch tail
+      for (int i = first + 1; i < sb.n; ++i)
+        for (int j = i; j > first && sb.j[j].dst < sb.j[j - 1].dst; --j) std::swap(sb.j[j], sb.j[j - 1]);
+    };
+    if (build) { jobs(0); if (save) jobs(1); }
+    // The step's clears.  They ride in the shadow launch; a step without one (!build) says per range where instead: EARLY at the end of
+    // the front kernel's blocks (first use: the back kernel's pooled sums), LATE in extra blocks of the first backward kernel
+    // (first use: the weight-gradient launch)
+    constexpr bool EARLY = true, LATE = false;
+    const char* zerr = nullptr;
+    auto zero = [&](void* ptr, size_t bytes, bool early) {
+      bytes = (bytes + 15) & ~size_t(15);
+      if (!bytes || zerr) return;
+      if (build) { sb.zero_ptr[sb.nzero] = ptr; sb.zero_bytes[sb.nzero++] = bytes; }
+      else if (bytes > 0xFFFFFFF0ull) zerr = "clear range too large";
+      else if (early && fa.nzero >= FUSED_FRONT_MAXZ) zerr = "too many early clear ranges";
+      else if (early) { fa.zero_ptr[fa.nzero] = ptr; fa.zero_bytes[fa.nzero++] = (unsigned)bytes; }
+      else if (c.nzero_bwd1 >= FUSED_BWD1_MAXZ) zerr = "too many late clear ranges";
+      else { c.zero_bwd1_ptr[c.nzero_bwd1] = ptr; c.zero_bwd1_bytes[c.nzero_bwd1++] = (unsigned)bytes; }
+    };
+    if (save) {
+      zero(w.zero_base, w.zero_bytes, EARLY);                // means, dfused, arrival counters, dK|dV and dQ2 sums
+      for (int i = 0; i < f.pad.n; ++i) zero(f.pad.r[i].ptr, f.pad.r[i].bytes, LATE);      // pad rows of every weight-gradient operand
+      zero(w.dHm1, (size_t)B * 2 * H * sizeof(float), EARLY); zero(w.dHm2, (size_t)B * 2 * H * sizeof(float), EARLY);   // atomically summed by the one-launch tail
     } else {
-      zero(w.zero_base, (size_t)(reinterpret_cast<char*>(w.dKV) - reinterpret_cast<char*>(w.zero_base)));
+      zero(w.zero_base, w.zero_fwd_bytes, EARLY);
       // (the one-launch tail's all-reduce buffers and counter words; the parameter-space block behind them belongs to the backward)
-      zero(w.tailsum, ((size_t)B * 4 * H + ((tail_counter_words(B) + 3) & ~size_t(3))) * sizeof(float));
+      zero(w.tailsum.F1sum, w.tailsum.bytes, EARLY);
     }
+    if (zerr) return fail(CAMO_E_ARG, zerr);
     // inference calls: the RG rows' folded in-projection rides with every rebuild of the forward set, and alone when the caller's valid
     // shadows come from the optimizer call, which does not build it (camo_forward_cached, shadows_valid = 2)
     const bool fold = !save && (build || c.fold_missing);
     if (build) CK(launch_weight_shadows(sb, st), "weight shadows");
     if (fold) CK(launch_fold_rg(P[CAMO_P_A1_IN_W], P[CAMO_P_A2_IN_W] + HH, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, P[CAMO_P_RG_PROJ_W], P[CAMO_P_RG_PROJ_B],
-                                f.Wf_rg, f.bf_rg, st), "folded in-projection");
-    if (!build) {
-      // no shadow launch this step: the clears ride elsewhere -- the atomics block and d(mean H) at the end of the front
-      // kernel's blocks (first use: the back kernel's pooled sums), the operand pad rows in extra blocks of the first backward
-      // kernel (first use: the weight-gradient launch)
-      for (int i = 0; i < sb.nzero; ++i) {
-        const bool early = sb.zero_ptr[i] == (void*)w.zero_base || sb.zero_ptr[i] == (void*)w.dHm1 || sb.zero_ptr[i] == (void*)w.dHm2 || sb.zero_ptr[i] == (void*)w.tailsum;
-        if (sb.zero_bytes[i] > 0xFFFFFFF0ull) return fail(CAMO_E_ARG, "clear range too large");
-        if (early) {
-          if (fa.nzero >= FUSED_FRONT_MAXZ) return fail(CAMO_E_ARG, "too many early clear ranges");
-          fa.zero_ptr[fa.nzero] = sb.zero_ptr[i]; fa.zero_bytes[fa.nzero++] = (unsigned)sb.zero_bytes[i];
-        } else {
-          if (c.nzero_bwd1 >= FUSED_BWD1_MAXZ) return fail(CAMO_E_ARG, "too many late clear ranges");
-          c.zero_bwd1_ptr[c.nzero_bwd1] = sb.zero_ptr[i]; c.zero_bwd1_bytes[c.nzero_bwd1++] = (unsigned)sb.zero_bytes[i];
-        }
-      }
-    }
+                                sh.Wf_rg, sh.bf_rg, st), "folded in-projection");
   }
   fa.qscale = 1.0f / sqrtf(32.0f); fa.save = save ? 1 : 0;
-  fa.s[0] = FrontStream{x.rg, T, f.Wrg, P[CAMO_P_RG_PROJ_B], f.Wqkv_rg, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, f.X16, f.R16, f.Q16, f.KV2_16, 0};
-  fa.s[1] = FrontStream{x.kg, TK, f.Wkg, P[CAMO_P_KG_PROJ_B], f.Wqkv_kg, P[CAMO_P_A2_IN_B], P[CAMO_P_A1_IN_B] + H, f.KG16, f.G16, f.Q2_16, f.KV16, 0};
+  fa.s[0] = FrontStream{x.rg, T, sh.Wrg, P[CAMO_P_RG_PROJ_B], sh.Wqkv_rg, P[CAMO_P_A1_IN_B], P[CAMO_P_A2_IN_B] + H, f.X16, f.R16, f.Q16, f.KV2_16, 0};
+  fa.s[1] = FrontStream{x.kg, TK, sh.Wkg, P[CAMO_P_KG_PROJ_B], sh.Wqkv_kg, P[CAMO_P_A2_IN_B], P[CAMO_P_A1_IN_B] + H, f.KG16, f.G16, f.Q2_16, f.KV16, 0};
   fa.stamps = g_dbg_stamps; fa.exp = x.opt->exp;
   if (pl.tail >= CAMO_TAIL_PLANES) {
     // the per-sample tail's weights as hi / lo bf16 planes in fragment order: extra blocks of the (KG rows') wide front launch
@@ -758,27 +560,28 @@ int forward_nodes17(Call& c, const Batch& x, float* attn_rg2kg, float* attn_kg2r
       J.dst = dst; J.N = N; J.K = K; J.transposed = transposed; J.nsrc = 4; J.lo = lo;
       for (int h = 0; h < 4; ++h) { J.src[h] = hsrc[h]; J.rows[h] = H / 2; J.ld[h] = H; }
     };
+    const Ws::F17::TailPlanes& tp = f.tp;
     for (int lo = 0; lo < 2; ++lo) {
-      xj(f.tailw[0 + lo], H, 2 * H, 0, P[CAMO_P_F1_W3], lo); xj(f.tailw[2 + lo], H, 2 * H, 0, P[CAMO_P_F2_W3], lo);
-      xj(f.tailw[4 + lo], H, 2 * H, 0, P[CAMO_P_FU_W0], lo); xj(f.tailw[6 + lo], H, H, 0, P[CAMO_P_FU_W3], lo);
+      xj(tp.W13[lo], H, 2 * H, 0, P[CAMO_P_F1_W3], lo); xj(tp.W23[lo], H, 2 * H, 0, P[CAMO_P_F2_W3], lo);
+      xj(tp.Wfu0[lo], H, 2 * H, 0, P[CAMO_P_FU_W0], lo); xj(tp.Wfu3[lo], H, H, 0, P[CAMO_P_FU_W3], lo);
     }
-    for (int lo = 0; lo < 2; ++lo) xheads(f.tailw[8 + lo], 2 * H, H, 0, lo);
+    for (int lo = 0; lo < 2; ++lo) xheads(tp.Wh0[lo], 2 * H, H, 0, lo);
     if (pl.tail != CAMO_TAIL_PLANES)        // training calls: the transposed planes of the tail's backward (tail_wide.h, TailWideBwdArgs)
       for (int lo = 0; lo < 2; ++lo) {
-        xheads(f.tailw[10 + lo], H, 2 * H, 1, lo);
-        xj(f.tailw[12 + lo], H, H, 1, P[CAMO_P_FU_W3], lo);
-        xj(f.tailw[14 + lo], 2 * H, H, 1, P[CAMO_P_FU_W0], lo);
-        xj(f.tailw[16 + lo], 2 * H, H, 1, P[CAMO_P_F1_W3], lo);
-        xj(f.tailw[18 + lo], 2 * H, H, 1, P[CAMO_P_F2_W3], lo);
+        xheads(tp.Wh0T[lo], H, 2 * H, 1, lo);
+        xj(tp.Wfu3T[lo], H, H, 1, P[CAMO_P_FU_W3], lo);
+        xj(tp.Wfu0T[lo], 2 * H, H, 1, P[CAMO_P_FU_W0], lo);
+        xj(tp.W13T[lo], 2 * H, H, 1, P[CAMO_P_F1_W3], lo);
+        xj(tp.W23T[lo], 2 * H, H, 1, P[CAMO_P_F2_W3], lo);
       }
   }
   if (pl.front == CAMO_FRONT_KG) { fa.split3 = 1; CK(launch_wide_front(fa, 1, st, 1), "fused forward, KG rows' front half (32-row tiles, one in-projection pass per block)"); }
   else if (pl.front == CAMO_FRONT_WIDE) CK(launch_wide_front(fa, pl.front_rt, st, 0), "fused forward, front half (wide tiles)");
   else CK(launch_fused_front(fa, x.opt->fused_variant, st), "fused forward, front half");
   BackArgs ba; std::memset(&ba, 0, sizeof(ba));
-  ba.s[0] = BackStream{f.Wo1, P[CAMO_P_A1_OUT_B], f.W1, P[CAMO_P_F1_B0], P[CAMO_P_LN1_W], P[CAMO_P_LN1_B], f.R16,
+  ba.s[0] = BackStream{sh.Wo1, P[CAMO_P_A1_OUT_B], sh.W1, P[CAMO_P_F1_B0], P[CAMO_P_LN1_W], P[CAMO_P_LN1_B], f.R16,
                        f.O16, f.Y16, f.XH16, f.rstd1, f.mask1, w.Ymean, w.H1mean, SITE_FFN_RG};
-  ba.s[1] = BackStream{f.Wo2, P[CAMO_P_A2_OUT_B], f.W2, P[CAMO_P_F2_B0], P[CAMO_P_LN2_W], P[CAMO_P_LN2_B], f.G16,
+  ba.s[1] = BackStream{sh.Wo2, P[CAMO_P_A2_OUT_B], sh.W2, P[CAMO_P_F2_B0], P[CAMO_P_LN2_W], P[CAMO_P_LN2_B], f.G16,
                        f.O2_16, f.Y2_16, f.XH2_16, f.rstd2, f.mask2, w.Y2mean, w.H2mean, SITE_FFN_KG};
   ba.Q16 = f.Q16; ba.KV16 = f.KV16; ba.Q2_16 = f.Q2_16; ba.KV2_16 = f.KV2_16;
   ba.off = x.rg_offsets; ba.tile_off = x.bd.tile_off; ba.tile_desc = x.bd.tile_desc; ba.inv_nr = x.bd.inv_nr; ba.lse2 = f.lse2;
@@ -787,7 +590,7 @@ int forward_nodes17(Call& c, const Batch& x, float* attn_rg2kg, float* attn_kg2r
   ba.drop = x.drop; ba.save = save ? 1 : 0; ba.save_lse2 = pl.maps; ba.exp = x.opt->exp;
   ba.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)g_dbg_stamp_blocks * 8 : nullptr;
   switch (pl.back) {
-    case CAMO_BACK_RG_64: CK(launch_wide2_rgfwd(fa.s[0], f.Wf_rg, f.bf_rg, fa.qscale, ba, max_nr, pl.save_r16, st), "fused forward, RG rows in one launch (64-row half-blocks)"); break;
+    case CAMO_BACK_RG_64: CK(launch_wide2_rgfwd(fa.s[0], sh.Wf_rg, sh.bf_rg, fa.qscale, ba, max_nr, pl.save_r16, st), "fused forward, RG rows in one launch (64-row half-blocks)"); break;
     case CAMO_BACK_RG_WIDE: CK(launch_wide_rgfwd(fa.s[0], fa.qscale, ba, pl.back_rt, max_nr, st), "fused forward, RG rows in one launch (wide tiles)"); break;
     case CAMO_BACK_WIDE: CK(launch_wide_back(ba, pl.back_rt, max_nr, st), "fused forward, back half (wide tiles)"); break;
     default: CK(launch_fused_back(ba, x.opt->fused_variant, x.opt->back_lead, st), "fused forward, back half");
@@ -893,7 +696,7 @@ int backward_nodes16(const Batch& x) {
 // the per-sample tail of the fused schedule as one launch (misc.hip, tail_fused_kernel); fl == null: forward only
 int tail17(Call& c, const Batch& x, float* outs, const FusedLoss* fl) {
   const camo_dims_t& d = *x.dims; const float* const* P = x.P; float* const* Gr = x.Gr; const Ws& w = x.w; hipStream_t st = x.st;
-  const int H = 256, B = x.B;
+  const int B = x.B;
   TailFusedArgs a; std::memset(&a, 0, sizeof(a));
   a.Ymean = w.Ymean; a.H1mean = w.H1mean; a.Y2mean = w.Y2mean; a.H2mean = w.H2mean;
   a.W13 = P[CAMO_P_F1_W3]; a.b13 = P[CAMO_P_F1_B3]; a.W23 = P[CAMO_P_F2_W3]; a.b23 = P[CAMO_P_F2_B3];
@@ -911,8 +714,7 @@ int tail17(Call& c, const Batch& x, float* outs, const FusedLoss* fl) {
     a.dcomb = w.dcomb; a.dHm1 = w.dHm1; a.dHm2 = w.dHm2;
   }
   a.outs = outs;
-  a.F1sum = w.tailsum; a.hidsum = w.tailsum + (size_t)B * H; a.dF1sum = w.tailsum + (size_t)B * 3 * H;
-  a.counters = reinterpret_cast<unsigned int*>(w.tailsum + (size_t)B * 4 * H);
+  a.F1sum = w.tailsum.F1sum; a.hidsum = w.tailsum.hidsum; a.dF1sum = w.tailsum.dF1sum; a.counters = w.tailsum.counters;
   a.B = B; a.C = d.num_classes; a.mode = fl ? 1 : 0; a.drop = x.drop;
   a.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)4 * g_dbg_stamp_blocks * 8 : nullptr;
   a.debug_skip = c.tail_skip;
@@ -935,8 +737,9 @@ int tail_planes_forward(const Batch& x, float* outs, const FusedLoss* fl) {
   const bool train = x.plan.tail != CAMO_TAIL_PLANES;
   TailWideArgs ta; std::memset(&ta, 0, sizeof(ta));
   ta.Ymean = w.Ymean; ta.H1mean = w.H1mean; ta.Y2mean = w.Y2mean; ta.H2mean = w.H2mean;
-  const us* const* tw = w.f.tailw;
-  ta.T13h = tw[0]; ta.T13l = tw[1]; ta.T23h = tw[2]; ta.T23l = tw[3]; ta.Tfu0h = tw[4]; ta.Tfu0l = tw[5]; ta.Tfu3h = tw[6]; ta.Tfu3l = tw[7]; ta.Th0h = tw[8]; ta.Th0l = tw[9];
+  const Ws::F17::TailPlanes& tp = w.f.tp;
+  ta.T13h = tp.W13.hi; ta.T13l = tp.W13.lo; ta.T23h = tp.W23.hi; ta.T23l = tp.W23.lo; ta.Tfu0h = tp.Wfu0.hi; ta.Tfu0l = tp.Wfu0.lo;
+  ta.Tfu3h = tp.Wfu3.hi; ta.Tfu3l = tp.Wfu3.lo; ta.Th0h = tp.Wh0.hi; ta.Th0l = tp.Wh0.lo;
   ta.b13 = P[CAMO_P_F1_B3]; ta.b23 = P[CAMO_P_F2_B3]; ta.bfu0 = P[CAMO_P_FU_B0]; ta.bfu3 = P[CAMO_P_FU_B3];
   for (int x = 0; x < 4; ++x) { ta.bh0[x] = P[CAMO_P_HEADS + 4 * x + 1]; ta.Wh3[x] = P[CAMO_P_HEADS + 4 * x + 2]; ta.bh3[x] = P[CAMO_P_HEADS + 4 * x + 3]; }
   ta.outs = outs; ta.B = x.B; ta.C = d.num_classes; ta.drop = x.drop;
@@ -952,10 +755,10 @@ int tail_planes_backward(const Batch& x) {
   const camo_dims_t& d = *x.dims; float* const* Gr = x.Gr; const Ws& w = x.w;
   const int H = d.hidden_dim, B = x.B;
   TailWideBwdArgs ta; std::memset(&ta, 0, sizeof(ta));
-  const us* const* tw = w.f.tailw;
+  const Ws::F17::TailPlanes& tp = w.f.tp;
   ta.dhid = w.dhid; ta.F1 = w.F1;
-  ta.Th0h = tw[10]; ta.Th0l = tw[11]; ta.Tfu3h = tw[12]; ta.Tfu3l = tw[13]; ta.Tfu0h = tw[14]; ta.Tfu0l = tw[15];
-  ta.T13h = tw[16]; ta.T13l = tw[17]; ta.T23h = tw[18]; ta.T23l = tw[19];
+  ta.Th0h = tp.Wh0T.hi; ta.Th0l = tp.Wh0T.lo; ta.Tfu3h = tp.Wfu3T.hi; ta.Tfu3l = tp.Wfu3T.lo; ta.Tfu0h = tp.Wfu0T.hi; ta.Tfu0l = tp.Wfu0T.lo;
+  ta.T13h = tp.W13T.hi; ta.T13l = tp.W13T.lo; ta.T23h = tp.W23T.hi; ta.T23l = tp.W23T.lo;
   ta.dfused = w.dfused; ta.dF1 = w.dF1; ta.dcomb = w.dcomb; ta.dHm1 = w.dHm1; ta.dHm2 = w.dHm2;
   ta.B = B; ta.scale = x.drop.scale;
   CK(launch_tail_wide_bwd(ta, x.st), "per-sample tail, input gradients (wide, one launch)");
@@ -974,11 +777,11 @@ int backward_nodes17(Call& c, const Batch& x) {
   const int32_t* rg_offsets = x.rg_offsets; const Desc& bd = x.bd;
   const int H = 256, D = 128, B = x.B, T = x.T, Nk = x.Nk, TK = B * Nk;
   const size_t HH = (size_t)H * H;
-  const Ws::F17& f = w.f;
+  const Ws::F17& f = w.f; const ShadowSet& sh = f.sh;
   Bwd1Args a1; std::memset(&a1, 0, sizeof(a1));
-  a1.s[0] = Bwd1Stream{f.W1T, f.Wo1T, f.mask1, f.XH16, f.rstd1, P[CAMO_P_LN1_W], w.dHm1, 2 * H, w.dcomb, 2 * H, f.dH16, f.dU16,
+  a1.s[0] = Bwd1Stream{sh.W1T, sh.Wo1T, f.mask1, f.XH16, f.rstd1, P[CAMO_P_LN1_W], w.dHm1, 2 * H, w.dcomb, 2 * H, f.dH16, f.dU16,
                        Gr[CAMO_P_LN1_W], Gr[CAMO_P_LN1_B]};
-  a1.s[1] = Bwd1Stream{f.W2T, f.Wo2T, f.mask2, f.XH2_16, f.rstd2, P[CAMO_P_LN2_W], w.dHm2, 2 * H, w.dcomb + H, 2 * H, f.dH2_16, f.dU2_16,
+  a1.s[1] = Bwd1Stream{sh.W2T, sh.Wo2T, f.mask2, f.XH2_16, f.rstd2, P[CAMO_P_LN2_W], w.dHm2, 2 * H, w.dcomb + H, 2 * H, f.dH2_16, f.dU2_16,
                        Gr[CAMO_P_LN2_W], Gr[CAMO_P_LN2_B]};
   a1.Q16 = f.Q16; a1.KV16 = f.KV16; a1.dQKV16 = f.dQKV16; a1.dKV = w.dKV;
   a1.O2_16 = f.O2_16; a1.dO2_16 = f.dO2_16; a1.delta2 = f.delta2;
@@ -1000,8 +803,8 @@ int backward_nodes17(Call& c, const Batch& x) {
   if (pl.tail_event == CAMO_EVENT_AFTER_BWD1) CK(record_tail_event(c, st), "tail event");      // (the one-launch tail's weight gradients are final behind the launch above)
   Bwd2Args a2; std::memset(&a2, 0, sizeof(a2));
   a2.Q2_16 = f.Q2_16; a2.dO2_16 = f.dO2_16; a2.lse2 = f.lse2; a2.delta2 = f.delta2; a2.KV2_16 = f.KV2_16; a2.dQKV16 = f.dQKV16;
-  a2.dU16 = f.dU16; a2.WcRgT = f.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
-  a2.dU2_16 = f.dU2_16; a2.WcKgT = f.WcKgT; a2.dQKVkg16 = f.dQKVkg16; a2.dG16 = f.dG16; a2.dGpart = f.dGpart;
+  a2.dU16 = f.dU16; a2.WcRgT = sh.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
+  a2.dU2_16 = f.dU2_16; a2.WcKgT = sh.WcKgT; a2.dQKVkg16 = f.dQKVkg16; a2.dG16 = f.dG16; a2.dGpart = f.dGpart;
   a2.tickets = w.tickets + B; a2.off = rg_offsets; a2.tile_off = bd.tile_off; a2.tile_desc = bd.tile_desc;
   a2.B = B; a2.Nk = Nk; a2.rows_rg = T; a2.rg_tiles_max = T / 32 + B; a2.qscale = a1.qscale; a2.drop = drop;
   a2.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)3 * g_dbg_stamp_blocks * 8 : nullptr;
@@ -1022,7 +825,7 @@ int backward_nodes17(Call& c, const Batch& x) {
       // first in the launch: dW_kgproj += Wq2^T (dQ2^T KG), db_kgproj += Wq2^T colsum(dQ2) -- the part of dG^T KG that bwd2 left out of its operand (dGpart)
       Gemm16Prob& p = g.tn(nullptr, H, f.KG16, D, Gr[CAMO_P_KG_PROJ_W], D, Gr[CAMO_P_KG_PROJ_B], H, D, TK);
       p.A = reinterpret_cast<const us*>(w.dQ2acc); p.flags |= GF_A_F32 | GF_KGQ;
-      p.kgq_wT = f.WcKgT; p.kgq_w = P[CAMO_P_A2_IN_W]; p.ldg = H;
+      p.kgq_wT = sh.WcKgT; p.kgq_w = P[CAMO_P_A2_IN_W]; p.ldg = H;
       // (the workspace's record: dG16 and the dQ2 columns of dQKVkg16, which nothing in this launch reads)
       p.C16 = f.dG16; p.ldc16 = H; p.kgq_part16 = reinterpret_cast<const us*>(f.dGpart); p.kgq_a16 = f.dQKVkg16; p.kgq_lda16 = 3 * H;
     }
@@ -1049,8 +852,7 @@ int backward_nodes17(Call& c, const Batch& x) {
   //   M = dQKV^T x  [3H][D],  db_in = colsum(dQKV);   dW_in = dQKV^T R = M W_p^T + db_in b_p^T;
   //   dW_p = dR^T x = dU^T x + W_in^T M,  db_p = colsum(dU) + W_in^T db_in      (dR = dU + dQKV W_in never exists)
   // -- 131 k MACs per row (M, dU^T x) instead of 427 k (dR, dQKV^T R, dR^T x), and one small fp32 launch behind them (misc.hip, unfold_kernel).
-  float* const Mrg = w.parM; float* const Mkg = Mrg + (size_t)3 * H * D;
-  float* const dbrg = Mkg + (size_t)3 * H * D; float* const dbkg = dbrg + 3 * H;
+  float* const Mrg = w.parM.Mrg; float* const Mkg = w.parM.Mkg; float* const dbrg = w.parM.dbrg; float* const dbkg = w.parM.dbkg;
   GB16 g(drop, *x.opt, st);
   g.tn(f.dH16, 2 * H, f.Y16, H, Gr[CAMO_P_F1_W0], H, Gr[CAMO_P_F1_B0], 2 * H, H, T);
   g.tn(f.dU16, H, f.O16, H, Gr[CAMO_P_A1_OUT_W], H, Gr[CAMO_P_A1_OUT_B], H, H, T);
@@ -1426,30 +1228,19 @@ int camo_clip_adamw_shadows(const camo_dims_t* dims, const float* const* params,
   if (step < 1) return fail(CAMO_E_ARG, "step is 1-based");
   if (!fused17_dims(*dims)) return fail(CAMO_E_UNSUPPORTED, "weight shadows exist for the fused schedule's configuration only");
   if (reinterpret_cast<uintptr_t>(shadows) & 255) return fail(CAMO_E_ARG, "the shadow buffer must be 256-byte aligned");
-  const int H = 256, D = 128;
-  const size_t HH = (size_t)H * H;
   const ShadowSet x = shadow_carve(shadows);
   AdamShadowArgs a; std::memset(&a, 0, sizeof(a));
   struct Cov { size_t off, len; } cov[ADAM_SHADOW_MAXB];
   int ncov = 0;
   bool ok = true;
-  auto blk = [&](const float* src, int rows, int cols, us16* plain, int pN, int pn0, us16* trans, int tK, int tk0) {
-    if (!src || src < p || src + (size_t)rows * cols > p + n) { ok = false; return; }
+  for (const ShadowSlice& sl : k_shadow_slices) {      // one block per slice: the update leaves its rows in the shadows the forward reads them from
+    const float* src = params[sl.param] ? params[sl.param] + (size_t)sl.r0 * sl.cols : nullptr;
+    if (!src || src < p || src + (size_t)sl.rows * sl.cols > p + n) { ok = false; break; }
     AdamShadowBlock& B = a.blk[a.nblk++];
-    B.off = (size_t)(src - p); B.rows = rows; B.cols = cols; B.plain = plain; B.pN = pN; B.pn0 = pn0; B.trans = trans; B.tK = tK; B.tk0 = tk0;
-    cov[ncov++] = Cov{B.off, (size_t)rows * cols};
-  };
-  const float* const* P = params;
-  blk(P[CAMO_P_RG_PROJ_W], H, D, x.Wrg, H, 0, nullptr, 0, 0);
-  blk(P[CAMO_P_KG_PROJ_W], H, D, x.Wkg, H, 0, nullptr, 0, 0);
-  blk(P[CAMO_P_A1_IN_W], H, H, x.Wqkv_rg, 3 * H, 0, x.WcRgT, 3 * H, 0);                    // Wq1
-  blk(P[CAMO_P_A1_IN_W] ? P[CAMO_P_A1_IN_W] + HH : nullptr, 2 * H, H, x.Wqkv_kg, 3 * H, H, x.WcKgT, 3 * H, H);   // Wk1 | Wv1
-  blk(P[CAMO_P_A2_IN_W], H, H, x.Wqkv_kg, 3 * H, 0, x.WcKgT, 3 * H, 0);                    // Wq2
-  blk(P[CAMO_P_A2_IN_W] ? P[CAMO_P_A2_IN_W] + HH : nullptr, 2 * H, H, x.Wqkv_rg, 3 * H, H, x.WcRgT, 3 * H, H);   // Wk2 | Wv2
-  blk(P[CAMO_P_A1_OUT_W], H, H, x.Wo1, H, 0, x.Wo1T, H, 0);
-  blk(P[CAMO_P_A2_OUT_W], H, H, x.Wo2, H, 0, x.Wo2T, H, 0);
-  blk(P[CAMO_P_F1_W0], 2 * H, H, x.W1, 2 * H, 0, x.W1T, 2 * H, 0);
-  blk(P[CAMO_P_F2_W0], 2 * H, H, x.W2, 2 * H, 0, x.W2T, 2 * H, 0);
+    B.off = (size_t)(src - p); B.rows = sl.rows; B.cols = sl.cols; B.plain = x.*sl.plain; B.pN = sl.pN; B.pn0 = sl.pn0;
+    B.trans = sl.trans ? x.*sl.trans : nullptr; B.tK = sl.tK; B.tk0 = sl.tk0;
+    cov[ncov++] = Cov{B.off, (size_t)sl.rows * sl.cols};
+  }
   if (!ok) return fail(CAMO_E_ARG, "the shadowed parameters must lie inside the flat buffer [p, p + n)");
   // the rest of the flat buffer: the gaps between the shadowed blocks, in address order
   for (int i = 1; i < ncov; ++i)
@@ -1567,22 +1358,7 @@ int camo_prof_end(double* gemm_ms, int32_t* gemm_launches, double* gemm_flops) {
 
 int64_t camo_debug_ws_offset(const camo_dims_t* dims, int32_t B, int32_t T, int32_t Nk, const char* name) {
   if (check_dims(dims, B, T, Nk) || !name) return -1;
-  char* base = reinterpret_cast<char*>(4096);
-  const Ws w = carve(*dims, B, T, Nk, base);
-  const struct { const char* n; const void* p; } tab[] = {
-      {"R16", w.f.R16}, {"G16", w.f.G16}, {"Q16", w.f.Q16}, {"Q2_16", w.f.Q2_16}, {"KV16", w.f.KV16}, {"KV2_16", w.f.KV2_16},
-      {"O16", w.f.O16}, {"O2_16", w.f.O2_16}, {"Y16", w.f.Y16}, {"Y2_16", w.f.Y2_16}, {"XH16", w.f.XH16}, {"XH2_16", w.f.XH2_16},
-      {"rstd1", w.f.rstd1}, {"rstd2", w.f.rstd2}, {"mask1", w.f.mask1}, {"mask2", w.f.mask2}, {"lse2", w.f.lse2}, {"X16", w.f.X16},
-      {"Wqkv_rg", w.f.Wqkv_rg}, {"W1s", w.f.W1}, {"W1T", w.f.W1T}, {"WcRgT", w.f.WcRgT}, {"dH16", w.f.dH16}, {"dH2_16", w.f.dH2_16},
-      {"dU16", w.f.dU16}, {"dU2_16", w.f.dU2_16}, {"dQKV16", w.f.dQKV16}, {"dQKVkg16", w.f.dQKVkg16}, {"dR16", w.f.dR16}, {"dG16", w.f.dG16},
-      {"dO2_16", w.f.dO2_16}, {"delta2", w.f.delta2}, {"dKV", w.dKV}, {"dQ2acc", w.dQ2acc}, {"Ymean", w.Ymean}, {"H1mean", w.H1mean}, {"Y2mean", w.Y2mean}, {"H2mean", w.H2mean},
-      {"R", w.R}, {"G", w.G}, {"Q", w.Q}, {"KV2", w.KV2}, {"KV", w.KV}, {"Q2", w.Q2}, {"P", w.P}, {"P2", w.P2},
-      {"O", w.O}, {"O2", w.O2}, {"U", w.U}, {"U2", w.U2}, {"Y", w.Y}, {"Y2", w.Y2}, {"H1", w.H1}, {"H2", w.H2},
-      {"comb", w.comb}, {"fused", w.fused}, {"F1", w.F1}, {"hid", w.hid}, {"dhid", w.dhid}, {"dfused", w.dfused}, {"dF1", w.dF1},
-      {"dcomb", w.dcomb}, {"dHm1", w.dHm1}, {"dHm2", w.dHm2}};
-  for (const auto& e : tab)
-    if (std::strcmp(e.n, name) == 0 && e.p) return static_cast<const char*>(e.p) - base;
-  return -1;
+  return ws_offset_of(*dims, B, T, Nk, name);
 }
 
 int camo_debug_plan(const camo_dims_t* dims, int32_t has_projections, int32_t B, int32_t T, int32_t Nk, int32_t max_nr,
