@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_close, bf16_oracle, oracle_step_at_relu_thresholds
+from helpers import assert_attention_grad_blocks_close, assert_close, bf16_oracle, oracle_step_at_relu_thresholds, single_column_attentions
 from oracle import fusion_oracle as FO
 from oracle import params as OP
 from test_fragment_maps import frag_order
@@ -257,6 +257,7 @@ def test_fused_backward_stage_by_stage(training, wide2, kg_real, fused_opts):
     assert total < 2e-3, total
     gn = np.sqrt(den)
     assert all(r < 1e-2 for r, n, _ in rels if n > 1e-3 * gn), rels[:6]
+    assert_attention_grad_blocks_close(got_grads, ref["raw_grads"], what=f"stage by stage, training={training} wide2={wide2} param_space={param_space}")
 
 
 @pytest.mark.parametrize("training,B,ncls", [(False, 9, 2), (True, 16, 2), (True, 1, 2), (True, 6, 2), (True, 13, 2), (True, 3, 2), (True, 17, 2), (True, 40, 2), (True, 48, 2),
@@ -370,6 +371,8 @@ def _training_step_shape_envelope(nrs, nk, pseed, fused_opts, wide2):
     print(f"nrs={nrs[:6]} nk={nk} pseed={pseed}: global relative gradient error vs the bf16-operand oracle {total:.5f}; worst {per[0][1]} {per[0][0]:.4f}")
     assert total < 2e-3, (total, per[:4])
     assert per[0][0] < 1e-2, per[:4]
+    assert_attention_grad_blocks_close(grads, ref["raw_grads"], what=f"nrs={nrs[:6]} nk={nk} pseed={pseed} wide2={wide2}",
+                                       single_column=single_column_attentions(nrs, nk))
     # the same step with the projections' / in-projections' weight gradients taken in parameter space (bwd2p_kernel + unfold_kernel;
     # by size from 10 240 packed rows, forced here -- or forced OFF where the size rule took it above), against the same oracle step
     fused_opts("param_space", 0 if sum(nrs) >= 10240 else 1)
@@ -385,6 +388,8 @@ def _training_step_shape_envelope(nrs, nk, pseed, fused_opts, wide2):
     print(f"   other form of the backward: global {float(np.sqrt(num2 / den)):.5f}; worst {per2[0][1]} {per2[0][0]:.4f}")
     assert float(np.sqrt(num2 / den)) < 2e-3, per2[:4]
     assert per2[0][0] < 1e-2, per2[:4]
+    assert_attention_grad_blocks_close(grads2, ref["raw_grads"], what=f"nrs={nrs[:6]} nk={nk} pseed={pseed} wide2={wide2}, other form of the backward",
+                                       single_column=single_column_attentions(nrs, nk))
 
 
 @pytest.mark.parametrize("B,ncls", [(1, 2), (17, 2), (32, 2), (33, 3), (100, 2)])

@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from conftest import load_golden
-from helpers import assert_close, bf16_oracle, oracle_batch_step
+from helpers import assert_attention_grad_blocks_close, assert_close, bf16_oracle, oracle_batch_step
 from oracle import fusion_oracle as FO
 from oracle import params as OP
 from test_hip_parity import make_model, outs6, t2n
@@ -138,6 +138,7 @@ def _train_step_vs_bf16_oracle(B, pseed, kg_real, nrs=None):
     print(f"B = {B} (T = {sum(nrs)}) training step: global relative gradient error vs the bf16-operand oracle {total:.5f}; worst {per[:3]}")
     assert total < 2e-3, (total, per[:4])
     assert per[0][0] < 1e-2, per[:4]
+    assert_attention_grad_blocks_close(grads, want, what=f"B = {B} (T = {sum(nrs)}) training step")
     return grads, per
 
 

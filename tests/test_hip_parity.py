@@ -274,7 +274,7 @@ def test_bf16_training_step_close_to_oracle():
     step of the oracle in its bf16-operand mode, at the absolute bounds of every other bf16 training test: global relative gradient
     error < 2e-3, every tensor that carries weight < 1e-2 (round 1 asserted 5 % / 15 % here against the f32 oracle)."""
     from camouflage_multimodal_amd import NativeTrainer
-    from helpers import oracle_step_at_relu_thresholds
+    from helpers import assert_attention_grad_blocks_close, oracle_step_at_relu_thresholds
     cfg, seed, nrs, nk, kg_fixed, _ = train_case("default")
     m = make_model(cfg, seed, "bf16").train()
     tr = NativeTrainer(m, keep_grads=True)
@@ -303,6 +303,7 @@ def test_bf16_training_step_close_to_oracle():
     assert total < 2e-3
     gn = np.sqrt(den)
     assert all(r < 1e-2 for r, n, _ in rels if n > 1e-3 * gn), rels[:4]
+    assert_attention_grad_blocks_close(grads, ref["raw_grads"], what="bf16 training step, golden 'default' minibatch")
 
 
 def test_product_path_loaded_native_library():

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import load_golden
-from helpers import assert_close
+from helpers import assert_attention_grad_blocks_close, assert_close
 from oracle import fusion_oracle as FO
 from oracle import params as OP
 from test_hip_parity import make_model, outs6, t2n
@@ -61,6 +61,7 @@ def test_benchmarked_mode_bf16_dropout_b16_matches_oracle(kg_real):
     print("bf16+dropout B=16: global relative gradient error vs the bf16-operand oracle", total, "worst tensors", [(f"{r:.3f}", f"{n:.2e}", k) for r, n, k in rels[:5]])
     assert total < 2e-3                                                # (measured 4.5e-4; worst tensor ffn_kg.0.weight 0.7 %)
     assert all(r < 1.5e-2 for r, n, _ in rels if n > 1e-3 * gn)
+    assert_attention_grad_blocks_close({k: t2n(p.grad) / np.float32(coef) for k, p in m.named_parameters()}, ref["raw_grads"], what="bf16 + dropout, B = 16")
 
 
 def test_long_sequence_config_nr2048(kg_real):

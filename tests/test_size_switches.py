@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_close, oracle_batch_step
+from helpers import QK_GAIN, _log_spread, _sharp_params, assert_close, oracle_batch_step
 from oracle import fusion_oracle as FO
 from oracle import params as OP
 from test_hip_large_batch import _histogram_batch, _packed_forward, _train_step_vs_bf16_oracle
@@ -32,30 +32,6 @@ pytestmark = pytest.mark.gpu
 
 DSEED = 0x0123456789ABCDEF
 SMALL_A = dict(rg_dim=32, kg_dim=48, hidden_dim=64, num_heads=4)       # (tests/golden train_small_a: head_dim 16)
-
-
-QK_GAIN = 12.0
-
-
-def _sharp_params(cfg, seed, gain=QK_GAIN):
-    """OP.make_params with the query and key rows (weights and biases) of both attention in-projections scaled by ``gain``: every
-    attention score scales by gain^2.  At the initialisation scale the maps are uniform to within ~1 % (the log-probability spread of
-    a map row is ~0.01), so an error in the scores' arithmetic -- the 1/sqrt(d) scale, a bias, a wrong row of Q -- moves them less
-    than their bounds; with gain 12 the spread is O(1) and a 1 % error in the scale moves the maps by percents."""
-    H = cfg["hidden_dim"]
-    p = OP.make_params(cfg, seed)
-    for a in ("fusion.cross_attn_rg2kg", "fusion.cross_attn_kg2rg"):
-        for k in (a + ".in_proj_weight", a + ".in_proj_bias"):
-            v = p[k].copy()
-            v[:2 * H] *= np.float32(gain)
-            p[k] = v
-    return p
-
-
-def _log_spread(maps):
-    """Mean over map rows of max - min of log P."""
-    lp = [np.log(np.asarray(m, np.float64)) for m in maps]
-    return float(np.concatenate([x.max(1) - x.min(1) for x in lp]).mean())
 
 
 def _f32_case(cfg, pseed, nrs, nk, y=None):
