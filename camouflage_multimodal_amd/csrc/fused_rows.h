@@ -81,8 +81,19 @@ struct Bwd1Stream {
   const float* dHm; int ld_dHm;                // d(mean H)  [B][ld]: gradient w.r.t. the pooled FFN activation
   const float* dcomb; int ld_dcomb;            // d(mean Z)  [B][ld] (+ this stream's column offset): pooled residual-path gradient
   us16* dH16; us16* dU16;                      // out: [rows][512] FFN pre-activation gradient, [rows][256] LayerNorm input gradient
-  float* dgamma; float* dbeta;                 // += (atomics)
+  float* dgamma; float* dbeta;                 // += (atomics; Bwd1Args::slabs: left to the second half, which adds the slab rows)
 };
+// Per-tile slabs instead of same-address fp32 atomics at small sizes (Bwd1Args::slabs).  The first half ends every RG tile with its
+// 13 x 512 dK | dV share and every block adds 512 LayerNorm sums: at the benchmark size 1.7 M + 0.13 M atomics whose drain at the
+// memory side kept the launch open ~6 us after its last instruction.  With slabs each block stores its
+// share to rows of its own and the second half -- behind the kernel boundary, so nothing waits inside a launch -- sums them in
+// block order: slabKV [RG tile][Nk][512], summed by the KG block of the tile's sample into dKV; slabLN [block of the first half:
+// RG tiles, then the B KG blocks][dgamma 256 | dbeta 256], summed by four blocks at the end of the second half's grid.
+// By size: at most FUSED_SLAB_MAX_TILES blocks (what the workspace carves; the first half's 32-row form ends near 16 384 rows
+// anyway) and, for slabKV, at most FUSED_SLAB_MAX_NR rows in a sample: a KG block reads 26 KB per tile of its sample (a
+// 2048-row sample: 1.7 MB through one block).
+#define FUSED_SLAB_MAX_TILES 512
+#define FUSED_SLAB_MAX_NR 640
 // The one-launch tail's weight gradients (misc.hip, tail_fused_kernel, one group of B <= 16 samples): nothing of this launch waits
 // for them, so they ride as extra blocks at the end of its grid instead of sitting on the tail's dependent chain.  Product p:
 // dW[r][c] += sum_b dy[b][r] x[b][c], db[r] += sum_b dy[b][r] (fp32, b in order, plain stores: every element has one writer), on
@@ -103,6 +114,9 @@ struct Bwd1Args {
   // clears for the weight-gradient launch (pad rows of its operands) when no shadow launch did them: one extra block each
   void* zero_ptr[FUSED_BWD1_MAXZ]; unsigned zero_bytes[FUSED_BWD1_MAXZ]; int nzero;
   TailWgArgs twg;                              // the tail's weight gradients: twg.tiles blocks behind the clearing blocks
+  float* slabKV; float* slabLN; int max_nr;    // the slabs (either null: none) and the largest sample's rows
+  int slabs;                                   // bit 0: dgamma / dbeta go to slabLN, bit 1: dK | dV go to slabKV, and the second half finishes them
+                                               // (Bwd2Args::slabs).  -1: by size -- the launcher decides and leaves the bits here for the caller
 };
 int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only = 0);   // kg_only: the KG rows' blocks alone (launch_wide2_bwd1)
 // the RG rows on 64-row half-blocks (bwd_wide2.hip) + the KG rows through launch_fused_bwd1(kg_only); same arguments, outputs and saved set
@@ -117,7 +131,7 @@ struct Bwd2Args {
   us16* dQKV16;                                // [T][768]: dQ in (columns 0..255, first half), dK2|dV2 out (columns 256..767)
   const us16* dU16; const us16* WcRgT; us16* dR16;    // dR = dU + [dQ|dK2|dV2] . [Wq1; Wk2; Wv2]: shadow [256 x 768] (transposed job), out [T][256]
   float* dQ2acc;                               // [B*Nk][256] += (atomics; zeroed by the caller)
-  const float* dKV;                            // [B*Nk][512] dK|dV sums of the first half
+  float* dKV;                                  // [B*Nk][512] dK|dV sums of the first half (slabs & 2: written here, by the sample's KG block)
   const us16* dU2_16; const us16* WcKgT; us16* dQKVkg16; us16* dG16;              // KG rows: [B*Nk][768] out (weight-gradient operand), [B*Nk][256] out
   float* dGpart;                               // [B*Nk][256] fp32 scratch: the part of dG an early block computes while the RG tiles run
   int* tickets;                                // [B] zeroed arrival counters (one per sample)
@@ -130,6 +144,9 @@ struct Bwd2Args {
                                                // unwritten: the caller's weight-gradient launch takes what dQ2 adds from the fp32 sums in dQ2acc and
                                                // writes both (gemm16.h, GF_A_F32 / GF_KGQ).  -1: by size -- the launcher decides
                                                // (B Nk <= FUSED_BWD2_DEFER_MAX_TK) and leaves 0 or 1 here for the caller
+  int slabs;                                   // (row space only) what the first half left in Bwd1Args::slabs: its slabs are summed here
+  int kg_split;                                // (filled by the launcher) early blocks per sample: 4 with slabs & 2 (each sums the slab rows of four KG rows), else 1
+  const float* slabKV; const float* slabLN; float* ln_dgamma[2]; float* ln_dbeta[2];   // ... into dKV and, +=, into the two streams' LayerNorm gradients
 };
 // A GF_KGQ block of the weight-gradient launch walks all B Nk rows in 64-row steps, then one more step and an ordinary block's atomics; up to
 // this many rows that is half the 16 steps of the launch's long blocks.  Measured with row space forced: B Nk =

@@ -854,7 +854,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
     {   // dgamma: column sums of dy * xhat over the tile's rows (thread t owns feature t)
       float sum = 0.f;
       for (int r = 0; r < nrows; ++r) sum += tile32[r * PT + tid];
-      atomicAdd(S.dgamma + tid, sum);
+      if (a.slabs & 1) a.slabLN[(size_t)blockIdx.x * 512 + tid] = sum;       // (this block's row: summed by the second half)
+      else atomicAdd(S.dgamma + tid, sum);
     }
     const float rstd = S.rstd[vrow];
 #pragma unroll
@@ -880,7 +881,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
     {   // dbeta: column sums of dy
       float sum = 0.f;
       for (int r = 0; r < nrows; ++r) sum += tile32[r * PT + tid];
-      atomicAdd(S.dbeta + tid, sum);
+      if (a.slabs & 1) a.slabLN[(size_t)blockIdx.x * 512 + 256 + tid] = sum;
+      else atomicAdd(S.dbeta + tid, sum);
     }
   }
   stamp(a.stamps, 2);
@@ -989,13 +991,34 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
       dK = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sA, qB, dK, 0, 0, 0);
       dV = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pA, oB, dV, 0, 0, 0);
     }
+    if (a.slabs & 2) {
+      // this tile's share goes to its own slab rows [Nk][512]: through the wave's image region (both heads' images are dead or not
+      // yet written: the products above have consumed this head's), [dK | dV][16 keys][32 features] fp32, so that a lane stores 16
+      // bytes of one row -- write-through, behind the tile's last weight stream, where the atomics were
+      float* xs = reinterpret_cast<float*>(imgs);
+      __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int j = acc_row(i, h);
-      if (j < a.Nk) {
-        float* dst = a.dKV + ((size_t)b * a.Nk + j) * 512 + 32 * head + l31;
-        atomicAdd(dst, dK[i]);
-        atomicAdd(dst + 256, dV[i]);
+      for (int i = 0; i < 8; ++i) { xs[acc_row(i, h) * 32 + l31] = dK[i]; xs[512 + acc_row(i, h) * 32 + l31] = dV[i]; }
+      __builtin_amdgcn_wave_barrier();
+      float* slab = a.slabKV + (size_t)blockIdx.x * a.Nk * 512 + 32 * head;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int c = lane + 64 * r, j = c >> 3;                       // 16-byte chunk c of the 16 x 32 image: key j, features 4 (c & 7) ..
+          const u32x4 v = *reinterpret_cast<const u32x4*>(xs + 512 * m + 4 * c);
+          if (j < a.Nk) store16_wt(slab + (size_t)j * 512 + 256 * m + 4 * (c & 7), v);
+        }
+      __builtin_amdgcn_wave_barrier();
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int j = acc_row(i, h);
+        if (j < a.Nk) {
+          float* dst = a.dKV + ((size_t)b * a.Nk + j) * 512 + 32 * head + l31;
+          atomicAdd(dst, dK[i]);
+          atomicAdd(dst + 256, dV[i]);
+        }
       }
     }
   }
@@ -1009,8 +1032,33 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
 // The last tile of a sample to finish (arrival counter, as in the forward) runs the same product for the sample's KG rows:
 // dG = dU2 + [dQ2 | dK | dV] . [Wq2; Wk1; Wv1].  Bwd2Args::kg_defer (small batches): no arrival, no finish -- the early blocks' part of
 // dG is the projection's weight-gradient operand and the weight-gradient launch adds what dQ2 contributes (gemm16.h, GF_KGQ).
+// Bwd2Args::slabs (small sizes): the first half left its dK | dV shares and LayerNorm sums in per-block slabs (fused_rows.h); the early
+// blocks -- four per sample then -- sum the dK | dV rows into dKV, four blocks at the end of the grid add the LayerNorm rows into the gradients.
 constexpr int X_Q2S = 0, X_DO2S = 16 * PK, X_TABS = 2 * 16 * PK, X_BUFT = X_TABS + 1536, X_IMGS = X_BUFT + 32 * PQ,
               X_RED = X_IMGS + 8192, X_LDS = X_RED + 64;                                        // 76352 bytes
+
+// The first half's LayerNorm slabs (fused_rows.h, Bwd1Args::slabs): block q of the four behind the tiles takes stream q >> 1 and
+// dgamma (q & 1 == 0) or dbeta, thread = column, the stream's slab rows added in row order into the gradient (+=: nothing else of
+// the step writes it).  SLAB_ROWS loads are in flight before the first add: a row index past the end is clamped and its value cleared.
+constexpr int SLAB_ROWS = 32;
+__device__ __forceinline__ void ln_slab_sum(const Bwd2Args& a, int q) {
+  const int tid = threadIdx.x, kgs = q >> 1;
+  const int n = kgs ? a.B : a.tile_off[a.B];                     // RG stream: the real tiles (the rows behind them were never written)
+  const float* src = a.slabLN + (size_t)(kgs ? a.rg_tiles_max : 0) * 512 + 256 * (q & 1) + tid;
+  float* dst = ((q & 1) ? a.ln_dbeta[kgs] : a.ln_dgamma[kgs]) + tid;
+  float sum = 0.f;
+  for (int r0 = 0; r0 < n; r0 += SLAB_ROWS) {
+    float v[SLAB_ROWS];
+#pragma unroll
+    for (int u = 0; u < SLAB_ROWS; ++u) v[u] = src[(size_t)min(r0 + u, n - 1) * 512];
+#pragma unroll
+    for (int u = 0; u < SLAB_ROWS; ++u) sum += r0 + u < n ? v[u] : 0.f;
+  }
+  *dst += sum;
+}
+
+// Tiles of a sample's slabKV rows in flight per pass of a KG block (8 floats per lane each); 20 tiles is the largest sample that takes slabs
+constexpr int SLAB_TILES = 10;
 
 template <int DEPTH, bool ROT>
 __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
@@ -1021,22 +1069,55 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
   char* Q2s = smem + X_Q2S; char* dO2s = smem + X_DO2S; float* tabs = reinterpret_cast<float*>(smem + X_TABS);
   char* bufT = smem + X_BUFT; char* imgs = smem + X_IMGS;
   int* flag = reinterpret_cast<int*>(smem + X_RED);
+  // grid: the B early blocks, the RG tiles, then (kg_split > 1) the other early blocks of every sample and (slabs & 1) the four LayerNorm blocks
+  const int xb = (int)blockIdx.x - a.B - a.rg_tiles_max, xearly = (a.kg_split - 1) * a.B;
+  if (xb >= xearly) { ln_slab_sum(a, xb - xearly); return; }
   stamp(a.stamps, 0);
-  const bool early = (int)blockIdx.x < a.B;          // the B early blocks: the part of dG that needs no RG tile of this launch
+  const bool early = (int)blockIdx.x < a.B || xb >= 0;   // the early blocks: the part of dG that needs no RG tile of this launch
   int b;
   if (early) {
     // dGpart = dU2 + [dK | dV] . [Wk1; Wv1]  (k steps 16..47 of the [Wq2; Wk1; Wv1] stream), fp32, and the dK | dV columns of the
     // KG rows' weight-gradient operand.  Counts as one arrival of its sample.
-    b = blockIdx.x;
+    // kg_split == 4 (the dK | dV sums come from the first half's slabs): four blocks per sample, block kq takes KG rows 4 kq .. 4 kq + 3
+    // -- one row per wave, so the slab rows of a sample (26 KB per tile) come in through four CUs, in one trip each; the other rows of
+    // its operand tile are zero and it writes its own rows only
+    b = xb >= 0 ? xb % a.B : (int)blockIdx.x;
+    const int kq = xb >= 0 ? 1 + xb / a.B : 0;
+    const int r_lo = a.kg_split > 1 ? min(4 * kq, Nk) : 0, r_hi = a.kg_split > 1 ? min(4 * kq + 4, Nk) : Nk;
     const size_t krow0 = (size_t)b * Nk;
     Stage<2, 32, true, DEPTH, false> se;
     se.prefetch(reinterpret_cast<const u32x4*>(a.WcKgT) + (size_t)w * (48 * 2 * 64) + 64 * (16 * 2) + lane, 0);
+    const int t0 = a.tile_off[b], t1 = a.tile_off[b + 1];
     for (int c = tid; c < 32 * 64; c += 256) {
-      const int j = c >> 6, ch = c & 63;
+      const int j = c >> 6, ch = c & 63;                     // (j is uniform over a wave)
       u32x4 v = u32x4{0u, 0u, 0u, 0u};
-      if (j < Nk) {
-        const float* src = a.dKV + (krow0 + j) * 512 + 8 * ch;
-        const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
+      if (j >= r_lo && j < r_hi) {
+        float4 x0, x1;
+        if (a.slabs & 2) {
+          // the sample's dK | dV sums from its tiles' slab rows (the first half's, behind the kernel boundary), added in tile order;
+          // every load of a pass is in flight before the first add (a tile past the last: clamped, its values cleared)
+          x0 = x1 = make_float4(0.f, 0.f, 0.f, 0.f);
+          const float* src = a.slabKV + (size_t)j * 512 + 8 * ch;
+          for (int tb = t0; tb < t1; tb += SLAB_TILES) {
+            float4 p0[SLAB_TILES], p1[SLAB_TILES];
+#pragma unroll
+            for (int u = 0; u < SLAB_TILES; ++u) {
+              const float* s = src + (size_t)min(tb + u, t1 - 1) * Nk * 512;
+              p0[u] = *reinterpret_cast<const float4*>(s); p1[u] = *reinterpret_cast<const float4*>(s + 4);
+            }
+#pragma unroll
+            for (int u = 0; u < SLAB_TILES; ++u) {
+              const bool ok = tb + u < t1;
+              x0.x += ok ? p0[u].x : 0.f; x0.y += ok ? p0[u].y : 0.f; x0.z += ok ? p0[u].z : 0.f; x0.w += ok ? p0[u].w : 0.f;
+              x1.x += ok ? p1[u].x : 0.f; x1.y += ok ? p1[u].y : 0.f; x1.z += ok ? p1[u].z : 0.f; x1.w += ok ? p1[u].w : 0.f;
+            }
+          }
+          float* dst = a.dKV + (krow0 + j) * 512 + 8 * ch;   // the tensor every later reader of dKV sees
+          *reinterpret_cast<float4*>(dst) = x0; *reinterpret_cast<float4*>(dst + 4) = x1;
+        } else {
+          const float* src = a.dKV + (krow0 + j) * 512 + 8 * ch;
+          x0 = *reinterpret_cast<const float4*>(src); x1 = *reinterpret_cast<const float4*>(src + 4);
+        }
         v = u32x4{pack2(x0.x, x0.y), pack2(x0.z, x0.w), pack2(x1.x, x1.y), pack2(x1.z, x1.w)};
       }
       *reinterpret_cast<u32x4*>(bufT + j * PQ + 512 + 16 * ch) = v;
@@ -1044,12 +1125,12 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     __syncthreads();
     f32x16 acc[2] = {zero16(), zero16()};
     se.run(bufT + l31 * PQ + 512 + 16 * h, acc);
-    copy_out<6>(bufT, PQ, 512, a.dQKVkg16 + 256, 768, krow0, Nk);
+    copy_out<6>(bufT + r_lo * PQ, PQ, 512, a.dQKVkg16 + 256, 768, krow0 + r_lo, r_hi - r_lo);
     if (a.kg_defer) {
       // no finish in this launch: dGpart, rounded, IS the projection's weight-gradient operand (in the dGpart scratch, as bf16 rows of 256);
       // what dQ2 . Wq2 adds to that gradient is taken from the finished dQ2 sums by the weight-gradient launch
       us16* const dGp16 = reinterpret_cast<us16*>(a.dGpart);
-      if (l31 < Nk) {
+      if (l31 >= r_lo && l31 < r_hi) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1060,11 +1141,11 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
                 u32x2{pack2(acc[t][4 * g] + bf_lo(uv.x), acc[t][4 * g + 1] + bf_hi(uv.x)), pack2(acc[t][4 * g + 2] + bf_lo(uv.y), acc[t][4 * g + 3] + bf_hi(uv.y))};
           }
       }
-      if (b == a.B - 1) {                                    // the operand's pad rows (the contraction runs over whole 128-row groups)
+      if (b == a.B - 1 && kq == 0) {                         // the operand's pad rows (the contraction runs over whole 128-row groups)
         const size_t tk = (size_t)a.B * Nk, n16 = (((tk + 127) & ~size_t(127)) - tk) * 32;
         for (size_t c = tid; c < n16; c += 256) *(reinterpret_cast<u32x4*>(dGp16 + tk * 256) + c) = u32x4{0u, 0u, 0u, 0u};
       }
-    } else if (l31 < Nk) {
+    } else if (l31 >= r_lo && l31 < r_hi) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1214,7 +1295,7 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
   __syncthreads();
   if (tid == 0) flag[0] = __hip_atomic_fetch_add(a.tickets + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
-  if (flag[0] != a.tile_off[b + 1] - a.tile_off[b]) return;          // (tiles + the early block)
+  if (flag[0] != a.tile_off[b + 1] - a.tile_off[b] + a.kg_split - 1) return;      // (tiles + the early blocks)
   Stage<2, 16, true, DEPTH, false> sg;
   sg.prefetch(reinterpret_cast<const u32x4*>(a.WcKgT) + (size_t)w * (48 * 2 * 64) + lane, 0);     // k steps 0..15: Wq2
   if (tid == 0) {
@@ -1548,6 +1629,10 @@ int launch_fused_bwd1(Bwd1Args& a, int variant, hipStream_t stream, int kg_only)
     p.tile_begin = t.tiles;
     t.tiles += (p.rows / 16) * (p.cols / 256);
   }
+  // slabs instead of atomics, by size (fused_rows.h); kg_only: the RG rows' launch adds its sums with atomics, so this one does too
+  if (a.slabs < 0)
+    a.slabs = (kg_only || !a.slabKV || !a.slabLN || a.B + a.rg_tiles_max > FUSED_SLAB_MAX_TILES) ? 0 : (a.max_nr >= 1 && a.max_nr <= FUSED_SLAB_MAX_NR ? 3 : 1);
+  if (a.slabs && (kg_only || !a.slabKV || !a.slabLN || !al16(a.slabKV) || !al16(a.slabLN) || (a.slabs & ~3))) return (int)hipErrorInvalidValue;
   Bwd1Args k = a;                                                    // (the kernel decodes a block's role from rg_tiles_max)
   if (kg_only) { k.rg_tiles_max = 0; k.stamps = nullptr; }           // (the timeline region belongs to the RG rows' launch then)
   const dim3 grid(k.B + k.rg_tiles_max + k.writer_blocks + k.nzero + k.twg.tiles);
@@ -1568,6 +1653,9 @@ int launch_fused_bwd2(Bwd2Args& a, int variant, hipStream_t stream) {
       !a.dU16 || !a.WcRgT || !a.dR16 || !a.dQ2acc || !a.dKV || !a.dU2_16 || !a.WcKgT || !a.dQKVkg16 || !a.dG16 || !a.dGpart || !a.tickets || !a.off || !a.tile_off || !a.tile_desc)
     return (int)hipErrorInvalidValue;
   if (!al16(a.dQKV16) || !al16(a.dQKVkg16) || !al16(a.WcRgT) || !al16(a.WcKgT) || !al16(a.dQ2acc) || !al16(a.dKV)) return (int)hipErrorInvalidValue;
+  // the first half's slabs (Bwd1Args::slabs) are summed by bwd2_kernel alone: its early blocks (dK | dV) and four blocks behind the tiles (LayerNorm)
+  if (a.slabs && (a.param_space || (a.slabs & ~3) || !a.slabKV || !a.slabLN || !a.ln_dgamma[0] || !a.ln_dgamma[1] || !a.ln_dbeta[0] || !a.ln_dbeta[1]))
+    return (int)hipErrorInvalidValue;
   // executed FLOPs per row: dR / dG (768 -> 256) unless the caller takes those gradients in parameter space; RG rows: the KG->RG
   // attention backward (5 products of Nk x 256)
   // (kg_defer: the KG rows' product stops at its [dK | dV] columns, K = 512)
@@ -1576,7 +1664,8 @@ int launch_fused_bwd2(Bwd2Args& a, int variant, hipStream_t stream) {
   const double dr = 2.0 * ((double)a.rows_rg * 768.0 + (double)a.B * a.Nk * (a.kg_defer ? 512.0 : 768.0)) * 256.0;
   const int prof = gemm_prof_open(stream, (a.param_space ? 0.0 : dr) + 10.0 * (double)a.rows_rg * a.Nk * 256.0, PROF_BWD2);
   if (!a.param_space) a.split_finish = 0;
-  if (!a.param_space) launch_lds<bwd2_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
+  a.kg_split = (a.slabs & 2) ? 4 : 1;
+  if (!a.param_space) launch_lds<bwd2_kernel<12, false>>(dim3(a.kg_split * a.B + a.rg_tiles_max + ((a.slabs & 1) ? 4 : 0)), dim3(256), X_LDS, stream, a);
   else                launch_lds<bwd2p_kernel<12, false>>(dim3(a.B + a.rg_tiles_max), dim3(256), X_LDS, stream, a);
   if (a.split_finish) hipLaunchKernelGGL(bwd2_finish_kernel, dim3(a.B), dim3(256), 0, stream, a);
   gemm_prof_close(prof, stream);

@@ -789,6 +789,9 @@ int backward_nodes17(Call& c, const Batch& x) {
   a1.B = B; a1.Nk = Nk; a1.rows_rg = T; a1.rg_tiles_max = T / 32 + B; a1.qscale = 1.0f / sqrtf(32.0f); a1.drop = drop;
   a1.stamps = g_dbg_stamps ? g_dbg_stamps + (size_t)2 * g_dbg_stamp_blocks * 8 : nullptr;
   a1.nzero = c.nzero_bwd1; a1.exp = x.opt->exp;
+  // per-block slabs instead of atomics for dK | dV and the LayerNorm sums: by size (the launcher's rule), where the second half is the kernel that sums them
+  a1.slabKV = f.slabKV; a1.slabLN = f.slabLN; a1.max_nr = x.max_nr;
+  a1.slabs = (pl.bwd1 == CAMO_BWD1_ROWS32 && pl.bwd2 == CAMO_BWD2_ROWS32 && pl.param_space == 0) ? -1 : 0;
   for (int i = 0; i < c.nzero_bwd1; ++i) { a1.zero_ptr[i] = c.zero_bwd1_ptr[i]; a1.zero_bytes[i] = c.zero_bwd1_bytes[i]; }
   if (pl.tail_wg == CAMO_TAIL_WG_BWD1) {
     // the one-launch tail's eight big weight gradients (tail17), from the operand copies it left
@@ -804,6 +807,8 @@ int backward_nodes17(Call& c, const Batch& x) {
   Bwd2Args a2; std::memset(&a2, 0, sizeof(a2));
   a2.Q2_16 = f.Q2_16; a2.dO2_16 = f.dO2_16; a2.lse2 = f.lse2; a2.delta2 = f.delta2; a2.KV2_16 = f.KV2_16; a2.dQKV16 = f.dQKV16;
   a2.dU16 = f.dU16; a2.WcRgT = sh.WcRgT; a2.dR16 = f.dR16; a2.dQ2acc = w.dQ2acc; a2.dKV = w.dKV;
+  a2.slabs = a1.slabs; a2.slabKV = f.slabKV; a2.slabLN = f.slabLN;
+  for (int i = 0; i < 2; ++i) { a2.ln_dgamma[i] = a1.s[i].dgamma; a2.ln_dbeta[i] = a1.s[i].dbeta; }
   a2.dU2_16 = f.dU2_16; a2.WcKgT = sh.WcKgT; a2.dQKVkg16 = f.dQKVkg16; a2.dG16 = f.dG16; a2.dGpart = f.dGpart;
   a2.tickets = w.tickets + B; a2.off = rg_offsets; a2.tile_off = bd.tile_off; a2.tile_desc = bd.tile_desc;
   a2.B = B; a2.Nk = Nk; a2.rows_rg = T; a2.rg_tiles_max = T / 32 + B; a2.qscale = a1.qscale; a2.drop = drop;

@@ -150,6 +150,7 @@ struct Ws {
     // backward: the bf16 gradients that are weight-gradient operands, per-sample exchange buffers
     us16 *dH16, *dH2_16, *dU16, *dU2_16, *dQKV16, *dQKVkg16, *dR16, *dG16, *dO2_16;
     float *delta2, *dGpart;
+    float *slabKV, *slabLN;   // the first backward half's per-block shares at small sizes (fused_rows.h, FUSED_SLAB_MAX_TILES): [RG tile][Nk][2H], [block][2H]
     PadRows pad;        // of the weight-gradient operands: their contraction runs over whole 64-row tiles
     // the per-sample tail's weights (tail_wide.h): W13, W23, Wfu0 [256 x 512], Wfu3 [256 x 256], the four heads' first layers
     // stacked [512 x 256]; and their transposes, for the tail's backward
@@ -226,6 +227,9 @@ template <class C> Ws carve_with(C& c, const camo_dims_t& d, int B, int T, int N
       planes(t.W13, 2 * H * H); planes(t.W23, 2 * H * H); planes(t.Wfu0, 2 * H * H); planes(t.Wfu3, H * H); planes(t.Wh0, 2 * H * H);
       planes(t.Wh0T, 2 * H * H); planes(t.Wfu3T, H * H); planes(t.Wfu0T, 2 * H * H); planes(t.W13T, 2 * H * H); planes(t.W23T, 2 * H * H);
       carve_shadows_fold(c, f.sh);
+      // (calls with more blocks than FUSED_SLAB_MAX_TILES take no slabs: the buffers stop growing there)
+      const size_t tiles = (size_t)T / 32 + B, cap = FUSED_SLAB_MAX_TILES;
+      c(f.slabKV, (tiles < cap ? tiles : cap) * Nk * 2 * H, "slabKV"); c(f.slabLN, (tiles + B < cap ? tiles + B : cap) * 2 * H, "slabLN");
     }
   } else {
     const size_t F = H / 2, Fh = F / 2, Dc = (size_t)d.rg_dim + d.kg_dim;

@@ -82,7 +82,8 @@ for k, name in enumerate(("front", "back", "bwd1", "bwd2") if train else ("front
             print(f"    tail dW tiles: start {(s[tw, 0].min() - t0) / 100:.2f}..{(s[tw, 0].max() - t0) / 100:.2f} us, last ends at "
                   f"{(s[tw, 3].max() - t0) / 100:.2f} us; the RG tiles and KG blocks end by {(s[~tw, 3].max() - t0) / 100:.2f} us")
     elif name == "bwd2":
-        groups = [("KG blocks", idx < B), ("RG tiles", idx >= B)]
+        rgmax = sum(nrs) // 32 + B             # (behind the tiles: the other early blocks of every sample when the KG rows are split over four)
+        groups = [("KG blocks", (idx < B) | (idx >= B + rgmax)), ("RG tiles", (idx >= B) & (idx < B + rgmax))]
     else:
         groups = [("all tiles", idx >= 0)]
     for gname, sel in groups:
