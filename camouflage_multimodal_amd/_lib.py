@@ -145,6 +145,11 @@ PROTOTYPES = {
         ("camo_rg_train_bn_workspace_bytes", sz, (rgdims, i32, i32, i32)),
         ("camo_rg_loss_backward_bn", i32, (rgdims, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, f32, vp, vp, vp)),
     ),
+    "camo_rg_train_drop.h": (
+        ("camo_rg_train_drop_workspace_bytes", sz, (rgdims, i32, i32, i32, i32)),
+        ("camo_rg_loss_backward_drop", i32, (rgdims, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, f32, vp, vp,
+                                             i32, f32, f32, f32, u64, vp)),
+    ),
     "camo_rg_targets.h": (
         ("camo_rg_node_targets", i32, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
     ),

@@ -12,6 +12,9 @@ enum : uint32_t {
   SITE_HEAD0 = 6, /* +0 mask, +1 instance, +2 edge, +3 score */
   SITE_LATE0 = 10 /* +0, +1 */
 };
+// dropout sites of region-graph training (include/camo_rg_train_drop.h states the same numbers as CAMO_RGT_SITE_*; rg_abi.hip holds
+// the two to each other): after each conv's batch norm + ReLU, after relu(fc_shared), after the heads' first layers + ReLU
+enum : uint32_t { SITE_RGT_CONV0 = 32 /* +k, k = 0..3 */, SITE_RGT_SHARED = 36, SITE_RGT_HEADS = 37 };
 
 struct DropCfg {
   uint32_t seed_lo, seed_hi;

@@ -1,7 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
-// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, and the node targets from
-// ground-truth masks.
+// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
+// the node targets from ground-truth masks.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +25,7 @@
 #include "../../include/camo_rg_detect.h"
 #include "../../include/camo_rg_train.h"
 #include "../../include/camo_rg_train_bn.h"
+#include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
 
 using namespace camo_abi;
@@ -62,10 +63,16 @@ int rg_check(const camo_rg_dims_t* d, int N) {
 // x -> h[3] (conv1 .. conv4, each with its batch norm and ReLU), then fc_shared + ReLU -> emb.  bb null: batch norm on the running
 // statistics, inside the aggregation kernels.  bb given (needs the saving buffers of f): the aggregations write the raw
 // pre-activation z to xhat[k], then the statistics of z over the N rows, then xhat in place and h[k] = relu(xhat weight + bias).
+// dr given (needs the saving buffers of f; include/camo_rg_train_drop.h): h[k] and emb leave their ReLU through inverted dropout, in the
+// kernel that applies the ReLU -- the saving aggregations (frozen), bn_apply (batch statistics), the fc_shared GEMM's epilogue.  A
+// class with p == 0 runs the kernels without dropout.
 int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, const int32_t* rowptr, const int32_t* col, const float* w,
-               int N, const RgFwd& f, float* emb, hipStream_t st, const RgBatchNorm* bb = nullptr) {
+               int N, const RgFwd& f, float* emb, hipStream_t st, const RgBatchNorm* bb = nullptr, const RgDropout* dr = nullptr) {
   const int C = d.hidden, K = d.heads, In = d.in_channels;
   const bool raw = bb != nullptr;
+  if (dr && !f.m) return fail(CAMO_E_ARG, "dropout needs the saving forward");
+  const DropCfg* dconv = dr && dr->conv.p > 0.f ? &dr->conv : nullptr;
+  const bool dshared = dr && dr->shared.p > 0.f;
   auto bn = [&](int slot) { return BnEval{P[slot], P[slot + 1], P[slot + 2], P[slot + 3]}; };
   auto batch_norm = [&](int layer, int slot) -> int {      // slot: the layer's batch-norm weight
     if (!raw) return 0;
@@ -73,10 +80,10 @@ int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, c
     CK(launch_rgt_bn_stats(f.xhat[layer], N, C, bb->momentum, bb->partial, mean, mean + C,
                            bb->batch_stats ? bb->batch_stats + (size_t)layer * 2 * C : nullptr, bb->running ? bb->running[2 * layer] : nullptr,
                            bb->running ? bb->running[2 * layer + 1] : nullptr, st), "batch statistics");
-    CK(launch_rgt_bn_apply(f.xhat[layer], mean, mean + C, P[slot], P[slot + 1], f.h[layer], N, C, st), "batch norm");
+    CK(launch_rgt_bn_apply(f.xhat[layer], mean, mean + C, P[slot], P[slot + 1], f.h[layer], N, C, st, dconv, SITE_RGT_CONV0 + layer), "batch norm");
     return 0;
   };
-  GB g(make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
+  GB g(dshared ? dr->shared : make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
   // conv1: GATConv (extract_rg_embeddings.py:104) + bn1 + relu
   g.nt(x, In, P[CAMO_RG_C1_W], In, nullptr, f.Hh, K * C, N, K * C, In);
   CK(g.run(), "gat projection");
@@ -84,7 +91,8 @@ int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, c
   // Two GAT kernels on purpose: inference runs an online softmax with __expf, training a two-pass softmax with expf because its
   // backward recomputes alpha from the saved m and S.  One kernel for both would change one path's bits.
   const float* b1 = P[CAMO_RG_C1_BIAS];
-  CK(f.m ? launch_rgt_gat_forward(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.m, f.S, f.O, f.xhat[0], f.h[0], N, K, C, st, raw)
+  CK(f.m ? launch_rgt_gat_forward(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.m, f.S, f.O, f.xhat[0], f.h[0], N, K, C, st, raw,
+                                  raw ? nullptr : dconv, SITE_RGT_CONV0)
          : launch_gat_aggregate(f.Hh, f.a_src, f.a_dst, rowptr, col, b1, bn(CAMO_RG_BN1), f.h[0], N, K, C, st), "gat aggregate");
   if (int e = batch_norm(0, CAMO_RG_BN1)) return e;
   // conv2..4: GCNConv with edge weights (:108-118) + bn + relu
@@ -93,11 +101,12 @@ int rg_forward(const camo_rg_dims_t& d, const float* const* P, const float* x, c
     const int base = CAMO_RG_C2_BIAS + 6 * k;
     g.nt(f.h[k], C, P[base + 1], C, nullptr, f.xw, C, N, C, C);
     CK(g.run(), "gcn projection");
-    CK(launch_gcn_aggregate(f.xw, rowptr, col, w, f.dinv, P[base], bn(base + 2), f.xhat[k + 1], f.h[k + 1], N, C, st, raw), "gcn aggregate");
+    CK(launch_gcn_aggregate(f.xw, rowptr, col, w, f.dinv, P[base], bn(base + 2), f.xhat[k + 1], f.h[k + 1], N, C, st, raw,
+                            raw ? nullptr : dconv, SITE_RGT_CONV0 + k + 1), "gcn aggregate");
     if (int e = batch_norm(k + 1, base + 2)) return e;
   }
   // fc_shared + relu (:121)
-  g.nt(f.h[3], C, P[CAMO_RG_FC_W], C, P[CAMO_RG_FC_B], emb, C, N, C, C, GF_RELU);
+  g.nt(f.h[3], C, P[CAMO_RG_FC_W], C, P[CAMO_RG_FC_B], emb, C, N, C, C, dshared ? GF_RELU | GF_DROPOUT : GF_RELU).drop_site = SITE_RGT_SHARED;
   CK(g.run(), "fc_shared");
   return 0;
 }
@@ -455,13 +464,15 @@ size_t camo_rg_train_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_cla
   return rgt_carve(*dims, num_classes, N, nullptr).bytes;
 }
 
-// The one launch sequence of both entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
-// (its stats and partial are filled in here from the workspace).
+// The one launch sequence of all three entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
+// (its stats and partial are filled in here from the workspace).  drop: null = no dropout, else include/camo_rg_train_drop.h -- the
+// forward's eight sites, and in the backward nothing but a scale: every ReLU mask is taken from the saved, dropped activation, which
+// is > 0 exactly where the element was kept and the ReLU is open, so the mask's 1 becomes 1 / (1 - p).
 static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
                    const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
                    const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
                    const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch) {
+                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch, const RgDropout* drop = nullptr) {
   if (int e = batch ? rgtbn_check(dims, num_classes, N, E) : rgt_check(dims, num_classes, N, E)) return e;
   if (!params || !head_params || !x || !rowptr || !col || !w || !rrowptr || !rcol || !rw || !mask_t || !inst_t || !edge_t || !workspace ||
       !loss || !grads)
@@ -502,12 +513,14 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
     return 0;
   };
   constexpr int KM = GF_A_KMAJOR | GF_B_KMAJOR;   // dW = dY^T . X without atomics: one block owns an output tile over the whole contraction
-  GB g(make_drop(0, 0.f, 0), CAMO_PREC_F32, st);
+  const bool dhead = drop && drop->head.p > 0.f;
+  const float s_conv = drop ? drop->conv.scale : 1.f, s_shared = drop ? drop->shared.scale : 1.f, s_head = drop ? drop->head.scale : 1.f;
+  GB g(dhead ? drop->head : make_drop(0, 0.f, 0), CAMO_PREC_F32, st);   // (only the heads' first layers carry GF_DROPOUT in this batch)
 
   // ---- forward, saving (camo_rg_node_embeddings + camo_rg_node_heads) ----
-  if (int e = rg_forward(d, P, x, rowptr, col, w, N, ws, ws.emb, st, batch)) return e;
+  if (int e = rg_forward(d, P, x, rowptr, col, w, N, ws, ws.emb, st, batch, drop)) return e;
   CK(launch_rgt_concat_heads(HP, ws.W1, ws.b1, C, st), "head weights");
-  g.nt(ws.emb, C, ws.W1, C, ws.b1, ws.Z, units, N, units, C, GF_RELU);
+  g.nt(ws.emb, C, ws.W1, C, ws.b1, ws.Z, units, N, units, C, dhead ? GF_RELU | GF_DROPOUT : GF_RELU).drop_site = SITE_RGT_HEADS;
   CK(g.run(), "head first layers");
   CK(launch_rgt_head_logits(HP, ws.Z, ws.logits, N, C, nc, st), "head logits");
 
@@ -524,19 +537,19 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
     CK(launch_rgt_colsum_finish(ws.partial, nb, nch * Hh, RgtSegs{{GH[4 * h + 2], nullptr, nullptr, nullptr}, {0, nch * Hh, 0, 0, 0}, 1}, st),
        "head second-layer gradient");
   }
-  CK(launch_rgt_head_dz(HP, ws.Z, ws.dlogits, ws.dZ, N, C, nc, st), "head hidden gradient");
+  CK(launch_rgt_head_dz(HP, ws.Z, ws.dlogits, ws.dZ, N, C, nc, st, s_head), "head hidden gradient");
   CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dZ, units, units, N, ws.partial, st), "head first-layer bias sums");
   CK(launch_rgt_colsum_finish(ws.partial, nb, units, RgtSegs{{GH[CAMO_RGD_MASK_B1], GH[CAMO_RGD_INST_B1], GH[CAMO_RGD_EDGE_B1], nullptr},
                                                              {0, Hh, 2 * Hh, units, units}, 3}, st), "head first-layer bias sums");
   for (int h = 0; h < 3; ++h) g.add(ws.dZ + h * Hh, units, ws.emb, C, GH[4 * h], C, Hh, C, N, KM);
-  set_relu_bwd(g.nn(ws.dZ, units, ws.W1, C, ws.dA, C, N, C, units), ws.emb, C, 1.f);                 // dA = d(fc_shared pre-activation)
+  set_relu_bwd(g.nn(ws.dZ, units, ws.W1, C, ws.dA, C, N, C, units), ws.emb, C, s_shared);            // dA = d(fc_shared pre-activation)
   CK(g.run(), "head first-layer gradients");
 
   // ---- fc_shared backward ----
   CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dA, C, C, N, ws.partial, st), "fc_shared bias sums");
   CK(launch_rgt_colsum_finish(ws.partial, nb, C, RgtSegs{{G[CAMO_RGT_FC_B], nullptr, nullptr, nullptr}, {0, C, 0, 0, 0}, 1}, st), "fc_shared bias sums");
   g.add(ws.dA, C, ws.h[3], C, G[CAMO_RGT_FC_W], C, C, C, N, KM);
-  set_relu_bwd(g.nn(ws.dA, C, P[CAMO_RG_FC_W], C, ws.dB, C, N, C, C), ws.h[3], C, 1.f);              // dB = dy of bn4 (ReLU-masked)
+  set_relu_bwd(g.nn(ws.dA, C, P[CAMO_RG_FC_W], C, ws.dB, C, N, C, C), ws.h[3], C, s_conv);           // dB = dy of bn4 (ReLU-masked)
   CK(g.run(), "fc_shared gradients");
 
   // ---- conv4 .. conv2 backward: dB = dy -> dPre (in place) -> dA = dXW -> dB = dy of the layer below ----
@@ -545,7 +558,7 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
     if (int e = bn_backward(k + 1, base + 2, G[gb + 2], G[gb + 3], G[gb])) return e;
     CK(launch_rgt_gcn_backward(ws.dB, rrowptr, rcol, rw, ws.dinv, ws.dA, N, C, st), "gcn aggregate backward");
     g.add(ws.dA, C, ws.h[k], C, G[gb + 1], C, C, C, N, KM);
-    set_relu_bwd(g.nn(ws.dA, C, P[base + 1], C, ws.dB, C, N, C, C), ws.h[k], C, 1.f);
+    set_relu_bwd(g.nn(ws.dA, C, P[base + 1], C, ws.dB, C, N, C, C), ws.h[k], C, s_conv);
     CK(g.run(), "gcn projection gradients");
   }
 
@@ -585,6 +598,34 @@ int camo_rg_loss_backward_bn(const camo_rg_dims_t* dims, int32_t num_classes, co
   RgBatchNorm batch{nullptr, nullptr, running, momentum, batch_stats};
   return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
                  w_edge, workspace, workspace_bytes, loss, grads, stream, &batch);
+}
+
+// ---- The same with dropout, in either batch-norm mode (include/camo_rg_train_drop.h) ----------------------------------
+static_assert(CAMO_RGT_SITE_CONV0 == SITE_RGT_CONV0 && CAMO_RGT_SITE_SHARED == SITE_RGT_SHARED && CAMO_RGT_SITE_HEADS == SITE_RGT_HEADS &&
+              SITE_RGT_CONV0 > SITE_LATE0 + 1 && SITE_RGT_CONV0 + 4 == SITE_RGT_SHARED, "the header states common.h's site numbers; the fusion sites end at 11");
+
+size_t camo_rg_train_drop_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E, int32_t batch_stats) {
+  return batch_stats ? camo_rg_train_bn_workspace_bytes(dims, num_classes, N, E) : camo_rg_train_workspace_bytes(dims, num_classes, N, E);
+}
+
+int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                               const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                               const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                               const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                               float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
+                               int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream) {
+  if (batch_stats_mode != 0 && batch_stats_mode != 1) return fail(CAMO_E_ARG, "batch_stats_mode must be 0 (frozen statistics) or 1 (batch statistics)");
+  for (float p : {p_conv, p_shared, p_head})
+    if (!std::isfinite(p) || !(p >= 0.f && p < 1.f)) return fail(CAMO_E_ARG, "dropout rates must be finite and in [0, 1)");
+  if (batch_stats_mode == 0 && (running || batch_stats))
+    return fail(CAMO_E_ARG, "running and batch_stats must be null in batch_stats_mode 0 (frozen statistics)");
+  if (dims && N >= 1 && dims->hidden >= 2 && (long long)N * (3 * (dims->hidden / 2)) >= (1ll << 32))
+    return fail(CAMO_E_UNSUPPORTED, "N * (3 hidden / 2) must be < 2^32 (32-bit dropout element indices)");
+  RgBatchNorm batch{nullptr, nullptr, running, momentum, batch_stats};
+  const RgDropout drop{make_drop(1, p_conv, seed), make_drop(1, p_shared, seed), make_drop(1, p_head, seed)};
+  const bool any = p_conv > 0.f || p_shared > 0.f || p_head > 0.f;      // all zero: the mode's existing entry, launch for launch
+  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                 w_edge, workspace, workspace_bytes, loss, grads, stream, batch_stats_mode ? &batch : nullptr, any ? &drop : nullptr);
 }
 
 // ---- Node targets from ground-truth masks (include/camo_rg_targets.h) ------------------------------------------

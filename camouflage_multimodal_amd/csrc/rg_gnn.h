@@ -29,5 +29,7 @@ int launch_gat_aggregate(const float* Hh, const float* a_src, const float* a_dst
                          BnEval bn, float* out, int N, int heads, int C, hipStream_t stream);
 // out[i,:] = relu(bn(sum_{j->i} dinv[j] w dinv[i] XW[j,:] + bias)); xhat non-null: the instantiation that also keeps xhat [N, C].
 // raw (needs xhat): xhat[i,:] = the sum + bias and nothing else -- bn is not read and out is not written (batch-statistics training)
+// drop (needs xhat, not raw; include/camo_rg_train_drop.h): out[i, c] *= drop_mult(*drop, site, i * C + c) after the ReLU, xhat undropped
 int launch_gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw = false);
+                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw = false,
+                         const DropCfg* drop = nullptr, uint32_t site = 0);

@@ -62,10 +62,12 @@ __global__ void gat_aggregate_kernel(const float* __restrict__ Hh, const float* 
 
 // one wave per target node, 4 nodes per block.  SAVE: the training forward's instantiation, which also keeps xhat for the backward.
 // RAW (batch-statistics training, rg_train.hip): the pre-activation acc + bias goes where xhat goes; no batch norm, no ReLU, out untouched
-template <int CPL, bool SAVE, bool RAW = false>
-__global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
-                                     const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
-                                     BnEval bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
+// DROP (gcn_aggregate_drop_kernel only, with SAVE): inverted dropout on out after the ReLU, element index i * C + c; xhat stays undropped
+template <int CPL, bool SAVE, bool RAW, bool DROP>
+__device__ __forceinline__ void gcn_aggregate_body(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                   const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
+                                                   const BnEval& bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C,
+                                                   const DropCfg& drop, uint32_t site) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= N) return;
   const float di = dinv[i];
@@ -88,10 +90,27 @@ __global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __
       } else {
         const float xh = bn_xhat(acc[q] + bias[c], bn, c);
         if constexpr (SAVE) xhat[(size_t)i * C + c] = xh;
-        out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+        float y = bn_relu(xh, bn, c);
+        if constexpr (DROP) y *= drop_mult(drop, site, (uint32_t)i * (uint32_t)C + (uint32_t)c);
+        out[(size_t)i * C + c] = y;
       }
     }
   }
+}
+
+template <int CPL, bool SAVE, bool RAW = false>
+__global__ void gcn_aggregate_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                     const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
+                                     BnEval bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C) {
+  gcn_aggregate_body<CPL, SAVE, RAW, false>(XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, DropCfg{}, 0u);
+}
+
+template <int CPL>
+__global__ void gcn_aggregate_drop_kernel(const float* __restrict__ XW, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                          const float* __restrict__ w, const float* __restrict__ dinv, const float* __restrict__ bias,
+                                          BnEval bn, float* __restrict__ xhat, float* __restrict__ out, int N, int C, DropCfg drop,
+                                          uint32_t site) {
+  gcn_aggregate_body<CPL, true, false, true>(XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, drop, site);
 }
 
 // ---- CSR-by-target construction from a COO edge list (counting sort by target; one self-loop per node) ----
@@ -181,8 +200,13 @@ static void gcn_aggregate(const float* XW, const int* rowptr, const int* col, co
 }
 
 int launch_gcn_aggregate(const float* XW, const int* rowptr, const int* col, const float* w, const float* dinv, const float* bias,
-                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw) {
-  if (C > 512 || (raw && !xhat)) return (int)hipErrorInvalidValue;
+                         BnEval bn, float* xhat, float* out, int N, int C, hipStream_t stream, bool raw, const DropCfg* drop, uint32_t site) {
+  if (C > 512 || (raw && !xhat) || (drop && (raw || !xhat))) return (int)hipErrorInvalidValue;
+  if (drop) {
+    if (C <= 128) hipLaunchKernelGGL(gcn_aggregate_drop_kernel<2>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, *drop, site);
+    else          hipLaunchKernelGGL(gcn_aggregate_drop_kernel<8>, dim3((N + 3) / 4), dim3(256), 0, stream, XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, *drop, site);
+    return (int)hipGetLastError();
+  }
   auto run = raw ? (C <= 128 ? gcn_aggregate<2, true, true> : gcn_aggregate<8, true, true>) : C <= 128 ? (xhat ? gcn_aggregate<2, true> : gcn_aggregate<2, false>) : (xhat ? gcn_aggregate<8, true> : gcn_aggregate<8, false>);
   run(XW, rowptr, col, w, dinv, bias, bn, xhat, out, N, C, stream);
   return (int)hipGetLastError();

@@ -6,15 +6,20 @@
 #pragma once
 #include "rg_gnn.h"
 
+// Dropout of the training forward (include/camo_rg_train_drop.h): one DropCfg per class, all of one seed; a class with p == 0 is off
+// and runs the kernels without dropout.  The backward needs the three scales only (the saved activations are the dropped ones).
+struct RgDropout { DropCfg conv, shared, head; };
+
 constexpr int RGT_ROWS = 64;        // node rows per block of the first stage of a column sum
 inline int rgt_row_blocks(int N) { return (N + RGT_ROWS - 1) / RGT_ROWS; }
 
 // GAT aggregate that keeps what the backward needs: m, S [N, heads] softmax maximum and denominator per target and head,
 // O [N, heads, C] per-head aggregates, xhat [N, C] = (pre - mean) / sqrt(var + 1e-5), out [N, C] = relu(xhat * weight + bias_bn).
 // raw: xhat = pre and nothing else -- bn is not read and out is not written (batch statistics; m, S, O are saved all the same)
+// drop (not raw; include/camo_rg_train_drop.h): out[i, c] *= drop_mult(*drop, site, i * C + c) after the ReLU, xhat undropped
 int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
                            BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream,
-                           bool raw = false);
+                           bool raw = false, const DropCfg* drop = nullptr, uint32_t site = 0);
 // (the GCN aggregate that keeps xhat is rg_gnn.h's launch_gcn_aggregate with a non-null xhat)
 // copies the three heads' first layers into one [3 hidden / 2, hidden] weight and one [3 hidden / 2] bias
 int launch_rgt_concat_heads(const float* const* hp, float* W1, float* b1, int hidden, hipStream_t stream);
@@ -24,8 +29,9 @@ int launch_rgt_head_logits(const float* const* hp, const float* Z, float* logits
 // weight / count
 int launch_rgt_loss(const float* logits, const int* mask_t, const int* inst_t, const float* edge_t, float wm, float wi, float we, int N,
                     int nc, float* loss, float* dlogits, hipStream_t stream);
-// dZ [N, 3 hidden / 2] = (Z > 0) * dlogits_h . W2_h
-int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream);
+// dZ [N, 3 hidden / 2] = (Z > 0 ? scale : 0) * dlogits_h . W2_h   (scale: 1, or 1 / (1 - p_head) when Z is the dropped activation)
+int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream,
+                       float scale = 1.f);
 
 // partial[b, m * NB + c] = sum over the rows r of block b of A[r * lda + m] * B[r * ldb + c]   (A null: ones, MA = 1)
 int launch_rgt_cross_partial(const float* A, int lda, int MA, const float* B, int ldb, int NB, int N, float* partial, hipStream_t stream);
@@ -47,9 +53,9 @@ int launch_rgt_bn_finish(const float* partial, int nb, BnEval bn, int C, float* 
 // running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var N / (N - 1)
 int launch_rgt_bn_stats(const float* z, int N, int C, float momentum, float* partial, float* mean, float* rstd, float* batch_stats,
                         float* running_mean, float* running_var, hipStream_t stream);
-// in place zx = xhat = (z - mean) rstd; out = relu(xhat weight + bias)
+// in place zx = xhat = (z - mean) rstd; out = relu(xhat weight + bias), times drop_mult(*drop, site, r * C + c) when drop is given
 int launch_rgt_bn_apply(float* zx, const float* mean, const float* rstd, const float* weight, const float* bias, float* out, int N, int C,
-                        hipStream_t stream);
+                        hipStream_t stream, const DropCfg* drop = nullptr, uint32_t site = 0);
 // in place d = weight rstd (d - dbias / N - xhat dweight / N): dy -> dz once dweight = sum dy xhat and dbias = sum dy are finished
 int launch_rgt_bn_dz(float* d, const float* xhat, const float* weight, const float* rstd, const float* dweight, const float* dbias, int N, int C,
                      hipStream_t stream);

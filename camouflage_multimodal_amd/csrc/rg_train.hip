@@ -16,12 +16,14 @@ struct HeadPtrs { const float* p[12]; };   // CAMO_RGD_* order
 // ---- forward, saving ------------------------------------------------------------------------------------------------------
 // grid N, block 64 * heads.  Two walks over the row: the maximum, then the sums (the saved m and S are what the backward
 // recomputes alpha from, so they are taken the plain way, not online).  RAW (batch statistics): the pre-activation goes where xhat
-// goes; no batch norm, no ReLU, out untouched.
-template <int CPL, bool RAW = false>
-__global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
-                                   const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias, BnEval bn,
-                                   float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O, float* __restrict__ xhat,
-                                   float* __restrict__ out, int heads, int C) {
+// goes; no batch norm, no ReLU, out untouched.  DROP (gat_forward_drop_kernel only, not RAW; include/camo_rg_train_drop.h): inverted
+// dropout on out after the ReLU, element index i * C + c; xhat stays undropped.
+template <int CPL, bool RAW, bool DROP>
+__device__ __forceinline__ void gat_forward_body(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
+                                                 const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias,
+                                                 const BnEval& bn, float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O,
+                                                 float* __restrict__ xhat, float* __restrict__ out, int heads, int C, const DropCfg& drop,
+                                                 uint32_t site) {
   __shared__ float red[8][64 * CPL];
   const int i = blockIdx.x, k = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float ad = a_dst[i * heads + k];
@@ -58,9 +60,27 @@ __global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __
     } else {
       const float xh = bn_xhat(v / (float)heads + bias[c], bn, c);
       xhat[(size_t)i * C + c] = xh;
-      out[(size_t)i * C + c] = bn_relu(xh, bn, c);
+      float y = bn_relu(xh, bn, c);
+      if constexpr (DROP) y *= drop_mult(drop, site, (uint32_t)i * (uint32_t)C + (uint32_t)c);
+      out[(size_t)i * C + c] = y;
     }
   }
+}
+
+template <int CPL, bool RAW = false>
+__global__ void gat_forward_kernel(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
+                                   const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias, BnEval bn,
+                                   float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O, float* __restrict__ xhat,
+                                   float* __restrict__ out, int heads, int C) {
+  gat_forward_body<CPL, RAW, false>(Hh, a_src, a_dst, rowptr, col, bias, bn, m_out, S_out, O, xhat, out, heads, C, DropCfg{}, 0u);
+}
+
+template <int CPL>
+__global__ void gat_forward_drop_kernel(const float* __restrict__ Hh, const float* __restrict__ a_src, const float* __restrict__ a_dst,
+                                        const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ bias, BnEval bn,
+                                        float* __restrict__ m_out, float* __restrict__ S_out, float* __restrict__ O, float* __restrict__ xhat,
+                                        float* __restrict__ out, int heads, int C, DropCfg drop, uint32_t site) {
+  gat_forward_body<CPL, false, true>(Hh, a_src, a_dst, rowptr, col, bias, bn, m_out, S_out, O, xhat, out, heads, C, drop, site);
 }
 
 __global__ void concat_heads_kernel(HeadPtrs P, float* __restrict__ W1, float* __restrict__ b1, int H) {
@@ -175,8 +195,9 @@ __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ lo
 }
 
 // ---- dense pieces that are too thin for the GEMM --------------------------------------------------------------------------
+// scale: 1 / (1 - p_head) when Z is the dropped activation (Z > 0 then says "kept and open"), else 1
 __global__ void head_dz_kernel(HeadPtrs P, const float* __restrict__ Z, const float* __restrict__ dlogits, float* __restrict__ dZ,
-                               long long total, int H, int nc) {
+                               long long total, int H, int nc, float scale) {
   const long long idx = (long long)blockIdx.x * NT + threadIdx.x;
   if (idx >= total) return;
   const int Hh = H >> 1, units = 3 * Hh, L = 2 * nc + 1;
@@ -187,6 +208,7 @@ __global__ void head_dz_kernel(HeadPtrs P, const float* __restrict__ Z, const fl
     const float* dl = dlogits + n * L + h * nc;
     const float* W2 = P.p[4 * h + 2];
     for (int c = 0; c < nch; ++c) v = fmaf(dl[c], W2[(size_t)c * Hh + j], v);
+    v *= scale;
   }
   dZ[idx] = v;
 }
@@ -316,9 +338,12 @@ __global__ void bn_stats_finish_kernel(const float* __restrict__ partial, int nb
 // constants once and walks the block's rows (no index division; a wave's lanes stay on consecutive channels of one row).
 constexpr int BN_EW_ROWS = 16;
 
-// in place zx = xhat = (z - mean) * rstd, out = relu(xhat * weight + bias)
-__global__ void bn_apply_kernel(float* __restrict__ zx, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out, int N, int C) {
+// in place zx = xhat = (z - mean) * rstd, out = relu(xhat * weight + bias); DROP (bn_apply_drop_kernel only): out *= the keep
+// multiplier of element r * C + c
+template <bool DROP>
+__device__ __forceinline__ void bn_apply_body(float* __restrict__ zx, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                              const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out, int N, int C,
+                                              const DropCfg& drop, uint32_t site) {
   const int c = blockIdx.y * NT + threadIdx.x;
   if (c >= C) return;
   const float mu = mean[c], rs = rstd[c], g = weight[c], b = bias[c];
@@ -327,8 +352,21 @@ __global__ void bn_apply_kernel(float* __restrict__ zx, const float* __restrict_
     const size_t at = (size_t)r * C + c;
     const float xh = (zx[at] - mu) * rs;
     zx[at] = xh;
-    out[at] = fmaxf(xh * g + b, 0.f);
+    float y = fmaxf(xh * g + b, 0.f);
+    if constexpr (DROP) y *= drop_mult(drop, site, (uint32_t)r * (uint32_t)C + (uint32_t)c);
+    out[at] = y;
   }
+}
+
+__global__ void bn_apply_kernel(float* __restrict__ zx, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out, int N, int C) {
+  bn_apply_body<false>(zx, mean, rstd, weight, bias, out, N, C, DropCfg{}, 0u);
+}
+
+__global__ void bn_apply_drop_kernel(float* __restrict__ zx, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                     const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out, int N, int C,
+                                     DropCfg drop, uint32_t site) {
+  bn_apply_body<true>(zx, mean, rstd, weight, bias, out, N, C, drop, site);
 }
 
 // in place d = dz = weight rstd (dy - dbias / N - xhat dweight / N), dweight and dbias being the finished column sums
@@ -467,8 +505,13 @@ HeadPtrs head_ptrs(const float* const* hp) {
 
 int launch_rgt_gat_forward(const float* Hh, const float* a_src, const float* a_dst, const int* rowptr, const int* col, const float* bias,
                            BnEval bn, float* m, float* S, float* O, float* xhat, float* out, int N, int heads, int C, hipStream_t stream,
-                           bool raw) {
-  if (heads < 1 || heads > 8 || C > 512) return (int)hipErrorInvalidValue;
+                           bool raw, const DropCfg* drop, uint32_t site) {
+  if (heads < 1 || heads > 8 || C > 512 || (drop && raw)) return (int)hipErrorInvalidValue;
+  if (drop) {
+    if (C <= 128) hipLaunchKernelGGL(gat_forward_drop_kernel<2>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C, *drop, site);
+    else          hipLaunchKernelGGL(gat_forward_drop_kernel<8>, dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C, *drop, site);
+    return (int)hipGetLastError();
+  }
   if (raw) {
     if (C <= 128) hipLaunchKernelGGL((gat_forward_kernel<2, true>), dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
     else          hipLaunchKernelGGL((gat_forward_kernel<8, true>), dim3(N), dim3(64 * heads), 0, stream, Hh, a_src, a_dst, rowptr, col, bias, bn, m, S, O, xhat, out, heads, C);
@@ -496,9 +539,10 @@ int launch_rgt_loss(const float* logits, const int* mask_t, const int* inst_t, c
   return (int)hipGetLastError();
 }
 
-int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream) {
+int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream,
+                       float scale) {
   const long long total = (long long)N * 3 * (hidden / 2);
-  hipLaunchKernelGGL(head_dz_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, stream, head_ptrs(hp), Z, dlogits, dZ, total, hidden, nc);
+  hipLaunchKernelGGL(head_dz_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, stream, head_ptrs(hp), Z, dlogits, dZ, total, hidden, nc, scale);
   return (int)hipGetLastError();
 }
 
@@ -537,9 +581,10 @@ int launch_rgt_bn_stats(const float* z, int N, int C, float momentum, float* par
 }
 
 int launch_rgt_bn_apply(float* zx, const float* mean, const float* rstd, const float* weight, const float* bias, float* out, int N, int C,
-                        hipStream_t stream) {
-  hipLaunchKernelGGL(bn_apply_kernel, dim3((N + BN_EW_ROWS - 1) / BN_EW_ROWS, (C + NT - 1) / NT), dim3(NT), 0, stream, zx, mean, rstd, weight, bias,
-                     out, N, C);
+                        hipStream_t stream, const DropCfg* drop, uint32_t site) {
+  const dim3 grid((N + BN_EW_ROWS - 1) / BN_EW_ROWS, (C + NT - 1) / NT);
+  if (drop) hipLaunchKernelGGL(bn_apply_drop_kernel, grid, dim3(NT), 0, stream, zx, mean, rstd, weight, bias, out, N, C, *drop, site);
+  else      hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(NT), 0, stream, zx, mean, rstd, weight, bias, out, N, C);
   return (int)hipGetLastError();
 }
 

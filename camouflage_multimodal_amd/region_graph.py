@@ -9,8 +9,9 @@ tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here,
 runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py).  ``loss_and_gradients``
 gives the loss on the heads and every parameter's gradient with the batch-norm statistics frozen (``camo_rg_loss_backward``,
 include/camo_rg_train.h) or, with ``batch_stats=True``, on the statistics of the call's own nodes, the running statistics updated
-(``camo_rg_loss_backward_bn``, include/camo_rg_train_bn.h); dropout (models/region_graph/train.py) is outside the path, so
-``forward`` in training mode raises.
+(``camo_rg_loss_backward_bn``, include/camo_rg_train_bn.h), and with ``dropout=`` under inverted dropout at the model's eight sites
+(``camo_rg_loss_backward_drop``, include/camo_rg_train_drop.h).  A training-mode logits entry is not built: ``forward`` in training
+mode raises.
 """
 from __future__ import annotations
 
@@ -502,9 +503,26 @@ class RegionGraphGNN(nn.Module):
                 bufs.append(t)
         return (C.c_void_p * 8)(*[t.data_ptr() for t in bufs]), bufs, float(mom.pop())
 
+    @staticmethod
+    def _dropout_rates(dropout):
+        """``dropout`` (None, a float for all three classes, or a (p_conv, p_shared, p_head) triple) -> the triple as the fp32 values
+        the library receives, or None when every rate is 0.  Each rate must be finite and in [0, 1): ``ValueError`` otherwise."""
+        if dropout is None:
+            return None
+        try:
+            rates = tuple(float(v) for v in dropout) if isinstance(dropout, (tuple, list)) else (float(dropout),) * 3
+        except (TypeError, ValueError):
+            raise ValueError(f"dropout must be a float or a (p_conv, p_shared, p_head) triple, got {dropout!r}") from None
+        if len(rates) != 3:
+            raise ValueError(f"dropout must be a float or a (p_conv, p_shared, p_head) triple, got {dropout!r}")
+        rates = tuple(C.c_float(v).value for v in rates)                        # what the C ABI sees
+        if any(not (0.0 <= v < 1.0) for v in rates):                            # (NaN and the infinities fail the comparison)
+            raise ValueError(f"every dropout rate must be finite and in [0, 1), got {dropout!r}")
+        return rates if any(v > 0.0 for v in rates) else None
+
     @torch.no_grad()
     def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None,
-                               batch_stats=False, update_running=True, stats_out=None):
+                               batch_stats=False, update_running=True, stats_out=None, dropout=None, seed=0):
         """``loss_and_gradients`` on CSR arrays the caller built: ``csr`` = (rowptr, col, w) by target, ``reversed_csr`` the same
         for the graph with every edge turned round (both from ``build_target_csr_device``; they must hold the same edges).  One
         library call (``camo_rg_loss_backward``, include/camo_rg_train.h).  Returns (loss fp32 [4] = total, mask, instance, edge;
@@ -514,11 +532,22 @@ class RegionGraphGNN(nn.Module):
         not written.
 
         ``batch_stats=True``: the four batch norms normalise by the statistics of this call's nodes (``camo_rg_loss_backward_bn``,
-        include/camo_rg_train_bn.h) -- ``model.train()`` arithmetic without dropout; the four conv-bias gradients are then exactly
+        include/camo_rg_train_bn.h) -- ``model.train()`` arithmetic, without dropout unless ``dropout`` is given; the four conv-bias gradients are then exactly
         +0.  With ``update_running`` the modules' ``running_mean`` / ``running_var`` are updated in place with the modules'
         ``momentum`` and ``num_batches_tracked`` goes up by one, on the device.  ``stats_out``: a contiguous fp32 device tensor
         [4, 2, hidden] that receives the batch mean and biased variance of each layer.  With the default ``batch_stats=False``
-        neither of the two is looked at and nothing changes, whatever the module's mode."""
+        neither of the two is looked at and nothing changes, whatever the module's mode.
+
+        ``dropout``: a float (all three classes) or a triple (p_conv, p_shared, p_head) of rates in [0, 1) -- inverted dropout after the
+        four conv blocks, after ``relu(fc_shared)`` and after the heads' first layers (``camo_rg_loss_backward_drop``,
+        include/camo_rg_train_drop.h), in whichever batch-norm mode ``batch_stats`` selects; with ``batch_stats=True`` this is the whole
+        of ``model.train()`` arithmetic.  The masks are a function of ``seed`` (a 64-bit integer), the site and the element index:
+        the same seed on the same arrays gives the same bytes, so a caller that wants fresh masks passes a new seed per step.
+        ``None``, 0 or all zeros: the calls above, unchanged.  A bad rate raises ``ValueError`` before any device work."""
+        rates = self._dropout_rates(dropout)
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
         _lib.require_device(x, "x")
         if x.dim() != 2 or x.shape[1] != self._dims.in_channels or x.shape[0] < 1:
             raise RuntimeError(f"x of shape {tuple(x.shape)} does not match in_channels {self._dims.in_channels}")
@@ -575,6 +604,19 @@ class RegionGraphGNN(nn.Module):
         htab, hkeep = self._head_table()
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         with torch.cuda.device(dev):
+            if rates is not None:
+                rc = _lib.lib().camo_rg_loss_backward_drop(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
+                                                           _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
+                                                           _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab,
+                                                           momentum if batch_stats else 0.0, rtab if batch_stats else None,
+                                                           None if stats_out is None or not batch_stats else _ptr(stats_out),
+                                                           1 if batch_stats else 0, rates[0], rates[1], rates[2], seed, _stream_ptr(dev))
+                _lib.check(rc, "camo_rg_loss_backward_drop")
+                if batch_stats and update_running:
+                    for bn in self._batch_norms():
+                        if bn.num_batches_tracked is not None:
+                            bn.num_batches_tracked.add_(1)
+                return loss, grads
             if batch_stats:
                 rc = _lib.lib().camo_rg_loss_backward_bn(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
                                                          _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
@@ -594,7 +636,7 @@ class RegionGraphGNN(nn.Module):
 
     @torch.no_grad()
     def loss_and_gradients(self, data, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), accumulate=False, csr=None,
-                           batch_stats=False, update_running=True):
+                           batch_stats=False, update_running=True, dropout=None, seed=0):
         """Loss on the three node heads and the gradient of every trainable parameter, with the BatchNorm layers on their running
         statistics and dropout off: eval-mode arithmetic (like ``node_probabilities``, whatever the module's mode) plus a backward --
         fine-tuning with frozen statistics (include/camo_rg_train.h).  ``data``: a ``RegionGraphData`` or ``RegionGraphBatch`` (the
@@ -608,7 +650,9 @@ class RegionGraphGNN(nn.Module):
         ``build_target_csr_device`` of this graph, for a graph that is trained on again and again; the builder leaves a row's edges in
         no particular order, so only calls on the same pair are sure to add in the same order and give the same bytes.
         ``batch_stats=True``: batch norm on the statistics of the call's nodes, the running statistics updated in place unless
-        ``update_running`` is false (see ``loss_and_gradients_csr``); a block-diagonal batch is one population."""
+        ``update_running`` is false (see ``loss_and_gradients_csr``); a block-diagonal batch is one population.
+        ``dropout`` / ``seed``: inverted dropout at the model's eight sites (see ``loss_and_gradients_csr``); the default is none."""
+        self._dropout_rates(dropout)                                             # a bad rate raises before the CSRs are built
         x, edge_index = data.x, data.edge_index
         edge_attr = getattr(data, "edge_attr", None)
         _lib.require_device(x, "x")
@@ -619,7 +663,7 @@ class RegionGraphGNN(nn.Module):
             csr = (build_target_csr_device(n, edge_index, ew), build_target_csr_device(n, edge_index.flip(0), ew))
         csr, rcsr = csr
         loss, grads = self.loss_and_gradients_csr(x, csr, rcsr, mask_target, instance_target, edge_target, loss_weights,
-                                                  batch_stats=batch_stats, update_running=update_running)
+                                                  batch_stats=batch_stats, update_running=update_running, dropout=dropout, seed=seed)
         for p, g in zip(self.trainable_parameters(), grads):
             g = g.to(p.dtype)
             if accumulate and p.grad is not None:
@@ -630,12 +674,14 @@ class RegionGraphGNN(nn.Module):
 
     def forward(self, data):
         """Eval mode: (mask_logits [n, c], instance_logits [n, c], edge_logits [n, 1]), views of one tensor.  Training mode raises:
-        the forward with batch statistics and dropout (train.py) is outside the MI355X path; ``loss_and_gradients`` gives the loss and
-        the gradients with the statistics frozen."""
+        a training-mode LOGITS entry (batch statistics and dropout without the loss and the backward) is not built -- training runs
+        through ``loss_and_gradients``, which gives the loss and every gradient in one call, with the statistics frozen or with
+        ``batch_stats=True`` and ``dropout=`` for the whole of ``model.train()`` arithmetic."""
         if self.training:
-            raise _lib.CamoError("RegionGraphGNN.forward in training mode: training the RG model (models/region_graph/train.py) is "
-                                 "outside the MI355X path; call .eval() for the node-classification heads, or use extract_node_embeddings() "
-                                 "(loss_and_gradients() gives the loss and gradients with the batch-norm statistics frozen)")
+            raise _lib.CamoError("RegionGraphGNN.forward in training mode: a training mode logits entry is outside the MI355X path (a "
+                                 "different feature from training itself); call .eval() for the node-classification heads, or use "
+                                 "extract_node_embeddings().  To train, call loss_and_gradients(): the loss and gradients with the batch-norm "
+                                 "statistics frozen, or with batch_stats=True and dropout=(p_conv, p_shared, p_head) as under model.train()")
         logits, _ = self.node_heads(self.extract_node_embeddings(data))
         c = self.num_classes
         return logits[:, :c], logits[:, c:2 * c], logits[:, 2 * c:]

@@ -4,7 +4,8 @@ What models/region_graph/train.py does around its forward and backward, with the
 path of ``RegionGraphGNN.loss_and_gradients``): ``node_targets_from_masks`` turns ground-truth masks into one target per superpixel
 for the three node heads (``camo_rg_node_targets``, three launches), ``prepare_finetune_batch`` builds everything a step reads from
 a batch of images once, and ``RegionGraphFineTuner`` holds the 32 trainable parameters in one flat buffer and takes a step as one
-``camo_rg_loss_backward`` plus the two launches of the clip + AdamW pair of optim.py.  PARITY UNPINNED: the reference's CODDataset
+``camo_rg_loss_backward`` plus the two launches of the clip + AdamW pair of optim.py (``batch_norm="batch"`` and ``dropout=`` switch the
+step to batch statistics and to dropout: include/camo_rg_train_bn.h, include/camo_rg_train_drop.h).  PARITY UNPINNED: the reference's CODDataset
 cannot be read here, so the header's text defines the targets.  There is no CPU path: tensors that are not on a HIP device raise.
 """
 from __future__ import annotations
@@ -138,13 +139,19 @@ class RegionGraphFineTuner(AdamWStateMixin):
     32 parameters, with no host synchronisation.  The running statistics are buffers of the model and are never written --
     unless ``batch_norm="batch"``: a step is then ``camo_rg_loss_backward_bn`` (batch statistics, include/camo_rg_train_bn.h), which
     updates the four layers' running statistics in place, the only thing outside the flat buffers that a step writes.
-    ``batch_norm="frozen"`` (the default) is the frozen path; any other value raises."""
+    ``batch_norm="frozen"`` (the default) is the frozen path; any other value raises.
+    ``dropout`` (a float or a (p_conv, p_shared, p_head) triple; ``None``, the default, is none) makes a step
+    ``camo_rg_loss_backward_drop`` (include/camo_rg_train_drop.h) in the chosen batch-norm mode; the step that follows ``step_count``
+    finished steps draws its masks from seed ``seed + step_count`` -- a host counter, no synchronisation -- and ``step_count`` is what
+    ``state_dict`` / ``load_state_dict`` already carry, so a resumed run continues the mask sequence."""
 
     def __init__(self, rg_model, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, loss_weights=(1.0, 1.0, 1.0),
-                 batch_norm="frozen"):
+                 batch_norm="frozen", dropout=None, seed=0):
         if batch_norm not in ("frozen", "batch"):
             raise ValueError(f'batch_norm must be "frozen" or "batch", got {batch_norm!r}')
         self.batch_norm = batch_norm
+        rg_model._dropout_rates(dropout)                            # a bad rate raises here, not at the first step
+        self.dropout, self.seed = dropout, int(seed)
         self.model = rg_model
         self.base_lr = self.lr = float(lr)
         self.weight_decay, self.betas, self.eps, self.max_norm = float(weight_decay), tuple(betas), float(eps), float(max_norm)
@@ -192,7 +199,8 @@ class RegionGraphFineTuner(AdamWStateMixin):
         self._check_resident()
         loss, _ = self.model.loss_and_gradients_csr(batch.graphs.x, batch.csr, batch.reversed_csr, batch.mask_target, batch.instance_target,
                                                     batch.edge_target, self.loss_weights, out=self.flat_grads,
-                                                    batch_stats=self.batch_norm == "batch")
+                                                    batch_stats=self.batch_norm == "batch", dropout=self.dropout,
+                                                    seed=(self.seed + self.step_count) & 0xFFFFFFFFFFFFFFFF)
         p, g, (m, v, ss) = self.flat_params, self.flat_grads, self._state()
         self.step_count += 1
         L = _lib.lib()

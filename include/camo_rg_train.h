@@ -4,7 +4,7 @@
  * The first slice of training the reference's RegionGraphGNN (models/region_graph/train.py): the loss on the three node heads and
  * the whole backward of the network, with every BatchNorm1d using its running statistics and every dropout layer the identity --
  * model.eval() arithmetic plus gradients, i.e. fine-tuning with frozen statistics.  Batch-statistics batch norm and dropout are NOT
- * here.  The node targets come from ground-truth masks through the entry point of camo_rg_targets.h; the optimizer step is
+ * here (camo_rg_train_bn.h, camo_rg_train_drop.h).  The node targets come from ground-truth masks through the entry point of camo_rg_targets.h; the optimizer step is
  * camo_grad_sumsq + camo_clip_adamw of camo_fusion.h on one flat buffer of these gradients, and any other optimizer
  * can step on the gradient buffers this call writes.
  * PARITY UNPINNED: the reference tree and torch_geometric are absent here, train.py (its loss weights, its targets) cannot be read

@@ -4,7 +4,7 @@
  * The second slice of training the reference's RegionGraphGNN (models/region_graph/train.py, which trains under model.train()):
  * camo_rg_train.h's call with every BatchNorm1d normalising by the statistics of the call's own nodes and updating its running
  * statistics, so that training from fresh weights produces the statistics the inference path (camo_rg_node_embeddings) reads.
- * Dropout is NOT here: every dropout layer is the identity, as in camo_rg_train.h.
+ * Dropout is NOT here: every dropout layer is the identity, as in camo_rg_train.h (camo_rg_train_drop.h is this call with dropout).
  * PARITY UNPINNED: the reference tree and torch_geometric are absent here, train.py cannot be read and no region-graph checkpoint
  * ships.  The text below is the definition; it is restated in torch float64 on the fp32 inputs in tests/rg_train_bn_ref.py, whose
  * batch-norm step is held to torch.nn.functional.batch_norm(training=True) and whose autograd gradients the kernels are tested

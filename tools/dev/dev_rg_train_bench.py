@@ -1,7 +1,8 @@
 """Developer aid / measurement of the Region-Graph GNN's loss and gradients with frozen batch norm: one
 loss_and_gradients call against extract_node_embeddings + node_heads on the same graphs, in the same run, at 16 and at 128 graphs of
 ~410 nodes.  --bn adds the batch-statistics call (running statistics updated) beside the frozen one, in the same run.
-  python tools/dev/dev_rg_train_bench.py [--bn] [graphs_per_batch ...]"""
+--dropout P adds the call with dropout P in all three classes beside the p = 0 call of each mode, in the same run.
+  python tools/dev/dev_rg_train_bench.py [--bn] [--dropout P] [graphs_per_batch ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -18,9 +19,13 @@ def timed(fn, it=30, warm=5):
     return (time.perf_counter() - t0) / it
 
 
-BN = "--bn" in sys.argv[1:]
+ARGS = sys.argv[1:]
+BN = "--bn" in ARGS
+DROP = float(ARGS[ARGS.index("--dropout") + 1]) if "--dropout" in ARGS else 0.0
+if "--dropout" in ARGS:
+    del ARGS[ARGS.index("--dropout"):ARGS.index("--dropout") + 2]
 m = RegionGraphGNN().cuda().eval()
-for G in [int(a) for a in sys.argv[1:] if a != "--bn"] or [16, 128]:
+for G in [int(a) for a in ARGS if a != "--bn"] or [16, 128]:
     gs = [RO.make_graph(int(n), seed=i) for i, n in enumerate(np.random.RandomState(0).randint(303, 518, size=G))]
     off = np.cumsum([0] + [g[0].shape[0] for g in gs])
     x = torch.from_numpy(np.concatenate([g[0] for g in gs])).cuda()
@@ -38,3 +43,11 @@ for G in [int(a) for a in sys.argv[1:] if a != "--bn"] or [16, 128]:
     if BN:
         bn = timed(lambda: m.loss_and_gradients(data, mt, it_, et, batch_stats=True))
         print(f"    with batch statistics {bn * 1e6:.1f} us = {bn / trn:.2f} x the frozen call, + {(bn - trn) * 1e6:.1f} us")
+    if DROP > 0:
+        # p = 0 and p = DROP interleaved, twice: what the second round repeats is the difference, what it does not is drift
+        for name, kw in (("frozen", {}),) + ((("batch statistics", dict(batch_stats=True)),) if BN else ()):
+            for rnd in (1, 2):
+                base = timed(lambda: m.loss_and_gradients(data, mt, it_, et, **kw))
+                drp = timed(lambda: m.loss_and_gradients(data, mt, it_, et, dropout=DROP, seed=rnd, **kw))
+                print(f"    {name}, round {rnd}: p = 0 {base * 1e6:.1f} us, dropout {DROP:g} {drp * 1e6:.1f} us = {drp / base:.3f} x, "
+                      f"+ {(drp - base) * 1e6:.1f} us")
