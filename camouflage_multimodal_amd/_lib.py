@@ -27,6 +27,10 @@ RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
 RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
 RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
 RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
+SEG_BINS = 256                      # CAMO_SEG_BINS
+SEG_QUADRANTS = 4                   # CAMO_SEG_QUADRANTS
+SEG_HIST_INTS = 2048                # CAMO_SEG_HIST_INTS
+SEG_WF_MAX_SIDE = 2048              # CAMO_SEG_WF_MAX_SIDE
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -152,6 +156,11 @@ PROTOTYPES = {
     ),
     "camo_rg_targets.h": (
         ("camo_rg_node_targets", i32, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
+    ),
+    "camo_seg_measures.h": (
+        ("camo_seg_histograms", i32, (vp, i64, vp, i32, i32, i32, vp, vp, vp)),
+        ("camo_seg_weighted_f_workspace_bytes", sz, (i32, i32, i32)),
+        ("camo_seg_weighted_f", i32, (vp, i64, vp, i32, i32, i32, vp, vp, sz, vp, vp)),
     ),
 }
 

@@ -1,4 +1,4 @@
-// Host-side vocabulary of the C ABI files (fusion_abi.hip with its workspace layout fusion_ws.h, rg_abi.hip): the error return, the
+// Host-side vocabulary of the C ABI files (fusion_abi.hip with its workspace layout fusion_ws.h, rg_abi.hip, seg_measures.hip): the error return, the
 // workspace carver and the builder of an exact-fp32 GEMM batch.  No device code.
 #pragma once
 #include <cstring>

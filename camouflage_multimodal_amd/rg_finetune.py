@@ -217,7 +217,10 @@ class RegionGraphFineTuner(AdamWStateMixin):
         return self.step(prepare_finetune_batch(images, gt_masks, instance_masks, edge_masks, n_segments, band_permille,
                                                 self.flat_params.device, edge_min_pixels))
 
-    def evaluate(self, images, gt_masks, n_segments=500, threshold=0.5):
-        """``detect_camouflage_batch``'s metrics of the model as it is now: a list of ``segmentation_metrics`` dicts, one per image."""
+    def evaluate(self, images, gt_masks, n_segments=500, threshold=0.5, cod_metrics=False):
+        """``detect_camouflage_batch``'s metrics of the model as it is now: a list of ``segmentation_metrics`` dicts, one per image.
+        With ``cod_metrics=True`` a dict instead: that list under "metrics" and, under "cod_metrics", the list of the benchmark
+        measures (S-alpha, E-phi, F-beta, MAE on the 8-bit map, ``wf``) of ``seg_measures.cod_metrics``."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
-        return detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device)["metrics"]
+        out = detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device, cod_metrics)
+        return {"metrics": out["metrics"], "cod_metrics": out["cod_metrics"]} if cod_metrics else out["metrics"]

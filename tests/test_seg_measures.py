@@ -1,0 +1,392 @@
+"""The camouflaged-object benchmark measures (include/camo_seg_measures.h) against tests/seg_measures_ref.py: the
+histogram table and everything taken from it (the weighted F-measure: test_seg_weighted_f.py).
+
+PARITY UNPINNED (utils/metrics.py and the usual toolkits cannot be read here): the header is the definition and the numpy
+restatement from the pixel arrays the checker.  CPU tests hold the restatement to hand cases, the host ratios taken from a table to
+the restatement's ratios taken from the pixels (1e-12 absolute: both are float64 formulas of about 20 operations on values in
+[0, 1], whose rounding is of order 1e-15), the split rule at its ties and the library's argument checks to the header.  GPU tests
+hold the kernels to the restatement: hist and split equal, integer for integer; two calls the same bytes; a batch the rows of its
+images; a channel of [N, 3, H, W] read in place.
+
+Hand cases (n pixels, G positive; eps terms left out).  E-phi of a perfect binary prediction is n / (n - 1): phi = 1 on every pixel
+and the header divides by n - 1 + eps, so "1" is reached only in the limit of large images -- 4/3 at 2 x 2, 12/11 at 3 x 4.
+  2 x 2, gt = one pixel at (0, 0), split (1, 1), every quadrant one pixel:
+    perfect   MAE8 0; F(t >= 1) = 1, F(0) = 1.3 * (1/4) / (0.3/4 + 1) = 13/43; E(t >= 1) = 4/3; S_o = S_r = 1 (one-pixel quadrants
+              have zero centred sums: ssim 1), S = 1.
+    inverted  MAE8 1; TP = 0 for t >= 1, so f_max = F(0) = 13/43 and f_adp = 0; E(0) = (phi(0, 3/4) + 3 phi(0, -1/4)) / 3 = 1/3;
+              both object means are 0 so S_o = 0, S_r = 1 as before, S = 1/2.
+  3 x 4, gt = columns 1..2 of rows 0..1 (Sx / G = 6/4: a tie, to the even 2, X = 3; Sy / G = 2/4: a tie, to 0, Y = 1):
+    perfect   f_max = 1, e_max = 12/11, S = 1, MAE8 0.
+    inverted  MAE8 1, f_adp = 0, S clipped to 0 (negative covariances).
+    constant 0.5: q = rint(127.5) = 128 (the even neighbour); MAE8 = (8 * 128 + 4 * 127) / 3060; F(t <= 128) = 1.3 / 3 / 1.1 = 13/33
+              and 0 above; the adaptive bound min(2 * 1536, 3060) = 3060 gives t_a = 255: nothing predicted, f_adp = 0.
+    all background, pred = (0.2, 0, 0, 0) per row (q = 51): S = 1 - 153/3060 = 0.95 = 1 - MAE8; E = 0 at t = 0, 9/11 for t = 1..51,
+              12/11 above; t_a = ceil(306 / 12) = 26, e_adp = 9/11; F = 1 where nothing is predicted (t >= 52): f_mean = 204/256.
+    all foreground, pred = (0.2, 1, 1, 1) per row: S = (3 * 51 + 9 * 255) / 3060 = 0.8, MAE8 0.2.
+"""
+import ctypes
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import seg_measures_ref as R
+from conftest import ROOT
+from oracle import rg_features_oracle as FO
+
+KEYS = ("s_measure", "e_max", "e_mean", "e_adp", "f_max", "f_mean", "f_adp", "mae_u8")
+G34 = np.array([[0, 255, 255, 0], [0, 255, 255, 0], [0, 0, 0, 0]], np.uint8)
+G22 = np.array([[255, 0], [0, 0]], np.uint8)
+
+
+def _pkg(pred, gt, curves=True):
+    """The package's host ratios of one image, from the restatement's table (no device)."""
+    from camouflage_multimodal_amd import cod_measures
+    pred, gt = np.asarray(pred, np.float32), np.asarray(gt, np.uint8)
+    hist, split = R.table(pred[None], gt[None])
+    return cod_measures(hist.tolist(), split.tolist(), pred.shape[0], pred.shape[1], curves=curves)[0]
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------------
+
+def test_header_binding_and_constants():
+    from camouflage_multimodal_amd import _lib
+    import camouflage_multimodal_amd as pkg
+    hdr = open(os.path.join(ROOT, "include", "camo_seg_measures.h")).read()
+    assert "PARITY UNPINNED" in hdr and "utils/metrics.py" in hdr and "min-max" in hdr
+    assert _lib.symbols("camo_seg_measures.h") == ("camo_seg_histograms", "camo_seg_weighted_f_workspace_bytes", "camo_seg_weighted_f")
+    assert _lib.ABI_VERSION == 13 and _lib.lib().camo_abi_version() == 13
+    for name in ("SEG_BINS", "SEG_QUADRANTS", "SEG_HIST_INTS", "SEG_WF_MAX_SIDE"):
+        assert int(re.search(rf"#define CAMO_{name} (\d+)\s", hdr).group(1)) == getattr(_lib, name), name
+    assert _lib.SEG_HIST_INTS == _lib.SEG_QUADRANTS * 2 * _lib.SEG_BINS
+    for name in ("segmentation_histograms", "cod_measures", "weighted_f_measure", "aggregate_cod_measures"):
+        assert name in pkg.__all__ and callable(getattr(pkg, name))
+
+
+def test_quantisation_rule():
+    f = np.float32
+    edge = f(0.5) / f(255) * f(255)
+    assert edge == f(0.5)
+    v = np.array([np.nan, -0.3, 1.7, 0.0, 1.0, 0.5, 0.1, np.nextafter(f(0.1), f(1)), -0.0, np.inf, -np.inf], f)
+    assert R.quantise(v).tolist() == [0, 0, 255, 0, 255, 128, 26, 26, 0, 255, 0]                 # 127.5 -> 128, the even neighbour
+    assert R.positive(np.array([0, 127, 128, 255], np.uint8)).tolist() == [False, False, True, True]
+
+
+def test_reference_on_hand_cases():
+    per = R.measures(G22 > 0, G22)
+    assert per["mae_u8"] == 0 and per["f_max"] == 1.0 and abs(per["s_measure"] - 1) < 1e-15 and abs(per["e_max"] - 4 / 3) < 1e-14
+    assert abs(per["f_curve"][0] - 13 / 43) < 1e-15 and per["f_adp"] == 1.0 and abs(per["e_adp"] - 4 / 3) < 1e-14
+    inv = R.measures(G22 == 0, G22)
+    assert inv["mae_u8"] == 1 and abs(inv["f_max"] - 13 / 43) < 1e-15 and inv["f_adp"] == 0 and abs(inv["e_max"] - 1 / 3) < 1e-15
+    assert abs(inv["s_measure"] - 0.5) < 1e-15 and max(inv["f_curve"][1:]) == 0
+
+    assert R.split_point(G34) == (3, 1)
+    per = R.measures(G34 > 0, G34)
+    assert per["mae_u8"] == 0 and per["f_max"] == 1.0 and abs(per["s_measure"] - 1) < 1e-14 and abs(per["e_max"] - 12 / 11) < 1e-14
+    inv = R.measures(G34 == 0, G34)
+    assert inv["mae_u8"] == 1 and inv["f_adp"] == 0 and inv["s_measure"] == 0.0
+    half = R.measures(np.full((3, 4), 0.5, np.float32), G34)
+    assert half["mae_u8"] == (8 * 128 + 4 * 127) / 3060 and abs(half["f_max"] - 13 / 33) < 1e-15 and half["f_adp"] == 0
+    assert half["f_curve"][128] == half["f_max"] and half["f_curve"][129] == 0
+    row = np.array([[0.2, 0, 0, 0]] * 3, np.float32)
+    bg = R.measures(row, np.zeros((3, 4), np.uint8))
+    assert abs(bg["s_measure"] - 0.95) < 1e-15 and abs(bg["mae_u8"] - 0.05) < 1e-15 and abs(bg["e_max"] - 12 / 11) < 1e-15
+    assert bg["e_curve"][0] == 0 and abs(bg["e_curve"][51] - 9 / 11) < 1e-15 and abs(bg["e_adp"] - 9 / 11) < 1e-15
+    assert bg["f_mean"] == 204 / 256 and bg["f_adp"] == 0 and bg["f_max"] == 1
+    fg = R.measures(np.array([[0.2, 1, 1, 1]] * 3, np.float32), np.full((3, 4), 255, np.uint8))
+    assert abs(fg["s_measure"] - 0.8) < 1e-15 and abs(fg["mae_u8"] - 0.2) < 1e-15
+
+
+def _cpu_cases():
+    rs = np.random.RandomState(0)
+    cases = [(G22 > 0, G22), (G22 == 0, G22), (G34 > 0, G34), (G34 == 0, G34), (np.full((3, 4), 0.5), G34),
+             (np.array([[0.2, 0, 0, 0]] * 3), np.zeros((3, 4))), (np.array([[0.2, 1, 1, 1]] * 3), np.full((3, 4), 255))]
+    # 8 x 10, column 2 positive from top to bottom: split (3, 5) (Sy / n = 7/2, a tie, to 4).  Quadrant 0 holds a part of the stripe
+    # under a constant prediction (zero variance of p with a varying g: a = 0, b != 0, ssim 0); quadrant 1 has no positive pixel and
+    # prediction 0 (a = b = 0: ssim 1); quadrant 3 has a constant ground truth under a varying prediction (ssim 0); quadrant 2 is
+    # the general case.  A zero test on rounded floats would go wrong exactly here.
+    gt = np.zeros((8, 10), np.uint8)
+    gt[:, 2] = 255
+    pred = rs.uniform(0, 1, (8, 10))
+    pred[:5, :3] = 0.3
+    pred[:5, 3:] = 0.0
+    assert R.split_point(gt) == (3, 5) and gt[:5, :3].min() != gt[:5, :3].max() and gt[:5, 3:].max() == 0 and gt[5:, 3:].max() == 0
+    cases.append((pred, gt))
+    for s in range(24):
+        H, W = rs.randint(2, 14), rs.randint(2, 14)
+        pred = rs.uniform(-0.1, 1.1, (H, W))
+        gt = (rs.uniform(size=(H, W)) < rs.uniform()) * 255
+        if s % 3 == 0:
+            pred[: H // 2 + 1] = 0.3
+        if s % 4 == 0:
+            gt[:, : W // 2 + 1] = 0
+        if s % 5 == 0:
+            pred = np.round(pred)
+        cases.append((pred, gt))
+    return cases
+
+
+def test_host_ratios_from_the_table_match_the_pixel_reference():
+    worst = 0.0
+    for pred, gt in _cpu_cases():
+        ref, got = R.measures(np.asarray(pred, np.float32), np.asarray(gt, np.uint8)), _pkg(pred, gt)
+        for k in KEYS:
+            worst = max(worst, abs(ref[k] - got[k]))
+            assert abs(ref[k] - got[k]) <= 1e-12, (k, ref[k], got[k])
+        for k in ("f_curve", "e_curve"):
+            d = max(abs(a - b) for a, b in zip(ref[k], got[k]))
+            worst = max(worst, d)
+            assert len(got[k]) == 256 and d <= 1e-12, (k, d)
+    print(f"largest |table ratios - pixel ratios| = {worst:.3e} (bound 1e-12)")
+    assert "f_curve" not in _pkg(G34 > 0, G34, curves=False)
+    with pytest.raises(ValueError, match="pixels"):
+        from camouflage_multimodal_amd import cod_measures
+        cod_measures(R.table(np.zeros((1, 3, 4), np.float32), G34[None])[0].tolist(), [[1, 1]], 3, 5)
+
+
+def test_split_rule_at_ties():
+    assert [R.rint_ratio(a, 2) for a in (1, 3, 5, 7)] == [0, 2, 2, 4] and R.rint_ratio(7, 3) == 2 and R.rint_ratio(8, 3) == 3
+    g = np.zeros((6, 7), np.uint8)
+    g[0, 0] = g[1, 1] = 255                                         # Sx / n = Sy / n = 1/2 -> 0 (even)
+    assert R.split_point(g) == (1, 1)
+    g[:] = 0
+    g[1, 1] = g[2, 2] = 255                                         # 3/2 -> 2
+    assert R.split_point(g) == (3, 3)
+    g[:] = 0
+    g[2, 4] = g[3, 3] = 255                                         # x: 7/2 -> 4, y: 5/2 -> 2
+    assert R.split_point(g) == (5, 3)
+    assert R.split_point(np.zeros((6, 7), np.uint8)) == (5, 4)      # no positive pixel: rint(7/2) = 4, rint(6/2) = 3
+    assert R.split_point(np.zeros((5, 2), np.uint8)) == (2, 3)      # rint(2/2) = 1, rint(5/2) = 2
+    g[:] = 0
+    g[5, 6] = 255                                                   # the last pixel: quadrants 1 to 3 are empty
+    assert R.split_point(g) == (7, 6)
+    hist, split = R.table(np.full((1, 6, 7), 0.4, np.float32), g[None])
+    assert hist[0, 1:].sum() == 0 and hist[0, 0, 0, 102] == 41 and hist[0, 0, 1, 102] == 1 and split.tolist() == [[7, 6]]
+
+
+def test_argument_checks_without_a_gpu():
+    from camouflage_multimodal_amd import _lib
+    L = _lib.lib()
+    p = ctypes.c_void_p(0x1000)                                      # (never dereferenced: every check comes before any launch)
+
+    def hist(pred=p, stride=64, gt=p, N=1, H=8, W=8, out=p, split=p):
+        return L.camo_seg_histograms(pred, stride, gt, N, H, W, out, split, None)
+    assert hist(N=0) == -1 and hist(H=0) == -1 and hist(W=0) == -1
+    assert hist(H=1, W=1) == -1 and b"H * W >= 2" in L.camo_last_error()
+    assert hist(N=65536) == -1 and b"MAX_IMAGES" in L.camo_last_error()
+    assert hist(H=8193, W=8192, stride=1 << 40) == -1 and b"MAX_IMAGE_PIXELS" in L.camo_last_error()
+    assert hist(stride=63) == -1 and b"stride" in L.camo_last_error()
+    for k in ("pred", "gt", "out", "split"):
+        assert hist(**{k: None}) == -1 and b"null" in L.camo_last_error(), k
+    assert hist(out=ctypes.c_void_p(0x1004)) == -1 and b"aligned" in L.camo_last_error()
+    assert hist(pred=ctypes.c_void_p(0x1002)) == -1 and b"aligned" in L.camo_last_error()
+
+    assert L.camo_seg_weighted_f_workspace_bytes(1, 1, 1) == 0 and L.camo_seg_weighted_f_workspace_bytes(0, 8, 8) == 0
+    assert L.camo_seg_weighted_f_workspace_bytes(1, 2049, 8) == 0 and L.camo_seg_weighted_f_workspace_bytes(1, 8, 2049) == 0
+    need = L.camo_seg_weighted_f_workspace_bytes(3, 33, 70)
+    assert need >= 3 * 33 * 70 * 5 and need % 256 == 0
+
+    def wf(pred=p, stride=64, gt=p, N=1, H=8, W=8, gauss=p, ws=p, nbytes=1 << 20, sums=p):
+        return L.camo_seg_weighted_f(pred, stride, gt, N, H, W, gauss, ws, nbytes, sums, None)
+    assert wf(N=0) == -1 and wf(H=0) == -1 and wf(H=1, W=1) == -1 and wf(stride=63) == -1
+    assert wf(H=2049, stride=1 << 30) == -1 and b"MAX_SIDE" in L.camo_last_error()
+    assert wf(W=2049, stride=1 << 30) == -1 and b"MAX_SIDE" in L.camo_last_error()
+    for k in ("pred", "gt", "gauss", "ws", "sums"):
+        assert wf(**{k: None}) == -1 and b"null" in L.camo_last_error(), k
+    assert wf(nbytes=L.camo_seg_weighted_f_workspace_bytes(1, 8, 8) - 1) == -1 and b"workspace" in L.camo_last_error()
+    assert wf(ws=ctypes.c_void_p(0x1010)) == -1 and b"aligned" in L.camo_last_error()
+
+
+def test_cpu_tensors_raise():
+    from camouflage_multimodal_amd import RegionGraphGNN, detect_camouflage_batch, segmentation_histograms, weighted_f_measure
+    from camouflage_multimodal_amd._lib import CamoError
+    pred, gt = torch.zeros(1, 4, 4), torch.zeros(1, 4, 4, dtype=torch.uint8)
+    with pytest.raises(CamoError):
+        segmentation_histograms(pred, gt)
+    with pytest.raises(CamoError):
+        weighted_f_measure(pred, gt)
+    with pytest.raises(CamoError):
+        detect_camouflage_batch(RegionGraphGNN().eval(), torch.zeros(2, 16, 16, 3), torch.zeros(2, 16, 16, dtype=torch.uint8), cod_metrics=True)
+
+
+def test_aggregate_two_images_by_hand():
+    """F curves (1, 0, 0, ...) and (0, 1/2, 0, ...) average to (1/2, 1/4, 0, ...): max 1/2 (not the mean of the maxima, 3/4), mean
+    3/4 / 256.  E curves constant 0.2 and 0.6: max = mean = 0.4.  The other numbers are means over the images."""
+    from camouflage_multimodal_amd import aggregate_cod_measures
+    a = dict(f_curve=[1.0] + [0.0] * 255, e_curve=[0.2] * 256, s_measure=0.5, e_adp=0.1, f_adp=0.3, mae_u8=0.25, f_max=1.0, wf=0.5)
+    b = dict(f_curve=[0.0, 0.5] + [0.0] * 254, e_curve=[0.6] * 256, s_measure=1.0, e_adp=0.3, f_adp=0.5, mae_u8=0.75, f_max=0.5, wf=1.0)
+    out = aggregate_cod_measures([a, b])
+    assert out["f_max"] == 0.5 and out["f_mean"] == 0.75 / 256 and abs(out["e_max"] - 0.4) < 1e-15 and abs(out["e_mean"] - 0.4) < 1e-14
+    assert out["s_measure"] == 0.75 and abs(out["e_adp"] - 0.2) < 1e-15 and out["f_adp"] == 0.4 and out["mae_u8"] == 0.5 and out["wf"] == 0.75
+    del b["wf"]
+    assert "wf" not in aggregate_cod_measures([a, b])
+    with pytest.raises(ValueError):
+        aggregate_cod_measures([])
+    with pytest.raises(ValueError, match="curves"):
+        aggregate_cod_measures([{"s_measure": 1.0}])
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------
+
+def _blobs(H, W, seed, k=3):
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[:H, :W]
+    g = np.zeros((H, W), np.uint8)
+    for _ in range(k):
+        cy, cx, r = rs.randint(0, H), rs.randint(0, W), rs.randint(3, max(4, min(H, W) // 3))
+        g[(yy - cy) ** 2 + (xx - cx) ** 2 < r * r] = rs.choice([128, 200, 255])
+    g[g == 0] = rs.choice(np.array([0, 127], np.uint8), int((g == 0).sum()))       # (127 is not positive)
+    return g
+
+
+def _uniform(H, W, seed):
+    """Uniform values, with a NaN, values outside [0, 1] and values on both sides of bin edges ((k + 1/2) / 255 and its neighbours)."""
+    f = np.float32
+    rs = np.random.RandomState(seed)
+    p = rs.uniform(0, 1, (H, W)).astype(f)
+    flat = p.ravel()
+    flat[0], flat[1], flat[2], flat[3], flat[4] = np.nan, -0.25, 1.75, -np.inf, np.inf
+    for j, k in enumerate((0, 1, 2, 100, 127, 128, 253, 254)):
+        e = f(k + 0.5) / f(255)
+        flat[8 + 3 * j: 11 + 3 * j] = np.nextafter(e, f(0)), e, np.nextafter(e, f(1))
+    return p
+
+
+def _painted(H, W, seed, regions=24):
+    """A piecewise-constant map as the detector paints it: one probability per Voronoi region, a few regions saturated at 0 and 1."""
+    seg = FO.voronoi_segments(H, W, regions, seed)
+    val = np.random.RandomState(seed).uniform(0, 1, int(seg.max()) + 2).astype(np.float32)
+    val[::5] = 0.0
+    val[1::7] = 1.0
+    return val[seg]
+
+
+@functools.lru_cache(maxsize=None)
+def _images():
+    """The (pred, gt) pairs at 33 x 70 -- no multiple of any tile or vector width -- in batches of three, and their reference tables.
+    Never written to."""
+    H, W = 33, 70
+    one = np.zeros((H, W), np.uint8); one[20, 11] = 255
+    corner = np.zeros((H, W), np.uint8); corner[H - 1, W - 1] = 255          # centroid in the last column and row: quadrants 1-3 empty
+    tie = np.zeros((H, W), np.uint8); tie[4, 9] = tie[5, 10] = tie[7, 12] = tie[8, 13] = 255      # Sx / n = 11, Sy / n = 6
+    tie2 = np.zeros((H, W), np.uint8); tie2[4, 9] = tie2[5, 10] = 255        # 19/2 and 9/2: both ties, one each way
+    full, empty = np.full((H, W), 255, np.uint8), np.zeros((H, W), np.uint8)
+    const = lambda v: np.full((H, W), v, np.float32)
+    pairs = [(_uniform(H, W, 1), _blobs(H, W, 1)), (_painted(H, W, 2), _blobs(H, W, 2)), (const(0.0), one),
+             (const(1.0), full), (const(0.4), corner), (_uniform(H, W, 3), empty),
+             (_painted(H, W, 4), tie2), (const(0.4), _blobs(H, W, 5)), (const(1.0), tie)]
+    batches = []
+    for b in range(3):
+        pred = np.stack([p for p, _ in pairs[3 * b: 3 * b + 3]])
+        gt = np.stack([g for _, g in pairs[3 * b: 3 * b + 3]])
+        hist, split = R.table(pred, gt)
+        for a in (pred, gt, hist, split):
+            a.setflags(write=False)
+        batches.append((pred, gt, hist, split))
+    assert batches[1][3][1].tolist() == [W, H] and batches[2][3][0].tolist() == [11, 5] and batches[2][3][2].tolist() == [12, 7]
+    return batches
+
+
+def _check_tables(pred, gt, hist, split):
+    from camouflage_multimodal_amd import segmentation_histograms
+    N, H, W = pred.shape
+    maps = np.random.RandomState(7).uniform(0, 1, (N, 3, H, W)).astype(np.float32)
+    maps[:, 1] = pred
+    mt, gtt = torch.from_numpy(maps).cuda(), torch.from_numpy(gt.copy()).cuda()
+    h, s = segmentation_histograms(mt[:, 1], gtt)                            # strided: channel 1 of [N, 3, H, W], read in place
+    assert h.dtype == torch.int32 and s.dtype == torch.int32 and h.is_cuda and tuple(h.shape) == (N, 4, 2, 256) and tuple(s.shape) == (N, 2)
+    hn, sn = h.cpu().numpy(), s.cpu().numpy()
+    print(f"{N} x {H} x {W}: split {sn.tolist()}, pixels per image {hn.reshape(N, -1).sum(1).tolist()}, differing bins {int((hn != hist).sum())}")
+    assert np.array_equal(sn, split)
+    assert (hn.reshape(N, -1).sum(1) == H * W).all()
+    assert np.array_equal(hn, hist)
+    h2, s2 = segmentation_histograms(mt[:, 1], gtt)                          # two calls: the same bytes
+    assert torch.equal(h2, h) and torch.equal(s2, s)
+    h3, s3 = segmentation_histograms(mt[:, 1].contiguous(), gtt)
+    assert torch.equal(h3, h) and torch.equal(s3, s)
+    for i in range(N):                                                       # a batch gives the rows of its images one by one
+        hi, si = segmentation_histograms(mt[i, 1], gtt[i])
+        assert torch.equal(hi[0], h[i]) and torch.equal(si[0], s[i])
+    return hn, sn
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("b", [0, 1, 2])
+def test_histograms_are_exact_at_33x70(b):
+    pred, gt, hist, split = _images()[b]
+    hn, sn = _check_tables(pred, gt, hist, split)
+    H, W = pred.shape[1:]
+    if b == 0:
+        assert hn[2, :, :, 0].sum() == H * W and hn[2, :, 1, 0].sum() == 1                # all 0: the one bin, one positive pixel in it
+    if b == 1:
+        assert hn[0, :, 1, 255].sum() == H * W                                            # all 1, all positive
+        assert hn[1, 0, 0, 102] == H * W - 1 and hn[1, 0, 1, 102] == 1 and hn[1, 1:].sum() == 0      # 0.4 -> 102; quadrants 1-3 empty
+        assert hn[2, :, 1].sum() == 0                                                     # an empty ground truth
+    if b == 2:
+        assert hn[1, :, :, 102].sum() == H * W
+    from camouflage_multimodal_amd import cod_measures, segmentation_histograms
+    got = cod_measures(*segmentation_histograms(torch.from_numpy(pred.copy()).cuda(), torch.from_numpy(gt.copy()).cuda() > 127), H, W)   # a bool mask
+    for i, m in enumerate(got):
+        ref = R.measures(pred[i], gt[i])
+        for k in KEYS:
+            assert abs(m[k] - ref[k]) <= 1e-12, (i, k, m[k], ref[k])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["uniform", "painted", "constant"])
+def test_histograms_are_exact_at_130x257(kind):
+    """One image of 33410 pixels: several blocks flush into the one table."""
+    H, W = 130, 257
+    pred = {"uniform": _uniform, "painted": lambda h, w, s: _painted(h, w, s, 60), "constant": lambda h, w, s: np.full((h, w), 1.0, np.float32)}[kind](H, W, 11)
+    gt = _blobs(H, W, 12, k=5)
+    hist, split = R.table(pred[None], gt[None])
+    hn, _ = _check_tables(pred[None], gt[None], hist, split)
+    if kind == "constant":
+        assert hn[0, :, :, 255].sum() == H * W
+
+
+@pytest.mark.gpu
+def test_detect_camouflage_batch_with_cod_metrics():
+    """Nothing is compared across arithmetic paths: "cod_metrics" against cod_measures / weighted_f_measure of the call's own mask
+    probabilities; every other key as without the flag."""
+    import slic_ref as SR
+    from camouflage_multimodal_amd import (RegionGraphFineTuner, RegionGraphGNN, cod_measures, detect_camouflage_batch, segmentation_counts,
+                                           segmentation_histograms, segmentation_metrics, weighted_f_measure)
+    torch.manual_seed(5)
+    m = RegionGraphGNN().cuda().eval()
+    H, W = 48, 64
+    imgs = torch.from_numpy(np.stack([SR.noise_image(H, W, 60 + i) for i in range(2)])).cuda()
+    yy, xx = np.mgrid[:H, :W]
+    gt = np.zeros((2, H, W), np.uint8)
+    gt[0][(yy - 20) ** 2 + (xx - 30) ** 2 < 12 ** 2] = 255
+    gt[1][30:44, 5:25] = 200
+    gtt = torch.from_numpy(gt).cuda()
+    plain = detect_camouflage_batch(m, imgs, gtt, n_segments=40)
+    out = detect_camouflage_batch(m, imgs, gtt, n_segments=40, cod_metrics=True)
+    assert "cod_metrics" not in plain and set(out) == set(plain) | {"cod_metrics"}
+    assert torch.equal(plain["segments"], out["segments"]) and torch.equal(plain["region_map"], out["region_map"])
+    assert float((plain["prob_maps"] - out["prob_maps"]).abs().max()) < 1e-5      # (two embedding forwards: the GNN's own bound)
+    prob = out["prob_maps"][:, 0]
+    # the keys from before are what they were: the mask and the metrics of the call's own maps, as without the flag
+    assert torch.equal(out["mask"], prob > 0.5) and out["metrics"] == segmentation_metrics(segmentation_counts(prob, gtt, 0.5), H, W)
+    assert plain["metrics"] == segmentation_metrics(segmentation_counts(plain["prob_maps"][:, 0], gtt, 0.5), H, W)
+    assert [sorted(d) for d in plain["metrics"]] == [sorted(d) for d in out["metrics"]]
+    want = cod_measures(*segmentation_histograms(prob, gtt), H, W)
+    wf = weighted_f_measure(prob, gtt)
+    assert len(out["cod_metrics"]) == 2
+    for i, got in enumerate(out["cod_metrics"]):
+        print(f"image {i}: " + ", ".join(f"{k} {got[k]:.4f}" for k in KEYS + ("wf",)))
+        assert set(got) == set(want[i]) | {"wf"} and got["wf"] == wf[i] and 0.0 <= got["wf"] <= 1.0
+        for k, v in want[i].items():
+            assert got[k] == v, (i, k)
+        ref = R.measures(prob[i].cpu().numpy(), gt[i])
+        for k in KEYS:
+            assert abs(got[k] - ref[k]) <= 1e-12, (i, k)
+    with pytest.raises(ValueError, match="gt_masks"):
+        detect_camouflage_batch(m, imgs, n_segments=40, cod_metrics=True)
+    tuner = RegionGraphFineTuner(m)
+    ev = tuner.evaluate(imgs, gtt, n_segments=40, cod_metrics=True)
+    assert set(ev) == {"metrics", "cod_metrics"} and len(ev["cod_metrics"]) == 2 and isinstance(tuner.evaluate(imgs, gtt, n_segments=40), list)
