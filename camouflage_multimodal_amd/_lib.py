@@ -31,6 +31,12 @@ SEG_BINS = 256                      # CAMO_SEG_BINS
 SEG_QUADRANTS = 4                   # CAMO_SEG_QUADRANTS
 SEG_HIST_INTS = 2048                # CAMO_SEG_HIST_INTS
 SEG_WF_MAX_SIDE = 2048              # CAMO_SEG_WF_MAX_SIDE
+RGD_MAX_IMAGES = 65535              # CAMO_RGD_MAX_IMAGES
+RSZ_FIELDS = 18                     # CAMO_RSZ_FIELDS
+RSZ_MAX_SIDE = 8192                 # CAMO_RSZ_MAX_SIDE
+RSZ_MAX_CHANNELS = 4                # CAMO_RSZ_MAX_CHANNELS
+RSZ_NEAREST, RSZ_BILINEAR, RSZ_AREA = 0, 1, 2      # CAMO_RSZ_NEAREST, CAMO_RSZ_BILINEAR, CAMO_RSZ_AREA
+RSZ_U8, RSZ_F32 = 0, 1              # CAMO_RSZ_U8, CAMO_RSZ_F32
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -161,6 +167,9 @@ PROTOTYPES = {
         ("camo_seg_histograms", i32, (vp, i64, vp, i32, i32, i32, vp, vp, vp)),
         ("camo_seg_weighted_f_workspace_bytes", sz, (i32, i32, i32)),
         ("camo_seg_weighted_f", i32, (vp, i64, vp, i32, i32, i32, vp, vp, sz, vp, vp)),
+    ),
+    "camo_resize.h": (
+        ("camo_resize", i32, (vp, i64, i32, vp, i64, i32, vp, i32, i32, i32, i64, vp, vp)),
     ),
 }
 

@@ -224,3 +224,21 @@ class RegionGraphFineTuner(AdamWStateMixin):
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         out = detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device, cod_metrics)
         return {"metrics": out["metrics"], "cod_metrics": out["cod_metrics"]} if cod_metrics else out["metrics"]
+
+    def step_from_ragged(self, images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, n_segments=500,
+                         band_permille=0, edge_min_pixels=1):
+        """``prepare_finetune_batch_ragged`` (resize.py: uint8 images and masks of mixed sizes, resized to ``size`` on the tuner's
+        device with a crop box and a flip per image), then ``step``."""
+        from .resize import prepare_finetune_batch_ragged
+        _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        return self.step(prepare_finetune_batch_ragged(images, gt_masks, instance_masks, edge_masks, size, crops, flips, n_segments=n_segments,
+                                                       band_permille=band_permille, device=self.flat_params.device,
+                                                       edge_min_pixels=edge_min_pixels))
+
+    def evaluate_ragged(self, images, gt_masks, size=(256, 256), n_segments=500, threshold=0.5, cod_metrics=False, evaluate_at="native"):
+        """``evaluate`` for uint8 images and masks of mixed sizes (``detect_camouflage_ragged`` of resize.py): the metrics are taken
+        against every mask at its own size, or at ``size`` with ``evaluate_at="resized"``.  Same return as ``evaluate``."""
+        from .resize import detect_camouflage_ragged
+        _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        out = detect_camouflage_ragged(self.model, images, gt_masks, size, n_segments, threshold, self.flat_params.device, cod_metrics, evaluate_at)
+        return {"metrics": out["metrics"], "cod_metrics": out["cod_metrics"]} if cod_metrics else out["metrics"]
