@@ -37,6 +37,9 @@ RSZ_MAX_SIDE = 8192                 # CAMO_RSZ_MAX_SIDE
 RSZ_MAX_CHANNELS = 4                # CAMO_RSZ_MAX_CHANNELS
 RSZ_NEAREST, RSZ_BILINEAR, RSZ_AREA = 0, 1, 2      # CAMO_RSZ_NEAREST, CAMO_RSZ_BILINEAR, CAMO_RSZ_AREA
 RSZ_U8, RSZ_F32 = 0, 1              # CAMO_RSZ_U8, CAMO_RSZ_F32
+INST_FIELDS = 8                     # CAMO_INST_FIELDS
+INST_COUNTS = 4                     # CAMO_INST_COUNTS
+INST_MAX_ROWS = 1 << 24             # CAMO_INST_MAX_ROWS
 RG_MAX_LABELS = 4096
 RG_NPARAMS = 28
 
@@ -170,6 +173,10 @@ PROTOTYPES = {
     ),
     "camo_resize.h": (
         ("camo_resize", i32, (vp, i64, i32, vp, i64, i32, vp, i32, i32, i32, i64, vp, vp)),
+    ),
+    "camo_instances.h": (
+        ("camo_instances_workspace_bytes", sz, (i32, i32, i32)),
+        ("camo_instances", i32, (vp, i64, f32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp)),
     ),
 }
 

@@ -1,0 +1,451 @@
+// Object instances of a predicted mask (include/camo_instances.h): binarise, fill holes, label the connected
+// components, drop the small ones, number the rest in reading order, and sum (area, box, Sx, Sy, Sq) per component.  4 B/pixel in
+// and 5 B/pixel out: the work is launches and latency, so every grid covers the whole batch.
+//
+//   label tiles  one block per 32 x 32 tile: membership of each pixel (background for the hole pass; foreground, or foreground and
+//                holes, for the component pass), union-find of the tile's members in LDS over the W / N (and NW / NE) neighbours,
+//                flattened: every member points at the smallest index of its component inside the tile
+//   join tiles   members on a tile border: the same union with their neighbours in other tiles, on the global parents
+//   flatten      every member finds its root and points at it.  Hole pass: a member on the image's border sets border[root].
+//                Component pass: area[root] += 1, runs of equal root combined in the wave and the block's first root in the block
+//   count        per chunk of 1024 pixels: the kept roots, the dropped roots, the pixels of the kept
+//   scan         one block per image: the chunks' exclusive prefix of kept roots; counts
+//   rank         id[root] = the prefix + the kept roots before it in the chunk + 1 (0 when dropped); the image's table rows cleared
+//   emit         labels, clean, and the table's sums, minima and maxima, through a block's LDS slots
+//
+// With fill_holes the first three run twice: on the background with the complementary connectivity, then on the filled foreground.
+// Union by atomicMin on the larger root (uf_inl.h): the output depends on the partition alone.  Integer atomics only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "instances.h"
+#include "uf_inl.h"
+
+namespace {
+
+constexpr int T = INST_TILE, NT = INST_NT, CHUNK = INST_CHUNK, PPT = INST_CHUNK / INST_NT;
+constexpr int MODE_BG = 0, MODE_FG = 1, MODE_FILLED = 2;
+constexpr int NONE = 0x7fffffff;
+constexpr unsigned long long BOX_MIN_INIT = 0x7fffffffffffffffull;
+static_assert(T == 32 && T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "a tile row is half a wave; whole waves, whole passes");
+
+// include/camo_seg_measures.h's quantisation: clamp (a NaN to 0), one fp32 multiply, round to nearest even
+__device__ __forceinline__ int quantise(float v) {
+  v = v == v ? v : 0.f;
+  v = fminf(fmaxf(v, 0.f), 1.f);
+  return (int)rintf(v * 255.0f);
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+
+// Runs of consecutive lanes with the same key (`head`: the lane starts a run): the lane one past the end of the calling lane's run.
+// Every lane of the wave calls.
+__device__ __forceinline__ int run_end(bool head, int lane) {
+  const unsigned long long hm = __ballot(head);
+  const unsigned long long above = lane < 63 ? hm >> (lane + 1) : 0ull;
+  return above ? lane + __ffsll((long long)above) : 64;
+}
+
+// grid (tiles of an image, images; an image loop when the grid would be too large).  MODE_BG: members are the background pixels,
+// border[] is cleared.  MODE_FG: members are the foreground pixels.  MODE_FILLED: the foreground pixels and those of the background
+// components (bgpar, flattened) that do not touch the border; a root of such a component counts one hole.  The component modes clear area[].
+template <int CONN, int MODE>
+__global__ __launch_bounds__(NT) void inst_label_tiles_kernel(const float* __restrict__ pred, long long stride, float threshold, int N, int H, int W,
+                                                              int tiles_x, const int* __restrict__ bgpar, unsigned char* border,
+                                                              int* __restrict__ par, int* __restrict__ area, int* __restrict__ misc) {
+  __shared__ int lab[T * T];
+  __shared__ int holes;
+  const int tid = threadIdx.x, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x, y0 = ty * T, x0 = tx * T;
+  const size_t HW = (size_t)H * W;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const size_t base = (size_t)n * HW;
+    const float* img = pred + (size_t)n * stride;
+    if (tid == 0) {
+      holes = 0;
+      if (MODE != MODE_FILLED && blockIdx.x == 0) misc[n] = 0;      // (MODE_FILLED adds to what the hole pass's launch cleared)
+    }
+    __syncthreads();
+    int nh = 0;
+    for (int l = tid; l < T * T; l += NT) {
+      const int y = y0 + l / T, x = x0 + l % T;
+      bool member = false;
+      if (y < H && x < W) {
+        const size_t q = (size_t)y * W + x, p = base + q;
+        const bool fg = img[q] > threshold;                          // (a NaN compares false: background)
+        if (MODE == MODE_BG) {
+          member = !fg;
+          border[p] = 0;
+        } else {
+          member = fg;
+          if (MODE == MODE_FILLED && !fg) {
+            const int r = bgpar[p];                                  // (flattened: the root)
+            member = !border[r];
+            if (member && r == (int)p) ++nh;
+          }
+          area[p] = 0;
+        }
+      }
+      // a row of the tile is half a wave: every member starts out pointing at the first pixel of its run in the row
+      const unsigned row = (unsigned)(__ballot(member) >> (tid & 32)), lx = tid & 31;
+      const unsigned gaps = ~row & ((1u << lx) - 1u);
+      lab[l] = member ? l - (int)lx + (gaps ? 32 - __clz((int)gaps) : 0) : -1;
+    }
+    if (MODE == MODE_FILLED && nh) atomicAdd(&holes, nh);
+    __syncthreads();
+    // The runs of one row meet the row above.  A union is left out where a neighbour's union says the same: with the pixel above,
+    // when the pixel to the left (same run) has a member above it too; with a diagonal pixel, when the pixel above is a member
+    // (same run as the diagonal one) or, for the upper left, when the pixel to the left is one
+    for (int l = tid; l < T * T; l += NT) {
+      if (lab[l] < 0 || l < T) continue;                            // (a member's entry never goes negative)
+      const int lx = l % T;
+      constexpr int SC = __HIP_MEMORY_SCOPE_WORKGROUP;
+      const bool up = lab[l - T] >= 0, left = lx > 0 && lab[l - 1] >= 0, upleft = lx > 0 && lab[l - T - 1] >= 0;
+      if (up) {
+        if (!(left && upleft)) uf_union<SC>(lab, l, l - T);
+      } else if (CONN == 8) {
+        if (upleft && !left) uf_union<SC>(lab, l, l - T - 1);
+        if (lx < T - 1 && lab[l - T + 1] >= 0) uf_union<SC>(lab, l, l - T + 1);
+      }
+    }
+    __syncthreads();
+    for (int l = tid; l < T * T; l += NT) {
+      const int y = y0 + l / T, x = x0 + l % T;
+      if (y >= H || x >= W) continue;
+      int r = -1;
+      if (lab[l] >= 0) {
+        const int q = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l);    // (no entry changes after the barrier)
+        r = (int)(base + (size_t)(y0 + q / T) * W + (x0 + q % T));       // row-major order inside the tile = order of the batch index
+      }
+      par[base + (size_t)y * W + x] = r;
+    }
+    if (MODE == MODE_FILLED && tid == 0 && holes) atomicAdd(misc + n, holes);
+    __syncthreads();                                                 // lab and holes are reused by the next image
+  }
+}
+
+template <int CONN>
+__global__ __launch_bounds__(NT) void inst_join_tiles_kernel(int* par, int N, int H, int W) {
+  const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
+  if (p >= total) return;
+  const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
+  const int ty = y % T, tx = x % T;
+  if (ty != 0 && tx != 0 && (CONN == 4 || tx != T - 1)) return;
+  if (par[p] < 0) return;                                         // (written by the launch before; stays >= 0)
+  const int i = (int)p;
+  constexpr int SC = __HIP_MEMORY_SCOPE_AGENT;
+  // x > 0, y > 0, x < W - 1: a neighbour is a pixel of the same image, never the next image's first row or the row's other end
+  const bool left = x > 0 && par[p - 1] >= 0, up = y > 0 && par[p - W] >= 0, upleft = x > 0 && y > 0 && par[p - W - 1] >= 0;
+  // A union is left out where the neighbours' unions say the same.  Across a column border: when the pixel above (same tile) and
+  // the one above the left one are members -- the pixel above joins them.  Across a row border: when the pixel to the left (same
+  // tile) and the one above it are members.  A tile's corner pixel leaves out neither.  Diagonally: as in the tile kernel.
+  if (tx == 0 && left && !(ty != 0 && up && upleft)) uf_union<SC>(par, i, i - 1);
+  if (ty == 0 && up && !(tx != 0 && left && upleft)) uf_union<SC>(par, i, i - W);
+  if (CONN == 8 && !up) {
+    if ((ty == 0 || tx == 0) && upleft && !left) uf_union<SC>(par, i, i - W - 1);
+    if ((ty == 0 || tx == T - 1) && y > 0 && x < W - 1 && par[p - W + 1] >= 0) uf_union<SC>(par, i, i - W + 1);
+  }
+}
+
+// hole pass: every background pixel points at its root; one on the image's border marks the root
+__global__ __launch_bounds__(NT) void inst_flatten_bg_kernel(int* par, unsigned char* border, int N, int H, int W) {
+  const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
+  if (p >= total) return;
+  if (par[p] < 0) return;
+  // (other threads shorten chains meanwhile: an entry read here is the old parent or the root, both lead to the root)
+  const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, (int)p);
+  if (r != (int)p) __hip_atomic_store(par + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
+  if (y == 0 || y == H - 1 || x == 0 || x == W - 1) border[r] = 1;      // (every writer stores the same byte)
+}
+
+// grid (chunks, images).  Component pass: every member points at its root, area[root] counts it.  The block's smallest root is
+// counted in LDS and added once; every other run of equal roots over consecutive lanes is one atomic.
+__global__ __launch_bounds__(NT) void inst_flatten_area_kernel(int* par, int* __restrict__ area, int H, int W) {
+  __shared__ int dom, dom_count;
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y, HW = H * W;
+  const size_t base = (size_t)n * HW;
+  if (tid == 0) { dom = NONE; dom_count = 0; }
+  __syncthreads();
+  int r[PPT], mine = NONE;
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    const int q = blockIdx.x * CHUNK + j * NT + tid;
+    r[j] = -1;
+    if (q < HW) {
+      const size_t p = base + q;
+      if (par[p] >= 0) {
+        r[j] = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, (int)p);
+        if (r[j] != (int)p) __hip_atomic_store(par + p, r[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        mine = min(mine, r[j]);
+      }
+    }
+  }
+  mine = wave_min(mine);
+  if (lane == 0 && mine != NONE) atomicMin(&dom, mine);
+  __syncthreads();
+  const int d = dom;
+  if (d == NONE) return;                                          // (the whole block: no member in the chunk)
+  int nd = 0;
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    nd += r[j] == d;
+    const int key = r[j] == d ? -1 : r[j];
+    if (__ballot(key >= 0) == 0ull) continue;                     // (wave-uniform)
+    const int prev = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || prev != key;
+    const int end = run_end(head, lane);
+    if (head && key >= 0) atomicAdd(area + key, end - lane);
+  }
+  nd = wave_sum(nd);
+  if (lane == 0 && nd) atomicAdd(&dom_count, nd);
+  __syncthreads();
+  if (tid == 0) atomicAdd(area + d, dom_count);
+}
+
+// grid (chunks, images): chunk[0] = roots of at least min_area pixels, chunk[1] = smaller roots, chunk[2] = pixels of the former
+__global__ __launch_bounds__(NT) void inst_count_kernel(const int* __restrict__ par, const int* __restrict__ area, int H, int W, int min_area,
+                                                        int N, int* __restrict__ chunk) {
+  __shared__ int s[3];
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y, HW = H * W;
+  const size_t base = (size_t)n * HW;
+  if (tid < 3) s[tid] = 0;
+  __syncthreads();
+  int nk = 0, ns = 0, np = 0;
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    const int q = blockIdx.x * CHUNK + j * NT + tid;
+    if (q >= HW) continue;
+    const size_t p = base + q;
+    if (par[p] != (int)p) continue;
+    const int a = area[p];
+    if (a >= min_area) { ++nk; np += a; } else ++ns;
+  }
+  nk = wave_sum(nk); ns = wave_sum(ns); np = wave_sum(np);
+  if (lane == 0) {
+    if (nk) { atomicAdd(&s[0], nk); atomicAdd(&s[2], np); }
+    if (ns) atomicAdd(&s[1], ns);
+  }
+  __syncthreads();
+  if (tid < 3) chunk[((size_t)tid * N + n) * gridDim.x + blockIdx.x] = s[tid];
+}
+
+// one block per image: chunk[0] becomes its exclusive prefix; counts = {kept, dropped, holes, pixels of the kept}
+__global__ __launch_bounds__(NT) void inst_scan_kernel(int* __restrict__ chunk, int chunks, int N, const int* __restrict__ misc,
+                                                       int* __restrict__ counts) {
+  __shared__ int s[NT];
+  __shared__ int tot[2];
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.x;
+  int* c = chunk + (size_t)n * chunks;
+  const int* cs = chunk + ((size_t)N + n) * chunks;
+  const int* cp = chunk + ((size_t)2 * N + n) * chunks;
+  if (tid < 2) tot[tid] = 0;
+  int carry = 0, ns = 0, np = 0;
+  for (int c0 = 0; c0 < chunks; c0 += NT) {
+    const bool in = c0 + tid < chunks;
+    const int v = in ? c[c0 + tid] : 0;
+    if (in) { ns += cs[c0 + tid]; np += cp[c0 + tid]; }
+    s[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+      const int t = tid >= d ? s[tid - d] : 0;
+      __syncthreads();
+      s[tid] += t;
+      __syncthreads();
+    }
+    if (in) c[c0 + tid] = carry + s[tid] - v;
+    carry += s[NT - 1];
+    __syncthreads();
+  }
+  ns = wave_sum(ns); np = wave_sum(np);
+  if (lane == 0) { atomicAdd(&tot[0], ns); atomicAdd(&tot[1], np); }
+  __syncthreads();
+  if (tid == 0) { counts[4 * n] = carry; counts[4 * n + 1] = tot[0]; counts[4 * n + 2] = misc[n]; counts[4 * n + 3] = tot[1]; }
+}
+
+// grid (chunks, images): rid[root] = the component's id, 0 when it is dropped.  The image's table rows are cleared on the way, the
+// box minima of the rows in use to the largest value.
+__global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ par, const int* __restrict__ area, int H, int W, int min_area,
+                                                       const int* __restrict__ chunk, const int* __restrict__ counts, int max_instances,
+                                                       int* __restrict__ rid, unsigned long long* __restrict__ table) {
+  __shared__ int wcount[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y, HW = H * W;
+  const size_t base = (size_t)n * HW;
+  {
+    const long long K = counts[4 * n], cells = (long long)max_instances * 8;
+    unsigned long long* rows = table + (size_t)n * cells;
+    for (long long i = (long long)blockIdx.x * NT + tid; i < cells; i += (long long)gridDim.x * NT) {
+      const int f = (int)(i & 7);
+      rows[i] = ((i >> 3) < K && (f == 1 || f == 2)) ? BOX_MIN_INIT : 0ull;
+    }
+  }
+  int running = chunk[(size_t)n * gridDim.x + blockIdx.x];
+  for (int j = 0; j < PPT; ++j) {
+    const int q = blockIdx.x * CHUNK + j * NT + tid;
+    const size_t p = base + q;
+    const bool root = q < HW && par[p] == (int)p;
+    const bool kept = root && area[p] >= min_area;
+    const unsigned long long mask = __ballot(kept);
+    if (lane == 0) wcount[wave] = __popcll(mask);
+    __syncthreads();
+    int before = __popcll(mask & ((1ull << lane) - 1)), total = 0;
+    for (int i = 0; i < NT / 64; ++i) {
+      if (i < wave) before += wcount[i];
+      total += wcount[i];
+    }
+    if (root) rid[p] = kept ? running + before + 1 : 0;
+    running += total;
+    __syncthreads();
+  }
+}
+
+// grid (chunks, images).  labels and clean of every pixel, and the table: a run of equal ids over consecutive lanes inside one image
+// row is one record (len, x, y, sum of q) whose sums have closed forms.  A record goes to the id's slot of a small LDS table (open
+// addressing from id mod EMIT_SLOTS; to the table in memory when every slot is another id's), and the block adds its slots to the
+// table in memory once: a block of one large object costs eight atomics, whatever else crosses its rows.
+constexpr int EMIT_SLOTS = 16;
+__global__ __launch_bounds__(NT) void inst_emit_kernel(const float* __restrict__ pred, long long stride, const int* __restrict__ par,
+                                                       const int* __restrict__ rid, int H, int W, int max_instances, int* __restrict__ labels,
+                                                       unsigned char* __restrict__ clean, unsigned long long* __restrict__ table) {
+  __shared__ int slot_id[EMIT_SLOTS];                             // 0: free
+  __shared__ unsigned long long slot[EMIT_SLOTS][8];
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y, HW = H * W;
+  const size_t base = (size_t)n * HW;
+  const float* img = pred + (size_t)n * stride;
+  if (tid < EMIT_SLOTS) slot_id[tid] = 0;
+  if (tid < EMIT_SLOTS * 8) slot[tid >> 3][tid & 7] = ((tid & 7) == 1 || (tid & 7) == 2) ? BOX_MIN_INIT : 0ull;
+  __syncthreads();
+  unsigned long long* rows = table + (size_t)n * max_instances * 8;
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    const int q = blockIdx.x * CHUNK + j * NT + tid;
+    int k = 0;
+    float pv = 0.f;
+    if (q < HW) {
+      const size_t p = base + q;
+      pv = img[q];
+      const int r = par[p];
+      const int id = r >= 0 ? rid[r] : 0;
+      labels[p] = id;
+      clean[p] = id > 0 ? 1 : 0;
+      if (id <= max_instances) k = id;                            // (ids past the table keep their label and have no row)
+    }
+    if (__ballot(k > 0) == 0ull) continue;                        // (wave-uniform)
+    const int y = q / W, x = q - y * W;                            // (k > 0 only where q < HW)
+    const int qv = k > 0 ? quantise(pv) : 0;
+    const int prev = __shfl_up(k, 1, 64);
+    const bool head = lane == 0 || prev != k || x == 0;
+    const int end = run_end(head, lane), len = end - lane;
+    int pre = qv;                                                  // inclusive prefix of q over the wave (at most 64 * 255)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(pre, o, 64);
+      if (lane >= o) pre += t;
+    }
+    const int sq = __shfl(pre, end - 1, 64) - (pre - qv);
+    if (head && k > 0) {                                           // (no branch around the shuffles above: every lane takes them)
+      const unsigned long long sx = (unsigned long long)len * x + (unsigned long long)len * (len - 1) / 2, sy = (unsigned long long)len * y;
+      unsigned long long* row = rows + (size_t)(k - 1) * 8;        // the table in memory, unless a slot takes the record
+      int s = k & (EMIT_SLOTS - 1);
+      for (int probe = 0; probe < EMIT_SLOTS; ++probe, s = (s + 1) & (EMIT_SLOTS - 1)) {
+        const int old = atomicCAS(&slot_id[s], 0, k);
+        if (old == 0 || old == k) { row = slot[s]; break; }
+      }
+      atomicAdd(row + 0, (unsigned long long)len);
+      atomicMin(row + 1, (unsigned long long)x);
+      atomicMin(row + 2, (unsigned long long)y);
+      atomicMax(row + 3, (unsigned long long)(x + len - 1));
+      atomicMax(row + 4, (unsigned long long)y);
+      atomicAdd(row + 5, sx);
+      atomicAdd(row + 6, sy);
+      atomicAdd(row + 7, (unsigned long long)sq);
+    }
+  }
+  __syncthreads();
+  if (tid >= EMIT_SLOTS * 8) return;
+  const int k = slot_id[tid >> 3], f = tid & 7;
+  if (k == 0) return;
+  const unsigned long long v = slot[tid >> 3][f];
+  unsigned long long* cell = rows + (size_t)(k - 1) * 8 + f;
+  if (f == 1 || f == 2) atomicMin(cell, v);
+  else if (f == 3 || f == 4) atomicMax(cell, v);
+  else atomicAdd(cell, v);
+}
+
+unsigned blocks_of(long long count) { return (unsigned)((count + NT - 1) / NT); }
+
+}  // namespace
+
+InstWs inst_carve(int N, int H, int W, void* base) {
+  InstWs w{};
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  const size_t npix = (size_t)N * H * W, chunks = ((size_t)H * W + CHUNK - 1) / CHUNK;
+  w.bgpar = reinterpret_cast<int*>(take(npix * sizeof(int)));
+  w.par = reinterpret_cast<int*>(take(npix * sizeof(int)));
+  w.area = reinterpret_cast<int*>(take(npix * sizeof(int)));
+  w.border = reinterpret_cast<unsigned char*>(take(npix));
+  w.chunk = reinterpret_cast<int*>(take(3 * (size_t)N * chunks * sizeof(int)));
+  w.misc = reinterpret_cast<int*>(take((size_t)N * sizeof(int)));
+  w.bytes = off;
+  return w;
+}
+
+template <int CONN, int MODE>
+static void label_pass(const float* pred, long long stride, float threshold, int N, int H, int W, const InstWs& ws, int* par, hipStream_t stream) {
+  const int tiles_x = (W + T - 1) / T, tiles_y = (H + T - 1) / T;
+  const long long tiles = (long long)tiles_x * tiles_y;                      // <= 2^21 (H * W <= 2^26)
+  // at most 2^32 - 1 threads in a grid: beyond that a block takes several images
+  const int rows = (int)std::min<long long>(N, ((1ll << 32) - 1) / (tiles * NT));
+  hipLaunchKernelGGL((inst_label_tiles_kernel<CONN, MODE>), dim3((unsigned)tiles, (unsigned)rows), dim3(NT), 0, stream, pred, stride, threshold, N, H,
+                     W, tiles_x, ws.bgpar, ws.border, par, ws.area, ws.misc);
+  hipLaunchKernelGGL(inst_join_tiles_kernel<CONN>, dim3(blocks_of((long long)N * H * W)), dim3(NT), 0, stream, par, N, H, W);
+}
+
+int launch_instances(const float* pred, long long stride, float threshold, int N, int H, int W, int connectivity, int min_area, bool fill_holes,
+                     int max_instances, const InstWs& ws, int* labels, unsigned char* clean, long long* table, int* counts, hipStream_t stream) {
+  const long long total = (long long)N * H * W;
+  const int chunks = (int)(((long long)H * W + CHUNK - 1) / CHUNK);
+  const dim3 raster(chunks, N);
+  const bool eight = connectivity == 8;
+  if (fill_holes) {
+    if (eight) label_pass<4, MODE_BG>(pred, stride, threshold, N, H, W, ws, ws.bgpar, stream);
+    else label_pass<8, MODE_BG>(pred, stride, threshold, N, H, W, ws, ws.bgpar, stream);
+    hipLaunchKernelGGL(inst_flatten_bg_kernel, dim3(blocks_of(total)), dim3(NT), 0, stream, ws.bgpar, ws.border, N, H, W);
+    if (eight) label_pass<8, MODE_FILLED>(pred, stride, threshold, N, H, W, ws, ws.par, stream);
+    else label_pass<4, MODE_FILLED>(pred, stride, threshold, N, H, W, ws, ws.par, stream);
+  } else {
+    if (eight) label_pass<8, MODE_FG>(pred, stride, threshold, N, H, W, ws, ws.par, stream);
+    else label_pass<4, MODE_FG>(pred, stride, threshold, N, H, W, ws, ws.par, stream);
+  }
+  unsigned long long* tab = reinterpret_cast<unsigned long long*>(table);
+  hipLaunchKernelGGL(inst_flatten_area_kernel, raster, dim3(NT), 0, stream, ws.par, ws.area, H, W);
+  hipLaunchKernelGGL(inst_count_kernel, raster, dim3(NT), 0, stream, ws.par, ws.area, H, W, min_area, N, ws.chunk);
+  hipLaunchKernelGGL(inst_scan_kernel, dim3(N), dim3(NT), 0, stream, ws.chunk, chunks, N, ws.misc, counts);
+  hipLaunchKernelGGL(inst_rank_kernel, raster, dim3(NT), 0, stream, ws.par, ws.area, H, W, min_area, ws.chunk, counts, max_instances, ws.bgpar, tab);
+  hipLaunchKernelGGL(inst_emit_kernel, raster, dim3(NT), 0, stream, pred, stride, ws.par, ws.bgpar, H, W, max_instances, labels, clean, tab);
+  return (int)hipGetLastError();
+}

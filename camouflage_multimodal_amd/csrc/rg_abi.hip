@@ -1,7 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks.
+// the node targets from ground-truth masks, and the object instances of a predicted mask.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "rg_detect.h"
 #include "rg_train.h"
 #include "rg_targets.h"
+#include "instances.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -27,6 +28,7 @@
 #include "../../include/camo_rg_train_bn.h"
 #include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
+#include "../../include/camo_instances.h"
 
 using namespace camo_abi;
 
@@ -654,6 +656,40 @@ int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, con
   if (!edge_t) return fail(CAMO_E_ARG, "edge_t is null");
   CK(launch_rg_node_targets(segments, region_map, node_off, gt_mask, gt_instance, gt_edge, N, H, W, label_bound, n_nodes, band_permille,
                             edge_min_pixels, counts, mask_t, inst_t, edge_t, static_cast<hipStream_t>(stream)), "rg node targets");
+  return 0;
+}
+
+// ---- Object instances of a predicted mask (include/camo_instances.h) ---------------------------------------------
+static int inst_check(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if (N > CAMO_RGD_MAX_IMAGES) return fail(CAMO_E_ARG, "N exceeds CAMO_RGD_MAX_IMAGES");
+  if ((long long)H * W > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGD_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_RGD_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGD_MAX_PIXELS (32-bit pixel indices)");
+  return 0;
+}
+
+size_t camo_instances_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+  if (inst_check(N, H, W)) return 0;
+  return inst_carve(N, H, W, nullptr).bytes;
+}
+
+int camo_instances(const float* pred, int64_t pred_image_stride, float threshold, int32_t N, int32_t H, int32_t W, int32_t connectivity,
+                   int32_t min_area, int32_t fill_holes, int32_t max_instances, int32_t* labels, uint8_t* clean, int64_t* table,
+                   int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (connectivity != 4 && connectivity != 8) return fail(CAMO_E_ARG, "connectivity must be 4 or 8");
+  if (min_area < 0) return fail(CAMO_E_ARG, "min_area must be >= 0");
+  if (max_instances < 1) return fail(CAMO_E_ARG, "max_instances must be >= 1");
+  if ((long long)N * max_instances > CAMO_INST_MAX_ROWS) return fail(CAMO_E_ARG, "N * max_instances exceeds CAMO_INST_MAX_ROWS");
+  if (pred_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "pred_image_stride must be >= H * W");
+  if (!std::isfinite(threshold)) return fail(CAMO_E_ARG, "threshold must be finite");
+  if (!pred || !labels || !clean || !table || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const InstWs w = inst_carve(N, H, W, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_instances_workspace_bytes()");
+  CK(launch_instances(pred, pred_image_stride, threshold, N, H, W, connectivity, min_area, fill_holes != 0, max_instances, w, labels, clean,
+                      reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "instances");
   return 0;
 }
 }  // extern "C"

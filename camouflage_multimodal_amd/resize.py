@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, seg_measures
+from . import _lib, instances as _instances, seg_measures
 from .engine import _ptr, _stream_ptr
 from .rg_detect import detect_camouflage_batch, segmentation_counts, segmentation_metrics
 from .rg_finetune import prepare_finetune_batch
@@ -316,16 +316,36 @@ def _score(preds, gts, threshold, cod, curves=False):
     return metrics, cods
 
 
+def _native_instances(preds, threshold, connectivity, min_area, fill_holes):
+    """``instances.detect_instances`` of every fp32 [H_i, W_i] map; maps of equal size share a call.  Returns (records, labels, clean
+    masks), three lists in the maps' order."""
+    groups = {}
+    for i, p in enumerate(preds):
+        groups.setdefault(tuple(p.shape), []).append(i)
+    rec, labels, clean = [None] * len(preds), [None] * len(preds), [None] * len(preds)
+    for idx in groups.values():
+        found = _instances.detect_instances(torch.stack([preds[i] for i in idx]), threshold, connectivity, min_area, fill_holes)
+        for j, i in enumerate(idx):
+            rec[i], labels[i], clean[i] = found["instances"][j], found["labels"][j], found["clean_mask"][j]
+    return rec, labels, clean
+
+
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
-                             cod_metrics=False, evaluate_at="native"):
+                             cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
     one buffer) and "mask_native": the list of bool [H_i, W_i] (probability > ``threshold``).  With ``gt_masks`` (N masks [H_i, W_i],
     uint8 positive above 127, or bool) "metrics" -- and "cod_metrics" with ``cod_metrics=True`` -- are taken per image against its own
     mask at its own size, which is where the benchmark tables take them; images of equal size share a call.
-    ``evaluate_at="resized"`` resizes the masks down (nearest) instead and scores at ``size``, as the reference does."""
+    ``evaluate_at="resized"`` resizes the masks down (nearest) instead and scores at ``size``, as the reference does.
+    ``instances=True`` takes the objects of every NATIVE-size map (``instances.detect_instances`` at ``threshold`` with ``min_area``,
+    ``fill_holes``, ``connectivity``; maps of equal size share a call): "instances_native" (per image the records),
+    "instance_labels_native" (int32 [H_i, W_i]) and "clean_mask_native" (bool [H_i, W_i]); with masks scored at native size also
+    "clean_metrics", ``segmentation_metrics`` of every clean mask against its own mask."""
+    if instances:
+        _instances.check_arguments(threshold, connectivity, min_area)
     if evaluate_at not in ("native", "resized"):
         raise ValueError(f'evaluate_at must be "native" or "resized", got {evaluate_at!r}')
     if cod_metrics and gt_masks is None:
@@ -349,6 +369,11 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         out["metrics"], cods = _score(native, [masks.image(i) for i in range(len(sizes))], threshold, cod_metrics)
         if cod_metrics:
             out["cod_metrics"] = cods
+    if instances:
+        rec, labels, clean = _native_instances(native, threshold, connectivity, min_area, fill_holes)
+        out.update({"instances_native": rec, "instance_labels_native": labels, "clean_mask_native": clean})
+        if masks is not None and not resized:
+            out["clean_metrics"], _ = _score([c.float() for c in clean], [masks.image(i) for i in range(len(sizes))], 0.5, False)
     return out
 
 

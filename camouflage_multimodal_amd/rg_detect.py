@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, seg_measures
+from . import _lib, instances as _instances, seg_measures
 from .engine import _ptr, _stream_ptr
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 
@@ -121,7 +121,8 @@ def segmentation_metrics(counts, H, W):
 
 
 @torch.no_grad()
-def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False):
+def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
+                            instances=False, min_area=0, fill_holes=False, connectivity=8):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -129,7 +130,13 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     against ``gt_masks`` [N, H, W] uint8 / bool) when ``gt_masks`` is given.  Host synchronisations: the graph sizes read-back and,
     with ``gt_masks``, one [N, 5] copy.  ``cod_metrics=True`` (needs ``gt_masks``) adds "cod_metrics": per image the dict of
     ``seg_measures.cod_metrics`` -- S-alpha, E-phi, the F-beta numbers, MAE on the 8-bit map and ``wf`` -- of the mask probability,
-    at the price of one more host copy, of the two small tables."""
+    at the price of one more host copy, of the two small tables.  ``instances=True`` adds the objects of the mask
+    (``instances.detect_instances`` of the mask probability at ``threshold`` with ``min_area``, ``fill_holes``, ``connectivity``):
+    "instances" (per image the records: id, area, box, centroid, score), "instance_labels" int32 [N, H, W], "clean_mask" bool
+    [N, H, W] (the mask without its small components, with its holes filled) and "instance_counts" int32 [N, 4]; with ``gt_masks``
+    also "clean_metrics", ``segmentation_metrics`` of the clean mask.  "metrics" and "cod_metrics" score the raw probability either way."""
+    if instances:
+        _instances.check_arguments(threshold, connectivity, min_area)
     img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
     N, H, W = img.shape[:3]
@@ -151,13 +158,21 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
             out["cod_metrics"] = seg_measures.cod_metrics(prob_maps[:, 0], gt)
     elif cod_metrics:
         raise ValueError("cod_metrics=True needs gt_masks")
+    if instances:
+        found = _instances.detect_instances(prob_maps[:, 0], threshold, connectivity, min_area, fill_holes)
+        out.update({"instances": found["instances"], "instance_labels": found["labels"], "clean_mask": found["clean_mask"],
+                    "instance_counts": found["counts"]})
+        if gt is not None:
+            out["clean_metrics"] = segmentation_metrics(segmentation_counts(found["clean_mask"].float(), gt, 0.5), H, W)
     return out
 
 
-def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False):
+def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
+                      min_area=0, fill_holes=False, connectivity=8):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
-    return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics)
+    return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
+                                   connectivity)

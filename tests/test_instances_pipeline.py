@@ -1,0 +1,131 @@
+"""The instance keywords of the detector entry points (camouflage_multimodal_amd/rg_detect.py, resize.py): a fresh
+``RegionGraphGNN``, two 64 x 96 images, 30 superpixels.  The new keys must be ``detect_instances`` of the call's own maps,
+"clean_metrics" the counts of the call's own clean mask, and ``instances=False`` must change nothing.
+
+The detector does not repeat itself bit for bit (``camo_rg_build_csr`` leaves a row's edges in no particular order:
+tests/test_resize_pipeline.py), so the comparison between two calls runs with every CSR row put into one order.
+"""
+import numpy as np
+import pytest
+import torch
+
+import slic_ref as SR
+
+pytestmark = pytest.mark.gpu
+NSEG = 30
+
+
+@pytest.fixture
+def fixed_row_order(monkeypatch):
+    """``build_target_csr_device`` with every row's edges after the leading self-loop sorted by source."""
+    from camouflage_multimodal_amd import region_graph, rg_finetune
+    real = region_graph.build_target_csr_device
+
+    def canonical(num_nodes, edge_index, edge_weight=None):
+        rowptr, col, w = real(num_nodes, edge_index, edge_weight)
+        rp = rowptr.long()
+        row = torch.repeat_interleave(torch.arange(num_nodes, device=col.device), rp[1:] - rp[:-1])
+        first = torch.zeros(col.shape[0], dtype=torch.bool, device=col.device)
+        first[rp[:-1]] = True
+        order = torch.argsort(row * (num_nodes + 1) + torch.where(first, torch.zeros_like(row), col.long() + 1), stable=True)
+        return rowptr, col[order].contiguous(), w[order].contiguous()
+    monkeypatch.setattr(region_graph, "build_target_csr_device", canonical)
+    monkeypatch.setattr(rg_finetune, "build_target_csr_device", canonical)
+
+
+def _model(seed=3):
+    from camouflage_multimodal_amd import RegionGraphGNN
+    torch.manual_seed(seed)
+    m = RegionGraphGNN().cuda().eval()
+    for bn in (m.bn1, m.bn2, m.bn3, m.bn4):
+        bn.running_mean.normal_(0, 0.1); bn.running_var.uniform_(0.5, 1.5)
+    return m
+
+
+def _disc(H, W, empty=False):
+    yy, xx = np.mgrid[:H, :W]
+    m = np.zeros((H, W), np.uint8)
+    if not empty:
+        m[(yy - H * 0.4) ** 2 + (xx - W * 0.55) ** 2 < (min(H, W) * 0.3) ** 2] = 255
+    return m
+
+
+def _threshold(prob):
+    """A threshold between the painted values, so the mask has both classes (a fresh model's probabilities sit close together)."""
+    v = torch.unique(prob)
+    return float((v[v.numel() // 2 - 1] + v[v.numel() // 2]) / 2) if v.numel() > 1 else 0.5
+
+
+def _same_instances(found, rec, labels, clean, counts=None):
+    assert rec == found["instances"]
+    assert torch.equal(labels, found["labels"]) and torch.equal(clean, found["clean_mask"]) and clean.dtype == torch.bool and labels.dtype == torch.int32
+    if counts is not None:
+        assert torch.equal(counts, found["counts"])
+
+
+def test_detect_camouflage_batch_instances(fixed_row_order):
+    from camouflage_multimodal_amd import (detect_camouflage, detect_camouflage_batch, detect_instances, segmentation_counts, segmentation_metrics)
+    m = _model()
+    H, W = 64, 96
+    img = torch.from_numpy(np.stack([SR.noise_image(H, W, 20 + i) for i in range(2)])).cuda()
+    gt = torch.from_numpy(np.stack([_disc(H, W), _disc(H, W, empty=True)])).cuda()
+    plain = detect_camouflage_batch(m, img, gt, n_segments=NSEG)
+    thr = _threshold(plain["prob_maps"][:, 0])
+    plain = detect_camouflage_batch(m, img, gt, n_segments=NSEG, threshold=thr)
+    off = detect_camouflage_batch(m, img, gt, n_segments=NSEG, threshold=thr, instances=False, min_area=9, fill_holes=True, connectivity=4)
+    assert list(off) == list(plain) and "instances" not in off and "clean_mask" not in off
+    assert off["prob_maps"].cpu().numpy().tobytes() == plain["prob_maps"].cpu().numpy().tobytes() and torch.equal(off["mask"], plain["mask"])
+    assert off["metrics"] == plain["metrics"]
+    assert 0 < int(plain["mask"].sum()) < plain["mask"].numel()
+
+    for kw in (dict(), dict(min_area=40, fill_holes=True, connectivity=4)):
+        out = detect_camouflage_batch(m, img, gt, n_segments=NSEG, threshold=thr, instances=True, **kw)
+        assert list(out)[:len(plain)] == list(plain) and set(out) - set(plain) == {"instances", "instance_labels", "clean_mask", "instance_counts", "clean_metrics"}
+        assert torch.equal(out["mask"], out["prob_maps"][:, 0] > thr)
+        found = detect_instances(out["prob_maps"][:, 0], thr, kw.get("connectivity", 8), kw.get("min_area", 0), kw.get("fill_holes", False))
+        _same_instances(found, out["instances"], out["instance_labels"], out["clean_mask"], out["instance_counts"])
+        assert len(out["instances"]) == 2 and sum(r["count"] for r in out["instances"]) >= 1
+        assert [r["pixels"] for r in out["instances"]] == out["clean_mask"].sum(dim=(1, 2)).tolist()
+        by_hand = segmentation_metrics(segmentation_counts(out["clean_mask"].float(), gt, 0.5), H, W)
+        assert out["clean_metrics"] == by_hand
+        clean, g = out["clean_mask"].cpu().numpy(), gt.cpu().numpy() > 127
+        for i in range(2):
+            assert by_hand[i]["tp"] == int((clean[i] & g[i]).sum()) and by_hand[i]["fp"] == int((clean[i] & ~g[i]).sum())
+        assert out["metrics"] == segmentation_metrics(segmentation_counts(out["prob_maps"][:, 0], gt, thr), H, W)      # the raw probability, as before
+        if not kw:
+            assert torch.equal(out["clean_mask"], out["mask"]) and out["clean_metrics"][0]["iou"] == out["metrics"][0]["iou"]
+        else:
+            assert all(r["area"] >= 40 for rec in out["instances"] for r in rec["instances"])
+    no_gt = detect_camouflage_batch(m, img, n_segments=NSEG, threshold=thr, instances=True)
+    assert "clean_metrics" not in no_gt and "metrics" not in no_gt and "instances" in no_gt
+    one = detect_camouflage(m, img[1], gt[1], n_segments=NSEG, threshold=thr, instances=True, min_area=40, fill_holes=True, connectivity=4)
+    found = detect_instances(one["prob_maps"][:, 0], thr, 4, 40, True)
+    _same_instances(found, one["instances"], one["instance_labels"], one["clean_mask"], one["instance_counts"])
+    assert len(one["clean_metrics"]) == 1
+
+
+def test_detect_camouflage_ragged_instances_at_native_size():
+    from camouflage_multimodal_amd import detect_camouflage_ragged, detect_instances, segmentation_counts, segmentation_metrics
+    m = _model()
+    shapes = ((48, 80), (96, 64), (48, 80))                        # two distinct native sizes; the first and the third share a call
+    images = [np.rint(SR.noise_image(H, W, 50 + i) * 255).astype(np.uint8) for i, (H, W) in enumerate(shapes)]
+    masks = [_disc(H, W, empty=i == 1) for i, (H, W) in enumerate(shapes)]
+    base = detect_camouflage_ragged(m, images, masks, size=(64, 64), n_segments=NSEG)
+    thr = _threshold(base["prob_maps"][:, 0])
+    kw = dict(min_area=12, fill_holes=True, connectivity=8)
+    out = detect_camouflage_ragged(m, images, masks, size=(64, 64), n_segments=NSEG, threshold=thr, instances=True, **kw)
+    assert set(out) - set(base) == {"instances_native", "instance_labels_native", "clean_mask_native", "clean_metrics"}
+    assert "instances" not in out and len(out["instances_native"]) == 3
+    for i, (H, W) in enumerate(shapes):
+        native = out["prob_maps_native"][i]
+        assert tuple(native.shape) == (H, W)
+        found = detect_instances(native, thr, 8, 12, True)           # that image's map alone
+        assert out["instances_native"][i] == found["instances"][0]
+        assert torch.equal(out["instance_labels_native"][i], found["labels"][0]) and torch.equal(out["clean_mask_native"][i], found["clean_mask"][0])
+        g = torch.from_numpy(masks[i]).cuda()
+        assert out["clean_metrics"][i] == segmentation_metrics(segmentation_counts(found["clean_mask"][0].float(), g, 0.5), H, W)[0]
+    assert sum(r["count"] for r in out["instances_native"]) >= 1
+    off = detect_camouflage_ragged(m, images, masks, size=(64, 64), n_segments=NSEG, threshold=thr, instances=False, **kw)
+    assert list(off) == list(base)
+    no_gt = detect_camouflage_ragged(m, images, size=(64, 64), n_segments=NSEG, threshold=thr, instances=True)
+    assert "clean_metrics" not in no_gt and len(no_gt["clean_mask_native"]) == 3
