@@ -1,7 +1,8 @@
 """Region-Graph GNN embedding path.  PARITY UNPINNED: torch_geometric is absent and the
 reference ships neither RG weights nor RG fixtures, so (1) the numpy restatement of the published GATConv /
 GCNConv algorithms is checked for algebraic self-consistency on CPU, (2) the HIP kernels are checked against that
-restatement on the GPU, (3) the host mirror keeps the reference's state_dict names."""
+restatement on the GPU, (3) the host mirror keeps the reference's state_dict names.
+Every graph here is a make_graph graph; tests/test_rg_gnn_forward.py holds the same path to float64 on everything that is not."""
 import numpy as np
 import pytest
 import torch
