@@ -1,7 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks, and the object instances of a predicted mask.
+// the node targets from ground-truth masks, the object instances of a predicted mask, and the guided-filter refinement of a mask.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,7 @@
 #include "rg_train.h"
 #include "rg_targets.h"
 #include "instances.h"
+#include "guided.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -29,6 +30,7 @@
 #include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
 #include "../../include/camo_instances.h"
+#include "../../include/camo_guided.h"
 
 using namespace camo_abi;
 
@@ -690,6 +692,56 @@ int camo_instances(const float* pred, int64_t pred_image_stride, float threshold
   if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_instances_workspace_bytes()");
   CK(launch_instances(pred, pred_image_stride, threshold, N, H, W, connectivity, min_area, fill_holes != 0, max_instances, w, labels, clean,
                       reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "instances");
+  return 0;
+}
+
+// ---- Edge-aware mask refinement: guided filter and native-size apply (include/camo_guided.h) ---------------------
+static int gf_check(int N, int H, int W, int C) {
+  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
+  if (N > CAMO_RGD_MAX_IMAGES) return fail(CAMO_E_ARG, "N exceeds CAMO_RGD_MAX_IMAGES");
+  if (H > CAMO_RSZ_MAX_SIDE || W > CAMO_RSZ_MAX_SIDE) return fail(CAMO_E_ARG, "H or W exceeds CAMO_RSZ_MAX_SIDE");
+  if ((long long)H * W > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGD_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_RGD_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGD_MAX_PIXELS");
+  if (C != 1 && C != 3) return fail(CAMO_E_ARG, "C must be 1 (grey guide) or 3 (colour guide)");
+  return 0;
+}
+
+size_t camo_guided_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C) {
+  if (gf_check(N, H, W, C)) return 0;
+  return gf_carve(N, H, W, C, nullptr).bytes;
+}
+
+int camo_guided_filter(const float* guide, const float* p, int64_t p_image_stride, int32_t N, int32_t H, int32_t W, int32_t C, int32_t radius,
+                       double eps, int32_t clamp, float* q, float* coef, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = gf_check(N, H, W, C)) return e;
+  if (radius < 1 || radius > CAMO_GF_MAX_RADIUS) return fail(CAMO_E_ARG, "radius must be in [1, CAMO_GF_MAX_RADIUS]");
+  if (!(eps >= CAMO_GF_MIN_EPS && eps <= CAMO_GF_MAX_EPS)) return fail(CAMO_E_ARG, "eps must be in [CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS]");
+  if (clamp != 0 && clamp != 1) return fail(CAMO_E_ARG, "clamp must be 0 or 1");
+  if (p_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "p_image_stride must be >= H * W");
+  if (!guide || !p || !q || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if ((reinterpret_cast<uintptr_t>(guide) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(coef)) & 3)
+    return fail(CAMO_E_ARG, "guide, p, q and coef must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const GfWs w = gf_carve(N, H, W, C, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_guided_workspace_bytes()");
+  CK(launch_guided_filter(guide, p, p_image_stride, N, H, W, C, radius, eps, clamp != 0, q, coef, w, static_cast<hipStream_t>(stream)),
+     "guided filter");
+  return 0;
+}
+
+int camo_guided_apply(const float* coef, int32_t N, int32_t C, int32_t h, int32_t w, const uint8_t* guide, int64_t guide_elems, float* out,
+                      int64_t out_elems, const int64_t* table, int64_t max_dst_pixels, int32_t clamp, int32_t* status, void* stream) {
+  if (int e = gf_check(N, h, w, C)) return e;
+  if (clamp != 0 && clamp != 1) return fail(CAMO_E_ARG, "clamp must be 0 or 1");
+  if (guide_elems < 1) return fail(CAMO_E_ARG, "need guide_elems >= 1");
+  if (out_elems < 1) return fail(CAMO_E_ARG, "need out_elems >= 1");
+  if (max_dst_pixels < 1 || max_dst_pixels > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "need 1 <= max_dst_pixels <= CAMO_RGD_MAX_IMAGE_PIXELS");
+  if (!coef || !guide || !out || !table || !status) return fail(CAMO_E_ARG, "null pointer argument");
+  if ((reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(status)) & 3)
+    return fail(CAMO_E_ARG, "coef, out and status must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
+  CK(launch_guided_apply(coef, N, C, h, w, guide, guide_elems, out, out_elems, reinterpret_cast<const long long*>(table), max_dst_pixels,
+                         clamp != 0, status, static_cast<hipStream_t>(stream)), "guided apply");
   return 0;
 }
 }  // extern "C"

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, instances as _instances, seg_measures
+from . import _lib, instances as _instances, refine as _refine, seg_measures
 from .engine import _ptr, _stream_ptr
 from .rg_detect import detect_camouflage_batch, segmentation_counts, segmentation_metrics
 from .rg_finetune import prepare_finetune_batch
@@ -332,7 +332,7 @@ def _native_instances(preds, threshold, connectivity, min_area, fill_holes):
 
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
-                             cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8):
+                             cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -343,9 +343,17 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     ``instances=True`` takes the objects of every NATIVE-size map (``instances.detect_instances`` at ``threshold`` with ``min_area``,
     ``fill_holes``, ``connectivity``; maps of equal size share a call): "instances_native" (per image the records),
     "instance_labels_native" (int32 [H_i, W_i]) and "clean_mask_native" (bool [H_i, W_i]); with masks scored at native size also
-    "clean_metrics", ``segmentation_metrics`` of every clean mask against its own mask."""
+    "clean_metrics", ``segmentation_metrics`` of every clean mask against its own mask.
+    ``refine`` (``detect_camouflage_batch``'s; the guide must be "rgb") runs the guided filter at ``size`` on the resized image and
+    applies its coefficients to the NATIVE bytes of every image (``refine.guided_upsample``: the fast guided filter), so the native
+    map's edges come from the native pixels: "prob_maps_native_refined" (fp32 [H_i, W_i], views of one buffer) and
+    "mask_native_refined" beside ``detect_camouflage_batch``'s own refine keys at ``size``; with masks scored at native size also
+    "refined_metrics" / "refined_cod_metrics" of the native refined maps.  "prob_maps_native" and the rest are unchanged."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
+    refine = _refine.refine_options(refine)
+    if refine is not None and refine["guide"] != "rgb":
+        raise ValueError('detect_camouflage_ragged applies the coefficients to the native 3-channel bytes: refine["guide"] must be "rgb"')
     if evaluate_at not in ("native", "resized"):
         raise ValueError(f'evaluate_at must be "native" or "resized", got {evaluate_at!r}')
     if cod_metrics and gt_masks is None:
@@ -361,7 +369,7 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         raise ValueError("every ground-truth mask must have its image's size")
     resized = masks is not None and evaluate_at == "resized"
     gt = resize_batch(masks, size, "nearest", out_dtype=torch.uint8) if resized else None
-    out = detect_camouflage_batch(rg_model, img, gt, n_segments, threshold, img.device, cod_metrics and resized)
+    out = detect_camouflage_batch(rg_model, img, gt, n_segments, threshold, img.device, cod_metrics and resized, refine=refine)
     native, _ = resize_to_sizes(out["prob_maps"][:, 0], sizes, "bilinear")
     out["prob_maps_native"] = native
     out["mask_native"] = [p > threshold for p in native]
@@ -374,6 +382,14 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         out.update({"instances_native": rec, "instance_labels_native": labels, "clean_mask_native": clean})
         if masks is not None and not resized:
             out["clean_metrics"], _ = _score([c.float() for c in clean], [masks.image(i) for i in range(len(sizes))], 0.5, False)
+    if refine is not None:
+        refined, _ = _refine.guided_upsample(out["refine_coefficients"], packed)
+        out["prob_maps_native_refined"] = refined
+        out["mask_native_refined"] = [p > threshold for p in refined]
+        if masks is not None and not resized:
+            out["refined_metrics"], cods = _score(refined, [masks.image(i) for i in range(len(sizes))], threshold, cod_metrics)
+            if cod_metrics:
+                out["refined_cod_metrics"] = cods
     return out
 
 
@@ -419,8 +435,11 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     ``**kw`` goes to it).  With ``mask_dir`` every image needs a mask file of the same stem.  With ``out_dir`` every native-size mask
     probability is written there as ``<stem>.png``, 8 bits, quantised as include/camo_seg_measures.h quantises (``quantise_map``).
     Returns {"files": stems, "metrics": per-file ``segmentation_metrics`` dicts and, with ``cod_metrics=True``, "cod_metrics":
-    per-file measures and "aggregate": ``seg_measures.aggregate_cod_measures`` of them}; the last three only with masks."""
+    per-file measures and "aggregate": ``seg_measures.aggregate_cod_measures`` of them}; the last three only with masks.
+    With ``refine`` (``detect_camouflage_ragged``'s) the map written to ``out_dir`` and the map scored are the REFINED ones
+    ("prob_maps_native_refined"; "prob_refined" with ``evaluate_at="resized"``); without it nothing changes."""
     from PIL import Image
+    refined = _refine.refine_options(kw.get("refine")) is not None
     cod = bool(kw.pop("cod_metrics", False))
     evaluate_at = kw.pop("evaluate_at", "native")
     threshold = kw.get("threshold", 0.5)
@@ -442,7 +461,7 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         part = stems[at:at + int(batch_size)]
         arrays = [np.array(Image.open(images[s]).convert("RGB")) for s in part]
         out = detect_camouflage_ragged(rg_model, arrays, **kw)
-        native = out["prob_maps_native"]
+        native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
         if out_dir is not None:
             for s, p in zip(part, native):
                 Image.fromarray(quantise_map(p).cpu().numpy()).save(os.path.join(out_dir, s + ".png"))
@@ -450,7 +469,7 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
             gts = _mask_list([np.array(Image.open(masks[s]).convert("L")) for s in part], len(part), "masks", native[0].device)
             if evaluate_at == "resized":
                 small = resize_batch(gts, size, "nearest", out_dtype=torch.uint8)
-                m, c = _score(list(out["prob_maps"][:, 0]), list(small), threshold, cod, curves=True)
+                m, c = _score(list(out["prob_refined"] if refined else out["prob_maps"][:, 0]), list(small), threshold, cod, curves=True)
             else:
                 m, c = _score(native, [gts.image(i) for i in range(len(part))], threshold, cod, curves=True)
             metrics += m

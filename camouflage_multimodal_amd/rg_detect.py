@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, instances as _instances, seg_measures
+from . import _lib, instances as _instances, refine as _refine, seg_measures
 from .engine import _ptr, _stream_ptr
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 
@@ -122,7 +122,7 @@ def segmentation_metrics(counts, H, W):
 
 @torch.no_grad()
 def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
-                            instances=False, min_area=0, fill_holes=False, connectivity=8):
+                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -134,9 +134,17 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     (``instances.detect_instances`` of the mask probability at ``threshold`` with ``min_area``, ``fill_holes``, ``connectivity``):
     "instances" (per image the records: id, area, box, centroid, score), "instance_labels" int32 [N, H, W], "clean_mask" bool
     [N, H, W] (the mask without its small components, with its holes filled) and "instance_counts" int32 [N, 4]; with ``gt_masks``
-    also "clean_metrics", ``segmentation_metrics`` of the clean mask.  "metrics" and "cod_metrics" score the raw probability either way."""
+    also "clean_metrics", ``segmentation_metrics`` of the clean mask.  "metrics" and "cod_metrics" score the raw probability either way.
+    ``refine`` -- ``None`` (off: no launch more than before), ``True`` or a dict with any of "radius" (8), "eps" (1e-4), "guide" ("rgb",
+    or "gray": the luma 0.2989 r + 0.5870 g + 0.1140 b of the image, taken in fp32 on the device) -- snaps the mask probability to
+    the image's edges with ``refine.guided_filter`` (include/camo_guided.h) and adds "prob_refined" fp32 [N, H, W] (clamped to
+    [0, 1]), "mask_refined" bool [N, H, W] (> ``threshold``) and "refine_coefficients" fp32 [N, C + 1, H, W] (what
+    ``refine.guided_upsample`` takes to a native size); with ``gt_masks`` also "refined_metrics" and, with ``cod_metrics=True``,
+    "refined_cod_metrics".  Every other key keeps its bytes; the instances of the refined map are
+    ``detect_instances(out["prob_refined"], ...)``."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
+    refine = _refine.refine_options(refine)
     img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
     N, H, W = img.shape[:3]
@@ -164,15 +172,23 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
                     "instance_counts": found["counts"]})
         if gt is not None:
             out["clean_metrics"] = segmentation_metrics(segmentation_counts(found["clean_mask"].float(), gt, 0.5), H, W)
+    if refine is not None:
+        guide = img if refine["guide"] == "rgb" else _refine.luma(img)
+        q, coef = _refine.guided_filter(guide, prob_maps[:, 0], refine["radius"], refine["eps"], True, True)
+        out.update({"prob_refined": q, "mask_refined": q > threshold, "refine_coefficients": coef})
+        if gt is not None:
+            out["refined_metrics"] = segmentation_metrics(segmentation_counts(q, gt, threshold), H, W)
+            if cod_metrics:
+                out["refined_cod_metrics"] = seg_measures.cod_metrics(q, gt)
     return out
 
 
 def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
-                      min_area=0, fill_holes=False, connectivity=8):
+                      min_area=0, fill_holes=False, connectivity=8, refine=None):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
     return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
-                                   connectivity)
+                                   connectivity, refine)
