@@ -19,15 +19,17 @@ __attribute__((visibility("hidden"))) int fail_hip(int e, const char* where);
     if (e_ != 0) return camo_abi::fail_hip(e_, where); \
   } while (0)
 
+// Hands out consecutive 256-byte aligned pieces of a workspace (null base: sizes only), from `start` on: a layout that continues another's.
 struct Carver {
   char* base; size_t off;
-  explicit Carver(void* b) : base(static_cast<char*>(b)), off(0) {}
+  explicit Carver(void* b, size_t start = 0) : base(static_cast<char*>(b)), off(start) {}
   template <typename T> T* take(size_t n) {
     off = (off + 255) & ~size_t(255);
     T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += n * sizeof(T);
     return p;
   }
+  size_t bytes() const { return (off + 255) & ~size_t(255); }      // what has been taken, the last piece rounded up like the others
 };
 
 struct GB {

@@ -6,16 +6,18 @@
 //                rows then columns in LDS, division by the blur of an all-ones image (a row factor times a column
 //                factor), 3 x 3 Sobel on the smoothed tile with the border pixel repeated -> gi, gj, magnitude
 //   label tiles  one block per tile: class of each pixel (interpolated non-maximum suppression + the two thresholds,
-//                fp32 without contraction), union-find of the tile's weak pixels in LDS over the W / NW / N / NE
-//                neighbours, flattened: every weak pixel points at the smallest index of its component inside the tile
-//   join tiles   weak pixels on a tile border: the same union with their neighbours in other tiles, on the global labels
+//                fp32 without contraction), then the 8-connected components of the tile's weak pixels in LDS (cc_inl.h):
+//                every weak pixel points at the smallest index of its component inside the tile
+//   join tiles   weak pixels on a tile border: cc_inl.h's unions with their neighbours in other tiles, on the global labels
 //   flag         every weak pixel finds its root and points at it; strong pixels set flag[root]
 //   emit         edges = weak and flag[root]
 //
-// Union by atomicMin on the larger root: parents only ever decrease, so there are no cycles, a component's root is its
-// smallest index whatever the order the unions ran in, and the output depends on the partition alone.
+// A component's root is its smallest index whatever the order the unions ran in (cc_inl.h), so the output depends on the
+// partition alone.
 #include <hip/hip_runtime.h>
+#include "abi_util.h"
 #include "canny.h"
+#include "cc_inl.h"
 
 namespace {
 
@@ -107,28 +109,6 @@ __device__ __forceinline__ int canny_classify(const float* __restrict__ g, int y
   return keep ? (m >= high ? 2 : 1) : 0;
 }
 
-template <int SCOPE>
-__device__ __forceinline__ int uf_find(int* L, int x) {
-  for (;;) {
-    const int p = __hip_atomic_load(L + x, __ATOMIC_RELAXED, SCOPE);
-    if (p == x) return x;
-    x = p;
-  }
-}
-// joins the components of a and b.  The larger root is pointed at the smaller with atomicMin; when another thread
-// linked that root first (the old value is not the root itself) its new parent still has to meet b: once more from there
-template <int SCOPE>
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find<SCOPE>(L, a); b = uf_find<SCOPE>(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
-    if (old == a) return;
-    a = old;
-  }
-}
-
 template <bool CLASSIFY>
 __global__ __launch_bounds__(NT) void canny_label_tiles_kernel(const float* __restrict__ grad, const unsigned char* __restrict__ cls_in,
                                                                unsigned char* __restrict__ cls_out, float low, float high, int H, int W,
@@ -145,56 +125,30 @@ __global__ __launch_bounds__(NT) void canny_label_tiles_kernel(const float* __re
       else c = cls_in[p];
       flag[p] = 0;
     }
-    lab[l] = c ? l : -1;
+    lab[l] = cc_run_parent<T, NT>(l, c != 0, cc_all{});
   }
   __syncthreads();
-  for (int l = tid; l < T * T; l += NT) {
-    if (lab[l] < 0) continue;                                   // (a weak pixel's entry never goes negative)
-    const int ly = l / T, lx = l % T;
-    if (lx > 0 && lab[l - 1] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l, l - 1);
-    if (ly > 0) {
-      if (lx > 0 && lab[l - T - 1] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l, l - T - 1);
-      if (lab[l - T] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l, l - T);
-      if (lx < T - 1 && lab[l - T + 1] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l, l - T + 1);
-    }
-  }
+  for (int l = tid; l < T * T; l += NT) cc_tile_unions<8, T>(lab, l, cc_all{});
   __syncthreads();
   for (int l = tid; l < T * T; l += NT) {
     const int y = y0 + l / T, x = x0 + l % T;
     if (y >= H || x >= W) continue;
-    int r = -1;
-    if (lab[l] >= 0) {
-      const int q = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l);    // (no entry changes after the barrier)
-      r = (int)(base + (size_t)(y0 + q / T) * W + (x0 + q % T));       // row-major order inside the tile = order of the batch index
-    }
-    label[base + (size_t)y * W + x] = r;
+    label[base + (size_t)y * W + x] = lab[l] >= 0 ? cc_tile_root<T>(lab, l, base, y0, x0, W) : -1;
   }
 }
 
 __global__ __launch_bounds__(NT) void canny_join_tiles_kernel(int* label, int N, int H, int W) {
   const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
-  const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
-  const int ty = y % T, tx = x % T;
-  if (ty != 0 && tx != 0 && tx != T - 1) return;
-  if (label[p] < 0) return;                                     // (written by the launch before; stays >= 0)
-  const int i = (int)p;
-  constexpr int SC = __HIP_MEMORY_SCOPE_AGENT;
-  if (tx == 0 && x > 0 && label[p - 1] >= 0) uf_union<SC>(label, i, i - 1);
-  if (y > 0) {
-    if ((ty == 0 || tx == 0) && x > 0 && label[p - W - 1] >= 0) uf_union<SC>(label, i, i - W - 1);
-    if (ty == 0 && label[p - W] >= 0) uf_union<SC>(label, i, i - W);
-    if ((ty == 0 || tx == T - 1) && x < W - 1 && label[p - W + 1] >= 0) uf_union<SC>(label, i, i - W + 1);
-  }
+  // (a weak pixel's label was written by the launch before and stays >= 0)
+  cc_join_borders<8, T>(label, p, H, W, [label](long long q) { return label[q] >= 0; }, cc_all{});
 }
 
 __global__ __launch_bounds__(NT) void canny_flag_kernel(int* label, const unsigned char* __restrict__ cls, unsigned char* flag, long long total) {
   const long long p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
   if (label[p] < 0) return;
-  // (other threads shorten chains meanwhile: an entry read here is the old parent or the root, both lead to the root)
-  const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(label, (int)p);
-  if (r != (int)p) __hip_atomic_store(label + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int r = cc_flatten(label, p);
   if (cls[p] >= 2) flag[r] = 1;                                 // (every writer stores the same byte)
 }
 
@@ -212,14 +166,12 @@ __global__ __launch_bounds__(NT) void canny_emit_kernel(const int* __restrict__ 
 
 CannyWs canny_carve(size_t npix, void* base) {
   CannyWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-  w.grad = reinterpret_cast<float*>(take(3 * npix * sizeof(float)));
-  w.cls = reinterpret_cast<unsigned char*>(take(npix));
-  w.label = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.flag = reinterpret_cast<unsigned char*>(take(npix));
-  w.bytes = off;
+  camo_abi::Carver c(base);
+  w.grad = c.take<float>(3 * npix);
+  w.cls = c.take<unsigned char>(npix);
+  w.label = c.take<int>(npix);
+  w.flag = c.take<unsigned char>(npix);
+  w.bytes = c.bytes();
   return w;
 }
 

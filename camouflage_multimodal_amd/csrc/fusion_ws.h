@@ -38,8 +38,7 @@ inline Desc desc_carve(int B, int T, void* base) {
   Carver c(base);
   d.row_sample = c.take<int>((size_t)T); d.inv_nr = c.take<float>((size_t)B); d.tile_off = c.take<int>((size_t)B + 1);
   d.tile_desc = c.take<int4>((size_t)T / 32 + B);       // one entry per block of the fused kernels' RG tile range
-  c.off = (c.off + 255) & ~size_t(255);
-  d.bytes = c.off;
+  d.bytes = c.bytes();
   return d;
 }
 
@@ -73,7 +72,7 @@ inline ShadowSet shadow_carve(void* base) {
   ShadowSet s{};
   Take c(base);
   carve_shadows_forward(c, s); carve_shadows_transposed(c, s); carve_shadows_fold(c, s);
-  s.bytes = (c.off + 255) & ~size_t(255);
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -241,8 +240,7 @@ template <class C> Ws carve_with(C& c, const camo_dims_t& d, int B, int T, int N
     c(w.F1, B * H, "F1"); c(w.a2, B * F); c(w.fused, B * F, "fused"); c(w.hid, B * 4 * Fh, "hid");      // (F1: a1)
     c(w.dlog, B * Wd); c(w.dhid, B * 4 * Fh, "dhid"); c(w.da2, B * F); c(w.dF1, B * H, "dF1");
   }
-  c.off = (c.off + 255) & ~size_t(255);
-  w.bytes = c.off;
+  w.bytes = c.bytes();
   return w;
 }
 inline Ws carve(const camo_dims_t& d, int B, int T, int Nk, void* base) { Take c(base); return carve_with(c, d, B, T, Nk); }

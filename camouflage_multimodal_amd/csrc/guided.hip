@@ -12,6 +12,7 @@
 //   apply      camo_resize's bilinear taps on the C + 1 coefficient planes, kept in double, times the native u8 pixel -> fp32
 #include <hip/hip_runtime.h>
 
+#include "abi_util.h"
 #include "guided.h"
 #include "resize_taps.h"
 #include "../../include/camo_guided.h"
@@ -225,13 +226,11 @@ __global__ __launch_bounds__(NT) void gf_apply(const float* __restrict__ coef, i
 
 GfWs gf_carve(int N, int H, int W, int C, void* base) {
   GfWs ws{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  camo_abi::Carver c(base);
   const size_t npix = (size_t)N * H * W;
-  ws.sums = reinterpret_cast<double*>(take(npix * gf_sum_planes(C) * sizeof(double)));
-  ws.ab = reinterpret_cast<double*>(take(npix * (C + 1) * sizeof(double)));
-  ws.bytes = off;
+  ws.sums = c.take<double>(npix * gf_sum_planes(C));
+  ws.ab = c.take<double>(npix * (C + 1));
+  ws.bytes = c.bytes();
   return ws;
 }
 

@@ -3,9 +3,9 @@
 // and 5 B/pixel out: the work is launches and latency, so every grid covers the whole batch.
 //
 //   label tiles  one block per 32 x 32 tile: membership of each pixel (background for the hole pass; foreground, or foreground and
-//                holes, for the component pass), union-find of the tile's members in LDS over the W / N (and NW / NE) neighbours,
-//                flattened: every member points at the smallest index of its component inside the tile
-//   join tiles   members on a tile border: the same union with their neighbours in other tiles, on the global parents
+//                holes, for the component pass), then the components of the tile's members in LDS (cc_inl.h): every member points
+//                at the smallest index of its component inside the tile
+//   join tiles   members on a tile border: cc_inl.h's unions with their neighbours in other tiles, on the global parents
 //   flatten      every member finds its root and points at it.  Hole pass: a member on the image's border sets border[root].
 //                Component pass: area[root] += 1, runs of equal root combined in the wave and the block's first root in the block
 //   count        per chunk of 1024 pixels: the kept roots, the dropped roots, the pixels of the kept
@@ -14,13 +14,15 @@
 //   emit         labels, clean, and the table's sums, minima and maxima, through a block's LDS slots
 //
 // With fill_holes the first three run twice: on the background with the complementary connectivity, then on the filled foreground.
-// Union by atomicMin on the larger root (uf_inl.h): the output depends on the partition alone.  Integer atomics only.
+// Union by atomicMin on the larger root (cc_inl.h): the output depends on the partition alone.  Integer atomics only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "abi_util.h"
+#include "cc_inl.h"
+#include "common.h"
 #include "instances.h"
-#include "uf_inl.h"
 
 namespace {
 
@@ -28,37 +30,13 @@ constexpr int T = INST_TILE, NT = INST_NT, CHUNK = INST_CHUNK, PPT = INST_CHUNK 
 constexpr int MODE_BG = 0, MODE_FG = 1, MODE_FILLED = 2;
 constexpr int NONE = 0x7fffffff;
 constexpr unsigned long long BOX_MIN_INIT = 0x7fffffffffffffffull;
-static_assert(T == 32 && T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "a tile row is half a wave; whole waves, whole passes");
+static_assert(T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "whole waves, whole passes");
 
 // include/camo_seg_measures.h's quantisation: clamp (a NaN to 0), one fp32 multiply, round to nearest even
 __device__ __forceinline__ int quantise(float v) {
   v = v == v ? v : 0.f;
   v = fminf(fmaxf(v, 0.f), 1.f);
   return (int)rintf(v * 255.0f);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
-  return v;
 }
 
 // Runs of consecutive lanes with the same key (`head`: the lane starts a run): the lane one past the end of the calling lane's run.
@@ -108,38 +86,16 @@ __global__ __launch_bounds__(NT) void inst_label_tiles_kernel(const float* __res
           area[p] = 0;
         }
       }
-      // a row of the tile is half a wave: every member starts out pointing at the first pixel of its run in the row
-      const unsigned row = (unsigned)(__ballot(member) >> (tid & 32)), lx = tid & 31;
-      const unsigned gaps = ~row & ((1u << lx) - 1u);
-      lab[l] = member ? l - (int)lx + (gaps ? 32 - __clz((int)gaps) : 0) : -1;
+      lab[l] = cc_run_parent<T, NT>(l, member, cc_all{});
     }
     if (MODE == MODE_FILLED && nh) atomicAdd(&holes, nh);
     __syncthreads();
-    // The runs of one row meet the row above.  A union is left out where a neighbour's union says the same: with the pixel above,
-    // when the pixel to the left (same run) has a member above it too; with a diagonal pixel, when the pixel above is a member
-    // (same run as the diagonal one) or, for the upper left, when the pixel to the left is one
-    for (int l = tid; l < T * T; l += NT) {
-      if (lab[l] < 0 || l < T) continue;                            // (a member's entry never goes negative)
-      const int lx = l % T;
-      constexpr int SC = __HIP_MEMORY_SCOPE_WORKGROUP;
-      const bool up = lab[l - T] >= 0, left = lx > 0 && lab[l - 1] >= 0, upleft = lx > 0 && lab[l - T - 1] >= 0;
-      if (up) {
-        if (!(left && upleft)) uf_union<SC>(lab, l, l - T);
-      } else if (CONN == 8) {
-        if (upleft && !left) uf_union<SC>(lab, l, l - T - 1);
-        if (lx < T - 1 && lab[l - T + 1] >= 0) uf_union<SC>(lab, l, l - T + 1);
-      }
-    }
+    for (int l = tid; l < T * T; l += NT) cc_tile_unions<CONN, T>(lab, l, cc_all{});
     __syncthreads();
     for (int l = tid; l < T * T; l += NT) {
       const int y = y0 + l / T, x = x0 + l % T;
       if (y >= H || x >= W) continue;
-      int r = -1;
-      if (lab[l] >= 0) {
-        const int q = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, l);    // (no entry changes after the barrier)
-        r = (int)(base + (size_t)(y0 + q / T) * W + (x0 + q % T));       // row-major order inside the tile = order of the batch index
-      }
-      par[base + (size_t)y * W + x] = r;
+      par[base + (size_t)y * W + x] = lab[l] >= 0 ? cc_tile_root<T>(lab, l, base, y0, x0, W) : -1;
     }
     if (MODE == MODE_FILLED && tid == 0 && holes) atomicAdd(misc + n, holes);
     __syncthreads();                                                 // lab and holes are reused by the next image
@@ -150,23 +106,8 @@ template <int CONN>
 __global__ __launch_bounds__(NT) void inst_join_tiles_kernel(int* par, int N, int H, int W) {
   const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
-  const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
-  const int ty = y % T, tx = x % T;
-  if (ty != 0 && tx != 0 && (CONN == 4 || tx != T - 1)) return;
-  if (par[p] < 0) return;                                         // (written by the launch before; stays >= 0)
-  const int i = (int)p;
-  constexpr int SC = __HIP_MEMORY_SCOPE_AGENT;
-  // x > 0, y > 0, x < W - 1: a neighbour is a pixel of the same image, never the next image's first row or the row's other end
-  const bool left = x > 0 && par[p - 1] >= 0, up = y > 0 && par[p - W] >= 0, upleft = x > 0 && y > 0 && par[p - W - 1] >= 0;
-  // A union is left out where the neighbours' unions say the same.  Across a column border: when the pixel above (same tile) and
-  // the one above the left one are members -- the pixel above joins them.  Across a row border: when the pixel to the left (same
-  // tile) and the one above it are members.  A tile's corner pixel leaves out neither.  Diagonally: as in the tile kernel.
-  if (tx == 0 && left && !(ty != 0 && up && upleft)) uf_union<SC>(par, i, i - 1);
-  if (ty == 0 && up && !(tx != 0 && left && upleft)) uf_union<SC>(par, i, i - W);
-  if (CONN == 8 && !up) {
-    if ((ty == 0 || tx == 0) && upleft && !left) uf_union<SC>(par, i, i - W - 1);
-    if ((ty == 0 || tx == T - 1) && y > 0 && x < W - 1 && par[p - W + 1] >= 0) uf_union<SC>(par, i, i - W + 1);
-  }
+  // (a member's parent was written by the launch before and stays >= 0)
+  cc_join_borders<CONN, T>(par, p, H, W, [par](long long q) { return par[q] >= 0; }, cc_all{});
 }
 
 // hole pass: every background pixel points at its root; one on the image's border marks the root
@@ -174,9 +115,7 @@ __global__ __launch_bounds__(NT) void inst_flatten_bg_kernel(int* par, unsigned 
   const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
   if (par[p] < 0) return;
-  // (other threads shorten chains meanwhile: an entry read here is the old parent or the root, both lead to the root)
-  const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, (int)p);
-  if (r != (int)p) __hip_atomic_store(par + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int r = cc_flatten(par, p);
   const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
   if (y == 0 || y == H - 1 || x == 0 || x == W - 1) border[r] = 1;      // (every writer stores the same byte)
 }
@@ -197,13 +136,12 @@ __global__ __launch_bounds__(NT) void inst_flatten_area_kernel(int* par, int* __
     if (q < HW) {
       const size_t p = base + q;
       if (par[p] >= 0) {
-        r[j] = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, (int)p);
-        if (r[j] != (int)p) __hip_atomic_store(par + p, r[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        r[j] = cc_flatten(par, (long long)p);
         mine = min(mine, r[j]);
       }
     }
   }
-  mine = wave_min(mine);
+  mine = wave_min_int(mine);
   if (lane == 0 && mine != NONE) atomicMin(&dom, mine);
   __syncthreads();
   const int d = dom;
@@ -219,7 +157,7 @@ __global__ __launch_bounds__(NT) void inst_flatten_area_kernel(int* par, int* __
     const int end = run_end(head, lane);
     if (head && key >= 0) atomicAdd(area + key, end - lane);
   }
-  nd = wave_sum(nd);
+  nd = wave_sum_int(nd);
   if (lane == 0 && nd) atomicAdd(&dom_count, nd);
   __syncthreads();
   if (tid == 0) atomicAdd(area + d, dom_count);
@@ -243,7 +181,7 @@ __global__ __launch_bounds__(NT) void inst_count_kernel(const int* __restrict__ 
     const int a = area[p];
     if (a >= min_area) { ++nk; np += a; } else ++ns;
   }
-  nk = wave_sum(nk); ns = wave_sum(ns); np = wave_sum(np);
+  nk = wave_sum_int(nk); ns = wave_sum_int(ns); np = wave_sum_int(np);
   if (lane == 0) {
     if (nk) { atomicAdd(&s[0], nk); atomicAdd(&s[2], np); }
     if (ns) atomicAdd(&s[1], ns);
@@ -258,31 +196,15 @@ __global__ __launch_bounds__(NT) void inst_scan_kernel(int* __restrict__ chunk, 
   __shared__ int s[NT];
   __shared__ int tot[2];
   const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.x;
-  int* c = chunk + (size_t)n * chunks;
   const int* cs = chunk + ((size_t)N + n) * chunks;
   const int* cp = chunk + ((size_t)2 * N + n) * chunks;
   if (tid < 2) tot[tid] = 0;
-  int carry = 0, ns = 0, np = 0;
-  for (int c0 = 0; c0 < chunks; c0 += NT) {
-    const bool in = c0 + tid < chunks;
-    const int v = in ? c[c0 + tid] : 0;
-    if (in) { ns += cs[c0 + tid]; np += cp[c0 + tid]; }
-    s[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-      const int t = tid >= d ? s[tid - d] : 0;
-      __syncthreads();
-      s[tid] += t;
-      __syncthreads();
-    }
-    if (in) c[c0 + tid] = carry + s[tid] - v;
-    carry += s[NT - 1];
-    __syncthreads();
-  }
-  ns = wave_sum(ns); np = wave_sum(np);
+  int ns = 0, np = 0;
+  const int kept = cc_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [&](int i) { ns += cs[i]; np += cp[i]; });
+  ns = wave_sum_int(ns); np = wave_sum_int(np);
   if (lane == 0) { atomicAdd(&tot[0], ns); atomicAdd(&tot[1], np); }
   __syncthreads();
-  if (tid == 0) { counts[4 * n] = carry; counts[4 * n + 1] = tot[0]; counts[4 * n + 2] = misc[n]; counts[4 * n + 3] = tot[1]; }
+  if (tid == 0) { counts[4 * n] = kept; counts[4 * n + 1] = tot[0]; counts[4 * n + 2] = misc[n]; counts[4 * n + 3] = tot[1]; }
 }
 
 // grid (chunks, images): rid[root] = the component's id, 0 when it is dropped.  The image's table rows are cleared on the way, the
@@ -291,7 +213,7 @@ __global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ p
                                                        const int* __restrict__ chunk, const int* __restrict__ counts, int max_instances,
                                                        int* __restrict__ rid, unsigned long long* __restrict__ table) {
   __shared__ int wcount[NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y, HW = H * W;
+  const int tid = threadIdx.x, n = blockIdx.y, HW = H * W;
   const size_t base = (size_t)n * HW;
   {
     const long long K = counts[4 * n], cells = (long long)max_instances * 8;
@@ -307,14 +229,8 @@ __global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ p
     const size_t p = base + q;
     const bool root = q < HW && par[p] == (int)p;
     const bool kept = root && area[p] >= min_area;
-    const unsigned long long mask = __ballot(kept);
-    if (lane == 0) wcount[wave] = __popcll(mask);
-    __syncthreads();
-    int before = __popcll(mask & ((1ull << lane) - 1)), total = 0;
-    for (int i = 0; i < NT / 64; ++i) {
-      if (i < wave) before += wcount[i];
-      total += wcount[i];
-    }
+    int total;
+    const int before = cc_block_rank<NT>(kept, wcount, total);
     if (root) rid[p] = kept ? running + before + 1 : 0;
     running += total;
     __syncthreads();
@@ -400,17 +316,15 @@ unsigned blocks_of(long long count) { return (unsigned)((count + NT - 1) / NT); 
 
 InstWs inst_carve(int N, int H, int W, void* base) {
   InstWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  camo_abi::Carver c(base);
   const size_t npix = (size_t)N * H * W, chunks = ((size_t)H * W + CHUNK - 1) / CHUNK;
-  w.bgpar = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.par = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.area = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.border = reinterpret_cast<unsigned char*>(take(npix));
-  w.chunk = reinterpret_cast<int*>(take(3 * (size_t)N * chunks * sizeof(int)));
-  w.misc = reinterpret_cast<int*>(take((size_t)N * sizeof(int)));
-  w.bytes = off;
+  w.bgpar = c.take<int>(npix);
+  w.par = c.take<int>(npix);
+  w.area = c.take<int>(npix);
+  w.border = c.take<unsigned char>(npix);
+  w.chunk = c.take<int>(3 * (size_t)N * chunks);
+  w.misc = c.take<int>((size_t)N);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -53,8 +53,7 @@ RgWs rg_carve(const camo_rg_dims_t& d, int N, void* base) {
   w.Hh = c.take<float>(n * K * C); w.a_src = c.take<float>(n * K); w.a_dst = c.take<float>(n * K); w.dinv = c.take<float>(n);
   w.xw = c.take<float>(n * C);
   w.h[0] = w.h[2] = c.take<float>(n * C); w.h[1] = w.h[3] = c.take<float>(n * C);      // ping-pong: a layer reads one and writes the other
-  c.off = (c.off + 255) & ~size_t(255);
-  w.bytes = c.off;
+  w.bytes = c.bytes();
   return w;
 }
 int rg_check(const camo_rg_dims_t* d, int N) {
@@ -138,8 +137,7 @@ RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base, bool batch_s
   w.W1 = c.take<float>(units * C); w.b1 = c.take<float>(units);
   w.partial = c.take<float>((size_t)rgt_row_blocks(N) * rgt_partial_width(d, nc));
   if (batch_stats) w.stats = c.take<float>(4 * 2 * C);
-  c.off = (c.off + 255) & ~size_t(255);
-  w.bytes = c.off;
+  w.bytes = c.bytes();
   return w;
 }
 int rgt_check(const camo_rg_dims_t* d, int nc, int N, int E) {

@@ -25,6 +25,7 @@
 // nobody reads before the launch ends.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include "abi_util.h"
 #include "rg_batch.h"
 
 namespace {
@@ -332,18 +333,16 @@ __global__ __launch_bounds__(64) void rgb_emit_kernel(const unsigned int* __rest
 
 RgBatchWs rg_batch_carve(int N, int label_bound, void* base) {
   RgBatchWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  camo_abi::Carver c(base);
   const size_t nl = (size_t)N * label_bound;
   w.words = (label_bound + 31) / 32;
-  w.acc = reinterpret_cast<unsigned long long*>(take(nl * RGB_NACC * sizeof(unsigned long long)));
-  w.adj = reinterpret_cast<unsigned int*>(take(nl * w.words * sizeof(unsigned int)));
-  w.kept = reinterpret_cast<int*>(take((size_t)N * sizeof(int)));
-  w.rowcount = reinterpret_cast<int*>(take(nl * sizeof(int)));
-  w.rowoff = reinterpret_cast<int*>(take(nl * sizeof(int)));
-  w.pairs = reinterpret_cast<int*>(take((size_t)N * sizeof(int)));
-  w.bytes = off;
+  w.acc = c.take<unsigned long long>(nl * RGB_NACC);
+  w.adj = c.take<unsigned int>(nl * w.words);
+  w.kept = c.take<int>((size_t)N);
+  w.rowcount = c.take<int>(nl);
+  w.rowoff = c.take<int>(nl);
+  w.pairs = c.take<int>((size_t)N);
+  w.bytes = c.bytes();
   return w;
 }
 

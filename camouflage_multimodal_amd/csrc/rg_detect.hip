@@ -136,20 +136,6 @@ __global__ void rgd_clear_kernel(unsigned long long* __restrict__ counts, int to
   if (i < total) counts[i] = 0ull;
 }
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
-  return v;
-}
-
 // grid (blocks per image, N): a block strides over its image's pixels; per-thread integers -> wave -> block (LDS) -> five 64-bit
 // integer atomics per block.  Integer addition in any order gives the same sum.
 __global__ __launch_bounds__(NT) void rgd_counts_kernel(const float* __restrict__ pred, long long stride, const unsigned char* __restrict__ gt,

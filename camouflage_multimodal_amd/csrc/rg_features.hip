@@ -13,6 +13,7 @@
 //   count      one block per label a: kept neighbours b > a
 //   emit       scan of the counts (one block), then per label a its pairs (i, j), (j, i) with the weight [:226-234]
 #include <hip/hip_runtime.h>
+#include "abi_util.h"
 #include "rg_features.h"
 
 namespace {
@@ -186,14 +187,12 @@ __global__ __launch_bounds__(64) void rgf_emit_kernel(const unsigned char* __res
 
 RgGraphWs rg_graph_carve(int n_labels, void* base) {
   RgGraphWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
-  w.acc = reinterpret_cast<double*>(take((size_t)n_labels * RGF_NACC * sizeof(double)));
-  w.adj = reinterpret_cast<unsigned char*>(take(((size_t)n_labels * n_labels + 3) & ~(size_t)3));
-  w.rowcount = reinterpret_cast<int*>(take((size_t)n_labels * sizeof(int)));
-  w.rowoff = reinterpret_cast<int*>(take(((size_t)n_labels + 1) * sizeof(int)));
-  w.bytes = off;
+  camo_abi::Carver c(base);
+  w.acc = c.take<double>((size_t)n_labels * RGF_NACC);
+  w.adj = c.take<unsigned char>(((size_t)n_labels * n_labels + 3) & ~(size_t)3);
+  w.rowcount = c.take<int>((size_t)n_labels);
+  w.rowoff = c.take<int>((size_t)n_labels + 1);
+  w.bytes = c.bytes();
   return w;
 }
 

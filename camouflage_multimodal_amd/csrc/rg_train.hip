@@ -112,17 +112,6 @@ __global__ void head_logits_kernel(HeadPtrs P, const float* __restrict__ Z, floa
 }
 
 // ---- loss -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ONE block of 1024 threads.  First the integer counts of the non-ignored nodes, then per node the three terms and dlogits, already
 // scaled by weight / count; the sums are per-thread doubles in node order, a butterfly per wave, the 16 waves in order.
 __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ logits, const int* __restrict__ mask_t, const int* __restrict__ inst_t,

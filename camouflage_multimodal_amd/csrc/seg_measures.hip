@@ -25,20 +25,6 @@ __device__ __forceinline__ int quantise(float v) {
   return (int)rintf(v * 255.0f);
 }
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
-  return v;
-}
-
 // rint(a / b) of the exact rational, a half to the even neighbour (a >= 0, b >= 1)
 __device__ __forceinline__ long long rint_div(unsigned long long a, unsigned long long b) {
   const unsigned long long q = a / b, r = a - q * b;
@@ -311,8 +297,7 @@ WfWs wf_carve(int N, int H, int W, void* base) {
   const size_t px = (size_t)N * H * W;
   w.d2 = c.take<int>(px);
   w.src = c.take<unsigned char>(px);
-  c.off = (c.off + 255) & ~size_t(255);
-  w.bytes = c.off;
+  w.bytes = c.bytes();
   return w;
 }
 

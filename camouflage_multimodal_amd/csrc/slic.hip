@@ -12,17 +12,17 @@
 //                64-bit integer atomic per table entry and quantity to global memory; a full table falls through to
 //                global atomics directly.  Integer sums: any order gives the same bits
 //   finalize     one lane per centroid: divides, and leaves the sums cleared for the next round
-//   connect      tile-local then cross-tile union-find of equal labels over the W / N neighbours (root = smallest index = the
-//                component's first pixel, as in canny.hip); flatten + component sizes; one lane per small component runs its
+//   connect      the 4-connected components of equal labels by cc_inl.h's tiled union-find (label tiles, join tiles; root =
+//                smallest index = the component's first pixel); flatten + component sizes; one lane per small component runs its
 //                breadth-first search with a queue carved from workspace, and each block counts the large components that
 //                start in its chunk; exclusive prefix of the chunk counts per image; ranks of the large components; emit,
 //                which follows the adopted labels of small components down to a large one or to none
 //
-// Union by atomicMin on the larger root: parents only ever decrease, so there are no cycles and a component's root is its
-// smallest index whatever the order the unions ran in.  A small component adopts from a component with a smaller root, so the
-// chains that emit follows end.  The queue offsets come from an atomic counter and differ from run to run; nothing read
-// back depends on them.
+// A small component adopts from a component with a smaller root, so the chains that emit follows end.  The queue offsets come
+// from an atomic counter and differ from run to run; nothing read back depends on them.
 #include <hip/hip_runtime.h>
+#include "abi_util.h"
+#include "cc_inl.h"
 #include "slic.h"
 
 // include/camo_slic.h fixes the operation order of steps 5 and 6; hipcc contracts a * b + c by default
@@ -225,28 +225,7 @@ __global__ __launch_bounds__(NT) void slic_finalize_kernel(long long* __restrict
 
 // ---- connectivity ----------------------------------------------------------------------------------------------------------
 
-template <int SCOPE>
-__device__ __forceinline__ int uf_find(int* L, int x) {
-  for (;;) {
-    const int p = __hip_atomic_load(L + x, __ATOMIC_RELAXED, SCOPE);
-    if (p == x) return x;
-    x = p;
-  }
-}
-// joins the components of a and b (canny.hip): the larger root is pointed at the smaller with atomicMin; when another thread
-// linked that root first its new parent still has to meet b: once more from there
-template <int SCOPE>
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find<SCOPE>(L, a); b = uf_find<SCOPE>(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
-    if (old == a) return;
-    a = old;
-  }
-}
-
+// members are the pixels inside the image, linked on equal labels (cc_inl.h); size, mark and misc are cleared on the way
 __global__ __launch_bounds__(NT) void slic_label_tiles_kernel(const int* __restrict__ seg, int H, int W, int* __restrict__ parent,
                                                               int* __restrict__ size, unsigned char* __restrict__ mark, int* __restrict__ misc) {
   __shared__ int par[T * T];
@@ -259,43 +238,33 @@ __global__ __launch_bounds__(NT) void slic_label_tiles_kernel(const int* __restr
   }
   for (int l = tid; l < T * T; l += NT) {
     const int y = y0 + l / T, x = x0 + l % T;
-    const bool in = y < H && x < W;
-    if (in) {
+    if (y < H && x < W) {
       const size_t p = base + (size_t)y * W + x;
       val[l] = seg[p]; size[p] = 0; mark[p] = 0;
     }
-    par[l] = in ? l : -1;
   }
   __syncthreads();
-  for (int l = tid; l < T * T; l += NT) {
-    if (par[l] < 0) continue;                                   // (an entry inside the image never goes negative)
-    if (l % T > 0 && val[l - 1] == val[l]) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l, l - 1);
-    if (l / T > 0 && val[l - T] == val[l]) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l, l - T);
-  }
+  const auto same = [&](int a, int b) { return val[a] == val[b]; };
+  for (int l = tid; l < T * T; l += NT) par[l] = cc_run_parent<T, NT>(l, y0 + l / T < H && x0 + l % T < W, same);
+  __syncthreads();
+  for (int l = tid; l < T * T; l += NT) cc_tile_unions<4, T>(par, l, same);
   __syncthreads();
   for (int l = tid; l < T * T; l += NT) {
     if (par[l] < 0) continue;
-    const int q = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l);      // (no entry changes after the barrier)
-    parent[base + (size_t)(y0 + l / T) * W + (x0 + l % T)] = (int)(base + (size_t)(y0 + q / T) * W + (x0 + q % T));
+    parent[base + (size_t)(y0 + l / T) * W + (x0 + l % T)] = cc_tile_root<T>(par, l, base, y0, x0, W);
   }
 }
 
 __global__ __launch_bounds__(NT) void slic_join_tiles_kernel(const int* __restrict__ seg, int* parent, int N, int H, int W) {
   const long long total = (long long)N * H * W, p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
-  const int q = (int)(p % ((long long)H * W)), y = q / W, x = q - y * W;
-  constexpr int SC = __HIP_MEMORY_SCOPE_AGENT;
-  if (x % T == 0 && x > 0 && seg[p - 1] == seg[p]) uf_union<SC>(parent, (int)p, (int)p - 1);
-  if (y % T == 0 && y > 0 && seg[p - W] == seg[p]) uf_union<SC>(parent, (int)p, (int)p - W);
+  cc_join_borders<4, T>(parent, p, H, W, [](long long) { return true; }, [seg](long long a, long long b) { return seg[a] == seg[b]; });
 }
 
 __global__ __launch_bounds__(NT) void slic_flatten_kernel(int* parent, int* size, long long total) {
   const long long p = (long long)blockIdx.x * NT + threadIdx.x;
   if (p >= total) return;
-  // (other threads shorten chains meanwhile: an entry read here is the old parent or the root, both lead to the root)
-  const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)p);
-  if (r != (int)p) __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  atomicAdd(size + r, 1);
+  atomicAdd(size + cc_flatten(parent, p), 1);
 }
 
 // the breadth-first search of include/camo_slic.h step 8 for the small component whose first pixel is `root`: -> the root of the
@@ -356,42 +325,21 @@ __global__ __launch_bounds__(NT) void slic_search_kernel(const int* __restrict__
 // one block per image: chunk[] becomes its exclusive prefix; counts = {large components + 1, oversized components}
 __global__ __launch_bounds__(NT) void slic_scan_kernel(int* __restrict__ chunk, int chunks, const int* __restrict__ misc, int* __restrict__ counts) {
   __shared__ int s[NT];
-  const int tid = threadIdx.x, n = blockIdx.x;
-  int* c = chunk + (size_t)n * chunks;
-  int carry = 0;
-  for (int c0 = 0; c0 < chunks; c0 += NT) {
-    const int v = c0 + tid < chunks ? c[c0 + tid] : 0;
-    s[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-      const int t = tid >= d ? s[tid - d] : 0;
-      __syncthreads();
-      s[tid] += t;
-      __syncthreads();
-    }
-    if (c0 + tid < chunks) c[c0 + tid] = carry + s[tid] - v;
-    carry += s[NT - 1];
-    __syncthreads();
-  }
-  if (tid == 0) { counts[2 * n] = carry + 1; counts[2 * n + 1] = misc[1 + n]; }
+  const int n = blockIdx.x;
+  const int large = cc_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [](int) {});
+  if (threadIdx.x == 0) { counts[2 * n] = large + 1; counts[2 * n + 1] = misc[1 + n]; }
 }
 
 __global__ __launch_bounds__(NT) void slic_rank_kernel(const int* __restrict__ parent, const int* __restrict__ size, int H, int W, int min_size,
                                                        const int* __restrict__ chunk, int* __restrict__ adj) {
   __shared__ int wcount[NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y, HW = H * W, base = n * HW;
+  const int tid = threadIdx.x, n = blockIdx.y, HW = H * W, base = n * HW;
   int running = chunk[n * gridDim.x + blockIdx.x];
   for (int j = 0; j < SLIC_CHUNK / NT; ++j) {
     const int q = blockIdx.x * SLIC_CHUNK + j * NT + tid, p = base + q;
     const bool is_large = q < HW && parent[p] == p && size[p] >= min_size;
-    const unsigned long long mask = __ballot(is_large);
-    if (lane == 0) wcount[wave] = __popcll(mask);
-    __syncthreads();
-    int before = __popcll(mask & ((1ull << lane) - 1)), total = 0;
-    for (int i = 0; i < NT / 64; ++i) {
-      if (i < wave) before += wcount[i];
-      total += wcount[i];
-    }
+    int total;
+    const int before = cc_block_rank<NT>(is_large, wcount, total);
     if (is_large) adj[p] = running + before + 1;
     running += total;
     __syncthreads();
@@ -411,33 +359,29 @@ __global__ __launch_bounds__(NT) void slic_emit_kernel(const int* __restrict__ p
 
 SlicConnWs slic_conn_carve(int N, int H, int W, void* base) {
   SlicConnWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  camo_abi::Carver c(base);
   const size_t npix = (size_t)N * H * W, chunks = ((size_t)H * W + SLIC_CHUNK - 1) / SLIC_CHUNK;
-  w.parent = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.size = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.adj = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.queue = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.mark = reinterpret_cast<unsigned char*>(take(npix));
-  w.chunk = reinterpret_cast<int*>(take((size_t)N * chunks * sizeof(int)));
-  w.misc = reinterpret_cast<int*>(take(((size_t)N + 1) * sizeof(int)));
-  w.bytes = off;
+  w.parent = c.take<int>(npix);
+  w.size = c.take<int>(npix);
+  w.adj = c.take<int>(npix);
+  w.queue = c.take<int>(npix);
+  w.mark = c.take<unsigned char>(npix);
+  w.chunk = c.take<int>((size_t)N * chunks);
+  w.misc = c.take<int>((size_t)N + 1);
+  w.bytes = c.bytes();
   return w;
 }
 
 SlicWs slic_carve(int N, int H, int W, int K, void* base) {
   SlicWs w{};
   w.conn = slic_conn_carve(N, H, W, base);
-  char* p = static_cast<char*>(base);
-  size_t off = w.conn.bytes;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+  camo_abi::Carver c(base, w.conn.bytes);
   const size_t npix = (size_t)N * H * W;
-  w.lab = reinterpret_cast<float*>(take(3 * npix * sizeof(float)));
-  w.nearest = reinterpret_cast<int*>(take(npix * sizeof(int)));
-  w.cent = reinterpret_cast<float*>(take((size_t)N * K * 5 * sizeof(float)));
-  w.sums = reinterpret_cast<long long*>(take((size_t)N * K * 6 * sizeof(long long)));
-  w.bytes = off;
+  w.lab = c.take<float>(3 * npix);
+  w.nearest = c.take<int>(npix);
+  w.cent = c.take<float>((size_t)N * K * 5);
+  w.sums = c.take<long long>((size_t)N * K * 6);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -216,6 +216,37 @@ def test_hysteresis_on_random_class_maps(shape, seed):
     assert a.tobytes() == b.tobytes()
 
 
+def _solid_class_maps():
+    """Class maps of solid weak regions -- what the run parents and the left-out unions of csrc/cc_inl.h are for; the maps
+    above are sparse."""
+    from test_instances import _ring
+    full = np.ones((1, 70, 33), np.uint8)
+    one_strong = full.copy()
+    one_strong[0, -1, -1] = 2                                                 # the last index: the root is the first
+    squares = np.zeros((1, 64, 64), np.uint8)                                 # they touch diagonally only, at a tile corner
+    squares[0, 12:32, 12:32] = 1
+    squares[0, 32:52, 32:52] = 1
+    squares[0, 40, 45] = 2
+    u = np.random.RandomState(5).uniform(0, 1, (2, 70, 33))
+    dense = (u < 0.9).astype(np.uint8) + (u < 0.001)
+    m = np.zeros((45, 70), bool)                                              # a wall without its corner: its ends meet diagonally
+    _ring(m, 10, 10, 40, 50)
+    m[10, 10] = False
+    ring = m.astype(np.uint8)[None]
+    ring[0, 10, 11] = 2
+    return {"all weak, one strong": one_strong, "all weak": full, "corner squares": squares, "dense": dense, "ring with a gap": ring}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["all weak, one strong", "all weak", "corner squares", "dense", "ring with a gap"])
+def test_hysteresis_on_solid_class_maps(name):
+    cls = _solid_class_maps()[name]
+    want = np.stack([R.hysteresis(c) for c in cls])
+    a, b = _hysteresis_device(cls), _hysteresis_device(cls)
+    assert ((a > 0) == want).all(), int(((a > 0) != want).sum())
+    assert a.tobytes() == b.tobytes()
+
+
 @pytest.mark.gpu
 def test_batch_equals_singles():
     import torch

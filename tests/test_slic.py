@@ -364,6 +364,29 @@ def test_connect_on_salted_voronoi_maps(shape, seed):
     assert (big == got).all()
 
 
+def _solid_label_maps():
+    """Label maps of large equal-label regions -- what the run parents and the left-out unions of csrc/cc_inl.h are for; the maps
+    above are thin paths and Voronoi cells."""
+    squares = np.zeros((1, 64, 64), np.int32)                                 # label 1 touches itself diagonally only, at a tile corner:
+    squares[0, 12:32, 12:32] = 1                                              # two components at 4-connectivity
+    squares[0, 32:52, 32:52] = 1
+    xx = np.broadcast_to(np.arange(70), (1, 70, 70))
+    maps = {"corner squares": squares, "one label": np.full((1, 33, 33), 7, np.int32),
+            "random": np.random.RandomState(11).randint(0, 3, (2, 70, 33)).astype(np.int32)}
+    for w in (1, 2, 33):
+        maps[f"stripes of {w}"] = (xx // w % 2).astype(np.int32)
+    return maps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("min_size", [0, 5])
+@pytest.mark.parametrize("name", ["corner squares", "stripes of 1", "stripes of 2", "stripes of 33", "one label", "random"])
+def test_connect_on_solid_label_maps(name, min_size):
+    got = _check_connect(_solid_label_maps()[name], min_size, 10 ** 6)
+    if name == "corner squares":
+        assert got[0, 12, 12] != got[0, 32, 32] and got.max() == 3
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)
 def test_whole_call_equals_its_stages_and_a_batch_its_images(name):
