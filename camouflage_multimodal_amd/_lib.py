@@ -23,6 +23,7 @@ NPARAMS_CROSS, NPARAMS_LATE = 44, 22
 
 RGB_TILE_SLOTS = 64                 # CAMO_RGB_TILE_SLOTS
 RGB_VAR_BOUND = 3.0 * 2.0 ** -37    # CAMO_RGB_VAR_BOUND
+RG_VAR_BOUND_PER_PIXEL = 9.0 * 2.0 ** -53      # CAMO_RG_VAR_BOUND_PER_PIXEL: times a region's pixels, camo_rg_region_graph's variances
 RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
 RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
 RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS

@@ -12,6 +12,20 @@
  *
  * Regions are renumbered in increasing label order, empty labels dropped (the reference's region_id_map); edges come
  * sorted by (i, j), i < j, each followed by its reverse (the reference's order is networkx's: a permutation).
+ *
+ * Arithmetic of the variance and std features (3, 4, 5, 7, 14).  A region of n pixels has the sums S1 = sum v and S2 = sum v^2 of
+ * its values v in [0, 1], added in double by atomics in the order the pixels arrive, and the feature is S2/n - (S1/n)^2, negative
+ * results set to 0.  With u = 2^-53 and terms that are all >= 0, n additions in ANY order leave S1 off by at most (n-1) u S1, and
+ * S2 -- whose terms carry one rounding of their own -- by at most n u S2.  1/n and the product with it round once each: q = S2/n
+ * is off by at most (n+2) u q, the mean m by (n+1) u m and its rounded square by (2n+3) u m^2; the subtraction adds u |var|.
+ * With q <= 1 and m^2 <= q,
+ *   |var - exact var|  <=  ((n+2) + (2n+3) + 1) u  =  3 (n+2) u  <=  CAMO_RG_VAR_BOUND_PER_PIXEL * n,  9 * 2^-53 per pixel
+ * (9 at n = 1; the factor tends to 3), whether or not the compiler contracts the subtraction into an fma (one rounding less).
+ * The sign of the error is an accident of the order.  Since |sqrt(a) - sqrt(b)| <= sqrt|a - b|, a std feature is off by at most
+ * sqrt(CAMO_RG_VAR_BOUND_PER_PIXEL * n) -- all of it where the exact variance is 0: 3.2e-8 for one pixel, 8.1e-6 for a flat
+ * region of 256 x 256 pixels -- and by about (bound) / (2 std) where it is not.  Both are before the one rounding to fp32.
+ * camo_rg_region_graph_batch (include/camo_rg_batch.h) sums integers instead and gives a flat region exactly 0.
+ *
  * Device pointers only, enqueue-only on `stream`, 0 = ok / negative CAMO_E_* as in camo_fusion.h. */
 #ifndef CAMO_RG_FEATURES_H
 #define CAMO_RG_FEATURES_H
@@ -23,6 +37,7 @@ extern "C" {
 
 #define CAMO_RG_NFEAT 15
 #define CAMO_RG_MAX_LABELS 4096
+#define CAMO_RG_VAR_BOUND_PER_PIXEL 9.99200722162640886e-16    /* 9 * 2^-53 */
 
 size_t camo_rg_graph_workspace_bytes(int32_t n_labels);
 

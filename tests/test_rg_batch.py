@@ -21,6 +21,12 @@ import torch
 import slic_ref as R
 from conftest import ROOT
 from oracle import rg_features_oracle as RO
+from rg_maps import FLAT_A, FLAT_B, check_against_oracle as _check_against_oracle, flat
+
+
+def _flat():
+    """rg_maps.flat(0): a saturated two-colour image whose regions are flat (every region of a 12-region map has one of two colours)."""
+    return flat(0)
 
 
 def _inputs(H, W, n, seed):
@@ -52,46 +58,10 @@ def _oracle(key):
     return [RO.region_graph(img[k], seg[k], canny[k]) for k in range(len(img))]
 
 
-FLAT_A, FLAT_B = np.array([1.0, 0.0, 0.3], np.float32), np.array([0.0, 1.0, 0.7], np.float32)
-
-
-def _flat():
-    """A saturated two-colour image whose regions are flat: every region of a 12-region map has one of two colours."""
-    seg = RO.voronoi_segments(64, 48, 12, 8)
-    img = np.where((seg % 2 == 0)[..., None], FLAT_A, FLAT_B).astype(np.float32)
-    canny = np.zeros((64, 48), bool)
-    return img, seg, canny
-
-
 def _build(img, seg, canny, **kw):
     from camouflage_multimodal_amd import create_region_graphs_from_segments
     return create_region_graphs_from_segments(torch.from_numpy(np.ascontiguousarray(img)).cuda(), torch.from_numpy(np.ascontiguousarray(seg)).cuda(),
                                               None if canny is None else torch.from_numpy(np.ascontiguousarray(canny)).cuda(), **kw)
-
-
-def _check_against_oracle(g, rm, want, what=""):
-    """Every image's slice of the batch against (x, edge_index, edge_attr, region_map) of the oracle: test 1's bounds."""
-    no, eo = g.node_offsets, g.edge_offsets
-    assert g.num_graphs == len(want) and len(no) == len(eo) == len(want) + 1 and no[0] == 0 and eo[0] == 0
-    assert g.x.shape == (no[-1], 15) and g.edge_index.shape == (2, eo[-1]) and g.edge_attr.shape == (eo[-1], 1) and g.batch.shape == (no[-1],)
-    gx, gei, gea, rm = g.x.cpu().numpy(), g.edge_index.cpu().numpy(), g.edge_attr.cpu().numpy()[:, 0], rm.cpu().numpy()
-    worst_x, worst_w = 0.0, 0.0
-    for k, (x, ei, ea, rmap) in enumerate(want):
-        assert (rm[k, :len(rmap)] == rmap).all() and (rm[k, len(rmap):] == -1).all(), (what, k)
-        assert no[k + 1] - no[k] == x.shape[0] and eo[k + 1] - eo[k] == ei.shape[1], (what, k, no, eo)
-        assert (gei[:, eo[k]:eo[k + 1]] - no[k] == ei).all(), (what, k)                      # same order: sorted (i, j), each followed by its reverse
-        xs = gx[no[k]:no[k + 1]]
-        scale = np.maximum(np.abs(x).max(0), 1e-3)
-        bound = 2e-6 * scale + 2e-6 * np.abs(x)
-        worst_x = max(worst_x, float((np.abs(xs - x) / bound).max()))
-        assert (np.abs(xs - x) <= bound).all(), (what, k, np.abs(xs - x).max(0) / scale)
-        ws = gea[eo[k]:eo[k + 1]]
-        if len(ea):
-            worst_w = max(worst_w, float((np.abs(ws - ea) / (2e-5 * ea + 1e-9)).max()))
-        assert (np.abs(ws - ea) <= 2e-5 * ea + 1e-9).all(), (what, k)
-    counts = np.diff(no)
-    assert (g.batch.cpu().numpy() == np.repeat(np.arange(len(want)), counts)).all()
-    print(f"{what}: worst |x - oracle| / bound {worst_x:.3f}, worst |w - oracle| / bound {worst_w:.3f}")
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,9 @@
 
 PARITY UNPINNED (skimage absent, no fixture shipped by the reference): the checker is oracle/rg_features_oracle.py, which
 restates extract_rg_embeddings.py:146-236 with the reference's own scipy.ndimage calls.  CPU tests hold the oracle to
-first-principles definitions on small inputs; GPU tests hold the HIP kernels to the oracle."""
+first-principles definitions on small inputs -- a Voronoi map, and every label of rg_maps.py's rings, stripes, checkerboard and thin
+images -- and GPU tests hold the HIP kernels to the oracle on Voronoi maps.  The same kernels on the other shapes (labels past
+1024, one-pixel regions, enclosure, flat colours, 300 images in a batch) are test_rg_graph_shapes.py's."""
 import numpy as np
 import pytest
 import torch
@@ -45,6 +47,52 @@ def test_oracle_features_follow_their_definitions():
         assert abs(f[13] - canny[m].mean()) < 1e-6
         ys, xs = np.nonzero(m)
         assert abs(f[8] - xs.mean() / 256) < 1e-7 and abs(f[9] - ys.mean() / 256) < 1e-7
+
+
+SMALL_MAPS = ("rings", "stripes", "stripes_t", "checker", "thin_1x1", "thin_1x70", "thin_70x1", "thin_2x2", "thin_3x35")
+
+
+@pytest.mark.parametrize("name", SMALL_MAPS)
+def test_oracle_follows_its_definitions_off_the_voronoi_maps(name):
+    """The perimeter and ring loop of the test above for EVERY label of rg_maps.py's small maps (enclosure, one-pixel stripes, a
+    checkerboard, images narrower than the ring), and adjacent_label_pairs against a 3 x 3 scan: the oracle is about to judge the
+    kernels on these shapes."""
+    import rg_maps as M
+    img, seg, canny = M.case(name)
+    img = img.astype(np.float64)
+    x, rmap = RO.region_features(img, seg, canny)
+    H, W = seg.shape
+    labels = np.unique(seg)
+    assert ((rmap >= 0) == np.isin(np.arange(len(rmap)), labels)).all() and (rmap[labels] == np.arange(len(labels))).all() and x.shape == (len(labels), 15)
+    near4 = ((-1, 0), (1, 0), (0, -1), (0, 1))
+    near12 = [(dy, dx) for dy in range(-2, 3) for dx in range(-2, 3) if 0 < abs(dy) + abs(dx) <= 2]
+    for lab in labels:
+        m = seg == lab
+        f = x[rmap[lab]]
+        per, ring = 0, np.zeros_like(m)
+        for y in range(H):
+            for xq in range(W):
+                if m[y, xq]:
+                    continue
+                per += any(0 <= y + dy < H and 0 <= xq + dx < W and m[y + dy, xq + dx] for dy, dx in near4)
+                ring[y, xq] = any(0 <= y + dy < H and 0 <= xq + dx < W and m[y + dy, xq + dx] for dy, dx in near12)
+        assert abs(f[11] - per ** 2 / (4 * np.pi * m.sum() + 1e-10)) <= 1e-4 * f[11], (name, lab)
+        want = np.linalg.norm(img[m].mean(0) - img[ring].mean(0)) if ring.any() else 0.0
+        assert abs(f[12] - want) < 1e-6 and (ring.any() or len(labels) == 1), (name, lab)
+        assert np.allclose(f[:3], img[m].mean(0), atol=1e-6) and np.allclose(f[3:6], img[m].std(0), atol=1e-6) and abs(f[10] - m.sum() / 65536) < 1e-9
+        assert abs(f[13] - canny[m].mean()) < 1e-6
+    pairs = set()
+    for y in range(H):
+        for xq in range(W):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    if 0 <= y + dy < H and 0 <= xq + dx < W and seg[y + dy, xq + dx] != seg[y, xq]:
+                        pairs.add((int(min(seg[y, xq], seg[y + dy, xq + dx])), int(max(seg[y, xq], seg[y + dy, xq + dx]))))
+    assert RO.adjacent_label_pairs(seg) == sorted(pairs), name
+    if name == "checker":
+        assert pairs == {(1, 2)} and x[0, 11] == np.float32((seg == 2).sum() ** 2 / (4 * np.pi * (seg == 1).sum() + 1e-10))    # every pixel of 2 is on 1's perimeter
+    if name.startswith("stripes"):
+        assert sorted(pairs) == [(a, b) for a in range(1, 6) for b in range(a + 1, 6) if b - a in (1, 4)]                      # neighbours in the cycle only
 
 
 def test_oracle_graph_structure():
