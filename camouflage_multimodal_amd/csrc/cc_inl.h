@@ -7,8 +7,7 @@
 //   cc_tile_root         label tiles, last: a tile entry's root as an index of the batch
 //   cc_join_borders      join tiles: the same unions across the tile borders, on the global parents
 //   cc_flatten           flatten: one pixel finds its root and points at it
-//   cc_chunk_prefix      scan: a block's exclusive prefix over an image's chunk counts
-//   cc_block_rank        rank: the kept roots before a thread in one pass of its block
+// (the scan and rank launches that follow use block_chunk_prefix and block_rank of label_inl.h)
 //
 // CONN is 4 or 8, T the tile side.  Two member pixels a, b that touch are LINKED when same(a, b): always for Canny and the instances
 // (cc_all), on equal labels for SLIC: `same` is an equivalence.  A union with the pixel above or to the left is left out only where
@@ -118,46 +117,4 @@ __device__ __forceinline__ int cc_flatten(int* par, long long p) {
   const int r = uf_find<__HIP_MEMORY_SCOPE_AGENT>(par, (int)p);
   if (r != (int)p) __hip_atomic_store(par + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return r;
-}
-
-// c[0 .. chunks) becomes its exclusive prefix (Hillis-Steele, NT entries at a time with a carry); every thread of a block of NT
-// calls, s is NT ints of LDS.  each(i) runs once for every chunk i, in the thread that loads c[i]: what else the caller sums over
-// the chunks rides on the same pass.  -> the total
-template <int NT, class Each>
-__device__ __forceinline__ int cc_chunk_prefix(int* __restrict__ c, int chunks, int* s, Each each) {
-  const int tid = threadIdx.x;
-  int carry = 0;
-  for (int c0 = 0; c0 < chunks; c0 += NT) {
-    const int v = c0 + tid < chunks ? c[c0 + tid] : 0;
-    if (c0 + tid < chunks) each(c0 + tid);
-    s[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < NT; d <<= 1) {
-      const int t = tid >= d ? s[tid - d] : 0;
-      __syncthreads();
-      s[tid] += t;
-      __syncthreads();
-    }
-    if (c0 + tid < chunks) c[c0 + tid] = carry + s[tid] - v;
-    carry += s[NT - 1];
-    __syncthreads();
-  }
-  return carry;
-}
-
-// One pass of a block of NT threads, every thread calls: -> how many threads before this one have `kept` set; total: how many have
-// it in all.  wcount is NT / 64 ints of LDS, free again after the caller's next barrier.
-template <int NT>
-__device__ __forceinline__ int cc_block_rank(bool kept, int* wcount, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long mask = __ballot(kept);
-  if (lane == 0) wcount[wave] = __popcll(mask);
-  __syncthreads();
-  int before = __popcll(mask & ((1ull << lane) - 1));
-  total = 0;
-  for (int i = 0; i < NT / 64; ++i) {
-    if (i < wave) before += wcount[i];
-    total += wcount[i];
-  }
-  return before;
 }

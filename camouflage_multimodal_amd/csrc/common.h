@@ -93,6 +93,13 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// inclusive prefix sum over the lanes: lane i gets v of lanes 0 .. i
+__device__ __forceinline__ int wave_scan_int(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+  return v;
+}
 __device__ __forceinline__ int wave_min_int(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -130,6 +137,13 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
   const f32x2_t v = {lo, hi};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+}
+// a prediction in [0, 1] -> 0 .. 255 (include/camo_seg_measures.h's quantisation): clamp (a NaN to 0), one fp32 multiply, round to
+// nearest even
+__device__ __forceinline__ int quantise_u8(float v) {
+  v = v == v ? v : 0.f;
+  v = fminf(fmaxf(v, 0.f), 1.f);
+  return (int)rintf(v * 255.0f);
 }
 
 // Launch of a kernel that asks for more dynamic LDS than a kernel gets without opting in: the opt-in attribute is set once per

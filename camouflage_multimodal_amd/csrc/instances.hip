@@ -23,6 +23,7 @@
 #include "cc_inl.h"
 #include "common.h"
 #include "instances.h"
+#include "label_inl.h"
 
 namespace {
 
@@ -31,13 +32,6 @@ constexpr int MODE_BG = 0, MODE_FG = 1, MODE_FILLED = 2;
 constexpr int NONE = 0x7fffffff;
 constexpr unsigned long long BOX_MIN_INIT = 0x7fffffffffffffffull;
 static_assert(T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "whole waves, whole passes");
-
-// include/camo_seg_measures.h's quantisation: clamp (a NaN to 0), one fp32 multiply, round to nearest even
-__device__ __forceinline__ int quantise(float v) {
-  v = v == v ? v : 0.f;
-  v = fminf(fmaxf(v, 0.f), 1.f);
-  return (int)rintf(v * 255.0f);
-}
 
 // Runs of consecutive lanes with the same key (`head`: the lane starts a run): the lane one past the end of the calling lane's run.
 // Every lane of the wave calls.
@@ -200,7 +194,7 @@ __global__ __launch_bounds__(NT) void inst_scan_kernel(int* __restrict__ chunk, 
   const int* cp = chunk + ((size_t)2 * N + n) * chunks;
   if (tid < 2) tot[tid] = 0;
   int ns = 0, np = 0;
-  const int kept = cc_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [&](int i) { ns += cs[i]; np += cp[i]; });
+  const int kept = block_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [&](int i) { ns += cs[i]; np += cp[i]; });
   ns = wave_sum_int(ns); np = wave_sum_int(np);
   if (lane == 0) { atomicAdd(&tot[0], ns); atomicAdd(&tot[1], np); }
   __syncthreads();
@@ -230,7 +224,7 @@ __global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ p
     const bool root = q < HW && par[p] == (int)p;
     const bool kept = root && area[p] >= min_area;
     int total;
-    const int before = cc_block_rank<NT>(kept, wcount, total);
+    const int before = block_rank<NT>(kept, wcount, total);
     if (root) rid[p] = kept ? running + before + 1 : 0;
     running += total;
     __syncthreads();
@@ -270,16 +264,11 @@ __global__ __launch_bounds__(NT) void inst_emit_kernel(const float* __restrict__
     }
     if (__ballot(k > 0) == 0ull) continue;                        // (wave-uniform)
     const int y = q / W, x = q - y * W;                            // (k > 0 only where q < HW)
-    const int qv = k > 0 ? quantise(pv) : 0;
+    const int qv = k > 0 ? quantise_u8(pv) : 0;
     const int prev = __shfl_up(k, 1, 64);
     const bool head = lane == 0 || prev != k || x == 0;
     const int end = run_end(head, lane), len = end - lane;
-    int pre = qv;                                                  // inclusive prefix of q over the wave (at most 64 * 255)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(pre, o, 64);
-      if (lane >= o) pre += t;
-    }
+    const int pre = wave_scan_int(qv);                             // inclusive prefix of q over the wave (at most 64 * 255)
     const int sq = __shfl(pre, end - 1, 64) - (pre - qv);
     if (head && k > 0) {                                           // (no branch around the shuffles above: every lane takes them)
       const unsigned long long sx = (unsigned long long)len * x + (unsigned long long)len * (len - 1) / 2, sy = (unsigned long long)len * y;

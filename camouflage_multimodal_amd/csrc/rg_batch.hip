@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "abi_util.h"
+#include "label_inl.h"
 #include "rg_batch.h"
 
 namespace {
@@ -37,10 +38,8 @@ static_assert(A_NCNT + 1 == RGB_NACC, "accumulator layout");
 
 constexpr int T = 32, NT = 256, PPT = T * T / NT, HALO = 2, LW = T + 2 * HALO;
 constexpr int SLOTS = RGB_SLOTS;
-static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS == 64, "the hash keeps log2(SLOTS) = 6 bits");
 constexpr double FIX = 68719476736.0, UNIT = 1.0 / 68719476736.0;      // 2^36, 2^-36
 static_assert(RGB_FIX_BITS == 36, "FIX is 2^RGB_FIX_BITS");
-constexpr int NFEAT = 15;
 
 typedef unsigned long long u64;
 
@@ -49,18 +48,6 @@ __global__ __launch_bounds__(NT) void rgb_clear_kernel(u64* acc, size_t nacc, un
   for (size_t k = i; k < nacc; k += stride) acc[k] = 0;
   for (size_t k = i; k < nwords; k += stride) adj[k] = 0u;
   if (i < 2) status[i] = 0;
-}
-
-// the slot of label k in the tile's table, or -1 when the table is full and k is not in it.  The table only fills, so a label
-// that once got a slot is found there by every later lookup, and one that met a full table never gets one.
-__device__ __forceinline__ int rgb_slot(int* keys, int k) {
-  const unsigned h = ((unsigned)k * 0x9E3779B1u) >> 26;
-  for (int t = 0; t < SLOTS; ++t) {
-    const int s = (h + t) & (SLOTS - 1);
-    const int prev = atomicCAS(&keys[s], -1, k);
-    if (prev == -1 || prev == k) return s;
-  }
-  return -1;
 }
 
 __global__ __launch_bounds__(NT) void rgb_accumulate_kernel(const float* __restrict__ images, const int* __restrict__ seg,
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(NT) void rgb_accumulate_kernel(const float* __restr
       const long long val[NOWN] = {1, vr, vg, vb, vl, (long long)(sr >> RGB_FIX_BITS), (long long)(sg >> RGB_FIX_BITS), (long long)(sb >> RGB_FIX_BITS),
                                    (long long)(sl >> RGB_FIX_BITS), (long long)((u64)sr & LO), (long long)((u64)sg & LO), (long long)((u64)sb & LO),
                                    (long long)((u64)sl & LO), y, x, canny[p] ? 1 : 0};
-      const int s = rgb_slot(keys, r);
+      const int s = label_slot<SLOTS>(keys, r);
       if (s >= 0) {
 #pragma unroll
         for (int q = 0; q < NOWN; ++q) if (val[q]) atomicAdd(&tab[s][q], (u64)val[q]);
@@ -122,34 +109,26 @@ __global__ __launch_bounds__(NT) void rgb_accumulate_kernel(const float* __restr
         for (int q = 0; q < NOWN; ++q) if (val[q]) atomicAdd(a + q, (u64)val[q]);
       }
     }
-    // neighbour labels: offsets within L1 distance 2 first in rings (4-neighbours, then the other 8), diagonals flagged for the RAG
-    const int dy[12] = {-1, 1, 0, 0, -2, 2, 0, 0, -1, -1, 1, 1};
-    const int dx[12] = {0, 0, -1, 1, 0, 0, -2, 2, -1, 1, -1, 1};
-    int seen[12]; int nseen = 0;
+    rg_visit_neighbours(
+        r, [&](int ddy, int ddx) { return c[ddy * LW + ddx]; },    // (-1 outside the image: the halo holds it)
+        [&](int l) {
+          if (l < r) return;                                        // The neighbour sees this pixel in ITS 8-neighbourhood, so the
+          unsigned int* w = adjn + (size_t)r * words + (l >> 5);    // pixel with the smaller label sets the bit of (min, max)
+          const unsigned int bit = 1u << (l & 31);
+          if (!(*w & bit)) atomicOr(w, bit);                        // (a stale 0 only repeats the atomic; the bits were cleared by an earlier launch)
+        },
+        [&](int l, bool four) {
+          const long long val[5] = {four ? 1 : 0, vr, vg, vb, 1};
+          const int s = label_slot<SLOTS>(keys, l);
+          if (s >= 0) {
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      const int l = c[dy[k] * LW + dx[k]];                       // (-1 outside the image: the halo holds it)
-      if (l == r || l < 0) continue;
-      if ((k < 4 || k >= 8) && l > r) {                           // 8-neighbourhood: the label pair is a RAG edge.  The neighbour
-        unsigned int* w = adjn + (size_t)r * words + (l >> 5);    // sees this pixel in ITS 8-neighbourhood, so the pixel with
-        const unsigned int bit = 1u << (l & 31);                  // the smaller label sets the bit of (min, max)
-        if (!(*w & bit)) atomicOr(w, bit);                        // (a stale 0 only repeats the atomic; the bits were cleared by an earlier launch)
-      }
-      bool dup = false;
-      for (int s = 0; s < nseen; ++s) dup |= (seen[s] == l);
-      if (dup) continue;
-      seen[nseen++] = l;
-      const long long val[5] = {k < 4 ? 1 : 0, vr, vg, vb, 1};    // (the first four offsets are the 4-neighbours: a label first seen there is on l's dilation)
-      const int s = rgb_slot(keys, l);
-      if (s >= 0) {
+            for (int q = 0; q < 5; ++q) if (val[q]) atomicAdd(&tab[s][A_PERIM + q], (u64)val[q]);
+          } else {
+            u64* b = accn + (size_t)l * RGB_NACC + A_PERIM;
 #pragma unroll
-        for (int q = 0; q < 5; ++q) if (val[q]) atomicAdd(&tab[s][A_PERIM + q], (u64)val[q]);
-      } else {
-        u64* b = accn + (size_t)l * RGB_NACC + A_PERIM;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) if (val[q]) atomicAdd(b + q, (u64)val[q]);
-      }
-    }
+            for (int q = 0; q < 5; ++q) if (val[q]) atomicAdd(b + q, (u64)val[q]);
+          }
+        });
   }
   __syncthreads();
   for (int i = tid; i < SLOTS * RGB_NACC; i += NT) {
@@ -164,26 +143,12 @@ __global__ __launch_bounds__(NT) void rgb_accumulate_kernel(const float* __restr
 __global__ __launch_bounds__(1024) void rgb_rank_kernel(const u64* __restrict__ acc, int label_bound, int* __restrict__ region_map,
                                                         int* __restrict__ kept) {
   __shared__ int wsum[16];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.x;
+  const int n = blockIdx.x;
   const u64* accn = acc + (size_t)n * label_bound * RGB_NACC;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int r0 = 0; r0 < label_bound; r0 += 1024) {
-    const int r = r0 + tid;
-    const bool keep = r < label_bound && accn[(size_t)r * RGB_NACC + A_CNT] > 0;
-    const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int off = base;
-    for (int k = 0; k < wave; ++k) off += wsum[k];
-    if (r < label_bound) region_map[(size_t)n * label_bound + r] = keep ? off + before : -1;
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wsum[k]; base += s; }
-    __syncthreads();
-  }
-  if (tid == 0) kept[n] = base;
+  int* rmap = region_map + (size_t)n * label_bound;
+  const int total = label_compact<1024>(
+      label_bound, wsum, [&](int r) { return accn[(size_t)r * RGB_NACC + A_CNT] > 0; }, [&](int r, int rank) { rmap[r] = rank; });
+  if (threadIdx.x == 0) kept[n] = total;
 }
 
 // sum of v[0 .. n) over the block's NT threads, the same value in every thread
@@ -191,8 +156,7 @@ __device__ __forceinline__ int rgb_block_prefix(const int* __restrict__ v, int n
   const int tid = threadIdx.x;
   int s = 0;
   for (int i = tid; i < n; i += NT) s += v[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum_int(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
@@ -236,15 +200,8 @@ __global__ __launch_bounds__(NT) void rgb_finalize_kernel(const u64* __restrict_
                  d2 = mb - (double)(long long)a[A_NB] * UNIT * q;
     contrast = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
   }
-  const double per = (double)a[A_PERIM];
-  float* o = x + (size_t)(first + rank) * NFEAT;
-  o[0] = (float)mr; o[1] = (float)mg; o[2] = (float)mb;
-  o[3] = (float)sqrt(vr); o[4] = (float)sqrt(vg); o[5] = (float)sqrt(vb);
-  o[6] = (float)ml; o[7] = (float)sqrt(vl);
-  o[8] = (float)((double)a[A_X] * inv / 256.0); o[9] = (float)((double)a[A_Y] * inv / 256.0);
-  o[10] = (float)(cnt / 65536.0);
-  o[11] = (float)(per * per / (4.0 * 3.14159265358979323846 * cnt + 1e-10));
-  o[12] = (float)contrast; o[13] = (float)((double)a[A_E] * inv); o[14] = (float)vl;
+  rg_store_features(x + (size_t)(first + rank) * RGF_NFEAT, {mr, mg, mb, ml, vr, vg, vb, vl, (double)a[A_X] * inv, (double)a[A_Y] * inv, cnt,
+                                                             (double)a[A_PERIM], contrast, (double)a[A_E] * inv});
   batch[first + rank] = n;
 }
 
@@ -256,8 +213,7 @@ __global__ __launch_bounds__(NT) void rgb_count_kernel(const unsigned int* __res
   const unsigned int* row = adj + ((size_t)n * label_bound + a) * words;
   int c = 0;
   for (int w = lane; w < words; w += 64) c += __popc(row[w]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum_int(c);
   if (lane == 0) rowcount[(size_t)n * label_bound + a] = c;
 }
 
@@ -265,26 +221,9 @@ __global__ __launch_bounds__(NT) void rgb_count_kernel(const unsigned int* __res
 __global__ __launch_bounds__(1024) void rgb_scan_kernel(const int* __restrict__ rowcount, int label_bound, int* __restrict__ rowoff,
                                                         int* __restrict__ pairs) {
   __shared__ int wsum[16];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.x;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int r0 = 0; r0 < label_bound; r0 += 1024) {
-    const int r = r0 + tid;
-    const int v = r < label_bound ? rowcount[(size_t)n * label_bound + r] : 0;
-    int inc = v;                                                // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int off = base;
-    for (int k = 0; k < wave; ++k) off += wsum[k];
-    if (r < label_bound) rowoff[(size_t)n * label_bound + r] = off + inc - v;
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wsum[k]; base += s; }
-    __syncthreads();
-  }
-  if (tid == 0) pairs[n] = base;
+  const size_t row = (size_t)blockIdx.x * label_bound;
+  const int total = label_scan<1024>(rowcount + row, label_bound, rowoff + row, wsum);
+  if (threadIdx.x == 0) pairs[blockIdx.x] = total;
 }
 
 // one wave per (image, label a): its neighbours b > a in increasing order
@@ -296,37 +235,19 @@ __global__ __launch_bounds__(64) void rgb_emit_kernel(const unsigned int* __rest
   const int a = blockIdx.x, n = blockIdx.y, lane = threadIdx.x;
   int before = 0;                                               // undirected edges of the images in front of this one
   for (int i = lane; i < n; i += 64) before += pairs[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+  before = wave_sum_int(before);
   if (a == 0 && lane == 0) {
     edge_off[n] = 2 * before;
     if (n == N - 1) { edge_off[N] = 2 * (before + pairs[n]); status[1] = 2 * (before + pairs[n]); }
   }
   const int* rmap = region_map + (size_t)n * label_bound;
   if (rmap[a] < 0) return;
-  const int first = node_off[n], i = first + rmap[a];
-  int pos = before + rowoff[(size_t)n * label_bound + a];
+  const int first = node_off[n];
   const unsigned int* row = adj + ((size_t)n * label_bound + a) * words;
-  const float* xi = x + (size_t)i * NFEAT;
-  for (int b0 = a + 1; b0 < label_bound; b0 += 64) {
-    const int b = b0 + lane;
-    const bool on = b < label_bound && ((row[b >> 5] >> (b & 31)) & 1u) && rmap[b] >= 0;
-    const unsigned long long bal = __ballot(on);
-    if (on) {
-      const int j = first + rmap[b];
-      const long long e = 2ll * (pos + __popcll(bal & ((1ull << lane) - 1ull)));
-      const float* xj = x + (size_t)j * NFEAT;
-      const float d0 = xi[0] - xj[0], d1 = xi[1] - xj[1], d2 = xi[2] - xj[2];
-      const float color = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-      const float wgt = expf(-color / 0.15f) * expf(-fabsf(xi[6] - xj[6]) / 0.08f) * expf(-fabsf(xi[12] - xj[12]) / 0.1f);
-      if (e + 1 < edge_capacity) {
-        edge_index[e] = i; edge_index[e + 1] = j;
-        edge_index[(size_t)edge_capacity + e] = j; edge_index[(size_t)edge_capacity + e + 1] = i;
-        edge_attr[e] = wgt; edge_attr[e + 1] = wgt;
-      }
-    }
-    pos += __popcll(bal);
-  }
+  rg_emit_row(
+      a, label_bound, before + rowoff[(size_t)n * label_bound + a], first + rmap[a], x,
+      [&](int b) { return ((row[b >> 5] >> (b & 31)) & 1u) && rmap[b] >= 0; }, [&](int b) { return first + rmap[b]; }, edge_index, edge_attr,
+      edge_capacity);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 //   emit       scan of the counts (one block), then per label a its pairs (i, j), (j, i) with the weight [:226-234]
 #include <hip/hip_runtime.h>
 #include "abi_util.h"
+#include "label_inl.h"
 #include "rg_features.h"
 
 namespace {
@@ -44,75 +45,47 @@ __global__ __launch_bounds__(256) void rgf_accumulate_kernel(const float* __rest
   atomicAdd(a + A_L, luma); atomicAdd(a + A_LL, luma * luma);
   atomicAdd(a + A_Y, (double)y); atomicAdd(a + A_X, (double)x);
   if (canny[p]) atomicAdd(a + A_E, 1.0);
-  // neighbour labels: offsets within L1 distance 2 first in rings (4-neighbours, then the other 8), diagonals flagged for the RAG
-  const int dy[12] = {-1, 1, 0, 0, -2, 2, 0, 0, -1, -1, 1, 1};
-  const int dx[12] = {0, 0, -1, 1, 0, 0, -2, 2, -1, 1, -1, 1};
-  int seen[12]; int nseen = 0, nseen4 = 0;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const int yy = y + dy[k], xx = x + dx[k];
-    if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-    const int l = seg[yy * W + xx];
-    if (l == r || l < 0 || l >= n_labels) continue;
-    if (k < 4 || k >= 8) {                                      // 8-neighbourhood: the label pair is a RAG edge
-      const int lo = min(l, r), hi = max(l, r);
-      adj[(size_t)lo * n_labels + hi] = 1;                      // (every writer stores the same byte)
-    }
-    bool dup = false;
-    for (int s = 0; s < nseen; ++s) dup |= (seen[s] == l);
-    if (dup) continue;
-    seen[nseen++] = l;
-    double* b = acc + (size_t)l * RGF_NACC;
-    if (k < 4) { atomicAdd(b + A_PERIM, 1.0); ++nseen4; }       // (the first four offsets are the 4-neighbours: a label first seen there is on l's dilation)
-    atomicAdd(b + A_NR, cr); atomicAdd(b + A_NG, cg); atomicAdd(b + A_NB, cb); atomicAdd(b + A_NCNT, 1.0);
-  }
-  (void)nseen4;
+  rg_visit_neighbours(
+      r,
+      [&](int ddy, int ddx) {
+        const int yy = y + ddy, xx = x + ddx;
+        if (yy < 0 || yy >= H || xx < 0 || xx >= W) return -1;
+        const int l = seg[yy * W + xx];
+        return l < n_labels ? l : -1;
+      },
+      [&](int l) { adj[(size_t)min(l, r) * n_labels + max(l, r)] = 1; },      // (every writer stores the same byte)
+      [&](int l, bool four) {
+        double* b = acc + (size_t)l * RGF_NACC;
+        if (four) atomicAdd(b + A_PERIM, 1.0);
+        atomicAdd(b + A_NR, cr); atomicAdd(b + A_NG, cg); atomicAdd(b + A_NB, cb); atomicAdd(b + A_NCNT, 1.0);
+      });
 }
 
 // one block of 1024 threads; n_labels <= 4096
 __global__ __launch_bounds__(1024) void rgf_finalize_kernel(const double* __restrict__ acc, int n_labels, float* __restrict__ x,
                                                             int* __restrict__ region_map, int* __restrict__ counts) {
   __shared__ int wsum[16];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int r0 = 0; r0 < n_labels; r0 += 1024) {
-    const int r = r0 + tid;
-    const bool keep = r < n_labels && acc[(size_t)r * RGF_NACC + A_CNT] > 0.0;
-    const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int off = base;
-    for (int k = 0; k < wave; ++k) off += wsum[k];
-    if (r < n_labels) region_map[r] = keep ? off + before : -1;
-    if (keep) {
-      const double* a = acc + (size_t)r * RGF_NACC;
-      const double n = a[A_CNT], inv = 1.0 / n;
-      const double mr = a[A_R] * inv, mg = a[A_G] * inv, mb = a[A_B] * inv, ml = a[A_L] * inv;
-      const double vl = fmax(a[A_LL] * inv - ml * ml, 0.0);
-      double contrast = 0.0;
-      if (a[A_NCNT] > 0.0) {
-        const double q = 1.0 / a[A_NCNT];
-        const double d0 = mr - a[A_NR] * q, d1 = mg - a[A_NG] * q, d2 = mb - a[A_NB] * q;
-        contrast = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-      }
-      float* o = x + (size_t)(off + before) * RGF_NFEAT;
-      o[0] = (float)mr; o[1] = (float)mg; o[2] = (float)mb;
-      o[3] = (float)sqrt(fmax(a[A_RR] * inv - mr * mr, 0.0)); o[4] = (float)sqrt(fmax(a[A_GG] * inv - mg * mg, 0.0));
-      o[5] = (float)sqrt(fmax(a[A_BB] * inv - mb * mb, 0.0));
-      o[6] = (float)ml; o[7] = (float)sqrt(vl);
-      o[8] = (float)(a[A_X] * inv / 256.0); o[9] = (float)(a[A_Y] * inv / 256.0);
-      o[10] = (float)(n / 65536.0);
-      o[11] = (float)(a[A_PERIM] * a[A_PERIM] / (4.0 * 3.14159265358979323846 * n + 1e-10));
-      o[12] = (float)contrast; o[13] = (float)(a[A_E] * inv); o[14] = (float)vl;
-    }
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wsum[k]; base += s; }
-    __syncthreads();
-  }
-  if (tid == 0) counts[0] = base;
+  const int kept = label_compact<1024>(
+      n_labels, wsum, [&](int r) { return acc[(size_t)r * RGF_NACC + A_CNT] > 0.0; },
+      [&](int r, int rank) {
+        region_map[r] = rank;
+        if (rank < 0) return;
+        const double* a = acc + (size_t)r * RGF_NACC;
+        const double n = a[A_CNT], inv = 1.0 / n;
+        const double mr = a[A_R] * inv, mg = a[A_G] * inv, mb = a[A_B] * inv, ml = a[A_L] * inv;
+        double contrast = 0.0;
+        if (a[A_NCNT] > 0.0) {
+          const double q = 1.0 / a[A_NCNT];
+          const double d0 = mr - a[A_NR] * q, d1 = mg - a[A_NG] * q, d2 = mb - a[A_NB] * q;
+          contrast = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        }
+        // (how the compiler contracts these four differences is part of the result)
+        rg_store_features(x + (size_t)rank * RGF_NFEAT,
+                          {mr, mg, mb, ml, fmax(a[A_RR] * inv - mr * mr, 0.0), fmax(a[A_GG] * inv - mg * mg, 0.0),
+                           fmax(a[A_BB] * inv - mb * mb, 0.0), fmax(a[A_LL] * inv - ml * ml, 0.0), a[A_X] * inv, a[A_Y] * inv, n,
+                           a[A_PERIM], contrast, a[A_E] * inv});
+      });
+  if (threadIdx.x == 0) counts[0] = kept;
 }
 
 __global__ __launch_bounds__(256) void rgf_count_kernel(const unsigned char* __restrict__ adj, const int* __restrict__ region_map, int n_labels,
@@ -122,8 +95,7 @@ __global__ __launch_bounds__(256) void rgf_count_kernel(const unsigned char* __r
   int c = 0;
   if (region_map[a] >= 0)
     for (int b = a + 1 + tid; b < n_labels; b += 256) c += (adj[(size_t)a * n_labels + b] && region_map[b] >= 0) ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum_int(c);
   if ((tid & 63) == 0) red[tid >> 6] = c;
   __syncthreads();
   if (tid == 0) rowcount[a] = red[0] + red[1] + red[2] + red[3];
@@ -131,56 +103,20 @@ __global__ __launch_bounds__(256) void rgf_count_kernel(const unsigned char* __r
 
 __global__ __launch_bounds__(1024) void rgf_scan_kernel(const int* __restrict__ rowcount, int n_labels, int* __restrict__ rowoff, int* __restrict__ counts) {
   __shared__ int wsum[16];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int r0 = 0; r0 < n_labels; r0 += 1024) {
-    const int r = r0 + tid;
-    const int v = r < n_labels ? rowcount[r] : 0;
-    int inc = v;                                                // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int off = base;
-    for (int k = 0; k < wave; ++k) off += wsum[k];
-    if (r < n_labels) rowoff[r] = off + inc - v;
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wsum[k]; base += s; }
-    __syncthreads();
-  }
-  if (tid == 0) { rowoff[n_labels] = base; counts[1] = 2 * base; }
+  const int pairs = label_scan<1024>(rowcount, n_labels, rowoff, wsum);
+  if (threadIdx.x == 0) { rowoff[n_labels] = pairs; counts[1] = 2 * pairs; }
 }
 
 // one wave per label a: its kept neighbours b > a in increasing order
 __global__ __launch_bounds__(64) void rgf_emit_kernel(const unsigned char* __restrict__ adj, const int* __restrict__ region_map, const int* __restrict__ rowoff,
                                                       const float* __restrict__ x, int n_labels, long long* __restrict__ edge_index,
                                                       float* __restrict__ edge_attr, int edge_capacity) {
-  const int a = blockIdx.x, lane = threadIdx.x;
+  const int a = blockIdx.x;
   const int i = region_map[a];
   if (i < 0) return;
-  int pos = rowoff[a];
-  const float* xi = x + (size_t)i * RGF_NFEAT;
-  for (int b0 = a + 1; b0 < n_labels; b0 += 64) {
-    const int b = b0 + lane;
-    const bool on = b < n_labels && adj[(size_t)a * n_labels + b] && region_map[b] >= 0;
-    const unsigned long long bal = __ballot(on);
-    if (on) {
-      const int j = region_map[b];
-      const int e = 2 * (pos + __popcll(bal & ((1ull << lane) - 1ull)));
-      const float* xj = x + (size_t)j * RGF_NFEAT;
-      const float d0 = xi[0] - xj[0], d1 = xi[1] - xj[1], d2 = xi[2] - xj[2];
-      const float color = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-      const float wgt = expf(-color / 0.15f) * expf(-fabsf(xi[6] - xj[6]) / 0.08f) * expf(-fabsf(xi[12] - xj[12]) / 0.1f);
-      if (e + 1 < edge_capacity) {
-        edge_index[e] = i; edge_index[e + 1] = j;
-        edge_index[(size_t)edge_capacity + e] = j; edge_index[(size_t)edge_capacity + e + 1] = i;
-        edge_attr[e] = wgt; edge_attr[e + 1] = wgt;
-      }
-    }
-    pos += __popcll(bal);
-  }
+  rg_emit_row(
+      a, n_labels, rowoff[a], i, x, [&](int b) { return adj[(size_t)a * n_labels + b] && region_map[b] >= 0; },
+      [&](int b) { return region_map[b]; }, edge_index, edge_attr, edge_capacity);
 }
 
 }  // namespace

@@ -15,29 +15,18 @@
 // reads them in stream order.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include "label_inl.h"
 #include "rg_targets.h"
 
 namespace {
 
 constexpr int T = RGTG_TILE, NT = 256, PPT = T * T / NT, LW = T + 2, SLOTS = RGTG_SLOTS;
-static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS == 64, "the hash keeps log2(SLOTS) = 6 bits");
 static_assert(T * T < (1 << 16), "two counts of a tile share a 32-bit word");
 enum : unsigned char { NEG = 0, POS = 1, OUTSIDE = 2 };
 
 __global__ __launch_bounds__(NT) void rgtg_clear_kernel(int* __restrict__ counts, size_t total) {
   const size_t stride = (size_t)gridDim.x * NT;
   for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < total; k += stride) counts[k] = 0;
-}
-
-// the slot of node v in the tile's table, or -1 when the table is full and v is not in it (rgb_slot of rg_batch.hip)
-__device__ __forceinline__ int rgtg_slot(int* keys, int v) {
-  const unsigned h = ((unsigned)v * 0x9E3779B1u) >> 26;
-  for (int t = 0; t < SLOTS; ++t) {
-    const int s = (h + t) & (SLOTS - 1);
-    const int prev = atomicCAS(&keys[s], -1, v);
-    if (prev == -1 || prev == v) return s;
-  }
-  return -1;
 }
 
 __global__ __launch_bounds__(NT) void rgtg_accumulate_kernel(const int* __restrict__ seg, const int* __restrict__ rmap,
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(NT) void rgtg_accumulate_kernel(const int* __restri
     if (gt_edge) e = gt_edge[p] > 127;
     else e = m && (c[-LW] == NEG || c[LW] == NEG || c[-1] == NEG || c[1] == NEG);      // (OUTSIDE is no neighbour)
     const unsigned w0 = 1u | (m << 16), w1 = in | (e << 16);
-    const int slot = rgtg_slot(keys, v);
+    const int slot = label_slot<SLOTS>(keys, v);
     if (slot >= 0) {
       atomicAdd(&tab[slot][0], w0);
       if (w1) atomicAdd(&tab[slot][1], w1);

@@ -18,13 +18,6 @@ constexpr unsigned NO_KEY = 0xFFFFu;         // key of an element outside the im
 static_assert(HIST == CAMO_SEG_QUADRANTS * 2 * CAMO_SEG_BINS && CAMO_SEG_BINS == 256, "a key is quadrant * 512 + g * 256 + q");
 static_assert(SEGM_SPAN == 16, "a span is four float4 loads");
 
-// the header's quantisation: clamp (a NaN to 0), one fp32 multiply, round to nearest even
-__device__ __forceinline__ int quantise(float v) {
-  v = v == v ? v : 0.f;
-  v = fminf(fmaxf(v, 0.f), 1.f);
-  return (int)rintf(v * 255.0f);
-}
-
 // rint(a / b) of the exact rational, a half to the even neighbour (a >= 0, b >= 1)
 __device__ __forceinline__ long long rint_div(unsigned long long a, unsigned long long b) {
   const unsigned long long q = a / b, r = a - q * b;
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(NT) void segm_fill_kernel(const float* __restrict__
         for (int e = 0; e < 4; ++e) {
           const bool in = whole || (q0 + e >= 0 && q0 + e < HW);
           const unsigned quad = ((unsigned)(y >= Y) << 1) | (unsigned)(x >= X);
-          const unsigned key = quad * 512u + (((gb >> (8 * e)) & 255u) > 127u ? 256u : 0u) + (unsigned)quantise(v[e]);
+          const unsigned key = quad * 512u + (((gb >> (8 * e)) & 255u) > 127u ? 256u : 0u) + (unsigned)quantise_u8(v[e]);
           k[4 * c + e] = in ? key : NO_KEY;
           if (++x == W) { x = 0; ++y; }
         }
@@ -237,7 +230,7 @@ __global__ __launch_bounds__(NT) void segm_wf_row_kernel(const float* __restrict
       }
     }
     d[x] = by < 0 ? -1 : best;
-    s[x] = by < 0 ? (unsigned char)0 : (unsigned char)quantise(p[(size_t)by * W + bx]);
+    s[x] = by < 0 ? (unsigned char)0 : (unsigned char)quantise_u8(p[(size_t)by * W + bx]);
   }
 }
 
@@ -267,7 +260,7 @@ __global__ __launch_bounds__(NT) void segm_wf_weight_kernel(const float* __restr
   if (x < W && y < H) {
     const size_t q = (size_t)y * W + x;
     const bool pos = gt[plane + q] > 127;
-    const double e = fabs((double)quantise(pred[(size_t)i * stride + q]) / 255.0 - (pos ? 1.0 : 0.0));
+    const double e = fabs((double)quantise_u8(pred[(size_t)i * stride + q]) / 255.0 - (pos ? 1.0 : 0.0));
     if (pos) {
       double ea = 0.0;
 #pragma unroll

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "abi_util.h"
 #include "cc_inl.h"
+#include "label_inl.h"
 #include "slic.h"
 
 // include/camo_slic.h fixes the operation order of steps 5 and 6; hipcc contracts a * b + c by default
@@ -114,8 +115,7 @@ __global__ __launch_bounds__(NT) void slic_assign_kernel(const float* __restrict
   __shared__ float c5[NT][5];         // the centroids of this round whose window meets the tile, in ascending k
   __shared__ int win[NT][5];          // their windows y0, y1, x0, x1 (half open) and k
   __shared__ int wcount[NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = blockIdx.z, ty0 = blockIdx.y * T, tx0 = blockIdx.x * T;
+  const int tid = threadIdx.x, n = blockIdx.z, ty0 = blockIdx.y * T, tx0 = blockIdx.x * T;
   const size_t HW = (size_t)H * W;
   const float two = (float)(2 * step), w = 1.0f / (float)(step * step), fH = (float)H, fW = (float)W;
   float pl[PPT], pa[PPT], pb[PPT], best[PPT];
@@ -140,14 +140,8 @@ __global__ __launch_bounds__(NT) void slic_assign_kernel(const float* __restrict
       wx0 = (int)fmaxf(c[1] - two, 0.f); wx1 = (int)fminf((c[1] + two) + 1.0f, fW);
       hit = wy0 < ty0 + T && wy1 > ty0 && wx0 < tx0 + T && wx1 > tx0;
     }
-    const unsigned long long mask = __ballot(hit);
-    if (lane == 0) wcount[wave] = __popcll(mask);
-    __syncthreads();
-    int slot = __popcll(mask & ((1ull << lane) - 1)), total = 0;
-    for (int i = 0; i < NT / 64; ++i) {
-      if (i < wave) slot += wcount[i];
-      total += wcount[i];
-    }
+    int total;
+    const int slot = block_rank<NT>(hit, wcount, total);
     if (hit) {
       for (int j = 0; j < 5; ++j) c5[slot][j] = c[j];
       win[slot][0] = wy0; win[slot][1] = wy1; win[slot][2] = wx0; win[slot][3] = wx1; win[slot][4] = k;
@@ -192,13 +186,7 @@ __global__ __launch_bounds__(NT) void slic_accumulate_kernel(const float* __rest
     if ((unsigned)k >= (unsigned)K) continue;
     const float* c = lab + p * 3;
     const long long val[6] = {y, x, llrintf(c[0] * FIX), llrintf(c[1] * FIX), llrintf(c[2] * FIX), 1};
-    int slot = -1;
-    const unsigned h = ((unsigned)k * 0x9E3779B1u) >> 25;
-    for (int t = 0; t < SLOTS; ++t) {
-      const int s = (h + t) & (SLOTS - 1);
-      const int prev = atomicCAS(&keys[s], -1, k);
-      if (prev == -1 || prev == k) { slot = s; break; }
-    }
+    const int slot = label_slot<SLOTS>(keys, k);
     if (slot >= 0)
       for (int q = 0; q < 6; ++q) atomicAdd(&acc[slot][q], (unsigned long long)val[q]);
     else
@@ -326,7 +314,7 @@ __global__ __launch_bounds__(NT) void slic_search_kernel(const int* __restrict__
 __global__ __launch_bounds__(NT) void slic_scan_kernel(int* __restrict__ chunk, int chunks, const int* __restrict__ misc, int* __restrict__ counts) {
   __shared__ int s[NT];
   const int n = blockIdx.x;
-  const int large = cc_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [](int) {});
+  const int large = block_chunk_prefix<NT>(chunk + (size_t)n * chunks, chunks, s, [](int) {});
   if (threadIdx.x == 0) { counts[2 * n] = large + 1; counts[2 * n + 1] = misc[1 + n]; }
 }
 
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(NT) void slic_rank_kernel(const int* __restrict__ p
     const int q = blockIdx.x * SLIC_CHUNK + j * NT + tid, p = base + q;
     const bool is_large = q < HW && parent[p] == p && size[p] >= min_size;
     int total;
-    const int before = cc_block_rank<NT>(is_large, wcount, total);
+    const int before = block_rank<NT>(is_large, wcount, total);
     if (is_large) adj[p] = running + before + 1;
     running += total;
     __syncthreads();

@@ -9,7 +9,8 @@ hold the HIP kernels to the checker, stage by stage and end to end:
                 be a few ulp looser than numpy's)
   assign        nearest and dist equal the float32 restatement bit for bit, on the float64 trajectory cast to fp32
   update        equal to the float32 restatement bit for bit; against float64 means: colours 2^-25 + 2^-24 |m| (the 2^-24
-                fixed point of the sums rounds each pixel by at most 2^-25, the fp32 result by half an ulp), coordinates 2^-24 |m|
+                fixed point of the sums rounds each pixel by at most 2^-25, the fp32 result by half an ulp), coordinates 2^-24 |m|;
+                bit for bit also on maps with more labels in a tile than the tile's table has slots
   connect       equal to the sequential loop, exactly
   end to end    the three clear-margin cases equal the float64 reference exactly
 
@@ -306,6 +307,38 @@ def test_update_against_float64_means(name):
         print(f"{name}[{k}]: max update error / bound = {float((err / bound).max()):.3f}, max error {float(err.max()):.3e}")
         assert (err <= bound).all()
         assert a[k].tobytes() == R.update(lab[k], near[k], cent[k], np.float32).tobytes()
+
+
+def _tile_labels(near):
+    """Distinct labels in each 32 x 32 tile of one map, tiles in reading order."""
+    H, W = near.shape
+    return [len(np.unique(near[y:y + 32, x:x + 32])) for y in range(0, H, 32) for x in range(0, W, 32)]
+
+
+# A tile's table holds 128 labels; real assignments stay far below that, so these maps are made to pass it: name -> (side, K,
+# near of the side x side pixels, distinct labels per tile).  Every pixel its own centroid; the same over four tiles; and every
+# centroid collecting pixels from several tiles, some through a table and some past a full one.
+FULL_TABLE_MAPS = {
+    "32x32 arange": (32, 1024, lambda n: np.arange(n), [1024]),
+    "40x40 arange": (40, 1600, lambda n: np.arange(n), [1024, 256, 256, 64]),
+    "40x40 stride 7 mod 300": (40, 300, lambda n: np.arange(n) * 7 % 300, [300, 120, 244, 64]),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(FULL_TABLE_MAPS))
+def test_update_past_a_full_tile_table_bit_for_bit(name):
+    side, K, fill, per_tile = FULL_TABLE_MAPS[name]
+    near = fill(side * side).reshape(side, side).astype(np.int32)
+    assert _tile_labels(near) == per_tile and max(per_tile) > 128
+    rs = np.random.RandomState(side + K)
+    lab = rs.uniform(-1.0, 1.0, (side, side, 3)).astype(np.float32)
+    cent = rs.uniform(0.0, side, (K, 5)).astype(np.float32)
+    want = R.update(lab, near, cent, np.float32)
+    a = _update_device(_cuda(lab[None]), _cuda(near[None]), _cuda(cent[None])).cpu().numpy()
+    b = _update_device(_cuda(lab[None]), _cuda(near[None]), _cuda(cent[None])).cpu().numpy()
+    assert a.tobytes() == b.tobytes()
+    assert a[0].tobytes() == want.tobytes(), int((a[0] != want).sum())
 
 
 def _check_connect(maps, min_size, max_size, oversized=False):
