@@ -41,6 +41,10 @@ RSZ_U8, RSZ_F32 = 0, 1              # CAMO_RSZ_U8, CAMO_RSZ_F32
 INST_FIELDS = 8                     # CAMO_INST_FIELDS
 INST_COUNTS = 4                     # CAMO_INST_COUNTS
 INST_MAX_ROWS = 1 << 24             # CAMO_INST_MAX_ROWS
+IM_MAX_THRESHOLDS = 16              # CAMO_IM_MAX_THRESHOLDS
+IM_MAX_IDS = 1024                   # CAMO_IM_MAX_IDS
+IM_MAX_CELLS = 1 << 26              # CAMO_IM_MAX_CELLS
+IM_COUNTS = 4                       # CAMO_IM_COUNTS
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -181,6 +185,10 @@ PROTOTYPES = {
     "camo_instances.h": (
         ("camo_instances_workspace_bytes", sz, (i32, i32, i32)),
         ("camo_instances", i32, (vp, i64, f32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp)),
+    ),
+    "camo_inst_match.h": (
+        ("camo_inst_match_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
+        ("camo_inst_match", i32, (vp, vp, i32, i32, i32, i32, i32, vp, i32, P(i32), i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp)),
     ),
     "camo_guided.h": (
         ("camo_guided_workspace_bytes", sz, (i32, i32, i32, i32)),

@@ -1,0 +1,279 @@
+// Instance matching (include/camo_inst_match.h): the pixels of every (predicted id, ground-truth id) pair of two label
+// maps, and the greedy matches of predictions to ground truth in score order at each IoU threshold.  8 B/pixel in, one pixel-rate
+// pass; the rest works on the small tables.  Every grid covers the whole batch.
+//
+//   clear    inter and counts to zero
+//   overlap  per chunk of 1024 pixels: a run of equal (p, g) over consecutive lanes is one record; records meet in a block's LDS
+//            slots (label_inl.h's label_slot; memory when the table is full), the block adds its slots to inter once
+//   areas    row sums (one wave per predicted id) and column sums (one thread per ground-truth id) of inter, and every predicted
+//            id's rank in score order (one thread per id)
+//   match    one block per (threshold, image): predicted ids in rank order, each takes the unmatched ground-truth id of highest IoU
+//            at or above the threshold; up to 16 more blocks per image write every prediction's best ground truth and the counts
+//
+// Integer arithmetic only, IoUs compared by cross-multiplication; 32-bit integer atomic adds only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "abi_util.h"
+#include "common.h"
+#include "inst_match.h"
+#include "instances.h"
+#include "label_inl.h"
+#include "../../include/camo_inst_match.h"
+
+namespace {
+
+constexpr int NT = INST_NT, CHUNK = INST_CHUNK, PPT = INST_CHUNK / INST_NT, WAVES = NT / 64;
+constexpr int SLOTS = 32;                  // pairs a block of the overlap launch sums in LDS
+constexpr int MAX_IDS = CAMO_IM_MAX_IDS;
+static_assert(CHUNK % NT == 0 && NT % 64 == 0, "whole waves, whole passes");
+static_assert(IM_MAX_THRESHOLDS == CAMO_IM_MAX_THRESHOLDS, "the kernel argument holds every threshold");
+
+__global__ __launch_bounds__(NT) void im_clear_kernel(int* __restrict__ inter, long long cells, int* __restrict__ counts, int ncounts) {
+  const long long step = (long long)gridDim.x * NT;
+  for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < cells; i += step) inter[i] = 0;
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < ncounts; i += NT) counts[i] = 0;
+}
+
+// grid (chunks, images).  key = p (G + 1) + g of a pixel with both labels in range, -1 otherwise (counted in counts[0], counts[1]).
+__global__ __launch_bounds__(NT) void im_overlap_kernel(const int* __restrict__ pl, const int* __restrict__ gl, int HW, int P, int G,
+                                                        int* __restrict__ inter, int* __restrict__ counts) {
+  __shared__ int slot_key[SLOTS];                                  // -1: free
+  __shared__ int slot_cnt[SLOTS];
+  __shared__ int oob[2];
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y;
+  const size_t base = (size_t)n * HW;
+  if (tid < SLOTS) { slot_key[tid] = -1; slot_cnt[tid] = 0; }
+  if (tid < 2) oob[tid] = 0;
+  __syncthreads();
+  int* cells = inter + (size_t)n * (P + 1) * (G + 1);
+  int np = 0, ng = 0;
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    const int q = blockIdx.x * CHUNK + j * NT + tid;
+    int key = -1;
+    if (q < HW) {
+      const int p = pl[base + q], g = gl[base + q];
+      const bool pin = (unsigned)p <= (unsigned)P, gin = (unsigned)g <= (unsigned)G;      // (a negative label is out of range)
+      np += !pin;
+      ng += !gin;
+      if (pin && gin) key = p * (G + 1) + g;
+    }
+    if (__ballot(key >= 0) == 0ull) continue;                      // (wave-uniform)
+    const int prev = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || prev != key;
+    const int len = run_end(head, lane) - lane;
+    if (head && key >= 0) {
+      const int s = label_slot<SLOTS>(slot_key, key);
+      if (s >= 0) atomicAdd(&slot_cnt[s], len);
+      else atomicAdd(cells + key, len);
+    }
+  }
+  np = wave_sum_int(np);
+  ng = wave_sum_int(ng);
+  if (lane == 0) {
+    if (np) atomicAdd(&oob[0], np);
+    if (ng) atomicAdd(&oob[1], ng);
+  }
+  __syncthreads();
+  if (tid < SLOTS && slot_key[tid] >= 0) atomicAdd(cells + slot_key[tid], slot_cnt[tid]);
+  if (tid < 2 && oob[tid]) atomicAdd(counts + CAMO_IM_COUNTS * n + tid, oob[tid]);
+}
+
+// The score Sq / area of a row (area, ..., Sq) of camo_instances' table; 0 / 1 when it is not a row.
+__device__ __forceinline__ void im_score(long long a, long long s, long long& sq, long long& area) {
+  const bool row = a > 0 && a <= CAMO_RGD_MAX_IMAGE_PIXELS && s >= 0 && s <= 255 * a;
+  sq = row ? s : 0;
+  area = row ? a : 1;
+}
+
+// grid (row blocks + column blocks + rank blocks, images).  Row blocks: a wave sums inter's row p.  Column blocks: a thread sums
+// column g (consecutive threads, consecutive addresses).  Rank blocks: a thread counts the ids that come before id p.
+__global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ inter, int P, int G, const long long* __restrict__ table, int nrows,
+                                                      int row_blocks, int col_blocks, int* __restrict__ area_p, int* __restrict__ area_g,
+                                                      int* __restrict__ rank, int* __restrict__ pred_rows, int* __restrict__ gt_area) {
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y;
+  const int* cells = inter + (size_t)n * (P + 1) * (G + 1);
+  int b = blockIdx.x;
+  if (b < row_blocks) {
+    const int p = b * WAVES + (tid >> 6);
+    if (p > P) return;                                             // (the whole wave)
+    int s = 0;
+    for (int g = lane; g <= G; g += 64) s += cells[(size_t)p * (G + 1) + g];
+    s = wave_sum_int(s);
+    if (lane == 0) {
+      area_p[(size_t)n * (P + 1) + p] = s;
+      if (p) pred_rows[((size_t)n * P + p - 1) * 4] = s;
+    }
+    return;
+  }
+  b -= row_blocks;
+  if (b < col_blocks) {
+    const int g = b * NT + tid;
+    if (g > G) return;
+    int s = 0;
+#pragma unroll 8                                                   // (independent loads: eight in flight)
+    for (int p = 0; p <= P; ++p) s += cells[(size_t)p * (G + 1) + g];
+    area_g[(size_t)n * (G + 1) + g] = s;
+    if (g) gt_area[(size_t)n * G + g - 1] = s;
+    return;
+  }
+  b -= col_blocks;
+  const int p = b * NT + tid + 1;
+  if (p > P) return;
+  int before = p - 1;                                              // no table: the order is by id
+  if (table) {
+    const long long* rows = table + (size_t)n * nrows * CAMO_INST_FIELDS;
+    const int have = min(P, nrows);                                // ids past the table's rows score 0 / 1
+    long long sp = 0, ap = 1;
+    if (p <= have) im_score(rows[(size_t)(p - 1) * CAMO_INST_FIELDS], rows[(size_t)(p - 1) * CAMO_INST_FIELDS + 7], sp, ap);
+    before = 0;
+#pragma unroll 8                                                   // (the rows are the same for every lane: eight pairs of loads in flight)
+    for (int q = 1; q <= have; ++q) {
+      long long sq, aq;
+      im_score(rows[(size_t)(q - 1) * CAMO_INST_FIELDS], rows[(size_t)(q - 1) * CAMO_INST_FIELDS + 7], sq, aq);
+      const long long l = sq * ap, r = sp * aq;                    // score q against score p: both below 2^60
+      before += l > r || (l == r && q < p);
+    }
+    if (sp == 0) before += max(0, p - 1 - have);                   // the ids have + 1 .. p - 1 tie with a score of 0 and come first
+  }
+  rank[(size_t)n * P + p - 1] = before;
+  pred_rows[((size_t)n * P + p - 1) * 4 + 1] = before;
+}
+
+// A candidate ground-truth id with its intersection i and union u; g == 0: none.  a before b: higher IoU, then smaller id.
+struct ImCand { int i, u, g; };
+__device__ __forceinline__ bool im_before(const ImCand& a, const ImCand& b) {
+  if (a.g == 0) return false;
+  if (b.g == 0) return true;
+  const long long l = (long long)a.i * b.u, r = (long long)b.i * a.u;
+  return l > r || (l == r && a.g < b.g);
+}
+// the wave's best candidate, in every lane
+__device__ __forceinline__ ImCand im_wave_best(ImCand c) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const ImCand other{__shfl_xor(c.i, o, 64), __shfl_xor(c.u, o, 64), __shfl_xor(c.g, o, 64)};
+    if (im_before(other, c)) c = other;
+  }
+  return c;
+}
+
+// The blocks past the thresholds' (block e of E): every prediction's ground-truth id of highest IoU, matched or not, one wave per
+// predicted id; block 0 also counts the ids in use.  ap, ag: the areas in LDS; used: two zeroed ints of LDS.
+__device__ __forceinline__ void im_best_rows(const int* __restrict__ cells, int P, int G, const int* ap, const int* ag, int* used, int e, int E,
+                                             int* __restrict__ rows, int* __restrict__ counts) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int p = e * WAVES + wave + 1; p <= P; p += E * WAVES) {
+    const int a = ap[p];
+    const int* row = cells + (size_t)p * (G + 1);
+    ImCand best{0, 1, 0};
+    if (a)
+      for (int g = lane + 1; g <= G; g += 64) {
+        const int i = row[g];
+        if (i <= 0) continue;
+        const ImCand c{i, a + ag[g] - i, g};
+        if (im_before(c, best)) best = c;
+      }
+    best = im_wave_best(best);
+    if (lane == 0) {
+      rows[(size_t)(p - 1) * 4 + 2] = best.g;
+      rows[(size_t)(p - 1) * 4 + 3] = best.i;
+    }
+  }
+  if (e) return;
+  int np = 0, ng = 0;
+  for (int p = tid + 1; p <= P; p += NT) np += ap[p] > 0;
+  for (int g = tid + 1; g <= G; g += NT) ng += ag[g] > 0;
+  np = wave_sum_int(np);
+  ng = wave_sum_int(ng);
+  if (lane == 0) { atomicAdd(&used[0], np); atomicAdd(&used[1], ng); }
+  __syncthreads();
+  if (tid < 2) counts[2 + tid] = used[tid];
+}
+
+// grid (thresholds + row blocks, images).  Thread t owns ground-truth ids t + 1, t + 1 + NT, ...: it alone reads and writes their taken[] flag.
+__global__ __launch_bounds__(NT) void im_match_kernel(const int* __restrict__ inter, int P, int G, ImThresholds thr, int T, const int* __restrict__ area_p,
+                                                      const int* __restrict__ area_g, const int* __restrict__ rank, int* __restrict__ match,
+                                                      int* __restrict__ gt_match, int* __restrict__ pred_rows, int* __restrict__ counts) {
+  __shared__ int ap[MAX_IDS + 1], ag[MAX_IDS + 1], taken[MAX_IDS + 1];
+  __shared__ int order[MAX_IDS];                                   // order[r] = the predicted id of rank r
+  __shared__ ImCand wbest[2][WAVES];
+  __shared__ int used[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = blockIdx.x, n = blockIdx.y;
+  const int* cells = inter + (size_t)n * (P + 1) * (G + 1);
+  for (int p = tid; p <= P; p += NT) ap[p] = area_p[(size_t)n * (P + 1) + p];
+  for (int g = tid; g <= G; g += NT) { ag[g] = area_g[(size_t)n * (G + 1) + g]; taken[g] = 0; }
+  if (k < T)
+    for (int p = tid; p < P; p += NT) order[rank[(size_t)n * P + p]] = p + 1;    // (rank is a permutation of 0 .. P - 1)
+  if (tid < 2) used[tid] = 0;
+  __syncthreads();
+  if (k >= T) {                                                    // (the whole block)
+    im_best_rows(cells, P, G, ap, ag, used, k - T, gridDim.x - T, pred_rows + (size_t)n * P * 4, counts + CAMO_IM_COUNTS * n);
+    return;
+  }
+
+  const long long num = thr.num[k], den = thr.den;
+  int* mrow = match + ((size_t)n * T + k) * P;
+  int buf = 0;
+  for (int r = 0; r < P; ++r) {
+    const int p = order[r], a = ap[p];
+    if (a == 0) {                                                  // (the whole block: no barrier is skipped by a part of it)
+      if (tid == 0) mrow[p - 1] = 0;
+      continue;
+    }
+    const int* row = cells + (size_t)p * (G + 1);
+    ImCand best{0, 1, 0};
+    for (int g = tid + 1; g <= G; g += NT) {
+      const int ga = ag[g];
+      if (ga == 0 || taken[g]) continue;
+      const int i = row[g];
+      if (i <= 0) continue;
+      const ImCand c{i, a + ga - i, g};
+      if (den * c.i < num * c.u) continue;
+      if (im_before(c, best)) best = c;
+    }
+    best = im_wave_best(best);
+    if (lane == 0) wbest[buf][wave] = best;
+    __syncthreads();
+    best = wbest[buf][0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w)
+      if (im_before(wbest[buf][w], best)) best = wbest[buf][w];
+    if (best.g && ((best.g - 1) & (NT - 1)) == tid) taken[best.g] = p;      // (the owner)
+    if (tid == 0) mrow[p - 1] = best.g;
+    buf ^= 1;      // the next round writes the other half: a wave still reading this one is at most one barrier behind
+  }
+  for (int g = tid + 1; g <= G; g += NT) gt_match[((size_t)n * T + k) * G + g - 1] = taken[g];
+}
+
+}  // namespace
+
+ImWs im_carve(int N, int P, int G, void* base) {
+  ImWs w{};
+  camo_abi::Carver c(base);
+  w.area_p = c.take<int>((size_t)N * (P + 1));
+  w.area_g = c.take<int>((size_t)N * (G + 1));
+  w.rank = c.take<int>((size_t)N * P);
+  w.bytes = c.bytes();
+  return w;
+}
+
+int launch_inst_match(const int* pred_labels, const int* gt_labels, int N, int H, int W, int P, int G, const long long* pred_table,
+                      int pred_table_rows, const ImThresholds& thr, int T, const ImWs& ws, int* inter, int* pred_rows, int* gt_area,
+                      int* match, int* gt_match, int* counts, hipStream_t stream) {
+  const int HW = H * W, chunks = (HW + CHUNK - 1) / CHUNK;
+  const long long cells = (long long)N * (P + 1) * (G + 1);
+  const unsigned clear_blocks = (unsigned)std::min<long long>((cells + NT - 1) / NT, 4096);
+  hipLaunchKernelGGL(im_clear_kernel, dim3(clear_blocks), dim3(NT), 0, stream, inter, cells, counts, CAMO_IM_COUNTS * N);
+  hipLaunchKernelGGL(im_overlap_kernel, dim3(chunks, N), dim3(NT), 0, stream, pred_labels, gt_labels, HW, P, G, inter, counts);
+  const int row_blocks = (P + 1 + WAVES - 1) / WAVES, col_blocks = (G + 1 + NT - 1) / NT, rank_blocks = (P + NT - 1) / NT;
+  hipLaunchKernelGGL(im_areas_kernel, dim3(row_blocks + col_blocks + rank_blocks, N), dim3(NT), 0, stream, inter, P, G, pred_table,
+                     pred_table_rows, row_blocks, col_blocks, ws.area_p, ws.area_g, ws.rank, pred_rows, gt_area);
+  const int best_blocks = std::min((P + WAVES - 1) / WAVES, 16);
+  hipLaunchKernelGGL(im_match_kernel, dim3(T + best_blocks, N), dim3(NT), 0, stream, inter, P, G, thr, T, ws.area_p, ws.area_g, ws.rank, match, gt_match,
+                     pred_rows, counts);
+  return (int)hipGetLastError();
+}

@@ -33,14 +33,6 @@ constexpr int NONE = 0x7fffffff;
 constexpr unsigned long long BOX_MIN_INIT = 0x7fffffffffffffffull;
 static_assert(T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "whole waves, whole passes");
 
-// Runs of consecutive lanes with the same key (`head`: the lane starts a run): the lane one past the end of the calling lane's run.
-// Every lane of the wave calls.
-__device__ __forceinline__ int run_end(bool head, int lane) {
-  const unsigned long long hm = __ballot(head);
-  const unsigned long long above = lane < 63 ? hm >> (lane + 1) : 0ull;
-  return above ? lane + __ffsll((long long)above) : 64;
-}
-
 // grid (tiles of an image, images; an image loop when the grid would be too large).  MODE_BG: members are the background pixels,
 // border[] is cleared.  MODE_FG: members are the foreground pixels.  MODE_FILLED: the foreground pixels and those of the background
 // components (bgpar, flattened) that do not touch the border; a root of such a component counts one hole.  The component modes clear area[].

@@ -1,7 +1,8 @@
-// Reductions over a label map, stated once for rg_features.hip, rg_batch.hip, rg_targets.hip, slic.hip and instances.hip (DESIGN.md
-// 10k).  The kernels stay in those files with their grids, LDS arrays and side effects; these are the device-inline pieces they share:
+// Reductions over a label map, stated once for rg_features.hip, rg_batch.hip, rg_targets.hip, slic.hip, instances.hip and inst_match.hip
+// (DESIGN.md 10k).  The kernels stay in those files with their grids, LDS arrays and side effects; these are the device-inline pieces they share:
 //
 //   label_slot           a label's slot in a tile's LDS hash table, -1 when the table is full
+//   run_end              where the run of equal keys a lane is in ends, over consecutive lanes of a wave
 //   block_rank           the kept threads before a thread in one pass of its block, and the pass total
 //   block_chunk_prefix   a block's exclusive prefix over an array of counts, in place, with a carry
 //   label_compact        ranks of the kept labels among 0 .. n, a block-wide pass at a time with the base carried
@@ -32,6 +33,14 @@ __device__ __forceinline__ int label_slot(int* keys, int k) {
     if (prev == -1 || prev == k) { slot = s; break; }
   }
   return slot;
+}
+
+// Runs of consecutive lanes with the same key (`head`: the lane starts a run): the lane one past the end of the calling lane's run.
+// Every lane of the wave calls.
+__device__ __forceinline__ int run_end(bool head, int lane) {
+  const unsigned long long hm = __ballot(head);
+  const unsigned long long above = lane < 63 ? hm >> (lane + 1) : 0ull;
+  return above ? lane + __ffsll((long long)above) : 64;
 }
 
 // One pass of a block of NT threads, every thread calls: -> how many threads before this one have `kept` set; total: how many have

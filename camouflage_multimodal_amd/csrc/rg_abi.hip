@@ -1,7 +1,8 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks, the object instances of a predicted mask, and the guided-filter refinement of a mask.
+// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances, and the
+// guided-filter refinement of a mask.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,7 @@
 #include "rg_train.h"
 #include "rg_targets.h"
 #include "instances.h"
+#include "inst_match.h"
 #include "guided.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
@@ -30,6 +32,7 @@
 #include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
 #include "../../include/camo_instances.h"
+#include "../../include/camo_inst_match.h"
 #include "../../include/camo_guided.h"
 
 using namespace camo_abi;
@@ -690,6 +693,46 @@ int camo_instances(const float* pred, int64_t pred_image_stride, float threshold
   if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_instances_workspace_bytes()");
   CK(launch_instances(pred, pred_image_stride, threshold, N, H, W, connectivity, min_area, fill_holes != 0, max_instances, w, labels, clean,
                       reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "instances");
+  return 0;
+}
+
+// ---- Instance matching: overlap table and greedy matches (include/camo_inst_match.h) -----------------------------
+static int im_check(int N, int H, int W, int P, int G, int T) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (P < 1 || P > CAMO_IM_MAX_IDS) return fail(CAMO_E_ARG, "P must be in [1, CAMO_IM_MAX_IDS]");
+  if (G < 1 || G > CAMO_IM_MAX_IDS) return fail(CAMO_E_ARG, "G must be in [1, CAMO_IM_MAX_IDS]");
+  if ((long long)N * (P + 1) * (G + 1) > CAMO_IM_MAX_CELLS) return fail(CAMO_E_ARG, "N * (P + 1) * (G + 1) exceeds CAMO_IM_MAX_CELLS");
+  if (T < 1 || T > CAMO_IM_MAX_THRESHOLDS) return fail(CAMO_E_ARG, "T must be in [1, CAMO_IM_MAX_THRESHOLDS]");
+  return 0;
+}
+
+size_t camo_inst_match_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t P, int32_t G, int32_t T) {
+  if (im_check(N, H, W, P, G, T)) return 0;
+  return im_carve(N, P, G, nullptr).bytes;
+}
+
+int camo_inst_match(const int32_t* pred_labels, const int32_t* gt_labels, int32_t N, int32_t H, int32_t W, int32_t P, int32_t G,
+                    const int64_t* pred_table, int32_t pred_table_rows, const int32_t* thr_num, int32_t thr_den, int32_t T, int32_t* inter,
+                    int32_t* pred_rows, int32_t* gt_area, int32_t* match, int32_t* gt_match, int32_t* counts, void* ws, size_t ws_bytes,
+                    void* stream) {
+  if (int e = im_check(N, H, W, P, G, T)) return e;
+  if (!thr_num) return fail(CAMO_E_ARG, "thr_num is null");
+  if (thr_den < 1 || thr_den > 1000) return fail(CAMO_E_ARG, "thr_den must be in [1, 1000]");
+  ImThresholds thr{};
+  thr.den = thr_den;
+  for (int k = 0; k < T; ++k) {
+    if (thr_num[k] < 1 || thr_num[k] > thr_den) return fail(CAMO_E_ARG, "every thr_num must be in [1, thr_den]");
+    thr.num[k] = thr_num[k];
+  }
+  if (pred_table && pred_table_rows < 1) return fail(CAMO_E_ARG, "pred_table_rows must be >= 1 when pred_table is given");
+  if (reinterpret_cast<uintptr_t>(pred_table) & 7) return fail(CAMO_E_ARG, "pred_table must be 8-byte aligned");
+  if (!pred_labels || !gt_labels || !inter || !pred_rows || !gt_area || !match || !gt_match || !counts || !ws)
+    return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const ImWs w = im_carve(N, P, G, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_inst_match_workspace_bytes()");
+  CK(launch_inst_match(pred_labels, gt_labels, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table), pred_table ? pred_table_rows : 0,
+                       thr, T, w, inter, pred_rows, gt_area, match, gt_match, counts, static_cast<hipStream_t>(stream)), "inst match");
   return 0;
 }
 

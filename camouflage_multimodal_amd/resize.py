@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, instances as _instances, refine as _refine, seg_measures
+from . import _lib, instance_match as _match, instances as _instances, refine as _refine, seg_measures
 from .engine import _ptr, _stream_ptr
 from .rg_detect import detect_camouflage_batch, segmentation_counts, segmentation_metrics
 from .rg_finetune import prepare_finetune_batch
@@ -318,21 +318,53 @@ def _score(preds, gts, threshold, cod, curves=False):
 
 def _native_instances(preds, threshold, connectivity, min_area, fill_holes):
     """``instances.detect_instances`` of every fp32 [H_i, W_i] map; maps of equal size share a call.  Returns (records, labels, clean
-    masks), three lists in the maps' order."""
+    masks, tables), four lists in the maps' order."""
     groups = {}
     for i, p in enumerate(preds):
         groups.setdefault(tuple(p.shape), []).append(i)
-    rec, labels, clean = [None] * len(preds), [None] * len(preds), [None] * len(preds)
+    rec, labels, clean, tables = [None] * len(preds), [None] * len(preds), [None] * len(preds), [None] * len(preds)
     for idx in groups.values():
         found = _instances.detect_instances(torch.stack([preds[i] for i in idx]), threshold, connectivity, min_area, fill_holes)
         for j, i in enumerate(idx):
-            rec[i], labels[i], clean[i] = found["instances"][j], found["labels"][j], found["clean_mask"][j]
-    return rec, labels, clean
+            rec[i], labels[i], clean[i], tables[i] = found["instances"][j], found["labels"][j], found["clean_mask"][j], found["table"][j]
+    return rec, labels, clean, tables
+
+
+def _native_matches(labels, tables, gt_labels, opts):
+    """``instance_match.match_detected`` of every int32 [H_i, W_i] label map against its ground-truth ids; maps of equal size share
+    a call.  Returns (records, tables), two lists in the maps' order (a table dict holds the image's own rows)."""
+    groups = {}
+    for i, (p, g) in enumerate(zip(labels, gt_labels)):
+        if tuple(p.shape) != tuple(g.shape):
+            raise ValueError(f"image {i}: the label map is {tuple(p.shape)}, its ground truth {tuple(g.shape)}")
+        groups.setdefault(tuple(p.shape), []).append(i)
+    rec, out = [None] * len(labels), [None] * len(labels)
+    for idx in groups.values():
+        r, t = _match.match_detected(torch.stack([labels[i] for i in idx]), torch.stack([tables[i] for i in idx]),
+                                     torch.stack([torch.as_tensor(gt_labels[i]).to(labels[i].device, torch.int32) for i in idx]), opts)
+        for j, i in enumerate(idx):
+            rec[i] = r[j]
+            out[i] = {k: (v[j] if isinstance(v, torch.Tensor) else v) for k, v in t.items()}
+    return rec, out
+
+
+def _native_gt_labels(masks, connectivity, max_gt):
+    """``instance_match.ground_truth_labels`` of every [H_i, W_i] mask; masks of equal size share a call."""
+    groups = {}
+    for i, m in enumerate(masks):
+        groups.setdefault(tuple(m.shape), []).append(i)
+    out = [None] * len(masks)
+    for idx in groups.values():
+        lab = _match.ground_truth_labels(torch.stack([masks[i] for i in idx]), connectivity, max_gt)
+        for j, i in enumerate(idx):
+            out[i] = lab[j]
+    return out
 
 
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
-                             cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None):
+                             cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None,
+                             *, match=None):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -348,9 +380,14 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     applies its coefficients to the NATIVE bytes of every image (``refine.guided_upsample``: the fast guided filter), so the native
     map's edges come from the native pixels: "prob_maps_native_refined" (fp32 [H_i, W_i], views of one buffer) and
     "mask_native_refined" beside ``detect_camouflage_batch``'s own refine keys at ``size``; with masks scored at native size also
-    "refined_metrics" / "refined_cod_metrics" of the native refined maps.  "prob_maps_native" and the rest are unchanged."""
+    "refined_metrics" / "refined_cod_metrics" of the native refined maps.  "prob_maps_native" and the rest are unchanged.
+    ``match`` (``detect_camouflage_batch``'s; "gt_labels" is a list of int32 [H_i, W_i] maps) matches the NATIVE-size instances to
+    the ground-truth ones -- by default the connected components of every native mask, which needs ``gt_masks`` scored at native
+    size; images of equal size share a call -- and adds "instance_match" (per image the records) and "instance_match_tables" (per
+    image ``match_instances``' dict of its own rows).  ``None``: nothing changes."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
+    match = _match.match_options(match, instances, gt_masks is not None and evaluate_at == "native")
     refine = _refine.refine_options(refine)
     if refine is not None and refine["guide"] != "rgb":
         raise ValueError('detect_camouflage_ragged applies the coefficients to the native 3-channel bytes: refine["guide"] must be "rgb"')
@@ -378,10 +415,17 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         if cod_metrics:
             out["cod_metrics"] = cods
     if instances:
-        rec, labels, clean = _native_instances(native, threshold, connectivity, min_area, fill_holes)
+        rec, labels, clean, tables = _native_instances(native, threshold, connectivity, min_area, fill_holes)
         out.update({"instances_native": rec, "instance_labels_native": labels, "clean_mask_native": clean})
         if masks is not None and not resized:
             out["clean_metrics"], _ = _score([c.float() for c in clean], [masks.image(i) for i in range(len(sizes))], 0.5, False)
+        if match is not None:
+            gt_labels = match["gt_labels"]
+            if gt_labels is None:
+                gt_labels = _native_gt_labels([masks.image(i) for i in range(len(sizes))], connectivity, match["max_gt"])
+            elif len(gt_labels) != len(sizes):
+                raise ValueError(f'match["gt_labels"] holds {len(gt_labels)} maps for {len(sizes)} images')
+            out["instance_match"], out["instance_match_tables"] = _native_matches(labels, tables, gt_labels, match)
     if refine is not None:
         refined, _ = _refine.guided_upsample(out["refine_coefficients"], packed)
         out["prob_maps_native_refined"] = refined
@@ -437,9 +481,14 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     Returns {"files": stems, "metrics": per-file ``segmentation_metrics`` dicts and, with ``cod_metrics=True``, "cod_metrics":
     per-file measures and "aggregate": ``seg_measures.aggregate_cod_measures`` of them}; the last three only with masks.
     With ``refine`` (``detect_camouflage_ragged``'s) the map written to ``out_dir`` and the map scored are the REFINED ones
-    ("prob_maps_native_refined"; "prob_refined" with ``evaluate_at="resized"``); without it nothing changes."""
+    ("prob_maps_native_refined"; "prob_refined" with ``evaluate_at="resized"``); without it nothing changes.
+    With ``match`` (``detect_camouflage_ragged``'s; needs ``instances=True`` and ``mask_dir``, or "gt_labels" for every file in
+    sorted order) the native-size instances of every file are matched to the ground-truth ones and the result also holds
+    "instance_match" (per-file records) and "instance_ap": ``instance_match.InstanceAP`` over all files, scored by every instance's
+    mean probability."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
+    match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None)
     cod = bool(kw.pop("cod_metrics", False))
     evaluate_at = kw.pop("evaluate_at", "native")
     threshold = kw.get("threshold", 0.5)
@@ -457,16 +506,28 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     stems = list(images)
     result = {"files": stems}
     metrics, cods = [], []
+    matched, ap = [], _match.InstanceAP()
+    if match is not None and match["gt_labels"] is not None and len(match["gt_labels"]) != len(stems):
+        raise ValueError(f'match["gt_labels"] holds {len(match["gt_labels"])} maps for {len(stems)} files')
     for at in range(0, len(stems), int(batch_size)):
         part = stems[at:at + int(batch_size)]
         arrays = [np.array(Image.open(images[s]).convert("RGB")) for s in part]
-        out = detect_camouflage_ragged(rg_model, arrays, **kw)
+        gts = None
+        if masks is not None:
+            gts = _mask_list([np.array(Image.open(masks[s]).convert("L")) for s in part], len(part), "masks", _device(kw.get("device", "cuda")))
+        if match is not None:
+            gt_labels = match["gt_labels"][at:at + len(part)] if match["gt_labels"] is not None else \
+                _native_gt_labels([gts.image(i) for i in range(len(part))], kw.get("connectivity", 8), match["max_gt"])
+            out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, gt_labels=gt_labels), **kw)
+            matched += out["instance_match"]
+            ap.add(out["instance_match"], [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]])
+        else:
+            out = detect_camouflage_ragged(rg_model, arrays, **kw)
         native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
         if out_dir is not None:
             for s, p in zip(part, native):
                 Image.fromarray(quantise_map(p).cpu().numpy()).save(os.path.join(out_dir, s + ".png"))
         if masks is not None:
-            gts = _mask_list([np.array(Image.open(masks[s]).convert("L")) for s in part], len(part), "masks", native[0].device)
             if evaluate_at == "resized":
                 small = resize_batch(gts, size, "nearest", out_dtype=torch.uint8)
                 m, c = _score(list(out["prob_refined"] if refined else out["prob_maps"][:, 0]), list(small), threshold, cod, curves=True)
@@ -479,4 +540,6 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         if cod:
             result["aggregate"] = seg_measures.aggregate_cod_measures(cods)
             result["cod_metrics"] = [{k: v for k, v in c.items() if k not in ("f_curve", "e_curve")} for c in cods]
+    if match is not None:
+        result["instance_match"], result["instance_ap"] = matched, ap.result()
     return result
