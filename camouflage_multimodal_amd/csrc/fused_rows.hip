@@ -100,7 +100,9 @@ __global__ __launch_bounds__(256) void shadow_kernel(const ShadowBatch sb, int t
 }
 
 // ------------------------------------------------------------------------------------------------ forward, front half
-constexpr int F_BUFR = 32 * PX, F_BUFQ = F_BUFR + 32 * PR, F_LDS = F_BUFQ + 32 * PQ;      // 8704, 25600, 75264
+// F_PTAB: the stream's bias vectors [b0 (256) | bq (256) | bkv (512)] fp32, four values per thread at block start: an epilogue
+// that loaded them behind its weight stream waited out a global round trip per group with nothing to hide it
+constexpr int F_BUFR = 32 * PX, F_BUFQ = F_BUFR + 32 * PR, F_PTAB = F_BUFQ + 32 * PQ, F_LDS = F_PTAB + 4096;      // 8704, 25600, 75264, 79360
 
 template <int DEPTH, bool ROT>
 __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
@@ -115,10 +117,13 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
   stamp(a.stamps, 0);
   Stage<2, 8, true, DEPTH> st0;
   st0.prefetch(reinterpret_cast<const u32x4*>(S.W0) + (size_t)w * (8 * 2 * 64) + lane, rot);
+  float* ptab = reinterpret_cast<float*>(smem + F_PTAB);
   {   // input tile: fp32 -> bf16, rows past the end cleared
     const int r = tid >> 3, c = tid & 7;
     const float4* src = reinterpret_cast<const float4*>(S.X + (size_t)(row0 + min(r, nrows - 1)) * 128 + 16 * c);
     float4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3];
+    const float p0 = S.b0[tid], p1 = S.bq[tid], p2 = S.bkv[tid], p3 = S.bkv[256 + tid];
+    ptab[tid] = p0; ptab[256 + tid] = p1; ptab[512 + tid] = p2; ptab[768 + tid] = p3;
     if (r >= nrows) { v0 = v1 = v2 = v3 = make_float4(0.f, 0.f, 0.f, 0.f); }
     *reinterpret_cast<u32x4*>(bufX + r * PX + 32 * c) = u32x4{pack2(v0.x, v0.y), pack2(v0.z, v0.w), pack2(v1.x, v1.y), pack2(v1.z, v1.w)};
     *reinterpret_cast<u32x4*>(bufX + r * PX + 32 * c + 16) = u32x4{pack2(v2.x, v2.y), pack2(v2.z, v2.w), pack2(v3.x, v3.y), pack2(v3.z, v3.w)};
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-        const float4 bv = *reinterpret_cast<const float4*>(S.b0 + c0);
+        const float4 bv = *reinterpret_cast<const float4*>(ptab + c0);
         *reinterpret_cast<u32x2*>(bufR + l31 * PR + 2 * c0) =
             u32x2{pack2(acc[t][4 * g] + bv.x, acc[t][4 * g + 1] + bv.y), pack2(acc[t][4 * g + 2] + bv.z, acc[t][4 * g + 3] + bv.w)};
       }
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
       const int tg = 6 * w + t;                                  // wave-uniform
-      const float* bias = tg < 8 ? S.bq + 32 * tg : S.bkv + 32 * (tg - 8);
+      const float* bias = ptab + 256 + 32 * tg;                  // [bq | bkv]
       const float sc = tg < 8 ? a.qscale : 1.0f;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -188,11 +193,13 @@ constexpr int B_VS = 16 * PK;                       // 8448
 // Two layouts.  OCC = 2 (launches of at most two blocks per CU: small batches, one tile per CU is the critical path): region A =
 // [0, 33280) is the attention scratch (8448 + 9216 bytes for an RG tile, 4 * 32 * 192 for a KG block) and, once the attention and the
 // out-projection are done with it, the fp32 tile of the LayerNorm output whose columns are summed for the mean pool (only the
-// tile's real rows are added: 13 for a KG chain); 68 KB.  OCC = 3 (larger launches): the pool is a halving butterfly in registers, the
+// tile's real rows are added: 13 for a KG chain); 71.5 KB with the parameter table.  OCC = 3 (larger launches): the pool is a halving butterfly in registers, the
 // LayerNorm output tile (bufY) and the normalised LayerNorm input of a saving call (bufXH) take region A's place; 51.7 KB, three
 // blocks per CU, 168 VGPRs.
 template <int OCC> struct BackL;
-template <> struct BackL<2> { static constexpr int XH = 0, O = 32 * PT * 4, Y = O + 32 * PR, RED = Y + 32 * PR, LDS = RED + 1024; };       // 0, 33280, 50176, 67072, 68096
+// OCC = 2 also keeps the stream's parameter vectors [bo (256) | ln_g (256) | ln_b (256) | b1 (512)] fp32 in LDS (PTAB, 5 KB; 73 216 bytes in
+// all): its epilogues sit on the critical path with one wave per SIMD, and a vector loaded behind a weight stream was a bare round trip.
+template <> struct BackL<2> { static constexpr int XH = 0, O = 32 * PT * 4, Y = O + 32 * PR, RED = Y + 32 * PR, PTAB = RED + 1024, LDS = PTAB + 5120; };       // 0, 33280, 50176, 67072, 68096, 73216
 template <> struct BackL<3> { static constexpr int Y = 0, XH = 32 * PR, O = 2 * 32 * PR, RED = O + 32 * PR, LDS = RED + 1024; };             // 0, 16896, 33792, 50688, 51712
 constexpr int B_LDS = BackL<2>::LDS;
 static_assert(BackL<3>::O >= 4 * 32 * 192 && BackL<3>::O >= 8448 + 9216 && BackL<2>::O >= 4 * 32 * 192, "attention scratch inside region A");
@@ -202,11 +209,18 @@ static_assert(BackL<3>::O >= 4 * 32 * 192 && BackL<3>::O >= 8448 + 9216 && BackL
 __device__ __forceinline__ void attn_rg_tile(const BackArgs& a, char* smem, char* bufO, int b, size_t row0, int nrows, int w, int lane) {
   const int tid = threadIdx.x, l31 = lane & 31, h = lane >> 5, Nk = a.Nk;
   char* Ks = smem; char* Vs = smem + B_VS;
-  // the sample's key | value rows: [Nk][512] bf16 -> two images, rows Nk..15 cleared
-  for (int c = tid; c < 16 * 64; c += 256) {
-    const int j = c >> 6, ch = c & 63;
-    u32x4 v = u32x4{0u, 0u, 0u, 0u};
-    if (j < Nk) v = *reinterpret_cast<const u32x4*>(a.KV16 + ((size_t)b * Nk + j) * 512 + 8 * ch);
+  // the sample's key | value rows: [Nk][512] bf16 -> two images, rows Nk..15 cleared.  Four unconditional loads in one batch (row
+  // clamped, value cleared): behind a branch each was a round trip of its own
+  u32x4 kv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i;
+    kv[i] = *reinterpret_cast<const u32x4*>(a.KV16 + ((size_t)b * Nk + min(c >> 6, Nk - 1)) * 512 + 8 * (c & 63));
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i, j = c >> 6, ch = c & 63;
+    const u32x4 v = j < Nk ? kv[i] : u32x4{0u, 0u, 0u, 0u};
     if (ch < 32) *reinterpret_cast<u32x4*>(Ks + j * PK + 16 * ch) = v;
     else         *reinterpret_cast<u32x4*>(Vs + j * PV + 16 * (ch - 32)) = v;
   }
@@ -464,6 +478,21 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   Stage<2, 16, true, DEPTH> sto;
   Stage<4, 16, false, DEPTH> stf;
   if (!kg) sto.prefetch(reinterpret_cast<const u32x4*>(S.Wo) + (size_t)w * (16 * 2 * 64) + lane, rot);   // (flows during the attention)
+  // OCC = 2: what the two epilogues read from global memory at addresses that depend on nothing this kernel computes is loaded in front of the
+  // attention (KG chain: in front of the combine) -- the parameter vectors, five values per thread, into the LDS table once the
+  // attention is through; this lane's residual row, clamped into the tile, into registers
+  float* ptab = reinterpret_cast<float*>(smem + BackL<2>::PTAB);
+  float pt[5];
+  u32x2 rres[2][4];
+  auto load_early = [&](size_t row) {
+    if constexpr (OCC == 2) {
+      pt[0] = S.bo[tid]; pt[1] = S.ln_g[tid]; pt[2] = S.ln_b[tid]; pt[3] = S.b1[tid]; pt[4] = S.b1[256 + tid];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rres[t][g] = *reinterpret_cast<const u32x2*>(S.R16 + row * 256 + 64 * w + 32 * t + 8 * g + 4 * h);
+    }
+  };
   if (kg) {
     b = vid / a.max_splits;
     const int sp = vid - b * a.max_splits;
@@ -490,6 +519,7 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
     for (int c = tid; c < 32 * PR / 16; c += 256) reinterpret_cast<u32x4*>(bufO)[c] = u32x4{0u, 0u, 0u, 0u};   // rows >= Nk stay zero
     __syncthreads();
     sto.prefetch(reinterpret_cast<const u32x4*>(S.Wo) + (size_t)w * (16 * 2 * 64) + lane, rot);
+    load_early((size_t)b * a.Nk + min(l31, a.Nk - 1));
     attn_kg_combine(a, smem, bufO, b, nsplit);
     stamp(a.stamps, 6);
     rowg0 = (size_t)b * a.Nk; nrows = a.Nk; inv_n = 1.0f / (float)a.Nk;
@@ -499,10 +529,19 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
     const int4 td = a.tile_desc[vid - nkg];
     if (td.x < 0) return;
     b = td.x; rowg0 = td.y; nrows = td.z; inv_n = __int_as_float(td.w);
+    load_early(rowg0 + min(l31, nrows - 1));
     attn_rg_tile(a, smem, bufO, b, rowg0, nrows, w, lane);
+  }
+  if constexpr (OCC == 2) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) ptab[256 * i + tid] = pt[i];
   }
   __syncthreads();
   stamp(a.stamps, 1);
+  auto pvec = [&](const float* g, int at, int c) {          // four values of a parameter vector: the LDS table (OCC = 2) or global memory
+    if constexpr (OCC == 2) return *reinterpret_cast<const float4*>(ptab + at + c);
+    else return *reinterpret_cast<const float4*>(g + c);
+  };
 
   // ---- out-projection + residual, LayerNorm (lane = row; wave w: features 64 w .. 64 w + 63)
   const size_t rrow = rowg0 + min(l31, nrows - 1);
@@ -518,8 +557,10 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-        const float4 bv = *reinterpret_cast<const float4*>(S.bo + c0);
-        const u32x2 rv = *reinterpret_cast<const u32x2*>(S.R16 + rrow * 256 + c0);
+        const float4 bv = pvec(S.bo, 0, c0);
+        u32x2 rv;
+        if constexpr (OCC == 2) rv = rres[t][g];
+        else rv = *reinterpret_cast<const u32x2*>(S.R16 + rrow * 256 + c0);
         float* o = u + 16 * t + 4 * g;
         o[0] = acc[t][4 * g] + bv.x + bf_lo(rv.x); o[1] = acc[t][4 * g + 1] + bv.y + bf_hi(rv.x);
         o[2] = acc[t][4 * g + 2] + bv.z + bf_lo(rv.y); o[3] = acc[t][4 * g + 3] + bv.w + bf_hi(rv.y);
@@ -546,7 +587,7 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-        const float4 gm = *reinterpret_cast<const float4*>(S.ln_g + c0), bt = *reinterpret_cast<const float4*>(S.ln_b + c0);
+        const float4 gm = pvec(S.ln_g, 256, c0), bt = pvec(S.ln_b, 512, c0);
         float* o = u + 16 * t + 4 * g;
         const float x0 = o[0] * rstd, x1 = o[1] * rstd, x2 = o[2] * rstd, x3 = o[3] * rstd;
         const float4 y = make_float4(x0 * gm.x + bt.x, x1 * gm.y + bt.y, x2 * gm.z + bt.z, x3 * gm.w + bt.w);
@@ -583,21 +624,25 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   }
   __syncthreads();
   stamp(a.stamps, 2);
+  float ymean_keep = 0.f;
   if constexpr (OCC == 2) {   // mean pool of the LayerNorm output: thread t owns feature t
     float sum = 0.f;
     for (int r = 0; r < nrows; ++r) sum += tile32[r * PT + tid];
-    atomicAdd(S.Ymean + (size_t)b * 256 + tid, sum * inv_n);
+    ymean_keep = sum * inv_n;                                 // (added behind the FFN stream: in front of it, the stream's first counted wait sat out the atomic)
   }
 
   // ---- FFN layer 0 + ReLU + dropout, pooled over the rows (lane = feature; wave w: features 128 w .. 128 w + 127)
   {
     f32x16 acc[4] = {zero16(), zero16(), zero16(), zero16()};
     stf.run(bufY + l31 * PR + 16 * h, acc);
+    if constexpr (OCC == 2) atomicAdd(S.Ymean + (size_t)b * 256 + tid, ymean_keep);
     const bool dodrop = a.drop.p > 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int f = 128 * w + 32 * t + l31;
-      const float bias = S.b1[f];
+      float bias;
+      if constexpr (OCC == 2) bias = ptab[768 + f];
+      else bias = S.b1[f];
       float colsum = 0.f;
       uint32_t wlo = 0u, whi = 0u;
 #pragma unroll
@@ -656,7 +701,9 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
 // over the tile into the sample's rows with fp32 atomics.  KG blocks emit dO2 and the softmax row-dots delta2 = dO2 . O2 that
 // the second half needs for the KG->RG direction.
 constexpr int W_GTAB = 0, W_BUFDU = 1024, W_KS = W_BUFDU + 32 * PR, W_VS = W_KS + 16 * PK, W_BUFDO = W_VS + 16 * PK,
-              W_IMGS = W_BUFDO + 32 * PR, W_RED = W_IMGS + 16384, W_LDS = W_RED + 1024;          // 69120 bytes
+              W_IMGS = W_BUFDO + 32 * PR, W_RED = W_IMGS + 16384, W_PTAB = W_RED + 1024, W_LDS = W_PTAB + 2048;          // 71168 bytes
+// W_PTAB: the sample's pooled-gradient row d(mean Z) and the stream's gamma, fp32 [256 | 256]
+static_assert(W_VS == W_KS + 16 * PK && 32 * PR == 2 * 16 * PK, "a KG block parks its O2 rows (32 x PR) in the two idle key | value images");
 static_assert(32 * PR + 16384 == 32 * PT * 4, "the fp32 column-sum tile aliases [bufdO | images]");
 
 // One tile of the tail's weight gradients (TailWgArgs): 16 rows x 256 columns of one product, thread t = column c0 + t, all 16 rows.
@@ -782,11 +829,29 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
   st1.prefetch(reinterpret_cast<const u32x4*>(S.W1T) + (size_t)w * (32 * 2 * 64) + lane, 0);
   const size_t vrow = rowg0 + min(l31, nrows - 1);                       // this lane's row, clamped into the tile
   const bool rok = l31 < nrows;
-  // per-sample FFN gradient row -> bf16 table (what a set mask bit selects); this row's 512 mask bits
-  {
-    const float gs = inv_n * a.drop.scale;
-    for (int f = tid; f < 512; f += 256) gtab[f] = f2bf(S.dHm[(size_t)b * S.ld_dHm + f] * gs);
+  // What the epilogues read from global memory at addresses known here is loaded here, in one batch with the tile's other inputs: loaded
+  // where it is used, behind a weight stream, each was a bare round trip.  The sample's pooled-gradient row and gamma go to the LDS table;
+  // this lane's own 64 features of xhat (KG block: and of O2) to the places in the dU tile (the idle key | value images) where the same
+  // lane picks them up again, so that no register is held across the streams; rstd stays in its register.
+  float* ptab = reinterpret_cast<float*>(smem + W_PTAB);
+  const float rstd = S.rstd[vrow];
+  const float ptv0 = S.dcomb[(size_t)b * S.ld_dcomb + tid], ptv1 = S.ln_g[tid];
+  u32x2 xv[2][4], ov[2][4];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
+      xv[t][g] = *reinterpret_cast<const u32x2*>(S.XH16 + vrow * 256 + c0);
+    }
+  if (kg) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) ov[t][g] = *reinterpret_cast<const u32x2*>(a.O2_16 + vrow * 256 + 64 * w + 32 * t + 8 * g + 4 * h);
   }
+  // per-sample FFN gradient row -> bf16 table (what a set mask bit selects); this row's 512 mask bits
+  const float dh0 = S.dHm[(size_t)b * S.ld_dHm + tid], dh1 = S.dHm[(size_t)b * S.ld_dHm + 256 + tid];
   u32x4 mw[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) mw[i] = reinterpret_cast<const u32x4*>(S.mask + vrow * 16)[i];
@@ -797,14 +862,34 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
       const int id = tid + 256 * i;
       qreg[i] = *reinterpret_cast<const u32x4*>(a.Q16 + (rowg0 + min(id >> 5, nrows - 1)) * 256 + 8 * (id & 31));
     }
-    for (int c = tid; c < 16 * 64; c += 256) {                           // the sample's key | value rows, rows Nk..15 cleared
-      const int j = c >> 6, ch = c & 63;
-      u32x4 v = u32x4{0u, 0u, 0u, 0u};
-      if (j < a.Nk) v = *reinterpret_cast<const u32x4*>(a.KV16 + ((size_t)b * a.Nk + j) * 512 + 8 * ch);
+    // the sample's key | value rows, rows Nk..15 cleared: one batch of unconditional loads (row clamped, value cleared)
+    u32x4 kv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      kv[i] = *reinterpret_cast<const u32x4*>(a.KV16 + ((size_t)b * a.Nk + min(c >> 6, a.Nk - 1)) * 512 + 8 * (c & 63));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i, j = c >> 6, ch = c & 63;
+      const u32x4 v = j < a.Nk ? kv[i] : u32x4{0u, 0u, 0u, 0u};
       if (ch < 32) *reinterpret_cast<u32x4*>(Ks + j * PK + 16 * ch) = v;
       else         *reinterpret_cast<u32x4*>(Vs + j * PK + 16 * (ch - 32)) = v;
     }
   }
+  {
+    const float gs = inv_n * a.drop.scale;
+    gtab[tid] = f2bf(dh0 * gs); gtab[256 + tid] = f2bf(dh1 * gs);
+  }
+  ptab[tid] = ptv0; ptab[256 + tid] = ptv1;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
+      *reinterpret_cast<u32x2*>(bufdU + l31 * PR + 2 * c0) = xv[t][g];
+      if (kg) *reinterpret_cast<u32x2*>(Ks + l31 * PR + 2 * c0) = ov[t][g];     // (32 rows of pitch PR are exactly the two images)
+    }
   __syncthreads();
   Stage<2, 16, true, DEPTH> st2;
   f32x16 acc1[2] = {zero16(), zero16()};
@@ -822,6 +907,7 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
   st2.prefetch(reinterpret_cast<const u32x4*>(S.WoT) + (size_t)w * (16 * 2 * 64) + lane, rot);
   stamp(a.stamps, 1);
   // ---- LayerNorm backward: g = dy * gamma, du = (g - mean(g) - xhat * mean(g * xhat)) * rstd; dgamma += dy * xhat, dbeta += dy
+  float sum_g = 0.f, sum_b = 0.f;
   {
     float gg[32], xh[32];
     float s1 = 0.f, s2 = 0.f;
@@ -830,9 +916,9 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-        const float4 dc = *reinterpret_cast<const float4*>(S.dcomb + (size_t)b * S.ld_dcomb + c0);
-        const float4 gm = *reinterpret_cast<const float4*>(S.ln_g + c0);
-        const u32x2 xv = *reinterpret_cast<const u32x2*>(S.XH16 + vrow * 256 + c0);
+        const float4 dc = *reinterpret_cast<const float4*>(ptab + c0);
+        const float4 gm = *reinterpret_cast<const float4*>(ptab + 256 + c0);
+        const u32x2 xv = *reinterpret_cast<const u32x2*>(bufdU + l31 * PR + 2 * c0);      // (this lane's own: parked at block start)
         float* G = gg + 16 * t + 4 * g; float* X = xh + 16 * t + 4 * g;
         X[0] = bf_lo(xv.x); X[1] = bf_hi(xv.x); X[2] = bf_lo(xv.y); X[3] = bf_hi(xv.y);
         const float d0 = fmaf(dc.x, inv_n, acc1[t][4 * g]), d1 = fmaf(dc.y, inv_n, acc1[t][4 * g + 1]);
@@ -851,13 +937,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
     };
     const float m1 = row_total(s1, 0) * (1.0f / 256.0f);
     const float m2 = row_total(s2, 1) * (1.0f / 256.0f);
-    {   // dgamma: column sums of dy * xhat over the tile's rows (thread t owns feature t)
-      float sum = 0.f;
-      for (int r = 0; r < nrows; ++r) sum += tile32[r * PT + tid];
-      if (a.slabs & 1) a.slabLN[(size_t)blockIdx.x * 512 + tid] = sum;       // (this block's row: summed by the second half)
-      else atomicAdd(S.dgamma + tid, sum);
-    }
-    const float rstd = S.rstd[vrow];
+    // dgamma: column sums of dy * xhat over the tile's rows (thread t owns feature t); both column sums leave behind the last weight stream
+    for (int r = 0; r < nrows; ++r) sum_g += tile32[r * PT + tid];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -878,17 +959,19 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
         *reinterpret_cast<float4*>(tile32 + l31 * PT + c0) = make_float4(acc1[t][4 * g], acc1[t][4 * g + 1], acc1[t][4 * g + 2], acc1[t][4 * g + 3]);
       }
     __syncthreads();
-    {   // dbeta: column sums of dy
-      float sum = 0.f;
-      for (int r = 0; r < nrows; ++r) sum += tile32[r * PT + tid];
-      if (a.slabs & 1) a.slabLN[(size_t)blockIdx.x * 512 + 256 + tid] = sum;
-      else atomicAdd(S.dbeta + tid, sum);
-    }
+    for (int r = 0; r < nrows; ++r) sum_b += tile32[r * PT + tid];         // dbeta: column sums of dy
   }
   stamp(a.stamps, 2);
   // ---- dO^T = Wo^T-side product: lane = row, wave w: the 64 features of heads 2w, 2w+1
   f32x16 acc2[2] = {zero16(), zero16()};
   st2.run(bufdU + l31 * PR + 16 * h, acc2);
+  if (a.slabs & 1) {                                                    // (this block's row: summed by the second half)
+    a.slabLN[(size_t)blockIdx.x * 512 + tid] = sum_g;
+    a.slabLN[(size_t)blockIdx.x * 512 + 256 + tid] = sum_b;
+  } else {
+    atomicAdd(S.dgamma + tid, sum_g);
+    atomicAdd(S.dbeta + tid, sum_b);
+  }
   copy_out<5>(bufdU, PR, 0, S.dU16, 256, rowg0, nrows);         // (behind the last weight stream of the block)
   if (kg) {
     // dO2 (bf16, the second half's MFMA operand) and delta2[head][j] = sum_f dO2[j][f] * O2[j][f]
@@ -898,7 +981,7 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-        const u32x2 ov = *reinterpret_cast<const u32x2*>(a.O2_16 + vrow * 256 + c0);
+        const u32x2 ov = *reinterpret_cast<const u32x2*>(Ks + l31 * PR + 2 * c0);         // (this lane's own: parked at block start)
         dot = fmaf(acc2[t][4 * g], bf_lo(ov.x), dot); dot = fmaf(acc2[t][4 * g + 1], bf_hi(ov.x), dot);
         dot = fmaf(acc2[t][4 * g + 2], bf_lo(ov.y), dot); dot = fmaf(acc2[t][4 * g + 3], bf_hi(ov.y), dot);
         if (rok) *reinterpret_cast<u32x2*>(a.dO2_16 + (rowg0 + l31) * 256 + c0) =
@@ -1087,6 +1170,13 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     const size_t krow0 = (size_t)b * Nk;
     Stage<2, 32, true, DEPTH, false> se;
     se.prefetch(reinterpret_cast<const u32x4*>(a.WcKgT) + (size_t)w * (48 * 2 * 64) + 64 * (16 * 2) + lane, 0);
+    // this lane's dU2 row (clamped into the sample's rows): in registers from here on, so that the epilogue behind the weight stream is
+    // stores only -- loaded there, between stores it may alias for all hipcc knows, each of the eight loads was a round trip of its own
+    u32x2 du2reg[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) du2reg[t][g] = *reinterpret_cast<const u32x2*>(a.dU2_16 + (krow0 + min(l31, Nk - 1)) * 256 + 64 * w + 32 * t + 8 * g + 4 * h);
     const int t0 = a.tile_off[b], t1 = a.tile_off[b + 1];
     for (int c = tid; c < 32 * 64; c += 256) {
       const int j = c >> 6, ch = c & 63;                     // (j is uniform over a wave)
@@ -1136,7 +1226,7 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-            const u32x2 uv = *reinterpret_cast<const u32x2*>(a.dU2_16 + (krow0 + l31) * 256 + c0);
+            const u32x2 uv = du2reg[t][g];
             *reinterpret_cast<u32x2*>(dGp16 + (krow0 + l31) * 256 + c0) =
                 u32x2{pack2(acc[t][4 * g] + bf_lo(uv.x), acc[t][4 * g + 1] + bf_hi(uv.x)), pack2(acc[t][4 * g + 2] + bf_lo(uv.y), acc[t][4 * g + 3] + bf_hi(uv.y))};
           }
@@ -1151,8 +1241,8 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-          const u32x2 uv = *reinterpret_cast<const u32x2*>(a.dU2_16 + (krow0 + l31) * 256 + c0);
-          float* dst = a.dGpart + (krow0 + l31) * 256 + c0;                 // (write-through: read by another block of this launch)
+          const u32x2 uv = du2reg[t][g];
+          float* dst = a.dGpart + (krow0 + l31) * 256 + c0;               // (write-through: read by another block of this launch)
           __hip_atomic_store(dst, acc[t][4 * g] + bf_lo(uv.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(dst + 1, acc[t][4 * g + 1] + bf_hi(uv.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store(dst + 2, acc[t][4 * g + 2] + bf_lo(uv.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1169,24 +1259,32 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
   const size_t vrow = rowg0 + min(l31, nrows - 1);
   Stage<2, 48, true, DEPTH, false> sr;
   sr.prefetch(reinterpret_cast<const u32x4*>(a.WcRgT) + (size_t)w * (48 * 2 * 64) + lane, 0);
-  // per-sample inputs: the Nk pre-scaled queries, the gradient of their attention output, softmax max / 1/sum, row-dots
-  for (int c = tid; c < 16 * 32; c += 256) {
-    const int j = c >> 5, ch = c & 31;
-    u32x4 q = u32x4{0u, 0u, 0u, 0u}, o = q;
-    if (j < Nk) {
-      q = *reinterpret_cast<const u32x4*>(a.Q2_16 + ((size_t)b * Nk + j) * 256 + 8 * ch);
-      o = *reinterpret_cast<const u32x4*>(a.dO2_16 + ((size_t)b * Nk + j) * 256 + 8 * ch);
+  // per-sample inputs: the Nk pre-scaled queries, the gradient of their attention output, softmax max / 1/sum, row-dots -- every load
+  // unconditional (row clamped, value cleared), so that they all leave in one batch with the tile's own rows below
+  {
+    u32x4 q[2], o[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + 256 * i;
+      const size_t r = (size_t)b * Nk + min(c >> 5, Nk - 1);
+      q[i] = *reinterpret_cast<const u32x4*>(a.Q2_16 + r * 256 + 8 * (c & 31));
+      o[i] = *reinterpret_cast<const u32x4*>(a.dO2_16 + r * 256 + 8 * (c & 31));
     }
-    *reinterpret_cast<u32x4*>(Q2s + j * PK + 16 * ch) = q;
-    *reinterpret_cast<u32x4*>(dO2s + j * PK + 16 * ch) = o;
-  }
-  if (tid < 128) {
-    const int j = tid & 15;
-    const size_t o = (size_t)b * 128 + tid;                  // [b][head][16]
-    const bool ok = j < Nk;
-    tabs[tid] = ok ? a.lse2[2 * o] : 0.f;
-    tabs[128 + tid] = ok ? 1.0f / a.lse2[2 * o + 1] : 0.f;
-    tabs[256 + tid] = ok ? a.delta2[o] : 0.f;
+    const size_t lo = (size_t)b * 128 + (tid & 127);         // [b][head][16]
+    const float2 ml = *reinterpret_cast<const float2*>(a.lse2 + 2 * lo);
+    const float d2 = a.delta2[lo];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + 256 * i, j = c >> 5, ch = c & 31;
+      *reinterpret_cast<u32x4*>(Q2s + j * PK + 16 * ch) = j < Nk ? q[i] : u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(dO2s + j * PK + 16 * ch) = j < Nk ? o[i] : u32x4{0u, 0u, 0u, 0u};
+    }
+    if (tid < 128) {
+      const bool ok = (tid & 15) < Nk;
+      tabs[tid] = ok ? ml.x : 0.f;
+      tabs[128 + tid] = ok ? 1.0f / ml.y : 0.f;
+      tabs[256 + tid] = ok ? d2 : 0.f;
+    }
   }
   u32x4 dqreg[4];
 #pragma unroll
@@ -1196,6 +1294,13 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     *reinterpret_cast<u32x4*>(bufT + (id >> 5) * PQ + 16 * (id & 31)) = *reinterpret_cast<const u32x4*>(a.KV2_16 + r * 512 + 8 * (id & 31));
     dqreg[i] = *reinterpret_cast<const u32x4*>(a.dQKV16 + r * 768 + 8 * (id & 31));
   }
+  // this lane's dU row (the residual term of dR), clamped into the tile: in registers from here on, so that the epilogue behind the
+  // weight stream is stores only (dU16 and dR16 may alias for all hipcc knows: loaded there, every load waited for the store before it)
+  u32x2 dureg[2][4];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) dureg[t][g] = *reinterpret_cast<const u32x2*>(a.dU16 + vrow * 256 + 64 * w + 32 * t + 8 * g + 4 * h);
   bf16x8 kf[2][2], vf[2][2];
   {
     const us16* kp = a.KV2_16 + vrow * 512 + 64 * w + 8 * h;
@@ -1275,7 +1380,7 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-          const u32x2 uv = *reinterpret_cast<const u32x2*>(a.dU16 + (rowg0 + l31) * 256 + c0);
+          const u32x2 uv = dureg[t][g];
           *reinterpret_cast<u32x2*>(a.dR16 + (rowg0 + l31) * 256 + c0) =
               u32x2{pack2(acc[t][4 * g] + bf_lo(uv.x), acc[t][4 * g + 1] + bf_hi(uv.x)), pack2(acc[t][4 * g + 2] + bf_lo(uv.y), acc[t][4 * g + 3] + bf_hi(uv.y))};
         }
@@ -1321,12 +1426,17 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     sg.run(bufT + l31 * PQ + 16 * h, acc);
     copy_out<5>(bufT, PQ, 0, a.dQKVkg16, 768, krow0, Nk);
     if (l31 < Nk) {
+      float4 pvs[2][4];                                      // (every load ahead of the first store: dGpart and dG16 may alias for all hipcc knows)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pvs[t][g] = *reinterpret_cast<const float4*>(a.dGpart + (krow0 + l31) * 256 + 64 * w + 32 * t + 8 * g + 4 * h);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int c0 = 64 * w + 32 * t + 8 * g + 4 * h;
-          const float4 pv = *reinterpret_cast<const float4*>(a.dGpart + (krow0 + l31) * 256 + c0);
+          const float4 pv = pvs[t][g];
           *reinterpret_cast<u32x2*>(a.dG16 + (krow0 + l31) * 256 + c0) =
               u32x2{pack2(acc[t][4 * g] + pv.x, acc[t][4 * g + 1] + pv.y), pack2(acc[t][4 * g + 2] + pv.z, acc[t][4 * g + 3] + pv.w)};
         }
