@@ -45,6 +45,9 @@ IM_MAX_THRESHOLDS = 16              # CAMO_IM_MAX_THRESHOLDS
 IM_MAX_IDS = 1024                   # CAMO_IM_MAX_IDS
 IM_MAX_CELLS = 1 << 26              # CAMO_IM_MAX_CELLS
 IM_COUNTS = 4                       # CAMO_IM_COUNTS
+RLE_MAX_ROWS = 1 << 26              # CAMO_RLE_MAX_ROWS
+RLE_MAX_ANNOTATIONS = 65535         # CAMO_RLE_MAX_ANNOTATIONS
+RLE_MAX_COUNTS = 1 << 26            # CAMO_RLE_MAX_COUNTS
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -194,6 +197,12 @@ PROTOTYPES = {
         ("camo_guided_workspace_bytes", sz, (i32, i32, i32, i32)),
         ("camo_guided_filter", i32, (vp, vp, i64, i32, i32, i32, i32, i32, f64, i32, vp, vp, vp, sz, vp)),
         ("camo_guided_apply", i32, (vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, vp, vp)),
+    ),
+    "camo_rle.h": (
+        ("camo_rle_runs_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_rle_runs", i32, (vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
+        ("camo_rle_decode_workspace_bytes", sz, (i32, i32, i32, i32, i32)),
+        ("camo_rle_decode", i32, (vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
     ),
 }
 

@@ -1,4 +1,4 @@
-// Reductions over a label map, stated once for rg_features.hip, rg_batch.hip, rg_targets.hip, slic.hip, instances.hip and inst_match.hip
+// Reductions over a label map, stated once for rg_features.hip, rg_batch.hip, rg_targets.hip, slic.hip, instances.hip, inst_match.hip and rle.hip
 // (DESIGN.md 10k).  The kernels stay in those files with their grids, LDS arrays and side effects; these are the device-inline pieces they share:
 //
 //   label_slot           a label's slot in a tile's LDS hash table, -1 when the table is full
@@ -104,7 +104,7 @@ __device__ __forceinline__ int label_compact(int n, int* wcount, Keep keep, Each
 }
 
 // out[r] = in[0] + .. + in[r - 1] for r < n, in passes of NT with the base carried.  Every thread of ONE block of NT calls
-// (rgf_scan_kernel, rgb_scan_kernel); wsum is NT / 64 ints of LDS, written before the pass's first barrier and free after its
+// (rgf_scan_kernel, rgb_scan_kernel, rle_scan_kernel); wsum is NT / 64 ints of LDS, written before the pass's first barrier and free after its
 // second.  -> the total, which the caller stores where it wants it
 template <int NT>
 __device__ __forceinline__ int label_scan(const int* __restrict__ in, int n, int* __restrict__ out, int* wsum) {

@@ -1,8 +1,8 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances, and the
-// guided-filter refinement of a mask.
+// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances, the
+// guided-filter refinement of a mask, and COCO run-length masks out of and into label maps.
 // No device code here.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "instances.h"
 #include "inst_match.h"
 #include "guided.h"
+#include "rle.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -34,6 +35,7 @@
 #include "../../include/camo_instances.h"
 #include "../../include/camo_inst_match.h"
 #include "../../include/camo_guided.h"
+#include "../../include/camo_rle.h"
 
 using namespace camo_abi;
 
@@ -783,6 +785,57 @@ int camo_guided_apply(const float* coef, int32_t N, int32_t C, int32_t h, int32_
   if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
   CK(launch_guided_apply(coef, N, C, h, w, guide, guide_elems, out, out_elems, reinterpret_cast<const long long*>(table), max_dst_pixels,
                          clamp != 0, status, static_cast<hipStream_t>(stream)), "guided apply");
+  return 0;
+}
+
+// ---- COCO run-length masks: label maps to runs, counts to label maps (include/camo_rle.h) -------------------------
+static int rle_runs_check(int N, int H, int W, int R) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (R < 1) return fail(CAMO_E_ARG, "R must be >= 1");
+  if ((long long)N * R > CAMO_RLE_MAX_ROWS) return fail(CAMO_E_ARG, "N * R exceeds CAMO_RLE_MAX_ROWS");
+  return 0;
+}
+
+size_t camo_rle_runs_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t R) {
+  if (rle_runs_check(N, H, W, R)) return 0;
+  return rle_runs_carve(N, H, W, nullptr).bytes;
+}
+
+int camo_rle_runs(const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t R, int32_t* runs, int32_t* counts, void* ws, size_t ws_bytes,
+                  void* stream) {
+  if (int e = rle_runs_check(N, H, W, R)) return e;
+  if (!labels || !runs || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(counts)) & 3) return fail(CAMO_E_ARG, "labels and counts must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(runs) & 7) return fail(CAMO_E_ARG, "runs must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const RleRunsWs w = rle_runs_carve(N, H, W, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_rle_runs_workspace_bytes()");
+  CK(launch_rle_runs(labels, N, H, W, R, w, runs, counts, static_cast<hipStream_t>(stream)), "rle runs");
+  return 0;
+}
+
+static int rle_decode_check(int N, int H, int W, int A, int total) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (A < 1 || A > CAMO_RLE_MAX_ANNOTATIONS) return fail(CAMO_E_ARG, "A must be in [1, CAMO_RLE_MAX_ANNOTATIONS]");
+  if (total < 0 || total > CAMO_RLE_MAX_COUNTS) return fail(CAMO_E_ARG, "total must be in [0, CAMO_RLE_MAX_COUNTS]");
+  return 0;
+}
+
+size_t camo_rle_decode_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t A, int32_t total) {
+  if (rle_decode_check(N, H, W, A, total)) return 0;
+  return rle_decode_carve(total, nullptr).bytes;
+}
+
+int camo_rle_decode(const int32_t* cnts, int32_t total, const int32_t* ann_off, const int32_t* ann_image, const int32_t* ann_value, int32_t A,
+                    int32_t N, int32_t H, int32_t W, int32_t* labels, int64_t* ann_sum, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = rle_decode_check(N, H, W, A, total)) return e;
+  if ((!cnts && total > 0) || !ann_off || !ann_image || !ann_value || !labels || !ann_sum || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(ann_sum) & 7) return fail(CAMO_E_ARG, "ann_sum must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const RleDecodeWs w = rle_decode_carve(total, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_rle_decode_workspace_bytes()");
+  CK(launch_rle_decode(cnts, total, ann_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_sum),
+                       static_cast<hipStream_t>(stream)), "rle decode");
   return 0;
 }
 }  // extern "C"

@@ -190,19 +190,25 @@ def instance_match_records(out):
 
 def match_options(match, instances=True, have_masks=True):
     """The pipeline's ``match`` keyword -- ``None`` (off), ``True`` or a dict with any of "thresholds" (COCO), "gt_labels" (int32
-    ground-truth ids; default: the connected components of the ground-truth mask) and "max_gt" (64) -- as a dict with all three, or
-    ``None``; the ``ValueError`` of a bad one by name, before anything touches the device."""
+    ground-truth ids; default: the connected components of the ground-truth mask), "gt_rles" (the ground-truth ids as COCO RLEs per
+    image, ``rle.decode_rles``' argument; not together with "gt_labels") and "max_gt" (64) -- as a dict with all four, or ``None``;
+    the ``ValueError`` of a bad one by name, before anything touches the device."""
     if match is None or match is False:
         return None
     if match is True:
         match = {}
-    if not isinstance(match, dict) or set(match) - {"thresholds", "gt_labels", "max_gt"}:
-        raise ValueError(f'match must be None, True or a dict with any of "thresholds", "gt_labels", "max_gt", got {match!r}')
+    if not isinstance(match, dict) or set(match) - {"thresholds", "gt_labels", "gt_rles", "max_gt"}:
+        raise ValueError(f'match must be None, True or a dict with any of "thresholds", "gt_labels", "gt_rles", "max_gt", got {match!r}')
     if not instances:
         raise ValueError("match needs instances=True: the predicted instances are what it matches")
-    opts = {"thresholds": match.get("thresholds", COCO), "gt_labels": match.get("gt_labels"), "max_gt": match.get("max_gt", 64)}
-    if opts["gt_labels"] is None and not have_masks:
-        raise ValueError('match needs ground truth: gt_masks, or match["gt_labels"]')
+    opts = {"thresholds": match.get("thresholds", COCO), "gt_labels": match.get("gt_labels"), "gt_rles": match.get("gt_rles"),
+            "max_gt": match.get("max_gt", 64)}
+    if opts["gt_labels"] is not None and opts["gt_rles"] is not None:
+        raise ValueError('match takes "gt_labels" or "gt_rles", not both')
+    if opts["gt_rles"] is not None and (not isinstance(opts["gt_rles"], (list, tuple)) or not opts["gt_rles"]):
+        raise ValueError('match["gt_rles"] must be a non-empty list with one list of RLEs per image')
+    if opts["gt_labels"] is None and opts["gt_rles"] is None and not have_masks:
+        raise ValueError('match needs ground truth: gt_masks, match["gt_labels"] or match["gt_rles"]')
     match_thresholds(opts["thresholds"])
     _id_bound(opts["max_gt"], 'match["max_gt"]')
     return opts

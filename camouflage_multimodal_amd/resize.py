@@ -10,13 +10,14 @@ integer arithmetic; tests/resize_ref.py restates it).  There is no CPU path: ten
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, instance_match as _match, instances as _instances, refine as _refine, seg_measures
+from . import _lib, instance_match as _match, instances as _instances, refine as _refine, rle as _rle, seg_measures
 from .engine import _ptr, _stream_ptr
 from .rg_detect import detect_camouflage_batch, segmentation_counts, segmentation_metrics
 from .rg_finetune import prepare_finetune_batch
@@ -348,6 +349,32 @@ def _native_matches(labels, tables, gt_labels, opts):
     return rec, out
 
 
+def _native_rles(labels):
+    """``rle.encode_instances`` of every int32 [H_i, W_i] label map; maps of equal size share a call."""
+    groups = {}
+    for i, m in enumerate(labels):
+        groups.setdefault(tuple(m.shape), []).append(i)
+    out = [None] * len(labels)
+    for idx in groups.values():
+        enc = _rle.encode_instances(torch.stack([labels[i] for i in idx]))
+        for j, i in enumerate(idx):
+            out[i] = enc[j]
+    return out
+
+
+def _native_rle_labels(gt_rles, sizes, device):
+    """``rle.decode_rles`` of every image's ground-truth RLEs at the image's own size; images of equal size share a call."""
+    groups = {}
+    for i, size in enumerate(sizes):
+        groups.setdefault(tuple(size), []).append(i)
+    out = [None] * len(sizes)
+    for (H, W), idx in groups.items():
+        lab = _rle.decode_rles([gt_rles[i] for i in idx], H, W, device, image_numbers=idx)
+        for j, i in enumerate(idx):
+            out[i] = lab[j]
+    return out
+
+
 def _native_gt_labels(masks, connectivity, max_gt):
     """``instance_match.ground_truth_labels`` of every [H_i, W_i] mask; masks of equal size share a call."""
     groups = {}
@@ -364,7 +391,7 @@ def _native_gt_labels(masks, connectivity, max_gt):
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
                              cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None,
-                             *, match=None):
+                             *, match=None, rle=False):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -384,9 +411,13 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     ``match`` (``detect_camouflage_batch``'s; "gt_labels" is a list of int32 [H_i, W_i] maps) matches the NATIVE-size instances to
     the ground-truth ones -- by default the connected components of every native mask, which needs ``gt_masks`` scored at native
     size; images of equal size share a call -- and adds "instance_match" (per image the records) and "instance_match_tables" (per
-    image ``match_instances``' dict of its own rows).  ``None``: nothing changes."""
+    image ``match_instances``' dict of its own rows).  ``None``: nothing changes.  "gt_rles" in ``match`` holds per image the COCO RLEs of
+    its ground-truth instances at the image's NATIVE size (``rle.decode_rles``; images of equal size share a call).
+    ``rle=True`` (needs ``instances=True``) adds "instance_rles_native": per image {id: RLE} of "instance_labels_native"
+    (``rle.encode_instances``; maps of equal size share a call)."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
+    rle = _rle.rle_options(rle, instances)
     match = _match.match_options(match, instances, gt_masks is not None and evaluate_at == "native")
     refine = _refine.refine_options(refine)
     if refine is not None and refine["guide"] != "rgb":
@@ -421,11 +452,17 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
             out["clean_metrics"], _ = _score([c.float() for c in clean], [masks.image(i) for i in range(len(sizes))], 0.5, False)
         if match is not None:
             gt_labels = match["gt_labels"]
-            if gt_labels is None:
+            if match["gt_rles"] is not None:
+                if len(match["gt_rles"]) != len(sizes):
+                    raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {len(sizes)} images')
+                gt_labels = _native_rle_labels(match["gt_rles"], sizes, img.device)
+            elif gt_labels is None:
                 gt_labels = _native_gt_labels([masks.image(i) for i in range(len(sizes))], connectivity, match["max_gt"])
             elif len(gt_labels) != len(sizes):
                 raise ValueError(f'match["gt_labels"] holds {len(gt_labels)} maps for {len(sizes)} images')
             out["instance_match"], out["instance_match_tables"] = _native_matches(labels, tables, gt_labels, match)
+        if rle:
+            out["instance_rles_native"] = _native_rles(labels)
     if refine is not None:
         refined, _ = _refine.guided_upsample(out["refine_coefficients"], packed)
         out["prob_maps_native_refined"] = refined
@@ -474,7 +511,7 @@ def _files_by_stem(folder):
     return {os.path.splitext(f)[0]: os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith(IMAGE_SUFFIXES)}
 
 
-def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None, batch_size=16, **kw):
+def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None, batch_size=16, results_json=None, image_ids=None, **kw):
     """``detect_camouflage_ragged`` over the image files of ``image_dir`` (read with PIL, in sorted order, ``batch_size`` at a time;
     ``**kw`` goes to it).  With ``mask_dir`` every image needs a mask file of the same stem.  With ``out_dir`` every native-size mask
     probability is written there as ``<stem>.png``, 8 bits, quantised as include/camo_seg_measures.h quantises (``quantise_map``).
@@ -485,10 +522,23 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     With ``match`` (``detect_camouflage_ragged``'s; needs ``instances=True`` and ``mask_dir``, or "gt_labels" for every file in
     sorted order) the native-size instances of every file are matched to the ground-truth ones and the result also holds
     "instance_match" (per-file records) and "instance_ap": ``instance_match.InstanceAP`` over all files, scored by every instance's
-    mean probability."""
+    mean probability.  "gt_rles" in ``match`` holds the RLE lists of every file in sorted order, as "gt_labels" does.
+    ``results_json`` (a path; needs ``instances=True``) writes the native-size instances of every file as a COCO results list: per
+    instance {"image_id": the stem, or ``image_ids[stem]``, "category_id": 1, "segmentation": {"size", "counts"} (include/camo_rle.h),
+    "score": the instance's Sq / (255 area), "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1]}; the result also holds "results": that list."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
     match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None)
+    if results_json is not None:
+        if not isinstance(results_json, (str, os.PathLike)):
+            raise ValueError(f"results_json must be a path, got {results_json!r}")
+        if not kw.get("instances", False):
+            raise ValueError("results_json needs instances=True: the instances are what it writes")
+        kw["rle"] = True
+    elif image_ids is not None:
+        raise ValueError("image_ids needs results_json")
+    if image_ids is not None and not isinstance(image_ids, dict):
+        raise ValueError(f"image_ids must be a dict from file stem to image id, got {type(image_ids).__name__}")
     cod = bool(kw.pop("cod_metrics", False))
     evaluate_at = kw.pop("evaluate_at", "native")
     threshold = kw.get("threshold", 0.5)
@@ -509,20 +559,30 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     matched, ap = [], _match.InstanceAP()
     if match is not None and match["gt_labels"] is not None and len(match["gt_labels"]) != len(stems):
         raise ValueError(f'match["gt_labels"] holds {len(match["gt_labels"])} maps for {len(stems)} files')
+    if match is not None and match["gt_rles"] is not None and len(match["gt_rles"]) != len(stems):
+        raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {len(stems)} files')
+    if image_ids is not None and set(stems) - set(image_ids):
+        raise ValueError(f"image_ids has no entry for {sorted(set(stems) - set(image_ids))[:5]}")
+    results = []
     for at in range(0, len(stems), int(batch_size)):
         part = stems[at:at + int(batch_size)]
         arrays = [np.array(Image.open(images[s]).convert("RGB")) for s in part]
         gts = None
         if masks is not None:
             gts = _mask_list([np.array(Image.open(masks[s]).convert("L")) for s in part], len(part), "masks", _device(kw.get("device", "cuda")))
-        if match is not None:
+        if match is not None and match["gt_rles"] is not None:
+            out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, gt_rles=match["gt_rles"][at:at + len(part)]), **kw)
+        elif match is not None:
             gt_labels = match["gt_labels"][at:at + len(part)] if match["gt_labels"] is not None else \
                 _native_gt_labels([gts.image(i) for i in range(len(part))], kw.get("connectivity", 8), match["max_gt"])
             out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, gt_labels=gt_labels), **kw)
-            matched += out["instance_match"]
-            ap.add(out["instance_match"], [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]])
         else:
             out = detect_camouflage_ragged(rg_model, arrays, **kw)
+        if match is not None:
+            matched += out["instance_match"]
+            ap.add(out["instance_match"], [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]])
+        if results_json is not None:
+            results += _rle.coco_results(part, out["instances_native"], out["instance_rles_native"], image_ids)
         native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
         if out_dir is not None:
             for s, p in zip(part, native):
@@ -542,4 +602,8 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
             result["cod_metrics"] = [{k: v for k, v in c.items() if k not in ("f_curve", "e_curve")} for c in cods]
     if match is not None:
         result["instance_match"], result["instance_ap"] = matched, ap.result()
+    if results_json is not None:
+        with open(results_json, "w") as f:
+            json.dump(results, f)
+        result["results"] = results
     return result

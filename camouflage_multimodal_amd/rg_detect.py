@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, instance_match as _match, instances as _instances, refine as _refine, seg_measures
+from . import _lib, instance_match as _match, instances as _instances, refine as _refine, rle as _rle, seg_measures
 from .engine import _ptr, _stream_ptr
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 
@@ -122,7 +122,7 @@ def segmentation_metrics(counts, H, W):
 
 @torch.no_grad()
 def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
-                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None):
+                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -146,9 +146,14 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     "gt_labels" (int32 [N, H, W] ground-truth ids; default: the connected components of ``gt_masks`` with ``connectivity``) and
     "max_gt" (64) -- needs ``instances=True`` and ``gt_masks`` or "gt_labels"; it matches the instances to the ground-truth ones
     (``instance_match.match_detected``, include/camo_inst_match.h) and adds "instance_match" (per image the records of
-    ``instance_match_records``) and "instance_match_tables" (``match_instances``' dict).  Every other key keeps its bytes."""
+    ``instance_match_records``) and "instance_match_tables" (``match_instances``' dict).  Every other key keeps its bytes.
+    "gt_rles" in ``match`` -- per image a list of COCO RLE dicts or (rle, id) pairs -- gives the ground-truth ids in the place of
+    "gt_labels" (both together raise): ``rle.decode_rles`` paints them on the device (include/camo_rle.h).
+    ``rle=True`` (needs ``instances=True``) adds "instance_rles": per image {id: {"size": [H, W], "counts": str}}, the COCO run-length
+    encoding of every instance of "instance_labels" (``rle.encode_instances``); ``False``: no launch more than before."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
+    rle = _rle.rle_options(rle, instances)
     match = _match.match_options(match, instances, gt_masks is not None)
     refine = _refine.refine_options(refine)
     img, _ = _image_batch(_as_tensor(images, device))
@@ -179,8 +184,15 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
         if gt is not None:
             out["clean_metrics"] = segmentation_metrics(segmentation_counts(found["clean_mask"].float(), gt, 0.5), H, W)
         if match is not None:
-            gt_labels = match["gt_labels"] if match["gt_labels"] is not None else _match.ground_truth_labels(gt, connectivity, match["max_gt"])
+            if match["gt_rles"] is not None:
+                if len(match["gt_rles"]) != N:
+                    raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {N} images')
+                gt_labels = _rle.decode_rles(match["gt_rles"], H, W, img.device)
+            else:
+                gt_labels = match["gt_labels"] if match["gt_labels"] is not None else _match.ground_truth_labels(gt, connectivity, match["max_gt"])
             out["instance_match"], out["instance_match_tables"] = _match.match_detected(found["labels"], found["table"], gt_labels, match)
+        if rle:
+            out["instance_rles"] = _rle.encode_instances(found["labels"])
     if refine is not None:
         guide = img if refine["guide"] == "rgb" else _refine.luma(img)
         q, coef = _refine.guided_filter(guide, prob_maps[:, 0], refine["radius"], refine["eps"], True, True)
@@ -193,11 +205,11 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
 
 
 def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
-                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None):
+                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
     return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
-                                   connectivity, refine, match=match)
+                                   connectivity, refine, match=match, rle=rle)
