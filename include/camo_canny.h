@@ -38,11 +38,13 @@ extern "C" {
 size_t camo_canny_workspace_bytes(int32_t N, int32_t H, int32_t W);
 
 /* images [N, H, W, 3] fp32 in [0, 1] -> edges [N, H, W] (0 / 1); grad, when not NULL, receives [N, 3, H, W] = gi, gj, m.
- * Needs N, H, W >= 1, sigma > 0, 0 < low <= high. */
+ * Needs N, H, W >= 1, sigma > 0, 0 < low <= high.  What workspace, edges and grad hold on entry is unspecified; every element of
+ * edges, and of grad when it is given, is written. */
 int camo_canny(const float* images, int32_t N, int32_t H, int32_t W, float sigma, float low, float high, void* workspace,
                size_t workspace_bytes, uint8_t* edges, float* grad, void* stream);
 
-/* Step 5 alone, as camo_canny runs it: cls [N, H, W] with 0 none, 1 weak, 2 strong -> edges [N, H, W] (0 / 1).  Same workspace. */
+/* Step 5 alone, as camo_canny runs it: cls [N, H, W] with 0 none, 1 weak, 2 strong -> edges [N, H, W] (0 / 1).  Same workspace.
+ * What workspace and edges hold on entry is unspecified; every element of edges is written. */
 int camo_canny_hysteresis(const uint8_t* cls, int32_t N, int32_t H, int32_t W, void* workspace, size_t workspace_bytes,
                           uint8_t* edges, void* stream);
 

@@ -64,6 +64,7 @@ size_t camo_guided_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
  * Needs 1 <= N <= CAMO_RGD_MAX_IMAGES, H, W in [1, CAMO_RSZ_MAX_SIDE], H * W <= CAMO_RGD_MAX_IMAGE_PIXELS, N * H * W <=
  * CAMO_RGD_MAX_PIXELS, C 1 or 3, radius, eps (not NaN) and clamp in the ranges above, p_image_stride >= H * W, non-null guide, p,
  * q, ws (fp32 pointers 4-byte aligned, ws 256-byte aligned), ws_bytes at least the workspace size: otherwise CAMO_E_ARG.
+ * What ws, q and coef hold on entry is unspecified; every element of q, and of coef when it is given, is written.
  *
  * LAUNCHES: row sums of the 4 / 13 planes; their column sums and the solve (a, b to the workspace); row sums of a, b; their column
  * sums and the output.  One thread per pixel in each, 256 threads a block, lanes along a row. */

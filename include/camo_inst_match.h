@@ -61,6 +61,8 @@ size_t camo_inst_match_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t 
  * Needs camo_instances' limits on N, H and W, 1 <= P, G <= CAMO_IM_MAX_IDS, N (P + 1) (G + 1) <= CAMO_IM_MAX_CELLS, the thresholds
  * as in 4, pred_table_rows >= 1 when pred_table is given and the table 8-byte aligned, no other null pointer, ws 256-byte aligned
  * and ws_bytes at least the workspace size: otherwise CAMO_E_ARG.
+ * What ws and the six outputs hold on entry is unspecified; every element of inter, pred_rows, gt_area, match, gt_match and counts
+ * is written.
  *
  * The overlap launch is the only pixel-rate pass: a block takes 1024 consecutive pixels of one image, a run of consecutive lanes
  * with the same pair is one record (its length), a record goes to the pair's slot of a small LDS table (to memory when every slot

@@ -52,6 +52,7 @@ size_t camo_instances_workspace_bytes(int32_t N, int32_t H, int32_t W);
  * Needs 1 <= N <= CAMO_RGD_MAX_IMAGES, H, W >= 1, H * W <= CAMO_RGD_MAX_IMAGE_PIXELS, N * H * W <= CAMO_RGD_MAX_PIXELS,
  * connectivity 4 or 8, min_area >= 0, 1 <= max_instances, N * max_instances <= CAMO_INST_MAX_ROWS, pred_image_stride >= H * W, a finite
  * threshold, no null pointer, table 8-byte aligned, ws 256-byte aligned and ws_bytes at least the workspace size: otherwise CAMO_E_ARG.
+ * What ws and the four outputs hold on entry is unspecified; every element of labels, clean, table and counts is written.
  *
  * 32 x 32 tiles are labelled in LDS by union-find, tile borders joined with agent-scope atomicMin on the larger root (parents only
  * decrease: the root is the smallest index whatever the order), never across an image's edge.  The statistics combine runs of equal

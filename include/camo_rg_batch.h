@@ -65,7 +65,10 @@ size_t camo_rg_batch_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t la
  * batch has more than edge_capacity directed edges, edge_off / status[1] still report what is needed and nothing is written
  * beyond the capacity.  Position features divide by 256 and the size feature by 256^2 whatever H and W are, as the
  * reference does.  Refused: N < 1 or > CAMO_RGB_MAX_IMAGES, H * W > CAMO_RGB_MAX_IMAGE_PIXELS, N * H * W > CAMO_RGB_MAX_PIXELS,
- * label_bound out of range, node_capacity < N * label_bound, edge_capacity < 2, a workspace smaller than the query's. */
+ * label_bound out of range, node_capacity < N * label_bound, edge_capacity < 2, a workspace smaller than the query's.
+ * What workspace and the outputs hold on entry is unspecified.  Every element of region_map, node_off, edge_off and status is
+ * written, the first node_off[N] rows of x and batch and the first min(edge_off[N], edge_capacity) columns of edge_index and
+ * edge_attr; what lies past them is not. */
 int camo_rg_region_graph_batch(const float* images, const int32_t* segments, const uint8_t* canny, int32_t N, int32_t H, int32_t W,
                                int32_t label_bound, void* workspace, size_t workspace_bytes, float* x, int32_t node_capacity,
                                int32_t* region_map, int64_t* edge_index, float* edge_attr, int32_t edge_capacity, int32_t* node_off,

@@ -82,7 +82,7 @@ int camo_rg_paint(const float* values, int32_t n_nodes, int32_t C, const int32_t
  *   precision = TP / (TP + FP), recall = TP / (TP + FN), F1 = 2 P R / (P + R): 0 when the denominator is 0;
  *   accuracy = (TP + TN) / (H W), MAE = A / 2^32 / (H W).
  * Needs N, H, W >= 1, N <= CAMO_RGD_MAX_IMAGES, H * W <= CAMO_RGD_MAX_IMAGE_PIXELS, pred_image_stride >= H * W, a threshold that is not NaN: otherwise
- * CAMO_E_ARG. */
+ * CAMO_E_ARG.  What counts holds on entry is unspecified; every element of it is written. */
 int camo_seg_counts(const float* pred, int64_t pred_image_stride, const uint8_t* gt, float threshold, int32_t N, int32_t H, int32_t W,
                     int64_t* counts, void* stream);
 

@@ -46,7 +46,9 @@ size_t camo_rg_graph_workspace_bytes(int32_t n_labels);
  * edge_index [2, edge_capacity] int64 (row 0 sources, row 1 targets; first counts[1] columns valid), edge_attr
  * [edge_capacity], counts [2] = {regions kept, directed edges}.  When the graph has more than edge_capacity directed
  * edges, counts[1] still reports the number needed and nothing is written beyond the capacity.  The position features
- * divide by 256 and the size feature by 256^2 whatever H and W are, as the reference does (its images are 256 x 256). */
+ * divide by 256 and the size feature by 256^2 whatever H and W are, as the reference does (its images are 256 x 256).
+ * What workspace and the outputs hold on entry is unspecified.  Every element of region_map and counts is written, the first
+ * counts[0] rows of x and the first min(counts[1], edge_capacity) columns of edge_index and edge_attr; what lies past them is not. */
 int camo_rg_region_graph(const float* image, const int32_t* segments, const uint8_t* canny, int32_t H, int32_t W,
                          int32_t n_labels, void* workspace, size_t workspace_bytes, float* x, int32_t* region_map,
                          int64_t* edge_index, float* edge_attr, int32_t edge_capacity, int32_t* counts, void* stream);

@@ -51,6 +51,7 @@ extern "C" {
  * band = 0 is strict majority: a tie gives 0 and no node with pixels is ignored.
  *   edge_t[v] = 1.0f when counts[v][3] >= edge_min_pixels, else 0.0f.
  * A node with pix == 0 gets mask_t = inst_t = -1 and edge_t = -1.0f.  Rows v >= n_nodes of the four outputs are not touched.
+ * What counts and the three target arrays hold on entry is unspecified; rows 0 .. n_nodes - 1 of all four are written.
  *
  * Every sum is an integer: 32-bit integer LDS atomics per (tile, node), then one 32-bit integer global atomic per (tile, node,
  * non-zero quantity); no floating-point atomic is on the path.  The outputs are functions of the inputs alone: two calls give the

@@ -42,6 +42,7 @@ size_t camo_rle_runs_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t R)
  *   3. Rows past min(M, R) are zero: the call writes the whole array.
  * Needs camo_instances' limits on N, H and W, 1 <= R, N * R <= CAMO_RLE_MAX_ROWS, no null pointer, labels and counts 4-byte and runs
  * 8-byte aligned, ws 256-byte aligned and ws_bytes at least the workspace size: otherwise CAMO_E_ARG.
+ * What ws, runs and counts hold on entry is unspecified; every element of runs and counts is written.
  *
  * The label map is row-major and the order is column-major, so the pixel pass is a transposition: a block loads a 64 x 64 tile and
  * the row above it with lanes along x, and reads it back from LDS with lanes along y.  A position is a head when p == 0 or its label
@@ -71,6 +72,7 @@ size_t camo_rle_decode_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t 
  * Needs camo_instances' limits on N, H and W, 1 <= A <= CAMO_RLE_MAX_ANNOTATIONS, 0 <= total <= CAMO_RLE_MAX_COUNTS, no null pointer
  * (cnts may be null when total == 0), ann_sum 8-byte aligned, ws 256-byte aligned and ws_bytes at least the workspace size: otherwise
  * CAMO_E_ARG.
+ * What ws, labels and ann_sum hold on entry is unspecified; every element of labels and ann_sum is written.
  *
  * The first launch clears labels and, one block per annotation, writes the start position of every run (the exclusive prefix of
  * the counts, taken in 64 bits and clamped to H W) into the workspace with ann_sum and the verdict of 4.  The second is the

@@ -55,6 +55,7 @@ extern "C" {
  * 32-bit INTEGER atomics: no floating-point atomic is on the path.
  * Needs N >= 1, N <= CAMO_RGD_MAX_IMAGES, H, W >= 1, 2 <= H * W <= CAMO_RGD_MAX_IMAGE_PIXELS (so every count fits int32),
  * pred_image_stride >= H * W: otherwise CAMO_E_ARG.
+ * What hist and split hold on entry is unspecified; every element of both is written.
  *
  * The measures are not part of the ABI; the Python surface computes them from the table with these conventions, every decision
  * ("is this sum zero") taken on the exact integers and never on a rounded float.  Per image, with h[g][q] = the table summed over
@@ -106,7 +107,7 @@ size_t camo_seg_weighted_f_workspace_bytes(int32_t N, int32_t H, int32_t W);
  * The host ratio, with a = A / 2^32: TPw = n_fg - a_fg, R = 1 - a_fg / n_fg, P = TPw / (TPw + a_bg + eps),
  *   F-beta-w = 2 R P / (R + P + eps), and 0 when n_fg = 0.
  * Needs N >= 1, N <= CAMO_RGD_MAX_IMAGES, 1 <= H, W <= CAMO_SEG_WF_MAX_SIDE, H * W >= 2, pred_image_stride >= H * W, ws_bytes at
- * least the workspace size: otherwise CAMO_E_ARG. */
+ * least the workspace size: otherwise CAMO_E_ARG.  What ws and sums hold on entry is unspecified; every element of sums is written. */
 int camo_seg_weighted_f(const float* pred, int64_t pred_image_stride, const uint8_t* gt, int32_t N, int32_t H, int32_t W,
                         const double* gauss, void* ws, size_t ws_bytes, int64_t* sums, void* stream);
 

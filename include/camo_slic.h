@@ -71,7 +71,8 @@ int camo_slic_grid(int32_t H, int32_t W, int32_t n_segments, int32_t* out);
 size_t camo_slic_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t n_segments);
 
 /* images [N, H, W, 3] fp32 in [0, 1] -> labels [N, H, W] int32 and counts [N, 2] = {largest label + 1, components of max_size
- * pixels or more}.  Needs compactness >= CAMO_SLIC_MIN_COMPACTNESS and sigma >= 0. */
+ * pixels or more}.  Needs compactness >= CAMO_SLIC_MIN_COMPACTNESS and sigma >= 0.  What workspace, labels and counts hold on entry
+ * is unspecified; every element of labels and counts is written. */
 int camo_slic(const float* images, int32_t N, int32_t H, int32_t W, int32_t n_segments, float compactness, float sigma,
               void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* counts, void* stream);
 
@@ -84,12 +85,14 @@ int camo_slic_assign(const float* lab, const float* centroids, int32_t N, int32_
                      int32_t* nearest, float* dist, void* stream);
 
 /* Step 6: centroids [N, K, 5] updated in place from lab and nearest (entries outside [0, K) are ignored).  sums: scratch of
- * N * K * 6 int64.  Three launches (camo_slic clears the sums once and lets each update leave them cleared: two). */
+ * N * K * 6 int64.  Three launches (camo_slic clears the sums once and lets each update leave them cleared: two).  What sums hold
+ * on entry is unspecified and what they hold on return is not promised; every centroid that has a pixel is written. */
 int camo_slic_update(const float* lab, const int32_t* nearest, int32_t N, int32_t H, int32_t W, int32_t K, int64_t* sums,
                      float* centroids, void* stream);
 
 /* Step 8 for any label map: labels_in [N, H, W] -> labels [N, H, W], counts [N, 2] as above.  Needs min_size >= 0, max_size >= 1
- * and a workspace of camo_slic_workspace_bytes(N, H, W, 0).  Seven launches. */
+ * and a workspace of camo_slic_workspace_bytes(N, H, W, 0).  Seven launches.  What workspace, labels and counts hold on entry is
+ * unspecified; every element of labels and counts is written. */
 int camo_slic_connect(const int32_t* labels_in, int32_t N, int32_t H, int32_t W, int32_t min_size, int32_t max_size,
                       void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* counts, void* stream);
 
