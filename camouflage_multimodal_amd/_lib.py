@@ -48,6 +48,11 @@ IM_COUNTS = 4                       # CAMO_IM_COUNTS
 RLE_MAX_ROWS = 1 << 26              # CAMO_RLE_MAX_ROWS
 RLE_MAX_ANNOTATIONS = 65535         # CAMO_RLE_MAX_ANNOTATIONS
 RLE_MAX_COUNTS = 1 << 26            # CAMO_RLE_MAX_COUNTS
+POLY_MAX_ANNOTATIONS = 65535        # CAMO_POLY_MAX_ANNOTATIONS
+POLY_MAX_POLYGONS = 65535           # CAMO_POLY_MAX_POLYGONS
+POLY_MAX_VERTICES = 1 << 20         # CAMO_POLY_MAX_VERTICES
+POLY_MARGIN = 1024                  # CAMO_POLY_MARGIN
+POLY_MAX_PLANE_WORDS = 1 << 28      # CAMO_POLY_MAX_PLANE_WORDS
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -203,6 +208,10 @@ PROTOTYPES = {
         ("camo_rle_runs", i32, (vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
         ("camo_rle_decode_workspace_bytes", sz, (i32, i32, i32, i32, i32)),
         ("camo_rle_decode", i32, (vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
+    ),
+    "camo_poly.h": (
+        ("camo_poly_decode_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
+        ("camo_poly_decode", i32, (vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
     ),
 }
 

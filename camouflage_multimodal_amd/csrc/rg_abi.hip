@@ -22,6 +22,7 @@
 #include "inst_match.h"
 #include "guided.h"
 #include "rle.h"
+#include "poly.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -36,6 +37,7 @@
 #include "../../include/camo_inst_match.h"
 #include "../../include/camo_guided.h"
 #include "../../include/camo_rle.h"
+#include "../../include/camo_poly.h"
 
 using namespace camo_abi;
 
@@ -836,6 +838,35 @@ int camo_rle_decode(const int32_t* cnts, int32_t total, const int32_t* ann_off, 
   if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_rle_decode_workspace_bytes()");
   CK(launch_rle_decode(cnts, total, ann_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_sum),
                        static_cast<hipStream_t>(stream)), "rle decode");
+  return 0;
+}
+
+// ---- COCO polygon annotations to label maps (include/camo_poly.h) --------------------------------------------------
+static int poly_check(int N, int H, int W, int A, int P, int V) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (A < 1 || A > CAMO_POLY_MAX_ANNOTATIONS) return fail(CAMO_E_ARG, "A must be in [1, CAMO_POLY_MAX_ANNOTATIONS]");
+  if (P < 0 || P > CAMO_POLY_MAX_POLYGONS) return fail(CAMO_E_ARG, "P must be in [0, CAMO_POLY_MAX_POLYGONS]");
+  if (V < 0 || V > CAMO_POLY_MAX_VERTICES) return fail(CAMO_E_ARG, "V must be in [0, CAMO_POLY_MAX_VERTICES]");
+  if ((long long)P * (((long long)H * W + 31) / 32) > CAMO_POLY_MAX_PLANE_WORDS) return fail(CAMO_E_ARG, "P * ceil(H W / 32) exceeds CAMO_POLY_MAX_PLANE_WORDS");
+  return 0;
+}
+
+size_t camo_poly_decode_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t A, int32_t P, int32_t V) {
+  if (poly_check(N, H, W, A, P, V)) return 0;
+  return poly_carve(H, W, A, P, nullptr).bytes;
+}
+
+int camo_poly_decode(const double* xy, int32_t V, const int32_t* poly_off, int32_t P, const int32_t* ann_poly_off, const int32_t* ann_image,
+                     const int32_t* ann_value, int32_t A, int32_t N, int32_t H, int32_t W, int32_t* labels, int64_t* ann_area, void* ws, size_t ws_bytes,
+                     void* stream) {
+  if (int e = poly_check(N, H, W, A, P, V)) return e;
+  if ((!xy && V > 0) || !poly_off || !ann_poly_off || !ann_image || !ann_value || !labels || !ann_area || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if ((reinterpret_cast<uintptr_t>(xy) | reinterpret_cast<uintptr_t>(ann_area)) & 7) return fail(CAMO_E_ARG, "xy and ann_area must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const PolyWs w = poly_carve(H, W, A, P, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_poly_decode_workspace_bytes()");
+  CK(launch_poly_decode(xy, V, poly_off, P, ann_poly_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_area),
+                        static_cast<hipStream_t>(stream)), "poly decode");
   return 0;
 }
 }  // extern "C"

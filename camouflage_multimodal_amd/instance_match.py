@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
+import os
 from fractions import Fraction
 
 import torch
@@ -188,26 +189,41 @@ def instance_match_records(out):
     return records
 
 
-def match_options(match, instances=True, have_masks=True):
+def match_options(match, instances=True, have_masks=True, coco=False):
     """The pipeline's ``match`` keyword -- ``None`` (off), ``True`` or a dict with any of "thresholds" (COCO), "gt_labels" (int32
     ground-truth ids; default: the connected components of the ground-truth mask), "gt_rles" (the ground-truth ids as COCO RLEs per
-    image, ``rle.decode_rles``' argument; not together with "gt_labels") and "max_gt" (64) -- as a dict with all four, or ``None``;
-    the ``ValueError`` of a bad one by name, before anything touches the device."""
+    image, ``rle.decode_rles``' argument; not together with "gt_labels"), "gt_segmentations" (per image a list of COCO
+    ``segmentation`` fields, polygons or RLEs, or (segmentation, id) pairs: ``polygons.decode_segmentations``' argument; not together
+    with either) and "max_gt" (64) -- as a dict with all five, or ``None``; the ``ValueError`` of a bad one by name, before anything
+    touches the device.  ``coco=True`` (``detect_camouflage_directory``) also takes "gt_coco", a COCO annotations file, in the place of
+    the other three."""
     if match is None or match is False:
         return None
     if match is True:
         match = {}
-    if not isinstance(match, dict) or set(match) - {"thresholds", "gt_labels", "gt_rles", "max_gt"}:
-        raise ValueError(f'match must be None, True or a dict with any of "thresholds", "gt_labels", "gt_rles", "max_gt", got {match!r}')
+    known = {"thresholds", "gt_labels", "gt_rles", "max_gt", "gt_segmentations"} | ({"gt_coco"} if coco else set())
+    if not isinstance(match, dict) or set(match) - known:
+        raise ValueError('match must be None, True or a dict with any of "thresholds", "gt_labels", "gt_rles", "max_gt", "gt_segmentations"'
+                         + (', "gt_coco"' if coco else "") + f", got {match!r}")
     if not instances:
         raise ValueError("match needs instances=True: the predicted instances are what it matches")
     opts = {"thresholds": match.get("thresholds", COCO), "gt_labels": match.get("gt_labels"), "gt_rles": match.get("gt_rles"),
-            "max_gt": match.get("max_gt", 64)}
+            "max_gt": match.get("max_gt", 64), "gt_segmentations": match.get("gt_segmentations")}
+    if coco:
+        opts["gt_coco"] = match.get("gt_coco")
     if opts["gt_labels"] is not None and opts["gt_rles"] is not None:
         raise ValueError('match takes "gt_labels" or "gt_rles", not both')
+    if opts["gt_segmentations"] is not None and (opts["gt_labels"] is not None or opts["gt_rles"] is not None):
+        raise ValueError('match takes one of "gt_labels", "gt_rles" and "gt_segmentations", not two')
+    if opts.get("gt_coco") is not None and any(opts[k] is not None for k in ("gt_labels", "gt_rles", "gt_segmentations")):
+        raise ValueError('match takes "gt_coco" or one of "gt_labels", "gt_rles" and "gt_segmentations", not both')
     if opts["gt_rles"] is not None and (not isinstance(opts["gt_rles"], (list, tuple)) or not opts["gt_rles"]):
         raise ValueError('match["gt_rles"] must be a non-empty list with one list of RLEs per image')
-    if opts["gt_labels"] is None and opts["gt_rles"] is None and not have_masks:
+    if opts["gt_segmentations"] is not None and (not isinstance(opts["gt_segmentations"], (list, tuple)) or not opts["gt_segmentations"]):
+        raise ValueError('match["gt_segmentations"] must be a non-empty list with one list of COCO segmentations per image')
+    if opts.get("gt_coco") is not None and not isinstance(opts["gt_coco"], (str, os.PathLike, dict)):
+        raise ValueError('match["gt_coco"] must be the path of a COCO annotations file or its dict')
+    if all(opts.get(k) is None for k in ("gt_labels", "gt_rles", "gt_segmentations", "gt_coco")) and not have_masks:
         raise ValueError('match needs ground truth: gt_masks, match["gt_labels"] or match["gt_rles"]')
     match_thresholds(opts["thresholds"])
     _id_bound(opts["max_gt"], 'match["max_gt"]')

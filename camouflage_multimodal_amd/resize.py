@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, instance_match as _match, instances as _instances, refine as _refine, rle as _rle, seg_measures
+from . import _lib, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures
 from .engine import _ptr, _stream_ptr
 from .rg_detect import detect_camouflage_batch, segmentation_counts, segmentation_metrics
 from .rg_finetune import prepare_finetune_batch
@@ -375,6 +375,19 @@ def _native_rle_labels(gt_rles, sizes, device):
     return out
 
 
+def _native_segmentation_labels(gt_segmentations, sizes, device):
+    """``polygons.decode_segmentations`` of every image's COCO segmentations at the image's own size; images of equal size share a call."""
+    groups = {}
+    for i, size in enumerate(sizes):
+        groups.setdefault(tuple(size), []).append(i)
+    out = [None] * len(sizes)
+    for (H, W), idx in groups.items():
+        lab = _polygons.decode_segmentations([gt_segmentations[i] for i in idx], H, W, device, image_numbers=idx)
+        for j, i in enumerate(idx):
+            out[i] = lab[j]
+    return out
+
+
 def _native_gt_labels(masks, connectivity, max_gt):
     """``instance_match.ground_truth_labels`` of every [H_i, W_i] mask; masks of equal size share a call."""
     groups = {}
@@ -412,7 +425,9 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     the ground-truth ones -- by default the connected components of every native mask, which needs ``gt_masks`` scored at native
     size; images of equal size share a call -- and adds "instance_match" (per image the records) and "instance_match_tables" (per
     image ``match_instances``' dict of its own rows).  ``None``: nothing changes.  "gt_rles" in ``match`` holds per image the COCO RLEs of
-    its ground-truth instances at the image's NATIVE size (``rle.decode_rles``; images of equal size share a call).
+    its ground-truth instances at the image's NATIVE size (``rle.decode_rles``; images of equal size share a call);
+    "gt_segmentations" holds per image its COCO ``segmentation`` fields, polygons or RLEs, in NATIVE coordinates
+    (``polygons.decode_segmentations``; images of equal size share a call).
     ``rle=True`` (needs ``instances=True``) adds "instance_rles_native": per image {id: RLE} of "instance_labels_native"
     (``rle.encode_instances``; maps of equal size share a call)."""
     if instances:
@@ -456,6 +471,10 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
                 if len(match["gt_rles"]) != len(sizes):
                     raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {len(sizes)} images')
                 gt_labels = _native_rle_labels(match["gt_rles"], sizes, img.device)
+            elif match["gt_segmentations"] is not None:
+                if len(match["gt_segmentations"]) != len(sizes):
+                    raise ValueError(f'match["gt_segmentations"] holds {len(match["gt_segmentations"])} lists for {len(sizes)} images')
+                gt_labels = _native_segmentation_labels(match["gt_segmentations"], sizes, img.device)
             elif gt_labels is None:
                 gt_labels = _native_gt_labels([masks.image(i) for i in range(len(sizes))], connectivity, match["max_gt"])
             elif len(gt_labels) != len(sizes):
@@ -522,13 +541,16 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     With ``match`` (``detect_camouflage_ragged``'s; needs ``instances=True`` and ``mask_dir``, or "gt_labels" for every file in
     sorted order) the native-size instances of every file are matched to the ground-truth ones and the result also holds
     "instance_match" (per-file records) and "instance_ap": ``instance_match.InstanceAP`` over all files, scored by every instance's
-    mean probability.  "gt_rles" in ``match`` holds the RLE lists of every file in sorted order, as "gt_labels" does.
+    mean probability.  "gt_rles" in ``match`` holds the RLE lists of every file in sorted order, as "gt_labels" does, and
+    "gt_segmentations" the lists of COCO ``segmentation`` fields.  "gt_coco" in ``match`` -- the path of a COCO annotations file, or its
+    dict -- takes them from that file by file stem (``polygons.coco_ground_truth``; a file whose size is not the one the annotations
+    state raises) and, with ``results_json`` and no ``image_ids``, numbers the results with the file's image ids.
     ``results_json`` (a path; needs ``instances=True``) writes the native-size instances of every file as a COCO results list: per
     instance {"image_id": the stem, or ``image_ids[stem]``, "category_id": 1, "segmentation": {"size", "counts"} (include/camo_rle.h),
     "score": the instance's Sq / (255 area), "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1]}; the result also holds "results": that list."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
-    match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None)
+    match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None, coco=True)
     if results_json is not None:
         if not isinstance(results_json, (str, os.PathLike)):
             raise ValueError(f"results_json must be a path, got {results_json!r}")
@@ -561,6 +583,16 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         raise ValueError(f'match["gt_labels"] holds {len(match["gt_labels"])} maps for {len(stems)} files')
     if match is not None and match["gt_rles"] is not None and len(match["gt_rles"]) != len(stems):
         raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {len(stems)} files')
+    coco_sizes = None
+    if match is not None:
+        coco = match.pop("gt_coco")
+        if coco is not None:
+            truth = _polygons.coco_ground_truth(coco, stems)
+            match["gt_segmentations"], coco_sizes = truth["segmentations"], truth["sizes"]
+            if results_json is not None and image_ids is None:
+                image_ids = truth["image_ids"]
+    if match is not None and match["gt_segmentations"] is not None and len(match["gt_segmentations"]) != len(stems):
+        raise ValueError(f'match["gt_segmentations"] holds {len(match["gt_segmentations"])} lists for {len(stems)} files')
     if image_ids is not None and set(stems) - set(image_ids):
         raise ValueError(f"image_ids has no entry for {sorted(set(stems) - set(image_ids))[:5]}")
     results = []
@@ -570,8 +602,14 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         gts = None
         if masks is not None:
             gts = _mask_list([np.array(Image.open(masks[s]).convert("L")) for s in part], len(part), "masks", _device(kw.get("device", "cuda")))
+        if coco_sizes is not None:
+            for s, a, size in zip(part, arrays, coco_sizes[at:at + len(part)]):
+                if tuple(a.shape[:2]) != tuple(size):
+                    raise ValueError(f"{s} is {a.shape[0]} x {a.shape[1]} and the annotations state {size[0]} x {size[1]}")
         if match is not None and match["gt_rles"] is not None:
             out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, gt_rles=match["gt_rles"][at:at + len(part)]), **kw)
+        elif match is not None and match["gt_segmentations"] is not None:
+            out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, gt_segmentations=match["gt_segmentations"][at:at + len(part)]), **kw)
         elif match is not None:
             gt_labels = match["gt_labels"][at:at + len(part)] if match["gt_labels"] is not None else \
                 _native_gt_labels([gts.image(i) for i in range(len(part))], kw.get("connectivity", 8), match["max_gt"])

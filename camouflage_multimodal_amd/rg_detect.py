@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, instance_match as _match, instances as _instances, refine as _refine, rle as _rle, seg_measures
+from . import _lib, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures
 from .engine import _ptr, _stream_ptr
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 
@@ -149,6 +149,9 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     ``instance_match_records``) and "instance_match_tables" (``match_instances``' dict).  Every other key keeps its bytes.
     "gt_rles" in ``match`` -- per image a list of COCO RLE dicts or (rle, id) pairs -- gives the ground-truth ids in the place of
     "gt_labels" (both together raise): ``rle.decode_rles`` paints them on the device (include/camo_rle.h).
+    "gt_segmentations" in ``match`` -- per image a list of COCO ``segmentation`` fields, polygon lists or RLE dicts, or
+    (segmentation, id) pairs -- does the same for annotations as a COCO file holds them (``polygons.decode_segmentations``,
+    include/camo_poly.h); it goes with neither of the other two.
     ``rle=True`` (needs ``instances=True``) adds "instance_rles": per image {id: {"size": [H, W], "counts": str}}, the COCO run-length
     encoding of every instance of "instance_labels" (``rle.encode_instances``); ``False``: no launch more than before."""
     if instances:
@@ -188,6 +191,10 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
                 if len(match["gt_rles"]) != N:
                     raise ValueError(f'match["gt_rles"] holds {len(match["gt_rles"])} lists for {N} images')
                 gt_labels = _rle.decode_rles(match["gt_rles"], H, W, img.device)
+            elif match["gt_segmentations"] is not None:
+                if len(match["gt_segmentations"]) != N:
+                    raise ValueError(f'match["gt_segmentations"] holds {len(match["gt_segmentations"])} lists for {N} images')
+                gt_labels = _polygons.decode_segmentations(match["gt_segmentations"], H, W, img.device)
             else:
                 gt_labels = match["gt_labels"] if match["gt_labels"] is not None else _match.ground_truth_labels(gt, connectivity, match["max_gt"])
             out["instance_match"], out["instance_match_tables"] = _match.match_detected(found["labels"], found["table"], gt_labels, match)

@@ -5,7 +5,7 @@ column-major order -- and returns device tensors; ``rles_from_runs`` reads every
 the runs on the host; ``encode_instances`` is the two together with a capacity that always holds every run.  ``decode_rles`` runs
 ``camo_rle_decode``: the counts of COCO annotations painted into int32 label maps on the device.  ``counts_to_string`` and
 ``string_to_counts`` are COCO's rleToString / rleFrString in numpy.
-PARITY UNPINNED: the header's text is the definition (restated in numpy in tests/rle_ref.py).  Out of scope: polygon annotations,
+PARITY UNPINNED: the header's text is the definition (restated in numpy in tests/rle_ref.py).  Polygon annotations: polygons.py.  Out of scope:
 ``iscrowd``, IoU in the RLE domain.  There is no CPU path for the label maps: tensors that are not on a HIP device raise.
 """
 from __future__ import annotations

@@ -9,7 +9,8 @@
  * the same bytes, a batch gives the rows of its images one by one).
  * PARITY UNPINNED: pycocotools is not part of this package, so its conventions are not pinned.  The text below is the definition; it
  * is restated in numpy in tests/rle_ref.py, which the kernels are tested against byte for byte.
- * OUT OF SCOPE: polygon annotations (COCO's frPoly), the iscrowd flag and IoU taken in the RLE domain.
+ * Polygon annotations (COCO's frPoly) have a call of their own: camo_poly.h.  OUT OF SCOPE: the iscrowd flag and IoU taken in the RLE
+ * domain.
  *
  * ORDER.  COCO flattens a mask column by column: pixel (y, x) of an [H, W] image has position p = x H + y, and a run continues
  * across the bottom of one column into the top of the next.
