@@ -23,17 +23,17 @@ from .train_multimodal import (NativeTrainer, SmartMultimodalDataset, calculate_
 from .region_graph import (RegionGraphBatch, RegionGraphData, RegionGraphGNN, build_target_csr, canny_edges, create_region_graph,  # noqa: F401,E402
                            create_region_graph_from_segments, create_region_graphs_from_segments, predict_from_image,
                            region_graph_from_image, region_graphs_from_images, slic_label_bound, slic_segments)
-from .rg_detect import (attention_to_pixels, detect_camouflage, detect_camouflage_batch, paint_regions, segmentation_counts,  # noqa: F401,E402
-                        segmentation_metrics)
-from .rg_finetune import (FineTuneBatch, RegionGraphFineTuner, node_targets_from_masks, prepare_finetune_batch)  # noqa: F401,E402
+from .rg_detect import attention_to_pixels, paint_regions, segmentation_counts, segmentation_metrics  # noqa: F401,E402
 from .seg_measures import (aggregate_cod_measures, cod_measures, segmentation_histograms, weighted_f_measure)  # noqa: F401,E402
 from .instances import detect_instances, instance_records, mask_instances  # noqa: F401,E402
 from .instance_match import InstanceAP, instance_match_records, match_instances  # noqa: F401,E402
 from .refine import guided_filter, guided_upsample  # noqa: F401,E402
 from .rle import (counts_to_string, decode_rles, encode_instances, label_runs, rle_area, rles_from_runs, string_to_counts)  # noqa: F401,E402
 from .polygons import (coco_ground_truth, decode_polygon_arrays, decode_polygons, decode_segmentations, polygons_to_rles)  # noqa: F401,E402
-from .resize import (RaggedImages, detect_camouflage_directory, detect_camouflage_ragged, pack_images, prepare_finetune_batch_ragged,  # noqa: F401,E402
-                     random_resized_crops, resize_batch, resize_to_sizes)
+from .resize import RaggedImages, pack_images, random_resized_crops, resize_batch, resize_to_sizes  # noqa: F401,E402
+from .pipeline import detect_camouflage, detect_camouflage_batch, detect_camouflage_directory, detect_camouflage_ragged  # noqa: F401,E402
+from .rg_finetune import (FineTuneBatch, RegionGraphFineTuner, node_targets_from_masks, prepare_finetune_batch,  # noqa: F401,E402
+                          prepare_finetune_batch_ragged)
 
 __all__ = ["decode_polygon_arrays", "decode_polygons", "polygons_to_rles", "decode_segmentations", "coco_ground_truth", "label_runs", "rles_from_runs", "encode_instances", "decode_rles", "counts_to_string", "string_to_counts", "rle_area", "match_instances", "instance_match_records", "InstanceAP", "guided_filter", "guided_upsample", "mask_instances", "instance_records", "detect_instances", "pack_images", "resize_batch", "resize_to_sizes", "random_resized_crops", "RaggedImages", "detect_camouflage_ragged", "prepare_finetune_batch_ragged", "detect_camouflage_directory",
            "segmentation_histograms", "cod_measures", "weighted_f_measure", "aggregate_cod_measures","node_targets_from_masks", "prepare_finetune_batch", "RegionGraphFineTuner", "FineTuneBatch", "detect_camouflage", "detect_camouflage_batch", "paint_regions", "attention_to_pixels", "segmentation_counts", "segmentation_metrics", "RegionGraphGNN", "RegionGraphData", "RegionGraphBatch", "create_region_graphs_from_segments", "region_graphs_from_images", "slic_label_bound", "predict_batch_from_images", "create_region_graph", "create_region_graph_from_segments", "canny_edges", "slic_segments", "region_graph_from_image", "predict_from_image", "build_target_csr", "build_multimodal_model", "MultimodalCamouflageDetector", "CrossAttentionFusion", "LateFusion",

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from .engine import _ptr, _stream_ptr
+from .instances import mask_instances
 
 COCO = tuple(Fraction(n, 20) for n in range(10, 20))
 MAX_DENOMINATOR = 1000
@@ -233,7 +234,6 @@ def match_options(match, instances=True, have_masks=True, coco=False):
 def ground_truth_labels(gt_masks, connectivity=8, max_gt=64):
     """The instances of ground-truth masks [N, H, W] (bool, or uint8 positive above 127): ``mask_instances``' labels of the mask's
     connected components with ``connectivity``, ``min_area=0`` and no hole filling."""
-    from .instances import mask_instances
     positive = gt_masks if gt_masks.dtype == torch.bool else gt_masks > 127
     return mask_instances(positive.to(torch.float32), 0.5, connectivity, 0, False, max_gt)["labels"]
 

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .engine import _ptr, _stream_ptr
+from .resize import _ragged
 
 DEFAULTS = {"radius": 8, "eps": 1e-4, "guide": "rgb"}
 LUMA = (0.2989, 0.5870, 0.1140)      # include/camo_canny.h step 1
@@ -135,7 +136,6 @@ def guided_upsample(coef, images, clamp=True):
     + bbar in float64, in ONE launch.  ``images``: anything ``resize_batch`` takes as a ragged batch -- a ``RaggedImages``, a list of
     uint8 images or a uint8 [N, H, W, C] / [N, H, W] device tensor -- with C channels.  Returns (list of N fp32 [H_i, W_i] views, the
     ONE packed buffer they are views of), like ``resize_to_sizes``."""
-    from .resize import _ragged                      # (resize.py imports the detector, which imports this module)
     if not isinstance(coef, torch.Tensor):
         raise ValueError("coef must be a tensor")
     _lib.require_device(coef, "coef")

@@ -6,7 +6,7 @@
 inference -- runs as HIP kernels behind ``camo_rg_node_embeddings`` (include/camo_rg_gnn.h).  The graph layers are
 torch_geometric's in the reference; the published algorithms they are restated from and the CPU checker the kernels are
 tested against are named in include/camo_rg_gnn.h (PARITY UNPINNED: no PyG here, no RG weights or fixtures shipped).  The node-classification ``forward``
-runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py).  ``loss_and_gradients``
+runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detector built on it is rg_detect.py and pipeline.py).  ``loss_and_gradients``
 gives the loss on the heads and every parameter's gradient with the batch-norm statistics frozen (``camo_rg_loss_backward``,
 include/camo_rg_train.h) or, with ``batch_stats=True``, on the statistics of the call's own nodes, the running statistics updated
 (``camo_rg_loss_backward_bn``, include/camo_rg_train_bn.h), and with ``dropout=`` under inverted dropout at the model's eight sites

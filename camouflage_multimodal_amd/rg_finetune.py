@@ -3,7 +3,7 @@
 What models/region_graph/train.py does around its forward and backward, with the batch-norm statistics frozen and dropout off (the
 path of ``RegionGraphGNN.loss_and_gradients``): ``node_targets_from_masks`` turns ground-truth masks into one target per superpixel
 for the three node heads (``camo_rg_node_targets``, three launches), ``prepare_finetune_batch`` builds everything a step reads from
-a batch of images once, and ``RegionGraphFineTuner`` holds the 32 trainable parameters in one flat buffer and takes a step as one
+a batch of images once (``prepare_finetune_batch_ragged``: from uint8 images of mixed sizes, through resize.py), and ``RegionGraphFineTuner`` holds the 32 trainable parameters in one flat buffer and takes a step as one
 ``camo_rg_loss_backward`` plus the two launches of the clip + AdamW pair of optim.py (``batch_norm="batch"`` and ``dropout=`` switch the
 step to batch statistics and to dropout: include/camo_rg_train_bn.h, include/camo_rg_train_drop.h).  PARITY UNPINNED: the reference's CODDataset
 cannot be read here, so the header's text defines the targets.  There is no CPU path: tensors that are not on a HIP device raise.
@@ -17,7 +17,9 @@ from .engine import _on, _ptr, _stream_ptr
 from .optim import AdamWStateMixin
 from .region_graph import (_as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments, slic_label_bound,
                            slic_segments)
-from .rg_detect import _offsets_tensor, detect_camouflage_batch
+from .pipeline import detect_camouflage_batch, detect_camouflage_ragged
+from .resize import _mask_list, _packed, _ragged, resize_batch
+from .rg_detect import _offsets_tensor
 
 PIECE = 64      # floats: every parameter starts on a 256-byte boundary of the flat buffers, as in loss_and_gradients_csr
 
@@ -128,6 +130,31 @@ def prepare_finetune_batch(images, gt_masks, instance_masks=None, edge_masks=Non
     csr = build_target_csr_device(n, graphs.edge_index, ew)
     rcsr = build_target_csr_device(n, graphs.edge_index.flip(0), ew)
     return FineTuneBatch(graphs, segments, region_map, mask_t, inst_t, edge_t, counts, csr, rcsr)
+
+
+@torch.no_grad()
+def prepare_finetune_batch_ragged(images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, **kw):
+    """``prepare_finetune_batch`` for uint8 images and masks of mixed sizes: the images are resized to ``size`` bilinear, every mask
+    nearest, all with the same ``crops`` and ``flips`` (``random_resized_crops`` draws them), and the result goes to
+    ``prepare_finetune_batch`` with ``**kw`` (n_segments, band_permille, device, edge_min_pixels)."""
+    device = kw.get("device", "cuda")
+    data, geo, C, _ = _ragged(images, device)
+    if C != 3:
+        raise ValueError(f"need images with 3 channels, got {C}")
+    packed = _packed(data, geo, C)
+    img = resize_batch(packed, size, "bilinear", crops, flips)
+    kw["device"] = img.device
+
+    def small(masks, name):
+        if masks is None:
+            return None
+        m = _mask_list(masks, len(packed), name, img.device)
+        if m.sizes != packed.sizes:
+            raise ValueError(f"every one of {name} must have its image's size")
+        return resize_batch(m, size, "nearest", crops, flips, out_dtype=torch.uint8)
+
+    return prepare_finetune_batch(img, small(gt_masks, "gt_masks"), small(instance_masks, "instance_masks"), small(edge_masks, "edge_masks"),
+                                  **kw)
 
 
 class RegionGraphFineTuner(AdamWStateMixin):
@@ -244,9 +271,8 @@ class RegionGraphFineTuner(AdamWStateMixin):
 
     def step_from_ragged(self, images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, n_segments=500,
                          band_permille=0, edge_min_pixels=1):
-        """``prepare_finetune_batch_ragged`` (resize.py: uint8 images and masks of mixed sizes, resized to ``size`` on the tuner's
+        """``prepare_finetune_batch_ragged`` (uint8 images and masks of mixed sizes, resized to ``size`` on the tuner's
         device with a crop box and a flip per image), then ``step``."""
-        from .resize import prepare_finetune_batch_ragged
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         return self.step(prepare_finetune_batch_ragged(images, gt_masks, instance_masks, edge_masks, size, crops, flips, n_segments=n_segments,
                                                        band_permille=band_permille, device=self.flat_params.device,
@@ -254,10 +280,9 @@ class RegionGraphFineTuner(AdamWStateMixin):
 
     def evaluate_ragged(self, images, gt_masks, size=(256, 256), n_segments=500, threshold=0.5, cod_metrics=False, evaluate_at="native",
                         instances=False, match=None, min_area=0, fill_holes=False, connectivity=8):
-        """``evaluate`` for uint8 images and masks of mixed sizes (``detect_camouflage_ragged`` of resize.py): the metrics are taken
+        """``evaluate`` for uint8 images and masks of mixed sizes (``detect_camouflage_ragged`` of pipeline.py): the metrics are taken
         against every mask at its own size, or at ``size`` with ``evaluate_at="resized"``.  Same return as ``evaluate``; the
         instances and their matches are those of the native-size maps."""
-        from .resize import detect_camouflage_ragged
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         out = detect_camouflage_ragged(self.model, images, gt_masks, size, n_segments, threshold, self.flat_params.device, cod_metrics, evaluate_at,
                                        instances, min_area, fill_holes, connectivity, match=match)

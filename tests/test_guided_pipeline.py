@@ -1,4 +1,4 @@
-"""The ``refine`` keyword of the detector entry points (camouflage_multimodal_amd/rg_detect.py, resize.py): a fresh
+"""The ``refine`` keyword of the detector entry points (camouflage_multimodal_amd/pipeline.py): a fresh
 ``RegionGraphGNN``, three 64 x 96 images, 30 superpixels.  The new keys must be ``guided_filter`` / ``guided_upsample`` of the call's
 own maps byte for byte, the refined metrics the counts of the call's own refined map, and ``refine=None`` must change nothing.
 Nothing here is compared across a threshold against a reference: the kernels are held to tests/guided_ref.py in tests/test_guided.py.

@@ -1,4 +1,4 @@
-"""The ``match`` keyword of the detector entry points (camouflage_multimodal_amd/rg_detect.py, resize.py, rg_finetune.py, DESIGN.md
+"""The ``match`` keyword of the detector entry points (camouflage_multimodal_amd/pipeline.py, rg_finetune.py, DESIGN.md
 10l): a fresh ``RegionGraphGNN``, 30 superpixels.  The new keys must be ``match_instances`` / ``instance_match_records`` of the
 call's own label maps, and ``match=None`` must change nothing.
 

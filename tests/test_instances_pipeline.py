@@ -1,4 +1,4 @@
-"""The instance keywords of the detector entry points (camouflage_multimodal_amd/rg_detect.py, resize.py): a fresh
+"""The instance keywords of the detector entry points (camouflage_multimodal_amd/pipeline.py): a fresh
 ``RegionGraphGNN``, two 64 x 96 images, 30 superpixels.  The new keys must be ``detect_instances`` of the call's own maps,
 "clean_metrics" the counts of the call's own clean mask, and ``instances=False`` must change nothing.
 

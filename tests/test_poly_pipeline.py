@@ -1,5 +1,5 @@
 """``match={"gt_segmentations": ...}`` and ``match={"gt_coco": ...}`` of the detector entry points (camouflage_multimodal_amd/
-rg_detect.py, resize.py): a fresh ``RegionGraphGNN``, 70 x 33 images of bright rectangles on a textured ground, 30
+pipeline.py): a fresh ``RegionGraphGNN``, 70 x 33 images of bright rectangles on a textured ground, 30
 superpixels, as tests/test_rle_pipeline.py.  Ground truth given as COCO polygons must match as the maps tests/poly_ref.py restates
 from the same polygons do, and with the keys absent the calls return the keys they returned before.
 

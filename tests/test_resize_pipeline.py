@@ -1,4 +1,4 @@
-"""The ragged entry points on top of the resize kernel (camouflage_multimodal_amd/resize.py): mixed-size uint8 images
+"""The ragged entry points on top of the resize kernel (camouflage_multimodal_amd/pipeline.py, rg_finetune.py): mixed-size uint8 images
 in, native-size maps and metrics out, fine-tuning from crops and flips, a directory of files.  Small model (hidden 32, 2 heads),
 working size 64 x 64, 30 superpixels.  The resize is exact, so images that already have the working size must give byte for byte
 what the fixed-size entry points give, and every native-size map must equal the restatement (tests/resize_ref.py) of the

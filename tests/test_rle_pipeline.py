@@ -1,5 +1,5 @@
 """The ``rle`` keyword, ``match={"gt_rles": ...}`` and ``results_json`` of the detector entry points (camouflage_multimodal_amd/
-rg_detect.py, resize.py): a fresh ``RegionGraphGNN``, 70 x 33 images of bright rectangles on a textured ground, 30
+pipeline.py): a fresh ``RegionGraphGNN``, 70 x 33 images of bright rectangles on a textured ground, 30
 superpixels.  The run-length encodings must decode to the call's own label maps, the RLE ground truth must match as the same ids
 given as label maps do, and the keywords left off must change nothing.
 
