@@ -45,6 +45,10 @@ IM_MAX_THRESHOLDS = 16              # CAMO_IM_MAX_THRESHOLDS
 IM_MAX_IDS = 1024                   # CAMO_IM_MAX_IDS
 IM_MAX_CELLS = 1 << 26              # CAMO_IM_MAX_CELLS
 IM_COUNTS = 4                       # CAMO_IM_COUNTS
+BD_MAX_DISTANCE = 1 << 12           # CAMO_BD_MAX_DISTANCE
+BD_STRIP = 64                       # CAMO_BD_STRIP
+BD_ROW_FIELDS = 6                   # CAMO_BD_ROW_FIELDS
+BD_GT_FIELDS = 2                    # CAMO_BD_GT_FIELDS
 RLE_MAX_ROWS = 1 << 26              # CAMO_RLE_MAX_ROWS
 RLE_MAX_ANNOTATIONS = 65535         # CAMO_RLE_MAX_ANNOTATIONS
 RLE_MAX_COUNTS = 1 << 26            # CAMO_RLE_MAX_COUNTS
@@ -197,6 +201,12 @@ PROTOTYPES = {
     "camo_inst_match.h": (
         ("camo_inst_match_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
         ("camo_inst_match", i32, (vp, vp, i32, i32, i32, i32, i32, vp, i32, P(i32), i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp)),
+    ),
+    "camo_boundary.h": (
+        ("camo_boundary_labels_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_boundary_labels", i32, (vp, i32, i32, i32, i32, vp, vp, sz, vp)),
+        ("camo_boundary_match_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
+        ("camo_boundary_match", i32, (vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, P(i32), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp)),
     ),
     "camo_guided.h": (
         ("camo_guided_workspace_bytes", sz, (i32, i32, i32, i32)),

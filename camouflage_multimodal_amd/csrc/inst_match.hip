@@ -90,10 +90,12 @@ __device__ __forceinline__ void im_score(long long a, long long s, long long& sq
 }
 
 // grid (row blocks + column blocks + rank blocks, images).  Row blocks: a wave sums inter's row p.  Column blocks: a thread sums
-// column g (consecutive threads, consecutive addresses).  Rank blocks: a thread counts the ids that come before id p.
+// column g (consecutive threads, consecutive addresses).  Rank blocks: a thread counts the ids that come before id p.  An id's row of
+// pred_rows has row_fields ints (the area goes to the first, the rank to the second), its entry of gt_area gt_fields.
 __global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ inter, int P, int G, const long long* __restrict__ table, int nrows,
                                                       int row_blocks, int col_blocks, int* __restrict__ area_p, int* __restrict__ area_g,
-                                                      int* __restrict__ rank, int* __restrict__ pred_rows, int* __restrict__ gt_area) {
+                                                      int* __restrict__ rank, int* __restrict__ pred_rows, int row_fields, int* __restrict__ gt_area,
+                                                      int gt_fields) {
   const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y;
   const int* cells = inter + (size_t)n * (P + 1) * (G + 1);
   int b = blockIdx.x;
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ in
     s = wave_sum_int(s);
     if (lane == 0) {
       area_p[(size_t)n * (P + 1) + p] = s;
-      if (p) pred_rows[((size_t)n * P + p - 1) * 4] = s;
+      if (p) pred_rows[((size_t)n * P + p - 1) * row_fields] = s;
     }
     return;
   }
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ in
 #pragma unroll 8                                                   // (independent loads: eight in flight)
     for (int p = 0; p <= P; ++p) s += cells[(size_t)p * (G + 1) + g];
     area_g[(size_t)n * (G + 1) + g] = s;
-    if (g) gt_area[(size_t)n * G + g - 1] = s;
+    if (g) gt_area[((size_t)n * G + g - 1) * gt_fields] = s;
     return;
   }
   b -= col_blocks;
@@ -140,25 +142,7 @@ __global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ in
     if (sp == 0) before += max(0, p - 1 - have);                   // the ids have + 1 .. p - 1 tie with a score of 0 and come first
   }
   rank[(size_t)n * P + p - 1] = before;
-  pred_rows[((size_t)n * P + p - 1) * 4 + 1] = before;
-}
-
-// A candidate ground-truth id with its intersection i and union u; g == 0: none.  a before b: higher IoU, then smaller id.
-struct ImCand { int i, u, g; };
-__device__ __forceinline__ bool im_before(const ImCand& a, const ImCand& b) {
-  if (a.g == 0) return false;
-  if (b.g == 0) return true;
-  const long long l = (long long)a.i * b.u, r = (long long)b.i * a.u;
-  return l > r || (l == r && a.g < b.g);
-}
-// the wave's best candidate, in every lane
-__device__ __forceinline__ ImCand im_wave_best(ImCand c) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const ImCand other{__shfl_xor(c.i, o, 64), __shfl_xor(c.u, o, 64), __shfl_xor(c.g, o, 64)};
-    if (im_before(other, c)) c = other;
-  }
-  return c;
+  pred_rows[((size_t)n * P + p - 1) * row_fields + 1] = before;
 }
 
 // The blocks past the thresholds' (block e of E): every prediction's ground-truth id of highest IoU, matched or not, one wave per
@@ -261,17 +245,26 @@ ImWs im_carve(int N, int P, int G, void* base) {
   return w;
 }
 
-int launch_inst_match(const int* pred_labels, const int* gt_labels, int N, int H, int W, int P, int G, const long long* pred_table,
-                      int pred_table_rows, const ImThresholds& thr, int T, const ImWs& ws, int* inter, int* pred_rows, int* gt_area,
-                      int* match, int* gt_match, int* counts, hipStream_t stream) {
+int launch_im_table(const int* pred_labels, const int* gt_labels, int N, int H, int W, int P, int G, const long long* pred_table,
+                    int pred_table_rows, bool with_rank, int* area_p, int* area_g, int* rank, int* inter, int* pred_rows, int row_fields,
+                    int* gt_area, int gt_fields, int* counts, hipStream_t stream) {
   const int HW = H * W, chunks = (HW + CHUNK - 1) / CHUNK;
   const long long cells = (long long)N * (P + 1) * (G + 1);
   const unsigned clear_blocks = (unsigned)std::min<long long>((cells + NT - 1) / NT, 4096);
   hipLaunchKernelGGL(im_clear_kernel, dim3(clear_blocks), dim3(NT), 0, stream, inter, cells, counts, CAMO_IM_COUNTS * N);
   hipLaunchKernelGGL(im_overlap_kernel, dim3(chunks, N), dim3(NT), 0, stream, pred_labels, gt_labels, HW, P, G, inter, counts);
-  const int row_blocks = (P + 1 + WAVES - 1) / WAVES, col_blocks = (G + 1 + NT - 1) / NT, rank_blocks = (P + NT - 1) / NT;
+  const int row_blocks = (P + 1 + WAVES - 1) / WAVES, col_blocks = (G + 1 + NT - 1) / NT, rank_blocks = with_rank ? (P + NT - 1) / NT : 0;
   hipLaunchKernelGGL(im_areas_kernel, dim3(row_blocks + col_blocks + rank_blocks, N), dim3(NT), 0, stream, inter, P, G, pred_table,
-                     pred_table_rows, row_blocks, col_blocks, ws.area_p, ws.area_g, ws.rank, pred_rows, gt_area);
+                     pred_table_rows, row_blocks, col_blocks, area_p, area_g, rank, pred_rows, row_fields, gt_area, gt_fields);
+  return (int)hipGetLastError();
+}
+
+int launch_inst_match(const int* pred_labels, const int* gt_labels, int N, int H, int W, int P, int G, const long long* pred_table,
+                      int pred_table_rows, const ImThresholds& thr, int T, const ImWs& ws, int* inter, int* pred_rows, int* gt_area,
+                      int* match, int* gt_match, int* counts, hipStream_t stream) {
+  if (int e = launch_im_table(pred_labels, gt_labels, N, H, W, P, G, pred_table, pred_table_rows, true, ws.area_p, ws.area_g, ws.rank, inter,
+                              pred_rows, 4, gt_area, 1, counts, stream))
+    return e;
   const int best_blocks = std::min((P + WAVES - 1) / WAVES, 16);
   hipLaunchKernelGGL(im_match_kernel, dim3(T + best_blocks, N), dim3(NT), 0, stream, inter, P, G, thr, T, ws.area_p, ws.area_g, ws.rank, match, gt_match,
                      pred_rows, counts);

@@ -1,7 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances, the
+// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances under mask and boundary IoU, the
 // guided-filter refinement of a mask, and COCO run-length masks out of and into label maps.
 // No device code here.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "rg_targets.h"
 #include "instances.h"
 #include "inst_match.h"
+#include "boundary.h"
 #include "guided.h"
 #include "rle.h"
 #include "poly.h"
@@ -35,6 +36,7 @@
 #include "../../include/camo_rg_targets.h"
 #include "../../include/camo_instances.h"
 #include "../../include/camo_inst_match.h"
+#include "../../include/camo_boundary.h"
 #include "../../include/camo_guided.h"
 #include "../../include/camo_rle.h"
 #include "../../include/camo_poly.h"
@@ -737,6 +739,65 @@ int camo_inst_match(const int32_t* pred_labels, const int32_t* gt_labels, int32_
   if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_inst_match_workspace_bytes()");
   CK(launch_inst_match(pred_labels, gt_labels, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table), pred_table ? pred_table_rows : 0,
                        thr, T, w, inter, pred_rows, gt_area, match, gt_match, counts, static_cast<hipStream_t>(stream)), "inst match");
+  return 0;
+}
+
+// ---- Boundary IoU: boundary regions of a label map, match under min(mask IoU, boundary IoU) (include/camo_boundary.h) ---
+static_assert(BD_STRIP == CAMO_BD_STRIP, "include/camo_boundary.h states the kernel's constant");
+
+static int bd_check(int N, int H, int W, int d) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (d < 1 || d > CAMO_BD_MAX_DISTANCE) return fail(CAMO_E_ARG, "d must be in [1, CAMO_BD_MAX_DISTANCE]");
+  return 0;
+}
+
+size_t camo_boundary_labels_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t d) {
+  if (bd_check(N, H, W, d)) return 0;
+  return ((size_t)N * H * W + 255) & ~size_t(255);
+}
+
+int camo_boundary_labels(const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t d, int32_t* out, void* ws, size_t ws_bytes,
+                         void* stream) {
+  if (int e = bd_check(N, H, W, d)) return e;
+  if (!labels) return fail(CAMO_E_ARG, "labels is null");
+  if (!out) return fail(CAMO_E_ARG, "out is null");
+  if (!ws) return fail(CAMO_E_ARG, "ws is null");
+  const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)N * H * W * 4;
+  if (a < b + bytes && b < a + bytes) return fail(CAMO_E_ARG, "labels and out must not overlap");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  if (ws_bytes < camo_boundary_labels_workspace_bytes(N, H, W, d)) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_boundary_labels_workspace_bytes()");
+  CK(launch_boundary_labels(labels, N, H, W, d, out, static_cast<unsigned char*>(ws), static_cast<hipStream_t>(stream)), "boundary labels");
+  return 0;
+}
+
+size_t camo_boundary_match_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t P, int32_t G, int32_t T) {
+  if (im_check(N, H, W, P, G, T)) return 0;
+  return bd_carve(N, P, G, nullptr).bytes;
+}
+
+int camo_boundary_match(const int32_t* pred_labels, const int32_t* gt_labels, const int32_t* pred_bd, const int32_t* gt_bd, int32_t N, int32_t H,
+                        int32_t W, int32_t P, int32_t G, const int64_t* pred_table, int32_t pred_table_rows, const int32_t* thr_num, int32_t thr_den,
+                        int32_t T, int32_t* inter, int32_t* inter_bd, int32_t* pred_rows, int32_t* gt_area, int32_t* match, int32_t* gt_match,
+                        int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = im_check(N, H, W, P, G, T)) return e;
+  if (!thr_num) return fail(CAMO_E_ARG, "thr_num is null");
+  if (thr_den < 1 || thr_den > 1000) return fail(CAMO_E_ARG, "thr_den must be in [1, 1000]");
+  ImThresholds thr{};
+  thr.den = thr_den;
+  for (int k = 0; k < T; ++k) {
+    if (thr_num[k] < 1 || thr_num[k] > thr_den) return fail(CAMO_E_ARG, "every thr_num must be in [1, thr_den]");
+    thr.num[k] = thr_num[k];
+  }
+  if (pred_table && pred_table_rows < 1) return fail(CAMO_E_ARG, "pred_table_rows must be >= 1 when pred_table is given");
+  if (reinterpret_cast<uintptr_t>(pred_table) & 7) return fail(CAMO_E_ARG, "pred_table must be 8-byte aligned");
+  if (!pred_labels || !gt_labels || !pred_bd || !gt_bd || !inter || !inter_bd || !pred_rows || !gt_area || !match || !gt_match || !counts || !ws)
+    return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  const BdWs w = bd_carve(N, P, G, ws);
+  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_boundary_match_workspace_bytes()");
+  CK(launch_boundary_match(pred_labels, gt_labels, pred_bd, gt_bd, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table),
+                           pred_table ? pred_table_rows : 0, thr, T, w, inter, inter_bd, pred_rows, gt_area, match, gt_match, counts,
+                           static_cast<hipStream_t>(stream)), "boundary match");
   return 0;
 }
 

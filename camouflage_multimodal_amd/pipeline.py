@@ -1,10 +1,10 @@
-"""The detection pipeline on MI355X: images in, masks, instances, matches and benchmark measures out (DESIGN.md 10d, 10g - 10n).
+"""The detection pipeline on MI355X: images in, masks, instances, matches and benchmark measures out (DESIGN.md 10d, 10g - 10o).
 
 ``detect_camouflage_batch`` (and the reference's name for one image, ``detect_camouflage``) runs the detector on a batch of one
 size; ``detect_camouflage_ragged`` takes uint8 images of mixed sizes through it and back to their own sizes, and
 ``detect_camouflage_directory`` takes a folder of files through that.  Everything here is host-side plumbing on top of the kernel
-bindings -- region_graph.py, rg_detect.py, seg_measures.py, instances.py, instance_match.py, rle.py, polygons.py, resize.py,
-refine.py -- and what the entry points share is stated once: ``_by_size`` (images of equal size share a library call) and
+bindings -- region_graph.py, rg_detect.py, seg_measures.py, instances.py, instance_match.py, boundary.py, rle.py, polygons.py,
+resize.py, refine.py -- and what the entry points share is stated once: ``_by_size`` (images of equal size share a library call) and
 ``_match_ground_truth`` (where the ground-truth ids of ``match`` come from).  This module imports all of those and is imported by
 rg_finetune.py only.  There is no CPU path: tensors that are not on a HIP device raise.
 """
@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures
+from . import _lib, boundary as _boundary, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 from .resize import _device, _mask_list, _packed, _ragged, resize_batch, resize_to_sizes
 from .rg_detect import paint_regions, segmentation_counts, segmentation_metrics
@@ -75,9 +75,36 @@ def _native_matches(labels, tables, gt_labels, opts):
     def matched(idx, _):
         r, t = _match.match_detected(_stack(labels, idx), _stack(tables, idx),
                                      torch.stack([torch.as_tensor(gt_labels[i]).to(labels[i].device, torch.int32) for i in idx]), opts)
-        return r, [{k: (v[j] if isinstance(v, torch.Tensor) else v) for k, v in t.items()} for j in range(len(idx))]
+        return r, _per_image(t, len(idx))
 
     return _by_size(labels, matched, 2)
+
+
+def _per_image(tables, n):
+    return [{k: (v[j] if isinstance(v, torch.Tensor) else v) for k, v in tables.items()} for j in range(n)]
+
+
+def _native_boundary_matches(labels, tables, gt_labels, opts, boundary):
+    """``_native_matches`` under the combined IoU (``boundary.match_detected_boundary``): a size group's distance comes from its own
+    H and W."""
+    _check_pairs(labels, gt_labels, "label map", "ground truth")
+
+    def matched(idx, _):
+        r, t = _boundary.match_detected_boundary(_stack(labels, idx), _stack(tables, idx),
+                                                 torch.stack([torch.as_tensor(gt_labels[i]).to(labels[i].device, torch.int32) for i in idx]), opts, boundary)
+        return r, _per_image(t, len(idx))
+
+    return _by_size(labels, matched, 2)
+
+
+def _positive(gt):
+    return gt if gt.dtype == torch.bool else gt > 127
+
+
+def _native_boundary_ious(masks, truths, boundary):
+    """``boundary.boundary_iou`` of every bool [H_i, W_i] mask against its ground-truth mask; masks of equal size share a call."""
+    _check_pairs(masks, truths, "mask", "ground-truth mask")
+    return _by_size(masks, lambda idx, _: _boundary.boundary_iou(_stack(masks, idx), _positive(_stack(truths, idx)), boundary["distance"], boundary["ratio"]))
 
 
 def _check_sources(match, n, noun):
@@ -103,7 +130,7 @@ def _match_ground_truth(match, n, noun, sizes, masks, connectivity, device):
 
 @torch.no_grad()
 def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
-                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False):
+                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -134,11 +161,18 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     (segmentation, id) pairs -- does the same for annotations as a COCO file holds them (``polygons.decode_segmentations``,
     include/camo_poly.h); it goes with neither of the other two.
     ``rle=True`` (needs ``instances=True``) adds "instance_rles": per image {id: {"size": [H, W], "counts": str}}, the COCO run-length
-    encoding of every instance of "instance_labels" (``rle.encode_instances``); ``False``: no launch more than before."""
+    encoding of every instance of "instance_labels" (``rle.encode_instances``); ``False``: no launch more than before.
+    ``boundary`` -- ``None`` (off: no launch more than before), ``True`` or a dict with any of "ratio" (1/50 of the diagonal) and
+    "distance" (the erosion distance itself) -- needs ``match``; it matches the instances once more under min(mask IoU, boundary IoU)
+    (``boundary.match_detected_boundary``, include/camo_boundary.h) and adds "boundary_match" (per image the records of
+    ``boundary.boundary_match_records``: ``InstanceAP`` of them is Boundary AP) and "boundary_match_tables"; with ``gt_masks`` also
+    "boundary_iou" (per image ``boundary.boundary_iou`` of "mask" against the ground-truth mask) and, with ``refine``,
+    "refined_boundary_iou" (of "mask_refined": what the guided filter did to the contour).  Every other key keeps its bytes."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
     match = _match.match_options(match, instances, gt_masks is not None)
+    boundary = _boundary.boundary_options(boundary, match)
     refine = _refine.refine_options(refine)
     img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
@@ -172,8 +206,13 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
             if gt_labels is None:
                 gt_labels = torch.stack(_match_ground_truth(match, N, "images", [(H, W)] * N, gt, connectivity, img.device))
             out["instance_match"], out["instance_match_tables"] = _match.match_detected(found["labels"], found["table"], gt_labels, match)
+            if boundary is not None:
+                out["boundary_match"], out["boundary_match_tables"] = _boundary.match_detected_boundary(found["labels"], found["table"], gt_labels,
+                                                                                                        match, boundary)
         if rle:
             out["instance_rles"] = _rle.encode_instances(found["labels"])
+    if boundary is not None and gt is not None:
+        out["boundary_iou"] = _boundary.boundary_iou(out["mask"], _positive(gt), boundary["distance"], boundary["ratio"])
     if refine is not None:
         guide = img if refine["guide"] == "rgb" else _refine.luma(img)
         q, coef = _refine.guided_filter(guide, prob_maps[:, 0], refine["radius"], refine["eps"], True, True)
@@ -182,24 +221,26 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
             out["refined_metrics"] = segmentation_metrics(segmentation_counts(q, gt, threshold), H, W)
             if cod_metrics:
                 out["refined_cod_metrics"] = seg_measures.cod_metrics(q, gt)
+            if boundary is not None:
+                out["refined_boundary_iou"] = _boundary.boundary_iou(out["mask_refined"], _positive(gt), boundary["distance"], boundary["ratio"])
     return out
 
 
 def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
-                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False):
+                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
     return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
-                                   connectivity, refine, match=match, rle=rle)
+                                   connectivity, refine, match=match, rle=rle, boundary=boundary)
 
 
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
                              cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None,
-                             *, match=None, rle=False):
+                             *, match=None, rle=False, boundary=None):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -224,11 +265,15 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     "gt_segmentations" holds per image its COCO ``segmentation`` fields, polygons or RLEs, in NATIVE coordinates
     (``polygons.decode_segmentations``; images of equal size share a call).
     ``rle=True`` (needs ``instances=True``) adds "instance_rles_native": per image {id: RLE} of "instance_labels_native"
-    (``rle.encode_instances``; maps of equal size share a call)."""
+    (``rle.encode_instances``; maps of equal size share a call).
+    ``boundary`` (``detect_camouflage_batch``'s; needs ``match``) works at NATIVE size, with the distance of every size group from
+    its own H and W: "boundary_match" (per image the records), "boundary_match_tables" (per image its own rows) and, with masks
+    scored at native size, "boundary_iou" of "mask_native" and, with ``refine``, "refined_boundary_iou" of "mask_native_refined"."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
     match = _match.match_options(match, instances, gt_masks is not None and evaluate_at == "native")
+    boundary = _boundary.boundary_options(boundary, match)
     refine = _refine.refine_options(refine)
     if refine is not None and refine["guide"] != "rgb":
         raise ValueError('detect_camouflage_ragged applies the coefficients to the native 3-channel bytes: refine["guide"] must be "rgb"')
@@ -268,8 +313,12 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         if match is not None:
             gt_labels = _match_ground_truth(match, len(sizes), "images", sizes, truth, connectivity, img.device)
             out["instance_match"], out["instance_match_tables"] = _native_matches(labels, tables, gt_labels, match)
+            if boundary is not None:
+                out["boundary_match"], out["boundary_match_tables"] = _native_boundary_matches(labels, tables, gt_labels, match, boundary)
         if rle:
             out["instance_rles_native"] = _by_size(labels, lambda idx, _: _rle.encode_instances(_stack(labels, idx)))
+    if boundary is not None and truth is not None:
+        out["boundary_iou"] = _native_boundary_ious(out["mask_native"], truth, boundary)
     if refine is not None:
         refined, _ = _refine.guided_upsample(out["refine_coefficients"], packed)
         out["prob_maps_native_refined"] = refined
@@ -278,6 +327,8 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
             out["refined_metrics"], cods = _score(refined, truth, threshold, cod_metrics)
             if cod_metrics:
                 out["refined_cod_metrics"] = cods
+            if boundary is not None:
+                out["refined_boundary_iou"] = _native_boundary_ious(out["mask_native_refined"], truth, boundary)
     return out
 
 
@@ -310,10 +361,14 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     state raises) and, with ``results_json`` and no ``image_ids``, numbers the results with the file's image ids.
     ``results_json`` (a path; needs ``instances=True``) writes the native-size instances of every file as a COCO results list: per
     instance {"image_id": the stem, or ``image_ids[stem]``, "category_id": 1, "segmentation": {"size", "counts"} (include/camo_rle.h),
-    "score": the instance's Sq / (255 area), "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1]}; the result also holds "results": that list."""
+    "score": the instance's Sq / (255 area), "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1]}; the result also holds "results": that list.
+    With ``boundary`` (``detect_camouflage_ragged``'s; needs ``match``) the result also holds "boundary_match" (per-file records) and
+    "boundary_ap": ``InstanceAP`` over them, which is Boundary AP; with masks scored at native size also "boundary_iou" per file and,
+    with ``refine``, "refined_boundary_iou"."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
     match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None, coco=True)
+    boundary = _boundary.boundary_options(kw.get("boundary"), match)
     if results_json is not None:
         if not isinstance(results_json, (str, os.PathLike)):
             raise ValueError(f"results_json must be a path, got {results_json!r}")
@@ -342,6 +397,7 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     result = {"files": stems}
     metrics, cods = [], []
     matched, ap = [], _match.InstanceAP()
+    bd_matched, bd_ap, bd_ious, bd_refined = [], _match.InstanceAP(), [], []
     coco_sizes = source = None
     if match is not None:
         coco = match.pop("gt_coco")
@@ -372,7 +428,11 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
                 _match_ground_truth(match, len(part), "files", gts.sizes, [gts.image(i) for i in range(len(part))], kw.get("connectivity", 8), None)
             out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, **{source or "gt_labels": ids}), **kw)
             matched += out["instance_match"]
-            ap.add(out["instance_match"], [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]])
+            scores = [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]]
+            ap.add(out["instance_match"], scores)
+            if boundary is not None:
+                bd_matched += out["boundary_match"]
+                bd_ap.add(out["boundary_match"], scores)
         if results_json is not None:
             results += _rle.coco_results(part, out["instances_native"], out["instance_rles_native"], image_ids)
         native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
@@ -384,7 +444,12 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
                 small = resize_batch(gts, size, "nearest", out_dtype=torch.uint8)
                 m, c = _score(list(out["prob_refined"] if refined else out["prob_maps"][:, 0]), list(small), threshold, cod, curves=True)
             else:
-                m, c = _score(native, [gts.image(i) for i in range(len(part))], threshold, cod, curves=True)
+                truth = [gts.image(i) for i in range(len(part))]
+                m, c = _score(native, truth, threshold, cod, curves=True)
+                if boundary is not None:                 # (the ragged call above was given no masks: the files' masks are scored here)
+                    bd_ious += _native_boundary_ious(out["mask_native"], truth, boundary)
+                    if refined:
+                        bd_refined += _native_boundary_ious(out["mask_native_refined"], truth, boundary)
             metrics += m
             cods += c or []
     if masks is not None:
@@ -394,6 +459,12 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
             result["cod_metrics"] = [{k: v for k, v in c.items() if k not in ("f_curve", "e_curve")} for c in cods]
     if match is not None:
         result["instance_match"], result["instance_ap"] = matched, ap.result()
+    if boundary is not None:
+        result["boundary_match"], result["boundary_ap"] = bd_matched, bd_ap.result()
+        if masks is not None and evaluate_at == "native":
+            result["boundary_iou"] = bd_ious
+            if refined:
+                result["refined_boundary_iou"] = bd_refined
     if results_json is not None:
         with open(results_json, "w") as f:
             json.dump(results, f)

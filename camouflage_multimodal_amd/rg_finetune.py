@@ -245,7 +245,7 @@ class RegionGraphFineTuner(AdamWStateMixin):
                                                 self.flat_params.device, edge_min_pixels))
 
     @staticmethod
-    def _evaluation(out, cod_metrics, instances, match, native=False):
+    def _evaluation(out, cod_metrics, instances, match, native=False, boundary=None):
         match = None if match is False else match
         if not (instances or match is not None):
             return {"metrics": out["metrics"], "cod_metrics": out["cod_metrics"]} if cod_metrics else out["metrics"]
@@ -254,20 +254,25 @@ class RegionGraphFineTuner(AdamWStateMixin):
             res["cod_metrics"] = out["cod_metrics"]
         if match is not None:
             res["instance_match"] = out["instance_match"]
+        if boundary is not None and boundary is not False:
+            res["boundary_match"] = out["boundary_match"]
+            if "boundary_iou" in out:
+                res["boundary_iou"] = out["boundary_iou"]
         return res
 
     def evaluate(self, images, gt_masks, n_segments=500, threshold=0.5, cod_metrics=False, instances=False, match=None, min_area=0,
-                 fill_holes=False, connectivity=8):
+                 fill_holes=False, connectivity=8, *, boundary=None):
         """``detect_camouflage_batch``'s metrics of the model as it is now: a list of ``segmentation_metrics`` dicts, one per image.
         With ``cod_metrics=True`` a dict instead: that list under "metrics" and, under "cod_metrics", the list of the benchmark
         measures (S-alpha, E-phi, F-beta, MAE on the 8-bit map, ``wf``) of ``seg_measures.cod_metrics``.  With ``instances=True``
         (``detect_camouflage_batch``'s, with ``min_area``, ``fill_holes``, ``connectivity``) a dict that also carries "instances"
         and, with ``match`` (``True`` or ``detect_camouflage_batch``'s dict), "instance_match": the records of the instances
-        matched to the ground-truth ones."""
+        matched to the ground-truth ones; with ``boundary`` (``detect_camouflage_batch``'s; needs ``match``) also "boundary_match",
+        the records under min(mask IoU, boundary IoU), and "boundary_iou" of the thresholded masks."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         out = detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device, cod_metrics, instances, min_area,
-                                      fill_holes, connectivity, match=match)
-        return self._evaluation(out, cod_metrics, instances, match)
+                                      fill_holes, connectivity, match=match, boundary=boundary)
+        return self._evaluation(out, cod_metrics, instances, match, boundary=boundary)
 
     def step_from_ragged(self, images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, n_segments=500,
                          band_permille=0, edge_min_pixels=1):
@@ -279,11 +284,11 @@ class RegionGraphFineTuner(AdamWStateMixin):
                                                        edge_min_pixels=edge_min_pixels))
 
     def evaluate_ragged(self, images, gt_masks, size=(256, 256), n_segments=500, threshold=0.5, cod_metrics=False, evaluate_at="native",
-                        instances=False, match=None, min_area=0, fill_holes=False, connectivity=8):
+                        instances=False, match=None, min_area=0, fill_holes=False, connectivity=8, *, boundary=None):
         """``evaluate`` for uint8 images and masks of mixed sizes (``detect_camouflage_ragged`` of pipeline.py): the metrics are taken
         against every mask at its own size, or at ``size`` with ``evaluate_at="resized"``.  Same return as ``evaluate``; the
-        instances and their matches are those of the native-size maps."""
+        instances and their matches -- ``boundary``'s too -- are those of the native-size maps."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         out = detect_camouflage_ragged(self.model, images, gt_masks, size, n_segments, threshold, self.flat_params.device, cod_metrics, evaluate_at,
-                                       instances, min_area, fill_holes, connectivity, match=match)
-        return self._evaluation(out, cod_metrics, instances, match, native=True)
+                                       instances, min_area, fill_holes, connectivity, match=match, boundary=boundary)
+        return self._evaluation(out, cod_metrics, instances, match, native=True, boundary=boundary)
