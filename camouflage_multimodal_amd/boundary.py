@@ -16,12 +16,13 @@ import ctypes as C
 import math
 import numbers
 from fractions import Fraction
+from functools import partial
 
 import torch
 
 from . import _lib
 from .engine import _ptr, _stream_ptr
-from .instance_match import COCO, _id_bound, _ratio, instance_match_records, match_instances, match_thresholds
+from .instance_match import COCO, _match_buffers, _match_detected, _match_inputs, _ratio, instance_match_records, match_instances
 
 RATIO = Fraction(1, 50)
 
@@ -118,51 +119,19 @@ def match_instances_boundary(pred_labels, gt_labels, pred_table=None, max_pred=N
     d = None
     if distance is not None or None in given.values():
         d = _distance(distance, ratio, H, W)
-    rows = 0
-    if pred_table is not None:
-        if not isinstance(pred_table, torch.Tensor) or pred_table.dtype != torch.int64:
-            raise ValueError("pred_table must be an int64 tensor")
-        if pred_table.dim() == 2:
-            pred_table = pred_table.unsqueeze(0)
-        if pred_table.dim() != 3 or pred_table.shape[0] != N or pred_table.shape[1] < 1 or pred_table.shape[2] != _lib.INST_FIELDS:
-            raise ValueError(f"need pred_table [N = {N}, rows >= 1, {_lib.INST_FIELDS}], got {tuple(pred_table.shape)}")
-        rows = int(pred_table.shape[1])
-    P = _id_bound((rows or 64) if max_pred is None else max_pred, "max_pred")
-    G = _id_bound(64 if max_gt is None else max_gt, "max_gt")
-    if N * (P + 1) * (G + 1) > _lib.IM_MAX_CELLS:
-        raise ValueError(f"max_pred = {P} and max_gt = {G} for {N} images exceed {_lib.IM_MAX_CELLS} table cells")
-    fr, nums, den = match_thresholds(thresholds)
-    T = len(nums)
-    _lib.require_device(pred_labels, "pred_labels")
-    dev = pred_labels.device
-    others = [("gt_labels", gt_labels), ("pred_table", pred_table)] + list(given.items())
-    for name, t in others:
-        if t is not None:
-            _lib.require_device(t, name)
-            if t.device != dev:
-                raise ValueError(f"{name} is on {t.device}, pred_labels on {dev}")
-    pred_labels, gt_labels = pred_labels.detach().contiguous(), gt_labels.detach().contiguous()
-    if pred_table is not None:
-        pred_table = pred_table.detach().contiguous()
-    pred_bd = boundary_labels(pred_labels, d) if given["pred_boundary"] is None else given["pred_boundary"].detach().contiguous()
-    gt_bd = boundary_labels(gt_labels, d) if given["gt_boundary"] is None else given["gt_boundary"].detach().contiguous()
-    L = _lib.lib()
-    nbytes = L.camo_boundary_match_workspace_bytes(N, H, W, P, G, T)
-    if nbytes == 0:
-        raise ValueError(f"camo_boundary_match does not support N = {N}, H = {H}, W = {W}, P = {P}, G = {G}, T = {T}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    inter, inter_bd = torch.empty(N, P + 1, G + 1, **i32), torch.empty(N, P + 1, G + 1, **i32)
-    pred_rows, gt_area = torch.empty(N, P, _lib.BD_ROW_FIELDS, **i32), torch.empty(N, G, _lib.BD_GT_FIELDS, **i32)
-    match, gt_match, counts = torch.empty(N, T, P, **i32), torch.empty(N, T, G, **i32), torch.empty(N, _lib.IM_COUNTS, **i32)
+    m = _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, thresholds, given.items())
+    pred_bd = boundary_labels(m.pred_labels, d) if given["pred_boundary"] is None else given["pred_boundary"].detach().contiguous()
+    gt_bd = boundary_labels(m.gt_labels, d) if given["gt_boundary"] is None else given["gt_boundary"].detach().contiguous()
+    L, dev, ws, out = _match_buffers("camo_boundary_match", m, (_lib.BD_ROW_FIELDS,), (_lib.BD_GT_FIELDS,))
+    inter_bd = torch.empty_like(out["inter"])
     with torch.cuda.device(dev):
-        rc = L.camo_boundary_match(_ptr(pred_labels), _ptr(gt_labels), _ptr(pred_bd), _ptr(gt_bd), N, H, W, P, G,
-                                   None if pred_table is None else _ptr(pred_table), rows, (C.c_int32 * T)(*nums), den, T, _ptr(inter),
-                                   _ptr(inter_bd), _ptr(pred_rows), _ptr(gt_area), _ptr(match), _ptr(gt_match), _ptr(counts), _ptr(ws), nbytes,
+        rc = L.camo_boundary_match(_ptr(m.pred_labels), _ptr(m.gt_labels), _ptr(pred_bd), _ptr(gt_bd), *m.dims, m.table_ptr, m.rows,
+                                   (C.c_int32 * m.T)(*m.nums), m.den, m.T, _ptr(out["inter"]), _ptr(inter_bd), _ptr(out["pred_rows"]),
+                                   _ptr(out["gt_area"]), _ptr(out["match"]), _ptr(out["gt_match"]), _ptr(out["counts"]), _ptr(ws), ws.numel(),
                                    _stream_ptr(dev))
     _lib.check(rc, "camo_boundary_match")
-    return {"inter": inter, "inter_bd": inter_bd, "pred_rows": pred_rows, "gt_area": gt_area, "match": match, "gt_match": gt_match,
-            "counts": counts, "thresholds": fr, "pred_boundary": pred_bd, "gt_boundary": gt_bd, "distance": d}
+    return {"inter": out["inter"], "inter_bd": inter_bd, **out, "thresholds": m.fr, "pred_boundary": pred_bd, "gt_boundary": gt_bd,
+            "distance": d}
 
 
 def boundary_match_records(out):
@@ -246,19 +215,5 @@ def match_detected_boundary(pred_labels, pred_table, gt_labels, opts, boundary):
     """``match_instances_boundary`` and ``boundary_match_records`` together, for the pipeline: (records, the dict).  ``opts``:
     ``match_options``' dict, ``boundary``: ``boundary_options``'.  The tables are sized as ``match_detected`` sizes them, with the
     same second call when an image carries a label past either; the boundary maps are made once."""
-    gt_labels = torch.as_tensor(gt_labels)
-    if gt_labels.dim() == 2:
-        gt_labels = gt_labels.unsqueeze(0)
-    gt_labels = gt_labels.to(device=pred_labels.device, dtype=torch.int32)
-    P, G = min(int(pred_table.shape[1]), _lib.IM_MAX_IDS), int(opts["max_gt"])
-    kw = dict(thresholds=opts["thresholds"], distance=boundary["distance"], ratio=boundary["ratio"])
-    tables = match_instances_boundary(pred_labels, gt_labels, pred_table, P, G, **kw)
-    rec = boundary_match_records(tables)
-    if any(r["truncated_pred"] or r["truncated_gt"] for r in rec):
-        P2 = min(max(P, int(pred_labels.max())), _lib.IM_MAX_IDS)
-        G2 = min(max(G, int(gt_labels.max())), _lib.IM_MAX_IDS)
-        if (P2, G2) != (P, G):
-            tables = match_instances_boundary(pred_labels, gt_labels, pred_table, P2, G2, pred_boundary=tables["pred_boundary"],
-                                              gt_boundary=tables["gt_boundary"], **kw)
-            rec = boundary_match_records(tables)
-    return rec, tables
+    match = partial(match_instances_boundary, thresholds=opts["thresholds"], distance=boundary["distance"], ratio=boundary["ratio"])
+    return _match_detected(match, boundary_match_records, pred_labels, pred_table, gt_labels, opts["max_gt"], ("pred_boundary", "gt_boundary"))

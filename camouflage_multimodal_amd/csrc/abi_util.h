@@ -1,6 +1,7 @@
-// Host-side vocabulary of the C ABI files (fusion_abi.hip with its workspace layout fusion_ws.h, rg_abi.hip, seg_measures.hip): the error return, the
-// workspace carver and the builder of an exact-fp32 GEMM batch.  No device code.
+// Host-side vocabulary of the C ABI files (fusion_abi.hip with its workspace layout fusion_ws.h, rg_abi.hip, image_abi.hip,
+// seg_measures.hip): the error return, the workspace carver and its check, and the builder of an exact-fp32 GEMM batch.  No device code.
 #pragma once
+#include <cstdint>
 #include <cstring>
 #include <string>
 
@@ -31,6 +32,14 @@ struct Carver {
   }
   size_t bytes() const { return (off + 255) & ~size_t(255); }      // what has been taken, the last piece rounded up like the others
 };
+
+// A caller's workspace `ws` of `ws_bytes` against the `need` bytes that `sizer` (the entry point's ..._workspace_bytes function)
+// returns: the alignment first, then the size.
+inline int ws_check(const void* ws, size_t ws_bytes, size_t need, const char* sizer) {
+  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
+  if (ws_bytes < need) return fail(CAMO_E_ARG, std::string("ws_bytes smaller than ") + sizer + "()");
+  return 0;
+}
 
 struct GB {
   GemmBatch b;

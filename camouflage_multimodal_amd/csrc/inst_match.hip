@@ -10,6 +10,8 @@
 //   match    one block per (threshold, image): predicted ids in rank order, each takes the unmatched ground-truth id of highest IoU
 //            at or above the threshold; up to 16 more blocks per image write every prediction's best ground truth and the counts
 //
+// The match of include/camo_boundary.h under min(mask IoU, boundary IoU) is the same code: clear, overlap and areas
+// once more for the table of the two boundary maps, and the match kernel's other instantiation.
 // Integer arithmetic only, IoUs compared by cross-multiplication; 32-bit integer atomic adds only.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +23,7 @@
 #include "instances.h"
 #include "label_inl.h"
 #include "../../include/camo_inst_match.h"
+#include "../../include/camo_boundary.h"
 
 namespace {
 
@@ -145,26 +148,52 @@ __global__ __launch_bounds__(NT) void im_areas_kernel(const int* __restrict__ in
   pred_rows[((size_t)n * P + p - 1) * row_fields + 1] = before;
 }
 
+// The boundary table of the combined match (BD): inter_bd and its row and column sums.  Nothing for the mask-only match.
+template <bool BD> struct ImBoundary {};
+template <> struct ImBoundary<true> { const int *inter, *area_p, *area_g; };
+
+// Ground-truth id g as a candidate of a predicted id, from its intersection i and union u in the mask table.  BD: under the smaller
+// of that fraction and the boundary table's -- brow the table's row of the predicted id, b its boundary area, bg the ground truth's.
+template <bool BD>
+__device__ __forceinline__ ImCand im_cand(int i, int u, int g, const int* __restrict__ brow, int b, const int* bg) {
+  if constexpr (BD) {
+    const int ib = brow[g];
+    return bd_cand(i, u, ib, b + bg[g] - ib, g);
+  } else {
+    return ImCand{i, u, g};
+  }
+}
+
 // The blocks past the thresholds' (block e of E): every prediction's ground-truth id of highest IoU, matched or not, one wave per
-// predicted id; block 0 also counts the ids in use.  ap, ag: the areas in LDS; used: two zeroed ints of LDS.
-__device__ __forceinline__ void im_best_rows(const int* __restrict__ cells, int P, int G, const int* ap, const int* ag, int* used, int e, int E,
-                                             int* __restrict__ rows, int* __restrict__ counts) {
+// predicted id, with the intersection (BD: the two intersections) to fields 2, 3 (and 5) of its row of `rows`; block 0 also counts the
+// ids in use, from the mask table's areas.  ap, ag, bp, bg: the areas in LDS; used: two zeroed ints of LDS.
+template <bool BD>
+__device__ __forceinline__ void im_best_rows(const int* __restrict__ cells, const int* __restrict__ bcells, int P, int G, const int* ap,
+                                             const int* ag, const int* bp, const int* bg, int* used, int e, int E, int* __restrict__ rows,
+                                             int* __restrict__ counts) {
+  constexpr int FIELDS = BD ? CAMO_BD_ROW_FIELDS : 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int p = e * WAVES + wave + 1; p <= P; p += E * WAVES) {
-    const int a = ap[p];
+    const int a = ap[p], b = BD ? bp[p] : 0;
     const int* row = cells + (size_t)p * (G + 1);
+    const int* brow = BD ? bcells + (size_t)p * (G + 1) : nullptr;
     ImCand best{0, 1, 0};
     if (a)
       for (int g = lane + 1; g <= G; g += 64) {
         const int i = row[g];
         if (i <= 0) continue;
-        const ImCand c{i, a + ag[g] - i, g};
+        const ImCand c = im_cand<BD>(i, a + ag[g] - i, g, brow, b, bg);
         if (im_before(c, best)) best = c;
       }
     best = im_wave_best(best);
     if (lane == 0) {
-      rows[(size_t)(p - 1) * 4 + 2] = best.g;
-      rows[(size_t)(p - 1) * 4 + 3] = best.i;
+      rows[(size_t)(p - 1) * FIELDS + 2] = best.g;
+      if constexpr (BD) {                                          // (best.i may be either table's)
+        rows[(size_t)(p - 1) * FIELDS + 3] = best.g ? row[best.g] : 0;
+        rows[(size_t)(p - 1) * FIELDS + 5] = best.g ? brow[best.g] : 0;
+      } else {
+        rows[(size_t)(p - 1) * FIELDS + 3] = best.i;
+      }
     }
   }
   if (e) return;
@@ -179,23 +208,39 @@ __device__ __forceinline__ void im_best_rows(const int* __restrict__ cells, int 
 }
 
 // grid (thresholds + row blocks, images).  Thread t owns ground-truth ids t + 1, t + 1 + NT, ...: it alone reads and writes their taken[] flag.
+// BD: the match under min(mask IoU, boundary IoU) -- the boundary table's areas beside the mask table's in LDS, a second row read per
+// candidate; pred_rows has CAMO_BD_ROW_FIELDS ints a row, not 4.
+template <bool BD>
 __global__ __launch_bounds__(NT) void im_match_kernel(const int* __restrict__ inter, int P, int G, ImThresholds thr, int T, const int* __restrict__ area_p,
                                                       const int* __restrict__ area_g, const int* __restrict__ rank, int* __restrict__ match,
-                                                      int* __restrict__ gt_match, int* __restrict__ pred_rows, int* __restrict__ counts) {
+                                                      int* __restrict__ gt_match, int* __restrict__ pred_rows, int* __restrict__ counts,
+                                                      ImBoundary<BD> bd) {
   __shared__ int ap[MAX_IDS + 1], ag[MAX_IDS + 1], taken[MAX_IDS + 1];
+  __shared__ int bp[BD ? MAX_IDS + 1 : 1], bg[BD ? MAX_IDS + 1 : 1];      // (not used, and no LDS, without BD)
   __shared__ int order[MAX_IDS];                                   // order[r] = the predicted id of rank r
   __shared__ ImCand wbest[2][WAVES];
   __shared__ int used[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = blockIdx.x, n = blockIdx.y;
-  const int* cells = inter + (size_t)n * (P + 1) * (G + 1);
-  for (int p = tid; p <= P; p += NT) ap[p] = area_p[(size_t)n * (P + 1) + p];
-  for (int g = tid; g <= G; g += NT) { ag[g] = area_g[(size_t)n * (G + 1) + g]; taken[g] = 0; }
+  const size_t table = (size_t)n * (P + 1) * (G + 1);
+  const int* cells = inter + table;
+  const int* bcells = nullptr;
+  if constexpr (BD) bcells = bd.inter + table;
+  for (int p = tid; p <= P; p += NT) {
+    ap[p] = area_p[(size_t)n * (P + 1) + p];
+    if constexpr (BD) bp[p] = bd.area_p[(size_t)n * (P + 1) + p];
+  }
+  for (int g = tid; g <= G; g += NT) {
+    ag[g] = area_g[(size_t)n * (G + 1) + g];
+    if constexpr (BD) bg[g] = bd.area_g[(size_t)n * (G + 1) + g];
+    taken[g] = 0;
+  }
   if (k < T)
     for (int p = tid; p < P; p += NT) order[rank[(size_t)n * P + p]] = p + 1;    // (rank is a permutation of 0 .. P - 1)
   if (tid < 2) used[tid] = 0;
   __syncthreads();
   if (k >= T) {                                                    // (the whole block)
-    im_best_rows(cells, P, G, ap, ag, used, k - T, gridDim.x - T, pred_rows + (size_t)n * P * 4, counts + CAMO_IM_COUNTS * n);
+    im_best_rows<BD>(cells, bcells, P, G, ap, ag, bp, bg, used, k - T, gridDim.x - T, pred_rows + (size_t)n * P * (BD ? CAMO_BD_ROW_FIELDS : 4),
+                     counts + CAMO_IM_COUNTS * n);
     return;
   }
 
@@ -203,19 +248,20 @@ __global__ __launch_bounds__(NT) void im_match_kernel(const int* __restrict__ in
   int* mrow = match + ((size_t)n * T + k) * P;
   int buf = 0;
   for (int r = 0; r < P; ++r) {
-    const int p = order[r], a = ap[p];
+    const int p = order[r], a = ap[p], b = BD ? bp[p] : 0;
     if (a == 0) {                                                  // (the whole block: no barrier is skipped by a part of it)
       if (tid == 0) mrow[p - 1] = 0;
       continue;
     }
     const int* row = cells + (size_t)p * (G + 1);
+    const int* brow = BD ? bcells + (size_t)p * (G + 1) : nullptr;
     ImCand best{0, 1, 0};
     for (int g = tid + 1; g <= G; g += NT) {
       const int ga = ag[g];
       if (ga == 0 || taken[g]) continue;
       const int i = row[g];
       if (i <= 0) continue;
-      const ImCand c{i, a + ga - i, g};
+      const ImCand c = im_cand<BD>(i, a + ga - i, g, brow, b, bg);
       if (den * c.i < num * c.u) continue;
       if (im_before(c, best)) best = c;
     }
@@ -233,14 +279,29 @@ __global__ __launch_bounds__(NT) void im_match_kernel(const int* __restrict__ in
   for (int g = tid + 1; g <= G; g += NT) gt_match[((size_t)n * T + k) * G + g - 1] = taken[g];
 }
 
+// the last launch of either call
+template <bool BD>
+int launch_im_match(const int* inter, int N, int P, int G, const ImThresholds& thr, int T, const ImWs& ws, int* match, int* gt_match, int* pred_rows,
+                    int* counts, ImBoundary<BD> bd, hipStream_t stream) {
+  const int best_blocks = std::min((P + WAVES - 1) / WAVES, 16);
+  hipLaunchKernelGGL(im_match_kernel<BD>, dim3(T + best_blocks, N), dim3(NT), 0, stream, inter, P, G, thr, T, ws.area_p, ws.area_g, ws.rank, match,
+                     gt_match, pred_rows, counts, bd);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
-ImWs im_carve(int N, int P, int G, void* base) {
+ImWs im_carve(int N, int P, int G, bool boundary, void* base) {
   ImWs w{};
   camo_abi::Carver c(base);
   w.area_p = c.take<int>((size_t)N * (P + 1));
   w.area_g = c.take<int>((size_t)N * (G + 1));
   w.rank = c.take<int>((size_t)N * P);
+  if (boundary) {
+    w.bd_area_p = c.take<int>((size_t)N * (P + 1));
+    w.bd_area_g = c.take<int>((size_t)N * (G + 1));
+    w.bd_counts = c.take<int>((size_t)N * CAMO_IM_COUNTS);
+  }
   w.bytes = c.bytes();
   return w;
 }
@@ -265,8 +326,18 @@ int launch_inst_match(const int* pred_labels, const int* gt_labels, int N, int H
   if (int e = launch_im_table(pred_labels, gt_labels, N, H, W, P, G, pred_table, pred_table_rows, true, ws.area_p, ws.area_g, ws.rank, inter,
                               pred_rows, 4, gt_area, 1, counts, stream))
     return e;
-  const int best_blocks = std::min((P + WAVES - 1) / WAVES, 16);
-  hipLaunchKernelGGL(im_match_kernel, dim3(T + best_blocks, N), dim3(NT), 0, stream, inter, P, G, thr, T, ws.area_p, ws.area_g, ws.rank, match, gt_match,
-                     pred_rows, counts);
-  return (int)hipGetLastError();
+  return launch_im_match<false>(inter, N, P, G, thr, T, ws, match, gt_match, pred_rows, counts, {}, stream);
+}
+
+int launch_boundary_match(const int* pred_labels, const int* gt_labels, const int* pred_bd, const int* gt_bd, int N, int H, int W, int P, int G,
+                          const long long* pred_table, int pred_table_rows, const ImThresholds& thr, int T, const ImWs& ws, int* inter,
+                          int* inter_bd, int* pred_rows, int* gt_area, int* match, int* gt_match, int* counts, hipStream_t stream) {
+  // the mask table: areas to fields 0 of pred_rows and gt_area, ranks to field 1; the boundary table: areas to fields 4 and 1
+  if (int e = launch_im_table(pred_labels, gt_labels, N, H, W, P, G, pred_table, pred_table_rows, true, ws.area_p, ws.area_g, ws.rank, inter, pred_rows,
+                              CAMO_BD_ROW_FIELDS, gt_area, CAMO_BD_GT_FIELDS, counts, stream))
+    return e;
+  if (int e = launch_im_table(pred_bd, gt_bd, N, H, W, P, G, nullptr, 0, false, ws.bd_area_p, ws.bd_area_g, nullptr, inter_bd, pred_rows + 4,
+                              CAMO_BD_ROW_FIELDS, gt_area + 1, CAMO_BD_GT_FIELDS, ws.bd_counts, stream))
+    return e;
+  return launch_im_match<true>(inter, N, P, G, thr, T, ws, match, gt_match, pred_rows, counts, {inter_bd, ws.bd_area_p, ws.bd_area_g}, stream);
 }

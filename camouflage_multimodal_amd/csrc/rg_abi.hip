@@ -1,9 +1,8 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
 // heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks, the object instances of a predicted mask, their matching to ground-truth instances under mask and boundary IoU, the
-// guided-filter refinement of a mask, and COCO run-length masks out of and into label maps.
-// No device code here.
+// the node targets from ground-truth masks.  The image pipeline around the detector (instances, their matching, boundary maps, the
+// guided filter, run-length masks, polygons) has image_abi.hip.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,12 +17,6 @@
 #include "rg_detect.h"
 #include "rg_train.h"
 #include "rg_targets.h"
-#include "instances.h"
-#include "inst_match.h"
-#include "boundary.h"
-#include "guided.h"
-#include "rle.h"
-#include "poly.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -34,12 +27,6 @@
 #include "../../include/camo_rg_train_bn.h"
 #include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
-#include "../../include/camo_instances.h"
-#include "../../include/camo_inst_match.h"
-#include "../../include/camo_boundary.h"
-#include "../../include/camo_guided.h"
-#include "../../include/camo_rle.h"
-#include "../../include/camo_poly.h"
 
 using namespace camo_abi;
 
@@ -665,269 +652,6 @@ int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, con
   if (!edge_t) return fail(CAMO_E_ARG, "edge_t is null");
   CK(launch_rg_node_targets(segments, region_map, node_off, gt_mask, gt_instance, gt_edge, N, H, W, label_bound, n_nodes, band_permille,
                             edge_min_pixels, counts, mask_t, inst_t, edge_t, static_cast<hipStream_t>(stream)), "rg node targets");
-  return 0;
-}
-
-// ---- Object instances of a predicted mask (include/camo_instances.h) ---------------------------------------------
-static int inst_check(int N, int H, int W) {
-  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
-  if (N > CAMO_RGD_MAX_IMAGES) return fail(CAMO_E_ARG, "N exceeds CAMO_RGD_MAX_IMAGES");
-  if ((long long)H * W > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGD_MAX_IMAGE_PIXELS");
-  if ((long long)N * H * W > CAMO_RGD_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGD_MAX_PIXELS (32-bit pixel indices)");
-  return 0;
-}
-
-size_t camo_instances_workspace_bytes(int32_t N, int32_t H, int32_t W) {
-  if (inst_check(N, H, W)) return 0;
-  return inst_carve(N, H, W, nullptr).bytes;
-}
-
-int camo_instances(const float* pred, int64_t pred_image_stride, float threshold, int32_t N, int32_t H, int32_t W, int32_t connectivity,
-                   int32_t min_area, int32_t fill_holes, int32_t max_instances, int32_t* labels, uint8_t* clean, int64_t* table,
-                   int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (connectivity != 4 && connectivity != 8) return fail(CAMO_E_ARG, "connectivity must be 4 or 8");
-  if (min_area < 0) return fail(CAMO_E_ARG, "min_area must be >= 0");
-  if (max_instances < 1) return fail(CAMO_E_ARG, "max_instances must be >= 1");
-  if ((long long)N * max_instances > CAMO_INST_MAX_ROWS) return fail(CAMO_E_ARG, "N * max_instances exceeds CAMO_INST_MAX_ROWS");
-  if (pred_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "pred_image_stride must be >= H * W");
-  if (!std::isfinite(threshold)) return fail(CAMO_E_ARG, "threshold must be finite");
-  if (!pred || !labels || !clean || !table || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
-  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const InstWs w = inst_carve(N, H, W, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_instances_workspace_bytes()");
-  CK(launch_instances(pred, pred_image_stride, threshold, N, H, W, connectivity, min_area, fill_holes != 0, max_instances, w, labels, clean,
-                      reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "instances");
-  return 0;
-}
-
-// ---- Instance matching: overlap table and greedy matches (include/camo_inst_match.h) -----------------------------
-static int im_check(int N, int H, int W, int P, int G, int T) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (P < 1 || P > CAMO_IM_MAX_IDS) return fail(CAMO_E_ARG, "P must be in [1, CAMO_IM_MAX_IDS]");
-  if (G < 1 || G > CAMO_IM_MAX_IDS) return fail(CAMO_E_ARG, "G must be in [1, CAMO_IM_MAX_IDS]");
-  if ((long long)N * (P + 1) * (G + 1) > CAMO_IM_MAX_CELLS) return fail(CAMO_E_ARG, "N * (P + 1) * (G + 1) exceeds CAMO_IM_MAX_CELLS");
-  if (T < 1 || T > CAMO_IM_MAX_THRESHOLDS) return fail(CAMO_E_ARG, "T must be in [1, CAMO_IM_MAX_THRESHOLDS]");
-  return 0;
-}
-
-size_t camo_inst_match_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t P, int32_t G, int32_t T) {
-  if (im_check(N, H, W, P, G, T)) return 0;
-  return im_carve(N, P, G, nullptr).bytes;
-}
-
-int camo_inst_match(const int32_t* pred_labels, const int32_t* gt_labels, int32_t N, int32_t H, int32_t W, int32_t P, int32_t G,
-                    const int64_t* pred_table, int32_t pred_table_rows, const int32_t* thr_num, int32_t thr_den, int32_t T, int32_t* inter,
-                    int32_t* pred_rows, int32_t* gt_area, int32_t* match, int32_t* gt_match, int32_t* counts, void* ws, size_t ws_bytes,
-                    void* stream) {
-  if (int e = im_check(N, H, W, P, G, T)) return e;
-  if (!thr_num) return fail(CAMO_E_ARG, "thr_num is null");
-  if (thr_den < 1 || thr_den > 1000) return fail(CAMO_E_ARG, "thr_den must be in [1, 1000]");
-  ImThresholds thr{};
-  thr.den = thr_den;
-  for (int k = 0; k < T; ++k) {
-    if (thr_num[k] < 1 || thr_num[k] > thr_den) return fail(CAMO_E_ARG, "every thr_num must be in [1, thr_den]");
-    thr.num[k] = thr_num[k];
-  }
-  if (pred_table && pred_table_rows < 1) return fail(CAMO_E_ARG, "pred_table_rows must be >= 1 when pred_table is given");
-  if (reinterpret_cast<uintptr_t>(pred_table) & 7) return fail(CAMO_E_ARG, "pred_table must be 8-byte aligned");
-  if (!pred_labels || !gt_labels || !inter || !pred_rows || !gt_area || !match || !gt_match || !counts || !ws)
-    return fail(CAMO_E_ARG, "null pointer argument");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const ImWs w = im_carve(N, P, G, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_inst_match_workspace_bytes()");
-  CK(launch_inst_match(pred_labels, gt_labels, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table), pred_table ? pred_table_rows : 0,
-                       thr, T, w, inter, pred_rows, gt_area, match, gt_match, counts, static_cast<hipStream_t>(stream)), "inst match");
-  return 0;
-}
-
-// ---- Boundary IoU: boundary regions of a label map, match under min(mask IoU, boundary IoU) (include/camo_boundary.h) ---
-static_assert(BD_STRIP == CAMO_BD_STRIP, "include/camo_boundary.h states the kernel's constant");
-
-static int bd_check(int N, int H, int W, int d) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (d < 1 || d > CAMO_BD_MAX_DISTANCE) return fail(CAMO_E_ARG, "d must be in [1, CAMO_BD_MAX_DISTANCE]");
-  return 0;
-}
-
-size_t camo_boundary_labels_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t d) {
-  if (bd_check(N, H, W, d)) return 0;
-  return ((size_t)N * H * W + 255) & ~size_t(255);
-}
-
-int camo_boundary_labels(const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t d, int32_t* out, void* ws, size_t ws_bytes,
-                         void* stream) {
-  if (int e = bd_check(N, H, W, d)) return e;
-  if (!labels) return fail(CAMO_E_ARG, "labels is null");
-  if (!out) return fail(CAMO_E_ARG, "out is null");
-  if (!ws) return fail(CAMO_E_ARG, "ws is null");
-  const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)N * H * W * 4;
-  if (a < b + bytes && b < a + bytes) return fail(CAMO_E_ARG, "labels and out must not overlap");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  if (ws_bytes < camo_boundary_labels_workspace_bytes(N, H, W, d)) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_boundary_labels_workspace_bytes()");
-  CK(launch_boundary_labels(labels, N, H, W, d, out, static_cast<unsigned char*>(ws), static_cast<hipStream_t>(stream)), "boundary labels");
-  return 0;
-}
-
-size_t camo_boundary_match_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t P, int32_t G, int32_t T) {
-  if (im_check(N, H, W, P, G, T)) return 0;
-  return bd_carve(N, P, G, nullptr).bytes;
-}
-
-int camo_boundary_match(const int32_t* pred_labels, const int32_t* gt_labels, const int32_t* pred_bd, const int32_t* gt_bd, int32_t N, int32_t H,
-                        int32_t W, int32_t P, int32_t G, const int64_t* pred_table, int32_t pred_table_rows, const int32_t* thr_num, int32_t thr_den,
-                        int32_t T, int32_t* inter, int32_t* inter_bd, int32_t* pred_rows, int32_t* gt_area, int32_t* match, int32_t* gt_match,
-                        int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = im_check(N, H, W, P, G, T)) return e;
-  if (!thr_num) return fail(CAMO_E_ARG, "thr_num is null");
-  if (thr_den < 1 || thr_den > 1000) return fail(CAMO_E_ARG, "thr_den must be in [1, 1000]");
-  ImThresholds thr{};
-  thr.den = thr_den;
-  for (int k = 0; k < T; ++k) {
-    if (thr_num[k] < 1 || thr_num[k] > thr_den) return fail(CAMO_E_ARG, "every thr_num must be in [1, thr_den]");
-    thr.num[k] = thr_num[k];
-  }
-  if (pred_table && pred_table_rows < 1) return fail(CAMO_E_ARG, "pred_table_rows must be >= 1 when pred_table is given");
-  if (reinterpret_cast<uintptr_t>(pred_table) & 7) return fail(CAMO_E_ARG, "pred_table must be 8-byte aligned");
-  if (!pred_labels || !gt_labels || !pred_bd || !gt_bd || !inter || !inter_bd || !pred_rows || !gt_area || !match || !gt_match || !counts || !ws)
-    return fail(CAMO_E_ARG, "null pointer argument");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const BdWs w = bd_carve(N, P, G, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_boundary_match_workspace_bytes()");
-  CK(launch_boundary_match(pred_labels, gt_labels, pred_bd, gt_bd, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table),
-                           pred_table ? pred_table_rows : 0, thr, T, w, inter, inter_bd, pred_rows, gt_area, match, gt_match, counts,
-                           static_cast<hipStream_t>(stream)), "boundary match");
-  return 0;
-}
-
-// ---- Edge-aware mask refinement: guided filter and native-size apply (include/camo_guided.h) ---------------------
-static int gf_check(int N, int H, int W, int C) {
-  if (N < 1 || H < 1 || W < 1) return fail(CAMO_E_ARG, "need N >= 1, H >= 1, W >= 1");
-  if (N > CAMO_RGD_MAX_IMAGES) return fail(CAMO_E_ARG, "N exceeds CAMO_RGD_MAX_IMAGES");
-  if (H > CAMO_RSZ_MAX_SIDE || W > CAMO_RSZ_MAX_SIDE) return fail(CAMO_E_ARG, "H or W exceeds CAMO_RSZ_MAX_SIDE");
-  if ((long long)H * W > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGD_MAX_IMAGE_PIXELS");
-  if ((long long)N * H * W > CAMO_RGD_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGD_MAX_PIXELS");
-  if (C != 1 && C != 3) return fail(CAMO_E_ARG, "C must be 1 (grey guide) or 3 (colour guide)");
-  return 0;
-}
-
-size_t camo_guided_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C) {
-  if (gf_check(N, H, W, C)) return 0;
-  return gf_carve(N, H, W, C, nullptr).bytes;
-}
-
-int camo_guided_filter(const float* guide, const float* p, int64_t p_image_stride, int32_t N, int32_t H, int32_t W, int32_t C, int32_t radius,
-                       double eps, int32_t clamp, float* q, float* coef, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = gf_check(N, H, W, C)) return e;
-  if (radius < 1 || radius > CAMO_GF_MAX_RADIUS) return fail(CAMO_E_ARG, "radius must be in [1, CAMO_GF_MAX_RADIUS]");
-  if (!(eps >= CAMO_GF_MIN_EPS && eps <= CAMO_GF_MAX_EPS)) return fail(CAMO_E_ARG, "eps must be in [CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS]");
-  if (clamp != 0 && clamp != 1) return fail(CAMO_E_ARG, "clamp must be 0 or 1");
-  if (p_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "p_image_stride must be >= H * W");
-  if (!guide || !p || !q || !ws) return fail(CAMO_E_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(guide) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(coef)) & 3)
-    return fail(CAMO_E_ARG, "guide, p, q and coef must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const GfWs w = gf_carve(N, H, W, C, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_guided_workspace_bytes()");
-  CK(launch_guided_filter(guide, p, p_image_stride, N, H, W, C, radius, eps, clamp != 0, q, coef, w, static_cast<hipStream_t>(stream)),
-     "guided filter");
-  return 0;
-}
-
-int camo_guided_apply(const float* coef, int32_t N, int32_t C, int32_t h, int32_t w, const uint8_t* guide, int64_t guide_elems, float* out,
-                      int64_t out_elems, const int64_t* table, int64_t max_dst_pixels, int32_t clamp, int32_t* status, void* stream) {
-  if (int e = gf_check(N, h, w, C)) return e;
-  if (clamp != 0 && clamp != 1) return fail(CAMO_E_ARG, "clamp must be 0 or 1");
-  if (guide_elems < 1) return fail(CAMO_E_ARG, "need guide_elems >= 1");
-  if (out_elems < 1) return fail(CAMO_E_ARG, "need out_elems >= 1");
-  if (max_dst_pixels < 1 || max_dst_pixels > CAMO_RGD_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "need 1 <= max_dst_pixels <= CAMO_RGD_MAX_IMAGE_PIXELS");
-  if (!coef || !guide || !out || !table || !status) return fail(CAMO_E_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(coef) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(status)) & 3)
-    return fail(CAMO_E_ARG, "coef, out and status must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
-  CK(launch_guided_apply(coef, N, C, h, w, guide, guide_elems, out, out_elems, reinterpret_cast<const long long*>(table), max_dst_pixels,
-                         clamp != 0, status, static_cast<hipStream_t>(stream)), "guided apply");
-  return 0;
-}
-
-// ---- COCO run-length masks: label maps to runs, counts to label maps (include/camo_rle.h) -------------------------
-static int rle_runs_check(int N, int H, int W, int R) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (R < 1) return fail(CAMO_E_ARG, "R must be >= 1");
-  if ((long long)N * R > CAMO_RLE_MAX_ROWS) return fail(CAMO_E_ARG, "N * R exceeds CAMO_RLE_MAX_ROWS");
-  return 0;
-}
-
-size_t camo_rle_runs_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t R) {
-  if (rle_runs_check(N, H, W, R)) return 0;
-  return rle_runs_carve(N, H, W, nullptr).bytes;
-}
-
-int camo_rle_runs(const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t R, int32_t* runs, int32_t* counts, void* ws, size_t ws_bytes,
-                  void* stream) {
-  if (int e = rle_runs_check(N, H, W, R)) return e;
-  if (!labels || !runs || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(counts)) & 3) return fail(CAMO_E_ARG, "labels and counts must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(runs) & 7) return fail(CAMO_E_ARG, "runs must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const RleRunsWs w = rle_runs_carve(N, H, W, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_rle_runs_workspace_bytes()");
-  CK(launch_rle_runs(labels, N, H, W, R, w, runs, counts, static_cast<hipStream_t>(stream)), "rle runs");
-  return 0;
-}
-
-static int rle_decode_check(int N, int H, int W, int A, int total) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (A < 1 || A > CAMO_RLE_MAX_ANNOTATIONS) return fail(CAMO_E_ARG, "A must be in [1, CAMO_RLE_MAX_ANNOTATIONS]");
-  if (total < 0 || total > CAMO_RLE_MAX_COUNTS) return fail(CAMO_E_ARG, "total must be in [0, CAMO_RLE_MAX_COUNTS]");
-  return 0;
-}
-
-size_t camo_rle_decode_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t A, int32_t total) {
-  if (rle_decode_check(N, H, W, A, total)) return 0;
-  return rle_decode_carve(total, nullptr).bytes;
-}
-
-int camo_rle_decode(const int32_t* cnts, int32_t total, const int32_t* ann_off, const int32_t* ann_image, const int32_t* ann_value, int32_t A,
-                    int32_t N, int32_t H, int32_t W, int32_t* labels, int64_t* ann_sum, void* ws, size_t ws_bytes, void* stream) {
-  if (int e = rle_decode_check(N, H, W, A, total)) return e;
-  if ((!cnts && total > 0) || !ann_off || !ann_image || !ann_value || !labels || !ann_sum || !ws) return fail(CAMO_E_ARG, "null pointer argument");
-  if (reinterpret_cast<uintptr_t>(ann_sum) & 7) return fail(CAMO_E_ARG, "ann_sum must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const RleDecodeWs w = rle_decode_carve(total, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_rle_decode_workspace_bytes()");
-  CK(launch_rle_decode(cnts, total, ann_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_sum),
-                       static_cast<hipStream_t>(stream)), "rle decode");
-  return 0;
-}
-
-// ---- COCO polygon annotations to label maps (include/camo_poly.h) --------------------------------------------------
-static int poly_check(int N, int H, int W, int A, int P, int V) {
-  if (int e = inst_check(N, H, W)) return e;
-  if (A < 1 || A > CAMO_POLY_MAX_ANNOTATIONS) return fail(CAMO_E_ARG, "A must be in [1, CAMO_POLY_MAX_ANNOTATIONS]");
-  if (P < 0 || P > CAMO_POLY_MAX_POLYGONS) return fail(CAMO_E_ARG, "P must be in [0, CAMO_POLY_MAX_POLYGONS]");
-  if (V < 0 || V > CAMO_POLY_MAX_VERTICES) return fail(CAMO_E_ARG, "V must be in [0, CAMO_POLY_MAX_VERTICES]");
-  if ((long long)P * (((long long)H * W + 31) / 32) > CAMO_POLY_MAX_PLANE_WORDS) return fail(CAMO_E_ARG, "P * ceil(H W / 32) exceeds CAMO_POLY_MAX_PLANE_WORDS");
-  return 0;
-}
-
-size_t camo_poly_decode_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t A, int32_t P, int32_t V) {
-  if (poly_check(N, H, W, A, P, V)) return 0;
-  return poly_carve(H, W, A, P, nullptr).bytes;
-}
-
-int camo_poly_decode(const double* xy, int32_t V, const int32_t* poly_off, int32_t P, const int32_t* ann_poly_off, const int32_t* ann_image,
-                     const int32_t* ann_value, int32_t A, int32_t N, int32_t H, int32_t W, int32_t* labels, int64_t* ann_area, void* ws, size_t ws_bytes,
-                     void* stream) {
-  if (int e = poly_check(N, H, W, A, P, V)) return e;
-  if ((!xy && V > 0) || !poly_off || !ann_poly_off || !ann_image || !ann_value || !labels || !ann_area || !ws) return fail(CAMO_E_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(xy) | reinterpret_cast<uintptr_t>(ann_area)) & 7) return fail(CAMO_E_ARG, "xy and ann_area must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(CAMO_E_ARG, "ws must be 256-byte aligned");
-  const PolyWs w = poly_carve(H, W, A, P, ws);
-  if (ws_bytes < w.bytes) return fail(CAMO_E_ARG, "ws_bytes smaller than camo_poly_decode_workspace_bytes()");
-  CK(launch_poly_decode(xy, V, poly_off, P, ann_poly_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_area),
-                        static_cast<hipStream_t>(stream)), "poly decode");
   return 0;
 }
 }  // extern "C"

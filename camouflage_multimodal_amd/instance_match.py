@@ -14,6 +14,8 @@ import math
 import numbers
 import os
 from fractions import Fraction
+from functools import partial
+from types import SimpleNamespace
 
 import torch
 
@@ -66,6 +68,56 @@ def _id_bound(v, name):
     return int(v)
 
 
+def _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, thresholds, more=()):
+    """What ``match_instances`` and ``match_instances_boundary`` check alike once their label maps are int32 [N, H, W] of one shape
+    (each words and orders those errors its own way): the table, P, G, the cell bound, the thresholds, and that every tensor is on
+    ``pred_labels``' HIP device -- ``more``: (name, map or ``None``) pairs of further maps.  Returns a namespace: the two maps and the table detached and contiguous, ``dims`` =
+    (N, H, W, P, G), the table's pointer and ``rows``, and ``match_thresholds``' ``fr``, ``nums``, ``den`` with ``T``."""
+    N, H, W = pred_labels.shape
+    rows = 0
+    if pred_table is not None:
+        if not isinstance(pred_table, torch.Tensor) or pred_table.dtype != torch.int64:
+            raise ValueError("pred_table must be an int64 tensor")
+        if pred_table.dim() == 2:
+            pred_table = pred_table.unsqueeze(0)
+        if pred_table.dim() != 3 or pred_table.shape[0] != N or pred_table.shape[1] < 1 or pred_table.shape[2] != _lib.INST_FIELDS:
+            raise ValueError(f"need pred_table [N = {N}, rows >= 1, {_lib.INST_FIELDS}], got {tuple(pred_table.shape)}")
+        rows = int(pred_table.shape[1])
+    P = _id_bound((rows or 64) if max_pred is None else max_pred, "max_pred")
+    G = _id_bound(64 if max_gt is None else max_gt, "max_gt")
+    if N * (P + 1) * (G + 1) > _lib.IM_MAX_CELLS:
+        raise ValueError(f"max_pred = {P} and max_gt = {G} for {N} images exceed {_lib.IM_MAX_CELLS} table cells")
+    fr, nums, den = match_thresholds(thresholds)
+    _lib.require_device(pred_labels, "pred_labels")
+    dev = pred_labels.device
+    for name, t in (("gt_labels", gt_labels), ("pred_table", pred_table), *more):
+        if t is not None:
+            _lib.require_device(t, name)
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, pred_labels on {dev}")
+    if pred_table is not None:
+        pred_table = pred_table.detach().contiguous()
+    return SimpleNamespace(pred_labels=pred_labels.detach().contiguous(), gt_labels=gt_labels.detach().contiguous(), pred_table=pred_table,
+                           table_ptr=None if pred_table is None else _ptr(pred_table), rows=rows, dims=(N, H, W, P, G), fr=fr, nums=nums,
+                           den=den, T=len(nums))
+
+
+def _match_buffers(entry, m, row_fields, gt_fields):
+    """The workspace of ``entry`` (``camo_inst_match`` or ``camo_boundary_match``) for ``_match_inputs``' ``m`` and the call's six
+    output tensors, "pred_rows" [N, P, *row_fields] and "gt_area" [N, G, *gt_fields]: (the library, the device, ws, the dict).  A step
+    of its own because ``match_instances_boundary`` makes its boundary maps, which may raise, between the checks and this."""
+    N, H, W, P, G = m.dims
+    L = _lib.lib()
+    nbytes = getattr(L, entry + "_workspace_bytes")(N, H, W, P, G, m.T)
+    if nbytes == 0:
+        raise ValueError(f"{entry} does not support N = {N}, H = {H}, W = {W}, P = {P}, G = {G}, T = {m.T}")
+    dev = m.pred_labels.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    shapes = {"inter": (N, P + 1, G + 1), "pred_rows": (N, P, *row_fields), "gt_area": (N, G, *gt_fields), "match": (N, m.T, P),
+              "gt_match": (N, m.T, G), "counts": (N, _lib.IM_COUNTS)}
+    return L, dev, ws, {k: torch.empty(*shape, dtype=torch.int32, device=dev) for k, shape in shapes.items()}
+
+
 @torch.no_grad()
 def match_instances(pred_labels, gt_labels, pred_table=None, max_pred=None, max_gt=None, thresholds=COCO):
     """``camo_inst_match``: ``pred_labels`` and ``gt_labels`` int32 [N, H, W] (or [H, W]), 0 on background, as ``mask_instances``
@@ -88,48 +140,14 @@ def match_instances(pred_labels, gt_labels, pred_table=None, max_pred=None, max_
     for t, name in ((pred_labels, "pred_labels"), (gt_labels, "gt_labels")):
         if t.dtype != torch.int32:
             raise ValueError(f"{name} must be int32, got {t.dtype}")
-    N, H, W = pred_labels.shape
-    rows = 0
-    if pred_table is not None:
-        if not isinstance(pred_table, torch.Tensor) or pred_table.dtype != torch.int64:
-            raise ValueError("pred_table must be an int64 tensor")
-        if pred_table.dim() == 2:
-            pred_table = pred_table.unsqueeze(0)
-        if pred_table.dim() != 3 or pred_table.shape[0] != N or pred_table.shape[1] < 1 or pred_table.shape[2] != _lib.INST_FIELDS:
-            raise ValueError(f"need pred_table [N = {N}, rows >= 1, {_lib.INST_FIELDS}], got {tuple(pred_table.shape)}")
-        rows = int(pred_table.shape[1])
-    P = _id_bound((rows or 64) if max_pred is None else max_pred, "max_pred")
-    G = _id_bound(64 if max_gt is None else max_gt, "max_gt")
-    if N * (P + 1) * (G + 1) > _lib.IM_MAX_CELLS:
-        raise ValueError(f"max_pred = {P} and max_gt = {G} for {N} images exceed {_lib.IM_MAX_CELLS} table cells")
-    fr, nums, den = match_thresholds(thresholds)
-    T = len(nums)
-    _lib.require_device(pred_labels, "pred_labels")
-    _lib.require_device(gt_labels, "gt_labels")
-    dev = pred_labels.device
-    if gt_labels.device != dev:
-        raise ValueError(f"gt_labels is on {gt_labels.device}, pred_labels on {dev}")
-    pred_labels, gt_labels = pred_labels.detach().contiguous(), gt_labels.detach().contiguous()
-    if pred_table is not None:
-        _lib.require_device(pred_table, "pred_table")
-        if pred_table.device != dev:
-            raise ValueError(f"pred_table is on {pred_table.device}, pred_labels on {dev}")
-        pred_table = pred_table.detach().contiguous()
-    L = _lib.lib()
-    nbytes = L.camo_inst_match_workspace_bytes(N, H, W, P, G, T)
-    if nbytes == 0:
-        raise ValueError(f"camo_inst_match does not support N = {N}, H = {H}, W = {W}, P = {P}, G = {G}, T = {T}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    inter, pred_rows, gt_area = torch.empty(N, P + 1, G + 1, **i32), torch.empty(N, P, 4, **i32), torch.empty(N, G, **i32)
-    match, gt_match, counts = torch.empty(N, T, P, **i32), torch.empty(N, T, G, **i32), torch.empty(N, _lib.IM_COUNTS, **i32)
+    m = _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, thresholds)
+    L, dev, ws, out = _match_buffers("camo_inst_match", m, (4,), ())
     with torch.cuda.device(dev):
-        rc = L.camo_inst_match(_ptr(pred_labels), _ptr(gt_labels), N, H, W, P, G, None if pred_table is None else _ptr(pred_table), rows,
-                               (C.c_int32 * T)(*nums), den, T, _ptr(inter), _ptr(pred_rows), _ptr(gt_area), _ptr(match), _ptr(gt_match),
-                               _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
+        rc = L.camo_inst_match(_ptr(m.pred_labels), _ptr(m.gt_labels), *m.dims, m.table_ptr, m.rows, (C.c_int32 * m.T)(*m.nums), m.den, m.T,
+                               _ptr(out["inter"]), _ptr(out["pred_rows"]), _ptr(out["gt_area"]), _ptr(out["match"]), _ptr(out["gt_match"]),
+                               _ptr(out["counts"]), _ptr(ws), ws.numel(), _stream_ptr(dev))
     _lib.check(rc, "camo_inst_match")
-    return {"inter": inter, "pred_rows": pred_rows, "gt_area": gt_area, "match": match, "gt_match": gt_match, "counts": counts,
-            "thresholds": fr}
+    return {**out, "thresholds": m.fr}
 
 
 def _ratio(a, b):
@@ -243,19 +261,26 @@ def match_detected(pred_labels, pred_table, gt_labels, opts):
     """``match_instances`` and ``instance_match_records`` together, for the pipeline: (records, ``match_instances``' dict).  The
     tables hold ``pred_table``'s rows and ``opts["max_gt"]`` ground-truth ids; when an image carries a label past either, the call
     is made once more with the tables sized to the largest labels (at most CAMO_IM_MAX_IDS), as ``detect_instances`` does."""
+    return _match_detected(partial(match_instances, thresholds=opts["thresholds"]), instance_match_records, pred_labels, pred_table, gt_labels,
+                           opts["max_gt"])
+
+
+def _match_detected(match, records, pred_labels, pred_table, gt_labels, max_gt, keep=()):
+    """``match(pred_labels, gt_labels, pred_table, P, G)`` and ``records`` of its dict, with the second call of ``match_detected``;
+    that call is given the first one's ``keep`` entries as keywords."""
     gt_labels = torch.as_tensor(gt_labels)
     if gt_labels.dim() == 2:
         gt_labels = gt_labels.unsqueeze(0)
     gt_labels = gt_labels.to(device=pred_labels.device, dtype=torch.int32)
-    P, G = min(int(pred_table.shape[1]), _lib.IM_MAX_IDS), int(opts["max_gt"])
-    tables = match_instances(pred_labels, gt_labels, pred_table, P, G, opts["thresholds"])
-    rec = instance_match_records(tables)
+    P, G = min(int(pred_table.shape[1]), _lib.IM_MAX_IDS), int(max_gt)
+    tables = match(pred_labels, gt_labels, pred_table, P, G)
+    rec = records(tables)
     if any(r["truncated_pred"] or r["truncated_gt"] for r in rec):
         P2 = min(max(P, int(pred_labels.max())), _lib.IM_MAX_IDS)
         G2 = min(max(G, int(gt_labels.max())), _lib.IM_MAX_IDS)
         if (P2, G2) != (P, G):
-            tables = match_instances(pred_labels, gt_labels, pred_table, P2, G2, opts["thresholds"])
-            rec = instance_match_records(tables)
+            tables = match(pred_labels, gt_labels, pred_table, P2, G2, **{k: tables[k] for k in keep})
+            rec = records(tables)
     return rec, tables
 
 

@@ -16,6 +16,7 @@ import torch
 
 import boundary_ref as B
 import inst_match_ref as R
+import test_inst_match as M
 from conftest import ROOT
 from guarded import Arrays
 
@@ -283,6 +284,22 @@ def test_the_strips_case_orders_differently_under_each_of_the_three_ious():
     assert ties["match"][0].tolist() == [[1], [0]] and ties["pred_rows"][0].tolist() == [[4, 0, 1, 2, 4, 2]]      # equal fractions: the smaller id
 
 
+def _is_the_mask_match(got, plain, what):
+    """`got`, the combined match with the label maps as their own boundary maps, against `plain`, the mask-only match: bd_cand keeps the
+    mask fraction where the two are equal, so every shared output is the same bytes and the boundary fields repeat the mask's."""
+    names = ("inter", "match", "gt_match", "counts", "pred_rows", "gt_area")
+    _same({**got, "pred_rows": np.ascontiguousarray(got["pred_rows"][..., :4]), "gt_area": np.ascontiguousarray(got["gt_area"][..., 0])}, plain, what, names)
+    assert got["inter_bd"].tobytes() == got["inter"].tobytes(), what
+    assert (got["pred_rows"][..., 4] == got["pred_rows"][..., 0]).all() and (got["pred_rows"][..., 5] == got["pred_rows"][..., 3]).all(), what
+    assert (got["gt_area"][..., 1] == got["gt_area"][..., 0]).all(), what
+
+
+def test_with_the_label_maps_as_boundary_maps_the_restated_match_is_the_mask_match():
+    for name in M.CASES:
+        pred, gt, P, G, table, thr = M._case(name)
+        _is_the_mask_match(B.boundary_match_ref(pred, gt, pred, gt, P, G, table, thr), M._ref(name), name)
+
+
 def test_argument_errors_by_name_and_no_cpu_path():
     from camouflage_multimodal_amd import boundary as bd
     from camouflage_multimodal_amd._lib import CamoError
@@ -509,6 +526,16 @@ def test_boundary_match_equals_the_restatement_bytewise(name):
     pb, gb = _match_maps(name)
     for fill in (0x00, 0xFF):
         _same(_raw_match(pred, gt, pb, gb, P, G, table, thr, fill), _match_ref(name), (name, fill))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", M.CASES)
+def test_with_the_label_maps_as_boundary_maps_the_match_is_camo_inst_matchs_bytewise(name):
+    """The two instantiations of the one match kernel, held to each other on test_inst_match's cases."""
+    pred, gt, P, G, table, thr = M._case(name)
+    plain = M._raw(pred, gt, P, G, table, thr)
+    for fill in (0x00, 0xFF):
+        _is_the_mask_match(_raw_match(pred, gt, pred, gt, P, G, table, thr, fill), plain, (name, fill))
 
 
 @pytest.mark.gpu
