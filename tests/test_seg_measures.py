@@ -6,7 +6,9 @@ restatement from the pixel arrays the checker.  CPU tests hold the restatement t
 the restatement's ratios taken from the pixels (1e-12 absolute: both are float64 formulas of about 20 operations on values in
 [0, 1], whose rounding is of order 1e-15), the split rule at its ties and the library's argument checks to the header.  GPU tests
 hold the kernels to the restatement: hist and split equal, integer for integer; two calls the same bytes; a batch the rows of its
-images; a channel of [N, 3, H, W] read in place.
+images; a channel of [N, 3, H, W] read in place.  The device shapes here are 3 x 33 x 70 (one block an image) and 1 x 130 x 257 (nine
+blocks, one trip of the fill kernel's loop); test_seg_measures_sizes.py holds the same checks at the sizes where the kernels take
+another path: past SEGM_MAX_BLOCKS blocks, at the SEGM_UNIFORM_LANES threshold, and at images of 2 to 70 pixels and of width 1 to 3.
 
 Hand cases (n pixels, G positive; eps terms left out).  E-phi of a perfect binary prediction is n / (n - 1): phi = 1 on every pixel
 and the header divides by n - 1 + eps, so "1" is reached only in the limit of large images -- 4/3 at 2 x 2, 12/11 at 3 x 4.

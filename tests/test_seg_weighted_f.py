@@ -4,7 +4,9 @@ The restatement takes the distance transform by brute force over all pairs of pi
 scipy.ndimage.distance_transform_edt (distances only: scipy's tie rule is unspecified, so indices are not compared).
 Bounds of the GPU tests: n_fg exact; A_fg and A_bg within H * W units of 2^-32 of the restatement -- per pixel the device's and
 numpy's double exp / sqrt / FMA contraction differ by a few 1e-16, far below 2^-32 = 2.3e-10, so llrint can differ by at most one
-unit on a pixel; two calls the same bytes; F-beta-w within 1e-6.
+unit on a pixel; two calls the same bytes; F-beta-w within 1e-6.  The device shapes here are 33 x 70 and the 5 x 9 tie case, whose two
+positive pixels share a row: W stays below SEGM_NT and the tie shows only the "smaller x'" half of the rule.  test_seg_measures_sizes.py
+runs `_check` at widths and heights past SEGM_NT, at a side of SEG_WF_MAX_SIDE, and on a diagonal and a column tie.
 
 Hand cases (K = the normalised 7 x 7 kernel, K[3, 3] its centre):
   a perfect binary prediction: E = 0 everywhere, sums (n_fg, 0, 0), R = 1, P = n_fg / (n_fg + eps), F-beta-w = 1 up to eps terms.
