@@ -8,6 +8,22 @@ MAX_IMAGE_PIXELS = 1 << 26      # CAMO_RGD_MAX_IMAGE_PIXELS
 COCO = tuple(Fraction(n, 20) for n in range(10, 20))
 
 
+def blocks(H, W, ids, seed, cell=4):
+    """A [H, W] case map of cell x cell blocks with ids 0 .. ids (test_inst_match, test_boundary; test_rle with cell = 3)."""
+    rng = np.random.default_rng(seed)
+    coarse = rng.integers(0, ids + 1, ((H + cell - 1) // cell, (W + cell - 1) // cell))
+    return np.kron(coarse, np.ones((cell, cell), np.int64))[:H, :W]
+
+
+def score_table(N, rows, seed):
+    """A [N, rows, 8] case table as camo_instances writes it: random areas and score sums, the other fields 0."""
+    rng = np.random.default_rng(seed)
+    area = rng.integers(1, 200, (N, rows))
+    t = np.zeros((N, rows, 8), np.int64)
+    t[..., 0], t[..., 7] = area, rng.integers(0, 255 * area + 1)
+    return t
+
+
 def overlap(pred, gt, P, G):
     """(inter int64 [P + 1, G + 1], pixels with pred out of 0 .. P, pixels with gt out of 0 .. G) of two [H, W] label maps."""
     pred, gt = np.asarray(pred, np.int64).ravel(), np.asarray(gt, np.int64).ravel()

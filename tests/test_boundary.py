@@ -18,11 +18,10 @@ import boundary_ref as B
 import inst_match_ref as R
 import test_inst_match as M
 from conftest import ROOT
-from guarded import Arrays
+from inst_match_ref import blocks as _blocks, score_table as _table
+from raw_calls import BOUNDARY_MATCH_NAMES as MATCH_NAMES, BUILDERS, execute, same_bytes
 
 from camouflage_multimodal_amd._lib import BD_STRIP as STRIP      # the column pass's strip height; test_header_constants holds it to the kernel's constant
-
-MATCH_NAMES = ("inter", "inter_bd", "pred_rows", "gt_area", "match", "gt_match", "counts")
 
 
 def _discs(N, H, W, seed, ids=5):
@@ -35,20 +34,6 @@ def _discs(N, H, W, seed, ids=5):
             cy, cx, r = rng.integers(0, H), rng.integers(0, W), rng.integers(2, max(3, min(max(H, W), 40) // 2))
             out[n][(y - cy) ** 2 + (x - cx) ** 2 <= r * r] = k
     return out
-
-
-def _blocks(H, W, ids, seed, cell=4):
-    rng = np.random.default_rng(seed)
-    coarse = rng.integers(0, ids + 1, ((H + cell - 1) // cell, (W + cell - 1) // cell))
-    return np.kron(coarse, np.ones((cell, cell), np.int64))[:H, :W]
-
-
-def _table(N, rows, seed):
-    rng = np.random.default_rng(seed)
-    area = rng.integers(1, 200, (N, rows))
-    t = np.zeros((N, rows, 8), np.int64)
-    t[..., 0], t[..., 7] = area, rng.integers(0, 255 * area + 1)
-    return t
 
 
 def _hand():
@@ -199,10 +184,8 @@ def _match_ref(name):
 
 
 def _same(got, want, what, names=MATCH_NAMES):
-    for k in names:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.dtype == w.dtype == np.int32 and g.shape == w.shape, (what, k, g.dtype, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k, np.argwhere(g != w)[:5].tolist())
+    assert all(np.asarray(want[k]).dtype == np.int32 for k in names)
+    same_bytes(got, want, what, names)
 
 
 # ---- CPU: the restatement itself, and the host side of the binding ----------------------------------------------------------
@@ -425,57 +408,13 @@ def test_workspace_and_argument_checks_of_the_library():
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 
-def _fill(piece, array):
-    piece.copy_(torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1)).cuda())
-
-
 def _raw_labels(lab, d, fill):
-    """camo_boundary_labels through ctypes, every buffer between guard bytes filled with `fill` -> out as numpy."""
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    N, H, W = lab.shape
-    nbytes = L.camo_boundary_labels_workspace_bytes(N, H, W, d)
-    assert nbytes > 0 and nbytes % 256 == 0
-    A = Arrays({"labels": ((N, H, W), np.int32), "out": ((N, H, W), np.int32), "ws": nbytes}, fill)
-    _fill(A.piece["labels"], lab)
-    rc = L.camo_boundary_labels(A.ptr("labels"), N, H, W, d, A.ptr("out"), A.ptr("ws"), nbytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    got = A.collect()
-    assert got["labels"].tobytes() == lab.tobytes(), "the input was written"
-    return got["out"]
-
-
-def _fractions(thr):
-    den = 1
-    for f in thr:
-        den = den * f.denominator // math.gcd(den, f.denominator)
-    return [int(f * den) for f in thr], int(den)
+    """camo_boundary_labels with every buffer -- input, output, workspace -- between guard bytes filled with `fill` -> out as numpy."""
+    return execute(BUILDERS["camo_boundary_labels"](lab, d), fill)["out"]
 
 
 def _raw_match(pred, gt, pb, gb, P, G, table, thr, fill):
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    N, H, W = pred.shape
-    T = len(thr)
-    nums, den = _fractions(thr)
-    nbytes = L.camo_boundary_match_workspace_bytes(N, H, W, P, G, T)
-    assert nbytes > 0 and nbytes % 256 == 0
-    spec = {"pl": ((N, H, W), np.int32), "gl": ((N, H, W), np.int32), "pb": ((N, H, W), np.int32), "gb": ((N, H, W), np.int32),
-            "inter": ((N, P + 1, G + 1), np.int32), "inter_bd": ((N, P + 1, G + 1), np.int32), "pred_rows": ((N, P, 6), np.int32),
-            "gt_area": ((N, G, 2), np.int32), "match": ((N, T, P), np.int32), "gt_match": ((N, T, G), np.int32), "counts": ((N, 4), np.int32), "ws": nbytes}
-    if table is not None:
-        spec["table"] = (table.shape, np.int64)
-    A = Arrays(spec, fill)
-    for k, v in (("pl", pred), ("gl", gt), ("pb", pb), ("gb", gb)) + ((("table", table),) if table is not None else ()):
-        _fill(A.piece[k], v)
-    rc = L.camo_boundary_match(A.ptr("pl"), A.ptr("gl"), A.ptr("pb"), A.ptr("gb"), N, H, W, P, G, None if table is None else A.ptr("table"),
-                               0 if table is None else table.shape[1], (ctypes.c_int32 * T)(*nums), den, T, *(A.ptr(k) for k in MATCH_NAMES), A.ptr("ws"),
-                               nbytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    got = A.collect()
-    for k, v in (("pl", pred), ("gl", gt), ("pb", pb), ("gb", gb)):
-        assert got[k].tobytes() == v.tobytes(), f"the input {k} was written"
-    return {k: got[k] for k in MATCH_NAMES}
+    return execute(BUILDERS["camo_boundary_match"](pred, gt, pb, gb, P, G, table, thr), fill)
 
 
 @pytest.mark.gpu

@@ -4,7 +4,9 @@ Every header under include/ says that the contents of a workspace and of an outp
 tests take both from torch.empty, which in a fresh process is mostly zero: a clear that is missing, covers the wrong extent or is
 skipped for one mode passes them, and so does a carve a few elements short of what the kernels index.  Here every C entry point that
 takes a workspace, or clears and accumulates into a caller array, is called through ctypes with the workspace of exactly
-``*_workspace_bytes`` bytes and every output in a guarded tensor of its own (tests/guarded.py), in three variants:
+``*_workspace_bytes`` bytes and every input and output in a guarded tensor of its own, in three variants (the harness -- ``Call``,
+``execute`` and one builder of a Call per entry point -- is tests/raw_calls.py on tests/guarded.py, shared with the modules' own tests;
+this file keeps the cases):
 
   clean   every byte of the workspace and of the outputs is 0.  Held to the module's reference exactly as the module's own test
           holds it: integers bytewise, floats with that test's bound, magnitudes from the reference.  No tolerance is new here.
@@ -28,7 +30,6 @@ Four calls with per-pixel workspace pieces run once more at a pixel count one pa
 short moves the pieces behind it (the note in front of that test).  The last part runs the clears that go over a capped grid with a
 stride loop past their caps, on 0xFF memory, against the numpy references bytewise: sizes the modules' own cases never reach, so the
 stride was never taken."""
-import ctypes
 import functools
 from fractions import Fraction as F
 from types import SimpleNamespace
@@ -56,64 +57,17 @@ import test_rg_targets as TT
 import test_rle as TR
 import test_seg_measures as TS
 import test_slic as TSL
-from guarded import Arrays
 from oracle import rg_features_oracle as RO
+from raw_calls import BUILDERS, execute, same_bytes as _same_bytes
 
 N3, H3, W3 = 3, 70, 133             # the free shape: more than one tile each way, a multiple of no tile or chunk, image 1 at an odd byte offset
 VARIANTS = ("clean", "0xFF", "stale")
-
-
-def _lib():
-    from camouflage_multimodal_amd import _lib as B
-    return B.lib()
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()         # (a writable, contiguous copy: the cached cases are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _t(a):
     """H and W exchanged: [N, H, W, ...] -> [N, W, H, ...]."""
     a = np.asarray(a)
     return np.ascontiguousarray(a.transpose((0, 2, 1) + tuple(range(3, a.ndim))))
-
-
-class Call:
-    """One call of an entry point: ``outs`` name -> (shape, dtype) of the caller arrays it writes, ``ws`` its workspace size in bytes
-    (0: it takes none), ``invoke(ptr, ws_ptr, ws_bytes)`` -> the return code, ``init`` name -> the array an in-out argument holds."""
-
-    def __init__(self, outs, ws, invoke, init=None):
-        self.outs, self.ws, self.invoke, self.init = outs, int(ws), invoke, init or {}
-
-
-def _execute(call, fill, before=()):
-    """``call`` on buffers filled with ``fill``, after the calls of ``before`` on the same buffers -> the outputs as numpy."""
-    L = _lib()
-    spec = dict(call.outs)
-    room = max([call.ws] + [c.ws for c in before])
-    if call.ws:
-        assert call.ws % 256 == 0
-        spec["ws"] = room
-    A = Arrays(spec, fill)
-    for c in list(before) + [call]:
-        for k, (shape, dtype) in c.outs.items():
-            assert int(np.prod(shape)) * np.dtype(dtype).itemsize == A.nbytes(k), (k, shape)
-        if c is call and call.ws:
-            A.refill("ws", call.ws)
-        for k, a in c.init.items():
-            A.piece[k].copy_(torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)))
-        rc = c.invoke({k: A.ptr(k) for k in c.outs}, A.ptr("ws") if c.ws else None, c.ws)
-        assert rc == 0, L.camo_last_error()
-        A.check_guards()
-    got = A.collect()
-    if call.ws:
-        assert A.tail_intact("ws", call.ws), "the workspace was written past the size the call was given"
-        del got["ws"]
-    return got
 
 
 class Entry:
@@ -127,18 +81,10 @@ class Entry:
     def run(self, variant):
         case = self.build("case")
         if variant == "clean":
-            return _execute(case, 0x00)
+            return execute(case, 0x00)
         if variant == "0xFF":
-            return _execute(case, 0xFF)
-        return _execute(case, 0xFF, before=(self.build("busy"), self.build("swapped")))
-
-
-def _same_bytes(got, want, what):
-    assert sorted(got) == sorted(want)
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, k, g.dtype, w.dtype, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k, np.argwhere(g != w)[:5].tolist())
+            return execute(case, 0xFF)
+        return execute(case, 0xFF, before=(self.build("busy"), self.build("swapped")))
 
 
 # ---- Canny ------------------------------------------------------------------------------------------------------------------
@@ -155,10 +101,7 @@ class Canny(Entry):
             img = np.random.RandomState(1).uniform(0, 1, img.shape).astype(np.float32)
         if variant == "swapped":
             img = _t(img)
-        L, d = _lib(), _dev(img)
-        N, H, W = img.shape[:3]
-        return Call({"edges": ((N, H, W), np.uint8), "grad": ((N, 3, H, W), np.float32)}, L.camo_canny_workspace_bytes(N, H, W),
-                    lambda p, w, nb: L.camo_canny(d.data_ptr(), N, H, W, 2.0, 0.1, 0.2, w, nb, p["edges"], p["grad"], _stream()))
+        return BUILDERS["camo_canny"](img, 2.0, 0.1, 0.2)
 
     def check(self, got):
         e, g = got["edges"], got["grad"]
@@ -187,11 +130,7 @@ class Hysteresis(Entry):
         self.shape = shape
 
     def build(self, variant):
-        cls = _class_maps(variant, self.shape)
-        L, d = _lib(), _dev(cls)
-        N, H, W = cls.shape
-        return Call({"edges": ((N, H, W), np.uint8)}, L.camo_canny_workspace_bytes(N, H, W),
-                    lambda p, w, nb: L.camo_canny_hysteresis(d.data_ptr(), N, H, W, w, nb, p["edges"], _stream()))
+        return BUILDERS["camo_canny_hysteresis"](_class_maps(variant, self.shape))
 
     @functools.lru_cache(maxsize=None)
     def _want(self):
@@ -217,12 +156,7 @@ class Slic(Entry):
             img = np.random.RandomState(3).uniform(0, 1, img.shape).astype(np.float32)
         if variant == "swapped":
             img = _t(img)
-        L, d = _lib(), _dev(img)
-        N, H, W = img.shape[:3]
-        ws = L.camo_slic_workspace_bytes(N, H, W, n)
-        assert ws > 0
-        return Call({"labels": ((N, H, W), np.int32), "counts": ((N, 2), np.int32)}, ws,
-                    lambda p, w, nb: L.camo_slic(d.data_ptr(), N, H, W, n, 10.0, 1.0, w, nb, p["labels"], p["counts"], _stream()))
+        return BUILDERS["camo_slic"](img, n, 10.0, 1.0)
 
     def check(self, got):
         for k in range(len(got["labels"])):
@@ -249,11 +183,7 @@ class SlicConnect(Entry):
         self.shape = shape
 
     def build(self, variant):
-        maps = _salted_maps(variant, self.shape)
-        L, d = _lib(), _dev(maps)
-        N, H, W = maps.shape
-        return Call({"labels": ((N, H, W), np.int32), "counts": ((N, 2), np.int32)}, L.camo_slic_workspace_bytes(N, H, W, 0),
-                    lambda p, w, nb: L.camo_slic_connect(d.data_ptr(), N, H, W, 6, 10 ** 6, w, nb, p["labels"], p["counts"], _stream()))
+        return BUILDERS["camo_slic_connect"](_salted_maps(variant, self.shape), 6, 10 ** 6)
 
     @functools.lru_cache(maxsize=None)
     def _want(self):
@@ -290,12 +220,7 @@ class SlicUpdate(Entry):
         return lab, near, cent
 
     def build(self, variant):
-        lab, near, cent = self._arrays(variant)
-        L, dl, dn = _lib(), _dev(lab), _dev(near)
-        (N, H, W), K = near.shape, cent.shape[1]
-        return Call({"sums": ((N, K, 6), np.int64), "centroids": ((N, K, 5), np.float32)}, 0,
-                    lambda p, w, nb: L.camo_slic_update(dl.data_ptr(), dn.data_ptr(), N, H, W, K, p["sums"], p["centroids"], _stream()),
-                    init={"centroids": cent})
+        return BUILDERS["camo_slic_update"](*self._arrays(variant))
 
     def declared(self, got):
         return {"centroids": got["centroids"]}
@@ -350,16 +275,6 @@ def _check_single_graph(got, want, std_floor=None):
     assert (np.abs(got["edge_attr"] - ea) <= M.w_bound(ea)).all()
 
 
-def _single_graph_call(img, seg, canny, n_labels, cap):
-    L, di, ds, dc = _lib(), _dev(img), _dev(seg), _dev(canny)
-    H, W = seg.shape
-    outs = {"x": ((n_labels, 15), np.float32), "region_map": ((n_labels,), np.int32), "edge_index": ((2, cap), np.int64),
-            "edge_attr": ((cap,), np.float32), "counts": ((2,), np.int32)}
-    return Call(outs, L.camo_rg_graph_workspace_bytes(n_labels),
-                lambda p, w, nb: L.camo_rg_region_graph(di.data_ptr(), ds.data_ptr(), dc.data_ptr(), H, W, n_labels, w, nb, p["x"], p["region_map"],
-                                                        p["edge_index"], p["edge_attr"], cap, p["counts"], _stream()))
-
-
 class RegionGraph(Entry):
     """camo_rg_region_graph on image 1 of the free shape (it starts at an odd byte offset of the canny batch) against the oracle with
     the project's bounds, the edge capacity exactly the need.  REFERENCE: the per-region sums are doubles added by atomics in arrival
@@ -369,23 +284,10 @@ class RegionGraph(Entry):
 
     def build(self, variant):
         img, seg, canny = _graph_inputs(variant)
-        return _single_graph_call(img[1], seg[1], canny[1], 41, _graph_oracle(1)[1].shape[1])
+        return BUILDERS["camo_rg_region_graph"](img[1], seg[1], canny[1], 41, _graph_oracle(1)[1].shape[1])
 
     def check(self, got):
         _check_single_graph(got, _graph_oracle(1))
-
-
-def _batch_graph_call(img, seg, canny, lb, cap):
-    L, di, ds, dc = _lib(), _dev(img), _dev(seg), _dev(canny)
-    N, H, W = seg.shape
-    nodes = N * lb
-    outs = {"x": ((nodes, 15), np.float32), "region_map": ((N, lb), np.int32), "edge_index": ((2, cap), np.int64), "edge_attr": ((cap,), np.float32),
-            "node_off": ((N + 1,), np.int32), "edge_off": ((N + 1,), np.int32), "batch": ((nodes,), np.int32), "status": ((2,), np.int32)}
-    ws = L.camo_rg_batch_workspace_bytes(N, H, W, lb)
-    assert ws > 0
-    return Call(outs, ws, lambda p, w, nb: L.camo_rg_region_graph_batch(
-        di.data_ptr(), ds.data_ptr(), dc.data_ptr(), N, H, W, lb, w, nb, p["x"], nodes, p["region_map"], p["edge_index"], p["edge_attr"], cap,
-        p["node_off"], p["edge_off"], p["batch"], p["status"], _stream()))
 
 
 def _declared_batch_graph(got):
@@ -411,22 +313,13 @@ class RegionGraphBatch(Entry):
 
     def build(self, variant):
         img, seg, canny = _graph_inputs(variant)
-        return _batch_graph_call(img, seg, canny, 41, sum(_graph_oracle(k)[1].shape[1] for k in range(N3)))
+        return BUILDERS["camo_rg_region_graph_batch"](img, seg, canny, 41, sum(_graph_oracle(k)[1].shape[1] for k in range(N3)))
 
     def declared(self, got):
         return _declared_batch_graph(got)
 
     def check(self, got):
         _check_batch_graph(got, [_graph_oracle(k) for k in range(N3)], "70 x 133 batch")
-
-
-def _targets_call(seg, rmap, off, gt, inst, edge, n_nodes, band, emin):
-    L = _lib()
-    d = [_dev(a) for a in (seg, rmap, np.asarray(off, np.int32), gt, inst, edge)]
-    N, H, W = seg.shape
-    outs = {"counts": ((n_nodes, 4), np.int32), "mask_t": ((n_nodes,), np.int32), "inst_t": ((n_nodes,), np.int32), "edge_t": ((n_nodes,), np.float32)}
-    return Call(outs, 0, lambda p, w, nb: L.camo_rg_node_targets(*(t.data_ptr() for t in d), N, H, W, rmap.shape[1], n_nodes, band, emin,
-                                                                 p["counts"], p["mask_t"], p["inst_t"], p["edge_t"], _stream()))
 
 
 class NodeTargets(Entry):
@@ -447,8 +340,8 @@ class NodeTargets(Entry):
         return seg, rmap, off, gt, inst, edge
 
     def build(self, variant):
-        seg, rmap, off, gt, inst, edge = self._arrays(variant)
-        return _targets_call(seg, rmap, off, gt, inst, edge, int(off[-1]), 100, 3)
+        arrays = self._arrays(variant)
+        return BUILDERS["camo_rg_node_targets"](*arrays, int(arrays[2][-1]), 100, 3)
 
     def check(self, got):
         seg, rmap, off, gt, inst, edge = self._arrays("case")
@@ -500,13 +393,7 @@ class Instances(Entry):
         self.connectivity, self.fill, self.shape = connectivity, fill, shape
 
     def build(self, variant):
-        pred = _instance_maps(variant, self.shape)
-        L, d = _lib(), _dev(pred)
-        N, H, W = pred.shape
-        outs = {"labels": ((N, H, W), np.int32), "clean": ((N, H, W), np.uint8), "table": ((N, 64, 8), np.int64), "counts": ((N, 4), np.int32)}
-        return Call(outs, L.camo_instances_workspace_bytes(N, H, W),
-                    lambda p, w, nb: L.camo_instances(d.data_ptr(), H * W, 0.5, N, H, W, self.connectivity, 5, int(self.fill), 64,
-                                                      p["labels"], p["clean"], p["table"], p["counts"], w, nb, _stream()))
+        return BUILDERS["camo_instances"](_instance_maps(variant, self.shape), 0.5, self.connectivity, 5, self.fill, 64)
 
     def check(self, got):
         want = _instances_ref(self.connectivity, self.fill, self.shape)
@@ -517,21 +404,6 @@ class Instances(Entry):
 @functools.lru_cache(maxsize=None)
 def _instances_ref(connectivity, fill, shape=(N3, H3, W3)):
     return IR.instances(_instance_maps("case", shape), 0.5, connectivity, 5, fill, 64)
-
-
-def _match_call(pred, gt, P, G, table, thr):
-    L = _lib()
-    N, H, W = pred.shape
-    T = len(thr)
-    nums, den = TM._fractions(thr)
-    dp, dg, dt = _dev(pred), _dev(gt), None if table is None else _dev(table)
-    shapes = {"inter": (N, P + 1, G + 1), "pred_rows": (N, P, 4), "gt_area": (N, G), "match": (N, T, P), "gt_match": (N, T, G), "counts": (N, 4)}
-    ws = L.camo_inst_match_workspace_bytes(N, H, W, P, G, T)
-    assert ws > 0
-    return Call({k: (shapes[k], np.int32) for k in TM.NAMES}, ws,
-                lambda p, w, nb: L.camo_inst_match(dp.data_ptr(), dg.data_ptr(), N, H, W, P, G, None if dt is None else dt.data_ptr(),
-                                                   0 if dt is None else dt.shape[1], (ctypes.c_int32 * T)(*nums), den, T,
-                                                   *(p[k] for k in TM.NAMES), w, nb, _stream()))
 
 
 class InstMatch(Entry):
@@ -545,17 +417,10 @@ class InstMatch(Entry):
             pred, gt = rs.randint(0, P + 1, pred.shape).astype(np.int32), rs.randint(0, G + 1, gt.shape).astype(np.int32)
         if variant == "swapped":
             pred, gt = _t(pred), _t(gt)
-        return _match_call(pred, gt, P, G, table, thr)
+        return BUILDERS["camo_inst_match"](pred, gt, P, G, table, thr)
 
     def check(self, got):
-        TM._same(got, TM._ref("batch"), "batch")
-
-
-def _runs_call(labels, R_):
-    L, d = _lib(), _dev(labels)
-    N, H, W = labels.shape
-    return Call({"runs": ((N, R_, 2), np.int32), "counts": ((N, 2), np.int32)}, L.camo_rle_runs_workspace_bytes(N, H, W, R_),
-                lambda p, w, nb: L.camo_rle_runs(d.data_ptr(), N, H, W, R_, p["runs"], p["counts"], w, nb, _stream()))
+        _same_bytes(got, TM._ref("batch"), "batch")
 
 
 class RleRuns(Entry):
@@ -569,23 +434,11 @@ class RleRuns(Entry):
             labels = ((xx + yy) % 2 * 9).astype(np.int32)
         if variant == "swapped":
             labels = _t(labels)
-        return _runs_call(labels, R_)
+        return BUILDERS["camo_rle_runs"](labels, R_)
 
     def check(self, got):
         labels, R_ = TR._case("batch")
-        TR._same(got, RR.runs_batch(labels, R_), "batch")
-
-
-def _decode_call(arrays, N, H, W):
-    cnts, off, img, val = arrays
-    L = _lib()
-    A, total = len(img), len(cnts)
-    d = [_dev(np.asarray(v, np.int32).reshape(-1)) for v in (cnts, off, img, val)]
-    ws = L.camo_rle_decode_workspace_bytes(N, H, W, A, total)
-    assert ws > 0 and total > 0
-    return Call({"labels": ((N, H, W), np.int32), "ann_sum": ((A,), np.int64)}, ws,
-                lambda p, w, nb: L.camo_rle_decode(d[0].data_ptr(), total, *(t.data_ptr() for t in d[1:]), A, N, H, W, p["labels"], p["ann_sum"],
-                                                   w, nb, _stream()))
+        _same_bytes(got, RR.runs_batch(labels, R_), "batch")
 
 
 @functools.lru_cache(maxsize=None)
@@ -614,13 +467,13 @@ class RleDecode(Entry):
     calls give the same bytes and test_decode_of_many_annotations_over_three_images compares the raw call's bytes with the wrapper's."""
 
     def build(self, variant):
-        return _decode_call(*_annotations(variant))
+        return BUILDERS["camo_rle_decode"](*_annotations(variant))
 
     def check(self, got):
         arrays, N, H, W = _annotations("case")
         want = RR.decode(*arrays, N, H, W)
         assert (want[1] == H * W).all() and want[0].any()
-        TR._same(got, dict(zip(("labels", "ann_sum"), want)), "forty annotations")
+        _same_bytes(got, dict(zip(("labels", "ann_sum"), want)), "forty annotations")
 
 
 # ---- guided filter and the segmentation measures -------------------------------------------------------------------------------------
@@ -643,13 +496,7 @@ class Guided(Entry):
         return (_t(guide), _t(p)) if variant == "swapped" else (guide, p)
 
     def build(self, variant):
-        guide, p = self._arrays(variant)
-        L, dg, dp = _lib(), _dev(guide), _dev(p)
-        N, H, W = p.shape
-        C = self.C
-        return Call({"q": ((N, H, W), np.float32), "coef": ((N, C + 1, H, W), np.float32)}, L.camo_guided_workspace_bytes(N, H, W, C),
-                    lambda q, w, nb: L.camo_guided_filter(dg.data_ptr(), dp.data_ptr(), H * W, N, H, W, C, self.r, self.eps, 0, q["q"], q["coef"],
-                                                          w, nb, _stream()))
+        return BUILDERS["camo_guided_filter"](*self._arrays(variant), self.C, self.r, self.eps)
 
     @functools.lru_cache(maxsize=None)
     def _refs(self):
@@ -683,10 +530,7 @@ class SegHistograms(Entry):
 
     def build(self, variant):
         maps, gt = _measure_maps(variant)
-        L, dm, dg = _lib(), _dev(maps), _dev(gt)
-        N, H, W = gt.shape
-        return Call({"hist": ((N, 4, 2, 256), np.int32), "split": ((N, 2), np.int32)}, 0,
-                    lambda p, w, nb: L.camo_seg_histograms(dm.data_ptr() + 4 * H * W, 3 * H * W, dg.data_ptr(), N, H, W, p["hist"], p["split"], _stream()))
+        return BUILDERS["camo_seg_histograms"](maps, 1, gt)
 
     def check(self, got):
         _, _, hist, split = TS._images()[0]
@@ -698,14 +542,8 @@ class SegWeightedF(Entry):
     test_seg_weighted_f._check.  BYTEWISE: that check asserts two calls give the same bytes (integer atomics after block-level sums)."""
 
     def build(self, variant):
-        from camouflage_multimodal_amd.seg_measures import gaussian_7x7
         maps, gt = _measure_maps(variant)
-        L, dm, dg = _lib(), _dev(maps), _dev(gt)
-        gauss = _dev(np.asarray(gaussian_7x7(), np.float64).reshape(-1))
-        N, H, W = gt.shape
-        return Call({"sums": ((N, 3), np.int64)}, L.camo_seg_weighted_f_workspace_bytes(N, H, W),
-                    lambda p, w, nb: L.camo_seg_weighted_f(dm.data_ptr() + 4 * H * W, 3 * H * W, dg.data_ptr(), N, H, W, gauss.data_ptr(), w, nb,
-                                                           p["sums"], _stream()))
+        return BUILDERS["camo_seg_weighted_f"](maps, 1, gt)
 
     @staticmethod
     @functools.lru_cache(maxsize=None)
@@ -739,10 +577,7 @@ class SegCounts(Entry):
 
     def build(self, variant):
         maps, gt = self._arrays(variant)
-        L, dm, dg = _lib(), _dev(maps), _dev(gt)
-        N, H, W = gt.shape
-        return Call({"counts": ((N, 5), np.int64)}, 0,
-                    lambda p, w, nb: L.camo_seg_counts(dm.data_ptr() + 4 * H * W, 3 * H * W, dg.data_ptr(), 0.5, N, H, W, p["counts"], _stream()))
+        return BUILDERS["camo_seg_counts"](maps, 1, gt, 0.5)
 
     def check(self, got):
         maps, gt = self._arrays("case")
@@ -810,7 +645,7 @@ def test_workspace_pieces_that_end_one_element_past_a_256_byte_boundary(name):
     """The entry points with per-pixel workspace pieces at 35 x 139 (the note above), workspace and outputs 0xFF, held to the reference
     as in the table above; the workspace guard is the check on the carve."""
     entry = CARVED[name]
-    entry.check(_execute(entry.build("case"), 0xFF))
+    entry.check(execute(entry.build("case"), 0xFF))
 
 
 # ---- the clears past their grid caps, on 0xFF memory ----------------------------------------------------------------------------
@@ -827,9 +662,9 @@ def test_decode_clears_label_maps_of_more_than_2_to_20_pixels():
     a[100:300, 50:700] = True
     b[400:650, 10:715] = True
     arrays = TR._annotation_arrays([[(RR.mask_counts(a), 3)], [(RR.mask_counts(b), 7)]])
-    got = _execute(_decode_call(arrays, N, H, W), 0xFF)
+    got = execute(BUILDERS["camo_rle_decode"](arrays, N, H, W), 0xFF)
     want = RR.decode(*arrays, N, H, W)
-    TR._same(got, dict(zip(("labels", "ann_sum"), want)), "725 x 725")
+    _same_bytes(got, dict(zip(("labels", "ann_sum"), want)), "725 x 725")
     assert got["labels"].sum() == 3 * a.sum() + 7 * b.sum() and not got["labels"][0][~a].any() and not got["labels"][1][~b].any()
 
 
@@ -839,11 +674,11 @@ def test_match_clears_overlap_tables_of_more_than_2_to_20_cells(N, ids):
     """camo_inst_match with N (P + 1) (G + 1) = 2^21 and 1.3 * 2^20 cells, past the 4096 blocks x 256 threads of one pass of
     im_clear_kernel: 64 x 64 maps of 4 x 4 blocks of random ids, one threshold, the buffers 0xFF, against inst_match_ref bytewise."""
     assert N * (ids + 1) ** 2 > 1 << 20
-    pred = np.stack([TM._blocks(64, 64, ids, 60 + n) for n in range(N)]).astype(np.int32)
-    gt = np.stack([np.roll(TM._blocks(64, 64, ids, 80 + n), 2, 1) for n in range(N)]).astype(np.int32)
+    pred = np.stack([IMR.blocks(64, 64, ids, 60 + n) for n in range(N)]).astype(np.int32)
+    gt = np.stack([np.roll(IMR.blocks(64, 64, ids, 80 + n), 2, 1) for n in range(N)]).astype(np.int32)
     thr = (F(1, 2),)
-    got = _execute(_match_call(pred, gt, ids, ids, None, thr), 0xFF)
-    TM._same(got, IMR.match_batch(pred, gt, ids, ids, None, thr), f"{N} x {ids} ids")
+    got = execute(BUILDERS["camo_inst_match"](pred, gt, ids, ids, None, thr), 0xFF)
+    _same_bytes(got, IMR.match_batch(pred, gt, ids, ids, None, thr), f"{N} x {ids} ids")
     assert got["inter"].sum() == N * 64 * 64
 
 
@@ -861,7 +696,7 @@ def test_node_targets_clear_counts_of_more_than_2_to_19_ints():
     assert len(np.unique(rmap)) == lb
     rs = np.random.RandomState(14)
     gt, inst, edge = TT._blobs(rs, 1, 33, 70), TT._blobs(rs, 1, 33, 70), TT._blobs(rs, 1, 33, 70, k=6)
-    got = _execute(_targets_call(seg, rmap, [0, n_nodes], gt, inst, edge, n_nodes, 0, 1), 0xFF)
+    got = execute(BUILDERS["camo_rg_node_targets"](seg, rmap, [0, n_nodes], gt, inst, edge, n_nodes, 0, 1), 0xFF)
     want = TG.node_targets(seg, rmap, [0, n_nodes], gt, inst, edge, 0, 1, n_nodes)
     _same_bytes(got, dict(zip(("mask_t", "inst_t", "edge_t", "counts"), want)), "131 109 nodes")
     used = np.zeros(n_nodes, bool)
@@ -878,7 +713,7 @@ def test_region_graph_clears_past_its_grid_on_a_dirty_workspace():
     assert 4096 * 18 > 1 << 16
     img, seg, canny = M.case("perm64")
     want = M.oracle("perm64")
-    got = _execute(_single_graph_call(img, seg, canny.astype(np.uint8), 4096, want[1].shape[1]), 0xFF)
+    got = execute(BUILDERS["camo_rg_region_graph"](img, seg, canny.astype(np.uint8), 4096, want[1].shape[1]), 0xFF)
     _check_single_graph(got, want, TGS._std_bound("perm64", want))
 
 
@@ -894,7 +729,7 @@ def test_batched_region_graph_clears_past_its_grid_on_a_dirty_workspace():
     assert 2 * lb * ((lb + 31) // 32) > 1 << 19 >= lb * ((lb + 31) // 32)
     img, seg, canny = (np.stack([a, a]) for a in M.case("perm64"))
     want = [M.oracle("perm64")] * 2
-    got = _execute(_batch_graph_call(img, seg, canny.astype(np.uint8), lb, 2 * want[0][1].shape[1]), 0xFF)
+    got = execute(BUILDERS["camo_rg_region_graph_batch"](img, seg, canny.astype(np.uint8), lb, 2 * want[0][1].shape[1]), 0xFF)
     _check_batch_graph(got, want, "perm64 twice")
     d = _declared_batch_graph(got)
     assert (d["x"][:, TGS.STD_COLS + [14]] == 0).all()

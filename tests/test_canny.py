@@ -21,6 +21,7 @@ import pytest
 
 import canny_ref as R
 from conftest import ROOT
+from raw_calls import BUILDERS, execute
 
 GRAD_BOUND = 2e-5                         # 8 * 40 * 2^-24 = 1.9e-5, rounded up
 EXCLUDED_CAP = 0.10
@@ -171,16 +172,7 @@ def test_end_to_end_against_float64(name):
 
 
 def _hysteresis_device(cls):
-    import torch
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
-    c = torch.from_numpy(np.ascontiguousarray(cls, np.uint8)).cuda()
-    N, H, W = c.shape
-    L = _lib.lib()
-    ws = torch.empty(L.camo_canny_workspace_bytes(N, H, W), dtype=torch.uint8, device="cuda")
-    out = torch.empty_like(c)
-    _lib.check(L.camo_canny_hysteresis(_ptr(c), N, H, W, _ptr(ws), ws.numel(), _ptr(out), _stream_ptr()), "camo_canny_hysteresis")
-    return out.cpu().numpy()
+    return execute(BUILDERS["camo_canny_hysteresis"](cls), 0xFF)["edges"]
 
 
 def _serpentine(n=128):

@@ -5,7 +5,6 @@ The GPU cases give the label maps directly as int32 tensors, so the kernels meet
 that change at every pixel, ids past the tables, 300 ids in use.  Every raw call places its six outputs between guard bytes."""
 import ctypes
 import functools
-import math
 import os
 import re
 from fractions import Fraction as F
@@ -16,29 +15,15 @@ import torch
 
 import inst_match_ref as R
 from conftest import ROOT
+from inst_match_ref import blocks as _blocks, score_table as _table
+from raw_calls import BUILDERS, MATCH_NAMES as NAMES, execute, same_bytes as _same
 
-NAMES = ("inter", "pred_rows", "gt_area", "match", "gt_match", "counts")
 STRIP10 = (np.array([[1, 1, 1, 1, 2, 2, 2, 2, 2, 2]]), np.array([[0, 0, 1, 1, 1, 1, 1, 1, 2, 2]]))
 STRIP4 = (np.array([[1, 1, 1, 1]]), np.array([[1, 1, 2, 2]]))
 
 
 def _row(area, sq):
     return [area, 0, 0, 0, 0, 0, 0, sq]
-
-
-def _blocks(H, W, ids, seed, cell=4):
-    """A [H, W] map of cell x cell blocks with ids 0 .. ids."""
-    rng = np.random.default_rng(seed)
-    coarse = rng.integers(0, ids + 1, ((H + cell - 1) // cell, (W + cell - 1) // cell))
-    return np.kron(coarse, np.ones((cell, cell), np.int64))[:H, :W]
-
-
-def _table(N, rows, seed):
-    rng = np.random.default_rng(seed)
-    area = rng.integers(1, 200, (N, rows))
-    t = np.zeros((N, rows, 8), np.int64)
-    t[..., 0], t[..., 7] = area, rng.integers(0, 255 * area + 1)
-    return t
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,57 +87,10 @@ def _ref(name):
     return R.match_batch(pred, gt, P, G, table, thr)
 
 
-def _fractions(thr):
-    den = 1
-    for f in thr:
-        den = den * f.denominator // math.gcd(den, f.denominator)
-    return [int(f * den) for f in thr], int(den)
-
-
-GUARD = 64
-
-
 def _raw(pred, gt, P, G, table, thr):
-    """camo_inst_match through ctypes with the six outputs carved from one buffer of 0xA5 bytes, GUARD bytes apart -> the outputs as
-    numpy arrays, after checking every guard byte."""
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    N, H, W = pred.shape
-    T = len(thr)
-    nums, den = _fractions(thr)
-    shapes = {"inter": (N, P + 1, G + 1), "pred_rows": (N, P, 4), "gt_area": (N, G), "match": (N, T, P), "gt_match": (N, T, G), "counts": (N, 4)}
-    at, off = GUARD, {}
-    for k in NAMES:
-        off[k] = at
-        at += 4 * int(np.prod(shapes[k])) + GUARD
-    buf = torch.full((at,), 0xA5, dtype=torch.uint8, device="cuda")
-    pl, gl = torch.from_numpy(pred).cuda(), torch.from_numpy(gt).cuda()
-    tab = None if table is None else torch.from_numpy(table).cuda()
-    nbytes = L.camo_inst_match_workspace_bytes(N, H, W, P, G, T)
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    ptr = {k: ctypes.c_void_p(buf.data_ptr() + off[k]) for k in NAMES}
-    rc = L.camo_inst_match(ctypes.c_void_p(pl.data_ptr()), ctypes.c_void_p(gl.data_ptr()), N, H, W, P, G,
-                           None if tab is None else ctypes.c_void_p(tab.data_ptr()), 0 if tab is None else tab.shape[1],
-                           (ctypes.c_int32 * T)(*nums), den, T, *(ptr[k] for k in NAMES), ctypes.c_void_p(ws.data_ptr()), nbytes,
-                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    host = buf.cpu().numpy()
-    used = np.zeros(at, bool)
-    out = {}
-    for k in NAMES:
-        n = 4 * int(np.prod(shapes[k]))
-        used[off[k]:off[k] + n] = True
-        out[k] = host[off[k]:off[k] + n].copy().view(np.int32).reshape(shapes[k])
-    assert (host[~used] == 0xA5).all(), "a guard byte was written"
-    return out
-
-
-def _same(got, want, what):
-    for k in NAMES:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.dtype == w.dtype == np.int32 and g.shape == w.shape, (what, k, g.dtype, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k, np.argwhere(g != w)[:5].tolist())
+    """camo_inst_match on guarded buffers (tests/raw_calls.py): the six outputs start from 0xA5 (the restatement holds -1 entries, which
+    0xFF would let a missed store pass) and are 4-byte aligned and no more, the workspace from 0xFF -> the outputs as numpy arrays."""
+    return execute(BUILDERS["camo_inst_match"](pred, gt, P, G, table, thr), 0xA5, ws_fill=0xFF, skew=4)
 
 
 # ---- CPU: the restatement itself, no library call ---------------------------------------------------------------------------

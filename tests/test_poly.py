@@ -13,6 +13,7 @@ import torch
 
 import poly_ref as P
 import rle_ref as R
+from raw_calls import BUILDERS, execute, same_bytes as _same
 
 SHAPES = ((1, 1), (1, 70), (70, 1), (6, 7), (33, 70), (70, 33), (64, 64), (65, 129))
 SQUARE, FULL, TRIANGLE = [1, 1, 4, 1, 4, 4, 1, 4], [0, 0, 7, 0, 7, 6, 0, 6], [-3, -2, 9, 2, 3, 9]
@@ -133,37 +134,8 @@ def _reference(name):
 
 
 def _raw_decode(arrays, N, H, W, fill):
-    """camo_poly_decode through ctypes, every buffer a guarded piece filled with `fill` -> {"labels", "ann_area"} as numpy arrays."""
-    from camouflage_multimodal_amd import _lib
-    from guarded import Arrays
-    L = _lib.lib()
-    xy, poly_off, ann_poly_off, img, val = arrays
-    A, Pn, V = len(img), len(poly_off) - 1, len(xy)
-    nbytes = L.camo_poly_decode_workspace_bytes(N, H, W, A, Pn, V)
-    assert nbytes > 0 and nbytes % 256 == 0
-    ins = {"xy": np.ascontiguousarray(xy, np.float64).reshape(-1), "poly_off": np.asarray(poly_off, np.int32), "ann_poly_off": np.asarray(ann_poly_off, np.int32),
-           "ann_image": np.asarray(img, np.int32), "ann_value": np.asarray(val, np.int32)}
-    spec = {k: ((v.size,), v.dtype) for k, v in ins.items()}
-    spec.update({"labels": ((N, H, W), np.int32), "ann_area": ((A,), np.int64), "ws": nbytes})
-    bufs = Arrays(spec, fill)
-    for k, v in ins.items():
-        if v.size:
-            bufs.piece[k].copy_(torch.from_numpy(v.view(np.uint8).copy()))
-    p = lambda k: ctypes.c_void_p(bufs.ptr(k))
-    rc = L.camo_poly_decode(p("xy") if V else None, V, p("poly_off"), Pn, p("ann_poly_off"), p("ann_image"), p("ann_value"), A, N, H, W, p("labels"),
-                            p("ann_area"), p("ws"), nbytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    got = bufs.collect()
-    for k, v in ins.items():
-        assert got[k].tobytes() == v.tobytes(), f"the call changed {k}"
-    return {"labels": got["labels"], "ann_area": got["ann_area"]}
-
-
-def _same(got, want, what):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, k, g.dtype, w.dtype, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k, np.argwhere(g != w)[:5].tolist())
+    """camo_poly_decode with every buffer a guarded piece filled with `fill` -> {"labels", "ann_area"} as numpy arrays."""
+    return execute(BUILDERS["camo_poly_decode"](arrays, N, H, W), fill)
 
 
 def _both_fills(arrays, N, H, W, want, what):

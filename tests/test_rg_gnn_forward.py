@@ -52,7 +52,8 @@ import torch
 import rg_detect_ref as R
 import rg_train_ref as TR
 from oracle import rg_gnn_oracle as RO
-from test_rg_train import (_case, _data, _embeddings_on_csr, _graph, _guarded, _guards_intact, _model, _saturate, _sharpen)
+from guarded import guarded as _guarded, guards_intact as _guards_intact
+from test_rg_train import _case, _data, _embeddings_on_csr, _graph, _model, _saturate, _sharpen
 
 REUSED = ("isolated", "directed", "sharp", "steep", "hub", "single", "many")       # of test_rg_train.CASES, through _case
 # name: (graph kind, n, in_channels, hidden, heads, seed, (att_src gain, att_dst gain) or None)

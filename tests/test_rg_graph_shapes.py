@@ -16,11 +16,11 @@ import re
 
 import numpy as np
 import pytest
-import torch
 from scipy import ndimage
 
 import rg_maps as M
 from conftest import ROOT
+from raw_calls import BUILDERS, execute
 from oracle import rg_features_oracle as RO
 from test_rg_batch import _build, _bytes, _mixed, _oracle
 
@@ -266,85 +266,47 @@ def test_two_batch_calls_give_the_same_bytes(name):
     assert _bytes(*_batch_of_one(name)) == _bytes(*_batch_of_one(name))
 
 
-GUARD, FILL = 64, 0x7F                                      # elements either side of every buffer, and the byte they hold
-
-
-def _guarded(n, dtype):
-    """(whole, piece): `piece` is n elements of `dtype` in the middle of `whole`, every byte of which is FILL."""
-    whole = torch.empty(n + 2 * GUARD, dtype=dtype, device="cuda")
-    whole.view(torch.uint8).fill_(FILL)
-    return whole, whole[GUARD:GUARD + n]
-
-
-def _untouched(whole):
-    """Both guards still hold FILL."""
-    b, e = whole.view(torch.uint8), whole.element_size()
-    return bool((b[:GUARD * e] == FILL).all()) and bool((b[b.numel() - GUARD * e:] == FILL).all())
+FILL = 0x7F                                                 # the byte every output and the workspace hold on entry
 
 
 def _sentinel_inputs():
     img, seg, canny = _arrays("perm64")
-    return (torch.from_numpy(img).cuda(), torch.from_numpy(seg).cuda(), torch.from_numpy(canny.astype(np.uint8)).cuda(), M.oracle("perm64"))
+    return img, seg, canny.astype(np.uint8), M.oracle("perm64")
 
 
-def _edges_written(ei, ea, cap, want):
+def _edges_written(got, cap, want):
     """Columns below the capacity (pairs are written whole, so below the even part of it) hold the oracle's edges; nothing else is written."""
     _, wei, wea, _ = want
+    ei, ea = got["edge_index"], got["edge_attr"]
     done = min(cap - cap % 2, wei.shape[1])
-    got = ei.view(2, cap).cpu().numpy()
-    assert (got[:, :done] == wei[:, :done]).all()
-    assert (np.abs(ea.cpu().numpy()[:done] - wea[:done]) <= M.w_bound(wea[:done])).all()
-    rest_i, rest_a = ei.view(2, cap)[:, done:].contiguous().view(torch.uint8), ea[done:].contiguous().view(torch.uint8)
-    assert bool((rest_i == FILL).all()) and bool((rest_a == FILL).all())
+    assert (ei[:, :done] == wei[:, :done]).all()
+    assert (np.abs(ea[:done] - wea[:done]) <= M.w_bound(wea[:done])).all()
+    assert (np.ascontiguousarray(ei[:, done:]).view(np.uint8) == FILL).all() and (ea[done:].view(np.uint8) == FILL).all()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("short", [0, 2, None])
 def test_single_image_abi_writes_inside_its_buffers(short):
-    """camo_rg_region_graph on perm64 (4096 labels, 32004 directed edges) with every output and the workspace between guards of 64
-    elements of 0x7F, at an edge capacity of exactly the need, the need - 2, and 2: guards intact, nothing at or past the capacity,
-    counts still the need."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
+    """camo_rg_region_graph on perm64 (4096 labels, 32004 directed edges) with every output and the workspace between guards
+    (tests/guarded.py) and filled with 0x7F, at an edge capacity of exactly the need, the need - 2, and 2: guards intact, nothing at
+    or past the capacity, counts still the need."""
     img, seg, canny, want = _sentinel_inputs()
-    need_e, L, n = want[1].shape[1], _lib.lib(), 4096
+    need_e, n = want[1].shape[1], 4096
     cap = 2 if short is None else need_e - short
-    nbytes = L.camo_rg_graph_workspace_bytes(n)
-    bufs = dict(ws=_guarded(nbytes // 8, torch.int64), x=_guarded(n * 15, torch.float32), rmap=_guarded(n, torch.int32),
-                ei=_guarded(2 * cap, torch.int64), ea=_guarded(cap, torch.float32), counts=_guarded(2, torch.int32))
-    assert nbytes % 8 == 0 and nbytes > 0
-    p = {k: piece for k, (_, piece) in bufs.items()}
-    _lib.check(L.camo_rg_region_graph(_ptr(img), _ptr(seg), _ptr(canny), 64, 64, n, _ptr(p["ws"]), nbytes, _ptr(p["x"]), _ptr(p["rmap"]),
-                                      _ptr(p["ei"]), _ptr(p["ea"]), cap, _ptr(p["counts"]), _stream_ptr()), "camo_rg_region_graph")
-    torch.cuda.synchronize()
-    for k, (whole, _) in bufs.items():
-        assert _untouched(whole), k
-    assert p["counts"].tolist() == [n, need_e]
-    assert (p["rmap"].cpu().numpy() == want[3]).all()
-    _edges_written(p["ei"], p["ea"], cap, want)
+    got = execute(BUILDERS["camo_rg_region_graph"](img, seg, canny, n, cap), FILL)
+    assert got["counts"].tolist() == [n, need_e]
+    assert (got["region_map"] == want[3]).all()
+    _edges_written(got, cap, want)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("short", [0, 2, None])
 def test_batch_abi_writes_inside_its_buffers(short):
     """camo_rg_region_graph_batch likewise, N = 1 and label_bound = node_capacity = 4096."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
     img, seg, canny, want = _sentinel_inputs()
-    need_e, L, n = want[1].shape[1], _lib.lib(), 4096
+    need_e, n = want[1].shape[1], 4096
     cap = 2 if short is None else need_e - short
-    nbytes = L.camo_rg_batch_workspace_bytes(1, 64, 64, n)
-    bufs = dict(ws=_guarded(nbytes // 8, torch.int64), x=_guarded(n * 15, torch.float32), rmap=_guarded(n, torch.int32),
-                ei=_guarded(2 * cap, torch.int64), ea=_guarded(cap, torch.float32), node_off=_guarded(2, torch.int32),
-                edge_off=_guarded(2, torch.int32), batch=_guarded(n, torch.int32), status=_guarded(2, torch.int32))
-    assert nbytes % 8 == 0 and nbytes > 0
-    p = {k: piece for k, (_, piece) in bufs.items()}
-    _lib.check(L.camo_rg_region_graph_batch(_ptr(img), _ptr(seg), _ptr(canny), 1, 64, 64, n, _ptr(p["ws"]), nbytes, _ptr(p["x"]), n, _ptr(p["rmap"]),
-                                            _ptr(p["ei"]), _ptr(p["ea"]), cap, _ptr(p["node_off"]), _ptr(p["edge_off"]), _ptr(p["batch"]),
-                                            _ptr(p["status"]), _stream_ptr()), "camo_rg_region_graph_batch")
-    torch.cuda.synchronize()
-    for k, (whole, _) in bufs.items():
-        assert _untouched(whole), k
-    assert p["status"].tolist() == [0, need_e] and p["node_off"].tolist() == [0, n] and p["edge_off"].tolist() == [0, need_e]
-    assert (p["rmap"].cpu().numpy() == want[3]).all() and (p["batch"] == 0).all()
-    _edges_written(p["ei"], p["ea"], cap, want)
+    got = execute(BUILDERS["camo_rg_region_graph_batch"](img[None], seg[None], canny[None], n, cap), FILL)
+    assert got["status"].tolist() == [0, need_e] and got["node_off"].tolist() == [0, n] and got["edge_off"].tolist() == [0, need_e]
+    assert (got["region_map"][0] == want[3]).all() and (got["batch"] == 0).all()
+    _edges_written(got, cap, want)

@@ -261,24 +261,14 @@ def test_excluded_pixels_and_a_node_without_pixels():
 def test_rows_past_n_nodes_are_untouched():
     """camo_rg_node_targets called directly with n_nodes below node_off[N]: the pixels of the nodes past it take no part, and the four
     outputs, each of exactly n_nodes rows in the middle of a tensor filled with a sentinel, are written inside their extents only."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
-    from test_rg_train import _guarded, _guards_intact
+    from raw_calls import BUILDERS, execute
     seg, rmap, off, gt, inst = _excluded_case()
     n = int(off[2]) - 9
-    assert off[1] < n < off[2]
+    assert off[1] < n < off[2] and rmap.shape[1] == 48
     want = TG.node_targets(seg, rmap, off, gt, inst, None, 100, 2, n_nodes=n)
     assert np.array_equal(want[3], TG.node_counts(seg, rmap, off, gt, inst)[:n])          # the rows below n do not change
-    d = [_dev(a) for a in (seg, rmap, np.asarray(off, np.int32), gt, inst)]
-    outs = [_guarded(4 * n * k, 0xEE) for k in (1, 1, 1, 4)]
-    rc = _lib.lib().camo_rg_node_targets(_ptr(d[0]), _ptr(d[1]), _ptr(d[2]), _ptr(d[3]), _ptr(d[4]), None, 2, 40, 36, 48, n, 100, 2,
-                                         _ptr(outs[3][1]), _ptr(outs[0][1]), _ptr(outs[1][1]), _ptr(outs[2][1]), _stream_ptr())
-    _lib.check(rc, "camo_rg_node_targets")
-    torch.cuda.synchronize()
-    for name, (whole, piece) in zip(("mask_t", "inst_t", "edge_t", "counts"), outs):
-        assert _guards_intact(whole, piece, 0xEE), name
-    got = [outs[0][1].view(torch.int32).cpu().numpy(), outs[1][1].view(torch.int32).cpu().numpy(),
-           outs[2][1].view(torch.float32).cpu().numpy(), outs[3][1].view(torch.int32).cpu().numpy().reshape(n, 4)]
+    got = execute(BUILDERS["camo_rg_node_targets"](seg, rmap, off, gt, inst, None, n, 100, 2), 0xA5)      # (the reference holds -1 entries)
+    got = [got[k] for k in ("mask_t", "inst_t", "edge_t", "counts")]
     _hold(got, want, "n_nodes below node_off[N]")
 
 

@@ -31,6 +31,7 @@ import torch
 import rg_detect_ref as R
 import rg_train_ref as TR
 from conftest import ROOT
+from guarded import guarded as _guarded, guards_intact as _guards_intact
 from oracle import rg_gnn_oracle as RO
 
 NAMES = TR.trainable_names()
@@ -501,24 +502,6 @@ def test_targets_outside_the_classes_are_ignored_like_minus_one():
         assert np.array_equal(_bits(l1.cpu()), _bits(l2.cpu()))
         for k, a, b in zip(NAMES, g1, g2):
             assert np.array_equal(_bits(a.cpu()), _bits(b.cpu())), k
-
-
-GUARD = 4096
-
-
-def _guarded(nbytes, fill):
-    """(whole, piece): `piece` is `nbytes` bytes on a 256-byte boundary in the middle of the uint8 device tensor `whole`, which is
-    filled with `fill` and has at least GUARD bytes on either side of the piece."""
-    whole = torch.full((nbytes + 2 * GUARD + 256,), fill, dtype=torch.uint8, device="cuda")
-    at = GUARD + (-(whole.data_ptr() + GUARD)) % 256
-    piece = whole[at:at + nbytes]
-    assert piece.data_ptr() % 256 == 0 and at >= GUARD and whole.numel() - at - nbytes >= GUARD
-    return whole, piece
-
-
-def _guards_intact(whole, piece, fill):
-    at = piece.data_ptr() - whole.data_ptr()
-    return bool((whole[:at] == fill).all()) and bool((whole[at + piece.numel():] == fill).all())
 
 
 @pytest.mark.gpu

@@ -37,7 +37,8 @@ import rg_train_bn_ref as BR
 import rg_train_ref as TR
 from conftest import ROOT
 from oracle import rg_gnn_oracle as RO
-from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _guarded, _guards_intact, _model, _targets
+from guarded import guarded as _guarded, guards_intact as _guards_intact
+from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _model, _targets
 
 BN_SIZES = (23, 2, 40)
 MANY_ORDER = (0, 1, 2) * 16 + (2, 1)

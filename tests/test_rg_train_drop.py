@@ -44,7 +44,8 @@ import rg_train_ref as TR
 from conftest import ROOT
 from oracle import rg_gnn_oracle as RO
 from oracle.fusion_oracle import dropout_keep
-from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _guarded, _guards_intact, _model, _targets
+from guarded import guarded as _guarded, guards_intact as _guards_intact
+from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _model, _targets
 from test_rg_train_bn import BIAS_NAMES, LOSS_KEYS, STAT_NAMES, _graph, _running, _sizes
 
 ALL = (0.2, 0.3, 0.5)

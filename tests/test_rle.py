@@ -11,15 +11,11 @@ import pytest
 import torch
 
 import rle_ref as R
+from inst_match_ref import blocks as _blocks
+from raw_calls import BUILDERS, execute, same_bytes as _same
 
 SHAPES = ((1, 1), (1, 70), (70, 1), (33, 70), (70, 33), (64, 64), (65, 129))      # tiles, halo rows and segment boundaries are all crossed
-GUARD = 64
-
-
-def _blocks(H, W, ids, seed, cell=3):
-    rng = np.random.default_rng(seed)
-    coarse = rng.integers(0, ids + 1, ((H + cell - 1) // cell, (W + cell - 1) // cell))
-    return np.kron(coarse, np.ones((cell, cell), np.int64))[:H, :W]
+FILL, SKEW = 0xA5, 8      # the outputs start from 0xA5 (rle_ref holds -1 entries, which 0xFF would let a missed store pass), 8-byte aligned and no more
 
 
 def _crossing():
@@ -36,7 +32,7 @@ def _case(name):
     kind, _, shape = name.partition("@")
     H, W = (int(v) for v in shape.split("x")) if shape else (0, 0)
     if kind == "blocks":
-        lab = _blocks(H, W, 5, H * 131 + W)[None]
+        lab = _blocks(H, W, 5, H * 131 + W, 3)[None]
     elif kind == "background":
         lab = np.zeros((1, H, W), np.int64)
     elif kind == "one_id":
@@ -48,7 +44,7 @@ def _case(name):
         lab = ((x + y) % 2)[None]                                      # H is odd: the last pixel of a column differs from the first of the next
         return lab.astype(np.int32), 65 * 129 - (kind == "checkerboard_short")
     elif kind == "extreme":
-        lab = np.array([-2 ** 31, -1, 0, 2 ** 31 - 1, 7, 2 ** 31 - 2])[_blocks(33, 70, 5, 9)][None]
+        lab = np.array([-2 ** 31, -1, 0, 2 ** 31 - 1, 7, 2 ** 31 - 2])[_blocks(33, 70, 5, 9, 3)][None]
     elif kind == "batch":
         lab = np.stack([_blocks(70, 33, 4, 40 + n, 2 + n) for n in range(5)])
     else:
@@ -60,67 +56,13 @@ def _case(name):
 CASES = [f"{k}@{H}x{W}" for H, W in SHAPES for k in ("blocks", "background", "one_id")] + ["crossing", "checkerboard", "checkerboard_short", "extreme", "batch"]
 
 
-def _guarded(shapes):
-    """One buffer of 0xA5 bytes with the named arrays GUARD bytes apart -> (buffer, offsets, bytes of each, total)."""
-    at, off, size = GUARD, {}, {}
-    for k, (shape, item) in shapes.items():
-        off[k], size[k] = at, item * int(np.prod(shape))
-        at += (size[k] + GUARD + 7) // 8 * 8
-    return torch.full((at,), 0xA5, dtype=torch.uint8, device="cuda"), off, size, at
-
-
-def _collect(buf, off, size, at, shapes, dtypes):
-    host = buf.cpu().numpy()
-    used = np.zeros(at, bool)
-    out = {}
-    for k in shapes:
-        used[off[k]:off[k] + size[k]] = True
-        out[k] = host[off[k]:off[k] + size[k]].copy().view(dtypes[k]).reshape(shapes[k][0])
-    assert (host[~used] == 0xA5).all(), "a guard byte was written"
-    return out
-
-
 def _raw_runs(labels, R_):
-    """camo_rle_runs through ctypes with runs and counts carved from one buffer of guard bytes -> the outputs as numpy arrays."""
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    N, H, W = labels.shape
-    shapes = {"runs": ((N, R_, 2), 4), "counts": ((N, 2), 4)}
-    buf, off, size, at = _guarded(shapes)
-    lab = torch.from_numpy(labels).cuda()
-    nbytes = L.camo_rle_runs_workspace_bytes(N, H, W, R_)
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    rc = L.camo_rle_runs(ctypes.c_void_p(lab.data_ptr()), N, H, W, R_, ctypes.c_void_p(buf.data_ptr() + off["runs"]),
-                         ctypes.c_void_p(buf.data_ptr() + off["counts"]), ctypes.c_void_p(ws.data_ptr()), nbytes,
-                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    return _collect(buf, off, size, at, shapes, {"runs": np.int32, "counts": np.int32})
+    """camo_rle_runs on guarded buffers (tests/raw_calls.py), the workspace 0xFF -> the outputs as numpy arrays."""
+    return execute(BUILDERS["camo_rle_runs"](labels, R_), FILL, ws_fill=0xFF, skew=SKEW)
 
 
 def _raw_decode(cnts, ann_off, ann_image, ann_value, N, H, W):
-    """camo_rle_decode through ctypes with labels and ann_sum between guard bytes."""
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    A, total = len(ann_image), len(cnts)
-    shapes = {"labels": ((N, H, W), 4), "ann_sum": ((A,), 8)}
-    buf, off, size, at = _guarded(shapes)
-    dev = [torch.tensor(np.asarray(v, np.int32).reshape(-1), dtype=torch.int32).cuda() for v in (cnts, ann_off, ann_image, ann_value)]
-    nbytes = L.camo_rle_decode_workspace_bytes(N, H, W, A, total)
-    assert nbytes > 0 and nbytes % 256 == 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    rc = L.camo_rle_decode(ctypes.c_void_p(dev[0].data_ptr()) if total else None, total, *(ctypes.c_void_p(d.data_ptr()) for d in dev[1:]), A, N, H, W,
-                           ctypes.c_void_p(buf.data_ptr() + off["labels"]), ctypes.c_void_p(buf.data_ptr() + off["ann_sum"]),
-                           ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, L.camo_last_error()
-    return _collect(buf, off, size, at, shapes, {"labels": np.int32, "ann_sum": np.int64})
-
-
-def _same(got, want, what):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, k, g.dtype, w.dtype, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k, np.argwhere(g != w)[:5].tolist())
+    return execute(BUILDERS["camo_rle_decode"]((cnts, ann_off, ann_image, ann_value), N, H, W), FILL, ws_fill=0xFF, skew=SKEW)
 
 
 def _annotation_arrays(per_image):
@@ -430,7 +372,7 @@ def test_decode_hand_cases_overlap_short_long_and_invalid():
     assert flat[:3].tolist() == [1, 1, 1] and flat[3] == 5 and (flat[4:8] == 5).all() and (flat[8:18] == 7).all() and not flat[18:].any()
     assert got["labels"][1].flatten(order="F").tolist() == [1] * 34 + [3]
     swapped = [list(reversed(anns)) for anns in per_image]             # the largest value wins whichever comes first
-    _same(_raw_decode(*_annotation_arrays(swapped), 3, H, W), {"labels": want[0]}, "reversed lists")
+    _same(_raw_decode(*_annotation_arrays(swapped), 3, H, W), {"labels": want[0]}, "reversed lists", ("labels",))
     # invalid annotations write nothing and get -1; the valid one beside them is painted
     cnts, off, img, val = _annotation_arrays([[([1, -1, 35], 4), ([2, 3, 30], 0), ([2, 3, 30], -5), ([4, 2, 29], 2)], []])
     img += [2, -1]; val += [3, 3]; cnts += [0, 35, 0, 35]; off += [off[-1] + 2, off[-1] + 4]      # images outside 0 .. N - 1

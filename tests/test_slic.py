@@ -30,6 +30,7 @@ import pytest
 
 import slic_ref as R
 from conftest import ROOT
+from raw_calls import BUILDERS, execute
 
 TAU = 2.1e-4
 CASES = R.cases()
@@ -215,24 +216,13 @@ def _assign_device(lab, cent, step):
 
 
 def _update_device(lab, near, cent):
-    import torch
-    N, H, W = lab.shape[:3]
-    out = cent.clone()
-    sums = torch.full((N, cent.shape[1], 6), 0x7F7F7F7F, dtype=torch.int64, device="cuda")      # (scratch: any content)
-    _call("camo_slic_update", lab, near, N, H, W, cent.shape[1], sums, out)
-    return out
+    """camo_slic_update on guarded buffers, numpy in and out; ``sums`` starts from 0x7F bytes (scratch: any content)."""
+    return execute(BUILDERS["camo_slic_update"](lab, near, cent), 0x7F)["centroids"]
 
 
 def _connect_device(maps, min_size, max_size):
-    import torch
-    from camouflage_multimodal_amd import _lib
-    seg = _cuda(np.asarray(maps, np.int32))
-    N, H, W = seg.shape
-    ws = torch.empty(_lib.lib().camo_slic_workspace_bytes(N, H, W, 0), dtype=torch.uint8, device="cuda")
-    out = torch.empty_like(seg)
-    counts = torch.empty(N, 2, dtype=torch.int32, device="cuda")
-    _call("camo_slic_connect", seg, N, H, W, min_size, max_size, ws, ws.numel(), out, counts)
-    return out.cpu().numpy(), counts.cpu().numpy()
+    got = execute(BUILDERS["camo_slic_connect"](np.asarray(maps, np.int32), min_size, max_size), 0xFF)
+    return got["labels"], got["counts"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -295,8 +285,7 @@ def test_update_against_float64_means(name):
     K = cent.shape[1]
     near = near.copy()
     near[near == 1] = 0; near[near == K - 2] = K - 1                          # two centroids left without a pixel
-    a = _update_device(_cuda(lab), _cuda(near), _cuda(cent)).cpu().numpy()
-    b = _update_device(_cuda(lab), _cuda(near), _cuda(cent)).cpu().numpy()
+    a, b = _update_device(lab, near, cent), _update_device(lab, near, cent)
     assert a.tobytes() == b.tobytes()
     for k in range(N):
         assert a[k, 1].tobytes() == cent[k, 1].tobytes() and a[k, K - 2].tobytes() == cent[k, K - 2].tobytes()
@@ -335,8 +324,7 @@ def test_update_past_a_full_tile_table_bit_for_bit(name):
     lab = rs.uniform(-1.0, 1.0, (side, side, 3)).astype(np.float32)
     cent = rs.uniform(0.0, side, (K, 5)).astype(np.float32)
     want = R.update(lab, near, cent, np.float32)
-    a = _update_device(_cuda(lab[None]), _cuda(near[None]), _cuda(cent[None])).cpu().numpy()
-    b = _update_device(_cuda(lab[None]), _cuda(near[None]), _cuda(cent[None])).cpu().numpy()
+    a, b = _update_device(lab[None], near[None], cent[None]), _update_device(lab[None], near[None], cent[None])
     assert a.tobytes() == b.tobytes()
     assert a[0].tobytes() == want.tobytes(), int((a[0] != want).sum())
 
@@ -430,11 +418,12 @@ def test_whole_call_equals_its_stages_and_a_batch_its_images(name):
     g = R.grid(H, W, n)
     labels, counts = _device(name)
     lab = _preprocess_device(images)
-    cent = _cuda(np.stack([R.initial_centroids(g, np.float32)] * N))
+    lab_host = lab.cpu().numpy()
+    cent = np.stack([R.initial_centroids(g, np.float32)] * N)
     for it in range(R.ITERATIONS):
-        near, _ = _assign_device(lab, cent, g["step"])
-        cent = _update_device(lab, near, cent)
-    got, cnt = _connect_device(near.cpu().numpy(), *R.sizes(H, W, g["K"]))
+        near = _assign_device(lab, _cuda(cent), g["step"])[0].cpu().numpy()
+        cent = _update_device(lab_host, near, cent)
+    got, cnt = _connect_device(near, *R.sizes(H, W, g["K"]))
     assert got.tobytes() == labels.tobytes() and cnt.tobytes() == counts.tobytes()
     again, counts2 = slic_segments(_cuda(images), n, return_counts=True)
     assert again.cpu().numpy().tobytes() == labels.tobytes() and counts2.cpu().numpy().tobytes() == counts.tobytes()
