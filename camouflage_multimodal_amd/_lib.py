@@ -126,6 +126,7 @@ PROTOTYPES = {
         ("camo_clip_adamw_shadows", i32, (dims, vp, vp, vp, vp, vp, sz, vp, f32, f32, f32, f32, f32, f32, i32, i32, vp, vp)),
         ("camo_forward_loss_backward", i32, (dims, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp, vp, i32, u64, i32, vp, vp, i32, vp)),
         ("camo_debug_gemm", i32, (vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp)),
+        ("camo_debug_gemm_batch", i32, (vp, P(i32), P(f32), i32, i32, f32, u64, vp)),
         ("camo_debug_gemm16", i32, (vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp)),
         ("camo_debug_ws_offset", i64, (dims, i32, i32, i32, C.c_char_p)),
         ("camo_debug_plan", i32, (dims, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(CamoPlan))),

@@ -43,10 +43,13 @@ inline int ws_check(const void* ws, size_t ws_bytes, size_t need, const char* si
 
 struct GB {
   GemmBatch b;
+  GemmProb spill;
   int prec; hipStream_t st;
   GB(const DropCfg& d, int prec_, hipStream_t st_) : prec(prec_), st(st_) { std::memset(&b, 0, sizeof(b)); b.drop = d; }
   GemmProb& add(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K, int flags) {
-    GemmProb& p = b.p[b.n++];
+    // (a 13th problem lands in a spare slot and is counted: launch_gemm_batch refuses the batch, run() reports it)
+    GemmProb& p = b.n < GEMM_MAXP ? b.p[b.n] : spill;
+    ++b.n;
     std::memset(&p, 0, sizeof(p));   // slots are reused across launches: no stale res/bias_grad/flags
     p.A = A; p.lda = lda; p.B = Bm; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.flags = flags;
     p.aux_scale = 1.f;

@@ -1286,6 +1286,25 @@ int camo_debug_gemm(const float* A, int32_t lda, const float* B, int32_t ldb, fl
   return 0;
 }
 
+int camo_debug_gemm_batch(const void* const* ptrs, const int32_t* ints, const float* aux_scale, int32_t n, int32_t precision,
+                          float drop_p, uint64_t seed, void* stream) {
+  if (!ptrs || !ints || !aux_scale || n < 1 || n > GEMM_MAXP) return fail(CAMO_E_ARG, "bad gemm batch arguments");
+  GB g(make_drop(1, drop_p, seed), precision, static_cast<hipStream_t>(stream));
+  for (int i = 0; i < n; ++i) {
+    const void* const* q = ptrs + 8 * i;
+    const int32_t* v = ints + 10 * i;
+    if (!q[0] || !q[1] || !q[2] || v[0] < 1 || v[1] < 1 || v[2] < 1) return fail(CAMO_E_ARG, "bad gemm batch problem");
+    GemmProb& p = g.add(static_cast<const float*>(q[0]), v[3], static_cast<const float*>(q[1]), v[4],
+                        static_cast<float*>(const_cast<void*>(q[2])), v[5], v[0], v[1], v[2], v[7]);
+    p.bias = static_cast<const float*>(q[3]); p.res = static_cast<const float*>(q[4]); p.ldr = v[6];
+    p.bias_grad = static_cast<float*>(const_cast<void*>(q[5]));
+    p.row_sample = static_cast<const int*>(q[6]); p.inv_nr = static_cast<const float*>(q[7]);
+    p.drop_site = (uint32_t)v[8]; p.uniform_n = v[9]; p.aux_scale = aux_scale[i];
+  }
+  CK(g.run(), "debug gemm batch (a refused combination: csrc/gemm.h)");
+  return 0;
+}
+
 int camo_debug_gemm16(const void* A16, int32_t lda, const void* B16, int32_t ldb, float* C, int32_t ldc, void* C16,
                       int32_t ldc16, const float* bias, const float* res, int32_t ldr, float* bias_grad, int32_t M,
                       int32_t N, int32_t K, int32_t flags, void* stream) {

@@ -18,6 +18,14 @@ enum : int {
   GF_A_F32 = 512,     // gemm16 TN only: A holds fp32 sums (lda in floats), rounded to bf16 while staging; rows >= K read as zero
   GF_KGQ = 1024       // gemm16 TN only, with GF_A_F32: the KG rows' deferred query-gradient chain (Gemm16Prob::kgq_wT)
 };
+// Refused: launch_gemm_batch returns hipErrorInvalidValue, before any launch and with every output untouched, for
+//   * more than GEMM_MAXP problems;
+//   * GF_A_KMAJOR | GF_B_KMAJOR | GF_ATOMIC (the weight-gradient form: C += A^T.B, bias_grad += rowsum) with `bias`, `res` or any of
+//     GF_RELU, GF_RELU_BWD, GF_DROPOUT, GF_SIGMOID, GF_RES_BCAST: the tile kernel's atomic epilogue applies none of them, the skinny
+//     kernel all, and a bias would be added once per K split;
+//   * GF_RELU_BWD or GF_RES_BCAST without `res`;
+//   * GF_RES_BCAST with neither row_sample + inv_nr nor uniform_n >= 1;
+//   * GF_RELU_BWD together with GF_RES_BCAST (`res` is either the aux map or the residual).
 
 // C[m,n] (+)= epi( sum_k A(m,k) * B(k,n) + bias[n] ) (+ res[m,n])
 struct GemmProb {

@@ -734,8 +734,22 @@ static int launch_skinny(GemmBatch& gb, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// What no kernel here computes (gemm.h, "Refused"): checked on the host before anything is launched.
+static bool refused(const GemmProb& p) {
+  const int f = p.flags;
+  const int wg = GF_A_KMAJOR | GF_B_KMAJOR | GF_ATOMIC;
+  if ((f & wg) == wg && (p.bias || p.res || (f & (GF_RELU | GF_RELU_BWD | GF_DROPOUT | GF_SIGMOID | GF_RES_BCAST)))) return true;
+  if ((f & (GF_RELU_BWD | GF_RES_BCAST)) && !p.res) return true;
+  if ((f & GF_RES_BCAST) && !(p.row_sample && p.inv_nr) && p.uniform_n < 1) return true;
+  if ((f & GF_RELU_BWD) && (f & GF_RES_BCAST)) return true;
+  return false;
+}
+
 int launch_gemm_batch(GemmBatch& gb, int precision, hipStream_t stream) {
   if (gb.n <= 0) return 0;
+  if (gb.n > GEMM_MAXP) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < gb.n; ++i)
+    if (refused(gb.p[i])) return (int)hipErrorInvalidValue;
   if (precision == 0) {
     // per-sample tail: every problem is skinny (few rows, or a contraction over few rows)
     bool skinny = true;

@@ -285,6 +285,15 @@ int camo_forward_loss_backward(const camo_dims_t* dims, const float* const* para
 int camo_debug_gemm(const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc,
                     const float* bias, const float* res, int32_t ldr, float* bias_grad,
                     int32_t M, int32_t N, int32_t K, int32_t flags, int32_t precision, void* stream);
+/* camo_debug_gemm_batch: n problems (1 .. 12) of the grouped GEMM in ONE launch.  ptrs, ints and aux_scale are HOST arrays.  Per problem i:
+ *   ptrs[8i..]   = A, B, C, bias, res, bias_grad, row_sample, inv_nr   (device pointers; null where absent)
+ *   ints[10i..]  = M, N, K, lda, ldb, ldc, ldr, flags, drop_site, uniform_n
+ *   aux_scale[i]
+ * drop_p > 0 turns GF_DROPOUT on with `seed` (make_drop(1, drop_p, seed)).  CAMO_E_ARG: n outside 1 .. 12, a null A / B / C, a size
+ * below 1.  A combination of flags and pointers that the launcher refuses (csrc/gemm.h, "Refused") returns CAMO_E_HIP with nothing
+ * launched and no output touched. */
+int camo_debug_gemm_batch(const void* const* ptrs, const int32_t* ints, const float* aux_scale, int32_t n,
+                          int32_t precision, float drop_p, uint64_t seed, void* stream);
 /* camo_debug_gemm16: one problem of the bf16-resident grouped GEMM (csrc/gemm16.h): A16/B16/C16 are bf16
  * bit patterns; flags 64|128 together = dW += A^T.B (rows of A/B up to round_up(K,128) must be readable). */
 int camo_debug_gemm16(const void* A16, int32_t lda, const void* B16, int32_t ldb, float* C, int32_t ldc,

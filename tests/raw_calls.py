@@ -1,4 +1,5 @@
-"""Every raw ctypes call of the image and region-graph pipeline, stated once, on the one guard harness (a helper module, not a conftest).
+"""Every raw ctypes call of the image and region-graph pipeline, and the grouped GEMM's two testing hooks, stated once, on the one guard
+harness (a helper module, not a conftest).
 
 ``BUILDERS`` maps an entry point's name to a function from data -- numpy arrays and parameters, never a test's name -- to a ``Call``;
 ``execute`` runs a Call with every caller array in a guarded piece of tests/guarded.py: the inputs copied in before each call and held
@@ -259,6 +260,50 @@ def poly_decode(arrays, N, H, W):
     return Call({"labels": ((N, H, W), np.int32), "ann_area": ((A,), np.int64)}, _sized(L.camo_poly_decode_workspace_bytes(N, H, W, A, Pn, V)),
                 lambda p, w, nb: L.camo_poly_decode(p["xy"], V, p["poly_off"], Pn, p["ann_poly_off"], p["ann_image"], p["ann_value"], A, N, H, W,
                                                     p["labels"], p["ann_area"], w, nb, _stream()), ins)
+
+
+# ---- the grouped GEMM's testing hooks (include/camo_fusion.h; not pipeline calls, so not in BUILDERS) --------------------------------------
+# A problem is a dict: M, N, K, lda, ldb, ldc, flags and, where they are not the defaults, ldr, drop_site, uniform_n, aux_scale; A, B, C
+# and, where present, bias, res, bias_grad, row_sample, inv_nr = (name of a caller array, offset into it in 4-byte elements).  An operand
+# that must start off a 16-byte boundary has offset 1: every array begins on a 256-byte boundary (execute's skew stays 0).  ``ins`` name
+# -> the array an input holds, ``outs`` name -> (shape, dtype) of the arrays the launch writes (several problems may name one), ``init``
+# name -> what an accumulator (C with GF_ATOMIC, bias_grad) holds on entry.  ``rc``: a list that takes the return code of a launch that
+# is expected to be refused (the Call then reports success, and the caller asserts the code and the untouched fill).
+GEMM_POINTERS = ("A", "B", "C", "bias", "res", "bias_grad", "row_sample", "inv_nr")
+GEMM_INTS = ("M", "N", "K", "lda", "ldb", "ldc", "ldr", "flags", "drop_site", "uniform_n")
+
+
+def _gemm_address(p, prob, k):
+    return None if prob.get(k) is None else p[prob[k][0]] + 4 * prob[k][1]
+
+
+def _gemm_rc(code, rc):
+    if rc is None:
+        return code
+    rc.append(code)
+    return 0
+
+
+def gemm(prob, prec, ins, outs, init=None, rc=None):
+    """One problem through camo_debug_gemm (which has no aux_scale, sample map, dropout: those go through gemm_batch)."""
+    L = _lib()
+    assert prob.get("aux_scale", 1.0) == 1.0 and not any(prob.get(k) for k in ("row_sample", "inv_nr", "uniform_n", "drop_site"))
+    a = lambda p, k: _gemm_address(p, prob, k)
+    return Call(outs, 0, lambda p, w, nb: _gemm_rc(L.camo_debug_gemm(
+        a(p, "A"), prob["lda"], a(p, "B"), prob["ldb"], a(p, "C"), prob["ldc"], a(p, "bias"), a(p, "res"), prob.get("ldr", 0), a(p, "bias_grad"),
+        prob["M"], prob["N"], prob["K"], prob["flags"], prec, _stream()), rc), ins, init)
+
+
+def gemm_batch(probs, prec, ins, outs, init=None, drop_p=0.0, seed=0, rc=None):
+    """``probs`` in ONE launch through camo_debug_gemm_batch."""
+    L, n = _lib(), len(probs)
+
+    def invoke(p, w, nb):
+        ptrs = (ctypes.c_void_p * (8 * n))(*(_gemm_address(p, q, k) for q in probs for k in GEMM_POINTERS))
+        ints = (ctypes.c_int32 * (10 * n))(*(int(q.get(k, 0)) for q in probs for k in GEMM_INTS))
+        aux = (ctypes.c_float * n)(*(float(q.get("aux_scale", 1.0)) for q in probs))
+        return _gemm_rc(L.camo_debug_gemm_batch(ptrs, ints, aux, n, prec, drop_p, seed, _stream()), rc)
+    return Call(outs, 0, invoke, ins, init)
 
 
 BUILDERS = {

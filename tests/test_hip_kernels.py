@@ -1,9 +1,8 @@
 """Kernel-level checks of the grouped MFMA GEMM through the C ABI's testing hook."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
+
+from raw_calls import execute, gemm
 
 pytestmark = pytest.mark.gpu
 
@@ -11,20 +10,16 @@ RELU, ATOMIC, AKM, BKM = 1, 4, 64, 128
 
 
 def run_gemm(A, B, M, N, K, flags, prec, bias=None, res=None, c0=None, want_bias_grad=False):
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    dev = "cuda"
-    a = torch.from_numpy(A).to(dev); b = torch.from_numpy(B).to(dev)
-    c = torch.from_numpy(c0).to(dev) if c0 is not None else torch.full((M, N), float("nan"), device=dev)
-    bt = torch.from_numpy(bias).to(dev) if bias is not None else None
-    rt = torch.from_numpy(res).to(dev) if res is not None else None
-    bg = torch.zeros(M, device=dev) if want_bias_grad else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-    rc = L.camo_debug_gemm(p(a), A.shape[1], p(b), B.shape[1], p(c), N, p(bt), p(rt), N, p(bg), M, N, K, flags, prec,
-                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "camo_debug_gemm")
-    torch.cuda.synchronize()
-    return c.cpu().numpy(), (bg.cpu().numpy() if bg is not None else None)
+    """Tight leading dimensions, every array between guard bands (tests/raw_calls.py); C is NaN on entry unless ``c0`` is given."""
+    ins = {k: a for k, a in (("A", A), ("B", B), ("bias", bias), ("res", res)) if a is not None}
+    prob = dict(M=M, N=N, K=K, lda=A.shape[1], ldb=B.shape[1], ldc=N, ldr=N, flags=flags, A=("A", 0), B=("B", 0), C=("C", 0),
+                bias=("bias", 0) if bias is not None else None, res=("res", 0) if res is not None else None,
+                bias_grad=("bias_grad", 0) if want_bias_grad else None)
+    outs, init = {"C": ((M, N), np.float32)}, ({"C": c0} if c0 is not None else {})
+    if want_bias_grad:
+        outs["bias_grad"], init["bias_grad"] = ((M,), np.float32), np.zeros(M, np.float32)
+    got = execute(gemm(prob, prec, ins, outs, init), 0xFF)
+    return got["C"], got.get("bias_grad")
 
 
 # error bound per output element: tol * sum_k |a_k||b_k|  (fp32: rounding of the running sum;
