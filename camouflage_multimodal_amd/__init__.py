@@ -28,6 +28,7 @@ from .seg_measures import (aggregate_cod_measures, cod_measures, segmentation_hi
 from .instances import detect_instances, instance_records, mask_instances  # noqa: F401,E402
 from .instance_match import InstanceAP, instance_match_records, match_instances  # noqa: F401,E402
 from . import boundary  # noqa: F401,E402  (Boundary IoU / Boundary AP: reached as camouflage_multimodal_amd.boundary.<name>)
+from . import split  # noqa: F401,E402  (touching objects split at their necks: reached as camouflage_multimodal_amd.split.<name>)
 from .refine import guided_filter, guided_upsample  # noqa: F401,E402
 from .rle import (counts_to_string, decode_rles, encode_instances, label_runs, rle_area, rles_from_runs, string_to_counts)  # noqa: F401,E402
 from .polygons import (coco_ground_truth, decode_polygon_arrays, decode_polygons, decode_segmentations, polygons_to_rles)  # noqa: F401,E402

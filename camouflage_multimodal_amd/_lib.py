@@ -57,6 +57,10 @@ POLY_MAX_POLYGONS = 65535           # CAMO_POLY_MAX_POLYGONS
 POLY_MAX_VERTICES = 1 << 20         # CAMO_POLY_MAX_VERTICES
 POLY_MARGIN = 1024                  # CAMO_POLY_MARGIN
 POLY_MAX_PLANE_WORDS = 1 << 28      # CAMO_POLY_MAX_PLANE_WORDS
+SPLIT_MAX_SPLIT = 8                 # CAMO_SPLIT_MAX_SPLIT
+SPLIT_MAX_DEN = 16                  # CAMO_SPLIT_MAX_DEN
+SPLIT_COUNTS = 4                    # CAMO_SPLIT_COUNTS
+SPLIT_LAUNCHES = 13                 # CAMO_SPLIT_LAUNCHES
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -223,6 +227,10 @@ PROTOTYPES = {
     "camo_poly.h": (
         ("camo_poly_decode_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
         ("camo_poly_decode", i32, (vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
+    ),
+    "camo_split.h": (
+        ("camo_split_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_split_instances", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp)),
     ),
 }
 

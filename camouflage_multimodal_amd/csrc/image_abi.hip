@@ -1,5 +1,5 @@
 // C ABI of the image pipeline around the detector (include/camo_instances.h, camo_inst_match.h, camo_boundary.h, camo_guided.h,
-// camo_rle.h, camo_poly.h): argument checks, workspace carving and the launchers' calls.  No device code here.
+// camo_rle.h, camo_poly.h, camo_split.h): argument checks, workspace carving and the launchers' calls.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,6 +11,7 @@
 #include "guided.h"
 #include "rle.h"
 #include "poly.h"
+#include "split.h"
 #include "../../include/camo_rg_detect.h"
 #include "../../include/camo_instances.h"
 #include "../../include/camo_inst_match.h"
@@ -18,6 +19,7 @@
 #include "../../include/camo_guided.h"
 #include "../../include/camo_rle.h"
 #include "../../include/camo_poly.h"
+#include "../../include/camo_split.h"
 
 using namespace camo_abi;
 
@@ -147,6 +149,41 @@ int camo_boundary_match(const int32_t* pred_labels, const int32_t* gt_labels, co
   CK(launch_boundary_match(pred_labels, gt_labels, pred_bd, gt_bd, N, H, W, P, G, reinterpret_cast<const long long*>(pred_table),
                            pred_table ? pred_table_rows : 0, thr, T, w, inter, inter_bd, pred_rows, gt_area, match, gt_match, counts,
                            static_cast<hipStream_t>(stream)), "boundary match");
+  return 0;
+}
+
+// ---- Instance splitter: distance-transform cores, nearest-core cells (include/camo_split.h) -------------------------
+static int split_check(int N, int H, int W, int max_split) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (H > CAMO_SEG_WF_MAX_SIDE || W > CAMO_SEG_WF_MAX_SIDE) return fail(CAMO_E_ARG, "H and W must be at most CAMO_SEG_WF_MAX_SIDE");
+  if (max_split < 1 || max_split > CAMO_SPLIT_MAX_SPLIT) return fail(CAMO_E_ARG, "max_split must be in [1, CAMO_SPLIT_MAX_SPLIT]");
+  return 0;
+}
+
+size_t camo_split_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t max_split) {
+  if (split_check(N, H, W, max_split)) return 0;
+  return split_carve(N, H, W, max_split, nullptr).bytes;
+}
+
+int camo_split_instances(const int32_t* labels, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W, int32_t ratio_num,
+                         int32_t ratio_den, int32_t min_core, int32_t max_split, int32_t max_instances, int32_t* out_labels, int64_t* table,
+                         int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = split_check(N, H, W, max_split)) return e;
+  if (ratio_den < 2 || ratio_den > CAMO_SPLIT_MAX_DEN) return fail(CAMO_E_ARG, "ratio_den must be in [2, CAMO_SPLIT_MAX_DEN]");
+  if (ratio_num < 1 || ratio_num >= ratio_den) return fail(CAMO_E_ARG, "ratio_num must be in [1, ratio_den)");
+  if (min_core < 0) return fail(CAMO_E_ARG, "min_core must be >= 0");
+  if (max_instances < 1) return fail(CAMO_E_ARG, "max_instances must be >= 1");
+  if ((long long)N * max_instances > CAMO_INST_MAX_ROWS) return fail(CAMO_E_ARG, "N * max_instances exceeds CAMO_INST_MAX_ROWS");
+  if (pred && pred_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "pred_image_stride must be >= H * W");
+  if (!labels) return fail(CAMO_E_ARG, "labels is null");
+  if (!out_labels || !table || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
+  const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(out_labels), bytes = (uintptr_t)N * H * W * 4;
+  if (a < b + bytes && b < a + bytes) return fail(CAMO_E_ARG, "labels and out_labels must not overlap");
+  const SplitWs w = split_carve(N, H, W, max_split, ws);
+  if (int e = ws_check(ws, ws_bytes, w.bytes, "camo_split_workspace_bytes")) return e;
+  CK(launch_split(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, w, out_labels,
+                  reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "split instances");
   return 0;
 }
 

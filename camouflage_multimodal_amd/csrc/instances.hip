@@ -11,7 +11,7 @@
 //   count        per chunk of 1024 pixels: the kept roots, the dropped roots, the pixels of the kept
 //   scan         one block per image: the chunks' exclusive prefix of kept roots; counts
 //   rank         id[root] = the prefix + the kept roots before it in the chunk + 1 (0 when dropped); the image's table rows cleared
-//   emit         labels, clean, and the table's sums, minima and maxima, through a block's LDS slots
+//   emit         labels, clean, and the table's sums, minima and maxima, through a block's LDS slots (inst_emit_inl.h)
 //
 // With fill_holes the first three run twice: on the background with the complementary connectivity, then on the filled foreground.
 // Union by atomicMin on the larger root (cc_inl.h): the output depends on the partition alone.  Integer atomics only.
@@ -22,6 +22,7 @@
 #include "abi_util.h"
 #include "cc_inl.h"
 #include "common.h"
+#include "inst_emit_inl.h"
 #include "instances.h"
 #include "label_inl.h"
 
@@ -30,7 +31,6 @@ namespace {
 constexpr int T = INST_TILE, NT = INST_NT, CHUNK = INST_CHUNK, PPT = INST_CHUNK / INST_NT;
 constexpr int MODE_BG = 0, MODE_FG = 1, MODE_FILLED = 2;
 constexpr int NONE = 0x7fffffff;
-constexpr unsigned long long BOX_MIN_INIT = 0x7fffffffffffffffull;
 static_assert(T * T % NT == 0 && CHUNK % NT == 0 && NT % 64 == 0, "whole waves, whole passes");
 
 // grid (tiles of an image, images; an image loop when the grid would be too large).  MODE_BG: members are the background pixels,
@@ -201,14 +201,7 @@ __global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ p
   __shared__ int wcount[NT / 64];
   const int tid = threadIdx.x, n = blockIdx.y, HW = H * W;
   const size_t base = (size_t)n * HW;
-  {
-    const long long K = counts[4 * n], cells = (long long)max_instances * 8;
-    unsigned long long* rows = table + (size_t)n * cells;
-    for (long long i = (long long)blockIdx.x * NT + tid; i < cells; i += (long long)gridDim.x * NT) {
-      const int f = (int)(i & 7);
-      rows[i] = ((i >> 3) < K && (f == 1 || f == 2)) ? BOX_MIN_INIT : 0ull;
-    }
-  }
+  emit_clear_rows<NT>(table + (size_t)n * max_instances * 8, counts[4 * n], max_instances);
   int running = chunk[(size_t)n * gridDim.x + blockIdx.x];
   for (int j = 0; j < PPT; ++j) {
     const int q = blockIdx.x * CHUNK + j * NT + tid;
@@ -223,21 +216,15 @@ __global__ __launch_bounds__(NT) void inst_rank_kernel(const int* __restrict__ p
   }
 }
 
-// grid (chunks, images).  labels and clean of every pixel, and the table: a run of equal ids over consecutive lanes inside one image
-// row is one record (len, x, y, sum of q) whose sums have closed forms.  A record goes to the id's slot of a small LDS table (open
-// addressing from id mod EMIT_SLOTS; to the table in memory when every slot is another id's), and the block adds its slots to the
-// table in memory once: a block of one large object costs eight atomics, whatever else crosses its rows.
-constexpr int EMIT_SLOTS = 16;
+// grid (chunks, images).  labels and clean of every pixel, and the table through inst_emit_inl.h's run records and LDS slots.
 __global__ __launch_bounds__(NT) void inst_emit_kernel(const float* __restrict__ pred, long long stride, const int* __restrict__ par,
                                                        const int* __restrict__ rid, int H, int W, int max_instances, int* __restrict__ labels,
                                                        unsigned char* __restrict__ clean, unsigned long long* __restrict__ table) {
-  __shared__ int slot_id[EMIT_SLOTS];                             // 0: free
-  __shared__ unsigned long long slot[EMIT_SLOTS][8];
-  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.y, HW = H * W;
+  __shared__ EmitSlots slots;
+  const int tid = threadIdx.x, n = blockIdx.y, HW = H * W;
   const size_t base = (size_t)n * HW;
   const float* img = pred + (size_t)n * stride;
-  if (tid < EMIT_SLOTS) slot_id[tid] = 0;
-  if (tid < EMIT_SLOTS * 8) slot[tid >> 3][tid & 7] = ((tid & 7) == 1 || (tid & 7) == 2) ? BOX_MIN_INIT : 0ull;
+  emit_slots_clear(slots);
   __syncthreads();
   unsigned long long* rows = table + (size_t)n * max_instances * 8;
 #pragma unroll
@@ -254,41 +241,10 @@ __global__ __launch_bounds__(NT) void inst_emit_kernel(const float* __restrict__
       clean[p] = id > 0 ? 1 : 0;
       if (id <= max_instances) k = id;                            // (ids past the table keep their label and have no row)
     }
-    if (__ballot(k > 0) == 0ull) continue;                        // (wave-uniform)
-    const int y = q / W, x = q - y * W;                            // (k > 0 only where q < HW)
-    const int qv = k > 0 ? quantise_u8(pv) : 0;
-    const int prev = __shfl_up(k, 1, 64);
-    const bool head = lane == 0 || prev != k || x == 0;
-    const int end = run_end(head, lane), len = end - lane;
-    const int pre = wave_scan_int(qv);                             // inclusive prefix of q over the wave (at most 64 * 255)
-    const int sq = __shfl(pre, end - 1, 64) - (pre - qv);
-    if (head && k > 0) {                                           // (no branch around the shuffles above: every lane takes them)
-      const unsigned long long sx = (unsigned long long)len * x + (unsigned long long)len * (len - 1) / 2, sy = (unsigned long long)len * y;
-      unsigned long long* row = rows + (size_t)(k - 1) * 8;        // the table in memory, unless a slot takes the record
-      int s = k & (EMIT_SLOTS - 1);
-      for (int probe = 0; probe < EMIT_SLOTS; ++probe, s = (s + 1) & (EMIT_SLOTS - 1)) {
-        const int old = atomicCAS(&slot_id[s], 0, k);
-        if (old == 0 || old == k) { row = slot[s]; break; }
-      }
-      atomicAdd(row + 0, (unsigned long long)len);
-      atomicMin(row + 1, (unsigned long long)x);
-      atomicMin(row + 2, (unsigned long long)y);
-      atomicMax(row + 3, (unsigned long long)(x + len - 1));
-      atomicMax(row + 4, (unsigned long long)y);
-      atomicAdd(row + 5, sx);
-      atomicAdd(row + 6, sy);
-      atomicAdd(row + 7, (unsigned long long)sq);
-    }
+    emit_record(slots, rows, k, q, W, quantise_u8(pv));
   }
   __syncthreads();
-  if (tid >= EMIT_SLOTS * 8) return;
-  const int k = slot_id[tid >> 3], f = tid & 7;
-  if (k == 0) return;
-  const unsigned long long v = slot[tid >> 3][f];
-  unsigned long long* cell = rows + (size_t)(k - 1) * 8 + f;
-  if (f == 1 || f == 2) atomicMin(cell, v);
-  else if (f == 3 || f == 4) atomicMax(cell, v);
-  else atomicAdd(cell, v);
+  emit_slots_flush(slots, rows);
 }
 
 unsigned blocks_of(long long count) { return (unsigned)((count + NT - 1) / NT); }

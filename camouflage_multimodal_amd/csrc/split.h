@@ -1,0 +1,30 @@
+// Instance splitter (split.hip, include/camo_split.h): the constants the kernels, the launcher and the entry points
+// share.  The launcher returns hipError_t as int.
+#pragma once
+#include "common.h"
+
+constexpr int SPLIT_IDS = 1025;        // an image's per-id arrays: entry 0 (background) and CAMO_IM_MAX_IDS ids
+constexpr int SPLIT_IDS_PAD = 1088;    // ints between two images' per-id arrays
+constexpr int SPLIT_MAX_SLOTS = 8;     // CAMO_SPLIT_MAX_SPLIT
+constexpr int SPLIT_MAX_SIDE = 2048;   // CAMO_SEG_WF_MAX_SIDE: a row of column distances in LDS
+
+struct SplitWs {
+  int* d2;                 // [N][H][W] the nearest background row of the pixel's column, then D2 (-1: the image has no background)
+  int* par;                // [N][H][W] union-find parent of the core pixels (index into the whole batch), -1 elsewhere
+  int* area;               // [N][H][W] area[root] = pixels of the root's core
+  int* rid;                // [N][H][W] rid[root] = the new id of a kept core of a split id
+  short* site;             // [N][max_split][H][W] the nearest site row of the slot's id in the pixel's column, -1: none
+  int* chunk;              // [N][max_split][chunks] per chunk the slot's kept cores, then their exclusive prefix
+  int* m2;                 // [N][SPLIT_IDS_PAD] M2(id) + 2, 0: the id has no pixel
+  int* ncore;              // [N][SPLIT_IDS_PAD] the id's kept cores
+  int* parts;              // [N][SPLIT_IDS_PAD] the id's parts
+  int* first;              // [N][SPLIT_IDS_PAD] the parts of the ids before it: its first new id - 1
+  int* slot_of;            // [N][SPLIT_IDS_PAD] the id's split slot, -1: it stays whole
+  int* slot_id;            // [N][SPLIT_MAX_SLOTS] the slot's id, 0: free
+  int* dropped;            // [N] cores dropped as small
+  size_t bytes;
+};
+SplitWs split_carve(int N, int H, int W, int max_split, void* base);
+
+int launch_split(const int* labels, const float* pred, long long stride, int N, int H, int W, int num, int den, int min_core, int max_split,
+                 int max_instances, const SplitWs& ws, int* out, long long* table, int* counts, hipStream_t stream);

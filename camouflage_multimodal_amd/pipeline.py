@@ -16,7 +16,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, boundary as _boundary, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures
+from . import _lib, boundary as _boundary, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures, \
+    split as _split
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 from .resize import _device, _mask_list, _packed, _ragged, resize_batch, resize_to_sizes
 from .rg_detect import paint_regions, segmentation_counts, segmentation_metrics
@@ -107,6 +108,15 @@ def _native_boundary_ious(masks, truths, boundary):
     return _by_size(masks, lambda idx, _: _boundary.boundary_iou(_stack(masks, idx), _positive(_stack(truths, idx)), boundary["distance"], boundary["ratio"]))
 
 
+def _split_found(found, prob, split):
+    """``split.split_detected`` of detected instances (``detect_instances``' "instances" and "labels") with the probability they came
+    from; ``split``: ``split_options``' dict.  An image with more ids than a label map may hold for the splitter raises."""
+    most = max(r["count"] for r in found["instances"])
+    if most > _lib.IM_MAX_IDS:
+        raise ValueError(f"split takes at most {_lib.IM_MAX_IDS} instances per image, an image holds {most}: raise min_area")
+    return _split.split_detected(found["labels"], prob, split)
+
+
 def _check_sources(match, n, noun):
     for key, what in GT_SOURCES:
         if match[key] is not None and len(match[key]) != n:
@@ -130,7 +140,8 @@ def _match_ground_truth(match, n, noun, sizes, masks, connectivity, device):
 
 @torch.no_grad()
 def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
-                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None):
+                            instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None,
+                            split=False):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -167,10 +178,17 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     (``boundary.match_detected_boundary``, include/camo_boundary.h) and adds "boundary_match" (per image the records of
     ``boundary.boundary_match_records``: ``InstanceAP`` of them is Boundary AP) and "boundary_match_tables"; with ``gt_masks`` also
     "boundary_iou" (per image ``boundary.boundary_iou`` of "mask" against the ground-truth mask) and, with ``refine``,
-    "refined_boundary_iou" (of "mask_refined": what the guided filter did to the contour).  Every other key keeps its bytes."""
+    "refined_boundary_iou" (of "mask_refined": what the guided filter did to the contour).  Every other key keeps its bytes.
+    ``split`` -- ``False`` (off: no launch more than before), ``True`` or a dict with any of "ratio" ((7, 10)), "min_core" (0),
+    "max_split" (4), "max_instances" (64) -- needs ``instances=True``; it splits the touching objects of "instance_labels" at their
+    necks (``split.split_detected``, include/camo_split.h) and adds "split_instances" (per image the records of
+    ``split.split_records``, scored by the mask probability), "split_labels" int32 [N, H, W] and "split_counts" int32 [N, 4].
+    ``match``, ``boundary`` and ``rle`` then work on the split labels and table, so instance AP and Boundary AP measure the split;
+    "instances", "instance_labels", "clean_mask" and every metric of the mask keep their bytes."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
+    split = _split.split_options(split, instances)
     match = _match.match_options(match, instances, gt_masks is not None)
     boundary = _boundary.boundary_options(boundary, match)
     refine = _refine.refine_options(refine)
@@ -201,6 +219,9 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
                     "instance_counts": found["counts"]})
         if gt is not None:
             out["clean_metrics"] = segmentation_metrics(segmentation_counts(found["clean_mask"].float(), gt, 0.5), H, W)
+        if split is not None:
+            found = _split_found(found, prob_maps[:, 0], split)
+            out.update({"split_instances": found["instances"], "split_labels": found["labels"], "split_counts": found["counts"]})
         if match is not None:
             gt_labels = match["gt_labels"]      # (a [N, H, W] tensor goes on as it is: ``match_detected`` holds it to the labels' shape)
             if gt_labels is None:
@@ -227,20 +248,20 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
 
 
 def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
-                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None):
+                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None, split=False):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
     return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
-                                   connectivity, refine, match=match, rle=rle, boundary=boundary)
+                                   connectivity, refine, match=match, rle=rle, boundary=boundary, split=split)
 
 
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
                              cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None,
-                             *, match=None, rle=False, boundary=None):
+                             *, match=None, rle=False, boundary=None, split=False):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -268,10 +289,14 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     (``rle.encode_instances``; maps of equal size share a call).
     ``boundary`` (``detect_camouflage_batch``'s; needs ``match``) works at NATIVE size, with the distance of every size group from
     its own H and W: "boundary_match" (per image the records), "boundary_match_tables" (per image its own rows) and, with masks
-    scored at native size, "boundary_iou" of "mask_native" and, with ``refine``, "refined_boundary_iou" of "mask_native_refined"."""
+    scored at native size, "boundary_iou" of "mask_native" and, with ``refine``, "refined_boundary_iou" of "mask_native_refined".
+    ``split`` (``detect_camouflage_batch``'s; needs ``instances=True``) splits the NATIVE-size instances, maps of equal size sharing a
+    call: "split_instances_native" (per image the records), "split_labels_native" (int32 [H_i, W_i]) and "split_counts_native"
+    (int32 [4]); ``match``, ``boundary`` and ``rle`` then work on them."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
+    split = _split.split_options(split, instances)
     match = _match.match_options(match, instances, gt_masks is not None and evaluate_at == "native")
     boundary = _boundary.boundary_options(boundary, match)
     refine = _refine.refine_options(refine)
@@ -310,6 +335,13 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         out.update({"instances_native": rec, "instance_labels_native": labels, "clean_mask_native": clean})
         if truth is not None:
             out["clean_metrics"], _ = _score([c.float() for c in clean], truth, 0.5, False)
+        if split is not None:
+            def parts(idx, _):
+                f = _split_found({"instances": [rec[i] for i in idx], "labels": _stack(labels, idx)}, _stack(native, idx), split)
+                return f["instances"], f["labels"], f["table"], f["counts"]
+
+            split_rec, labels, tables, split_counts = _by_size(native, parts, 4)
+            out.update({"split_instances_native": split_rec, "split_labels_native": labels, "split_counts_native": split_counts})
         if match is not None:
             gt_labels = _match_ground_truth(match, len(sizes), "images", sizes, truth, connectivity, img.device)
             out["instance_match"], out["instance_match_tables"] = _native_matches(labels, tables, gt_labels, match)
@@ -364,9 +396,12 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     "score": the instance's Sq / (255 area), "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1]}; the result also holds "results": that list.
     With ``boundary`` (``detect_camouflage_ragged``'s; needs ``match``) the result also holds "boundary_match" (per-file records) and
     "boundary_ap": ``InstanceAP`` over them, which is Boundary AP; with masks scored at native size also "boundary_iou" per file and,
-    with ``refine``, "refined_boundary_iou"."""
+    with ``refine``, "refined_boundary_iou".
+    With ``split`` (``detect_camouflage_ragged``'s; needs ``instances=True``) the instances matched, scored and written to
+    ``results_json`` are the split ones ("split_instances_native")."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
+    found_key = "instances_native" if _split.split_options(kw.get("split", False), kw.get("instances", False)) is None else "split_instances_native"
     match = _match.match_options(kw.pop("match", None), kw.get("instances", False), mask_dir is not None, coco=True)
     boundary = _boundary.boundary_options(kw.get("boundary"), match)
     if results_json is not None:
@@ -428,13 +463,13 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
                 _match_ground_truth(match, len(part), "files", gts.sizes, [gts.image(i) for i in range(len(part))], kw.get("connectivity", 8), None)
             out = detect_camouflage_ragged(rg_model, arrays, match=dict(match, **{source or "gt_labels": ids}), **kw)
             matched += out["instance_match"]
-            scores = [[inst["score"] for inst in r["instances"]] for r in out["instances_native"]]
+            scores = [[inst["score"] for inst in r["instances"]] for r in out[found_key]]
             ap.add(out["instance_match"], scores)
             if boundary is not None:
                 bd_matched += out["boundary_match"]
                 bd_ap.add(out["boundary_match"], scores)
         if results_json is not None:
-            results += _rle.coco_results(part, out["instances_native"], out["instance_rles_native"], image_ids)
+            results += _rle.coco_results(part, out[found_key], out["instance_rles_native"], image_ids)
         native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
         if out_dir is not None:
             for s, p in zip(part, native):

@@ -1,0 +1,151 @@
+"""Touching objects split on MI355X (include/camo_split.h): one connected component of the mask that holds two
+animals becomes two instances.
+
+``mask_instances`` finds objects as connected components, so two objects that touch, or that one superpixel bridges, are one
+instance.  ``split_instances`` runs ``camo_split_instances`` on a label map -- the exact squared distance to the background, the
+cores above ``ratio`` of each id's largest distance, every pixel of an id with two cores or more to the core of its own id with the
+nearest core pixel -- and returns device tensors; ``split_records`` takes the ratios from the integers on the host;
+``split_detected`` is the two together with a table that always holds every instance, for the pipeline; ``split_options`` is the
+pipeline's ``split`` keyword.
+PARITY UNPINNED: the header's text is the definition (restated in numpy in tests/split_ref.py).  There is no CPU path: tensors
+that are not on a HIP device raise.
+"""
+from __future__ import annotations
+
+import numbers
+
+import torch
+
+from . import _lib
+from .engine import _ptr, _stream_ptr
+from .instances import instance_records
+
+RATIO = (7, 10)
+OPTIONS = {"ratio": RATIO, "min_core": 0, "max_split": 4, "max_instances": 64}
+
+
+def _integer(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def check_arguments(ratio=RATIO, min_core=0, max_split=4, max_instances=64, n_images=1):
+    """The ``ValueError`` of every bad setting, by name, before anything touches the device.  -> (num, den) of ``ratio``."""
+    if not isinstance(ratio, (tuple, list)) or len(ratio) != 2 or not all(_integer(v) for v in ratio) or \
+            not 0 < ratio[0] < ratio[1] <= _lib.SPLIT_MAX_DEN:
+        raise ValueError(f"ratio must be a pair of integers (num, den) with 0 < num < den <= {_lib.SPLIT_MAX_DEN}, got {ratio!r}")
+    if not _integer(min_core) or min_core < 0:
+        raise ValueError(f"min_core must be an integer >= 0, got {min_core!r}")
+    if not _integer(max_split) or not 1 <= max_split <= _lib.SPLIT_MAX_SPLIT:
+        raise ValueError(f"max_split must be an integer in [1, {_lib.SPLIT_MAX_SPLIT}], got {max_split!r}")
+    if not _integer(max_instances) or max_instances < 1:
+        raise ValueError(f"max_instances must be an integer >= 1, got {max_instances!r}")
+    if n_images * max_instances > _lib.INST_MAX_ROWS:
+        raise ValueError(f"max_instances = {max_instances} for {n_images} images exceeds {_lib.INST_MAX_ROWS} table rows")
+    return int(ratio[0]), int(ratio[1])
+
+
+def _label_map(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"need {name} [N, H, W] or [H, W] with at least one pixel, got {tuple(t.shape)}")
+    if t.dtype != torch.int32:
+        raise ValueError(f"{name} must be int32, got {t.dtype}")
+    return t
+
+
+@torch.no_grad()
+def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max_instances=64):
+    """``camo_split_instances``: ``labels`` int32 [N, H, W] (or [H, W]), 0 on background and an id in 1 .. 1024 per component
+    (``mask_instances``' "labels"); ``pred``: ``None``, or the fp32 [N, H, W] probability the labels came from (one channel of a
+    [N, C, H, W] map is read in place), for the table's Sq -> {"labels": int32 [N, H, W], the new ids 1 .. K' in input-id order, the
+    parts of one id in the reading order of their cores' first pixels; "table": int64 [N, max_instances, 8] = ``mask_instances``'
+    row of every new id (Sq 0 without ``pred``); "counts": int32 [N, 4] = (K', ids split, cores dropped as smaller than ``min_core``,
+    qualifying ids left whole because ``max_split`` were split before them)}, all on the device, no host synchronisation.  A pixel
+    is a core pixel when its squared distance to the background exceeds (num / den)^2 of its id's largest, ``ratio`` = (num, den)."""
+    labels = _label_map(labels, "labels")
+    N, H, W = labels.shape
+    if pred is not None:
+        if not isinstance(pred, torch.Tensor):
+            raise ValueError("pred must be a tensor or None")
+        if pred.dim() == 2:
+            pred = pred.unsqueeze(0)
+        if tuple(pred.shape) != (N, H, W):
+            raise ValueError(f"need pred of labels' shape {(N, H, W)}, got {tuple(pred.shape)}")
+    num, den = check_arguments(ratio, min_core, max_split, max_instances, N)
+    _lib.require_device(labels, "labels")
+    labels = labels.detach().contiguous()
+    stride = 0
+    if pred is not None:
+        _lib.require_device(pred, "pred")
+        pred = pred.detach()
+        if pred.dtype != torch.float32 or pred.stride(2) != 1 or pred.stride(1) != W or (N > 1 and pred.stride(0) < H * W):
+            pred = pred.to(torch.float32).contiguous()
+        stride = pred.stride(0) if N > 1 else H * W
+    dev = labels.device
+    L = _lib.lib()
+    nbytes = L.camo_split_workspace_bytes(N, H, W, int(max_split))
+    if nbytes == 0:
+        raise ValueError(f"camo_split_instances does not support N = {N}, H = {H}, W = {W} (a side is at most {_lib.SEG_WF_MAX_SIDE})")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(labels)
+    table = torch.empty(N, int(max_instances), _lib.INST_FIELDS, dtype=torch.int64, device=dev)
+    counts = torch.empty(N, _lib.SPLIT_COUNTS, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.camo_split_instances(_ptr(labels), None if pred is None else _ptr(pred), stride, N, H, W, num, den, int(min_core), int(max_split),
+                                    int(max_instances), _ptr(out), _ptr(table), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
+    _lib.check(rc, "camo_split_instances")
+    return {"labels": out, "table": table, "counts": counts}
+
+
+def split_records(table, counts, H, W):
+    """``instance_records`` on ``split_instances``' table plus its counts (tensors or nested lists; device tensors cost the one host
+    copy).  Per image {"instances": [{"id", "area", "box", "centroid", "score"} in id order], "count": K', "truncated": K' > the rows
+    the table holds, "split": the ids split, "cores_dropped", "left_whole": the qualifying ids past ``max_split``}."""
+    if isinstance(table, torch.Tensor) and isinstance(counts, torch.Tensor):
+        rows = table.shape[1] if table.dim() == 3 else 0
+        flat = torch.cat([table.reshape(-1), counts.to(device=table.device, dtype=torch.int64).reshape(-1)]).tolist()      # (the one copy)
+        nt, F, C = table.numel(), _lib.INST_FIELDS, _lib.SPLIT_COUNTS
+        counts = [flat[nt + C * i: nt + C * (i + 1)] for i in range(counts.shape[0])]
+        table = [[flat[(i * rows + k) * F: (i * rows + k + 1) * F] for k in range(rows)] for i in range(table.shape[0])]
+    counts = [list(c) for c in counts]
+    if any(len(c) != _lib.SPLIT_COUNTS for c in counts):
+        raise ValueError(f"need counts rows of {_lib.SPLIT_COUNTS} integers")
+    base = instance_records(table, [[c[0], 0, 0, 0] for c in counts], H, W)
+    return [{"instances": r["instances"], "count": r["count"], "truncated": r["truncated"], "split": int(c[1]), "cores_dropped": int(c[2]),
+             "left_whole": int(c[3])} for r, c in zip(base, counts)]
+
+
+def split_options(split, instances=True):
+    """The pipeline's ``split`` keyword -- ``None`` or ``False`` (off), ``True`` or a dict with any of "ratio" ((7, 10)), "min_core"
+    (0), "max_split" (4) and "max_instances" (64) -- as a dict with all four, or ``None``; the ``ValueError`` of a bad one by name,
+    before anything touches the device.  ``instances``: the pipeline's keyword -- the instances are what it splits."""
+    if split is None or split is False:
+        return None
+    if split is True:
+        split = {}
+    if not isinstance(split, dict) or set(split) - set(OPTIONS):
+        raise ValueError(f'split must be None, False, True or a dict with any of "ratio", "min_core", "max_split", "max_instances", got {split!r}')
+    if not instances:
+        raise ValueError("split needs instances=True: the instances are what it splits")
+    opts = {**OPTIONS, **split}
+    opts["ratio"] = check_arguments(**opts)
+    return opts
+
+
+@torch.no_grad()
+def split_detected(labels, pred, opts):
+    """``split_instances`` and ``split_records`` together, for the pipeline: ``split_instances``' dict plus "instances"
+    (``split_records``' list).  ``opts``: ``split_options``' dict.  When an image holds more than "max_instances" parts the call is
+    made once more with the table sized to the largest count, so no list is truncated."""
+    args = (opts["ratio"], opts["min_core"], opts["max_split"])
+    out = split_instances(labels, pred, *args, opts["max_instances"])
+    H, W = out["labels"].shape[1:]
+    rec = split_records(out["table"], out["counts"], H, W)
+    if any(r["truncated"] for r in rec):
+        out = split_instances(labels, pred, *args, max(r["count"] for r in rec))
+        rec = split_records(out["table"], out["counts"], H, W)
+    out["instances"] = rec
+    return out
