@@ -28,6 +28,8 @@ RGD_NPARAMS = 12                    # CAMO_RGD_NPARAMS
 RGD_MAX_CHANNELS = 16               # CAMO_RGD_MAX_CHANNELS
 RGD_FIX_BITS = 32                   # CAMO_RGD_FIX_BITS
 RGT_NGRADS = 32                     # CAMO_RGT_NGRADS
+RGPL_MAX_RADIUS = 31                # CAMO_RGPL_MAX_RADIUS
+RGPL_MAX_GAIN = 16                  # CAMO_RGPL_MAX_GAIN
 SEG_BINS = 256                      # CAMO_SEG_BINS
 SEG_QUADRANTS = 4                   # CAMO_SEG_QUADRANTS
 SEG_HIST_INTS = 2048                # CAMO_SEG_HIST_INTS
@@ -190,6 +192,11 @@ PROTOTYPES = {
     ),
     "camo_rg_targets.h": (
         ("camo_rg_node_targets", i32, (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp)),
+    ),
+    "camo_rg_pixel_loss.h": (
+        ("camo_rg_pixel_weights", i32, (vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp)),
+        ("camo_rg_loss_backward_pixel", i32, (rgdims, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, sz, vp, vp, f32, vp, vp,
+                                              i32, f32, f32, f32, u64, vp, vp, i32, i32, f32, vp)),
     ),
     "camo_seg_measures.h": (
         ("camo_seg_histograms", i32, (vp, i64, vp, i32, i32, i32, vp, vp, vp)),

@@ -1,7 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
 // sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
-// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, and
-// the node targets from ground-truth masks.  The image pipeline around the detector (instances, their matching, boundary maps, the
+// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, with or
+// without the structure loss on the painted mask, and the node targets and node weights from ground-truth masks.  The image pipeline around the detector (instances, their matching, boundary maps, the
 // guided filter, run-length masks, polygons) has image_abi.hip.  No device code here.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "rg_detect.h"
 #include "rg_train.h"
 #include "rg_targets.h"
+#include "rg_pixel_loss.h"
 #include "../../include/camo_rg_gnn.h"
 #include "../../include/camo_rg_features.h"
 #include "../../include/camo_rg_batch.h"
@@ -27,6 +28,7 @@
 #include "../../include/camo_rg_train_bn.h"
 #include "../../include/camo_rg_train_drop.h"
 #include "../../include/camo_rg_targets.h"
+#include "../../include/camo_rg_pixel_loss.h"
 
 using namespace camo_abi;
 
@@ -465,12 +467,15 @@ size_t camo_rg_train_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_cla
 // The one launch sequence of all three entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
 // (its stats and partial are filled in here from the workspace).  drop: null = no dropout, else include/camo_rg_train_drop.h -- the
 // forward's eight sites, and in the backward nothing but a scale: every ReLU mask is taken from the saved, dropped activation, which
-// is > 0 exactly where the element was kept and the ReLU is open, so the mask's 1 becomes 1 / (1 - p).
+// is > 0 exactly where the element was kept and the ReLU is open, so the mask's 1 becomes 1 / (1 - p).  pixel: null = today's sequence
+// launch for launch, else include/camo_rg_pixel_loss.h -- two launches right after the loss, which add the pixel term to dlogits and
+// to the loss figures (loss is float[6] then); the backward that follows does not know.
 static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
                    const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
                    const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
                    const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch, const RgDropout* drop = nullptr) {
+                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch, const RgDropout* drop = nullptr,
+                   const RgPixel* pixel = nullptr) {
   if (int e = batch ? rgtbn_check(dims, num_classes, N, E) : rgt_check(dims, num_classes, N, E)) return e;
   if (!params || !head_params || !x || !rowptr || !col || !w || !rrowptr || !rcol || !rw || !mask_t || !inst_t || !edge_t || !workspace ||
       !loss || !grads)
@@ -524,6 +529,7 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
 
   // ---- loss and dlogits ----
   CK(launch_rgt_loss(ws.logits, mask_t, inst_t, edge_t, w_mask, w_instance, w_edge, N, nc, loss, ws.dlogits, st), "loss");
+  if (pixel) CK(launch_rgt_pixel_loss(ws.logits, *pixel, N, nc, loss, ws.dlogits, st), "pixel loss");
 
   // ---- heads backward ----
   CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dlogits, L, L, N, ws.partial, st), "head bias sums");
@@ -606,12 +612,14 @@ size_t camo_rg_train_drop_workspace_bytes(const camo_rg_dims_t* dims, int32_t nu
   return batch_stats ? camo_rg_train_bn_workspace_bytes(dims, num_classes, N, E) : camo_rg_train_workspace_bytes(dims, num_classes, N, E);
 }
 
-int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
-                               const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
-                               const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
-                               const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                               float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
-                               int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream) {
+// camo_rg_loss_backward_drop, and camo_rg_loss_backward_pixel (include/camo_rg_pixel_loss.h) once it has checked its own arguments
+static int rgt_run_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                        const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                        const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                        const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                        float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
+                        int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream,
+                        const RgPixel* pixel) {
   if (batch_stats_mode != 0 && batch_stats_mode != 1) return fail(CAMO_E_ARG, "batch_stats_mode must be 0 (frozen statistics) or 1 (batch statistics)");
   for (float p : {p_conv, p_shared, p_head})
     if (!std::isfinite(p) || !(p >= 0.f && p < 1.f)) return fail(CAMO_E_ARG, "dropout rates must be finite and in [0, 1)");
@@ -623,7 +631,41 @@ int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, 
   const RgDropout drop{make_drop(1, p_conv, seed), make_drop(1, p_shared, seed), make_drop(1, p_head, seed)};
   const bool any = p_conv > 0.f || p_shared > 0.f || p_head > 0.f;      // all zero: the mode's existing entry, launch for launch
   return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
-                 w_edge, workspace, workspace_bytes, loss, grads, stream, batch_stats_mode ? &batch : nullptr, any ? &drop : nullptr);
+                 w_edge, workspace, workspace_bytes, loss, grads, stream, batch_stats_mode ? &batch : nullptr, any ? &drop : nullptr, pixel);
+}
+
+int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                               const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                               const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                               const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                               float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
+                               int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream) {
+  return rgt_run_drop(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask,
+                      w_instance, w_edge, workspace, workspace_bytes, loss, grads, momentum, running, batch_stats, batch_stats_mode, p_conv,
+                      p_shared, p_head, seed, stream, nullptr);
+}
+
+// ---- The same with the structure loss on the painted mask (include/camo_rg_pixel_loss.h) -----------------------------
+static_assert(RGPL_MAX_RADIUS == CAMO_RGPL_MAX_RADIUS && RGPL_MAX_GAIN == CAMO_RGPL_MAX_GAIN, "include/camo_rg_pixel_loss.h states the kernel's constants");
+
+int camo_rg_loss_backward_pixel(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
+                                const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
+                                const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
+                                const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
+                                float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
+                                int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, const int64_t* node_w,
+                                const int32_t* node_off, int32_t n_images, int32_t radius, float w_pixel, void* stream) {
+  if (num_classes != 2) return fail(CAMO_E_UNSUPPORTED, "the pixel loss needs num_classes == 2 (one logit difference per node)");
+  if (n_images < 1) return fail(CAMO_E_ARG, "n_images must be >= 1");
+  if (radius < 0 || radius > CAMO_RGPL_MAX_RADIUS) return fail(CAMO_E_ARG, "radius must be in [0, CAMO_RGPL_MAX_RADIUS]");
+  if (!std::isfinite(w_pixel) || !(w_pixel >= 0.f)) return fail(CAMO_E_ARG, "w_pixel must be finite and >= 0");
+  if (!node_w) return fail(CAMO_E_ARG, "node_w is null");
+  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
+  static_assert(sizeof(long long) == sizeof(int64_t), "node_w is int64");
+  const RgPixel pixel{reinterpret_cast<const long long*>(node_w), node_off, n_images, radius, w_pixel};
+  return rgt_run_drop(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask,
+                      w_instance, w_edge, workspace, workspace_bytes, loss, grads, momentum, running, batch_stats, batch_stats_mode, p_conv,
+                      p_shared, p_head, seed, stream, &pixel);
 }
 
 // ---- Node targets from ground-truth masks (include/camo_rg_targets.h) ------------------------------------------
@@ -652,6 +694,29 @@ int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, con
   if (!edge_t) return fail(CAMO_E_ARG, "edge_t is null");
   CK(launch_rg_node_targets(segments, region_map, node_off, gt_mask, gt_instance, gt_edge, N, H, W, label_bound, n_nodes, band_permille,
                             edge_min_pixels, counts, mask_t, inst_t, edge_t, static_cast<hipStream_t>(stream)), "rg node targets");
+  return 0;
+}
+
+// ---- Node weights of the pixel loss from ground-truth masks (include/camo_rg_pixel_loss.h) ----------------------------
+int camo_rg_pixel_weights(const int32_t* segments, const int32_t* region_map, const int32_t* node_off, const uint8_t* gt_mask, int32_t N,
+                          int32_t H, int32_t W, int32_t label_bound, int32_t n_nodes, int32_t radius, int32_t gain, int64_t* node_w,
+                          void* stream) {
+  if (N < 1) return fail(CAMO_E_ARG, "N must be >= 1");
+  if (H < 1) return fail(CAMO_E_ARG, "H must be >= 1");
+  if (W < 1) return fail(CAMO_E_ARG, "W must be >= 1");
+  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, CAMO_RG_MAX_LABELS]");
+  if (n_nodes < 1) return fail(CAMO_E_ARG, "n_nodes must be >= 1");
+  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGB_MAX_PIXELS");
+  if (radius < 0 || radius > CAMO_RGPL_MAX_RADIUS) return fail(CAMO_E_ARG, "radius must be in [0, CAMO_RGPL_MAX_RADIUS]");
+  if (gain < 0 || gain > CAMO_RGPL_MAX_GAIN) return fail(CAMO_E_ARG, "gain must be in [0, CAMO_RGPL_MAX_GAIN]");
+  if (!segments) return fail(CAMO_E_ARG, "segments is null");
+  if (!region_map) return fail(CAMO_E_ARG, "region_map is null");
+  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
+  if (!gt_mask) return fail(CAMO_E_ARG, "gt_mask is null");
+  if (!node_w) return fail(CAMO_E_ARG, "node_w is null");
+  CK(launch_rg_pixel_weights(segments, region_map, node_off, gt_mask, N, H, W, label_bound, n_nodes, radius, gain,
+                             reinterpret_cast<long long*>(node_w), static_cast<hipStream_t>(stream)), "rg pixel weights");
   return 0;
 }
 }  // extern "C"

@@ -29,6 +29,12 @@ int launch_rgt_head_logits(const float* const* hp, const float* Z, float* logits
 // weight / count
 int launch_rgt_loss(const float* logits, const int* mask_t, const int* inst_t, const float* edge_t, float wm, float wi, float we, int N,
                     int nc, float* loss, float* dlogits, hipStream_t stream);
+// The structure loss on the painted mask (include/camo_rg_pixel_loss.h): node_w [N, 2] int64 = (A, B) per node, node_off
+// [n_images + 1] (clamped to [0, N] on the device).  TWO launches after launch_rgt_loss, nc == 2: one block per image adds
+// w_pixel dP/dz to dlogits[v][1] and subtracts it from dlogits[v][0]; one block adds w_pixel P to loss[0] and writes loss[4], loss[5]
+// = mean wbce, mean wiou.  w_pixel == 0: dlogits and loss[0] keep their bytes.
+struct RgPixel { const long long* node_w; const int* node_off; int n_images; int radius; float w_pixel; };
+int launch_rgt_pixel_loss(const float* logits, const RgPixel& px, int N, int nc, float* loss, float* dlogits, hipStream_t stream);
 // dZ [N, 3 hidden / 2] = (Z > 0 ? scale : 0) * dlogits_h . W2_h   (scale: 1, or 1 / (1 - p_head) when Z is the dropped activation)
 int launch_rgt_head_dz(const float* const* hp, const float* Z, const float* dlogits, float* dZ, int N, int hidden, int nc, hipStream_t stream,
                        float scale = 1.f);

@@ -1,5 +1,6 @@
 // Loss and backward of the region-graph GNN with frozen batch-norm statistics (include/camo_rg_train.h) or with the
-// statistics of the call's own nodes (include/camo_rg_train_bn.h).
+// statistics of the call's own nodes (include/camo_rg_train_bn.h); and the structure loss on the painted mask that
+// include/camo_rg_pixel_loss.h adds to the loss.
 // Like the forward (rg_gnn.hip) the sparse part is latency- and HBM-bound gathers: one wave (GCN) or one block of `heads` waves
 // (GAT) per row of a CSR, source rows read as coalesced pieces, CPL channels per lane.  The backward of an aggregation is the same
 // gather walked over the REVERSED CSR, so every output row has one owner and no scatter is needed; every column sum over the
@@ -180,6 +181,113 @@ __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ lo
     }
     loss[0] = (float)((double)wm * term[0] + (double)wi * term[1] + (double)we * term[2]);
     loss[1] = (float)term[0]; loss[2] = (float)term[1]; loss[3] = (float)term[2];
+  }
+}
+
+// ---- structure loss on the painted mask (include/camo_rg_pixel_loss.h) ----------------------------------------
+// An image's five sums, each a double: SA, SB, I = sum p B, sum p A, sum [B sp(-z) + (A - B) sp(z)].
+struct PixSums { double sa, sb, i, pa, w; };
+struct PixNode { double A, B, p; float z; };
+
+__device__ __forceinline__ float softplus_f32(float z) { return fmaxf(z, 0.f) + logf(1.0f + expf(-fabsf(z))); }
+
+__device__ __forceinline__ PixNode pix_node(const float* __restrict__ logits, const long long* __restrict__ node_w, int v, int L) {
+  const float* l = logits + (size_t)v * L;
+  const float z = l[1] - l[0];
+  return PixNode{(double)node_w[2 * (size_t)v], (double)node_w[2 * (size_t)v + 1], (double)(1.0f / (1.0f + expf(-z))), z};
+}
+
+// the caller's share of the sums of the nodes lo .. hi - 1: lo + first, lo + first + stride, ... in that order
+__device__ __forceinline__ PixSums pix_partial(const float* __restrict__ logits, const long long* __restrict__ node_w, int lo, int hi, int first,
+                                               int stride, int L) {
+  PixSums s{0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int v = lo + first; v < hi; v += stride) {
+    const PixNode n = pix_node(logits, node_w, v, L);
+    s.sa += n.A; s.sb += n.B; s.i += n.p * n.B; s.pa += n.p * n.A;
+    s.w += n.B * (double)softplus_f32(-n.z) + (n.A - n.B) * (double)softplus_f32(n.z);
+  }
+  return s;
+}
+
+__device__ __forceinline__ PixSums pix_wave_sum(PixSums s) {
+  return PixSums{wave_sum_f64(s.sa), wave_sum_f64(s.sb), wave_sum_f64(s.i), wave_sum_f64(s.pa), wave_sum_f64(s.w)};
+}
+
+// node_off[i] clamped to [0, N]; a decreasing pair is an empty image
+__device__ __forceinline__ void pix_range(const int* __restrict__ node_off, int i, int N, int& lo, int& hi) {
+  lo = min(max(node_off[i], 0), N);
+  hi = max(min(max(node_off[i + 1], 0), N), lo);
+}
+
+// grid n_images, block 256: ONE block per image.  n_img first (every block counts the images with SA > 0 itself, a wave per image:
+// integer sums, so all blocks agree), then the image's five sums -- per-thread doubles in node order, a butterfly per wave, the 4
+// waves in order -- then per node t = w_pixel dP/dz in double, rounded once, added to dlogits[v][1] and subtracted from dlogits[v][0].
+__global__ __launch_bounds__(256) void rgt_pixel_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ node_w,
+                                                             const int* __restrict__ node_off, int n_images, int N, int L, double K,
+                                                             float w_pixel, float* __restrict__ dlogits) {
+  __shared__ int cnt_w[4];
+  __shared__ double sum_w[5][4];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  int lo, hi;
+  pix_range(node_off, blockIdx.x, N, lo, hi);
+  if (hi == lo || !(w_pixel > 0.f)) return;
+  int c = 0;
+  for (int j = wave; j < n_images; j += 4) {
+    int a, b;
+    pix_range(node_off, j, N, a, b);
+    unsigned long long s = 0;
+    for (int v = a + lane; v < b; v += 64) s += (unsigned long long)node_w[2 * (size_t)v];
+    c += (long long)wave_sum_u64(s) > 0;
+  }
+  if (lane == 0) cnt_w[wave] = c;
+  const PixSums part = pix_wave_sum(pix_partial(logits, node_w, lo, hi, tid, 256, L));
+  if (lane == 0) { sum_w[0][wave] = part.sa; sum_w[1][wave] = part.sb; sum_w[2][wave] = part.i; sum_w[3][wave] = part.pa; sum_w[4][wave] = part.w; }
+  __syncthreads();
+  double t[5];
+  for (int k = 0; k < 5; ++k) t[k] = ((sum_w[k][0] + sum_w[k][1]) + sum_w[k][2]) + sum_w[k][3];
+  const int n_img = cnt_w[0] + cnt_w[1] + cnt_w[2] + cnt_w[3];
+  const double SA = t[0], IK = t[2] + K, D = t[3] + t[1] - t[2] + K;
+  if (!(SA > 0.0) || n_img < 1) return;
+  const double scale = (double)w_pixel / (double)n_img;
+  for (int v = lo + tid; v < hi; v += 256) {
+    const PixNode n = pix_node(logits, node_w, v, L);
+    const double dz = (n.A * n.p - n.B) / SA - n.p * (1.0 - n.p) * (n.B * D - IK * (n.A - n.B)) / (D * D);
+    const float g = (float)(scale * dz);
+    float* d = dlogits + (size_t)v * L;
+    d[1] += g;
+    d[0] -= g;
+  }
+}
+
+// ONE block of 1024 threads: a wave per image (the 16 waves stride over the images), its sums by one butterfly; every wave adds
+// its images' wbce and wiou in image order, then the 16 waves in order.  loss[0] += w_pixel P, loss[4] = mean wbce, loss[5] = mean wiou.
+__global__ __launch_bounds__(1024) void rgt_pixel_finish_kernel(const float* __restrict__ logits, const long long* __restrict__ node_w,
+                                                                const int* __restrict__ node_off, int n_images, int N, int L, double K,
+                                                                float w_pixel, float* __restrict__ loss) {
+  __shared__ int cnt_w[16];
+  __shared__ double sum_w[2][16];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  int c = 0;
+  double bce = 0.0, iou = 0.0;
+  for (int j = wave; j < n_images; j += 16) {
+    int lo, hi;
+    pix_range(node_off, j, N, lo, hi);
+    const PixSums s = pix_wave_sum(pix_partial(logits, node_w, lo, hi, lane, 64, L));
+    if (s.sa > 0.0) {
+      ++c;
+      bce += s.w / s.sa;
+      iou += 1.0 - (s.i + K) / (s.pa + s.sb - s.i + K);
+    }
+  }
+  if (lane == 0) { cnt_w[wave] = c; sum_w[0][wave] = bce; sum_w[1][wave] = iou; }
+  __syncthreads();
+  if (tid == 0) {
+    int n_img = 0;
+    double b = 0.0, u = 0.0;
+    for (int v = 0; v < 16; ++v) { n_img += cnt_w[v]; b += sum_w[0][v]; u += sum_w[1][v]; }
+    if (n_img > 0) { b /= (double)n_img; u /= (double)n_img; }
+    if (w_pixel > 0.f) loss[0] = (float)((double)loss[0] + (double)w_pixel * (b + u));
+    loss[4] = (float)b; loss[5] = (float)u;
   }
 }
 
@@ -525,6 +633,16 @@ int launch_rgt_head_logits(const float* const* hp, const float* Z, float* logits
 int launch_rgt_loss(const float* logits, const int* mask_t, const int* inst_t, const float* edge_t, float wm, float wi, float we, int N,
                     int nc, float* loss, float* dlogits, hipStream_t stream) {
   hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(1024), 0, stream, logits, mask_t, inst_t, edge_t, wm, wi, we, N, nc, loss, dlogits);
+  return (int)hipGetLastError();
+}
+
+int launch_rgt_pixel_loss(const float* logits, const RgPixel& px, int N, int nc, float* loss, float* dlogits, hipStream_t stream) {
+  const int L = 2 * nc + 1, win = 2 * px.radius + 1;
+  const double K = (double)(win * win);
+  hipLaunchKernelGGL(rgt_pixel_loss_kernel, dim3((unsigned)px.n_images), dim3(256), 0, stream, logits, px.node_w, px.node_off, px.n_images, N, L,
+                     K, px.w_pixel, dlogits);
+  hipLaunchKernelGGL(rgt_pixel_finish_kernel, dim3(1), dim3(1024), 0, stream, logits, px.node_w, px.node_off, px.n_images, N, L, K, px.w_pixel,
+                     loss);
   return (int)hipGetLastError();
 }
 

@@ -10,7 +10,8 @@ runs in eval mode (``camo_rg_node_heads``, include/camo_rg_detect.h; the detecto
 gives the loss on the heads and every parameter's gradient with the batch-norm statistics frozen (``camo_rg_loss_backward``,
 include/camo_rg_train.h) or, with ``batch_stats=True``, on the statistics of the call's own nodes, the running statistics updated
 (``camo_rg_loss_backward_bn``, include/camo_rg_train_bn.h), and with ``dropout=`` under inverted dropout at the model's eight sites
-(``camo_rg_loss_backward_drop``, include/camo_rg_train_drop.h).  A training-mode logits entry is not built: ``forward`` in training
+(``camo_rg_loss_backward_drop``, include/camo_rg_train_drop.h), and with ``pixel=`` plus the structure loss on the painted mask
+(``camo_rg_loss_backward_pixel``, include/camo_rg_pixel_loss.h).  A training-mode logits entry is not built: ``forward`` in training
 mode raises.
 """
 from __future__ import annotations
@@ -366,6 +367,14 @@ class _GCNParams(nn.Module):
         nn.init.xavier_uniform_(self.lin.weight)
 
 
+def loss_figures(loss):
+    """The 0-d views of the loss a training call returns: [4], or [6] with the pixel term (include/camo_rg_pixel_loss.h)."""
+    out = {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
+    if loss.numel() == 6:
+        out.update(pixel_loss=loss[4] + loss[5], wbce=loss[4], wiou=loss[5])
+    return out
+
+
 class RegionGraphGNN(nn.Module):
     def __init__(self, in_channels=15, hidden_channels=128, num_classes=2, heads=4):
         super().__init__()
@@ -522,7 +531,7 @@ class RegionGraphGNN(nn.Module):
 
     @torch.no_grad()
     def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None,
-                               batch_stats=False, update_running=True, stats_out=None, dropout=None, seed=0):
+                               batch_stats=False, update_running=True, stats_out=None, dropout=None, seed=0, pixel=None):
         """``loss_and_gradients`` on CSR arrays the caller built: ``csr`` = (rowptr, col, w) by target, ``reversed_csr`` the same
         for the graph with every edge turned round (both from ``build_target_csr_device``; they must hold the same edges).  One
         library call (``camo_rg_loss_backward``, include/camo_rg_train.h).  Returns (loss fp32 [4] = total, mask, instance, edge;
@@ -543,8 +552,21 @@ class RegionGraphGNN(nn.Module):
         include/camo_rg_train_drop.h), in whichever batch-norm mode ``batch_stats`` selects; with ``batch_stats=True`` this is the whole
         of ``model.train()`` arithmetic.  The masks are a function of ``seed`` (a 64-bit integer), the site and the element index:
         the same seed on the same arrays gives the same bytes, so a caller that wants fresh masks passes a new seed per step.
-        ``None``, 0 or all zeros: the calls above, unchanged.  A bad rate raises ``ValueError`` before any device work."""
+        ``None``, 0 or all zeros: the calls above, unchanged.  A bad rate raises ``ValueError`` before any device work.
+
+        ``pixel``: a tuple (node_w, node_offsets, radius, weight) adds ``weight`` times the structure loss on the painted mask
+        (``camo_rg_loss_backward_pixel``, include/camo_rg_pixel_loss.h; needs ``num_classes == 2``): ``node_w`` int64 [n, 2] of
+        ``rg_finetune.pixel_loss_weights`` with ``radius``, ``node_offsets`` the first node of every image (images + 1 integers, list or
+        tensor).  In every batch-norm and dropout mode; the loss returned is then fp32 [6] = total, mask, instance, edge, mean
+        weighted BCE, mean weighted IoU.  ``None``: the calls above, byte for byte."""
         rates = self._dropout_rates(dropout)
+        if pixel is not None:
+            node_w, node_off, radius, w_pixel = pixel
+            radius, w_pixel = int(radius), C.c_float(float(w_pixel)).value
+            if not (0 <= radius <= _lib.RGPL_MAX_RADIUS):
+                raise ValueError(f"the pixel loss's radius must be in [0, {_lib.RGPL_MAX_RADIUS}], got {radius}")
+            if not (0.0 <= w_pixel < float("inf")):                              # (NaN fails the comparison)
+                raise ValueError(f"the pixel loss's weight must be finite and >= 0, got {pixel[3]!r}")
         seed = int(seed)
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed must be in [0, 2^64), got {seed}")
@@ -570,6 +592,15 @@ class RegionGraphGNN(nn.Module):
                 raise RuntimeError(f"{name} has {t.shape[0]} entries for {n} nodes")
             tg.append(t)
         wm, wi, we = (float(v) for v in loss_weights)
+        if pixel is not None:
+            _lib.require_device(node_w, "pixel node_w")
+            if node_w.dtype != torch.int64 or tuple(node_w.shape) != (n, 2):
+                raise RuntimeError(f"pixel node_w must be int64 [{n}, 2], got {node_w.dtype} {tuple(node_w.shape)}")
+            node_w = node_w.to(dev).contiguous()
+            node_off = (node_off.to(device=dev, dtype=torch.int32) if isinstance(node_off, torch.Tensor)
+                        else torch.tensor(list(node_off), dtype=torch.int32, device=dev)).reshape(-1).contiguous()
+            if node_off.numel() < 2:
+                raise RuntimeError("pixel node_offsets must hold images + 1 >= 2 integers")
         if batch_stats:
             if any(bn.eps != 1e-5 for bn in self._batch_norms()):
                 raise _lib.CamoError("batch-statistics batch norm on the MI355X path is built for eps = 1e-5 only")
@@ -599,11 +630,26 @@ class RegionGraphGNN(nn.Module):
         for p in params:
             grads.append(flat[at:at + p.numel()].view(p.shape))
             at += -(-p.numel() // 64) * 64
-        loss = torch.empty(4, dtype=torch.float32, device=dev)
+        loss = torch.empty(4 if pixel is None else 6, dtype=torch.float32, device=dev)
         tab, keep = self._param_table()
         htab, hkeep = self._head_table()
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         with torch.cuda.device(dev):
+            if pixel is not None:
+                pc, ps, ph = rates if rates is not None else (0.0, 0.0, 0.0)
+                rc = _lib.lib().camo_rg_loss_backward_pixel(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
+                                                            _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
+                                                            _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab,
+                                                            momentum if batch_stats else 0.0, rtab if batch_stats else None,
+                                                            None if stats_out is None or not batch_stats else _ptr(stats_out),
+                                                            1 if batch_stats else 0, pc, ps, ph, seed, _ptr(node_w), _ptr(node_off),
+                                                            node_off.numel() - 1, radius, w_pixel, _stream_ptr(dev))
+                _lib.check(rc, "camo_rg_loss_backward_pixel")
+                if batch_stats and update_running:
+                    for bn in self._batch_norms():
+                        if bn.num_batches_tracked is not None:
+                            bn.num_batches_tracked.add_(1)
+                return loss, grads
             if rates is not None:
                 rc = _lib.lib().camo_rg_loss_backward_drop(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
                                                            _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
@@ -636,7 +682,7 @@ class RegionGraphGNN(nn.Module):
 
     @torch.no_grad()
     def loss_and_gradients(self, data, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), accumulate=False, csr=None,
-                           batch_stats=False, update_running=True, dropout=None, seed=0):
+                           batch_stats=False, update_running=True, dropout=None, seed=0, pixel=None):
         """Loss on the three node heads and the gradient of every trainable parameter, with the BatchNorm layers on their running
         statistics and dropout off: eval-mode arithmetic (like ``node_probabilities``, whatever the module's mode) plus a backward --
         fine-tuning with frozen statistics (include/camo_rg_train.h).  ``data``: a ``RegionGraphData`` or ``RegionGraphBatch`` (the
@@ -651,7 +697,9 @@ class RegionGraphGNN(nn.Module):
         no particular order, so only calls on the same pair are sure to add in the same order and give the same bytes.
         ``batch_stats=True``: batch norm on the statistics of the call's nodes, the running statistics updated in place unless
         ``update_running`` is false (see ``loss_and_gradients_csr``); a block-diagonal batch is one population.
-        ``dropout`` / ``seed``: inverted dropout at the model's eight sites (see ``loss_and_gradients_csr``); the default is none."""
+        ``dropout`` / ``seed``: inverted dropout at the model's eight sites (see ``loss_and_gradients_csr``); the default is none.
+        ``pixel``: (node_w, node_offsets, radius, weight) adds the structure loss on the painted mask (see ``loss_and_gradients_csr``);
+        the returned dict then also carries ``pixel_loss`` (mean weighted BCE + mean weighted IoU), ``wbce`` and ``wiou``."""
         self._dropout_rates(dropout)                                             # a bad rate raises before the CSRs are built
         x, edge_index = data.x, data.edge_index
         edge_attr = getattr(data, "edge_attr", None)
@@ -663,14 +711,14 @@ class RegionGraphGNN(nn.Module):
             csr = (build_target_csr_device(n, edge_index, ew), build_target_csr_device(n, edge_index.flip(0), ew))
         csr, rcsr = csr
         loss, grads = self.loss_and_gradients_csr(x, csr, rcsr, mask_target, instance_target, edge_target, loss_weights,
-                                                  batch_stats=batch_stats, update_running=update_running, dropout=dropout, seed=seed)
+                                                  batch_stats=batch_stats, update_running=update_running, dropout=dropout, seed=seed, pixel=pixel)
         for p, g in zip(self.trainable_parameters(), grads):
             g = g.to(p.dtype)
             if accumulate and p.grad is not None:
                 p.grad.add_(g)
             else:
                 p.grad = g
-        return {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
+        return loss_figures(loss)
 
     def forward(self, data):
         """Eval mode: (mask_logits [n, c], instance_logits [n, c], edge_logits [n, 1]), views of one tensor.  Training mode raises:

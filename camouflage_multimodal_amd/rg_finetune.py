@@ -5,7 +5,8 @@ path of ``RegionGraphGNN.loss_and_gradients``): ``node_targets_from_masks`` turn
 for the three node heads (``camo_rg_node_targets``, three launches), ``prepare_finetune_batch`` builds everything a step reads from
 a batch of images once (``prepare_finetune_batch_ragged``: from uint8 images of mixed sizes, through resize.py), and ``RegionGraphFineTuner`` holds the 32 trainable parameters in one flat buffer and takes a step as one
 ``camo_rg_loss_backward`` plus the two launches of the clip + AdamW pair of optim.py (``batch_norm="batch"`` and ``dropout=`` switch the
-step to batch statistics and to dropout: include/camo_rg_train_bn.h, include/camo_rg_train_drop.h).  PARITY UNPINNED: the reference's CODDataset
+step to batch statistics and to dropout: include/camo_rg_train_bn.h, include/camo_rg_train_drop.h; ``pixel_loss=`` adds F3Net's structure
+loss on the painted mask from ``pixel_loss_weights``, two launches over the ground truth: include/camo_rg_pixel_loss.h).  PARITY UNPINNED: the reference's CODDataset
 cannot be read here, so the header's text defines the targets.  There is no CPU path: tensors that are not on a HIP device raise.
 """
 from __future__ import annotations
@@ -15,8 +16,8 @@ import torch
 from . import _lib
 from .engine import _on, _ptr, _stream_ptr
 from .optim import AdamWStateMixin
-from .region_graph import (_as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments, slic_label_bound,
-                           slic_segments)
+from .region_graph import (_as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments, loss_figures,
+                           slic_label_bound, slic_segments)
 from .pipeline import detect_camouflage_batch, detect_camouflage_ragged
 from .resize import _mask_list, _packed, _ragged, resize_batch
 from .rg_detect import _offsets_tensor
@@ -98,24 +99,77 @@ def node_targets_from_masks(segments, region_map, node_offsets, gt_masks, instan
     return mask_t, inst_t, edge_t, counts
 
 
+@torch.no_grad()
+def pixel_loss_weights(segments, region_map, node_offsets, gt_masks, radius=15, gain=5, n_nodes=None):
+    """The two integer weights per node that turn F3Net's structure loss on the painted mask into a loss on the nodes
+    (``camo_rg_pixel_weights``, include/camo_rg_pixel_loss.h, two launches): arguments as ``node_targets_from_masks`` takes them.
+    With K = (2 radius + 1)^2 and S the sum of the ground truth over the K-window around a pixel (zero padding), a pixel weighs
+    q = K + gain |S - K g|; returns int64 [n, 2] on the device = (sum q, sum q g) over every node's pixels, what
+    ``loss_and_gradients(pixel=(node_w, node_offsets, radius, weight))`` takes.  Integer sums: two calls give the same bytes."""
+    _lib.require_device(segments, "segments")
+    _lib.require_device(region_map, "region_map")
+    dev = segments.device
+    if segments.dim() == 2:
+        segments, region_map = segments.unsqueeze(0), region_map.reshape(1, -1)
+    if segments.dim() != 3 or region_map.dim() != 2 or region_map.shape[0] != segments.shape[0] or segments.numel() == 0 \
+            or region_map.numel() == 0:
+        raise ValueError(f"need segments [N, H, W] and region_map [N, label_bound]; got {tuple(segments.shape)}, {tuple(region_map.shape)}")
+    N, H, W = segments.shape
+    if n_nodes is None:
+        n_nodes = int(node_offsets[-1])
+    off = _offsets_tensor(node_offsets, dev)
+    if off.numel() != N + 1:
+        raise ValueError(f"node_offsets must hold N + 1 = {N + 1} integers, got {off.numel()}")
+    gt = _mask_bytes(gt_masks, "gt_masks", (N, H, W), dev)
+    if gt is None:
+        raise ValueError("gt_masks is required")
+    seg = segments.to(dtype=torch.int32).contiguous()
+    rmap = region_map.to(device=dev, dtype=torch.int32).contiguous()
+    n = int(n_nodes)
+    node_w = torch.empty(max(n, 0), 2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().camo_rg_pixel_weights(_ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), N, H, W, rmap.shape[1], n, int(radius), int(gain),
+                                              _ptr(node_w), _stream_ptr(dev))
+    _lib.check(rc, "camo_rg_pixel_weights")
+    return node_w
+
+
+def _pixel_options(pixel_loss):
+    """``pixel_loss`` of ``prepare_finetune_batch`` -> None, or (radius, gain)."""
+    if pixel_loss is None or pixel_loss is False:
+        return None
+    if pixel_loss is True:
+        return 15, 5
+    if not isinstance(pixel_loss, dict) or set(pixel_loss) - {"radius", "gain"}:
+        raise ValueError(f'pixel_loss must be None, True or a dict with "radius" and / or "gain", got {pixel_loss!r}')
+    return int(pixel_loss.get("radius", 15)), int(pixel_loss.get("gain", 5))
+
+
 class FineTuneBatch:
     """What a fine-tuning step reads, built once and kept on the device: ``graphs`` (RegionGraphBatch), ``segments`` int32
     [N, H, W], ``region_map`` int32 [N, label_bound], ``mask_target`` / ``instance_target`` / ``edge_target`` / ``counts`` of
-    ``node_targets_from_masks``, and ``csr`` / ``reversed_csr`` (by target, and of the graph with every edge turned round)."""
+    ``node_targets_from_masks``, and ``csr`` / ``reversed_csr`` (by target, and of the graph with every edge turned round).
+    With the pixel loss also ``pixel_weights`` (int64 [n, 2] of ``pixel_loss_weights``), ``node_offsets`` (int32 [N + 1] on the
+    device) and ``pixel_radius``; ``None`` without."""
 
-    def __init__(self, graphs, segments, region_map, mask_target, instance_target, edge_target, counts, csr, reversed_csr):
+    def __init__(self, graphs, segments, region_map, mask_target, instance_target, edge_target, counts, csr, reversed_csr,
+                 pixel_weights=None, node_offsets=None, pixel_radius=None):
         self.graphs, self.segments, self.region_map = graphs, segments, region_map
         self.mask_target, self.instance_target, self.edge_target, self.counts = mask_target, instance_target, edge_target, counts
         self.csr, self.reversed_csr = csr, reversed_csr
+        self.pixel_weights, self.node_offsets, self.pixel_radius = pixel_weights, node_offsets, pixel_radius
 
 
 @torch.no_grad()
 def prepare_finetune_batch(images, gt_masks, instance_masks=None, edge_masks=None, n_segments=500, band_permille=0, device="cuda",
-                           edge_min_pixels=1):
+                           edge_min_pixels=1, pixel_loss=None):
     """``images`` [N, H, W, 3] float in [0, 1] and their ground-truth masks [N, H, W] -> ``FineTuneBatch``: superpixels, edge maps
     and region graphs on the device (region_graph.py), the node targets, and both CSRs built once with ``build_target_csr_device``,
     so that a resident dataset is trained on epoch after epoch through the ``csr=`` path of ``loss_and_gradients`` with nothing
-    rebuilt.  The only host synchronisation is the sizes read-back of ``create_region_graphs_from_segments``."""
+    rebuilt.  The only host synchronisation is the sizes read-back of ``create_region_graphs_from_segments``.
+    ``pixel_loss``: ``True`` or ``{"radius": .., "gain": ..}`` (15 and 5 when left out) also stores ``pixel_loss_weights`` of the
+    masks, which a ``RegionGraphFineTuner`` with ``pixel_loss > 0`` needs."""
+    pixel = _pixel_options(pixel_loss)
     img, _ = _image_batch(_as_tensor(images, device))
     _lib.require_device(img, "images")
     N, H, W = img.shape[:3]
@@ -129,14 +183,18 @@ def prepare_finetune_batch(images, gt_masks, instance_masks=None, edge_masks=Non
     n, ew = graphs.x.shape[0], graphs.edge_attr.reshape(-1)
     csr = build_target_csr_device(n, graphs.edge_index, ew)
     rcsr = build_target_csr_device(n, graphs.edge_index.flip(0), ew)
-    return FineTuneBatch(graphs, segments, region_map, mask_t, inst_t, edge_t, counts, csr, rcsr)
+    if pixel is None:
+        return FineTuneBatch(graphs, segments, region_map, mask_t, inst_t, edge_t, counts, csr, rcsr)
+    node_w = pixel_loss_weights(segments, region_map, graphs.node_offsets, gt, pixel[0], pixel[1], n_nodes=n)
+    return FineTuneBatch(graphs, segments, region_map, mask_t, inst_t, edge_t, counts, csr, rcsr, node_w,
+                         _offsets_tensor(graphs.node_offsets, img.device), pixel[0])
 
 
 @torch.no_grad()
 def prepare_finetune_batch_ragged(images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, **kw):
     """``prepare_finetune_batch`` for uint8 images and masks of mixed sizes: the images are resized to ``size`` bilinear, every mask
     nearest, all with the same ``crops`` and ``flips`` (``random_resized_crops`` draws them), and the result goes to
-    ``prepare_finetune_batch`` with ``**kw`` (n_segments, band_permille, device, edge_min_pixels)."""
+    ``prepare_finetune_batch`` with ``**kw`` (n_segments, band_permille, device, edge_min_pixels, pixel_loss)."""
     device = kw.get("device", "cuda")
     data, geo, C, _ = _ragged(images, device)
     if C != 3:
@@ -170,12 +228,22 @@ class RegionGraphFineTuner(AdamWStateMixin):
     ``dropout`` (a float or a (p_conv, p_shared, p_head) triple; ``None``, the default, is none) makes a step
     ``camo_rg_loss_backward_drop`` (include/camo_rg_train_drop.h) in the chosen batch-norm mode; the step that follows ``step_count``
     finished steps draws its masks from seed ``seed + step_count`` -- a host counter, no synchronisation -- and ``step_count`` is what
-    ``state_dict`` / ``load_state_dict`` already carry, so a resumed run continues the mask sequence."""
+    ``state_dict`` / ``load_state_dict`` already carry, so a resumed run continues the mask sequence.
+    ``pixel_loss`` (a weight, 0.0 = off and no launch more) adds that many times F3Net's structure loss on the painted mask to the
+    loss of every step (``camo_rg_loss_backward_pixel``, include/camo_rg_pixel_loss.h) in whichever mode the other arguments choose;
+    ``step`` then needs a batch prepared with ``pixel_loss=``, which ``step_from_images`` and ``step_from_ragged`` do with
+    ``pixel_radius`` and ``pixel_gain``.  ``loss_weights=(0, 1, 1)`` beside it trains the mask head on pixels alone."""
 
     def __init__(self, rg_model, lr=1e-4, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, loss_weights=(1.0, 1.0, 1.0),
-                 batch_norm="frozen", dropout=None, seed=0):
+                 batch_norm="frozen", dropout=None, seed=0, pixel_loss=0.0, pixel_radius=15, pixel_gain=5):
         if batch_norm not in ("frozen", "batch"):
             raise ValueError(f'batch_norm must be "frozen" or "batch", got {batch_norm!r}')
+        self.pixel_loss, self.pixel_radius, self.pixel_gain = float(pixel_loss), int(pixel_radius), int(pixel_gain)
+        if not (0.0 <= self.pixel_loss < float("inf")):
+            raise ValueError(f"pixel_loss must be finite and >= 0, got {pixel_loss!r}")
+        if not (0 <= self.pixel_radius <= _lib.RGPL_MAX_RADIUS and 0 <= self.pixel_gain <= _lib.RGPL_MAX_GAIN):
+            raise ValueError(f"pixel_radius must be in [0, {_lib.RGPL_MAX_RADIUS}] and pixel_gain in [0, {_lib.RGPL_MAX_GAIN}], got "
+                             f"{pixel_radius!r}, {pixel_gain!r}")
         self.batch_norm = batch_norm
         rg_model._dropout_rates(dropout)                            # a bad rate raises here, not at the first step
         self.dropout, self.seed = dropout, int(seed)
@@ -221,13 +289,20 @@ class RegionGraphFineTuner(AdamWStateMixin):
     @torch.no_grad()
     def step(self, batch):
         """One clip + AdamW step on a ``FineTuneBatch``.  Returns 0-d device tensors ``loss``, ``mask_loss``, ``instance_loss``,
-        ``edge_loss`` of the parameters BEFORE the update.  No host synchronisation; the gradient buffer is the tuner's own."""
+        ``edge_loss`` of the parameters BEFORE the update -- with ``pixel_loss > 0`` also ``pixel_loss``, ``wbce`` and ``wiou``.  No
+        host synchronisation; the gradient buffer is the tuner's own."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         self._check_resident()
+        pixel = None
+        if self.pixel_loss > 0.0:
+            if getattr(batch, "pixel_weights", None) is None or batch.node_offsets is None or batch.pixel_radius is None:
+                raise ValueError("pixel_loss > 0 needs a batch that carries pixel_weights, node_offsets and pixel_radius: prepare it with "
+                                 "prepare_finetune_batch(..., pixel_loss=True)")
+            pixel = (batch.pixel_weights, batch.node_offsets, batch.pixel_radius, self.pixel_loss)
         loss, _ = self.model.loss_and_gradients_csr(batch.graphs.x, batch.csr, batch.reversed_csr, batch.mask_target, batch.instance_target,
                                                     batch.edge_target, self.loss_weights, out=self.flat_grads,
                                                     batch_stats=self.batch_norm == "batch", dropout=self.dropout,
-                                                    seed=(self.seed + self.step_count) & 0xFFFFFFFFFFFFFFFF)
+                                                    seed=(self.seed + self.step_count) & 0xFFFFFFFFFFFFFFFF, pixel=pixel)
         p, g, (m, v, ss) = self.flat_params, self.flat_grads, self._state()
         self.step_count += 1
         L = _lib.lib()
@@ -236,13 +311,16 @@ class RegionGraphFineTuner(AdamWStateMixin):
             _lib.check(L.camo_grad_sumsq(_ptr(g), g.numel(), _ptr(ss), st), "camo_grad_sumsq")
             _lib.check(L.camo_clip_adamw(_ptr(p), _ptr(g), _ptr(m), _ptr(v), g.numel(), _ptr(ss), self.max_norm, self.lr, self.betas[0],
                                          self.betas[1], self.eps, self.weight_decay, self.step_count, 0, st), "camo_clip_adamw")
-        return {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
+        return loss_figures(loss)
+
+    def _pixel_options(self):
+        return {"radius": self.pixel_radius, "gain": self.pixel_gain} if self.pixel_loss > 0.0 else None
 
     def step_from_images(self, images, gt_masks, instance_masks=None, edge_masks=None, n_segments=500, band_permille=0, edge_min_pixels=1):
-        """``prepare_finetune_batch`` on the tuner's device, then ``step``."""
+        """``prepare_finetune_batch`` on the tuner's device (with the pixel weights when ``pixel_loss > 0``), then ``step``."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         return self.step(prepare_finetune_batch(images, gt_masks, instance_masks, edge_masks, n_segments, band_permille,
-                                                self.flat_params.device, edge_min_pixels))
+                                                self.flat_params.device, edge_min_pixels, self._pixel_options()))
 
     @staticmethod
     def _evaluation(out, cod_metrics, instances, match, native=False, boundary=None):
@@ -281,7 +359,7 @@ class RegionGraphFineTuner(AdamWStateMixin):
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
         return self.step(prepare_finetune_batch_ragged(images, gt_masks, instance_masks, edge_masks, size, crops, flips, n_segments=n_segments,
                                                        band_permille=band_permille, device=self.flat_params.device,
-                                                       edge_min_pixels=edge_min_pixels))
+                                                       edge_min_pixels=edge_min_pixels, pixel_loss=self._pixel_options()))
 
     def evaluate_ragged(self, images, gt_masks, size=(256, 256), n_segments=500, threshold=0.5, cod_metrics=False, evaluate_at="native",
                         instances=False, match=None, min_area=0, fill_holes=False, connectivity=8, *, boundary=None):
