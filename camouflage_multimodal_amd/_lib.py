@@ -63,6 +63,10 @@ SPLIT_MAX_SPLIT = 8                 # CAMO_SPLIT_MAX_SPLIT
 SPLIT_MAX_DEN = 16                  # CAMO_SPLIT_MAX_DEN
 SPLIT_COUNTS = 4                    # CAMO_SPLIT_COUNTS
 SPLIT_LAUNCHES = 13                 # CAMO_SPLIT_LAUNCHES
+SPLIT_GEO_TILE = 32                 # CAMO_SPLIT_GEO_TILE
+SPLIT_GEO_MAX_ROUNDS = 1024         # CAMO_SPLIT_GEO_MAX_ROUNDS
+SPLIT_GEO_LAUNCHES = 13             # CAMO_SPLIT_GEO_LAUNCHES (plus the rounds)
+SPLIT_GEO_RESUME_LAUNCHES = 2       # CAMO_SPLIT_GEO_RESUME_LAUNCHES (plus the rounds)
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -238,6 +242,11 @@ PROTOTYPES = {
     "camo_split.h": (
         ("camo_split_workspace_bytes", sz, (i32, i32, i32, i32)),
         ("camo_split_instances", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp)),
+    ),
+    "camo_split_geo.h": (
+        ("camo_split_geodesic_workspace_bytes", sz, (i32, i32, i32, i32)),
+        ("camo_split_instances_geodesic", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
+        ("camo_split_geodesic_resume", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
     ),
 }
 

@@ -1,5 +1,5 @@
 // C ABI of the image pipeline around the detector (include/camo_instances.h, camo_inst_match.h, camo_boundary.h, camo_guided.h,
-// camo_rle.h, camo_poly.h, camo_split.h): argument checks, workspace carving and the launchers' calls.  No device code here.
+// camo_rle.h, camo_poly.h, camo_split.h, camo_split_geo.h): argument checks, workspace carving and the launchers' calls.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +20,7 @@
 #include "../../include/camo_rle.h"
 #include "../../include/camo_poly.h"
 #include "../../include/camo_split.h"
+#include "../../include/camo_split_geo.h"
 
 using namespace camo_abi;
 
@@ -165,9 +166,10 @@ size_t camo_split_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t max_s
   return split_carve(N, H, W, max_split, nullptr).bytes;
 }
 
-int camo_split_instances(const int32_t* labels, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W, int32_t ratio_num,
-                         int32_t ratio_den, int32_t min_core, int32_t max_split, int32_t max_instances, int32_t* out_labels, int64_t* table,
-                         int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+// What the three calls check before the workspace, in this order.
+static int split_args(const int32_t* labels, const float* pred, int64_t pred_image_stride, int N, int H, int W, int ratio_num, int ratio_den,
+                      int min_core, int max_split, int max_instances, const int32_t* out_labels, const int64_t* table, const int32_t* counts,
+                      const void* ws) {
   if (int e = split_check(N, H, W, max_split)) return e;
   if (ratio_den < 2 || ratio_den > CAMO_SPLIT_MAX_DEN) return fail(CAMO_E_ARG, "ratio_den must be in [2, CAMO_SPLIT_MAX_DEN]");
   if (ratio_num < 1 || ratio_num >= ratio_den) return fail(CAMO_E_ARG, "ratio_num must be in [1, ratio_den)");
@@ -180,10 +182,60 @@ int camo_split_instances(const int32_t* labels, const float* pred, int64_t pred_
   if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
   const uintptr_t a = reinterpret_cast<uintptr_t>(labels), b = reinterpret_cast<uintptr_t>(out_labels), bytes = (uintptr_t)N * H * W * 4;
   if (a < b + bytes && b < a + bytes) return fail(CAMO_E_ARG, "labels and out_labels must not overlap");
+  return 0;
+}
+
+int camo_split_instances(const int32_t* labels, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W, int32_t ratio_num,
+                         int32_t ratio_den, int32_t min_core, int32_t max_split, int32_t max_instances, int32_t* out_labels, int64_t* table,
+                         int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = split_args(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, out_labels, table, counts, ws))
+    return e;
   const SplitWs w = split_carve(N, H, W, max_split, ws);
   if (int e = ws_check(ws, ws_bytes, w.bytes, "camo_split_workspace_bytes")) return e;
   CK(launch_split(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, w, out_labels,
                   reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "split instances");
+  return 0;
+}
+
+// ---- Geodesic growth for the splitter: connected parts from cores (include/camo_split_geo.h) -----------------------
+size_t camo_split_geodesic_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t max_split) {
+  if (split_check(N, H, W, max_split)) return 0;
+  return split_geo_carve(N, H, W, max_split, nullptr).bytes;
+}
+
+static int split_geo_args(const int32_t* labels, const float* pred, int64_t pred_image_stride, int N, int H, int W, int ratio_num, int ratio_den,
+                          int min_core, int max_split, int max_instances, const int32_t* out_labels, const int64_t* table, const int32_t* counts,
+                          void* ws, size_t ws_bytes, int rounds, const int32_t* pending, SplitGeoWs* w) {
+  if (int e = split_args(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, out_labels, table, counts, ws))
+    return e;
+  if (rounds < 1 || rounds > CAMO_SPLIT_GEO_MAX_ROUNDS) return fail(CAMO_E_ARG, "rounds must be in [1, CAMO_SPLIT_GEO_MAX_ROUNDS]");
+  if (!pending) return fail(CAMO_E_ARG, "pending is null");
+  *w = split_geo_carve(N, H, W, max_split, ws);
+  return ws_check(ws, ws_bytes, w->bytes, "camo_split_geodesic_workspace_bytes");
+}
+
+int camo_split_instances_geodesic(const int32_t* labels, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W,
+                                  int32_t ratio_num, int32_t ratio_den, int32_t min_core, int32_t max_split, int32_t max_instances,
+                                  int32_t* out_labels, int64_t* table, int32_t* counts, void* ws, size_t ws_bytes, void* stream, int32_t rounds,
+                                  int32_t* pending) {
+  SplitGeoWs w;
+  if (int e = split_geo_args(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, out_labels, table, counts,
+                             ws, ws_bytes, rounds, pending, &w))
+    return e;
+  CK(launch_split_geo(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, rounds, w, out_labels,
+                      reinterpret_cast<long long*>(table), counts, pending, static_cast<hipStream_t>(stream)), "split instances, geodesic");
+  return 0;
+}
+
+int camo_split_geodesic_resume(const int32_t* labels, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W, int32_t ratio_num,
+                               int32_t ratio_den, int32_t min_core, int32_t max_split, int32_t max_instances, int32_t* out_labels, int64_t* table,
+                               int32_t* counts, void* ws, size_t ws_bytes, void* stream, int32_t rounds, int32_t* pending) {
+  SplitGeoWs w;
+  if (int e = split_geo_args(labels, pred, pred_image_stride, N, H, W, ratio_num, ratio_den, min_core, max_split, max_instances, out_labels, table, counts,
+                             ws, ws_bytes, rounds, pending, &w))
+    return e;
+  CK(launch_split_geo_resume(labels, pred, pred_image_stride, N, H, W, max_instances, rounds, w, out_labels, reinterpret_cast<long long*>(table), counts,
+                             pending, static_cast<hipStream_t>(stream)), "split instances, geodesic resume");
   return 0;
 }
 

@@ -1,5 +1,5 @@
-// Instance splitter (split.hip, include/camo_split.h): the constants the kernels, the launcher and the entry points
-// share.  The launcher returns hipError_t as int.
+// Instance splitter (split.hip, split_geo.hip, split_inl.h; include/camo_split.h, include/camo_split_geo.h): the
+// constants the kernels, the launchers and the entry points share.  The launchers return hipError_t as int.
 #pragma once
 #include "common.h"
 
@@ -13,7 +13,8 @@ struct SplitWs {
   int* par;                // [N][H][W] union-find parent of the core pixels (index into the whole batch), -1 elsewhere
   int* area;               // [N][H][W] area[root] = pixels of the root's core
   int* rid;                // [N][H][W] rid[root] = the new id of a kept core of a split id
-  short* site;             // [N][max_split][H][W] the nearest site row of the slot's id in the pixel's column, -1: none
+  short* site;             // [N][max_split][H][W] the nearest site row of the slot's id in the pixel's column, -1: none (null for the
+                           // geodesic call, which has no sites)
   int* chunk;              // [N][max_split][chunks] per chunk the slot's kept cores, then their exclusive prefix
   int* m2;                 // [N][SPLIT_IDS_PAD] M2(id) + 2, 0: the id has no pixel
   int* ncore;              // [N][SPLIT_IDS_PAD] the id's kept cores
@@ -24,7 +25,25 @@ struct SplitWs {
   int* dropped;            // [N] cores dropped as small
   size_t bytes;
 };
-SplitWs split_carve(int N, int H, int W, int max_split, void* base);
+SplitWs split_carve(int N, int H, int W, int max_split, void* base, bool sites = true);
 
 int launch_split(const int* labels, const float* pred, long long stride, int N, int H, int W, int num, int den, int min_core, int max_split,
                  int max_instances, const SplitWs& ws, int* out, long long* table, int* counts, hipStream_t stream);
+
+// ---- geodesic growth (split_geo.hip, include/camo_split_geo.h) ----------------------------------------------------
+constexpr int SPLIT_GEO_TILE = 32;         // CAMO_SPLIT_GEO_TILE: a grow block's tile, INST_TILE
+constexpr int SPLIT_GEO_SWEEPS = 128;      // Jacobi sweeps of one tile in one launch: 4 tile sides.  A tile still changing then flags itself
+
+struct SplitGeoWs {
+  SplitWs s;                 // the common launches' arrays, site null
+  unsigned long long* key;   // [N][H][W] 0 off the split ids, else (g << 32) | (new id << 4) | (slot + 1); g = SPLIT_GEO_FAR + ...: not reached
+  int* flag[2];              // [N][tiles] each: the tiles to grow in the rounds of even / odd number
+  size_t bytes;
+};
+SplitGeoWs split_geo_carve(int N, int H, int W, int max_split, void* base);
+
+// init, `rounds` grow launches, finish, table after the ten common launches; the resume: the grow launches, finish, table
+int launch_split_geo(const int* labels, const float* pred, long long stride, int N, int H, int W, int num, int den, int min_core, int max_split,
+                     int max_instances, int rounds, const SplitGeoWs& ws, int* out, long long* table, int* counts, int* pending, hipStream_t stream);
+int launch_split_geo_resume(const int* labels, const float* pred, long long stride, int N, int H, int W, int max_instances, int rounds,
+                            const SplitGeoWs& ws, int* out, long long* table, const int* counts, int* pending, hipStream_t stream);

@@ -180,7 +180,8 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     "boundary_iou" (per image ``boundary.boundary_iou`` of "mask" against the ground-truth mask) and, with ``refine``,
     "refined_boundary_iou" (of "mask_refined": what the guided filter did to the contour).  Every other key keeps its bytes.
     ``split`` -- ``False`` (off: no launch more than before), ``True`` or a dict with any of "ratio" ((7, 10)), "min_core" (0),
-    "max_split" (4), "max_instances" (64) -- needs ``instances=True``; it splits the touching objects of "instance_labels" at their
+    "max_split" (4), "max_instances" (64), "growth" ("euclidean"; "geodesic": connected parts, include/camo_split_geo.h, at the
+    cost of one host synchronisation) and "rounds" -- needs ``instances=True``; it splits the touching objects of "instance_labels" at their
     necks (``split.split_detected``, include/camo_split.h) and adds "split_instances" (per image the records of
     ``split.split_records``, scored by the mask probability), "split_labels" int32 [N, H, W] and "split_counts" int32 [N, 4].
     ``match``, ``boundary`` and ``rle`` then work on the split labels and table, so instance AP and Boundary AP measure the split;

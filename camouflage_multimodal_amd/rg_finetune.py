@@ -323,11 +323,13 @@ class RegionGraphFineTuner(AdamWStateMixin):
                                                 self.flat_params.device, edge_min_pixels, self._pixel_options()))
 
     @staticmethod
-    def _evaluation(out, cod_metrics, instances, match, native=False, boundary=None):
+    def _evaluation(out, cod_metrics, instances, match, native=False, boundary=None, split=None):
         match = None if match is False else match
         if not (instances or match is not None):
             return {"metrics": out["metrics"], "cod_metrics": out["cod_metrics"]} if cod_metrics else out["metrics"]
         res = {"metrics": out["metrics"], "instances": out["instances_native" if native else "instances"]}
+        if split is not None and split is not False:
+            res["split_instances"] = out["split_instances_native" if native else "split_instances"]
         if cod_metrics:
             res["cod_metrics"] = out["cod_metrics"]
         if match is not None:
@@ -339,18 +341,22 @@ class RegionGraphFineTuner(AdamWStateMixin):
         return res
 
     def evaluate(self, images, gt_masks, n_segments=500, threshold=0.5, cod_metrics=False, instances=False, match=None, min_area=0,
-                 fill_holes=False, connectivity=8, *, boundary=None):
+                 fill_holes=False, connectivity=8, *, boundary=None, split=None):
         """``detect_camouflage_batch``'s metrics of the model as it is now: a list of ``segmentation_metrics`` dicts, one per image.
         With ``cod_metrics=True`` a dict instead: that list under "metrics" and, under "cod_metrics", the list of the benchmark
         measures (S-alpha, E-phi, F-beta, MAE on the 8-bit map, ``wf``) of ``seg_measures.cod_metrics``.  With ``instances=True``
         (``detect_camouflage_batch``'s, with ``min_area``, ``fill_holes``, ``connectivity``) a dict that also carries "instances"
         and, with ``match`` (``True`` or ``detect_camouflage_batch``'s dict), "instance_match": the records of the instances
         matched to the ground-truth ones; with ``boundary`` (``detect_camouflage_batch``'s; needs ``match``) also "boundary_match",
-        the records under min(mask IoU, boundary IoU), and "boundary_iou" of the thresholded masks."""
+        the records under min(mask IoU, boundary IoU), and "boundary_iou" of the thresholded masks.  With ``split``
+        (``detect_camouflage_batch``'s: ``True`` or a dict, ``{"growth": "geodesic"}`` for connected parts; needs ``instances=True``)
+        also "split_instances", the records of the instances split at their necks, and "instance_match" and "boundary_match" are
+        then those of the split instances, as in the pipeline.  ``split=None``: nothing changes."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        split = False if split is None else split
         out = detect_camouflage_batch(self.model, images, gt_masks, n_segments, threshold, self.flat_params.device, cod_metrics, instances, min_area,
-                                      fill_holes, connectivity, match=match, boundary=boundary)
-        return self._evaluation(out, cod_metrics, instances, match, boundary=boundary)
+                                      fill_holes, connectivity, match=match, boundary=boundary, split=split)
+        return self._evaluation(out, cod_metrics, instances, match, boundary=boundary, split=split)
 
     def step_from_ragged(self, images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, n_segments=500,
                          band_permille=0, edge_min_pixels=1):
@@ -362,11 +368,13 @@ class RegionGraphFineTuner(AdamWStateMixin):
                                                        edge_min_pixels=edge_min_pixels, pixel_loss=self._pixel_options()))
 
     def evaluate_ragged(self, images, gt_masks, size=(256, 256), n_segments=500, threshold=0.5, cod_metrics=False, evaluate_at="native",
-                        instances=False, match=None, min_area=0, fill_holes=False, connectivity=8, *, boundary=None):
+                        instances=False, match=None, min_area=0, fill_holes=False, connectivity=8, *, boundary=None, split=None):
         """``evaluate`` for uint8 images and masks of mixed sizes (``detect_camouflage_ragged`` of pipeline.py): the metrics are taken
         against every mask at its own size, or at ``size`` with ``evaluate_at="resized"``.  Same return as ``evaluate``; the
-        instances and their matches -- ``boundary``'s too -- are those of the native-size maps."""
+        instances and their matches -- ``boundary``'s too -- are those of the native-size maps, and with ``split`` (``evaluate``'s)
+        "split_instances" holds the native-size records ("split_instances_native" of the pipeline)."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
+        split = False if split is None else split
         out = detect_camouflage_ragged(self.model, images, gt_masks, size, n_segments, threshold, self.flat_params.device, cod_metrics, evaluate_at,
-                                       instances, min_area, fill_holes, connectivity, match=match, boundary=boundary)
-        return self._evaluation(out, cod_metrics, instances, match, native=True, boundary=boundary)
+                                       instances, min_area, fill_holes, connectivity, match=match, boundary=boundary, split=split)
+        return self._evaluation(out, cod_metrics, instances, match, native=True, boundary=boundary, split=split)

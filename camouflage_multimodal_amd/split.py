@@ -6,7 +6,8 @@ instance.  ``split_instances`` runs ``camo_split_instances`` on a label map -- t
 cores above ``ratio`` of each id's largest distance, every pixel of an id with two cores or more to the core of its own id with the
 nearest core pixel -- and returns device tensors; ``split_records`` takes the ratios from the integers on the host;
 ``split_detected`` is the two together with a table that always holds every instance, for the pipeline; ``split_options`` is the
-pipeline's ``split`` keyword.
+pipeline's ``split`` keyword.  With ``growth="geodesic"`` (include/camo_split_geo.h) the last step measures the distance
+along paths INSIDE the id, so every part is one connected piece -- what a coiled or curled animal needs.
 PARITY UNPINNED: the header's text is the definition (restated in numpy in tests/split_ref.py).  There is no CPU path: tensors
 that are not on a HIP device raise.
 """
@@ -22,6 +23,7 @@ from .instances import instance_records
 
 RATIO = (7, 10)
 OPTIONS = {"ratio": RATIO, "min_core": 0, "max_split": 4, "max_instances": 64}
+GROWTHS = ("euclidean", "geodesic")
 
 
 def _integer(v):
@@ -44,6 +46,16 @@ def check_arguments(ratio=RATIO, min_core=0, max_split=4, max_instances=64, n_im
     return int(ratio[0]), int(ratio[1])
 
 
+def check_growth(growth="euclidean", rounds=None):
+    """The ``ValueError`` of a bad ``growth`` or ``rounds``, by name."""
+    if growth not in GROWTHS:
+        raise ValueError(f'growth must be "euclidean" or "geodesic", got {growth!r}')
+    if rounds is not None and (not _integer(rounds) or not 1 <= rounds <= _lib.SPLIT_GEO_MAX_ROUNDS):
+        raise ValueError(f"rounds must be None or an integer in [1, {_lib.SPLIT_GEO_MAX_ROUNDS}], got {rounds!r}")
+    if rounds is not None and growth != "geodesic":
+        raise ValueError(f'rounds belongs to growth="geodesic", got growth={growth!r}')
+
+
 def _label_map(t, name):
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name} must be a tensor")
@@ -57,14 +69,21 @@ def _label_map(t, name):
 
 
 @torch.no_grad()
-def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max_instances=64):
+def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max_instances=64, growth="euclidean", rounds=None):
     """``camo_split_instances``: ``labels`` int32 [N, H, W] (or [H, W]), 0 on background and an id in 1 .. 1024 per component
     (``mask_instances``' "labels"); ``pred``: ``None``, or the fp32 [N, H, W] probability the labels came from (one channel of a
     [N, C, H, W] map is read in place), for the table's Sq -> {"labels": int32 [N, H, W], the new ids 1 .. K' in input-id order, the
     parts of one id in the reading order of their cores' first pixels; "table": int64 [N, max_instances, 8] = ``mask_instances``'
     row of every new id (Sq 0 without ``pred``); "counts": int32 [N, 4] = (K', ids split, cores dropped as smaller than ``min_core``,
     qualifying ids left whole because ``max_split`` were split before them)}, all on the device, no host synchronisation.  A pixel
-    is a core pixel when its squared distance to the background exceeds (num / den)^2 of its id's largest, ``ratio`` = (num, den)."""
+    is a core pixel when its squared distance to the background exceeds (num / den)^2 of its id's largest, ``ratio`` = (num, den).
+
+    ``growth="geodesic"`` runs ``camo_split_instances_geodesic`` instead: a pixel goes to the core that the cheapest 8-neighbour path
+    inside its id reaches (5 a straight step, 7 a diagonal one, a tie to the core first in reading order), so every part is connected
+    and contains its core.  The growth runs in rounds of one launch each; ``rounds`` (default: tiles_x + tiles_y of 32 x 32 tiles,
+    enough for every path that is monotone in both axes) are enqueued, then "pending" is read -- ONE HOST SYNCHRONISATION, which the
+    Euclidean path does not have -- and ``camo_split_geodesic_resume`` runs twice the rounds again until no image has a tile left
+    to grow, so the result is the header's definition for any content.  The dict then also holds "rounds": the rounds run in all."""
     labels = _label_map(labels, "labels")
     N, H, W = labels.shape
     if pred is not None:
@@ -75,6 +94,7 @@ def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max
         if tuple(pred.shape) != (N, H, W):
             raise ValueError(f"need pred of labels' shape {(N, H, W)}, got {tuple(pred.shape)}")
     num, den = check_arguments(ratio, min_core, max_split, max_instances, N)
+    check_growth(growth, rounds)
     _lib.require_device(labels, "labels")
     labels = labels.detach().contiguous()
     stride = 0
@@ -86,18 +106,33 @@ def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max
         stride = pred.stride(0) if N > 1 else H * W
     dev = labels.device
     L = _lib.lib()
-    nbytes = L.camo_split_workspace_bytes(N, H, W, int(max_split))
+    geodesic = growth == "geodesic"
+    nbytes = (L.camo_split_geodesic_workspace_bytes if geodesic else L.camo_split_workspace_bytes)(N, H, W, int(max_split))
     if nbytes == 0:
         raise ValueError(f"camo_split_instances does not support N = {N}, H = {H}, W = {W} (a side is at most {_lib.SEG_WF_MAX_SIDE})")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty_like(labels)
     table = torch.empty(N, int(max_instances), _lib.INST_FIELDS, dtype=torch.int64, device=dev)
     counts = torch.empty(N, _lib.SPLIT_COUNTS, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_split_instances(_ptr(labels), None if pred is None else _ptr(pred), stride, N, H, W, num, den, int(min_core), int(max_split),
-                                    int(max_instances), _ptr(out), _ptr(table), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_split_instances")
-    return {"labels": out, "table": table, "counts": counts}
+    args = (_ptr(labels), None if pred is None else _ptr(pred), stride, N, H, W, num, den, int(min_core), int(max_split), int(max_instances), _ptr(out),
+            _ptr(table), _ptr(counts), _ptr(ws), nbytes)
+    if not geodesic:
+        with torch.cuda.device(dev):
+            rc = L.camo_split_instances(*args, _stream_ptr(dev))
+        _lib.check(rc, "camo_split_instances")
+        return {"labels": out, "table": table, "counts": counts}
+    T = _lib.SPLIT_GEO_TILE
+    step = int(rounds) if rounds is not None else min(-(-H // T) + -(-W // T), _lib.SPLIT_GEO_MAX_ROUNDS)
+    pending = torch.empty(N, dtype=torch.int32, device=dev)
+    call, name, total = L.camo_split_instances_geodesic, "camo_split_instances_geodesic", 0
+    while True:
+        with torch.cuda.device(dev):
+            rc = call(*args, _stream_ptr(dev), step, _ptr(pending))
+        _lib.check(rc, name)
+        total += step
+        if not any(pending.tolist()):                              # (the host synchronisation)
+            return {"labels": out, "table": table, "counts": counts, "rounds": total}
+        call, name, step = L.camo_split_geodesic_resume, "camo_split_geodesic_resume", min(2 * step, _lib.SPLIT_GEO_MAX_ROUNDS)
 
 
 def split_records(table, counts, H, W):
@@ -120,18 +155,22 @@ def split_records(table, counts, H, W):
 
 def split_options(split, instances=True):
     """The pipeline's ``split`` keyword -- ``None`` or ``False`` (off), ``True`` or a dict with any of "ratio" ((7, 10)), "min_core"
-    (0), "max_split" (4) and "max_instances" (64) -- as a dict with all four, or ``None``; the ``ValueError`` of a bad one by name,
-    before anything touches the device.  ``instances``: the pipeline's keyword -- the instances are what it splits."""
+    (0), "max_split" (4), "max_instances" (64), "growth" ("euclidean"; "geodesic": connected parts) and "rounds" (``None``;
+    ``split_instances``') -- as a dict with the first four, and "growth" and "rounds" where the caller gave them, or ``None``; the
+    ``ValueError`` of a bad one by name, before anything touches the device.  ``instances``: the pipeline's keyword -- the
+    instances are what it splits."""
     if split is None or split is False:
         return None
     if split is True:
         split = {}
-    if not isinstance(split, dict) or set(split) - set(OPTIONS):
-        raise ValueError(f'split must be None, False, True or a dict with any of "ratio", "min_core", "max_split", "max_instances", got {split!r}')
+    if not isinstance(split, dict) or set(split) - set(OPTIONS) - {"growth", "rounds"}:
+        raise ValueError('split must be None, False, True or a dict with any of "ratio", "min_core", "max_split", "max_instances", "growth", "rounds", '
+                         f"got {split!r}")
     if not instances:
         raise ValueError("split needs instances=True: the instances are what it splits")
     opts = {**OPTIONS, **split}
-    opts["ratio"] = check_arguments(**opts)
+    opts["ratio"] = check_arguments(**{k: opts[k] for k in OPTIONS})
+    check_growth(opts.get("growth", "euclidean"), opts.get("rounds"))
     return opts
 
 
@@ -141,11 +180,12 @@ def split_detected(labels, pred, opts):
     (``split_records``' list).  ``opts``: ``split_options``' dict.  When an image holds more than "max_instances" parts the call is
     made once more with the table sized to the largest count, so no list is truncated."""
     args = (opts["ratio"], opts["min_core"], opts["max_split"])
-    out = split_instances(labels, pred, *args, opts["max_instances"])
+    growth = {k: opts[k] for k in ("growth", "rounds") if k in opts}
+    out = split_instances(labels, pred, *args, opts["max_instances"], **growth)
     H, W = out["labels"].shape[1:]
     rec = split_records(out["table"], out["counts"], H, W)
     if any(r["truncated"] for r in rec):
-        out = split_instances(labels, pred, *args, max(r["count"] for r in rec))
+        out = split_instances(labels, pred, *args, max(r["count"] for r in rec), **growth)
         rec = split_records(out["table"], out["counts"], H, W)
     out["instances"] = rec
     return out

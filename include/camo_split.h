@@ -12,9 +12,9 @@
  * package, so their conventions are not pinned.  The text below is the definition; it is restated sequentially in numpy, with a
  * brute-force distance transform and a brute-force nearest site, in tests/split_ref.py, which the kernels are tested against byte for
  * byte.
- * Not built: geodesic (connected-cell) growth -- a cell is a Euclidean Voronoi cell of its core cut to the component, and in a concave
- * component it may come out in several pieces --, h-maxima marker merging, a per-component absolute radius, and
- * RegionGraphFineTuner.evaluate on the split instances.
+ * A cell is a Euclidean Voronoi cell of its core cut to the component, and in a concave component it may come out in several pieces:
+ * include/camo_split_geo.h grows connected cells along paths inside the component instead.
+ * Not built: h-maxima marker merging and a per-component absolute radius.
  *
  * Device pointers only, enqueue-only on `stream` (no allocation, no synchronisation), 0 = ok / CAMO_E_ARG as in camo_fusion.h; every
  * argument check runs on the host before any launch.  The ABI version is that of camo_fusion.h. */

@@ -1,0 +1,93 @@
+"""Developer aid / measurement of geodesic growth for the instance splitter (include/camo_split_geo.h):
+  python tools/dev/dev_split_geo_bench.py launches   microseconds per call of camo_split_instances_geodesic at N = 16 of 256 x 256 and at
+                                                     one 1024 x 1024 -- the shapes of dev_split_bench.py --, on the label maps camo_instances
+                                                     makes of dev_instances_bench.py's blob-like mask with one coiled shape per image (a
+                                                     two-turn spiral, a blob at either end, in a cleared box: what the growth is for);
+                                                     beside it camo_split_instances on the same inputs, and the rounds to convergence
+The rounds to convergence are counted first: one call of 1 round, then resumes of 1 round each until pending is all zero (each read
+synchronises; none of that is timed).  Timed: the geodesic call with the default rounds of split.split_instances (tiles_x + tiles_y), the
+geodesic call with exactly the rounds the content needed, and the Euclidean call.  The library is called directly with every buffer
+allocated beforehand; every case is warmed up; a window is 200 calls between two device events (50 at 1024 x 1024), the smallest of five
+windows is the figure and the largest is printed beside it.  After the timed calls pending must be all zero, and at 256 x 256 image
+0's outputs are checked against the restatement (tests/split_geo_ref.py).  No time is asserted."""
+import os, sys
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_geo_ref as G
+from dev_instances_bench import SIZES, inputs, timed
+from dev_split_bench import ROWS, label_maps
+
+SPIRAL = ((20, 20), (20, 25), (15, 25), (15, 15), (25, 15), (25, 30), (10, 30), (10, 10), (30, 10), (30, 35), (5, 35), (5, 5), (36, 5))
+
+
+def coiled(pred, scale):
+    """``pred`` with, per image, a box of 42 * scale pixels cleared in the top left corner and a two-turn spiral drawn into it: a
+    corridor 2 * scale wide (tests/test_split_geo.py's fixture, enlarged), a disc at the centre and one at the outer end."""
+    side = 42 * scale
+    yy, xx = np.mgrid[:side, :side]
+    box = np.zeros((side, side), bool)
+    for (y0, x0), (y1, x1) in zip(SPIRAL, SPIRAL[1:]):
+        ya, yb, xa, xb = min(y0, y1) * scale, (max(y0, y1) + 2) * scale, min(x0, x1) * scale, (max(x0, x1) + 2) * scale
+        box[ya:yb, xa:xb] = True
+    for cy, cx in (SPIRAL[0], SPIRAL[-1]):
+        box |= (yy - cy * scale - scale) ** 2 + (xx - cx * scale - scale) ** 2 <= (3.5 * scale) ** 2
+    out = pred.copy()
+    out[:, :side, :side] = np.where(box, np.float32(0.9), np.float32(0.1))
+    return out
+
+
+def launches():
+    import torch
+    from camouflage_multimodal_amd import _lib
+    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
+    L, T = _lib.lib(), _lib.SPLIT_GEO_TILE
+    for N, H, W, iters in SIZES:
+        pred = coiled(inputs(N, H, W)["blobs"], H // 128)
+        p, labels, min_area = label_maps(pred)
+        dev = p.device
+        st = _stream_ptr(dev)
+        nbytes, gbytes = L.camo_split_workspace_bytes(N, H, W, 4), L.camo_split_geodesic_workspace_bytes(N, H, W, 4)
+        ws = torch.empty(max(nbytes, gbytes), dtype=torch.uint8, device=dev)
+        out, eout = (torch.empty(N, H, W, dtype=torch.int32, device=dev) for _ in range(2))
+        table = torch.empty(N, ROWS, 8, dtype=torch.int64, device=dev)
+        counts = torch.empty(N, 4, dtype=torch.int32, device=dev)
+        pending = torch.empty(N, dtype=torch.int32, device=dev)
+        head = (_ptr(labels), _ptr(p), H * W, N, H, W, 7, 10, 0, 4, ROWS)
+
+        def geodesic(rounds, fn=L.camo_split_instances_geodesic):
+            rc = fn(*head, _ptr(out), _ptr(table), _ptr(counts), _ptr(ws), gbytes, st, rounds, _ptr(pending))
+            if rc != 0: raise RuntimeError(L.camo_last_error())
+
+        def euclidean():
+            rc = L.camo_split_instances(*head, _ptr(eout), _ptr(table), _ptr(counts), _ptr(ws), nbytes, st)
+            if rc != 0: raise RuntimeError(L.camo_last_error())
+        geodesic(1)
+        needed = 1
+        while any(pending.tolist()):
+            geodesic(1, L.camo_split_geodesic_resume)
+            needed += 1
+            if needed > 4096: raise RuntimeError("the growth does not converge")
+        default = -(-H // T) + -(-W // T)
+        te = timed(euclidean, iters)
+        tn = timed(lambda: geodesic(needed), iters)
+        left_n = pending.tolist()
+        td = timed(lambda: geodesic(max(default, needed)), iters)
+        left_d = pending.tolist()
+        c = counts.cpu().numpy()
+        differ = int((out != eout).sum())
+        if H * W <= 256 * 256:
+            want = G.split_image(labels[0].cpu().numpy(), pred[0], max_instances=ROWS)
+            same = all(np.array_equal(a, b) for a, b in zip((out[0].cpu().numpy(), table[0].cpu().numpy(), c[0]), want[:3]))
+            verdict = f"image 0 {'equal to' if same else 'DIFFERENT FROM'} the restatement"
+        else:
+            ok = bool(((out > 0) == (labels > 0)).all()) and int(out.max()) == int(c[:, 0].max())
+            verdict = f"foreground and id range {'kept' if ok else 'WRONG'} (the restatement is not run at this size)"
+        print(f"N = {N}, {H} x {W}, blobs and a coil (min_area {min_area}): {needed} rounds to convergence (default {default}); geodesic with {needed} rounds "
+              f"{tn[0]:.1f} us (up to {tn[1]:.1f}), {_lib.SPLIT_GEO_LAUNCHES + needed} launches, pending {sum(left_n)}; with {max(default, needed)} rounds "
+              f"{td[0]:.1f} us (up to {td[1]:.1f}), pending {sum(left_d)}; Euclidean {te[0]:.1f} us (up to {te[1]:.1f}), {_lib.SPLIT_LAUNCHES} launches; "
+              f"(K', split, dropped, left whole) over the batch {c.sum(axis=0).tolist()}; {differ} pixels differ between the two; {verdict}", flush=True)
+
+
+if __name__ == "__main__":
+    {"launches": launches}[sys.argv[1]](*sys.argv[2:4])
