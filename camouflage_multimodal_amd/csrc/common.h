@@ -48,10 +48,16 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
 // element counter offset by a per-(site, seed) constant and whitened with the seed's high word: two 32-bit
 // multiplies per element (v_mul_lo_u32 is quarter rate on gfx950; the two-round version of round 1 cost ~150
 // cycles per element and showed up as microseconds in every epilogue that draws a mask).
-__device__ __forceinline__ float drop_mult(const DropCfg& d, uint32_t site, uint32_t idx) {
+__device__ __forceinline__ bool drop_keep(const DropCfg& d, uint32_t site, uint32_t idx) {
   const uint32_t x = fmix32((idx + (site * 0x85EBCA77u + d.seed_lo)) ^ d.seed_hi);
-  return x >= d.thr ? d.scale : 0.0f;
+  return x >= d.thr;
 }
+__device__ __forceinline__ float drop_mult(const DropCfg& d, uint32_t site, uint32_t idx) {
+  return drop_keep(d, site, idx) ? d.scale : 0.0f;
+}
+// The draw depends on indices only, so a kernel can take it before its data arrives: bit k of a register of keep bits drawn at
+// block start -> the multiplier drop_mult would have returned for that element.
+__device__ __forceinline__ float keep_mult(const DropCfg& d, uint32_t bits, int k) { return (bits >> k) & 1u ? d.scale : 0.0f; }
 
 // lane `i` of the VGPR `v` <- the wave-uniform 32-bit value `s`: one v_writelane_b32.  This hipcc declares no writelane builtin, so
 // the LLVM intrinsic is bound by its name -- NOT inline assembly: gfx950 wants two wait states between a VALU instruction writing an

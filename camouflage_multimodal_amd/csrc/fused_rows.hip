@@ -21,47 +21,84 @@
 
 namespace {
 
-// ---- one linear layer of a tile: acc[t] (+)= sum over KS k steps.  `wp` = the wave's fragment stream + lane (16-byte
+// ---- one linear layer of a tile: acc[t] (+)= sum over KS k steps (tile-major walk: acc[t] = the sum, whatever it held).  `wp` = the wave's fragment stream + lane (16-byte
 // units: fragment i of the stream is wp[64 i]); `act` = LDS address of this lane's first activation fragment (row
 // lane & 31, byte offset 16 (lane >> 5)); k step ks is 32 bytes further.  DEPTH weight fragments are kept in flight.
 // `rot` (block-uniform) rotates the order of the k steps (tiles of a launch all walk the SAME weight stream).
 // prefetch() issues the first DEPTH weight loads and may be called well before run() -- ahead of the epilogue or the
 // attention that produces the stage's input -- so that the stream is already flowing when the MFMAs start.
-template <int NT, int KS, bool W_IS_A, int DEPTH, bool USE_ROT = true>
+//
+// Two walk orders over the same fragment-order shadow (only the order of the addresses differs; every accumulator sees its
+// k steps in the same rotated order either way, so each fp32 sum is bit-identical between the two):
+//   k-major (default): step i = (k step i / NT, tile i % NT) -- one activation read per k step, all NT accumulators finish together.
+//   TILE_MAJOR:        step i = (tile i / KS, k step i % KS) -- tile t is finished KS steps before tile t + 1, so its epilogue can
+//                      run in the gaps of tile t + 1's stream instead of behind the whole stage.  The activation fragment is
+//                      read from LDS once per MFMA (one ds_read_b128 per gap).
+// run_s / run_fs take a `side(i)` functor that is called behind MFMA i, in front of the step's scheduling barrier: with one
+// wave per SIMD the vector instructions placed there issue while the stream waits for its next fragment.  RULE: a side slot
+// holds arithmetic, LDS traffic and loads only.  vmcnt retires loads, stores and atomics in order, so a global store or atomic
+// in front of, or inside, a stream makes the stream's next counted wait sit out the write: they all stay behind the last MFMA.
+template <int NT, int KS, bool W_IS_A, int DEPTH, bool USE_ROT = true, bool TILE_MAJOR = false>
 struct Stage {
   static constexpr int TOTAL = NT * KS;
   static constexpr int D = DEPTH < TOTAL ? DEPTH : TOTAL;
+  static constexpr int XSTEP = TILE_MAJOR ? 1 : NT;          // steps between two activation reads
   static_assert(!USE_ROT || (KS & (KS - 1)) == 0, "rotated k order: power-of-two k steps");
   u32x4 buf[D];
-  const u32x4* wp; int rot;
+  const u32x4* wp; int rot; unsigned ln = 0u;
+  static __device__ __forceinline__ constexpr int step_ks(int i) { return TILE_MAJOR ? i % KS : i / NT; }
+  static __device__ __forceinline__ constexpr int step_t(int i) { return TILE_MAJOR ? i / KS : i % NT; }
   __device__ __forceinline__ int keff(int ks) const { return USE_ROT ? ((ks + rot) & (KS - 1)) : ks; }
-  __device__ __forceinline__ const u32x4* wptr(int i) const { return wp + 64 * (keff(i / NT) * NT + (i % NT)); }
+  __device__ __forceinline__ const u32x4* wptr(int i) const {
+    if constexpr (TILE_MAJOR) {   // scalar base of the k step + (lane, tile) as an unsigned 32-bit byte offset: the load's scalar-address form
+      const char* kbase = reinterpret_cast<const char*>(wp) + (size_t)(keff(step_ks(i)) * (NT * 1024));
+      return reinterpret_cast<const u32x4*>(kbase + (size_t)(uint32_t)(16u * ln + 1024u * (unsigned)step_t(i)));
+    } else {
+      return wp + 64 * (keff(step_ks(i)) * NT + step_t(i)) + ln;
+    }
+  }
   __device__ __forceinline__ void prefetch(const u32x4* __restrict__ wp_, int rot_) {
     wp = wp_; rot = rot_;
 #pragma unroll
     for (int i = 0; i < D; ++i) buf[i] = *wptr(i);
   }
+  // the same with the wave's stream (block-uniform) and the lane apart: a fragment's address is then a scalar base plus one lane offset.
+  // The tile-major walk comes back to every rotated k step once per tile; with the lane folded into the pointer it kept all KS
+  // fragment addresses in vector registers through the whole stream (32 VGPRs for 16 k steps)
+  __device__ __forceinline__ void prefetch(const u32x4* __restrict__ wave_stream, int lane, int rot_) {
+    ln = (unsigned)lane;
+    prefetch(wave_stream, rot_);
+  }
   __device__ __forceinline__ void run(const char* act, f32x16 (&acc)[NT]) {
-    run_f([&](int ks) { return *reinterpret_cast<const bf16x8*>(act + 32 * ks); }, acc);
+    run_fs([&](int ks) { return *reinterpret_cast<const bf16x8*>(act + 32 * ks); }, acc, [](int) {});
+  }
+  template <class S>
+  __device__ __forceinline__ void run_s(const char* act, f32x16 (&acc)[NT], S&& side) {
+    run_fs([&](int ks) { return *reinterpret_cast<const bf16x8*>(act + 32 * ks); }, acc, side);
   }
   // frag(ks): this lane's activation fragment of k step ks (the default reads it from the LDS tile)
   template <class F>
-  __device__ __forceinline__ void run_f(F&& frag, f32x16 (&acc)[NT]) {
+  __device__ __forceinline__ void run_f(F&& frag, f32x16 (&acc)[NT]) { run_fs(frag, acc, [](int) {}); }
+  template <class F, class S>
+  __device__ __forceinline__ void run_fs(F&& frag, f32x16 (&acc)[NT], S&& side) {
     bf16x8 x = frag(keff(0)), xn = x;
-    // One step = {issue the weight load DEPTH fragments ahead, (first tile of a k step: start the NEXT k step's activation
-    // read), MFMA}.  The scheduling barrier pins that order: left alone, hipcc sinks every load next to its use and the
-    // stream runs at one L2 round trip per fragment (measured: s_waitcnt vmcnt(1) in front of almost every MFMA).
+    // One step = {issue the weight load DEPTH fragments ahead, (first step on an activation fragment: start the read of the
+    // NEXT one), MFMA, side slot}.  The scheduling barrier pins that order: left alone, hipcc sinks every load next to its use
+    // and the stream runs at one L2 round trip per fragment (measured: s_waitcnt vmcnt(1) in front of almost every MFMA).
 #pragma unroll
     for (int i = 0; i < TOTAL; ++i) {
-      const int ks = i / NT, t = i % NT;
+      const int t = step_t(i);
       const bf16x8 wf = as_frag(buf[i % D]);
       if (i + D < TOTAL) buf[i % D] = *wptr(i + D);
-      if (t == 0) {
+      if (i % XSTEP == 0) {
         x = xn;
-        if (ks + 1 < KS) xn = frag(keff(ks + 1));
+        if (i + XSTEP < TOTAL) xn = frag(keff(step_ks(i + XSTEP)));
       }
-      if constexpr (W_IS_A) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, x, acc[t], 0, 0, 0);
-      else                  acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, wf, acc[t], 0, 0, 0);
+      // (tile-major: a tile's first step starts from zero, not from acc[t] -- the tiles not yet reached hold no registers)
+      const f32x16 c = (TILE_MAJOR && step_ks(i) == 0) ? zero16() : acc[t];
+      if constexpr (W_IS_A) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, x, c, 0, 0, 0);
+      else                  acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, wf, c, 0, 0, 0);
+      side(i);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -69,8 +106,11 @@ struct Stage {
 
 // Developer timeline (testing hook "stamps"): when a buffer is given, wave 0 of every block records the 100 MHz wall clock
 // at its phase boundaries: stamps[block * 8 + k].  Product calls pass null and execute none of it.
+// The store goes through a global-address-space pointer: where hipcc cannot prove that for itself it emits a flat store, and a flat
+// operation anywhere in front of a stream -- executed or not -- makes the stream's first wait a vmcnt(0) behind the load just issued.
 __device__ __forceinline__ void stamp(unsigned long long* stamps, int k) {
-  if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  typedef __attribute__((address_space(1))) unsigned long long global_u64;
+  if (stamps && threadIdx.x == 0) ((global_u64*)stamps)[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
 }
 
 // rows [0, nrows) of a bf16 LDS tile -> global, 16 bytes per thread, whole rows contiguous (LOG2C: log2 of 16-byte chunks per row)
@@ -131,11 +171,11 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
   __syncthreads();
   // projection 128 -> 256  (every global store of the tile waits for the end of the kernel: vmcnt counts stores too and
   // retires in order, so a store issued in front of a weight stream makes the stream's first waits sit out its write latency)
-  Stage<6, 16, true, DEPTH> st1;
+  Stage<6, 16, true, DEPTH, true, true> st1;                 // tile-major: tile t's epilogue runs under tile t + 1's stream
   {
     f32x16 acc[2] = {zero16(), zero16()};
     st0.run(bufX + l31 * PX + 16 * h, acc);
-    st1.prefetch(reinterpret_cast<const u32x4*>(S.W1) + (size_t)w * (16 * 6 * 64) + lane, rot);
+    st1.prefetch(reinterpret_cast<const u32x4*>(S.W1) + (size_t)w * (16 * 6 * 64), lane, rot);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -153,21 +193,24 @@ __global__ __launch_bounds__(256, 2) void front_kernel(const FrontArgs a) {
     f32x16 acc[6];
 #pragma unroll
     for (int t = 0; t < 6; ++t) acc[t] = zero16();
-    st1.run(bufR + l31 * PR + 16 * h, acc);
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
+    // register group g of feature tile t: bias from the LDS table, scale, pack, into bufQ (which nobody reads before the barrier below)
+    auto epi = [&](int t, int g) {
       const int tg = 6 * w + t;                                  // wave-uniform
       const float* bias = ptab + 256 + 32 * tg;                  // [bq | bkv]
       const float sc = tg < 8 ? a.qscale : 1.0f;
+      const int c = 8 * g + 4 * h;
+      const float4 bv = *reinterpret_cast<const float4*>(bias + c);
+      *reinterpret_cast<u32x2*>(bufQ + l31 * PQ + 2 * (32 * tg + c)) =
+          u32x2{pack2((acc[t][4 * g] + bv.x) * sc, (acc[t][4 * g + 1] + bv.y) * sc),
+                pack2((acc[t][4 * g + 2] + bv.z) * sc, (acc[t][4 * g + 3] + bv.w) * sc)};
+    };
+    // tile t's four groups ride in tile t + 1's stream, one per four k steps; only the last tile's are left behind it
+    st1.run_s(bufR + l31 * PR + 16 * h, acc, [&](int i) {
+      const int t = i >> 4, r = i & 15;
+      if (t > 0 && (r & 3) == 2) epi(t - 1, r >> 2);
+    });
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = 8 * g + 4 * h;
-        const float4 bv = *reinterpret_cast<const float4*>(bias + c);
-        *reinterpret_cast<u32x2*>(bufQ + l31 * PQ + 2 * (32 * tg + c)) =
-            u32x2{pack2((acc[t][4 * g] + bv.x) * sc, (acc[t][4 * g + 1] + bv.y) * sc),
-                  pack2((acc[t][4 * g + 2] + bv.z) * sc, (acc[t][4 * g + 3] + bv.w) * sc)};
-      }
-    }
+    for (int g = 0; g < 4; ++g) epi(5, g);
   }
   __syncthreads();
   stamp(a.stamps, 2);
@@ -298,6 +341,22 @@ __device__ __forceinline__ void attn_kg_split(const BackArgs& a, char* smem, int
       const int id = lane + 64 * i;
       vv[c][i] = *reinterpret_cast<const u32x4*>(vbase + (size_t)min(r0 + 32 * c + (id >> 3), nr - 1) * 512 + 8 * (id & 7));
     }
+  // the split's 64 dropout draws depend on indices only: taken here, behind the issue of every load and in front of the first wait, where
+  // the block had nothing to do (bit 16 hd + i of keep[c]: head 2 w + hd, key row acc_row(i, h) of chunk c); the exp loop only selects
+  const bool dodrop = a.drop.p > 0.f;
+  uint32_t keep[2] = {0u, 0u};
+  if (dodrop) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int hd = 0; hd < 2; ++hd)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int row = r0 + 32 * c + acc_row(i, h);
+          keep[c] |= (uint32_t)drop_keep(a.drop, SITE_ATTN_KG2RG, ((uint32_t)(rb + row) * 8u + (uint32_t)(2 * w + hd)) * (uint32_t)Nk + (uint32_t)l31) << (16 * hd + i);
+        }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // scores S[c][hd][row acc_row(i, h) of chunk c][query l31] (queries are pre-scaled), maximum over the split's valid keys
   f32x16 S[2][2];
   float mx[2] = {-INFINITY, -INFINITY};
@@ -316,7 +375,6 @@ __device__ __forceinline__ void attn_kg_split(const BackArgs& a, char* smem, int
   stamp(a.stamps, 1);
   f32x16 Z[2] = {zero16(), zero16()};
   float L[2] = {0.f, 0.f};
-  const bool dodrop = a.drop.p > 0.f;
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -330,7 +388,7 @@ __device__ __forceinline__ void attn_kg_split(const BackArgs& a, char* smem, int
         const int row = r0 + 32 * c + acc_row(i, h);
         e[i] = row < nr ? __expf(S[c][hd][i] - mx[hd]) : 0.f;
         L[hd] += e[i];
-        if (dodrop) e[i] *= drop_mult(a.drop, SITE_ATTN_KG2RG, ((uint32_t)(rb + row) * 8u + (uint32_t)(2 * w + hd)) * (uint32_t)Nk + (uint32_t)l31);
+        if (dodrop) e[i] *= keep_mult(a.drop, keep[c], 16 * hd + i);
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -452,7 +510,7 @@ __device__ __forceinline__ void attn_kg_combine(const BackArgs& a, char* smem, c
   }
 }
 
-// OCC: blocks per CU the register budget is sized for -- 3 (168 VGPRs, a few dwords of scratch) for launches of more than two
+// OCC: blocks per CU the register budget is sized for -- 3 (168 VGPRs) for launches of more than two
 // blocks per CU, where the third co-resident tile hides the others' waits (B = 64: 77 -> 68 us, B = 1024: 1.33 -> 1.16 ms);
 // 2 for the small batches whose one tile per CU is the critical path (B = 16: the tighter budget cost 1.7 us).
 template <int DEPTH, bool ROT, int OCC>
@@ -476,7 +534,7 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   stamp(a.stamps, 0);
   const BackStream& S = a.s[kg ? 1 : 0];
   Stage<2, 16, true, DEPTH> sto;
-  Stage<4, 16, false, DEPTH> stf;
+  Stage<4, 16, false, DEPTH, true, true> stf;              // tile-major: tile t's epilogue runs under tile t + 1's stream
   if (!kg) sto.prefetch(reinterpret_cast<const u32x4*>(S.Wo) + (size_t)w * (16 * 2 * 64) + lane, rot);   // (flows during the attention)
   // OCC = 2: what the two epilogues read from global memory at addresses that depend on nothing this kernel computes is loaded in front of the
   // attention (KG chain: in front of the combine) -- the parameter vectors, five values per thread, into the LDS table once the
@@ -550,7 +608,7 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   {
     f32x16 acc[2] = {zero16(), zero16()};
     sto.run(bufO + l31 * PR + 16 * h, acc);
-    stf.prefetch(reinterpret_cast<const u32x4*>(S.W1) + (size_t)w * (16 * 4 * 64) + lane, rot);           // (flows during the LayerNorm)
+    stf.prefetch(reinterpret_cast<const u32x4*>(S.W1) + (size_t)w * (16 * 4 * 64), lane, rot);           // (flows during the LayerNorm)
     float part = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -634,37 +692,49 @@ __global__ __launch_bounds__(256, OCC) void back_kernel(const BackArgs a) {
   // ---- FFN layer 0 + ReLU + dropout, pooled over the rows (lane = feature; wave w: features 128 w .. 128 w + 127)
   {
     f32x16 acc[4] = {zero16(), zero16(), zero16(), zero16()};
-    stf.run(bufY + l31 * PR + 16 * h, acc);
-    if constexpr (OCC == 2) atomicAdd(S.Ymean + (size_t)b * 256 + tid, ymean_keep);
     const bool dodrop = a.drop.p > 0.f;
+    float bias[4], colsum[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t wlo[4] = {0u, 0u, 0u, 0u}, whi[4] = {0u, 0u, 0u, 0u};
+    // register i of feature tile t: bias, ReLU, dropout draw, rows past the tile's end cleared, column sum, and the saved mask bit
+    // (lane i of wlo / whi <- the ballot's halves, common.h).  Same arithmetic in the same order as when the four tiles were walked
+    // behind the stream; what it produces -- four column sums, eight mask words -- stays in registers until the stream is through.
+    auto epi = [&](int t, int i) {
+      if (8 * (i >> 2) >= nrows) return;                    // (block-uniform) a register group whose rows are all past the tile's end: the
+                                                            // KG tile has 13 rows, so half of its epilogue -- on the kernel's critical path -- goes
+      const int row = acc_row(i, h);
+      float v = fmaxf(acc[t][i] + bias[t], 0.f);
+      if (dodrop) v *= drop_mult(a.drop, S.site_ffn, (uint32_t)(rowg0 + row) * 512u + (uint32_t)(128 * w + 32 * t + l31));
+      if (row >= nrows) v = 0.f;
+      colsum[t] += v;
+      if (a.save) {
+        const unsigned long long bal = __ballot(v > 0.f);
+        SET_LANE(wlo[t], (uint32_t)bal, i); SET_LANE(whi[t], (uint32_t)(bal >> 32), i);
+      }
+    };
+    // side slots: k step ks of tile t + 1 carries register ks of tile t (sixteen k steps, sixteen registers), so only the last tile's
+    // epilogue is left behind the stream; a tile's bias value is
+    // fetched in the middle of its own stream (a load, not a store: it retires in order in front of the fragments issued behind it)
+    stf.run_s(bufY + l31 * PR + 16 * h, acc, [&](int i) {
+      const int t = i >> 4, r = i & 15;
+      if (r == 8) {
+        if constexpr (OCC == 2) bias[t] = ptab[768 + 128 * w + 32 * t + l31];
+        else bias[t] = S.b1[128 * w + 32 * t + l31];
+      }
+      if (t > 0) epi(t - 1, r);
+    });
+    stamp(a.stamps, 7);                                      // last FFN MFMA issued: what follows is the last tile's epilogue and the saves
+    if constexpr (OCC == 2) atomicAdd(S.Ymean + (size_t)b * 256 + tid, ymean_keep);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) epi(3, i);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int f = 128 * w + 32 * t + l31;
-      float bias;
-      if constexpr (OCC == 2) bias = ptab[768 + f];
-      else bias = S.b1[f];
-      float colsum = 0.f;
-      uint32_t wlo = 0u, whi = 0u;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        if (8 * (i >> 2) >= nrows) continue;                // (block-uniform) a register group whose rows are all past the tile's end: the
-                                                            // KG tile has 13 rows, so half of its epilogue -- on the kernel's critical path -- goes
-        const int row = acc_row(i, h);
-        float v = fmaxf(acc[t][i] + bias, 0.f);
-        if (dodrop) v *= drop_mult(a.drop, S.site_ffn, (uint32_t)(rowg0 + row) * 512u + (uint32_t)f);
-        if (row >= nrows) v = 0.f;
-        colsum += v;
-        if (a.save) {
-          const unsigned long long bal = __ballot(v > 0.f);
-          SET_LANE(wlo, (uint32_t)bal, i); SET_LANE(whi, (uint32_t)(bal >> 32), i);      // lane i <- the ballot's halves (common.h)
-        }
-      }
-      colsum += __shfl_xor(colsum, 32, 64);
-      if (h == 0) atomicAdd(S.Hmean + (size_t)b * 512 + f, colsum * inv_n);
+      const float cs = colsum[t] + __shfl_xor(colsum[t], 32, 64);
+      if (h == 0) atomicAdd(S.Hmean + (size_t)b * 512 + f, cs * inv_n);
       if (a.save && lane < 16) {                       // lane i holds the words of rows acc_row(i, 0) and acc_row(i, 1), features 32 (4 w + t) ..
         const int ra = acc_row(lane, 0);
-        if (ra < nrows) S.mask[(rowg0 + ra) * 16 + 4 * w + t] = wlo;
-        if (ra + 4 < nrows) S.mask[(rowg0 + ra + 4) * 16 + 4 * w + t] = whi;
+        if (ra < nrows) S.mask[(rowg0 + ra) * 16 + 4 * w + t] = wlo[t];
+        if (ra + 4 < nrows) S.mask[(rowg0 + ra + 4) * 16 + 4 * w + t] = whi[t];
       }
     }
   }
@@ -856,6 +926,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) mw[i] = reinterpret_cast<const u32x4*>(S.mask + vrow * 16)[i];
   u32x4 qreg[4];
+  const bool dodrop = a.drop.p > 0.f;
+  uint32_t keep = 0u;                                                    // the attention backward's 16 draws: bit 8 t + i = head 2 w + t, key acc_row(i, h)
   if (!kg) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {                                        // query tile: slot id -> row id >> 5, 16-byte chunk id & 31
@@ -868,6 +940,15 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
     for (int i = 0; i < 4; ++i) {
       const int c = tid + 256 * i;
       kv[i] = *reinterpret_cast<const u32x4*>(a.KV16 + ((size_t)b * a.Nk + min(c >> 6, a.Nk - 1)) * 512 + 8 * (c & 63));
+    }
+    if (dodrop) {                                                        // (indices only: drawn while the block's loads are in flight)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const uint32_t ibase = ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)(2 * w + t)) * (uint32_t)a.Nk;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) keep |= (uint32_t)drop_keep(a.drop, SITE_ATTN_RG2KG, ibase + (uint32_t)acc_row(i, h)) << (8 * t + i);
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1006,7 +1087,6 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
           rok ? u32x2{pack2(acc2[t][4 * g], acc2[t][4 * g + 1]), pack2(acc2[t][4 * g + 2], acc2[t][4 * g + 3])} : u32x2{0u, 0u};
     }
   __syncthreads();
-  const bool dodrop = a.drop.p > 0.f;
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -1021,9 +1101,8 @@ __global__ __launch_bounds__(256, 2) void bwd1_kernel(const Bwd1Args a) {
     }
     float pr[8], mm[8];
     rg_softmax(Sc, h, a.Nk, pr);
-    const uint32_t ibase = ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)head) * (uint32_t)a.Nk;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) mm[i] = dodrop ? drop_mult(a.drop, SITE_ATTN_RG2KG, ibase + (uint32_t)acc_row(i, h)) : 1.0f;
+    for (int i = 0; i < 8; ++i) mm[i] = dodrop ? keep_mult(a.drop, keep, 8 * t + i) : 1.0f;
     // dPd^T[j][row] = V_h[j] . dO_h[row]: the dO accumulator is the B operand (k order of its registers), so the A fragment
     // takes features 16 s + 4 h .. + 3 and 16 s + 8 + 4 h .. + 3 of value row j
     f32x16 dP = zero16();
@@ -1312,8 +1391,19 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
         vf[t][s] = as_frag(*reinterpret_cast<const u32x4*>(kp + 256 + 32 * t + 16 * s));
       }
   }
-  __syncthreads();
+  // the 16 dropout draws depend on indices only: taken while the block's loads are in flight (bit 8 t + i: head 2 w + t, query acc_row(i, h))
   const bool dodrop = a.drop.p > 0.f;
+  uint32_t keep = 0u;
+  if (dodrop) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const uint32_t ibase = ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)(2 * w + t)) * (uint32_t)Nk;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) keep |= (uint32_t)drop_keep(a.drop, SITE_ATTN_KG2RG, ibase + (uint32_t)acc_row(i, h)) << (8 * t + i);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -1330,7 +1420,7 @@ __global__ __launch_bounds__(256, 2) void bwd2_kernel(const Bwd2Args a) {
     for (int i = 0; i < 8; ++i) {
       const int j = acc_row(i, h);
       const float p = (j < Nk && rok) ? __expf(S2[i] - tabs[head * 16 + j]) * tabs[128 + head * 16 + j] : 0.f;
-      const float mm = dodrop ? drop_mult(a.drop, SITE_ATTN_KG2RG, ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)head) * (uint32_t)Nk + (uint32_t)j) : 1.0f;
+      const float mm = dodrop ? keep_mult(a.drop, keep, 8 * t + i) : 1.0f;
       ds[i] = p * (dP[i] * mm - tabs[256 + head * 16 + j]);
       pd[i] = p * mm;
     }
@@ -1525,8 +1615,19 @@ __global__ __launch_bounds__(256, 2) void bwd2p_kernel(const Bwd2Args a) {
         vf[t][s] = as_frag(*reinterpret_cast<const u32x4*>(kp + 256 + 32 * t + 16 * s));
       }
   }
-  __syncthreads();
+  // the 16 dropout draws depend on indices only: taken while the block's loads are in flight (bit 8 t + i: head 2 w + t, query acc_row(i, h))
   const bool dodrop = a.drop.p > 0.f;
+  uint32_t keep = 0u;
+  if (dodrop) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const uint32_t ibase = ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)(2 * w + t)) * (uint32_t)Nk;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) keep |= (uint32_t)drop_keep(a.drop, SITE_ATTN_KG2RG, ibase + (uint32_t)acc_row(i, h)) << (8 * t + i);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -1543,7 +1644,7 @@ __global__ __launch_bounds__(256, 2) void bwd2p_kernel(const Bwd2Args a) {
     for (int i = 0; i < 8; ++i) {
       const int j = acc_row(i, h);
       const float p = (j < Nk && rok) ? __expf(S2[i] - tabs[head * 16 + j]) * tabs[128 + head * 16 + j] : 0.f;
-      const float mm = dodrop ? drop_mult(a.drop, SITE_ATTN_KG2RG, ((uint32_t)(rowg0 + l31) * 8u + (uint32_t)head) * (uint32_t)Nk + (uint32_t)j) : 1.0f;
+      const float mm = dodrop ? keep_mult(a.drop, keep, 8 * t + i) : 1.0f;
       ds[i] = p * (dP[i] * mm - tabs[256 + head * 16 + j]);
       pd[i] = p * mm;
     }

@@ -57,7 +57,7 @@ for k, name in enumerate(("front", "back", "bwd1", "bwd2") if train else ("front
             nl = sp[sp[:, 6] == 0]
             if len(nl) and (nl[:, 1] > 0).all():
                 print(f"    KG split blocks that are not last arrivers: scores ready {np.median(nl[:, 1] - nl[:, 0]) / 100:.2f} us, exp/PV done "
-                      f"{np.median(nl[:, 2] - nl[:, 0]) / 100:.2f}, partial stored {np.median(nl[:, 4] - nl[:, 0]) / 100:.2f}, ticket {np.median(nl[:, 5] - nl[:, 0]) / 100:.2f}")
+                      f"{np.median(nl[:, 2] - nl[:, 0]) / 100:.2f} (stamp 1 -> 2: {np.median(nl[:, 2] - nl[:, 1]) / 100:.2f}), partial stored {np.median(nl[:, 4] - nl[:, 0]) / 100:.2f}, ticket {np.median(nl[:, 5] - nl[:, 0]) / 100:.2f}")
             print(f"    KG->RG attention: {len(sp)} splits: split {np.median(sp[:, 4] - sp[:, 0]) / 100:.2f} us (max {(sp[:, 4] - sp[:, 0]).max() / 100:.2f}), "
                   f"drain+ticket {np.median(sp[:, 5] - sp[:, 4]) / 100:.2f} (max {(sp[:, 5] - sp[:, 4]).max() / 100:.2f}); {len(la)} last arrivers: "
                   f"start->ticket {np.median(la[:, 5] - la[:, 0]) / 100:.2f}, combine {np.median(la[:, 6] - la[:, 5]) / 100:.2f} us; "
@@ -91,3 +91,7 @@ for k, name in enumerate(("front", "back", "bwd1", "bwd2") if train else ("front
             print(f"  {gname:10s} n={sel.sum():4d}  phase durations us (median / max): " +
                   "  ".join(f"{np.median(ph[sel, j]):.2f}/{ph[sel, j].max():.2f}" for j in range(3)) +
                   f"   block total median {np.median(ph[sel].sum(1)):.2f} max {ph[sel].sum(1).max():.2f}")
+        if name == "back" and (sel & (s[:, 7] > 0)).any():      # stamp 7: last FFN MFMA issued (splits the third phase)
+            f = s[sel & (s[:, 7] > 0)]
+            print(f"  {gname:10s} FFN phase: stream (stamp 2 -> 7) {np.median(f[:, 7] - f[:, 2]) / 100:.2f}/{(f[:, 7] - f[:, 2]).max() / 100:.2f}"
+                  f"  epilogue remainder + saves (stamp 7 -> 3) {np.median(f[:, 3] - f[:, 7]) / 100:.2f}/{(f[:, 3] - f[:, 7]).max() / 100:.2f}")
