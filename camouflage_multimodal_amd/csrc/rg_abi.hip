@@ -1,8 +1,7 @@
 // C ABI of the region-graph side (include/camo_rg_*.h, camo_canny.h, camo_slic.h): argument checks, workspace carving and the launch
-// sequences of the CSR build, the GNN embedding path, region-graph construction (single image and batched), Canny, SLIC, the node
-// heads / painting / metrics, the GNN's loss and gradients with batch norm frozen or on batch statistics, with or without dropout, with or
-// without the structure loss on the painted mask, and the node targets and node weights from ground-truth masks.  The image pipeline around the detector (instances, their matching, boundary maps, the
-// guided filter, run-length masks, polygons) has image_abi.hip.  No device code here.
+// sequences of the CSR build, the GNN embedding path, region-graph construction, Canny, SLIC, the node heads / painting / metrics, the
+// GNN's training call (four entries, one sequence: rgt_run) and the node targets and weights from ground-truth masks.  The image
+// pipeline around the detector has image_abi.hip.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -138,27 +137,53 @@ RgtWs rgt_carve(const camo_rg_dims_t& d, int nc, int N, void* base, bool batch_s
   w.bytes = c.bytes();
   return w;
 }
-int rgt_check(const camo_rg_dims_t* d, int nc, int N, int E) {
+// rg_check's envelope, plus E >= N and an even hidden, hence >= 2; under batch statistics N >= 2 as well: the unbiased variance of the
+// running update divides by N - 1.  The message states the whole of it.
+int rgt_check(const camo_rg_dims_t* d, int nc, int N, int E, bool batch) {
   if (!d) return fail(CAMO_E_ARG, "dims is null");
-  // (rg_check's envelope, plus E >= N and an even hidden, hence >= 2; the message states the whole of it)
-  if (rg_check(d, N) || E < N || (d->hidden & 1))
-    return fail(CAMO_E_UNSUPPORTED, "need N >= 1, E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8");
+  if (rg_check(d, N) || (batch && N < 2) || E < N || (d->hidden & 1))
+    return fail(CAMO_E_UNSUPPORTED,
+                batch ? "need N >= 2 (batch statistics), E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8"
+                      : "need N >= 1, E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8");
   if (nc < 2 || nc > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_UNSUPPORTED, "num_classes must be in [2, 8]");
   return 0;
 }
-// (rgt_check's envelope, plus N >= 2: the unbiased variance of the running update divides by N - 1)
-int rgtbn_check(const camo_rg_dims_t* d, int nc, int N, int E) {
-  if (!d) return fail(CAMO_E_ARG, "dims is null");
-  if (rg_check(d, N) || N < 2 || E < N || (d->hidden & 1))
-    return fail(CAMO_E_UNSUPPORTED, "need N >= 2 (batch statistics), E >= N (one self-loop per node), hidden even and in [2, 512], 1 <= heads <= 8");
-  if (nc < 2 || nc > CAMO_RGD_MAX_CLASSES) return fail(CAMO_E_UNSUPPORTED, "num_classes must be in [2, 8]");
-  return 0;
+size_t rgt_workspace_bytes(const camo_rg_dims_t* d, int nc, int N, int E, bool batch) {      // the three camo_rg_train*_workspace_bytes
+  if (rgt_check(d, nc, N, E, batch)) return 0;
+  return rgt_carve(*d, nc, N, nullptr, batch).bytes;
 }
 constexpr bool rg_running_slot(int i) {      // the 8 running-statistic slots of camo_rg_gnn.h's table
   return i == CAMO_RG_BN1 + 2 || i == CAMO_RG_BN1 + 3 || (i >= CAMO_RG_C2_BIAS && i < CAMO_RG_FC_W && (i - CAMO_RG_C2_BIAS) % 6 >= 4);
 }
 static_assert(rg_running_slot(6) && rg_running_slot(7) && rg_running_slot(12) && rg_running_slot(25) && !rg_running_slot(5) && !rg_running_slot(8) &&
               !rg_running_slot(11) && !rg_running_slot(26), "the running statistics are slots 6, 7, then 12, 13 of every six");
+
+// The 24 arguments the four training entries share, in ABI order (include/camo_rg_train.h): every entry fills one.
+struct RgtCall {
+  const camo_rg_dims_t* dims; int32_t num_classes; const float* const* params; const float* const* head_params;
+  const float* x; const int32_t* rowptr; const int32_t* col; const float* w; const int32_t* rrowptr; const int32_t* rcol; const float* rw;
+  int32_t N, E; const int32_t* mask_t; const int32_t* inst_t; const float* edge_t; float w_mask, w_instance, w_edge;
+  void* workspace; size_t workspace_bytes; float* loss; float* const* grads; void* stream;
+};
+
+// What camo_rg_node_targets and camo_rg_pixel_weights share: the sizes of the label maps, and (after each entry's own scalars) the maps.
+int rg_maps_sizes(int N, int H, int W, int label_bound, int n_nodes) {
+  if (N < 1) return fail(CAMO_E_ARG, "N must be >= 1");
+  if (H < 1) return fail(CAMO_E_ARG, "H must be >= 1");
+  if (W < 1) return fail(CAMO_E_ARG, "W must be >= 1");
+  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, CAMO_RG_MAX_LABELS]");
+  if (n_nodes < 1) return fail(CAMO_E_ARG, "n_nodes must be >= 1");
+  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS");
+  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGB_MAX_PIXELS");
+  return 0;
+}
+int rg_maps_pointers(const int32_t* segments, const int32_t* region_map, const int32_t* node_off, const uint8_t* gt_mask) {
+  if (!segments) return fail(CAMO_E_ARG, "segments is null");
+  if (!region_map) return fail(CAMO_E_ARG, "region_map is null");
+  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
+  if (!gt_mask) return fail(CAMO_E_ARG, "gt_mask is null");
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -460,52 +485,47 @@ int camo_seg_counts(const float* pred, int64_t pred_image_stride, const uint8_t*
 static_assert(CAMO_RGT_NGRADS == 32 && CAMO_RGT_FC_B == 19 && CAMO_RGT_HEADS == 20, "the gradient table is the 20 + 12 trainable parameters");
 
 size_t camo_rg_train_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E) {
-  if (rgt_check(dims, num_classes, N, E)) return 0;
-  return rgt_carve(*dims, num_classes, N, nullptr).bytes;
+  return rgt_workspace_bytes(dims, num_classes, N, E, false);
 }
 
-// The one launch sequence of all three entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
+// The one launch sequence of all four entries.  batch: null = frozen statistics (camo_rg_loss_backward), else the batch-statistics mode
 // (its stats and partial are filled in here from the workspace).  drop: null = no dropout, else include/camo_rg_train_drop.h -- the
 // forward's eight sites, and in the backward nothing but a scale: every ReLU mask is taken from the saved, dropped activation, which
-// is > 0 exactly where the element was kept and the ReLU is open, so the mask's 1 becomes 1 / (1 - p).  pixel: null = today's sequence
-// launch for launch, else include/camo_rg_pixel_loss.h -- two launches right after the loss, which add the pixel term to dlogits and
-// to the loss figures (loss is float[6] then); the backward that follows does not know.
-static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
-                   const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
-                   const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
-                   const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                   float* loss, float* const* grads, void* stream, RgBatchNorm* batch, const RgDropout* drop = nullptr,
-                   const RgPixel* pixel = nullptr) {
-  if (int e = batch ? rgtbn_check(dims, num_classes, N, E) : rgt_check(dims, num_classes, N, E)) return e;
-  if (!params || !head_params || !x || !rowptr || !col || !w || !rrowptr || !rcol || !rw || !mask_t || !inst_t || !edge_t || !workspace ||
-      !loss || !grads)
+// is > 0 exactly where the element was kept and the ReLU is open, so the mask's 1 becomes 1 / (1 - p).  pixel: null = the sequence
+// without it launch for launch, else include/camo_rg_pixel_loss.h -- two launches right after the loss, which add the pixel term to
+// dlogits and to the loss figures (loss is float[6] then); the backward that follows does not know.
+static int rgt_run(const RgtCall& c, RgBatchNorm* batch, const RgDropout* drop, const RgPixel* pixel) {
+  const int N = c.N, nc = c.num_classes;
+  if (int e = rgt_check(c.dims, nc, N, c.E, batch != nullptr)) return e;
+  if (!c.params || !c.head_params || !c.x || !c.rowptr || !c.col || !c.w || !c.rrowptr || !c.rcol || !c.rw || !c.mask_t || !c.inst_t ||
+      !c.edge_t || !c.workspace || !c.loss || !c.grads)
     return fail(CAMO_E_ARG, "null pointer argument");
   for (int i = 0; i < CAMO_RG_NPARAMS; ++i)
-    if (!params[i] && !(batch && rg_running_slot(i))) return fail(CAMO_E_ARG, "null pointer in the parameter table");
+    if (!c.params[i] && !(batch && rg_running_slot(i))) return fail(CAMO_E_ARG, "null pointer in the parameter table");
   for (int i = 0; i < CAMO_RGD_NPARAMS; ++i)
-    if (!head_params[i]) return fail(CAMO_E_ARG, "null pointer in the head parameter table");
+    if (!c.head_params[i]) return fail(CAMO_E_ARG, "null pointer in the head parameter table");
   for (int i = 0; i < CAMO_RGT_NGRADS; ++i)
-    if (!grads[i]) return fail(CAMO_E_ARG, "null pointer in the gradient table");
-  if (!std::isfinite(w_mask) || !std::isfinite(w_instance) || !std::isfinite(w_edge)) return fail(CAMO_E_ARG, "loss weights must be finite");
+    if (!c.grads[i]) return fail(CAMO_E_ARG, "null pointer in the gradient table");
+  if (!std::isfinite(c.w_mask) || !std::isfinite(c.w_instance) || !std::isfinite(c.w_edge)) return fail(CAMO_E_ARG, "loss weights must be finite");
   if (batch && batch->running) {
     for (int i = 0; i < 8; ++i)
       if (!batch->running[i]) return fail(CAMO_E_ARG, "null pointer in the running-statistics table");
     if (!std::isfinite(batch->momentum) || !(batch->momentum > 0.f && batch->momentum <= 1.f))
       return fail(CAMO_E_ARG, "momentum must be finite and in (0, 1] when running is given");
   }
-  const camo_rg_dims_t& d = *dims;
-  const RgtWs ws = rgt_carve(d, num_classes, N, workspace, batch != nullptr);
-  if (workspace_bytes < ws.bytes)
+  const camo_rg_dims_t& d = *c.dims;
+  const RgtWs ws = rgt_carve(d, nc, N, c.workspace, batch != nullptr);
+  if (c.workspace_bytes < ws.bytes)
     return fail(CAMO_E_WORKSPACE, batch ? "workspace smaller than camo_rg_train_bn_workspace_bytes()" : "workspace smaller than camo_rg_train_workspace_bytes()");
   if (batch) { batch->stats = ws.stats; batch->partial = ws.partial; }
   const bool bs = batch != nullptr;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int C = d.hidden, K = d.heads, In = d.in_channels, nc = num_classes, Hh = C / 2, units = 3 * Hh, L = 2 * nc + 1;
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  const int C = d.hidden, K = d.heads, In = d.in_channels, Hh = C / 2, units = 3 * Hh, L = 2 * nc + 1;
   const int nb = rgt_row_blocks(N);
-  const float* const* P = params;
-  const float* const* HP = head_params;
-  float* const* G = grads;
-  float* const* GH = grads + CAMO_RGT_HEADS;
+  const float* const* P = c.params;
+  const float* const* HP = c.head_params;
+  float* const* G = c.grads;
+  float* const* GH = c.grads + CAMO_RGT_HEADS;
   auto bn = [&](int slot) { return BnEval{P[slot], P[slot + 1], P[slot + 2], P[slot + 3]}; };
   // dy (ReLU-masked, in dB) -> the layer's batch-norm gradients, its conv-bias gradient, and dPre in place.  Frozen: dPre = dy weight /
   // sqrt(var + eps), scaled by the first launch.  Batch statistics: the sums first, then dz from the finished sums (a third launch).
@@ -521,15 +541,15 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
   GB g(dhead ? drop->head : make_drop(0, 0.f, 0), CAMO_PREC_F32, st);   // (only the heads' first layers carry GF_DROPOUT in this batch)
 
   // ---- forward, saving (camo_rg_node_embeddings + camo_rg_node_heads) ----
-  if (int e = rg_forward(d, P, x, rowptr, col, w, N, ws, ws.emb, st, batch, drop)) return e;
+  if (int e = rg_forward(d, P, c.x, c.rowptr, c.col, c.w, N, ws, ws.emb, st, batch, drop)) return e;
   CK(launch_rgt_concat_heads(HP, ws.W1, ws.b1, C, st), "head weights");
   g.nt(ws.emb, C, ws.W1, C, ws.b1, ws.Z, units, N, units, C, dhead ? GF_RELU | GF_DROPOUT : GF_RELU).drop_site = SITE_RGT_HEADS;
   CK(g.run(), "head first layers");
   CK(launch_rgt_head_logits(HP, ws.Z, ws.logits, N, C, nc, st), "head logits");
 
   // ---- loss and dlogits ----
-  CK(launch_rgt_loss(ws.logits, mask_t, inst_t, edge_t, w_mask, w_instance, w_edge, N, nc, loss, ws.dlogits, st), "loss");
-  if (pixel) CK(launch_rgt_pixel_loss(ws.logits, *pixel, N, nc, loss, ws.dlogits, st), "pixel loss");
+  CK(launch_rgt_loss(ws.logits, c.mask_t, c.inst_t, c.edge_t, c.w_mask, c.w_instance, c.w_edge, N, nc, c.loss, ws.dlogits, st), "loss");
+  if (pixel) CK(launch_rgt_pixel_loss(ws.logits, *pixel, N, nc, c.loss, ws.dlogits, st), "pixel loss");
 
   // ---- heads backward ----
   CK(launch_rgt_cross_partial(nullptr, 0, 1, ws.dlogits, L, L, N, ws.partial, st), "head bias sums");
@@ -560,7 +580,7 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
   for (int k = 2; k >= 0; --k) {
     const int base = CAMO_RG_C2_BIAS + 6 * k, gb = CAMO_RGT_C2_BIAS + 4 * k;
     if (int e = bn_backward(k + 1, base + 2, G[gb + 2], G[gb + 3], G[gb])) return e;
-    CK(launch_rgt_gcn_backward(ws.dB, rrowptr, rcol, rw, ws.dinv, ws.dA, N, C, st), "gcn aggregate backward");
+    CK(launch_rgt_gcn_backward(ws.dB, c.rrowptr, c.rcol, c.rw, ws.dinv, ws.dA, N, C, st), "gcn aggregate backward");
     g.add(ws.dA, C, ws.h[k], C, G[gb + 1], C, C, C, N, KM);
     set_relu_bwd(g.nn(ws.dA, C, P[base + 1], C, ws.dB, C, N, C, C), ws.h[k], C, s_conv);
     CK(g.run(), "gcn projection gradients");
@@ -568,13 +588,13 @@ static int rgt_run(const camo_rg_dims_t* dims, int32_t num_classes, const float*
 
   // ---- conv1 (GAT) backward ----
   if (int e = bn_backward(0, CAMO_RG_BN1, G[CAMO_RGT_BN1_W], G[CAMO_RGT_BN1_B], G[CAMO_RGT_C1_BIAS])) return e;
-  CK(launch_rgt_gat_backward_a(ws.dB, ws.Hh, ws.O, ws.a_src, ws.a_dst, ws.m, ws.S, rowptr, col, ws.r, ws.da_dst, N, K, C, st), "gat backward A");
+  CK(launch_rgt_gat_backward_a(ws.dB, ws.Hh, ws.O, ws.a_src, ws.a_dst, ws.m, ws.S, c.rowptr, c.col, ws.r, ws.da_dst, N, K, C, st), "gat backward A");
   CK(launch_rgt_gat_backward_b(ws.dB, ws.Hh, ws.a_src, ws.a_dst, ws.m, ws.S, ws.r, ws.da_dst, P[CAMO_RG_C1_ATT_SRC], P[CAMO_RG_C1_ATT_DST],
-                               rrowptr, rcol, ws.da_src, ws.dh, N, K, C, st), "gat backward B");
+                               c.rrowptr, c.rcol, ws.da_src, ws.dh, N, K, C, st), "gat backward B");
   CK(launch_rgt_att_partial(ws.da_src, ws.da_dst, ws.Hh, N, K, C, ws.partial, st), "attention vector sums");
   CK(launch_rgt_colsum_finish(ws.partial, nb, 2 * K * C, RgtSegs{{G[CAMO_RGT_C1_ATT_SRC], G[CAMO_RGT_C1_ATT_DST], nullptr, nullptr},
                                                                  {0, K * C, 2 * K * C, 0, 0}, 2}, st), "attention vector sums");
-  g.add(ws.dh, K * C, x, In, G[CAMO_RGT_C1_W], In, K * C, In, N, KM);
+  g.add(ws.dh, K * C, c.x, In, G[CAMO_RGT_C1_W], In, K * C, In, N, KM);
   CK(g.run(), "gat projection gradient");
   return 0;
 }
@@ -584,14 +604,14 @@ int camo_rg_loss_backward(const camo_rg_dims_t* dims, int32_t num_classes, const
                           const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
                           const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
                           float* loss, float* const* grads, void* stream) {
-  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
-                 w_edge, workspace, workspace_bytes, loss, grads, stream, nullptr);
+  const RgtCall c{dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                  w_edge, workspace, workspace_bytes, loss, grads, stream};
+  return rgt_run(c, nullptr, nullptr, nullptr);
 }
 
 // ---- The same with batch-statistics batch norm (include/camo_rg_train_bn.h) --------------------------------------
 size_t camo_rg_train_bn_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E) {
-  if (rgtbn_check(dims, num_classes, N, E)) return 0;
-  return rgt_carve(*dims, num_classes, N, nullptr, true).bytes;
+  return rgt_workspace_bytes(dims, num_classes, N, E, true);
 }
 
 int camo_rg_loss_backward_bn(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
@@ -599,9 +619,10 @@ int camo_rg_loss_backward_bn(const camo_rg_dims_t* dims, int32_t num_classes, co
                              const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
                              const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
                              float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats, void* stream) {
+  const RgtCall c{dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                  w_edge, workspace, workspace_bytes, loss, grads, stream};
   RgBatchNorm batch{nullptr, nullptr, running, momentum, batch_stats};
-  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
-                 w_edge, workspace, workspace_bytes, loss, grads, stream, &batch);
+  return rgt_run(c, &batch, nullptr, nullptr);
 }
 
 // ---- The same with dropout, in either batch-norm mode (include/camo_rg_train_drop.h) ----------------------------------
@@ -609,29 +630,23 @@ static_assert(CAMO_RGT_SITE_CONV0 == SITE_RGT_CONV0 && CAMO_RGT_SITE_SHARED == S
               SITE_RGT_CONV0 > SITE_LATE0 + 1 && SITE_RGT_CONV0 + 4 == SITE_RGT_SHARED, "the header states common.h's site numbers; the fusion sites end at 11");
 
 size_t camo_rg_train_drop_workspace_bytes(const camo_rg_dims_t* dims, int32_t num_classes, int32_t N, int32_t E, int32_t batch_stats) {
-  return batch_stats ? camo_rg_train_bn_workspace_bytes(dims, num_classes, N, E) : camo_rg_train_workspace_bytes(dims, num_classes, N, E);
+  return rgt_workspace_bytes(dims, num_classes, N, E, batch_stats != 0);
 }
 
 // camo_rg_loss_backward_drop, and camo_rg_loss_backward_pixel (include/camo_rg_pixel_loss.h) once it has checked its own arguments
-static int rgt_run_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
-                        const float* x, const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* rrowptr,
-                        const int32_t* rcol, const float* rw, int32_t N, int32_t E, const int32_t* mask_t, const int32_t* inst_t,
-                        const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
-                        float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
-                        int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream,
-                        const RgPixel* pixel) {
+static int rgt_run_drop(const RgtCall& c, float momentum, float* const* running, float* batch_stats, int32_t batch_stats_mode, float p_conv,
+                        float p_shared, float p_head, uint64_t seed, const RgPixel* pixel) {
   if (batch_stats_mode != 0 && batch_stats_mode != 1) return fail(CAMO_E_ARG, "batch_stats_mode must be 0 (frozen statistics) or 1 (batch statistics)");
   for (float p : {p_conv, p_shared, p_head})
     if (!std::isfinite(p) || !(p >= 0.f && p < 1.f)) return fail(CAMO_E_ARG, "dropout rates must be finite and in [0, 1)");
   if (batch_stats_mode == 0 && (running || batch_stats))
     return fail(CAMO_E_ARG, "running and batch_stats must be null in batch_stats_mode 0 (frozen statistics)");
-  if (dims && N >= 1 && dims->hidden >= 2 && (long long)N * (3 * (dims->hidden / 2)) >= (1ll << 32))
+  if (c.dims && c.N >= 1 && c.dims->hidden >= 2 && (long long)c.N * (3 * (c.dims->hidden / 2)) >= (1ll << 32))
     return fail(CAMO_E_UNSUPPORTED, "N * (3 hidden / 2) must be < 2^32 (32-bit dropout element indices)");
   RgBatchNorm batch{nullptr, nullptr, running, momentum, batch_stats};
   const RgDropout drop{make_drop(1, p_conv, seed), make_drop(1, p_shared, seed), make_drop(1, p_head, seed)};
   const bool any = p_conv > 0.f || p_shared > 0.f || p_head > 0.f;      // all zero: the mode's existing entry, launch for launch
-  return rgt_run(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
-                 w_edge, workspace, workspace_bytes, loss, grads, stream, batch_stats_mode ? &batch : nullptr, any ? &drop : nullptr, pixel);
+  return rgt_run(c, batch_stats_mode ? &batch : nullptr, any ? &drop : nullptr, pixel);
 }
 
 int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, const float* const* params, const float* const* head_params,
@@ -640,9 +655,9 @@ int camo_rg_loss_backward_drop(const camo_rg_dims_t* dims, int32_t num_classes, 
                                const float* edge_t, float w_mask, float w_instance, float w_edge, void* workspace, size_t workspace_bytes,
                                float* loss, float* const* grads, float momentum, float* const* running, float* batch_stats,
                                int32_t batch_stats_mode, float p_conv, float p_shared, float p_head, uint64_t seed, void* stream) {
-  return rgt_run_drop(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask,
-                      w_instance, w_edge, workspace, workspace_bytes, loss, grads, momentum, running, batch_stats, batch_stats_mode, p_conv,
-                      p_shared, p_head, seed, stream, nullptr);
+  const RgtCall c{dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                  w_edge, workspace, workspace_bytes, loss, grads, stream};
+  return rgt_run_drop(c, momentum, running, batch_stats, batch_stats_mode, p_conv, p_shared, p_head, seed, nullptr);
 }
 
 // ---- The same with the structure loss on the painted mask (include/camo_rg_pixel_loss.h) -----------------------------
@@ -663,9 +678,9 @@ int camo_rg_loss_backward_pixel(const camo_rg_dims_t* dims, int32_t num_classes,
   if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
   static_assert(sizeof(long long) == sizeof(int64_t), "node_w is int64");
   const RgPixel pixel{reinterpret_cast<const long long*>(node_w), node_off, n_images, radius, w_pixel};
-  return rgt_run_drop(dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask,
-                      w_instance, w_edge, workspace, workspace_bytes, loss, grads, momentum, running, batch_stats, batch_stats_mode, p_conv,
-                      p_shared, p_head, seed, stream, &pixel);
+  const RgtCall c{dims, num_classes, params, head_params, x, rowptr, col, w, rrowptr, rcol, rw, N, E, mask_t, inst_t, edge_t, w_mask, w_instance,
+                  w_edge, workspace, workspace_bytes, loss, grads, stream};
+  return rgt_run_drop(c, momentum, running, batch_stats, batch_stats_mode, p_conv, p_shared, p_head, seed, &pixel);
 }
 
 // ---- Node targets from ground-truth masks (include/camo_rg_targets.h) ------------------------------------------
@@ -675,19 +690,10 @@ int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, con
                          const uint8_t* gt_instance, const uint8_t* gt_edge, int32_t N, int32_t H, int32_t W, int32_t label_bound,
                          int32_t n_nodes, int32_t band_permille, int32_t edge_min_pixels, int32_t* counts, int32_t* mask_t,
                          int32_t* inst_t, float* edge_t, void* stream) {
-  if (N < 1) return fail(CAMO_E_ARG, "N must be >= 1");
-  if (H < 1) return fail(CAMO_E_ARG, "H must be >= 1");
-  if (W < 1) return fail(CAMO_E_ARG, "W must be >= 1");
-  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, CAMO_RG_MAX_LABELS]");
-  if (n_nodes < 1) return fail(CAMO_E_ARG, "n_nodes must be >= 1");
-  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS");
-  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGB_MAX_PIXELS");
+  if (int e = rg_maps_sizes(N, H, W, label_bound, n_nodes)) return e;
   if (band_permille < 0 || band_permille >= 500) return fail(CAMO_E_ARG, "band_permille must be in [0, 500)");
   if (edge_min_pixels < 1) return fail(CAMO_E_ARG, "edge_min_pixels must be >= 1");
-  if (!segments) return fail(CAMO_E_ARG, "segments is null");
-  if (!region_map) return fail(CAMO_E_ARG, "region_map is null");
-  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
-  if (!gt_mask) return fail(CAMO_E_ARG, "gt_mask is null");
+  if (int e = rg_maps_pointers(segments, region_map, node_off, gt_mask)) return e;
   if (!counts) return fail(CAMO_E_ARG, "counts is null");
   if (!mask_t) return fail(CAMO_E_ARG, "mask_t is null");
   if (!inst_t) return fail(CAMO_E_ARG, "inst_t is null");
@@ -701,19 +707,10 @@ int camo_rg_node_targets(const int32_t* segments, const int32_t* region_map, con
 int camo_rg_pixel_weights(const int32_t* segments, const int32_t* region_map, const int32_t* node_off, const uint8_t* gt_mask, int32_t N,
                           int32_t H, int32_t W, int32_t label_bound, int32_t n_nodes, int32_t radius, int32_t gain, int64_t* node_w,
                           void* stream) {
-  if (N < 1) return fail(CAMO_E_ARG, "N must be >= 1");
-  if (H < 1) return fail(CAMO_E_ARG, "H must be >= 1");
-  if (W < 1) return fail(CAMO_E_ARG, "W must be >= 1");
-  if (label_bound < 1 || label_bound > CAMO_RG_MAX_LABELS) return fail(CAMO_E_ARG, "label_bound must be in [1, CAMO_RG_MAX_LABELS]");
-  if (n_nodes < 1) return fail(CAMO_E_ARG, "n_nodes must be >= 1");
-  if ((long long)H * W > CAMO_RGB_MAX_IMAGE_PIXELS) return fail(CAMO_E_ARG, "H * W exceeds CAMO_RGB_MAX_IMAGE_PIXELS");
-  if ((long long)N * H * W > CAMO_RGB_MAX_PIXELS) return fail(CAMO_E_ARG, "N * H * W exceeds CAMO_RGB_MAX_PIXELS");
+  if (int e = rg_maps_sizes(N, H, W, label_bound, n_nodes)) return e;
   if (radius < 0 || radius > CAMO_RGPL_MAX_RADIUS) return fail(CAMO_E_ARG, "radius must be in [0, CAMO_RGPL_MAX_RADIUS]");
   if (gain < 0 || gain > CAMO_RGPL_MAX_GAIN) return fail(CAMO_E_ARG, "gain must be in [0, CAMO_RGPL_MAX_GAIN]");
-  if (!segments) return fail(CAMO_E_ARG, "segments is null");
-  if (!region_map) return fail(CAMO_E_ARG, "region_map is null");
-  if (!node_off) return fail(CAMO_E_ARG, "node_off is null");
-  if (!gt_mask) return fail(CAMO_E_ARG, "gt_mask is null");
+  if (int e = rg_maps_pointers(segments, region_map, node_off, gt_mask)) return e;
   if (!node_w) return fail(CAMO_E_ARG, "node_w is null");
   CK(launch_rg_pixel_weights(segments, region_map, node_off, gt_mask, N, H, W, label_bound, n_nodes, radius, gain,
                              reinterpret_cast<long long*>(node_w), static_cast<hipStream_t>(stream)), "rg pixel weights");

@@ -367,6 +367,22 @@ class _GCNParams(nn.Module):
         nn.init.xavier_uniform_(self.lin.weight)
 
 
+PIECE = 64      # floats: every parameter starts on a 256-byte boundary of a flat buffer
+
+
+def flat_layout(shapes):
+    """The flat layout of tensors of ``shapes`` in order: ([(offset, numel), ...], total floats).  Every piece is rounded up to 64
+    floats -- the layout ``RegionGraphGNN.loss_and_gradients_csr`` gives its gradients."""
+    pieces, at = [], 0
+    for shape in shapes:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        pieces.append((at, n))
+        at += -(-n // PIECE) * PIECE
+    return pieces, at
+
+
 def loss_figures(loss):
     """The 0-d views of the loss a training call returns: [4], or [6] with the pixel term (include/camo_rg_pixel_loss.h)."""
     out = {"loss": loss[0], "mask_loss": loss[1], "instance_loss": loss[2], "edge_loss": loss[3]}
@@ -529,6 +545,17 @@ class RegionGraphGNN(nn.Module):
             raise ValueError(f"every dropout rate must be finite and in [0, 1), got {dropout!r}")
         return rates if any(v > 0.0 for v in rates) else None
 
+    @staticmethod
+    def _training_entry(batch_stats, rates, pixel):
+        """The library entry ``loss_and_gradients_csr`` calls: ``rates`` as ``_dropout_rates`` returns them, ``pixel`` its argument.
+        Each entry takes the arguments of the one before it and more; at neutral extras they give the same bytes, so only this
+        function says which one runs."""
+        if pixel is not None:
+            return "camo_rg_loss_backward_pixel"                                # (with zero rates when there is no dropout)
+        if rates is not None:
+            return "camo_rg_loss_backward_drop"
+        return "camo_rg_loss_backward_bn" if batch_stats else "camo_rg_loss_backward"
+
     @torch.no_grad()
     def loss_and_gradients_csr(self, x, csr, reversed_csr, mask_target, instance_target, edge_target, loss_weights=(1., 1., 1.), out=None,
                                batch_stats=False, update_running=True, stats_out=None, dropout=None, seed=0, pixel=None):
@@ -618,7 +645,7 @@ class RegionGraphGNN(nn.Module):
         ws = _workspace("camo_rg_train_bn_workspace_bytes" if batch_stats else "camo_rg_train_workspace_bytes", C.byref(self._dims),
                         self.num_classes, n, E, device=dev)
         params = self.trainable_parameters()
-        total = sum(-(-p.numel() // 64) * 64 for p in params)                                                # (256-byte aligned pieces)
+        pieces, total = flat_layout([p.shape for p in params])
         if out is None:
             flat = torch.empty(total, dtype=torch.float32, device=dev)
         else:
@@ -626,58 +653,29 @@ class RegionGraphGNN(nn.Module):
             if out.dtype != torch.float32 or out.dim() != 1 or out.numel() != total or not out.is_contiguous() or out.device != dev:
                 raise RuntimeError(f"out must be a contiguous fp32 buffer of {total} floats on {dev}")
             flat = out
-        grads, at = [], 0
-        for p in params:
-            grads.append(flat[at:at + p.numel()].view(p.shape))
-            at += -(-p.numel() // 64) * 64
+        grads = [flat[at:at + k].view(p.shape) for (at, k), p in zip(pieces, params)]
         loss = torch.empty(4 if pixel is None else 6, dtype=torch.float32, device=dev)
         tab, keep = self._param_table()
         htab, hkeep = self._head_table()
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        # what every entry takes (and the stream, which goes last); then the batch-norm tail; then the dropout and pixel entries' own
+        common = (C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w), _ptr(rrowptr), _ptr(rcol),
+                  _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab)
+        name = self._training_entry(batch_stats, rates, pixel)
+        tail = ()
+        if name != "camo_rg_loss_backward":
+            tail = (momentum, rtab, None if stats_out is None else _ptr(stats_out)) if batch_stats else (0.0, None, None)
+        if name in ("camo_rg_loss_backward_drop", "camo_rg_loss_backward_pixel"):
+            tail += (1 if batch_stats else 0, *(rates or (0.0, 0.0, 0.0)), seed)
+        if name == "camo_rg_loss_backward_pixel":
+            tail += (_ptr(node_w), _ptr(node_off), node_off.numel() - 1, radius, w_pixel)
         with torch.cuda.device(dev):
-            if pixel is not None:
-                pc, ps, ph = rates if rates is not None else (0.0, 0.0, 0.0)
-                rc = _lib.lib().camo_rg_loss_backward_pixel(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
-                                                            _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
-                                                            _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab,
-                                                            momentum if batch_stats else 0.0, rtab if batch_stats else None,
-                                                            None if stats_out is None or not batch_stats else _ptr(stats_out),
-                                                            1 if batch_stats else 0, pc, ps, ph, seed, _ptr(node_w), _ptr(node_off),
-                                                            node_off.numel() - 1, radius, w_pixel, _stream_ptr(dev))
-                _lib.check(rc, "camo_rg_loss_backward_pixel")
-                if batch_stats and update_running:
-                    for bn in self._batch_norms():
-                        if bn.num_batches_tracked is not None:
-                            bn.num_batches_tracked.add_(1)
-                return loss, grads
-            if rates is not None:
-                rc = _lib.lib().camo_rg_loss_backward_drop(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
-                                                           _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
-                                                           _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab,
-                                                           momentum if batch_stats else 0.0, rtab if batch_stats else None,
-                                                           None if stats_out is None or not batch_stats else _ptr(stats_out),
-                                                           1 if batch_stats else 0, rates[0], rates[1], rates[2], seed, _stream_ptr(dev))
-                _lib.check(rc, "camo_rg_loss_backward_drop")
-                if batch_stats and update_running:
-                    for bn in self._batch_norms():
-                        if bn.num_batches_tracked is not None:
-                            bn.num_batches_tracked.add_(1)
-                return loss, grads
-            if batch_stats:
-                rc = _lib.lib().camo_rg_loss_backward_bn(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col),
-                                                         _ptr(w), _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]),
-                                                         _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab, momentum, rtab,
-                                                         None if stats_out is None else _ptr(stats_out), _stream_ptr(dev))
-                _lib.check(rc, "camo_rg_loss_backward_bn")
-                if update_running:
-                    for bn in self._batch_norms():
-                        if bn.num_batches_tracked is not None:
-                            bn.num_batches_tracked.add_(1)
-                return loss, grads
-            rc = _lib.lib().camo_rg_loss_backward(C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w),
-                                                  _ptr(rrowptr), _ptr(rcol), _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi,
-                                                  we, _ptr(ws), ws.numel(), _ptr(loss), gtab, _stream_ptr(dev))
-        _lib.check(rc, "camo_rg_loss_backward")
+            rc = getattr(_lib.lib(), name)(*common, *tail, _stream_ptr(dev))
+        _lib.check(rc, name)
+        if batch_stats and update_running:
+            for bn in self._batch_norms():
+                if bn.num_batches_tracked is not None:
+                    bn.num_batches_tracked.add_(1)
         return loss, grads
 
     @torch.no_grad()

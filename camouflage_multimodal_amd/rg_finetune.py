@@ -16,26 +16,11 @@ import torch
 from . import _lib
 from .engine import _on, _ptr, _stream_ptr
 from .optim import AdamWStateMixin
-from .region_graph import (_as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments, loss_figures,
-                           slic_label_bound, slic_segments)
+from .region_graph import (PIECE, _as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments,  # noqa: F401
+                           flat_layout, loss_figures, slic_label_bound, slic_segments)
 from .pipeline import detect_camouflage_batch, detect_camouflage_ragged
 from .resize import _mask_list, _packed, _ragged, resize_batch
 from .rg_detect import _offsets_tensor
-
-PIECE = 64      # floats: every parameter starts on a 256-byte boundary of the flat buffers, as in loss_and_gradients_csr
-
-
-def flat_layout(shapes):
-    """The flat layout of tensors of ``shapes`` in order: ([(offset, numel), ...], total floats).  Every piece is rounded up to 64
-    floats -- the layout ``RegionGraphGNN.loss_and_gradients_csr`` gives its gradients."""
-    pieces, at = [], 0
-    for shape in shapes:
-        n = 1
-        for d in shape:
-            n *= int(d)
-        pieces.append((at, n))
-        at += -(-n // PIECE) * PIECE
-    return pieces, at
 
 
 def _mask_bytes(mask, name, shape, dev):

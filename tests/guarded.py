@@ -1,5 +1,5 @@
 """Buffers between guard bands, for tests that call the C entry points directly (a helper module, not a conftest): the only guard
-implementation for the image and region-graph pipeline.  tests/raw_calls.py runs every raw call on it; tests/test_guarded.py holds it,
+implementation for the image and region-graph pipeline.  tests/raw_calls.py runs every raw call on it, tests/rg_train_calls.py the training call; tests/test_guarded.py holds it,
 on CPU tensors, to seeing a byte written on either side of a piece.
 
 A kernel that writes a few elements past an extent lands in whatever the allocator put next, unseen.  Here every buffer is a piece

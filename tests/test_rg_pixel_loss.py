@@ -13,10 +13,9 @@ entries' argument checks to the header.  On the GPU
     e32 being the same error of torch-CPU float32 autograd of the NODE form, computed in the same test.  The graphs, parameters and
     seeds are those of tests/test_rg_train.py's cases "real", "batch", "many" and "saturated" (and of tests/test_rg_train_drop.py's
     "real" for batch statistics and dropout): their flip-clear margins depend on neither targets nor loss, and are asserted on the
-    reference again.  The label maps are synthetic, 33 x 70 or smaller.  The library is called directly, its workspace and its 33
-    outputs between guard bands.
+    reference again.  The label maps are synthetic, 33 x 70 or smaller.  The library is called directly (tests/rg_train_calls.py), its
+    workspace and its 33 outputs between guard bands.
 """
-import ctypes
 import functools
 import os
 
@@ -33,9 +32,9 @@ import test_rg_targets as TT
 import test_rg_train as T0
 import test_rg_train_drop as TD
 from conftest import ROOT
-from guarded import guarded as _guarded, guards_intact as _guards_intact
 from oracle import rg_features_oracle as FO
 from raw_calls import Call, execute
+from rg_train_calls import direct, refuse
 from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _model, _targets
 
 E_ARG, E_UNSUPPORTED = -1, -2
@@ -216,28 +215,18 @@ def test_argument_checks_of_the_weights_entry_match_the_header():
 
 
 def test_argument_checks_of_the_loss_entry_match_the_header():
-    from camouflage_multimodal_amd import _lib
-    L = _lib.lib()
-    fake = 0x1000
-    tabs = [(ctypes.c_void_p * n)(*([fake] * n)) for n in (28, 12, 32)]
-
-    def call(nc=2, n_images=1, radius=15, w_pixel=1.0, node_w=fake, node_off=fake, ws_bytes=None, x=fake, mode=0, p_conv=0.0):
-        d = _lib.CamoRgDims(15, 32, 2)
-        need = L.camo_rg_train_drop_workspace_bytes(ctypes.byref(d), nc, 23, 100, mode)
-        rc = L.camo_rg_loss_backward_pixel(ctypes.byref(d), nc, tabs[0], tabs[1], x, fake, fake, fake, fake, fake, fake, 23, 100, fake, fake, fake,
-                                           1.0, 1.0, 1.0, fake, need if ws_bytes is None else ws_bytes, fake, tabs[2], 0.1, None, None, mode,
-                                           p_conv, 0.0, 0.0, 0, node_w, node_off, n_images, radius, w_pixel, None)
-        return rc, L.camo_last_error()
+    def call(**kw):                                  # fake pointers: every check runs on the host before any launch
+        return refuse("camo_rg_loss_backward_pixel", hidden=32, heads=2, **kw)[:2]
 
     rc, msg = call(nc=3)
     assert rc == E_UNSUPPORTED and b"num_classes == 2" in msg
     for kw, word in ((dict(n_images=0), b"n_images"), (dict(radius=-1), b"radius"), (dict(radius=32), b"radius"), (dict(w_pixel=-0.5), b"w_pixel"),
-                     (dict(w_pixel=float("inf")), b"w_pixel"), (dict(w_pixel=float("nan")), b"w_pixel"), (dict(node_w=None), b"node_w"),
-                     (dict(node_off=None), b"node_off")):
+                     (dict(w_pixel=float("inf")), b"w_pixel"), (dict(w_pixel=float("nan")), b"w_pixel"), (dict(null="node_w"), b"node_w"),
+                     (dict(null="node_off"), b"node_off")):
         rc, msg = call(**kw)
         assert rc == E_ARG and word in msg, (kw, rc, msg)
     # what camo_rg_loss_backward_drop refuses is refused as it refuses it
-    assert call(ws_bytes=1024)[0] == -3 and call(x=None)[0] == E_ARG and call(mode=2)[0] == E_ARG and call(p_conv=1.0)[0] == E_ARG
+    assert call(ws_bytes=1024)[0] == -3 and call(null="x")[0] == E_ARG and call(mode=2)[0] == E_ARG and call(rates=(1.0, 0.0, 0.0))[0] == E_ARG
 
 
 def test_cpu_tensors_and_bad_options_raise():
@@ -423,43 +412,17 @@ def _loss_case(name, w_pixel, weights=(1.0, 1.0, 1.0), maps=None, drop_key=None)
 
 
 def _direct(m, c, d, pair, w_pixel=None, node_w=None, node_off=None, entry="pixel"):
-    """camo_rg_loss_backward_pixel (or _drop: `entry`) called directly on a workspace of exactly camo_rg_train_drop_workspace_bytes and
-    on 33 outputs of exactly their sizes, each between guard bands and filled with a sentinel (0xFF: a NaN in every float): the guards
-    are checked and every output element must have been written.  Returns (loss, the 32 gradients, batch_stats or None)."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
-    csr, rcsr = pair
-    t = _targets(c)
-    mode, rates = c.get("mode", 0), c.get("rates", (0.0, 0.0, 0.0))
-    L, n, E, C = _lib.lib(), c["n"], csr[1].shape[0], c["hidden"]
-    need = L.camo_rg_train_drop_workspace_bytes(ctypes.byref(m._dims), c["nc"], n, E, mode)
-    assert need > 0
-    figures = 6 if entry == "pixel" else 4
-    sizes = [p.numel() for p in m.trainable_parameters()] + [figures] + ([4 * 2 * C] if mode else [])
-    pairs = [_guarded(need, 0xA5)] + [_guarded(4 * k, 0xFF) for k in sizes]
-    ws, outs = pairs[0][1], [piece.view(torch.float32) for _, piece in pairs[1:]]
-    running = [m.state_dict()[k] for k in TD.STAT_NAMES] if mode else None
-    tab, keep = m._param_table()
-    htab, hkeep = m._head_table()
-    gtab = (ctypes.c_void_p * 32)(*[o.data_ptr() for o in outs[:32]])
-    rtab = (ctypes.c_void_p * 8)(*[r.data_ptr() for r in running]) if mode else None
-    x = d.x.contiguous()
-    wm, wi, we = c.get("weights", (1.0, 1.0, 1.0))
-    head = (ctypes.byref(m._dims), c["nc"], tab, htab, _ptr(x), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]), _ptr(rcsr[0]), _ptr(rcsr[1]), _ptr(rcsr[2]),
-            n, E, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), wm, wi, we, _ptr(ws), need, _ptr(outs[32]), gtab, BR.MOMENTUM if mode else 0.0, rtab,
-            _ptr(outs[33]) if mode else None, mode, rates[0], rates[1], rates[2], c.get("seed", 0))
+    """camo_rg_loss_backward_pixel (or _drop: `entry`) called directly through rg_train_calls.direct, which checks the guards round the
+    workspace and every output and that every output element was written.  Returns (loss, the 32 gradients, batch_stats or None, the
+    eight running statistics the call updated or None); the model's own are not touched."""
+    own = None
     if entry == "pixel":
         nw = torch.from_numpy(np.array(c["node_w"] if node_w is None else node_w)).cuda()
         no = torch.from_numpy(np.array(c["maps"][2] if node_off is None else node_off, np.int32)).cuda()
-        _lib.check(L.camo_rg_loss_backward_pixel(*head, _ptr(nw), _ptr(no), no.numel() - 1, PR.RADIUS, c["w_pixel"] if w_pixel is None else w_pixel,
-                                                 _stream_ptr()), "camo_rg_loss_backward_pixel")
-    else:
-        _lib.check(L.camo_rg_loss_backward_drop(*head, _stream_ptr()), "camo_rg_loss_backward_drop")
-    torch.cuda.synchronize()
-    for k, ((whole, piece), fill) in zip(["workspace"] + NAMES + ["loss", "batch_stats"], zip(pairs, [0xA5] + [0xFF] * 34)):
-        assert _guards_intact(whole, piece, fill), k
-    assert all(bool(torch.isfinite(o).all()) for o in outs), "an output element was not written"
-    return outs[32], [o.view(p.shape) for o, p in zip(outs[:32], m.trainable_parameters())], outs[33].view(4, 2, C) if mode else None
+        own = (nw, no, PR.RADIUS, c["w_pixel"] if w_pixel is None else w_pixel)
+    got = direct("camo_rg_loss_backward_" + entry, m, d.x, pair, _targets(c), weights=c.get("weights", (1.0, 1.0, 1.0)), mode=c.get("mode", 0),
+                 rates=c.get("rates", (0.0, 0.0, 0.0)), seed=c.get("seed", 0), momentum=BR.MOMENTUM, pixel=own)
+    return got.loss, got.grads, got.bs, got.run
 
 
 def _hold(c, loss6, grads, tag, skip=()):
@@ -484,12 +447,12 @@ def _run_case(c, tag, **kw):
     assert c["margin"] > TR.FLIP_MARGIN                                # on the CPU reference, before the device is looked at
     m, d = _model(c).train(), _data(c)
     pair = _csr_pair(c, d)             # ONE pair for a test: the device builder leaves a row's edges in no particular order
-    loss, grads, bs = _direct(m, c, d, pair, **kw)
+    loss, grads, bs, run = _direct(m, c, d, pair, **kw)
     loss6 = loss.cpu().numpy().tolist()
     _hold(c, loss6, [g.cpu().numpy() for g in grads], tag, skip=TD.BIAS_NAMES if c["mode"] else ())
     assert abs(c["l64"][0] - (c["weights"][0] * c["l64"][1] + c["weights"][1] * c["l64"][2] + c["weights"][2] * c["l64"][3]
                               + c["w_pixel"] * (c["l64"][4] + c["l64"][5]))) <= 1e-12
-    return m, d, pair, loss, grads, bs
+    return m, d, pair, loss, grads, bs, run
 
 
 @pytest.mark.gpu
@@ -506,7 +469,7 @@ def test_an_image_may_be_empty_and_offsets_are_clamped():
     kernel clamps: the bytes of the call on the clamped offsets."""
     c = _loss_case("many", 1.0, maps="many51")
     assert len(c["maps"][2]) == 52 and 0 in np.diff(c["maps"][2])
-    m, d, pair, loss, grads, _ = _run_case(c, "many as 51 images")
+    m, d, pair, loss, grads, _, _ = _run_case(c, "many as 51 images")
     wild = _direct(m, c, d, pair, node_off=[-7, 24, 4000, 30])
     tame = _direct(m, c, d, pair, node_off=[0, 24, 1049, 1049])
     assert np.array_equal(_bits(wild[0].cpu()), _bits(tame[0].cpu())) and all(TD._same(a, b) for a, b in zip(wild[1], tame[1]))
@@ -541,14 +504,13 @@ def test_zero_weight_is_the_existing_entry_byte_for_byte_and_two_calls_agree(nam
 @pytest.mark.parametrize("key", [(1, (0.0, 0.0, 0.0), 0), (0, TD.ALL, TD.CONFIGS[("real", 0, TD.ALL)])], ids=["batch-statistics", "dropout"])
 def test_batch_statistics_and_dropout_take_the_pixel_term_and_nothing_else_changes(key):
     c = _loss_case("real", 1.0, maps="real", drop_key=key)
-    m, d, pair, loss, grads, bs = _run_case(c, "batch statistics" if key[0] else "dropout")
-    other = _model(c).train()
-    old = _direct(other, c, d, pair, entry="drop")
+    m, d, pair, loss, grads, bs, run = _run_case(c, "batch statistics" if key[0] else "dropout")
+    old = _direct(_model(c).train(), c, d, pair, entry="drop")
     assert TD._same(loss[1:4], old[0][1:4])                            # the three existing terms
     if key[0]:                                                         # the batch statistics and the running statistics updated as without it
         assert TD._same(bs, old[2])
-        for k in TD.STAT_NAMES:
-            assert TD._same(m.state_dict()[k], other.state_dict()[k]) and not np.array_equal(_bits(m.state_dict()[k].cpu()), _bits(c["p"][k])), k
+        for k, a, b in zip(TD.STAT_NAMES, run, old[3]):
+            assert TD._same(a, b) and not np.array_equal(_bits(a.cpu()), _bits(c["p"][k])), k
 
 
 @pytest.mark.gpu

@@ -37,14 +37,13 @@ import rg_train_bn_ref as BR
 import rg_train_ref as TR
 from conftest import ROOT
 from oracle import rg_gnn_oracle as RO
-from guarded import guarded as _guarded, guards_intact as _guards_intact
+from rg_train_calls import STAT_NAMES, direct, refuse        # (STAT_NAMES, the order of the `running` table: imported from here by others)
 from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _model, _targets
 
 BN_SIZES = (23, 2, 40)
 MANY_ORDER = (0, 1, 2) * 16 + (2, 1)
 OFFSET = 32.0                # "offset": at this value a float32 one-pass variance misses the bound (test_a_one_pass_variance_...)
 BIAS_NAMES = ("conv1.bias", "conv2.bias", "conv3.bias", "conv4.bias")
-STAT_NAMES = tuple(f"bn{k}.running_{s}" for k in (1, 2, 3, 4) for s in ("mean", "var"))       # the order of the `running` table
 
 # name: (graph kind, n, hidden, heads, classes, seed); flip margins on the float64 reference in the comments
 CASES = {
@@ -188,31 +187,9 @@ def test_argument_checks_match_the_header():
     """(e)"""
     from camouflage_multimodal_amd import _lib
     L = _lib.lib()
-    fake = 0x1000                                    # never dereferenced: every check runs on the host before any launch
-    tabs = [(ctypes.c_void_p * n)(*([fake] * n)) for n in (28, 12, 32, 8)]
-    running_slots = (6, 7, 12, 13, 18, 19, 24, 25)
 
-    def call(hidden=128, nc=2, N=23, E=100, ws_bytes=None, null=None, heads=4, momentum=0.1, running=True, table_null=None, stats=True):
-        d = _lib.CamoRgDims(15, hidden, heads)
-        need = L.camo_rg_train_bn_workspace_bytes(ctypes.byref(d), nc, N, E)
-        ptr = {k: fake for k in ("x", "rowptr", "col", "w", "rrowptr", "rcol", "rw", "mt", "it", "et", "ws", "loss")}
-        t = list(tabs)
-        if null in ptr:
-            ptr[null] = None
-        if null in ("params", "heads", "grads"):
-            t[("params", "heads", "grads").index(null)] = None
-        if table_null == "grads":
-            t[2] = (ctypes.c_void_p * 32)(*([fake] * 31 + [None]))
-        if table_null == "running":
-            t[3] = (ctypes.c_void_p * 8)(*([fake] * 7 + [None]))
-        if table_null == "running slots of params":
-            t[0] = (ctypes.c_void_p * 28)(*[None if i in running_slots else fake for i in range(28)])
-        if table_null == "params":
-            t[0] = (ctypes.c_void_p * 28)(*[None if i == 5 else fake for i in range(28)])
-        rc = L.camo_rg_loss_backward_bn(ctypes.byref(d), nc, t[0], t[1], ptr["x"], ptr["rowptr"], ptr["col"], ptr["w"], ptr["rrowptr"],
-                                        ptr["rcol"], ptr["rw"], N, E, ptr["mt"], ptr["it"], ptr["et"], 1.0, 1.0, 1.0, ptr["ws"],
-                                        need if ws_bytes is None else ws_bytes, ptr["loss"], t[2], momentum, t[3] if running else None,
-                                        fake if stats else None, None)
+    def call(running=True, stats=True, **kw):         # fake pointers: every check runs on the host before any launch
+        rc, _, need = refuse("camo_rg_loss_backward_bn", running=running, stats=stats, **kw)
         return rc, need
 
     E_ARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
@@ -469,43 +446,19 @@ def test_the_frozen_call_on_the_batch_statistics_gives_the_same_losses(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["many", "tail"])
 def test_the_library_writes_inside_its_workspace_and_its_output_buffers(name):
-    """camo_rg_loss_backward_bn called directly on a workspace of exactly camo_rg_train_bn_workspace_bytes and on 32 gradient buffers,
+    """camo_rg_loss_backward_bn called directly (tests/rg_train_calls.py) on a workspace of exactly camo_rg_train_bn_workspace_bytes and on 32 gradient buffers,
     loss, batch_stats and the 8 running buffers of exactly their sizes, each between two 4 KiB bands of a sentinel: no guard byte
     changes, every output element is written (the outputs start as NaN; the running buffers start as the model's), and the bytes are
     the wrapper's."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
     c = _case(name)
     m, d, t = _model(c).train(), _data(c), _targets(c)
-    csr, rcsr = _csr_pair(c, d)
+    pair = _csr_pair(c, d)
     other = copy.deepcopy(m)
-    want_loss, want, want_bs = _call(other, c, d, (csr, rcsr))
+    want_loss, want, want_bs = _call(other, c, d, pair)
     want_run = [other.state_dict()[k] for k in STAT_NAMES]
-    L, n, E, C = _lib.lib(), c["n"], csr[1].shape[0], c["hidden"]
-    need = L.camo_rg_train_bn_workspace_bytes(ctypes.byref(m._dims), c["nc"], n, E)
-    assert need > 0
-    ws_whole, ws = _guarded(need, 0xA5)
-    outs = [_guarded(4 * k, 0xFF) for k in [p.numel() for p in m.trainable_parameters()] + [4, 4 * 2 * C]]
-    assert all(bool(torch.isnan(piece.view(torch.float32)).all()) for _, piece in outs)
-    runs = [_guarded(4 * C, 0xFF) for _ in STAT_NAMES]
-    for (_, piece), k in zip(runs, STAT_NAMES):
-        piece.view(torch.float32).copy_(m.state_dict()[k])
-    tab, keep = m._param_table()
-    htab, hkeep = m._head_table()
-    gtab = (ctypes.c_void_p * 32)(*[piece.data_ptr() for _, piece in outs[:32]])
-    rtab = (ctypes.c_void_p * 8)(*[piece.data_ptr() for _, piece in runs])
-    x = d.x.contiguous()
-    _lib.check(L.camo_rg_loss_backward_bn(ctypes.byref(m._dims), c["nc"], tab, htab, _ptr(x), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]),
-                                          _ptr(rcsr[0]), _ptr(rcsr[1]), _ptr(rcsr[2]), n, E, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), 1.0, 1.0, 1.0,
-                                          _ptr(ws), need, _ptr(outs[32][1]), gtab, m.bn1.momentum, rtab, _ptr(outs[33][1]), _stream_ptr()),
-               "camo_rg_loss_backward_bn")
-    torch.cuda.synchronize()
-    assert _guards_intact(ws_whole, ws, 0xA5), "workspace"
+    got = direct("camo_rg_loss_backward_bn", m, d.x, pair, t, momentum=m.bn1.momentum)       # (guards and "every element written": asserted there)
     refs = list(want) + [want_loss, want_bs] + want_run
-    for k, (whole, piece), ref in zip(NAMES + ["loss", "batch_stats"] + list(STAT_NAMES), outs + runs, refs):
-        assert _guards_intact(whole, piece, 0xFF), k
-        got = piece.view(torch.float32)
-        assert bool(torch.isfinite(got).all()), k
-        assert np.array_equal(_bits(got.cpu()), _bits(ref.reshape(-1).cpu())), k
+    for k, a, ref in zip(NAMES + ["loss", "batch_stats"] + list(STAT_NAMES), got.grads + [got.loss, got.bs] + got.run, refs):
+        assert np.array_equal(_bits(a.cpu()), _bits(ref.cpu())), k
     for k, v in m.state_dict().items():                       # the model whose tables were passed was not written: `running` was
         assert torch.equal(v.cpu(), torch.from_numpy(c["p"][k].copy())) if k in c["p"] else int(v) == 0, k

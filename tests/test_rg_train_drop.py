@@ -44,7 +44,7 @@ import rg_train_ref as TR
 from conftest import ROOT
 from oracle import rg_gnn_oracle as RO
 from oracle.fusion_oracle import dropout_keep
-from guarded import guarded as _guarded, guards_intact as _guards_intact
+from rg_train_calls import direct, refuse
 from test_rg_train import NAMES, _bits, _csr_pair, _data, _err, _model, _targets
 from test_rg_train_bn import BIAS_NAMES, LOSS_KEYS, STAT_NAMES, _graph, _running, _sizes
 
@@ -215,13 +215,9 @@ def test_header_symbols_sites_binding_and_abi_version():
 def test_argument_checks_match_the_header():
     from camouflage_multimodal_amd import _lib
     L = _lib.lib()
-    fake = 0x1000                                    # never dereferenced: every check runs on the host before any launch
-    tabs = [(ctypes.c_void_p * n)(*([fake] * n)) for n in (28, 12, 32, 8)]
 
-    def call(mode=1, rates=(0.1, 0.2, 0.3), hidden=128, N=23, E=100, ws_bytes=8, running=None, stats=None, momentum=0.1, heads=4):
-        d = _lib.CamoRgDims(15, hidden, heads)
-        return L.camo_rg_loss_backward_drop(ctypes.byref(d), 2, tabs[0], tabs[1], fake, fake, fake, fake, fake, fake, fake, N, E, fake, fake, fake,
-                                            1.0, 1.0, 1.0, fake, ws_bytes, fake, tabs[2], momentum, running, stats, mode, *rates, 7, None)
+    def call(mode=1, rates=(0.1, 0.2, 0.3), ws_bytes=8, **kw):       # fake pointers: every check runs on the host before any launch
+        return refuse("camo_rg_loss_backward_drop", mode=mode, rates=rates, ws_bytes=ws_bytes, seed=7, **kw)[0]
 
     E_ARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
     for mode in (0, 1):
@@ -233,10 +229,10 @@ def test_argument_checks_match_the_header():
                 assert call(mode, tuple(rates)) == E_ARG, (mode, bad, slot)
                 assert b"dropout rates" in L.camo_last_error()
         assert call(mode, (0.0, 0.0, 0.0)) == E_WORKSPACE and call(mode, (float(np.float32(1 - 2.0 ** -24)),) * 3) == E_WORKSPACE
-    assert call(0, running=tabs[3]) == E_ARG and b"must be null" in L.camo_last_error()
-    assert call(0, stats=fake) == E_ARG and b"must be null" in L.camo_last_error()
-    assert call(1, running=tabs[3], stats=fake) == E_WORKSPACE
-    assert call(1, running=tabs[3], momentum=0.0) == E_ARG and b"momentum" in L.camo_last_error()   # the mode's own checks follow
+    assert call(0, running=True) == E_ARG and b"must be null" in L.camo_last_error()
+    assert call(0, stats=True) == E_ARG and b"must be null" in L.camo_last_error()
+    assert call(1, running=True, stats=True) == E_WORKSPACE
+    assert call(1, running=True, momentum=0.0) == E_ARG and b"momentum" in L.camo_last_error()   # the mode's own checks follow
     assert call(2) == E_ARG and call(-1) == E_ARG and b"batch_stats_mode" in L.camo_last_error()
     assert call(1, N=1, E=1) == E_UNSUPPORTED and call(0, N=1, E=1) == E_WORKSPACE                   # N >= 2 is batch statistics' own
     assert call(0, hidden=127) == E_UNSUPPORTED and call(0, heads=9) == E_UNSUPPORTED
@@ -281,6 +277,21 @@ def test_bad_rates_and_cpu_tensors_raise_before_any_device_work():
         m.train()(data)                                                        # forward in training mode keeps raising
 
 
+def test_the_wrapper_picks_its_entry_by_batch_stats_rates_and_pixel():
+    """At neutral extras the four entries give the same bytes, so no GPU test sees a wrong choice: the rule is held here, on all eight
+    combinations, and composed with _dropout_rates, whose zeros must not reach the dropout entry."""
+    from camouflage_multimodal_amd import RegionGraphGNN
+    entry, rates_of = RegionGraphGNN._training_entry, RegionGraphGNN._dropout_rates
+    pixel = (None, [0, 23], 15, 1.0)                                          # (given or not: its fields are not looked at)
+    for bs in (False, True):
+        assert entry(bs, None, None) == ("camo_rg_loss_backward_bn" if bs else "camo_rg_loss_backward")
+        assert entry(bs, ALL, None) == "camo_rg_loss_backward_drop"
+        assert entry(bs, None, pixel) == entry(bs, ALL, pixel) == "camo_rg_loss_backward_pixel"
+        for zero in (None, 0, 0.0, (0, 0, 0)):
+            assert entry(bs, rates_of(zero), None) == entry(bs, None, None), zero
+        assert entry(bs, rates_of(0.3), None) == entry(bs, rates_of((0, 0, 0.5)), None) == "camo_rg_loss_backward_drop"
+
+
 @pytest.mark.parametrize("key", sorted(CONFIGS), ids=_key_id)
 def test_configurations_stay_clear_of_a_relu_flip(key):
     c = _case(key)
@@ -307,41 +318,10 @@ def test_the_configurations_are_the_issues():
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 
-def _direct(m, c, d, pair, mode, rates, seed, guarded=False, momentum=BR.MOMENTUM):
-    """camo_rg_loss_backward_drop called directly (the wrapper sends zero rates to the older entries).  Returns a dict: loss [4],
-    grads (32 tensors), bs [4, 2, C] and run (8 tensors) in mode 1, and with `guarded` the (whole, piece) pairs of every buffer."""
-    from camouflage_multimodal_amd import _lib
-    from camouflage_multimodal_amd.engine import _ptr, _stream_ptr
-    csr, rcsr = pair
-    t = _targets(c)
-    L, n, E, C = _lib.lib(), c["n"], csr[1].shape[0], c["hidden"]
-    need = L.camo_rg_train_drop_workspace_bytes(ctypes.byref(m._dims), c["nc"], n, E, mode)
-    assert need > 0
-    sizes = [p.numel() for p in m.trainable_parameters()] + [4] + ([4 * 2 * C] + [C] * 8 if mode else [])
-    if guarded:
-        pairs = [_guarded(need, 0xA5)] + [_guarded(4 * k, 0xFF) for k in sizes]
-        bufs = [piece for _, piece in pairs]
-    else:
-        pairs = None
-        bufs = [torch.empty(need, dtype=torch.uint8, device="cuda")] + [torch.full((4 * k,), 0xFF, dtype=torch.uint8, device="cuda") for k in sizes]
-    ws, outs = bufs[0], [b.view(torch.float32) for b in bufs[1:]]
-    assert all(bool(torch.isnan(o).all()) for o in outs)
-    if mode:
-        for o, k in zip(outs[34:], STAT_NAMES):
-            o.copy_(m.state_dict()[k])
-    tab, keep = m._param_table()
-    htab, hkeep = m._head_table()
-    gtab = (ctypes.c_void_p * 32)(*[o.data_ptr() for o in outs[:32]])
-    rtab = (ctypes.c_void_p * 8)(*[o.data_ptr() for o in outs[34:]]) if mode else None
-    x = d.x.contiguous()
-    _lib.check(L.camo_rg_loss_backward_drop(ctypes.byref(m._dims), c["nc"], tab, htab, _ptr(x), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]),
-                                            _ptr(rcsr[0]), _ptr(rcsr[1]), _ptr(rcsr[2]), n, E, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), 1.0, 1.0, 1.0,
-                                            _ptr(ws), need, _ptr(outs[32]), gtab, momentum if mode else 0.0, rtab,
-                                            _ptr(outs[33]) if mode else None, mode, rates[0], rates[1], rates[2], seed, _stream_ptr()),
-               "camo_rg_loss_backward_drop")
-    torch.cuda.synchronize()
-    return dict(loss=outs[32], grads=[o.view(p.shape) for o, p in zip(outs[:32], m.trainable_parameters())], bs=outs[33].view(4, 2, C) if mode else None,
-                run=outs[34:] if mode else None, pairs=pairs, need=need)
+def _direct(m, c, d, pair, mode, rates, seed):
+    """camo_rg_loss_backward_drop called directly (the wrapper sends zero rates to the older entries): rg_train_calls.direct's record,
+    every buffer having been between guard bands."""
+    return direct("camo_rg_loss_backward_drop", m, d.x, pair, _targets(c), mode=mode, rates=rates, seed=seed, momentum=BR.MOMENTUM)
 
 
 def _wrapper(m, c, d, pair, mode, rates, seed):
@@ -369,14 +349,14 @@ def test_zero_rates_are_the_existing_entry_byte_for_byte(mode):
     got = _direct(new, c, d, pair, mode, (0.0, 0.0, 0.0), 0xDEADBEEF12345678)
     L, E = _lib.lib(), pair[0][1].shape[0]
     query = L.camo_rg_train_bn_workspace_bytes if mode else L.camo_rg_train_workspace_bytes
-    assert got["need"] == query(ctypes.byref(old._dims), c["nc"], c["n"], E)
-    assert _same(got["loss"], wl)
-    for k, a, b in zip(NAMES, got["grads"], wg):
+    assert got.need == query(ctypes.byref(old._dims), c["nc"], c["n"], E)
+    assert _same(got.loss, wl)
+    for k, a, b in zip(NAMES, got.grads, wg):
         assert _same(a, b), k
     if mode:
-        assert _same(got["bs"], wbs)
+        assert _same(got.bs, wbs)
         want = _running(old)
-        for k, a in zip(STAT_NAMES, got["run"]):
+        for k, a in zip(STAT_NAMES, got.run):
             assert np.array_equal(_bits(a.cpu()), _bits(want[k])) and not np.array_equal(_bits(want[k]), _bits(c["p"][k])), k
     # and the wrapper sends None, 0 and zeros down the existing entry
     for zero in (0, 0.0, (0, 0, 0)):
@@ -467,16 +447,12 @@ def test_the_library_writes_inside_its_workspace_and_its_output_buffers(mode):
     other = _model(c).train()
     wl, wg, wbs = _wrapper(other, c, d, pair, mode, ALL, 21)
     m = _model(c).train()
-    got = _direct(m, c, d, pair, mode, ALL, 21, guarded=True)
-    (ws_whole, ws), outs = got["pairs"][0], got["pairs"][1:]
-    assert _guards_intact(ws_whole, ws, 0xA5), "workspace"
+    got = _direct(m, c, d, pair, mode, ALL, 21)                 # (the guards and "every element written" are asserted there)
+    outs = got.grads + [got.loss] + ([got.bs] + got.run if mode else [])
     refs = list(wg) + [wl] + ([wbs] + [other.state_dict()[k] for k in STAT_NAMES] if mode else [])
     names = NAMES + ["loss"] + (["batch_stats"] + list(STAT_NAMES) if mode else [])
     assert len(outs) == len(refs) == len(names)
-    for k, (whole, piece), ref in zip(names, outs, refs):
-        assert _guards_intact(whole, piece, 0xFF), k
-        val = piece.view(torch.float32)
-        assert bool(torch.isfinite(val).all()), k
-        assert np.array_equal(_bits(val.cpu()), _bits(ref.reshape(-1).cpu())), k
+    for k, val, ref in zip(names, outs, refs):
+        assert _same(val, ref), k
     for k, v in m.state_dict().items():                       # the model whose tables were passed was not written
         assert torch.equal(v.cpu(), torch.from_numpy(c["p"][k].copy())) if k in c["p"] else int(v) == 0, k
