@@ -40,6 +40,10 @@ RSZ_MAX_SIDE = 8192                 # CAMO_RSZ_MAX_SIDE
 RSZ_MAX_CHANNELS = 4                # CAMO_RSZ_MAX_CHANNELS
 RSZ_NEAREST, RSZ_BILINEAR, RSZ_AREA = 0, 1, 2      # CAMO_RSZ_NEAREST, CAMO_RSZ_BILINEAR, CAMO_RSZ_AREA
 RSZ_U8, RSZ_F32 = 0, 1              # CAMO_RSZ_U8, CAMO_RSZ_F32
+AUG_FIELDS = 24                     # CAMO_AUG_FIELDS
+AUG_FRAC_BITS = 16                  # CAMO_AUG_FRAC_BITS
+AUG_MAX_FACTOR = 1024               # CAMO_AUG_MAX_FACTOR
+AUG_TILE = 32                       # CAMO_AUG_TILE
 INST_FIELDS = 8                     # CAMO_INST_FIELDS
 INST_COUNTS = 4                     # CAMO_INST_COUNTS
 INST_MAX_ROWS = 1 << 24             # CAMO_INST_MAX_ROWS
@@ -247,6 +251,10 @@ PROTOTYPES = {
         ("camo_split_geodesic_workspace_bytes", sz, (i32, i32, i32, i32)),
         ("camo_split_instances_geodesic", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
         ("camo_split_geodesic_resume", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
+    ),
+    "camo_augment.h": (
+        ("camo_augment_workspace_bytes", sz, (i32, i32, i32, i32, i32)),
+        ("camo_augment", i32, (vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp)),
     ),
 }
 

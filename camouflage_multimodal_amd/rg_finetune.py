@@ -19,6 +19,7 @@ from .optim import AdamWStateMixin
 from .region_graph import (PIECE, _as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments,  # noqa: F401
                            flat_layout, loss_figures, slic_label_bound, slic_segments)
 from .pipeline import detect_camouflage_batch, detect_camouflage_ragged
+from .augment import affine_rows, augment_batch
 from .resize import _mask_list, _packed, _ragged, resize_batch
 from .rg_detect import _offsets_tensor
 
@@ -176,16 +177,26 @@ def prepare_finetune_batch(images, gt_masks, instance_masks=None, edge_masks=Non
 
 
 @torch.no_grad()
-def prepare_finetune_batch_ragged(images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, **kw):
+def prepare_finetune_batch_ragged(images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, augment=None, **kw):
     """``prepare_finetune_batch`` for uint8 images and masks of mixed sizes: the images are resized to ``size`` bilinear, every mask
     nearest, all with the same ``crops`` and ``flips`` (``random_resized_crops`` draws them), and the result goes to
-    ``prepare_finetune_batch`` with ``**kw`` (n_segments, band_permille, device, edge_min_pixels, pixel_loss)."""
+    ``prepare_finetune_batch`` with ``**kw`` (n_segments, band_permille, device, edge_min_pixels, pixel_loss).
+    ``augment`` -- a dict of ``augment.random_cod_augmentation``, in the place of ``crops`` and ``flips`` (giving both raises) -- adds
+    its rotation and its four enhancement factors (include/camo_augment.h): the images go through ``augment_batch`` bilinear with the
+    factors, every mask through the same maps nearest without them, what lies outside an image is 0.  ``augment=None`` (the
+    default) is the path above, launch for launch."""
+    if augment is not None and (crops is not None or flips is not None):
+        raise ValueError("augment holds its own crops and flips: give crops and flips, or augment, not both")
     device = kw.get("device", "cuda")
     data, geo, C, _ = _ragged(images, device)
     if C != 3:
         raise ValueError(f"need images with 3 channels, got {C}")
     packed = _packed(data, geo, C)
-    img = resize_batch(packed, size, "bilinear", crops, flips)
+    if augment is not None:
+        rows = affine_rows(packed.sizes, size, augment["crops"], augment["flips"], augment["angles"], border="constant", fill=0)
+        img = augment_batch(packed, size, rows, augment.get("factors"), "bilinear")
+    else:
+        img = resize_batch(packed, size, "bilinear", crops, flips)
     kw["device"] = img.device
 
     def small(masks, name):
@@ -194,6 +205,8 @@ def prepare_finetune_batch_ragged(images, gt_masks, instance_masks=None, edge_ma
         m = _mask_list(masks, len(packed), name, img.device)
         if m.sizes != packed.sizes:
             raise ValueError(f"every one of {name} must have its image's size")
+        if augment is not None:
+            return augment_batch(m, size, rows, None, "nearest", out_dtype=torch.uint8)
         return resize_batch(m, size, "nearest", crops, flips, out_dtype=torch.uint8)
 
     return prepare_finetune_batch(img, small(gt_masks, "gt_masks"), small(instance_masks, "instance_masks"), small(edge_masks, "edge_masks"),
@@ -344,11 +357,12 @@ class RegionGraphFineTuner(AdamWStateMixin):
         return self._evaluation(out, cod_metrics, instances, match, boundary=boundary, split=split)
 
     def step_from_ragged(self, images, gt_masks, instance_masks=None, edge_masks=None, size=(256, 256), crops=None, flips=None, n_segments=500,
-                         band_permille=0, edge_min_pixels=1):
+                         band_permille=0, edge_min_pixels=1, augment=None):
         """``prepare_finetune_batch_ragged`` (uint8 images and masks of mixed sizes, resized to ``size`` on the tuner's
-        device with a crop box and a flip per image), then ``step``."""
+        device with a crop box and a flip per image -- or with ``augment``, a dict of ``augment.random_cod_augmentation``: crop,
+        flip, rotation and the four enhancements), then ``step``."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")
-        return self.step(prepare_finetune_batch_ragged(images, gt_masks, instance_masks, edge_masks, size, crops, flips, n_segments=n_segments,
+        return self.step(prepare_finetune_batch_ragged(images, gt_masks, instance_masks, edge_masks, size, crops, flips, augment, n_segments=n_segments,
                                                        band_permille=band_permille, device=self.flat_params.device,
                                                        edge_min_pixels=edge_min_pixels, pixel_loss=self._pixel_options()))
 
