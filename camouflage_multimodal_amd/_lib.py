@@ -319,6 +319,81 @@ def require_device(t, name):
                         "fallback (move the model and its inputs to 'cuda').")
 
 
+# ---- what every wrapper of a library call repeats, stated once.  torch is imported where a function needs it, so
+# this module still imports without it.  The fusion engine's step path (engine.py, optim.py, losses.py) takes the two pointers from
+# here and nothing else: it caches its sizes, and a Python call level is time it has not got.
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+_torch = _raw_stream = None
+
+
+def _bind_torch():
+    """torch and its raw-stream getter, bound at ``_stream_ptr``'s first call: the engine's step pays no import statement per call."""
+    global _torch, _raw_stream
+    import torch
+    _torch, _raw_stream = torch, getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    return torch
+
+
+def _stream_ptr(device=None):
+    """The current HIP stream of ``device`` (default: the current device) as a void*."""
+    torch = _torch or _bind_torch()
+    if _raw_stream is not None:                              # (a plain C call: ~0.3 us against ~8 us for torch.cuda.current_stream())
+        idx = device.index if isinstance(device, torch.device) and device.index is not None else torch.cuda.current_device()
+        return C.c_void_p(_raw_stream(idx))
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(entry, device, *args):
+    """The library's ``entry(*args)`` with ``device`` current, then ``check``: the name is stated once.  The stream is one of
+    ``args``, where the entry's prototype has it."""
+    import torch
+    with torch.cuda.device(device):
+        rc = getattr(lib(), entry)(*args)
+    check(rc, entry)
+
+
+def workspace(bytes_entry, *args, device, refuse=None):
+    """(a uint8 buffer on ``device`` of the size the library's ``bytes_entry(*args)`` states, that size).  0 is the library's answer
+    to arguments it does not take: ``refuse()``, the call site's exception, is raised then -- ``None`` raises ``CamoError`` with the
+    library's own words (``check``), ``False`` says that 0 is a valid answer here, and the buffer is then one byte."""
+    import torch
+    need = int(getattr(lib(), bytes_entry)(*args))
+    if need == 0 and refuse is not False:
+        if refuse is None:
+            check(-1, bytes_entry)
+        raise refuse()
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need
+
+
+def image_planes(t):
+    """A prediction map [N, H, W] as (fp32 tensor the library reads in place through its image stride, that stride): one channel of a
+    [N, C, H, W] map stays where it is, anything else is made contiguous; the stride of a single image is H W."""
+    import torch
+    N, H, W = t.shape
+    t = t.detach()
+    if t.dtype != torch.float32 or t.stride(2) != 1 or t.stride(1) != W or (N > 1 and t.stride(0) < H * W):
+        t = t.to(torch.float32).contiguous()
+    return t, (t.stride(0) if N > 1 else H * W)
+
+
+def label_map(t, name):
+    """An int32 label map [N, H, W], or [H, W] as N = 1; the ``ValueError`` of anything else names the argument."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"need {name} [N, H, W] or [H, W] with at least one pixel, got {tuple(t.shape)}")
+    if t.dtype != torch.int32:
+        raise ValueError(f"{name} must be int32, got {t.dtype}")
+    return t
+
+
 def tail_timeouts(device=None):
     """Number of arrival waits of the one-launch tail kernel that gave up on ``device`` (default: the current HIP device) since the
     library was loaded (synchronous; see camo_tail_timeouts in include/camo_fusion.h).  A step that hit one is not applied: its

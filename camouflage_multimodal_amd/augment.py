@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
-from .resize import _ragged
+from ._lib import _ptr, _stream_ptr, call, workspace
+from .resize import _ragged, check_filter, check_out_dtype, check_size, draw_crop, upload_table
 
 FILTERS = {"nearest": _lib.RSZ_NEAREST, "bilinear": _lib.RSZ_BILINEAR}
 BORDERS = {"constant": 0, "replicate": 1}
@@ -47,8 +47,7 @@ def affine_rows(sizes, size, crops=None, flips=None, angles=None, zooms=None, bo
     Ho, Wo = (int(v) for v in size)
     if border not in BORDERS:
         raise ValueError(f"border must be one of {sorted(BORDERS)}, got {border!r}")
-    if not (1 <= Ho <= _lib.RSZ_MAX_SIDE and 1 <= Wo <= _lib.RSZ_MAX_SIDE):
-        raise ValueError(f"size must be within [1, {_lib.RSZ_MAX_SIDE}] a side, got {(Ho, Wo)}")
+    check_size((Ho, Wo))
     crops = [(0, 0, h, w) for h, w in sizes] if crops is None else [tuple(int(v) for v in c) for c in crops]
     flips = [0] * N if flips is None else [int(f) for f in flips]
     angles = [0.0] * N if angles is None else [float(a) for a in angles]
@@ -93,16 +92,7 @@ def random_cod_augmentation(sizes, size=(256, 256), seed=0, rotate_p=0.2, max_an
     ranges = (brightness, contrast, colour, sharpness)
     crops, flips, angles, factors = [], [], [], []
     for H, W in sizes:
-        H, W = int(H), int(W)
-        box = (0, 0, H, W)
-        for _ in range(10):
-            area = H * W * rs.uniform(scale[0], scale[1])
-            aspect = math.exp(rs.uniform(math.log(ratio[0]), math.log(ratio[1])))
-            w, h = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
-            if 0 < w <= W and 0 < h <= H:
-                box = (int(rs.randint(0, H - h + 1)), int(rs.randint(0, W - w + 1)), h, w)
-                break
-        crops.append(box)
+        crops.append(draw_crop(rs, H, W, scale, ratio))
         flips.append(1 if rs.uniform() < flip_p else 0)
         turn, angle = rs.uniform() < rotate_p, float(rs.uniform(-max_angle, max_angle))
         angles.append(angle if turn else 0.0)
@@ -135,13 +125,14 @@ def augment_table(src, table, channels, size, filter="bilinear", enhance=False, 
     (default ``numel()``), ``table`` int64 [N, 24] -- a device tensor is used unchecked (the kernel guards every row), anything else is
     checked with ``check_rows`` and uploaded.  Returns (dst [N, Ho, Wo, C] of ``out_dtype``, the int32 [N] status tensor on the device,
     which nothing here reads back)."""
-    if filter not in FILTERS:
-        raise ValueError(f"filter must be one of {sorted(FILTERS)}, got {filter!r}")
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-    Ho, Wo = (int(v) for v in size)
-    if not (1 <= Ho <= _lib.RSZ_MAX_SIDE and 1 <= Wo <= _lib.RSZ_MAX_SIDE):
-        raise ValueError(f"size must be within [1, {_lib.RSZ_MAX_SIDE}] a side, got {(Ho, Wo)}")
+    check_filter(filter, FILTERS)
+    check_out_dtype(out_dtype)
+    return _augment(src, table, channels, check_size(size), filter, enhance, out_dtype, src_elems)
+
+
+def _augment(src, table, channels, size, filter, enhance, out_dtype, src_elems=None):
+    """``augment_table`` past the checks of ``size``, ``filter`` and ``out_dtype``, which ``augment_batch`` has made by then."""
+    Ho, Wo = size
     C, enhance = int(channels), bool(enhance)
     if enhance and C != 3:
         raise ValueError(f"the enhancements need images with 3 channels, got {C}")
@@ -150,26 +141,19 @@ def augment_table(src, table, channels, size, filter="bilinear", enhance=False, 
         raise ValueError(f"src must be uint8, got {src.dtype}")
     dev = src.device
     src_elems = int(src.numel() if src_elems is None else src_elems)
-    if isinstance(table, torch.Tensor) and table.is_cuda:
-        tb = table.to(device=dev, dtype=torch.int64).contiguous()
-    else:
-        rows = table.tolist() if isinstance(table, (torch.Tensor, np.ndarray)) else [list(r) for r in table]
+
+    def check(rows):
         if not rows or any(len(r) != _lib.AUG_FIELDS for r in rows):
             raise ValueError(f"need a table [N, {_lib.AUG_FIELDS}]")
         check_rows(rows, C, src_elems, enhance)
-        tb = torch.tensor(rows, dtype=torch.int64).to(dev)
-    if tb.dim() != 2 or tb.shape[1] != _lib.AUG_FIELDS or tb.shape[0] == 0:
-        raise ValueError(f"need a table [N, {_lib.AUG_FIELDS}], got {tuple(tb.shape)}")
+
+    tb = upload_table(table, _lib.AUG_FIELDS, dev, check)
     N = tb.shape[0]
-    L = _lib.lib()
     dst = torch.empty((N, Ho, Wo, C), dtype=out_dtype, device=dev)
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    need = int(L.camo_augment_workspace_bytes(N, Ho, Wo, C, int(enhance)))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_augment(_ptr(src), src_elems, _ptr(dst), _lib.RSZ_F32 if out_dtype == torch.float32 else _lib.RSZ_U8, _ptr(tb), N, C, Ho, Wo,
-                            FILTERS[filter], int(enhance), _ptr(status), _ptr(ws), need, _stream_ptr(dev))
-    _lib.check(rc, "camo_augment")
+    ws, need = workspace("camo_augment_workspace_bytes", N, Ho, Wo, C, int(enhance), device=dev, refuse=False)      # (the warp alone needs none)
+    call("camo_augment", dev, _ptr(src), src_elems, _ptr(dst), _lib.RSZ_F32 if out_dtype == torch.float32 else _lib.RSZ_U8, _ptr(tb), N, C, Ho, Wo,
+         FILTERS[filter], int(enhance), _ptr(status), _ptr(ws), need, _stream_ptr(dev))
     return dst, status
 
 
@@ -181,13 +165,9 @@ def augment_batch(images, size=(256, 256), rows=None, factors=None, filter="bili
     ``out_dtype=torch.uint8``; images given as [H, W] come back [N, Ho, Wo].  ``factors``: N tuples (brightness, contrast, colour,
     sharpness) of Q8 integers in [0, 1024] -- the four enhancements after the warp, 3 channels only; ``None``: the warp alone, ONE
     launch.  ``filter``: "nearest" or "bilinear"."""
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-    if filter not in FILTERS:
-        raise ValueError(f"filter must be one of {sorted(FILTERS)}, got {filter!r}")
-    Ho, Wo = (int(v) for v in size)
-    if not (1 <= Ho <= _lib.RSZ_MAX_SIDE and 1 <= Wo <= _lib.RSZ_MAX_SIDE):
-        raise ValueError(f"size must be within [1, {_lib.RSZ_MAX_SIDE}] a side, got {(Ho, Wo)}")
+    check_out_dtype(out_dtype)
+    check_filter(filter, FILTERS)
+    Ho, Wo = check_size(size)
     data, geo, C, squeeze = _ragged(images)
     N = len(geo)
     if rows is None:
@@ -204,5 +184,5 @@ def augment_batch(images, size=(256, 256), rows=None, factors=None, filter="bili
         if C != 3:
             raise ValueError(f"factors need images with 3 channels, got {C}")
     table = [[o, h, w, rs, ps, 1, *r, *k, 0, 0] for (o, h, w, rs, ps), r, k in zip(geo, rows, ks)]
-    out, _ = augment_table(data, table, C, (Ho, Wo), filter, factors is not None, out_dtype)
+    out, _ = _augment(data, table, C, (Ho, Wo), filter, factors is not None, out_dtype)
     return out[..., 0] if squeeze else out

@@ -21,7 +21,7 @@ from functools import partial
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, label_map, workspace
 from .instance_match import COCO, _match_buffers, _match_detected, _match_inputs, _ratio, instance_match_records, match_instances
 
 RATIO = Fraction(1, 50)
@@ -62,38 +62,21 @@ def _distance(distance, ratio, H, W):
     return int(distance)
 
 
-def _label_map(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.numel() == 0:
-        raise ValueError(f"need {name} [N, H, W] or [H, W] with at least one pixel, got {tuple(t.shape)}")
-    if t.dtype != torch.int32:
-        raise ValueError(f"{name} must be int32, got {t.dtype}")
-    return t
-
-
 @torch.no_grad()
 def boundary_labels(labels, distance=None, ratio=RATIO):
     """``camo_boundary_labels``: ``labels`` int32 [N, H, W] (or [H, W]), 0 on background -> int32 [N, H, W], every instance's id on
     its boundary region and 0 elsewhere.  ``distance``: the erosion distance d (default ``boundary_distance(H, W, ratio)``).  Two
     launches, no host synchronisation."""
-    labels = _label_map(labels, "labels")
+    labels = label_map(labels, "labels")
     N, H, W = labels.shape
     d = _distance(distance, ratio, H, W)
     _lib.require_device(labels, "labels")
     labels = labels.detach().contiguous()
-    L = _lib.lib()
-    nbytes = L.camo_boundary_labels_workspace_bytes(N, H, W, d)
-    if nbytes == 0:
-        raise ValueError(f"camo_boundary_labels does not support N = {N}, H = {H}, W = {W}, d = {d}")
     dev = labels.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_boundary_labels_workspace_bytes", N, H, W, d, device=dev,
+                           refuse=lambda: ValueError(f"camo_boundary_labels does not support N = {N}, H = {H}, W = {W}, d = {d}"))
     out = torch.empty_like(labels)
-    with torch.cuda.device(dev):
-        rc = L.camo_boundary_labels(_ptr(labels), N, H, W, d, _ptr(out), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_boundary_labels")
+    call("camo_boundary_labels", dev, _ptr(labels), N, H, W, d, _ptr(out), _ptr(ws), nbytes, _stream_ptr(dev))
     return out
 
 
@@ -106,14 +89,14 @@ def match_instances_boundary(pred_labels, gt_labels, pred_table=None, max_pred=N
     "inter", "pred_rows" int32 [N, P, 6] = (area, rank, ground-truth id of highest combined IoU, the mask intersection with it,
     boundary area, the boundary intersection with it), "gt_area" int32 [N, G, 2] = (area, boundary area), "pred_boundary",
     "gt_boundary" (the maps) and "distance" (``None`` when both maps were given without one).  No host synchronisation."""
-    pred_labels, gt_labels = _label_map(pred_labels, "pred_labels"), _label_map(gt_labels, "gt_labels")
+    pred_labels, gt_labels = label_map(pred_labels, "pred_labels"), label_map(gt_labels, "gt_labels")
     if tuple(gt_labels.shape) != tuple(pred_labels.shape):
         raise ValueError(f"need gt_labels of pred_labels' shape {tuple(pred_labels.shape)}, got {tuple(gt_labels.shape)}")
     N, H, W = pred_labels.shape
     given = {"pred_boundary": pred_boundary, "gt_boundary": gt_boundary}
     for name, t in given.items():
         if t is not None:
-            given[name] = t = _label_map(t, name)
+            given[name] = t = label_map(t, name)
             if tuple(t.shape) != (N, H, W):
                 raise ValueError(f"need {name} of pred_labels' shape {(N, H, W)}, got {tuple(t.shape)}")
     d = None
@@ -122,14 +105,11 @@ def match_instances_boundary(pred_labels, gt_labels, pred_table=None, max_pred=N
     m = _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, thresholds, given.items())
     pred_bd = boundary_labels(m.pred_labels, d) if given["pred_boundary"] is None else given["pred_boundary"].detach().contiguous()
     gt_bd = boundary_labels(m.gt_labels, d) if given["gt_boundary"] is None else given["gt_boundary"].detach().contiguous()
-    L, dev, ws, out = _match_buffers("camo_boundary_match", m, (_lib.BD_ROW_FIELDS,), (_lib.BD_GT_FIELDS,))
+    dev, ws, out = _match_buffers("camo_boundary_match", m, (_lib.BD_ROW_FIELDS,), (_lib.BD_GT_FIELDS,))
     inter_bd = torch.empty_like(out["inter"])
-    with torch.cuda.device(dev):
-        rc = L.camo_boundary_match(_ptr(m.pred_labels), _ptr(m.gt_labels), _ptr(pred_bd), _ptr(gt_bd), *m.dims, m.table_ptr, m.rows,
-                                   (C.c_int32 * m.T)(*m.nums), m.den, m.T, _ptr(out["inter"]), _ptr(inter_bd), _ptr(out["pred_rows"]),
-                                   _ptr(out["gt_area"]), _ptr(out["match"]), _ptr(out["gt_match"]), _ptr(out["counts"]), _ptr(ws), ws.numel(),
-                                   _stream_ptr(dev))
-    _lib.check(rc, "camo_boundary_match")
+    call("camo_boundary_match", dev, _ptr(m.pred_labels), _ptr(m.gt_labels), _ptr(pred_bd), _ptr(gt_bd), *m.dims, m.table_ptr, m.rows,
+         (C.c_int32 * m.T)(*m.nums), m.den, m.T, _ptr(out["inter"]), _ptr(inter_bd), _ptr(out["pred_rows"]), _ptr(out["gt_area"]),
+         _ptr(out["match"]), _ptr(out["gt_match"]), _ptr(out["counts"]), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return {"inter": out["inter"], "inter_bd": inter_bd, **out, "thresholds": m.fr, "pred_boundary": pred_bd, "gt_boundary": gt_bd,
             "distance": d}
 

@@ -20,7 +20,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, workspace
 from .instances import mask_instances
 
 COCO = tuple(Fraction(n, 20) for n in range(10, 20))
@@ -104,18 +104,15 @@ def _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, threshol
 
 def _match_buffers(entry, m, row_fields, gt_fields):
     """The workspace of ``entry`` (``camo_inst_match`` or ``camo_boundary_match``) for ``_match_inputs``' ``m`` and the call's six
-    output tensors, "pred_rows" [N, P, *row_fields] and "gt_area" [N, G, *gt_fields]: (the library, the device, ws, the dict).  A step
+    output tensors, "pred_rows" [N, P, *row_fields] and "gt_area" [N, G, *gt_fields]: (the device, ws, the dict).  A step
     of its own because ``match_instances_boundary`` makes its boundary maps, which may raise, between the checks and this."""
     N, H, W, P, G = m.dims
-    L = _lib.lib()
-    nbytes = getattr(L, entry + "_workspace_bytes")(N, H, W, P, G, m.T)
-    if nbytes == 0:
-        raise ValueError(f"{entry} does not support N = {N}, H = {H}, W = {W}, P = {P}, G = {G}, T = {m.T}")
     dev = m.pred_labels.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, _ = workspace(entry + "_workspace_bytes", N, H, W, P, G, m.T, device=dev,
+                      refuse=lambda: ValueError(f"{entry} does not support N = {N}, H = {H}, W = {W}, P = {P}, G = {G}, T = {m.T}"))
     shapes = {"inter": (N, P + 1, G + 1), "pred_rows": (N, P, *row_fields), "gt_area": (N, G, *gt_fields), "match": (N, m.T, P),
               "gt_match": (N, m.T, G), "counts": (N, _lib.IM_COUNTS)}
-    return L, dev, ws, {k: torch.empty(*shape, dtype=torch.int32, device=dev) for k, shape in shapes.items()}
+    return dev, ws, {k: torch.empty(*shape, dtype=torch.int32, device=dev) for k, shape in shapes.items()}
 
 
 @torch.no_grad()
@@ -141,12 +138,10 @@ def match_instances(pred_labels, gt_labels, pred_table=None, max_pred=None, max_
         if t.dtype != torch.int32:
             raise ValueError(f"{name} must be int32, got {t.dtype}")
     m = _match_inputs(pred_labels, gt_labels, pred_table, max_pred, max_gt, thresholds)
-    L, dev, ws, out = _match_buffers("camo_inst_match", m, (4,), ())
-    with torch.cuda.device(dev):
-        rc = L.camo_inst_match(_ptr(m.pred_labels), _ptr(m.gt_labels), *m.dims, m.table_ptr, m.rows, (C.c_int32 * m.T)(*m.nums), m.den, m.T,
-                               _ptr(out["inter"]), _ptr(out["pred_rows"]), _ptr(out["gt_area"]), _ptr(out["match"]), _ptr(out["gt_match"]),
-                               _ptr(out["counts"]), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "camo_inst_match")
+    dev, ws, out = _match_buffers("camo_inst_match", m, (4,), ())
+    call("camo_inst_match", dev, _ptr(m.pred_labels), _ptr(m.gt_labels), *m.dims, m.table_ptr, m.rows, (C.c_int32 * m.T)(*m.nums), m.den, m.T,
+         _ptr(out["inter"]), _ptr(out["pred_rows"]), _ptr(out["gt_area"]), _ptr(out["match"]), _ptr(out["gt_match"]),
+         _ptr(out["counts"]), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return {**out, "thresholds": m.fr}
 
 

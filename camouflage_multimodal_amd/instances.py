@@ -15,7 +15,8 @@ import numbers
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, image_planes, workspace
+
 
 def check_arguments(threshold=0.5, connectivity=8, min_area=0, max_instances=64, n_images=1):
     """The ``ValueError`` of every bad setting, by name, before anything touches the device."""
@@ -47,24 +48,16 @@ def mask_instances(pred, threshold=0.5, connectivity=8, min_area=0, fill_holes=F
     N, H, W = pred.shape
     check_arguments(threshold, connectivity, min_area, max_instances, N)
     _lib.require_device(pred, "pred")
-    pred = pred.detach()
-    if pred.dtype != torch.float32 or pred.stride(2) != 1 or pred.stride(1) != W or (N > 1 and pred.stride(0) < H * W):
-        pred = pred.to(torch.float32).contiguous()
-    stride = pred.stride(0) if N > 1 else H * W
+    pred, stride = image_planes(pred)
     dev = pred.device
-    L = _lib.lib()
-    nbytes = L.camo_instances_workspace_bytes(N, H, W)
-    if nbytes == 0:
-        raise ValueError(f"camo_instances does not support N = {N}, H = {H}, W = {W}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_instances_workspace_bytes", N, H, W, device=dev,
+                           refuse=lambda: ValueError(f"camo_instances does not support N = {N}, H = {H}, W = {W}"))
     labels = torch.empty(N, H, W, dtype=torch.int32, device=dev)
     clean = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
     table = torch.empty(N, int(max_instances), _lib.INST_FIELDS, dtype=torch.int64, device=dev)
     counts = torch.empty(N, _lib.INST_COUNTS, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_instances(_ptr(pred), stride, float(threshold), N, H, W, int(connectivity), int(min_area), 1 if fill_holes else 0, int(max_instances),
-                              _ptr(labels), _ptr(clean), _ptr(table), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_instances")
+    call("camo_instances", dev, _ptr(pred), stride, float(threshold), N, H, W, int(connectivity), int(min_area), 1 if fill_holes else 0,
+         int(max_instances), _ptr(labels), _ptr(clean), _ptr(table), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
     return {"labels": labels, "clean_mask": clean.view(torch.bool), "table": table, "counts": counts}
 
 

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, rle as _rle
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, workspace
 
 MAX_BOUNDARY_POINTS = 1 << 28        # the sum of n_j the header's PRECONDITION allows
 
@@ -81,21 +81,16 @@ def decode_polygon_arrays(xy, poly_off, ann_poly_off, ann_image, ann_value, N, H
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _no_cpu(dev)
-    L = _lib.lib()
-    nbytes = L.camo_poly_decode_workspace_bytes(int(N), H, W, A, P, V)
-    if nbytes == 0:
-        raise ValueError(f"camo_poly_decode does not support N = {N}, H = {H}, W = {W}, {A} annotations, {P} polygons, {V} vertices")
+    ws, nbytes = workspace("camo_poly_decode_workspace_bytes", int(N), H, W, A, P, V, device=dev,
+                           refuse=lambda: ValueError(f"camo_poly_decode does not support N = {N}, H = {H}, W = {W}, {A} annotations, {P} polygons, {V} vertices"))
     ints = np.concatenate([poly_off, ann_poly_off, ann_image, ann_value])
     up = torch.from_numpy(np.concatenate([xy.reshape(-1).view(np.uint8), ints.view(np.uint8)])).to(dev)      # (the one copy; xy first: 8-byte aligned)
     at = [16 * V + 4 * v for v in (0, P + 1, P + A + 2, P + 2 * A + 2)]
     d_xy, d_poff, d_aoff, d_img, d_val = up[:16 * V], up[at[0]:at[1]], up[at[1]:at[2]], up[at[2]:at[3]], up[at[3]:]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     labels = torch.empty(int(N), H, W, dtype=torch.int32, device=dev)
     area = torch.empty(A, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_poly_decode(_ptr(d_xy) if V else None, V, _ptr(d_poff), P, _ptr(d_aoff), _ptr(d_img), _ptr(d_val), A, int(N), H, W, _ptr(labels),
-                                _ptr(area), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_poly_decode")
+    call("camo_poly_decode", dev, _ptr(d_xy) if V else None, V, _ptr(d_poff), P, _ptr(d_aoff), _ptr(d_img), _ptr(d_val), A, int(N), H, W,
+         _ptr(labels), _ptr(area), _ptr(ws), nbytes, _stream_ptr(dev))
     return labels, area
 
 

@@ -16,8 +16,8 @@ import numbers
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
-from .resize import _ragged
+from ._lib import _ptr, _stream_ptr, call, image_planes, workspace
+from .resize import _ragged, upload_table
 
 DEFAULTS = {"radius": 8, "eps": 1e-4, "guide": "rgb"}
 LUMA = (0.2989, 0.5870, 0.1140)      # include/camo_canny.h step 1
@@ -80,22 +80,14 @@ def guided_filter(guide, p, radius=8, eps=1e-4, clamp=True, return_coefficients=
     if guide.device != p.device:
         raise ValueError("guide and p must be on the same device")
     guide = guide.detach().to(torch.float32).contiguous()
-    p = p.detach()
-    if p.dtype != torch.float32 or p.stride(2) != 1 or p.stride(1) != W or (N > 1 and p.stride(0) < H * W):
-        p = p.to(torch.float32).contiguous()
-    stride = p.stride(0) if N > 1 else H * W
+    p, stride = image_planes(p)
     dev = p.device
-    L = _lib.lib()
-    nbytes = L.camo_guided_workspace_bytes(N, H, W, C)
-    if nbytes == 0:
-        raise ValueError(f"camo_guided_filter does not support N = {N}, H = {H}, W = {W}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_guided_workspace_bytes", N, H, W, C, device=dev,
+                           refuse=lambda: ValueError(f"camo_guided_filter does not support N = {N}, H = {H}, W = {W}"))
     q = torch.empty(N, H, W, dtype=torch.float32, device=dev)
     coef = torch.empty(N, C + 1, H, W, dtype=torch.float32, device=dev) if return_coefficients else None
-    with torch.cuda.device(dev):
-        rc = L.camo_guided_filter(_ptr(guide), _ptr(p), stride, N, H, W, C, int(radius), float(eps), 1 if clamp else 0, _ptr(q),
-                                  _ptr(coef), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_guided_filter")
+    call("camo_guided_filter", dev, _ptr(guide), _ptr(p), stride, N, H, W, C, int(radius), float(eps), 1 if clamp else 0, _ptr(q),
+         _ptr(coef), _ptr(ws), nbytes, _stream_ptr(dev))
     return (q, coef) if return_coefficients else q
 
 
@@ -117,15 +109,11 @@ def guided_apply_table(coef, guide, out, table, max_dst_pixels, clamp=True):
     if not (guide.is_contiguous() and out.is_contiguous()):
         raise ValueError("guide and out must be contiguous buffers")
     coef = coef.detach().contiguous()
-    tb = (table if isinstance(table, torch.Tensor) else torch.tensor([list(r) for r in table], dtype=torch.int64)).to(device=dev, dtype=torch.int64).contiguous()
     N, _, h, w = coef.shape
-    if tb.dim() != 2 or tuple(tb.shape) != (N, _lib.GF_FIELDS):
-        raise ValueError(f"need a table [{N}, {_lib.GF_FIELDS}], got {tuple(tb.shape)}")
+    tb = upload_table(table, _lib.GF_FIELDS, dev, n=N)
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_guided_apply(_ptr(coef), N, coef.shape[1] - 1, h, w, _ptr(guide), guide.numel(), _ptr(out), out.numel(), _ptr(tb),
-                                          int(max_dst_pixels), 1 if clamp else 0, _ptr(status), _stream_ptr(dev))
-    _lib.check(rc, "camo_guided_apply")
+    call("camo_guided_apply", dev, _ptr(coef), N, coef.shape[1] - 1, h, w, _ptr(guide), guide.numel(), _ptr(out), out.numel(), _ptr(tb),
+         int(max_dst_pixels), 1 if clamp else 0, _ptr(status), _stream_ptr(dev))
     return status
 
 

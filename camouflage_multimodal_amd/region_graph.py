@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, workspace
 
 
 def _as_tensor(value, device):
@@ -39,14 +39,6 @@ def _image_batch(img, single_ok=False):
     if img.dim() != 4 or img.shape[3] != 3 or img.numel() == 0:
         raise ValueError(f"need images {'[H, W, 3] or ' if single_ok else ''}[N, H, W, 3], got {tuple(img.shape)}")
     return img.to(torch.float32).contiguous(), single
-
-
-def _workspace(bytes_fn, *args, device):
-    """A device buffer of the size the library's ``bytes_fn(*args)`` states; 0 is its answer to arguments it does not take."""
-    need = getattr(_lib.lib(), bytes_fn)(*args)
-    if need == 0:
-        _lib.check(-1, bytes_fn)
-    return torch.empty(need, dtype=torch.uint8, device=device)
 
 
 def build_target_csr_device(num_nodes, edge_index, edge_weight=None):
@@ -135,13 +127,11 @@ def canny_edges(images, sigma=2.0, low_threshold=0.1, high_threshold=0.2, device
     img, single = _image_batch(img, single_ok=True)
     dev = img.device
     N, H, W = img.shape[:3]
-    ws = _workspace("camo_canny_workspace_bytes", N, H, W, device=dev)
+    ws, nbytes = workspace("camo_canny_workspace_bytes", N, H, W, device=dev)
     edges = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
     grad = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev) if return_gradients else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_canny(_ptr(img), N, H, W, float(sigma), float(low_threshold), float(high_threshold), _ptr(ws),
-                                   ws.numel(), _ptr(edges), _ptr(grad), _stream_ptr(dev))
-    _lib.check(rc, "camo_canny")
+    call("camo_canny", dev, _ptr(img), N, H, W, float(sigma), float(low_threshold), float(high_threshold), _ptr(ws), nbytes, _ptr(edges),
+         _ptr(grad), _stream_ptr(dev))
     edges = edges.to(torch.bool)
     if single:
         edges, grad = edges[0], (None if grad is None else grad[0])
@@ -173,18 +163,15 @@ def create_region_graph_from_segments(image, segments, edges_canny=None, device=
         raise ValueError(f"segment labels must lie in [0, {_lib.RG_MAX_LABELS}), got [{lo}, {hi}]")
     n_labels = hi + 1
     cap = int(edge_capacity) if edge_capacity else 16 * n_labels        # (a planar adjacency has < 3 n pairs; 8-connectivity adds corner contacts)
-    L = _lib.lib()
     while True:
-        ws = torch.empty(L.camo_rg_graph_workspace_bytes(n_labels), dtype=torch.uint8, device=dev)
+        ws, nbytes = workspace("camo_rg_graph_workspace_bytes", n_labels, device=dev)
         x = torch.empty(n_labels, 15, dtype=torch.float32, device=dev)
         rmap = torch.empty(n_labels, dtype=torch.int32, device=dev)
         ei = torch.empty(2, cap, dtype=torch.int64, device=dev)
         ea = torch.empty(cap, dtype=torch.float32, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.camo_rg_region_graph(_ptr(img), _ptr(seg), _ptr(can), H, W, n_labels, _ptr(ws), ws.numel(), _ptr(x), _ptr(rmap),
-                                        _ptr(ei), _ptr(ea), cap, _ptr(counts), _stream_ptr(dev))
-        _lib.check(rc, "camo_rg_region_graph")
+        call("camo_rg_region_graph", dev, _ptr(img), _ptr(seg), _ptr(can), H, W, n_labels, _ptr(ws), nbytes, _ptr(x), _ptr(rmap), _ptr(ei),
+             _ptr(ea), cap, _ptr(counts), _stream_ptr(dev))
         n, e = (int(v) for v in counts.tolist())                         # (the one synchronisation: the sizes of what was built)
         if e <= cap:
             break
@@ -223,8 +210,7 @@ def create_region_graphs_from_segments(images, segments, edges_canny=None, devic
         raise ValueError(f"label_bound must lie in [1, {_lib.RG_MAX_LABELS}], got {label_bound}")
     nodes = N * label_bound
     cap = int(edge_capacity) if edge_capacity else 16 * nodes             # (a planar adjacency has < 3 n pairs; 8-connectivity adds corner contacts)
-    L = _lib.lib()
-    ws = _workspace("camo_rg_batch_workspace_bytes", N, H, W, label_bound, device=dev)
+    ws, nbytes = workspace("camo_rg_batch_workspace_bytes", N, H, W, label_bound, device=dev)
     x = torch.empty(nodes, 15, dtype=torch.float32, device=dev)
     rmap = torch.empty(N, label_bound, dtype=torch.int32, device=dev)
     batch = torch.empty(nodes, dtype=torch.int32, device=dev)
@@ -233,11 +219,8 @@ def create_region_graphs_from_segments(images, segments, edges_canny=None, devic
     while True:
         ei = torch.empty(2, cap, dtype=torch.int64, device=dev)
         ea = torch.empty(cap, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.camo_rg_region_graph_batch(_ptr(img), _ptr(seg), _ptr(can), N, H, W, label_bound, _ptr(ws), ws.numel(), _ptr(x), nodes,
-                                              _ptr(rmap), _ptr(ei), _ptr(ea), cap, _ptr(node_off), _ptr(edge_off), _ptr(batch), _ptr(status),
-                                              _stream_ptr(dev))
-        _lib.check(rc, "camo_rg_region_graph_batch")
+        call("camo_rg_region_graph_batch", dev, _ptr(img), _ptr(seg), _ptr(can), N, H, W, label_bound, _ptr(ws), nbytes, _ptr(x), nodes,
+             _ptr(rmap), _ptr(ei), _ptr(ea), cap, _ptr(node_off), _ptr(edge_off), _ptr(batch), _ptr(status), _stream_ptr(dev))
         host = sizes.tolist()                                             # (the one synchronisation: the sizes of what was built)
         no, eo, (bad, e) = host[:N + 1], host[N + 1:2 * (N + 1)], host[2 * (N + 1):]
         if bad:
@@ -282,13 +265,11 @@ def slic_segments(images, n_segments=500, compactness=10.0, sigma=1.0, device="c
     img, single = _image_batch(img, single_ok=True)
     dev = img.device
     N, H, W = img.shape[:3]
-    ws = _workspace("camo_slic_workspace_bytes", N, H, W, int(n_segments), device=dev)
+    ws, nbytes = workspace("camo_slic_workspace_bytes", N, H, W, int(n_segments), device=dev)
     labels = torch.empty(N, H, W, dtype=torch.int32, device=dev)
     counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_slic(_ptr(img), N, H, W, int(n_segments), float(compactness), float(sigma), _ptr(ws), ws.numel(),
-                                  _ptr(labels), _ptr(counts), _stream_ptr(dev))
-    _lib.check(rc, "camo_slic")
+    call("camo_slic", dev, _ptr(img), N, H, W, int(n_segments), float(compactness), float(sigma), _ptr(ws), nbytes, _ptr(labels), _ptr(counts),
+         _stream_ptr(dev))
     if single:
         labels, counts = labels[0], counts[0]
     return (labels, counts) if return_counts else labels
@@ -450,11 +431,11 @@ class RegionGraphGNN(nn.Module):
         ew = None if edge_attr is None or edge_attr.numel() == 0 else edge_attr.reshape(-1)     # :98
         rowptr, col, w = build_target_csr_device(n, edge_index, ew)
         x = x.detach().to(torch.float32).contiguous()
-        ws = _workspace("camo_rg_workspace_bytes", C.byref(self._dims), n, device=x.device)
+        ws, nbytes = workspace("camo_rg_workspace_bytes", C.byref(self._dims), n, device=x.device)
         out = torch.empty(n, self._dims.hidden, dtype=torch.float32, device=x.device)
         tab, keep = self._param_table()
         rc = _lib.lib().camo_rg_node_embeddings(C.byref(self._dims), tab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w), n, col.shape[0],
-                                                _ptr(ws), ws.numel(), _ptr(out), _stream_ptr())
+                                                _ptr(ws), nbytes, _ptr(out), _stream_ptr())
         _lib.check(rc, "camo_rg_node_embeddings")
         return out
 
@@ -487,10 +468,8 @@ class RegionGraphGNN(nn.Module):
         logits = torch.empty(n, 2 * self.num_classes + 1, dtype=torch.float32, device=emb.device)
         probs = torch.empty(n, 3, dtype=torch.float32, device=emb.device)
         tab, keep = self._head_table()
-        with torch.cuda.device(emb.device):
-            rc = _lib.lib().camo_rg_node_heads(C.byref(self._dims), self.num_classes, tab, _ptr(emb), n, _ptr(logits), _ptr(probs),
-                                               _stream_ptr(emb.device))
-        _lib.check(rc, "camo_rg_node_heads")
+        call("camo_rg_node_heads", emb.device, C.byref(self._dims), self.num_classes, tab, _ptr(emb), n, _ptr(logits), _ptr(probs),
+             _stream_ptr(emb.device))
         return logits, probs
 
     def node_probabilities(self, data):
@@ -642,8 +621,8 @@ class RegionGraphGNN(nn.Module):
                 if stats_out.dtype != torch.float32 or tuple(stats_out.shape) != (4, 2, self._dims.hidden) or not stats_out.is_contiguous() \
                         or stats_out.device != dev:
                     raise RuntimeError(f"stats_out must be a contiguous fp32 tensor [4, 2, {self._dims.hidden}] on {dev}")
-        ws = _workspace("camo_rg_train_bn_workspace_bytes" if batch_stats else "camo_rg_train_workspace_bytes", C.byref(self._dims),
-                        self.num_classes, n, E, device=dev)
+        ws, nbytes = workspace("camo_rg_train_bn_workspace_bytes" if batch_stats else "camo_rg_train_workspace_bytes", C.byref(self._dims),
+                               self.num_classes, n, E, device=dev)
         params = self.trainable_parameters()
         pieces, total = flat_layout([p.shape for p in params])
         if out is None:
@@ -660,7 +639,7 @@ class RegionGraphGNN(nn.Module):
         gtab = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         # what every entry takes (and the stream, which goes last); then the batch-norm tail; then the dropout and pixel entries' own
         common = (C.byref(self._dims), self.num_classes, tab, htab, _ptr(x), _ptr(rowptr), _ptr(col), _ptr(w), _ptr(rrowptr), _ptr(rcol),
-                  _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi, we, _ptr(ws), ws.numel(), _ptr(loss), gtab)
+                  _ptr(rw), n, E, _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]), wm, wi, we, _ptr(ws), nbytes, _ptr(loss), gtab)
         name = self._training_entry(batch_stats, rates, pixel)
         tail = ()
         if name != "camo_rg_loss_backward":
@@ -669,9 +648,7 @@ class RegionGraphGNN(nn.Module):
             tail += (1 if batch_stats else 0, *(rates or (0.0, 0.0, 0.0)), seed)
         if name == "camo_rg_loss_backward_pixel":
             tail += (_ptr(node_w), _ptr(node_off), node_off.numel() - 1, radius, w_pixel)
-        with torch.cuda.device(dev):
-            rc = getattr(_lib.lib(), name)(*common, *tail, _stream_ptr(dev))
-        _lib.check(rc, name)
+        call(name, dev, *common, *tail, _stream_ptr(dev))
         if batch_stats and update_running:
             for bn in self._batch_norms():
                 if bn.num_batches_tracked is not None:

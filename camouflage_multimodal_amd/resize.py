@@ -4,7 +4,8 @@ The data of this project are 8-bit files, each of its own size; the model works 
 scored at each ground truth's own size.  ``pack_images`` puts a list of uint8 images into one device buffer, ``resize_batch``
 resamples them -- with a crop box and a flip per image -- to a fixed fp32 batch in ONE launch of ``camo_resize``, and
 ``resize_to_sizes`` takes fp32 maps back to ragged native sizes in one launch; ``random_resized_crops`` draws the boxes and flips
-of an augmentation.  This module is the header's binding and imports nothing but it: what runs on top -- the entry points for
+of an augmentation (``draw_crop``, one box; with ``check_size``, ``check_filter``, ``check_out_dtype`` and ``upload_table`` what augment.py
+and refine.py share with this module).  This module is the header's binding and imports nothing but it: what runs on top -- the entry points for
 images of mixed sizes and for a folder of files -- is in pipeline.py, and the fine-tune preparation for mixed sizes in
 rg_finetune.py.  PARITY UNPINNED: cv2 and skimage are absent, so the header's text defines the filters (exact integer arithmetic;
 tests/resize_ref.py restates it).  There is no CPU path: tensors that are not on a HIP device raise.
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call
 
 FILTERS = {"nearest": _lib.RSZ_NEAREST, "bilinear": _lib.RSZ_BILINEAR, "area": _lib.RSZ_AREA}
 
@@ -116,6 +117,41 @@ def check_table(rows, channels, src_elems, dst_elems, max_dst_pixels):
             raise ValueError(f"image {i}: {dh} x {dw} destination pixels exceed max_dst_pixels = {max_dst_pixels}")
 
 
+def check_size(size):
+    """``size`` = (Ho, Wo) as two integers, each within [1, RSZ_MAX_SIDE]."""
+    Ho, Wo = (int(v) for v in size)
+    if not (1 <= Ho <= _lib.RSZ_MAX_SIDE and 1 <= Wo <= _lib.RSZ_MAX_SIDE):
+        raise ValueError(f"size must be within [1, {_lib.RSZ_MAX_SIDE}] a side, got {(Ho, Wo)}")
+    return Ho, Wo
+
+
+def check_filter(filter, filters):
+    """``filter`` against a module's own ``FILTERS``."""
+    if filter not in filters:
+        raise ValueError(f"filter must be one of {sorted(filters)}, got {filter!r}")
+
+
+def check_out_dtype(out_dtype):
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+
+
+def upload_table(table, fields, device, check=None, n=None):
+    """The int64 [N, ``fields``] table of a ragged call on ``device``: a device tensor is used unchecked (the kernel guards every
+    row), anything else goes through ``check(rows)``, the caller's row conditions on host integers, and is uploaded; without a
+    checker a host tensor goes up as it is.  ``n``: the N the caller knows."""
+    if isinstance(table, torch.Tensor) and (table.is_cuda or check is None):
+        tb = table.to(device=device, dtype=torch.int64).contiguous()
+    else:
+        rows = table.tolist() if isinstance(table, (torch.Tensor, np.ndarray)) else [list(r) for r in table]
+        if check is not None:
+            check(rows)
+        tb = torch.tensor(rows, dtype=torch.int64).to(device)
+    if tb.dim() != 2 or tb.shape[1] != fields or tb.shape[0] == 0 or (n is not None and tb.shape[0] != n):
+        raise ValueError(f"need a table [{'N' if n is None else n}, {fields}], got {tuple(tb.shape)}")
+    return tb
+
+
 def _type_of(t, name):
     if t.dtype == torch.uint8:
         return _lib.RSZ_U8
@@ -133,31 +169,26 @@ def resize_table(src, dst, table, channels, filter="bilinear", max_dst_pixels=No
     zeroed), which nothing here reads back."""
     _lib.require_device(src, "src")
     _lib.require_device(dst, "dst")
-    if filter not in FILTERS:
-        raise ValueError(f"filter must be one of {sorted(FILTERS)}, got {filter!r}")
+    check_filter(filter, FILTERS)
     dev = src.device
     if dst.device != dev:
         raise ValueError("src and dst must be on the same device")
     src_elems = int(src.numel() if src_elems is None else src_elems)
     dst_elems = int(dst.numel() if dst_elems is None else dst_elems)
-    if isinstance(table, torch.Tensor) and table.is_cuda:
-        tb = table.to(device=dev, dtype=torch.int64).contiguous()
-        if max_dst_pixels is None:
-            raise ValueError("a device table needs max_dst_pixels")
-    else:
-        rows = table.tolist() if isinstance(table, (torch.Tensor, np.ndarray)) else [list(r) for r in table]
+    if max_dst_pixels is None and isinstance(table, torch.Tensor) and table.is_cuda:
+        raise ValueError("a device table needs max_dst_pixels")
+
+    def check(rows):
+        nonlocal max_dst_pixels
         if max_dst_pixels is None:
             max_dst_pixels = max(int(r[12]) * int(r[13]) for r in rows)
         check_table(rows, channels, src_elems, dst_elems, int(max_dst_pixels))
-        tb = torch.tensor(rows, dtype=torch.int64).to(dev)
-    if tb.dim() != 2 or tb.shape[1] != _lib.RSZ_FIELDS or tb.shape[0] == 0:
-        raise ValueError(f"need a table [N, {_lib.RSZ_FIELDS}], got {tuple(tb.shape)}")
+
+    tb = upload_table(table, _lib.RSZ_FIELDS, dev, check)
     N = tb.shape[0]
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_resize(_ptr(src), src_elems, _type_of(src, "src"), _ptr(dst), dst_elems, _type_of(dst, "dst"), _ptr(tb), N,
-                                    int(channels), FILTERS[filter], int(max_dst_pixels), _ptr(status), _stream_ptr(dev))
-    _lib.check(rc, "camo_resize")
+    call("camo_resize", dev, _ptr(src), src_elems, _type_of(src, "src"), _ptr(dst), dst_elems, _type_of(dst, "dst"), _ptr(tb), N,
+         int(channels), FILTERS[filter], int(max_dst_pixels), _ptr(status), _stream_ptr(dev))
     return status
 
 
@@ -206,15 +237,13 @@ def resize_batch(images, size=(256, 256), filter="bilinear", crops=None, flips=N
     ``filter``: "nearest", "bilinear" (cv2.INTER_LINEAR's sampling) or "area" (cv2.INTER_AREA's box; bilinear on an axis that grows).
     ``crops``: N boxes (y0, x0, h, w) resampled in place of the whole images, the border repeated at the box's edge; ``flips``: N
     values, bit 0 mirrors columns and bit 1 rows.  A box outside its image, or any side above 8192, raises ``ValueError``."""
-    if out_dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+    check_out_dtype(out_dtype)
     Ho, Wo = (int(v) for v in size)
     data, geo, C, squeeze = _ragged(images)
     crops, flips = _boxes(crops, flips, geo)
     rows = [[o, h, w, rs, ps, 1, y0, x0, ch, cw, f, i * Ho * Wo * C, Ho, Wo, Wo * C, C, 1, 0]
             for i, ((o, h, w, rs, ps), (y0, x0, ch, cw), f) in enumerate(zip(geo, crops, flips))]
-    if not (1 <= Ho <= _lib.RSZ_MAX_SIDE and 1 <= Wo <= _lib.RSZ_MAX_SIDE):
-        raise ValueError(f"size must be within [1, {_lib.RSZ_MAX_SIDE}] a side, got {(Ho, Wo)}")
+    check_size((Ho, Wo))                                     # (the images' and the boxes' own errors come first)
     out = torch.empty((len(geo), Ho, Wo) if squeeze else (len(geo), Ho, Wo, C), dtype=out_dtype, device=data.device)
     resize_table(data, out, rows, C, filter, Ho * Wo)
     return out
@@ -257,6 +286,20 @@ def resize_to_sizes(maps, sizes, filter="bilinear"):
     return views, buf
 
 
+def draw_crop(rs, H, W, scale, ratio):
+    """One RandomResizedCrop box (y0, x0, h, w) of an H x W image from the ``RandomState`` ``rs``: up to ten draws of an area
+    fraction in ``scale`` and an aspect ratio (w / h) log-uniform in ``ratio``, two draws each; the first box that fits is placed
+    with two draws more; after ten rejected draws the box is the whole image."""
+    H, W = int(H), int(W)
+    for _ in range(10):
+        area = H * W * rs.uniform(scale[0], scale[1])
+        aspect = math.exp(rs.uniform(math.log(ratio[0]), math.log(ratio[1])))
+        w, h = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
+        if 0 < w <= W and 0 < h <= H:
+            return int(rs.randint(0, H - h + 1)), int(rs.randint(0, W - w + 1)), h, w
+    return 0, 0, H, W
+
+
 def random_resized_crops(sizes, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0):
     """The boxes and flips of a RandomResizedCrop + RandomHorizontalFlip for images of ``sizes`` [(H, W), ...]: host only, driven by
     ``numpy.random.RandomState(seed)``, so the same seed gives the same list.  Per image up to ten draws of an area fraction in
@@ -265,16 +308,7 @@ def random_resized_crops(sizes, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0
     rs = np.random.RandomState(seed)
     crops, flips = [], []
     for H, W in sizes:
-        H, W = int(H), int(W)
-        box = (0, 0, H, W)
-        for _ in range(10):
-            area = H * W * rs.uniform(scale[0], scale[1])
-            aspect = math.exp(rs.uniform(math.log(ratio[0]), math.log(ratio[1])))
-            w, h = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
-            if 0 < w <= W and 0 < h <= H:
-                box = (int(rs.randint(0, H - h + 1)), int(rs.randint(0, W - w + 1)), h, w)
-                break
-        crops.append(box)
+        crops.append(draw_crop(rs, H, W, scale, ratio))
         flips.append(1 if rs.uniform() < flip_p else 0)
     return crops, flips
 

@@ -13,7 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, image_planes
 
 
 def _offsets_tensor(node_offsets, device):
@@ -54,10 +54,7 @@ def paint_regions(values, segments, region_map, node_offsets, fill=0.0):
     seg = segments.to(device=dev, dtype=torch.int32).contiguous()
     rmap = region_map.to(device=dev, dtype=torch.int32).contiguous()
     maps = torch.empty(N, ch, H, W, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_rg_paint(_ptr(val), n, ch, _ptr(seg), _ptr(rmap), _ptr(off), N, H, W, rmap.shape[1], float(fill), _ptr(maps),
-                                      _stream_ptr(dev))
-    _lib.check(rc, "camo_rg_paint")
+    call("camo_rg_paint", dev, _ptr(val), n, ch, _ptr(seg), _ptr(rmap), _ptr(off), N, H, W, rmap.shape[1], float(fill), _ptr(maps), _stream_ptr(dev))
     return maps
 
 
@@ -87,17 +84,12 @@ def segmentation_counts(pred, gt, threshold=0.5):
     if pred.dim() != 3 or gt.shape != pred.shape or pred.numel() == 0:
         raise ValueError(f"need pred [N, H, W] and gt of the same shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
     N, H, W = pred.shape
-    pred = pred.detach()
-    if pred.dtype != torch.float32 or pred.stride(2) != 1 or pred.stride(1) != W or (N > 1 and pred.stride(0) < H * W):
-        pred = pred.to(torch.float32).contiguous()
-    stride = pred.stride(0) if N > 1 else H * W
+    pred, stride = image_planes(pred)
     dev = pred.device
     g = gt.to(device=dev)
     g = (g.to(torch.uint8) * 255 if g.dtype == torch.bool else g.to(torch.uint8)).contiguous()
     counts = torch.empty(N, 5, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_seg_counts(_ptr(pred), stride, _ptr(g), float(threshold), N, H, W, _ptr(counts), _stream_ptr(dev))
-    _lib.check(rc, "camo_seg_counts")
+    call("camo_seg_counts", dev, _ptr(pred), stride, _ptr(g), float(threshold), N, H, W, _ptr(counts), _stream_ptr(dev))
     return counts
 
 

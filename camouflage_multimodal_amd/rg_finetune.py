@@ -14,7 +14,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .engine import _on, _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call
+from .engine import _on
 from .optim import AdamWStateMixin
 from .region_graph import (PIECE, _as_tensor, _image_batch, build_target_csr_device, create_region_graphs_from_segments,  # noqa: F401
                            flat_layout, loss_figures, slic_label_bound, slic_segments)
@@ -77,11 +78,8 @@ def node_targets_from_masks(segments, region_map, node_offsets, gt_masks, instan
     mask_t = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
     inst_t = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
     edge_t = torch.empty(max(n, 0), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_rg_node_targets(_ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), _ptr(inst), _ptr(edge), N, H, W, rmap.shape[1], n,
-                                             int(band_permille), int(edge_min_pixels), _ptr(counts), _ptr(mask_t), _ptr(inst_t),
-                                             _ptr(edge_t), _stream_ptr(dev))
-    _lib.check(rc, "camo_rg_node_targets")
+    call("camo_rg_node_targets", dev, _ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), _ptr(inst), _ptr(edge), N, H, W, rmap.shape[1], n,
+         int(band_permille), int(edge_min_pixels), _ptr(counts), _ptr(mask_t), _ptr(inst_t), _ptr(edge_t), _stream_ptr(dev))
     return mask_t, inst_t, edge_t, counts
 
 
@@ -113,10 +111,8 @@ def pixel_loss_weights(segments, region_map, node_offsets, gt_masks, radius=15, 
     rmap = region_map.to(device=dev, dtype=torch.int32).contiguous()
     n = int(n_nodes)
     node_w = torch.empty(max(n, 0), 2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_rg_pixel_weights(_ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), N, H, W, rmap.shape[1], n, int(radius), int(gain),
-                                              _ptr(node_w), _stream_ptr(dev))
-    _lib.check(rc, "camo_rg_pixel_weights")
+    call("camo_rg_pixel_weights", dev, _ptr(seg), _ptr(rmap), _ptr(off), _ptr(gt), N, H, W, rmap.shape[1], n, int(radius), int(gain),
+         _ptr(node_w), _stream_ptr(dev))
     return node_w
 
 

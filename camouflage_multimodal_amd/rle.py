@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, label_map, workspace
 
 
 def _counts_array(cnts, name="counts"):
@@ -120,18 +120,6 @@ def rle_area(rle):
     return int(_rle_counts(rle)[0][1::2].sum())
 
 
-def _check_labels(labels):
-    if not isinstance(labels, torch.Tensor):
-        raise ValueError("labels must be a tensor")
-    if labels.dim() == 2:
-        labels = labels.unsqueeze(0)
-    if labels.dim() != 3 or labels.numel() == 0:
-        raise ValueError(f"need labels [N, H, W] or [H, W] with at least one pixel, got {tuple(labels.shape)}")
-    if labels.dtype != torch.int32:
-        raise ValueError(f"labels must be int32, got {labels.dtype}")
-    return labels
-
-
 def _check_max_runs(max_runs, n_images):
     if isinstance(max_runs, bool) or not isinstance(max_runs, numbers.Integral) or max_runs < 1:
         raise ValueError(f"max_runs must be an integer >= 1, got {max_runs!r}")
@@ -145,22 +133,17 @@ def label_runs(labels, max_runs=4096):
     """``camo_rle_runs``: ``labels`` int32 [N, H, W] (or [H, W]) -> {"runs": int32 [N, max_runs, 2] = (start, label) of every
     maximal run of equal label along p = x H + y, background runs included, zero past the last, "counts": int32 [N, 2] = (the runs
     the image holds, the runs written)}, on the device, no host synchronisation."""
-    labels = _check_labels(labels)
+    labels = label_map(labels, "labels")
     N, H, W = labels.shape
     R = _check_max_runs(max_runs, N)
     _lib.require_device(labels, "labels")
     labels = labels.detach().contiguous()
     dev = labels.device
-    L = _lib.lib()
-    nbytes = L.camo_rle_runs_workspace_bytes(N, H, W, R)
-    if nbytes == 0:
-        raise ValueError(f"camo_rle_runs does not support N = {N}, H = {H}, W = {W}, max_runs = {R}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_rle_runs_workspace_bytes", N, H, W, R, device=dev,
+                           refuse=lambda: ValueError(f"camo_rle_runs does not support N = {N}, H = {H}, W = {W}, max_runs = {R}"))
     runs = torch.empty(N, R, 2, dtype=torch.int32, device=dev)
     counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_rle_runs(_ptr(labels), N, H, W, R, _ptr(runs), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_rle_runs")
+    call("camo_rle_runs", dev, _ptr(labels), N, H, W, R, _ptr(runs), _ptr(counts), _ptr(ws), nbytes, _stream_ptr(dev))
     return {"runs": runs, "counts": counts}
 
 
@@ -214,7 +197,7 @@ def encode_instances(labels, max_runs=4096):
     """``label_runs`` and ``rles_from_runs`` together: per image {id: RLE} of ``labels`` int32 [N, H, W] (or [H, W]).  When an image
     holds more than ``max_runs`` runs the call is made once more with the capacity of the largest count, so no RLE is cut short.
     Two host copies: the counts, then the rows of ``runs`` that hold a run."""
-    labels = _check_labels(labels)
+    labels = label_map(labels, "labels")
     N, H, W = labels.shape
     out = label_runs(labels, max_runs)
     c = out["counts"].cpu().numpy()
@@ -285,19 +268,14 @@ def decode_counts(cnts, ann_off, ann_image, ann_value, N, H, W, device="cuda"):
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.CamoError(f"the label maps are painted on {dev}: camo_rle_decode runs as HIP kernels on an MI355X and has no CPU fallback")
-    L = _lib.lib()
-    nbytes = L.camo_rle_decode_workspace_bytes(int(N), int(H), int(W), A, total)
-    if nbytes == 0:
-        raise ValueError(f"camo_rle_decode does not support N = {N}, H = {H}, W = {W}, {A} annotations, {total} counts")
+    ws, nbytes = workspace("camo_rle_decode_workspace_bytes", int(N), int(H), int(W), A, total, device=dev,
+                           refuse=lambda: ValueError(f"camo_rle_decode does not support N = {N}, H = {H}, W = {W}, {A} annotations, {total} counts"))
     up = torch.from_numpy(np.concatenate([ann_off, ann_image, ann_value, cnts])).to(dev)      # (the one copy)
     d_off, d_img, d_val, d_cnt = up[:A + 1], up[A + 1:2 * A + 1], up[2 * A + 1:3 * A + 1], up[3 * A + 1:]
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     labels = torch.empty(int(N), int(H), int(W), dtype=torch.int32, device=dev)
     ann_sum = torch.empty(A, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_rle_decode(_ptr(d_cnt) if total else None, total, _ptr(d_off), _ptr(d_img), _ptr(d_val), A, int(N), int(H), int(W), _ptr(labels),
-                               _ptr(ann_sum), _ptr(ws), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "camo_rle_decode")
+    call("camo_rle_decode", dev, _ptr(d_cnt) if total else None, total, _ptr(d_off), _ptr(d_img), _ptr(d_val), A, int(N), int(H), int(W),
+         _ptr(labels), _ptr(ann_sum), _ptr(ws), nbytes, _stream_ptr(dev))
     return labels, ann_sum
 
 

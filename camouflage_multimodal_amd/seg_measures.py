@@ -15,7 +15,7 @@ import math
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, image_planes, workspace
 
 EPS = 2.0 ** -52
 MEASURE_KEYS = ("s_measure", "e_max", "e_mean", "e_adp", "f_max", "f_mean", "f_adp", "mae_u8")
@@ -32,10 +32,7 @@ def _planes(pred, gt):
     N, H, W = pred.shape
     if H * W < 2:
         raise ValueError("the measures need at least two pixels per image")
-    pred = pred.detach()
-    if pred.dtype != torch.float32 or pred.stride(2) != 1 or pred.stride(1) != W or (N > 1 and pred.stride(0) < H * W):
-        pred = pred.to(torch.float32).contiguous()
-    stride = pred.stride(0) if N > 1 else H * W
+    pred, stride = image_planes(pred)
     g = gt.to(device=pred.device)
     g = (g.to(torch.uint8) * 255 if g.dtype == torch.bool else g.to(torch.uint8)).contiguous()
     return pred, stride, g
@@ -51,9 +48,7 @@ def segmentation_histograms(pred, gt):
     dev = pred.device
     hist = torch.empty(N, _lib.SEG_QUADRANTS, 2, _lib.SEG_BINS, dtype=torch.int32, device=dev)
     split = torch.empty(N, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().camo_seg_histograms(_ptr(pred), stride, _ptr(g), N, H, W, _ptr(hist), _ptr(split), _stream_ptr(dev))
-    _lib.check(rc, "camo_seg_histograms")
+    call("camo_seg_histograms", dev, _ptr(pred), stride, _ptr(g), N, H, W, _ptr(hist), _ptr(split), _stream_ptr(dev))
     return hist, split
 
 
@@ -75,16 +70,11 @@ def weighted_f_sums(pred, gt):
     if max(H, W) > _lib.SEG_WF_MAX_SIDE:
         raise ValueError(f"the weighted F-measure takes images of at most {_lib.SEG_WF_MAX_SIDE} pixels a side, got {H} x {W}")
     dev = pred.device
-    L = _lib.lib()
-    nbytes = L.camo_seg_weighted_f_workspace_bytes(N, H, W)
-    if nbytes == 0:
-        raise _lib.CamoError(f"camo_seg_weighted_f does not support N = {N}, H = {H}, W = {W}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_seg_weighted_f_workspace_bytes", N, H, W, device=dev,
+                           refuse=lambda: _lib.CamoError(f"camo_seg_weighted_f does not support N = {N}, H = {H}, W = {W}"))
     gauss = torch.tensor(gaussian_7x7(), dtype=torch.float64, device=dev)
     sums = torch.empty(N, 3, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.camo_seg_weighted_f(_ptr(pred), stride, _ptr(g), N, H, W, _ptr(gauss), _ptr(ws), nbytes, _ptr(sums), _stream_ptr(dev))
-    _lib.check(rc, "camo_seg_weighted_f")
+    call("camo_seg_weighted_f", dev, _ptr(pred), stride, _ptr(g), N, H, W, _ptr(gauss), _ptr(ws), nbytes, _ptr(sums), _stream_ptr(dev))
     return sums
 
 

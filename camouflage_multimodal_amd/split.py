@@ -18,7 +18,7 @@ import numbers
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream_ptr
+from ._lib import _ptr, _stream_ptr, call, image_planes, label_map, workspace
 from .instances import instance_records
 
 RATIO = (7, 10)
@@ -56,18 +56,6 @@ def check_growth(growth="euclidean", rounds=None):
         raise ValueError(f'rounds belongs to growth="geodesic", got growth={growth!r}')
 
 
-def _label_map(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.numel() == 0:
-        raise ValueError(f"need {name} [N, H, W] or [H, W] with at least one pixel, got {tuple(t.shape)}")
-    if t.dtype != torch.int32:
-        raise ValueError(f"{name} must be int32, got {t.dtype}")
-    return t
-
-
 @torch.no_grad()
 def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max_instances=64, growth="euclidean", rounds=None):
     """``camo_split_instances``: ``labels`` int32 [N, H, W] (or [H, W]), 0 on background and an id in 1 .. 1024 per component
@@ -84,7 +72,7 @@ def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max
     enough for every path that is monotone in both axes) are enqueued, then "pending" is read -- ONE HOST SYNCHRONISATION, which the
     Euclidean path does not have -- and ``camo_split_geodesic_resume`` runs twice the rounds again until no image has a tile left
     to grow, so the result is the header's definition for any content.  The dict then also holds "rounds": the rounds run in all."""
-    labels = _label_map(labels, "labels")
+    labels = label_map(labels, "labels")
     N, H, W = labels.shape
     if pred is not None:
         if not isinstance(pred, torch.Tensor):
@@ -100,39 +88,29 @@ def split_instances(labels, pred=None, ratio=RATIO, min_core=0, max_split=4, max
     stride = 0
     if pred is not None:
         _lib.require_device(pred, "pred")
-        pred = pred.detach()
-        if pred.dtype != torch.float32 or pred.stride(2) != 1 or pred.stride(1) != W or (N > 1 and pred.stride(0) < H * W):
-            pred = pred.to(torch.float32).contiguous()
-        stride = pred.stride(0) if N > 1 else H * W
+        pred, stride = image_planes(pred)
     dev = labels.device
-    L = _lib.lib()
     geodesic = growth == "geodesic"
-    nbytes = (L.camo_split_geodesic_workspace_bytes if geodesic else L.camo_split_workspace_bytes)(N, H, W, int(max_split))
-    if nbytes == 0:
-        raise ValueError(f"camo_split_instances does not support N = {N}, H = {H}, W = {W} (a side is at most {_lib.SEG_WF_MAX_SIDE})")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = workspace("camo_split_geodesic_workspace_bytes" if geodesic else "camo_split_workspace_bytes", N, H, W, int(max_split), device=dev,
+                           refuse=lambda: ValueError(f"camo_split_instances does not support N = {N}, H = {H}, W = {W} (a side is at most {_lib.SEG_WF_MAX_SIDE})"))
     out = torch.empty_like(labels)
     table = torch.empty(N, int(max_instances), _lib.INST_FIELDS, dtype=torch.int64, device=dev)
     counts = torch.empty(N, _lib.SPLIT_COUNTS, dtype=torch.int32, device=dev)
     args = (_ptr(labels), None if pred is None else _ptr(pred), stride, N, H, W, num, den, int(min_core), int(max_split), int(max_instances), _ptr(out),
             _ptr(table), _ptr(counts), _ptr(ws), nbytes)
     if not geodesic:
-        with torch.cuda.device(dev):
-            rc = L.camo_split_instances(*args, _stream_ptr(dev))
-        _lib.check(rc, "camo_split_instances")
+        call("camo_split_instances", dev, *args, _stream_ptr(dev))
         return {"labels": out, "table": table, "counts": counts}
     T = _lib.SPLIT_GEO_TILE
     step = int(rounds) if rounds is not None else min(-(-H // T) + -(-W // T), _lib.SPLIT_GEO_MAX_ROUNDS)
     pending = torch.empty(N, dtype=torch.int32, device=dev)
-    call, name, total = L.camo_split_instances_geodesic, "camo_split_instances_geodesic", 0
+    entry, total = "camo_split_instances_geodesic", 0
     while True:
-        with torch.cuda.device(dev):
-            rc = call(*args, _stream_ptr(dev), step, _ptr(pending))
-        _lib.check(rc, name)
+        call(entry, dev, *args, _stream_ptr(dev), step, _ptr(pending))
         total += step
         if not any(pending.tolist()):                              # (the host synchronisation)
             return {"labels": out, "table": table, "counts": counts, "rounds": total}
-        call, name, step = L.camo_split_geodesic_resume, "camo_split_geodesic_resume", min(2 * step, _lib.SPLIT_GEO_MAX_ROUNDS)
+        entry, step = "camo_split_geodesic_resume", min(2 * step, _lib.SPLIT_GEO_MAX_ROUNDS)
 
 
 def split_records(table, counts, H, W):

@@ -243,6 +243,14 @@ def test_random_cod_augmentation_is_reproducible_and_in_range():
     assert all(AR.row_ok([0, H, W, 3 * W, 3, 1] + r + list(k) + [0, 0], 3, H * W * 3, True) for (H, W), r, k in zip(sizes, rows, a["factors"]))
 
 
+def test_random_cod_augmentation_pinned_draws():
+    """The order and number of draws from the generator are part of the function: a seed gives exactly this dict."""
+    from camouflage_multimodal_amd.augment import random_cod_augmentation
+    assert random_cod_augmentation([(33, 70), (8, 9), (600, 800)], seed=5) == {
+        "crops": [(0, 8, 33, 42), (1, 1, 7, 6), (2, 4, 591, 769)], "flips": [1, 0, 0], "angles": [0.0, 0.0, 0.0],
+        "factors": [(253, 382, 414, 499), (132, 152, 423, 640), (344, 286, 288, 283)]}
+
+
 GOOD = [0, 8, 9, 27, 3, 1, 1, 2, 6, 5, 32768, 0, -32768, 0, 32768, -32768, 0, FILL, 256, 0, 1024, 300, 0, 0]
 # one row per violated condition: (field, value, only with enhance = 1)
 VIOLATIONS = ((1, 0, False), (1, 8193, False), (2, 0, False), (8, 0, False), (9, 8193, False), (6, -1, False), (7, -1, False), (6, 3, False),

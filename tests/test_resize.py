@@ -179,6 +179,12 @@ def test_random_resized_crops():
     assert whole == [(0, 0, H, W) for H, W in sizes]
 
 
+def test_random_resized_crops_pinned_draws():
+    """The order and number of draws from the generator are part of the function: a seed gives these boxes and flips."""
+    from camouflage_multimodal_amd import random_resized_crops
+    assert random_resized_crops([(33, 70), (8, 9), (600, 800)], seed=5) == ([(0, 8, 33, 42), (0, 0, 7, 7), (44, 205, 476, 545)], [1, 1, 1])
+
+
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
 
 def _want(images, size, f, out, crops=None, flips=None):

@@ -18,32 +18,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import augment_ref as AR
+from dev_timing import alternate
 
 SIZE = (256, 256)
 BATCHES = ((16, 768, 1024), (16, 256, 256))
-
-
-def window(fn, iters):
-    import torch
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters): fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / iters * 1e3
-
-
-def alternate(fns, iters, windows=5):
-    """{name: (smallest, largest) microseconds per call}: every function warmed up, then one window each in turn, ``windows`` times."""
-    import torch
-    for fn in fns.values():
-        for _ in range(20): fn()
-    torch.cuda.synchronize()
-    us = {k: [] for k in fns}
-    for _ in range(windows):
-        for k, fn in fns.items():
-            us[k].append(window(fn, iters))
-    return {k: (min(v), max(v)) for k, v in us.items()}
 
 
 def scene(N, H, W, seed=0):

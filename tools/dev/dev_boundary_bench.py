@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import boundary_ref as B
 import inst_match_ref as R
-from dev_inst_match_bench import inputs as match_inputs, timed
+from dev_inst_match_bench import inputs as match_inputs
+from dev_timing import timed
 
 P = G = 64
 SHAPES = {"labels": (256, 256, 7), "labels_big": (768, 1024, 26), "labels_big_d1": (768, 1024, 1)}
@@ -105,7 +106,7 @@ def calls():
         for N in (1, 16):
             lab = blobs(N, H, W)
             call, out, dev = prepared_labels(lab, d)
-            t = timed(call)
+            t = timed(call, 200)
             best = None
             for _ in range(3):
                 torch.cuda.synchronize()
@@ -122,7 +123,7 @@ def calls():
             pred, gt, pb, gb, table = match_case(N, name)
             plain, _, _ = prepared_match(N, pred, gt, pb, gb, table, False)
             call, out, _ = prepared_match(N, pred, gt, pb, gb, table, True)
-            tp, tb = timed(plain), timed(call)
+            tp, tb = timed(plain, 200), timed(call, 200)
             want = B.boundary_match_image(pred[0], gt[0], pb[0], gb[0], P, G, table[0], R.COCO)
             same = all(np.array_equal(out[k][0].cpu().numpy(), want[k]) for k in want)
             print(f"camo_boundary_match N = {N:2d}, 256 x 256, d = 7, P = G = {P}, {name:5s}: {tb[0]:.1f} us (up to {tb[1]:.1f}) per call, 7 launches; "

@@ -12,23 +12,9 @@ import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+from dev_timing import timed
 
 STREAM_BYTES_PER_US = 6.29e6        # tools/dev/microbench/stream_bench.hip: the measured float4 copy rate of the MI355X
-
-
-def timed(fn, iters, windows=5, warm=5):
-    import torch
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def filter_bytes(N, H, W, C):
@@ -76,7 +62,7 @@ def bench_filter():
                 def call():
                     rc = L.camo_guided_filter(_ptr(I), _ptr(p), H * W, N, H, W, C, r, 1e-4, 1, _ptr(q), _ptr(coef), _ptr(ws), nbytes, st)
                     if rc != 0: raise RuntimeError(L.camo_last_error())
-                t = timed(call, 50 if N == 1 else 10)
+                t = timed(call, 50 if N == 1 else 10, warm=5)
                 u = timed(lambda: torch_filter(I, p, r, 1e-4), 5, windows=3, warm=2)
                 diff = float((torch_filter(I, p, r, 1e-4) - q).abs().max())
                 print(f"filter N = {N:2d}, 256 x 256, C = {C}, r = {r:2d}: {t[0]:.1f} us (up to {t[1]:.1f}) = {t[0] / floor:.1f} x the traffic floor of "
@@ -100,7 +86,7 @@ def bench_apply():
             up = torch.stack(planes).double()
             g = native.permute(0, 3, 1, 2).double() / 255.0
             return ((up[:, :C] * g).sum(1) + up[:, C]).clamp(0, 1).float()
-        t = timed(lambda: guided_upsample(coef, packed), 20)
+        t = timed(lambda: guided_upsample(coef, packed), 20, warm=5)
         u = timed(composed, 5, windows=3, warm=2)
         diff = float((composed() - guided_upsample(coef, packed)[1].view(N, H, W)).abs().max())
         print(f"apply N = {N}, 256 x 256 -> {H} x {W}, C = {C}: {t[0]:.1f} us (up to {t[1]:.1f}) per call (with the table upload) = {t[0] / floor:.1f} x the "

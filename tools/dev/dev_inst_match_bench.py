@@ -15,6 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import inst_match_ref as R
+from dev_timing import timed
 
 H = W = 256
 P = G = 64
@@ -35,21 +36,6 @@ def inputs(N):
     table[..., 0] = rs.randint(1, 4000, (N, P))
     table[..., 7] = (table[..., 0] * rs.uniform(128, 255, (N, P))).astype(np.int64)
     return {"blobs": (blobs, np.roll(blobs, (3, 5), (1, 2))), "pairs": (pairs, pairs_gt)}, table
-
-
-def timed(fn, iters=200, windows=5):
-    import torch
-    for _ in range(20): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def prepared(N, pred, gt, table):
@@ -79,7 +65,7 @@ def calls():
         maps, table = inputs(N)
         for name, (pred, gt) in maps.items():
             call, out, (pl, gl) = prepared(N, pred, gt, table)
-            t = timed(call)
+            t = timed(call, 200)
             want = R.match_image(pred[0], gt[0], P, G, table[0], R.COCO)
             same = all(np.array_equal(out[k][0].cpu().numpy(), want[k]) for k in want)
             print(f"N = {N:2d}, {H} x {W}, P = G = {P}, {name:5s}: {t[0]:.1f} us (up to {t[1]:.1f}) per call, {LAUNCHES} launches; ids in use "

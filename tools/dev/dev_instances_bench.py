@@ -14,6 +14,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import instances_ref as R
+from dev_timing import timed
 
 SIZES = ((16, 256, 256, 200), (1, 1024, 1024, 50))
 COPY_BYTES_PER_US = 6.29e6          # measured float4 copy bandwidth of the MI355X
@@ -33,21 +34,6 @@ def inputs(N, H, W):
         blobs[i, ys, xs] = 1.0 - blobs[i, ys, xs]
     noise = rs.uniform(0, 1, (N, H, W)).astype(np.float32)
     return {"blobs": blobs, "noise": noise}
-
-
-def timed(fn, iters, windows=5):
-    import torch
-    for _ in range(20): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def launches(only_n=None, only_name=None):

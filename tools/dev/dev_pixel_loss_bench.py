@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rg_pixel_loss_ref as PR
 import rg_targets_ref as TG
-from dev_instances_bench import COPY_BYTES_PER_US, inputs, timed
+from dev_instances_bench import COPY_BYTES_PER_US, inputs
+from dev_timing import timed
 from oracle import rg_features_oracle as FO
 
 H = W = 256

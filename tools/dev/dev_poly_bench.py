@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import poly_ref as P
 import rle_ref as R
+from dev_timing import timed
 
 LOADS = {"a": (16, 256, 256, 4), "b": (1, 768, 1024, 20)}
 VERTICES = 100
@@ -34,21 +35,6 @@ def load(name):
             anns.append(([np.stack([cx + rad * np.cos(ang), cy + rad * np.sin(ang)], axis=1).reshape(-1).tolist()], k + 1))
         per.append(anns)
     return per, N, H, W
-
-
-def timed(fn, iters=200, windows=5):
-    import torch
-    for _ in range(20): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def wall(fn, repeats=3):
@@ -113,7 +99,7 @@ def calls():
         host_us = (time.perf_counter() - t0) * 1e6
         tu, _ = wall(lambda: torch.from_numpy(want).cuda())
         call, labels, (A, Pn, V) = prepared_poly(per, N, H, W)
-        t = timed(call)
+        t = timed(call, 200)
         same = labels.cpu().numpy().tobytes() == want.tobytes()
         points = sum(len(P.boundary_points(*P.scaled_vertices(p))[0]) for anns in per for polys, _ in anns for p in polys)
         print(f"load ({name}): N = {N}, {H} x {W}, {A} annotations, {V} vertices, {points} boundary points: camo_poly_decode {t[0]:.1f} us (up to {t[1]:.1f}) "
@@ -123,7 +109,7 @@ def calls():
         # the existing way in: every annotation's own mask as an RLE (rasterised on the host beforehand, not timed)
         rles = [[({"size": [H, W], "counts": counts_to_string(R.mask_counts(P.label_map([(polys, 1)], H, W) > 0))}, v) for polys, v in anns] for anns in per]
         call, back, total = prepared_rle(rles, N, H, W)
-        t = timed(call)
+        t = timed(call, 200)
         print(f"        camo_rle_decode on the RLEs of the same masks {t[0]:.1f} us (up to {t[1]:.1f}) per call, 2 launches, {total} counts; "
               f"{'equal' if back.cpu().numpy().tobytes() == want.tobytes() else 'DIFFERENT'}", flush=True)
         tw, got = wall(lambda: decode_rles(rles, H, W))

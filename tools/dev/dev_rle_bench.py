@@ -15,6 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import rle_ref as R
+from dev_timing import timed
 
 H = W = 256
 CAP = 32768
@@ -34,21 +35,6 @@ def inputs(N):
     noise = rs.uniform(0, 1, (N, H, W)).astype(np.float32)
     return {"blobs": mask_instances(torch.from_numpy(blobs).cuda(), 0.5, 8, 0, False, 64)["labels"],
             "noise": mask_instances(torch.from_numpy(noise).cuda(), 0.45, 8, 8, False, 64)["labels"]}
-
-
-def timed(fn, iters=200, windows=5):
-    import torch
-    for _ in range(20): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def wall(fn, repeats=3):
@@ -125,7 +111,7 @@ def calls():
         for name, labels in inputs(N).items():
             host = labels.cpu().numpy()
             call, runs, counts = prepared_runs(labels)
-            t = timed(call)
+            t = timed(call, 200)
             want = R.runs_batch(host, CAP)
             same = np.array_equal(runs.cpu().numpy(), want["runs"]) and np.array_equal(counts.cpu().numpy(), want["counts"])
             print(f"N = {N:2d}, {H} x {W}, {name:5s}: camo_rle_runs {t[0]:.1f} us (up to {t[1]:.1f}) per call, 3 launches; runs per image up to "
@@ -137,7 +123,7 @@ def calls():
             if not any(rles):
                 continue
             call, back, (A, total) = prepared_decode(rles)
-            t = timed(call)
+            t = timed(call, 200)
             same = torch.equal(back, labels)
             print(f"        camo_rle_decode {t[0]:.1f} us (up to {t[1]:.1f}) per call, 2 launches, {A} annotations, {total} counts; "
                   f"{'equal to' if same else 'DIFFERENT FROM'} the label maps", flush=True)

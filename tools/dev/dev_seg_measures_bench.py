@@ -12,6 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import seg_measures_ref as R
+from dev_timing import timed
 from oracle import rg_features_oracle as FO
 
 N, H, W = 16, 352, 352
@@ -28,21 +29,6 @@ def inputs():
     painted = np.stack([rs.uniform(0, 1, 501).astype(np.float32)[FO.voronoi_segments(H, W, 500, 10 + i)] for i in range(N)])
     saturated = (gt > 127).astype(np.float32)
     return gt, {"uniform": uniform, "painted": painted, "saturated": saturated}
-
-
-def timed(fn, iters=200, windows=5):
-    import torch
-    for _ in range(20): fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters): fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / iters)
-    return min(ms) * 1e3, max(ms) * 1e3
 
 
 def launches():
@@ -67,8 +53,8 @@ def launches():
 
         def check(rc):
             if rc != 0: raise RuntimeError(L.camo_last_error())
-        tc = timed(lambda: check(L.camo_seg_counts(_ptr(p), H * W, _ptr(g), 0.5, N, H, W, _ptr(counts), st)))
-        th = timed(lambda: check(L.camo_seg_histograms(_ptr(p), H * W, _ptr(g), N, H, W, _ptr(hist), _ptr(split), st)))
+        tc = timed(lambda: check(L.camo_seg_counts(_ptr(p), H * W, _ptr(g), 0.5, N, H, W, _ptr(counts), st)), 200)
+        th = timed(lambda: check(L.camo_seg_histograms(_ptr(p), H * W, _ptr(g), N, H, W, _ptr(hist), _ptr(split), st)), 200)
         tw = timed(lambda: check(L.camo_seg_weighted_f(_ptr(p), H * W, _ptr(g), N, H, W, _ptr(gauss), _ptr(ws), nbytes, _ptr(sums), st)), iters=50)
         print(f"N = {N}, {H} x {W}, {name:9s}: camo_seg_counts {tc[0]:.1f} us (up to {tc[1]:.1f}), camo_seg_histograms {th[0]:.1f} us (up to {th[1]:.1f}), "
               f"camo_seg_weighted_f {tw[0]:.1f} us (up to {tw[1]:.1f}) per call", flush=True)

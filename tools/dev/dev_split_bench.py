@@ -18,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import instances_ref as IR
 import split_ref as R
-from dev_instances_bench import COPY_BYTES_PER_US, SIZES, inputs, timed
+from dev_instances_bench import COPY_BYTES_PER_US, SIZES, inputs
+from dev_timing import timed
 
 ROWS = 64
 

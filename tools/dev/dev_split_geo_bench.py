@@ -15,7 +15,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import split_geo_ref as G
-from dev_instances_bench import SIZES, inputs, timed
+from dev_instances_bench import SIZES, inputs
+from dev_timing import timed
 from dev_split_bench import ROWS, label_maps
 
 SPIRAL = ((20, 20), (20, 25), (15, 25), (15, 15), (25, 15), (25, 30), (10, 30), (10, 10), (30, 10), (30, 35), (5, 35), (5, 5), (36, 5))
