@@ -71,6 +71,8 @@ SPLIT_GEO_TILE = 32                 # CAMO_SPLIT_GEO_TILE
 SPLIT_GEO_MAX_ROUNDS = 1024         # CAMO_SPLIT_GEO_MAX_ROUNDS
 SPLIT_GEO_LAUNCHES = 13             # CAMO_SPLIT_GEO_LAUNCHES (plus the rounds)
 SPLIT_GEO_RESUME_LAUNCHES = 2       # CAMO_SPLIT_GEO_RESUME_LAUNCHES (plus the rounds)
+SPLIT_MERGE_COUNTS = 4              # CAMO_SPLIT_MERGE_COUNTS
+SPLIT_MERGE_LAUNCHES = 6            # CAMO_SPLIT_MERGE_LAUNCHES
 GF_MAX_RADIUS = 64                  # CAMO_GF_MAX_RADIUS
 GF_MIN_EPS, GF_MAX_EPS = 1e-6, 1.0  # CAMO_GF_MIN_EPS, CAMO_GF_MAX_EPS
 GF_FIELDS = 4                       # CAMO_GF_FIELDS
@@ -251,6 +253,10 @@ PROTOTYPES = {
         ("camo_split_geodesic_workspace_bytes", sz, (i32, i32, i32, i32)),
         ("camo_split_instances_geodesic", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
         ("camo_split_geodesic_resume", i32, (vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp, i32, vp)),
+    ),
+    "camo_split_merge.h": (
+        ("camo_split_merge_workspace_bytes", sz, (i32, i32, i32)),
+        ("camo_split_merge", i32, (vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp)),
     ),
     "camo_augment.h": (
         ("camo_augment_workspace_bytes", sz, (i32, i32, i32, i32, i32)),

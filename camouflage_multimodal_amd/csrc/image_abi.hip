@@ -1,5 +1,5 @@
 // C ABI of the image pipeline around the detector (include/camo_instances.h, camo_inst_match.h, camo_boundary.h, camo_guided.h,
-// camo_rle.h, camo_poly.h, camo_split.h, camo_split_geo.h): argument checks, workspace carving and the launchers' calls.  No device code here.
+// camo_rle.h, camo_poly.h, camo_split.h, camo_split_geo.h, camo_split_merge.h): argument checks, workspace carving and the launchers' calls.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +21,7 @@
 #include "../../include/camo_poly.h"
 #include "../../include/camo_split.h"
 #include "../../include/camo_split_geo.h"
+#include "../../include/camo_split_merge.h"
 
 using namespace camo_abi;
 
@@ -236,6 +237,36 @@ int camo_split_geodesic_resume(const int32_t* labels, const float* pred, int64_t
     return e;
   CK(launch_split_geo_resume(labels, pred, pred_image_stride, N, H, W, max_instances, rounds, w, out_labels, reinterpret_cast<long long*>(table), counts,
                              pending, static_cast<hipStream_t>(stream)), "split instances, geodesic resume");
+  return 0;
+}
+
+// ---- Low-dynamic cores merged: a post-pass on either growth's part map (include/camo_split_merge.h) ----------------
+size_t camo_split_merge_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+  if (split_check(N, H, W, 1)) return 0;
+  return split_merge_carve(N, H, W, nullptr).bytes;
+}
+
+int camo_split_merge(const int32_t* labels, const int32_t* parts, const float* pred, int64_t pred_image_stride, int32_t N, int32_t H, int32_t W,
+                     int32_t merge_num, int32_t merge_den, int32_t max_instances, int32_t* out_labels, int64_t* table, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream) {
+  if (int e = split_check(N, H, W, 1)) return e;
+  if (merge_den < 1 || merge_den > CAMO_SPLIT_MAX_DEN) return fail(CAMO_E_ARG, "merge_den must be in [1, CAMO_SPLIT_MAX_DEN]");
+  if (merge_num < 1 || merge_num > merge_den) return fail(CAMO_E_ARG, "merge_num must be in [1, merge_den]");
+  if (max_instances < 1) return fail(CAMO_E_ARG, "max_instances must be >= 1");
+  if ((long long)N * max_instances > CAMO_INST_MAX_ROWS) return fail(CAMO_E_ARG, "N * max_instances exceeds CAMO_INST_MAX_ROWS");
+  if (pred && pred_image_stride < (long long)H * W) return fail(CAMO_E_ARG, "pred_image_stride must be >= H * W");
+  if (!labels) return fail(CAMO_E_ARG, "labels is null");
+  if (!parts) return fail(CAMO_E_ARG, "parts is null");
+  if (!out_labels || !table || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(CAMO_E_ARG, "table must be 8-byte aligned");
+  const uintptr_t a = reinterpret_cast<uintptr_t>(labels), p = reinterpret_cast<uintptr_t>(parts), b = reinterpret_cast<uintptr_t>(out_labels),
+                  bytes = (uintptr_t)N * H * W * 4;
+  if (a < b + bytes && b < a + bytes) return fail(CAMO_E_ARG, "labels and out_labels must not overlap");
+  if (p < b + bytes && b < p + bytes) return fail(CAMO_E_ARG, "parts and out_labels must not overlap");
+  const SplitMergeWs w = split_merge_carve(N, H, W, ws);
+  if (int e = ws_check(ws, ws_bytes, w.bytes, "camo_split_merge_workspace_bytes")) return e;
+  CK(launch_split_merge(labels, parts, pred, pred_image_stride, N, H, W, merge_num, merge_den, max_instances, w, out_labels,
+                        reinterpret_cast<long long*>(table), counts, static_cast<hipStream_t>(stream)), "split merge");
   return 0;
 }
 

@@ -1,4 +1,5 @@
-// Instance splitter (split.hip, split_geo.hip, split_inl.h; include/camo_split.h, include/camo_split_geo.h): the
+// Instance splitter (split.hip, split_geo.hip, split_merge.hip, split_inl.h; include/camo_split.h, include/camo_split_geo.h,
+// include/camo_split_merge.h): the
 // constants the kernels, the launchers and the entry points share.  The launchers return hipError_t as int.
 #pragma once
 #include "common.h"
@@ -29,6 +30,21 @@ SplitWs split_carve(int N, int H, int W, int max_split, void* base, bool sites =
 
 int launch_split(const int* labels, const float* pred, long long stride, int N, int H, int W, int num, int den, int min_core, int max_split,
                  int max_instances, const SplitWs& ws, int* out, long long* table, int* counts, hipStream_t stream);
+
+// ---- low-dynamic cores merged (split_merge.hip, include/camo_split_merge.h) -------------------------------------------
+struct SplitMergeWs {
+  int* d2;                   // [N][H][W] the nearest background row of the pixel's column, then D2 (-1: the image has no background)
+  unsigned long long* pass;  // [N][SPLIT_IDS_PAD] per part (its best contact value with a higher part << 11) | (2047 - that part), 0: none
+  int* peak;                 // [N][SPLIT_IDS_PAD] peak(part) + 2, 0: the part has no pixel
+  int* owner;                // [N][SPLIT_IDS_PAD] the largest input id over the part's pixels
+  int* new_id;               // [N][SPLIT_IDS_PAD] the part's new id, 0: the part has no pixel
+  int* bad;                  // [N] 1: a foreground pixel holds a part value out of range, the image is not supported
+  size_t bytes;
+};
+SplitMergeWs split_merge_carve(int N, int H, int W, void* base);
+
+int launch_split_merge(const int* labels, const int* parts, const float* pred, long long stride, int N, int H, int W, int num, int den,
+                       int max_instances, const SplitMergeWs& ws, int* out, long long* table, int* counts, hipStream_t stream);
 
 // ---- geodesic growth (split_geo.hip, include/camo_split_geo.h) ----------------------------------------------------
 constexpr int SPLIT_GEO_TILE = 32;         // CAMO_SPLIT_GEO_TILE: a grow block's tile, INST_TILE

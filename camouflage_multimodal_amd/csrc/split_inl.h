@@ -1,7 +1,8 @@
 // The kernels of the instance splitter that both growth rules run (split.hip: the Euclidean cells of include/camo_split.h;
 // split_geo.hip: the geodesic cells of include/camo_split_geo.h), stated once as cc_inl.h and label_inl.h state
 // theirs: the ten launches from the distance transform to each kept core's new id, and the table over out_labels.  Each file that
-// includes this states its own launch list; the kernels have internal linkage.
+// includes this states its own launch list; the kernels have internal linkage.  split_merge.hip (include/camo_split_merge.h, 10u)
+// takes the device functions only: column_nearest, row_distance2 and table_rows.
 //
 //   column   per column the nearest background row of every pixel, 16 columns by 16 row segments a block (column_nearest); the first
 //            block of an image clears its per-id arrays
@@ -86,10 +87,23 @@ __global__ __launch_bounds__(NT) void split_column_kernel(const int* __restrict_
   column_nearest(H, W, x < W, [&](int y) { return split_id(g[(size_t)y * W]) == 0; }, ny + (size_t)n * H * W + min(x, W - 1));
 }
 
-// grid (H, N): a block takes one row.  A foreground pixel starts from its own column's distance and looks at the columns dx to the
-// left and right for as long as dx^2 alone is below the best: nothing farther can be nearer.  The row is overwritten in place with D2
-// (0 on background, -1 when the image has no background: then no column of the row has a row to offer).  top[id] = the row's largest
-// D2 + 2 (so that an id with a pixel is never 0), added to m2 once per block and id.
+// D2 of the foreground pixel (y, x) from row[]: the nearest background row of every column of the image, as column_nearest leaves
+// it, staged in LDS.  The pixel starts from its own column's distance and looks at the columns dx to the left and right for as long
+// as dx^2 alone is below the best: nothing farther can be nearer.  -1 when no column has a row to offer: the image has no background.
+// (split_d2_kernel, and split_merge.hip's d2 launch)
+__device__ __forceinline__ int row_distance2(const int* row, int W, int x, int y) {
+  int best = FAR;
+  int r = row[x];
+  if (r >= 0) best = (y - r) * (y - r);
+  for (int dx = 1; dx * dx < best && (dx <= x || x + dx < W); ++dx) {
+    if (dx <= x && (r = row[x - dx]) >= 0) best = min(best, dx * dx + (y - r) * (y - r));
+    if (x + dx < W && (r = row[x + dx]) >= 0) best = min(best, dx * dx + (y - r) * (y - r));
+  }
+  return best == FAR ? -1 : best;
+}
+
+// grid (H, N): a block takes one row.  The row is overwritten in place with D2 (row_distance2; 0 on background, -1 when the image has
+// no background).  top[id] = the row's largest D2 + 2 (so that an id with a pixel is never 0), added to m2 once per block and id.
 __global__ __launch_bounds__(NT) void split_d2_kernel(const int* __restrict__ labels, int H, int W, int* __restrict__ d2, int* __restrict__ m2) {
   __shared__ int row[SIDE];
   __shared__ int top[IDS];
@@ -103,14 +117,7 @@ __global__ __launch_bounds__(NT) void split_d2_kernel(const int* __restrict__ la
     const int id = split_id(lab[x]);
     int best = 0;
     if (id) {
-      best = FAR;
-      int r = row[x];
-      if (r >= 0) best = (y - r) * (y - r);
-      for (int dx = 1; dx * dx < best && (dx <= x || x + dx < W); ++dx) {
-        if (dx <= x && (r = row[x - dx]) >= 0) best = min(best, dx * dx + (y - r) * (y - r));
-        if (x + dx < W && (r = row[x + dx]) >= 0) best = min(best, dx * dx + (y - r) * (y - r));
-      }
-      if (best == FAR) best = -1;
+      best = row_distance2(row, W, x, y);
       if (top[id] < best + 2) atomicMax(&top[id], best + 2);
     }
     d[x] = best;
@@ -293,10 +300,10 @@ __global__ __launch_bounds__(NT) void split_rank_kernel(const int* __restrict__ 
   }
 }
 
-// grid (chunks, images): the table's rows from out; Sq from pred, 0 when it is null
-__global__ __launch_bounds__(NT) void split_table_kernel(const float* __restrict__ pred, long long stride, const int* __restrict__ out, int H, int W,
-                                                         int max_instances, unsigned long long* __restrict__ table) {
-  __shared__ EmitSlots slots;
+// Image blockIdx.y's rows of the table from out, the block's chunk of 1024 pixels of them; Sq from pred, 0 when it is null.  Every
+// thread of a grid (chunks, images) calls (split_table_kernel, and split_merge.hip's table launch).
+__device__ __forceinline__ void table_rows(EmitSlots& slots, const float* __restrict__ pred, long long stride, const int* __restrict__ out, int H, int W,
+                                           int max_instances, unsigned long long* __restrict__ table) {
   const int tid = threadIdx.x, n = blockIdx.y, HW = H * W;
   const size_t base = (size_t)n * HW;
   emit_slots_clear(slots);
@@ -317,6 +324,13 @@ __global__ __launch_bounds__(NT) void split_table_kernel(const float* __restrict
   }
   __syncthreads();
   emit_slots_flush(slots, rows);
+}
+
+// grid (chunks, images): the table's rows from out
+__global__ __launch_bounds__(NT) void split_table_kernel(const float* __restrict__ pred, long long stride, const int* __restrict__ out, int H, int W,
+                                                         int max_instances, unsigned long long* __restrict__ table) {
+  __shared__ EmitSlots slots;
+  table_rows(slots, pred, stride, out, H, W, max_instances, table);
 }
 
 unsigned blocks_of(long long count) { return (unsigned)((count + NT - 1) / NT); }

@@ -185,7 +185,10 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     necks (``split.split_detected``, include/camo_split.h) and adds "split_instances" (per image the records of
     ``split.split_records``, scored by the mask probability), "split_labels" int32 [N, H, W] and "split_counts" int32 [N, 4].
     ``match``, ``boundary`` and ``rle`` then work on the split labels and table, so instance AP and Boundary AP measure the split;
-    "instances", "instance_labels", "clean_mask" and every metric of the mask keep their bytes."""
+    "instances", "instance_labels", "clean_mask" and every metric of the mask keep their bytes.  "merge" in ``split`` -- a pair
+    (num, den), e.g. (4, 5) -- joins the parts across their high passes after the split (``split.merge_parts``,
+    include/camo_split_merge.h): "split_instances" and "split_labels" are then the merged ones, "split_counts" stays the splitter's,
+    and the one key more is "split_merge_counts" int32 [N, 4]."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
@@ -223,6 +226,8 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
         if split is not None:
             found = _split_found(found, prob_maps[:, 0], split)
             out.update({"split_instances": found["instances"], "split_labels": found["labels"], "split_counts": found["counts"]})
+            if "merge" in split:
+                out["split_merge_counts"] = found["merge_counts"]
         if match is not None:
             gt_labels = match["gt_labels"]      # (a [N, H, W] tensor goes on as it is: ``match_detected`` holds it to the labels' shape)
             if gt_labels is None:
@@ -293,7 +298,8 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     scored at native size, "boundary_iou" of "mask_native" and, with ``refine``, "refined_boundary_iou" of "mask_native_refined".
     ``split`` (``detect_camouflage_batch``'s; needs ``instances=True``) splits the NATIVE-size instances, maps of equal size sharing a
     call: "split_instances_native" (per image the records), "split_labels_native" (int32 [H_i, W_i]) and "split_counts_native"
-    (int32 [4]); ``match``, ``boundary`` and ``rle`` then work on them."""
+    (int32 [4]); ``match``, ``boundary`` and ``rle`` then work on them.  With "merge" in ``split`` they are the merged ones, and
+    "split_merge_counts_native" (int32 [4] per image) is the one key more."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
@@ -339,10 +345,12 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
         if split is not None:
             def parts(idx, _):
                 f = _split_found({"instances": [rec[i] for i in idx], "labels": _stack(labels, idx)}, _stack(native, idx), split)
-                return f["instances"], f["labels"], f["table"], f["counts"]
+                return f["instances"], f["labels"], f["table"], f["counts"], f.get("merge_counts", [None] * len(idx))
 
-            split_rec, labels, tables, split_counts = _by_size(native, parts, 4)
+            split_rec, labels, tables, split_counts, merge_counts = _by_size(native, parts, 5)
             out.update({"split_instances_native": split_rec, "split_labels_native": labels, "split_counts_native": split_counts})
+            if "merge" in split:
+                out["split_merge_counts_native"] = merge_counts
         if match is not None:
             gt_labels = _match_ground_truth(match, len(sizes), "images", sizes, truth, connectivity, img.device)
             out["instance_match"], out["instance_match_tables"] = _native_matches(labels, tables, gt_labels, match)
@@ -399,7 +407,7 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     "boundary_ap": ``InstanceAP`` over them, which is Boundary AP; with masks scored at native size also "boundary_iou" per file and,
     with ``refine``, "refined_boundary_iou".
     With ``split`` (``detect_camouflage_ragged``'s; needs ``instances=True``) the instances matched, scored and written to
-    ``results_json`` are the split ones ("split_instances_native")."""
+    ``results_json`` are the split ones ("split_instances_native"), the merged ones with "merge" in ``split``."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
     found_key = "instances_native" if _split.split_options(kw.get("split", False), kw.get("instances", False)) is None else "split_instances_native"

@@ -343,7 +343,8 @@ class RegionGraphFineTuner(AdamWStateMixin):
         and, with ``match`` (``True`` or ``detect_camouflage_batch``'s dict), "instance_match": the records of the instances
         matched to the ground-truth ones; with ``boundary`` (``detect_camouflage_batch``'s; needs ``match``) also "boundary_match",
         the records under min(mask IoU, boundary IoU), and "boundary_iou" of the thresholded masks.  With ``split``
-        (``detect_camouflage_batch``'s: ``True`` or a dict, ``{"growth": "geodesic"}`` for connected parts; needs ``instances=True``)
+        (``detect_camouflage_batch``'s: ``True`` or a dict, ``{"growth": "geodesic"}`` for connected parts, ``{"merge": (4, 5)}`` to
+        join the parts again across their high passes; needs ``instances=True``)
         also "split_instances", the records of the instances split at their necks, and "instance_match" and "boundary_match" are
         then those of the split instances, as in the pipeline.  ``split=None``: nothing changes."""
         _lib.require_device(self.flat_params, "RegionGraphFineTuner parameters")

@@ -14,7 +14,8 @@
  * byte.
  * A cell is a Euclidean Voronoi cell of its core cut to the component, and in a concave component it may come out in several pieces:
  * include/camo_split_geo.h grows connected cells along paths inside the component instead.
- * Not built: h-maxima marker merging and a per-component absolute radius.
+ * One level set cuts a low lobe off its body as readily as a body off its neighbour: include/camo_split_merge.h joins the parts again
+ * whose pass to a higher part is nearly as high as their own peak.  Not built: a per-component absolute radius.
  *
  * Device pointers only, enqueue-only on `stream` (no allocation, no synchronisation), 0 = ok / CAMO_E_ARG as in camo_fusion.h; every
  * argument check runs on the host before any launch.  The ABI version is that of camo_fusion.h. */

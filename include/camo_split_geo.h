@@ -36,7 +36,8 @@
  * content by reading pending between calls.  tiles_x + tiles_y rounds are enough for every path that is monotone in both axes, a
  * convex blob among them; a corridor needs about one round per tile border it crosses, and one more per CAMO_SPLIT_GEO_TILE * 4
  * pixels it runs inside one tile.
- * Not built here either: h-maxima marker merging, a per-component absolute radius.
+ * Marker merging is a post-pass on the parts of either growth: include/camo_split_merge.h.
+ * Not built here either: a per-component absolute radius.
  *
  * Device pointers only, enqueue-only on `stream` (no allocation, no synchronisation), 0 = ok / CAMO_E_ARG as in camo_fusion.h; every
  * argument check runs on the host before any launch.  The ABI version is that of camo_fusion.h. */
