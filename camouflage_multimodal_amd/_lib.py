@@ -63,6 +63,12 @@ POLY_MAX_POLYGONS = 65535           # CAMO_POLY_MAX_POLYGONS
 POLY_MAX_VERTICES = 1 << 20         # CAMO_POLY_MAX_VERTICES
 POLY_MARGIN = 1024                  # CAMO_POLY_MARGIN
 POLY_MAX_PLANE_WORDS = 1 << 28      # CAMO_POLY_MAX_PLANE_WORDS
+CONTOUR_RING_FIELDS = 5             # CAMO_CONTOUR_RING_FIELDS
+CONTOUR_COUNTS = 6                  # CAMO_CONTOUR_COUNTS
+CONTOUR_MAX_CRACKS = 1 << 26        # CAMO_CONTOUR_MAX_CRACKS
+CONTOUR_MAX_RINGS = 1 << 24         # CAMO_CONTOUR_MAX_RINGS
+CONTOUR_MAX_VERTICES = 1 << 26      # CAMO_CONTOUR_MAX_VERTICES
+CONTOUR_LDS_CRACKS = 1 << 14        # CAMO_CONTOUR_LDS_CRACKS
 SPLIT_MAX_SPLIT = 8                 # CAMO_SPLIT_MAX_SPLIT
 SPLIT_MAX_DEN = 16                  # CAMO_SPLIT_MAX_DEN
 SPLIT_COUNTS = 4                    # CAMO_SPLIT_COUNTS
@@ -244,6 +250,10 @@ PROTOTYPES = {
     "camo_poly.h": (
         ("camo_poly_decode_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
         ("camo_poly_decode", i32, (vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp)),
+    ),
+    "camo_contours.h": (
+        ("camo_contours_workspace_bytes", sz, (i32, i32, i32, i32, i32, i32)),
+        ("camo_contours", i32, (vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp)),
     ),
     "camo_split.h": (
         ("camo_split_workspace_bytes", sz, (i32, i32, i32, i32)),

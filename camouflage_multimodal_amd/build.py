@@ -17,8 +17,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcamo_fusion.so")
-SOURCES = ("gemm.hip", "gemm16.hip", "attn.hip", "attn_fast.hip", "attn_mfma.hip", "misc.hip", "rg_gnn.hip", "rg_features.hip", "rg_batch.hip", "fused_rows.hip", "fused_wide.hip", "fused_wide2.hip", "bwd_wide2.hip", "tail_wide.hip", "attn_maps.hip", "fusion_abi.hip", "rg_abi.hip", "image_abi.hip", "canny.hip", "slic.hip", "rg_detect.hip", "rg_train.hip", "rg_targets.hip", "rg_pixel_loss.hip", "seg_measures.hip", "resize.hip", "instances.hip", "inst_match.hip", "boundary.hip", "guided.hip", "rle.hip", "poly.hip", "split.hip", "split_geo.hip", "split_merge.hip", "augment.hip")
-HEADERS = ("common.h", "abi_util.h", "fusion_ws.h", "gemm.h", "gemm16.h", "attn.h", "misc.h", "rg_gnn.h", "rg_features.h", "rg_batch.h", "canny.h", "slic.h", "rg_detect.h", "rg_train.h", "rg_targets.h", "rg_pixel_loss.h", "seg_measures.h", "instances.h", "inst_match.h", "boundary.h", "guided.h", "rle.h", "poly.h", "split.h", "split_inl.h", "inst_emit_inl.h", "resize_taps.h", "cc_inl.h", "label_inl.h", "fused_rows.h", "shadow_inl.h", "mfma_inl.h", "wide2_inl.h", "tail_wide.h", "attn_maps.h", os.path.join("..", "..", "include", "camo_fusion.h"), os.path.join("..", "..", "include", "camo_rg_gnn.h"), os.path.join("..", "..", "include", "camo_rg_features.h"), os.path.join("..", "..", "include", "camo_rg_batch.h"), os.path.join("..", "..", "include", "camo_canny.h"), os.path.join("..", "..", "include", "camo_slic.h"), os.path.join("..", "..", "include", "camo_rg_detect.h"), os.path.join("..", "..", "include", "camo_rg_train.h"), os.path.join("..", "..", "include", "camo_rg_train_bn.h"), os.path.join("..", "..", "include", "camo_rg_train_drop.h"), os.path.join("..", "..", "include", "camo_rg_targets.h"), os.path.join("..", "..", "include", "camo_rg_pixel_loss.h"), os.path.join("..", "..", "include", "camo_seg_measures.h"), os.path.join("..", "..", "include", "camo_resize.h"), os.path.join("..", "..", "include", "camo_instances.h"), os.path.join("..", "..", "include", "camo_inst_match.h"), os.path.join("..", "..", "include", "camo_boundary.h"), os.path.join("..", "..", "include", "camo_guided.h"), os.path.join("..", "..", "include", "camo_rle.h"), os.path.join("..", "..", "include", "camo_poly.h"), os.path.join("..", "..", "include", "camo_split.h"), os.path.join("..", "..", "include", "camo_split_geo.h"), os.path.join("..", "..", "include", "camo_split_merge.h"), os.path.join("..", "..", "include", "camo_augment.h"))
+SOURCES = ("gemm.hip", "gemm16.hip", "attn.hip", "attn_fast.hip", "attn_mfma.hip", "misc.hip", "rg_gnn.hip", "rg_features.hip", "rg_batch.hip", "fused_rows.hip", "fused_wide.hip", "fused_wide2.hip", "bwd_wide2.hip", "tail_wide.hip", "attn_maps.hip", "fusion_abi.hip", "rg_abi.hip", "image_abi.hip", "canny.hip", "slic.hip", "rg_detect.hip", "rg_train.hip", "rg_targets.hip", "rg_pixel_loss.hip", "seg_measures.hip", "resize.hip", "instances.hip", "inst_match.hip", "boundary.hip", "guided.hip", "rle.hip", "poly.hip", "contours.hip", "split.hip", "split_geo.hip", "split_merge.hip", "augment.hip")
+HEADERS = ("common.h", "abi_util.h", "fusion_ws.h", "gemm.h", "gemm16.h", "attn.h", "misc.h", "rg_gnn.h", "rg_features.h", "rg_batch.h", "canny.h", "slic.h", "rg_detect.h", "rg_train.h", "rg_targets.h", "rg_pixel_loss.h", "seg_measures.h", "instances.h", "inst_match.h", "boundary.h", "guided.h", "rle.h", "poly.h", "contours.h", "split.h", "split_inl.h", "inst_emit_inl.h", "resize_taps.h", "cc_inl.h", "label_inl.h", "fused_rows.h", "shadow_inl.h", "mfma_inl.h", "wide2_inl.h", "tail_wide.h", "attn_maps.h", os.path.join("..", "..", "include", "camo_fusion.h"), os.path.join("..", "..", "include", "camo_rg_gnn.h"), os.path.join("..", "..", "include", "camo_rg_features.h"), os.path.join("..", "..", "include", "camo_rg_batch.h"), os.path.join("..", "..", "include", "camo_canny.h"), os.path.join("..", "..", "include", "camo_slic.h"), os.path.join("..", "..", "include", "camo_rg_detect.h"), os.path.join("..", "..", "include", "camo_rg_train.h"), os.path.join("..", "..", "include", "camo_rg_train_bn.h"), os.path.join("..", "..", "include", "camo_rg_train_drop.h"), os.path.join("..", "..", "include", "camo_rg_targets.h"), os.path.join("..", "..", "include", "camo_rg_pixel_loss.h"), os.path.join("..", "..", "include", "camo_seg_measures.h"), os.path.join("..", "..", "include", "camo_resize.h"), os.path.join("..", "..", "include", "camo_instances.h"), os.path.join("..", "..", "include", "camo_inst_match.h"), os.path.join("..", "..", "include", "camo_boundary.h"), os.path.join("..", "..", "include", "camo_guided.h"), os.path.join("..", "..", "include", "camo_rle.h"), os.path.join("..", "..", "include", "camo_poly.h"), os.path.join("..", "..", "include", "camo_contours.h"), os.path.join("..", "..", "include", "camo_split.h"), os.path.join("..", "..", "include", "camo_split_geo.h"), os.path.join("..", "..", "include", "camo_split_merge.h"), os.path.join("..", "..", "include", "camo_augment.h"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-file additions.  fused_wide2.hip: no SLP vectorisation (v_pk_*_f32 beside MFMAs cost more issue time than the two scalar
 # instructions they replace: MI355X guide, cycle constants) and no NaN canonicalisation in front of every v_max_f32 (the kernel

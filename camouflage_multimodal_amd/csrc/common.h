@@ -106,6 +106,13 @@ __device__ __forceinline__ int wave_scan_int(int v) {
   for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
   return v;
 }
+// the same in 64 bits (rle.hip's run starts, contours.hip's a2 terms)
+__device__ __forceinline__ long long wave_scan_ll(long long v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const long long t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+  return v;
+}
 __device__ __forceinline__ int wave_min_int(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));

@@ -1,5 +1,5 @@
 // C ABI of the image pipeline around the detector (include/camo_instances.h, camo_inst_match.h, camo_boundary.h, camo_guided.h,
-// camo_rle.h, camo_poly.h, camo_split.h, camo_split_geo.h, camo_split_merge.h): argument checks, workspace carving and the launchers' calls.  No device code here.
+// camo_rle.h, camo_poly.h, camo_contours.h, camo_split.h, camo_split_geo.h, camo_split_merge.h): argument checks, workspace carving and the launchers' calls.  No device code here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,6 +11,7 @@
 #include "guided.h"
 #include "rle.h"
 #include "poly.h"
+#include "contours.h"
 #include "split.h"
 #include "../../include/camo_rg_detect.h"
 #include "../../include/camo_instances.h"
@@ -19,6 +20,7 @@
 #include "../../include/camo_guided.h"
 #include "../../include/camo_rle.h"
 #include "../../include/camo_poly.h"
+#include "../../include/camo_contours.h"
 #include "../../include/camo_split.h"
 #include "../../include/camo_split_geo.h"
 #include "../../include/camo_split_merge.h"
@@ -393,6 +395,37 @@ int camo_poly_decode(const double* xy, int32_t V, const int32_t* poly_off, int32
   if (int e = ws_check(ws, ws_bytes, w.bytes, "camo_poly_decode_workspace_bytes")) return e;
   CK(launch_poly_decode(xy, V, poly_off, P, ann_poly_off, ann_image, ann_value, A, N, H, W, w, labels, reinterpret_cast<long long*>(ann_area),
                         static_cast<hipStream_t>(stream)), "poly decode");
+  return 0;
+}
+
+// ---- Instance contours: label maps to rings of corner vertices (include/camo_contours.h) ---------------------------
+static int contour_check(int N, int H, int W, int C, int R, int V) {
+  if (int e = inst_check(N, H, W)) return e;
+  if (C < 1 || C > 4ll * H * W) return fail(CAMO_E_ARG, "C must be in [1, 4 H W]");
+  if (R < 1) return fail(CAMO_E_ARG, "R must be >= 1");
+  if (V < 1) return fail(CAMO_E_ARG, "V must be >= 1");
+  if ((long long)N * C > CAMO_CONTOUR_MAX_CRACKS) return fail(CAMO_E_ARG, "N * C exceeds CAMO_CONTOUR_MAX_CRACKS");
+  if ((long long)N * R > CAMO_CONTOUR_MAX_RINGS) return fail(CAMO_E_ARG, "N * R exceeds CAMO_CONTOUR_MAX_RINGS");
+  if ((long long)N * V > CAMO_CONTOUR_MAX_VERTICES) return fail(CAMO_E_ARG, "N * V exceeds CAMO_CONTOUR_MAX_VERTICES");
+  return 0;
+}
+
+size_t camo_contours_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t R, int32_t V) {
+  if (contour_check(N, H, W, C, R, V)) return 0;
+  return contour_carve(N, H, W, C, nullptr).bytes;
+}
+
+int camo_contours(const int32_t* labels, int32_t N, int32_t H, int32_t W, int32_t connectivity, int32_t C, int32_t R, int32_t V, int64_t* rings,
+                  int32_t* xy, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = contour_check(N, H, W, C, R, V)) return e;
+  if (connectivity != 4 && connectivity != 8) return fail(CAMO_E_ARG, "connectivity must be 4 or 8");
+  if (!labels || !rings || !xy || !counts || !ws) return fail(CAMO_E_ARG, "null pointer argument");
+  if ((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(counts)) & 3) return fail(CAMO_E_ARG, "labels and counts must be 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(rings) | reinterpret_cast<uintptr_t>(xy)) & 7) return fail(CAMO_E_ARG, "rings and xy must be 8-byte aligned");
+  const ContourWs w = contour_carve(N, H, W, C, ws);
+  if (int e = ws_check(ws, ws_bytes, w.bytes, "camo_contours_workspace_bytes")) return e;
+  CK(launch_contours(labels, N, H, W, connectivity, C, R, V, w, reinterpret_cast<long long*>(rings), xy, counts, static_cast<hipStream_t>(stream)),
+     "contours");
   return 0;
 }
 }  // extern "C"

@@ -91,14 +91,6 @@ __global__ __launch_bounds__(NT) void rle_emit_kernel(const int* __restrict__ la
   for (long long r = min(counts[2 * n], R) + (long long)blockIdx.x * NT + threadIdx.x; r < R; r += step) rows[r] = make_int2(0, 0);
 }
 
-// inclusive prefix sum over the lanes in 64 bits
-__device__ __forceinline__ long long wave_scan_ll(long long v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const long long t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-  return v;
-}
-
 // grid (annotations + clear blocks).  Block a < A: start[i] of annotation a's counts, ann_sum[a].  The others: labels to 0.
 __global__ __launch_bounds__(NT) void rle_prefix_kernel(const int* __restrict__ cnts, int total, const int* __restrict__ ann_off,
                                                         const int* __restrict__ ann_image, const int* __restrict__ ann_value, int A, int N, int HW,

@@ -1,9 +1,9 @@
-"""The detection pipeline on MI355X: images in, masks, instances, matches and benchmark measures out (DESIGN.md 10d, 10g - 10o).
+"""The detection pipeline on MI355X: images in, masks, instances, matches and benchmark measures out (DESIGN.md 10d, 10g - 10o, 10v).
 
 ``detect_camouflage_batch`` (and the reference's name for one image, ``detect_camouflage``) runs the detector on a batch of one
 size; ``detect_camouflage_ragged`` takes uint8 images of mixed sizes through it and back to their own sizes, and
 ``detect_camouflage_directory`` takes a folder of files through that.  Everything here is host-side plumbing on top of the kernel
-bindings -- region_graph.py, rg_detect.py, seg_measures.py, instances.py, instance_match.py, boundary.py, rle.py, polygons.py,
+bindings -- region_graph.py, rg_detect.py, seg_measures.py, instances.py, instance_match.py, boundary.py, rle.py, polygons.py, contours.py,
 resize.py, refine.py -- and what the entry points share is stated once: ``_by_size`` (images of equal size share a library call) and
 ``_match_ground_truth`` (where the ground-truth ids of ``match`` come from).  This module imports all of those and is imported by
 rg_finetune.py only.  There is no CPU path: tensors that are not on a HIP device raise.
@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, boundary as _boundary, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures, \
+from . import _lib, boundary as _boundary, contours as _contours, instance_match as _match, instances as _instances, polygons as _polygons, refine as _refine, rle as _rle, seg_measures, \
     split as _split
 from .region_graph import _as_tensor, _image_batch, create_region_graphs_from_segments, slic_label_bound, slic_segments
 from .resize import _device, _mask_list, _packed, _ragged, resize_batch, resize_to_sizes
@@ -141,7 +141,7 @@ def _match_ground_truth(match, n, noun, sizes, masks, connectivity, device):
 @torch.no_grad()
 def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False,
                             instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None,
-                            split=False):
+                            split=False, polygons=False):
     """``detect_camouflage`` of the reference (models/region_graph/test.py) for a batch: ``images`` [N, H, W, 3] float in [0, 1] ->
     {"prob_maps": fp32 [N, 3, H, W] (mask, instance, edge probability of every pixel's superpixel), "mask": bool [N, H, W]
     (mask probability > ``threshold``), "node_probs": [n, 3], "graphs": RegionGraphBatch, "segments": int32 [N, H, W],
@@ -188,10 +188,16 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
     "instances", "instance_labels", "clean_mask" and every metric of the mask keep their bytes.  "merge" in ``split`` -- a pair
     (num, den), e.g. (4, 5) -- joins the parts across their high passes after the split (``split.merge_parts``,
     include/camo_split_merge.h): "split_instances" and "split_labels" are then the merged ones, "split_counts" stays the splitter's,
-    and the one key more is "split_merge_counts" int32 [N, 4]."""
+    and the one key more is "split_merge_counts" int32 [N, 4].
+    ``polygons=True`` (needs ``instances=True``) adds "instance_polygons": per image {id: {"polygons": [[x0, y0, x1, y1, ...], ...],
+    "holes": [...], "area": pixels}}, the outlines of every instance of the labels ``rle`` works on, vertices on pixel corners, traced
+    with the call's ``connectivity`` (``contours.encode_instance_polygons``, include/camo_contours.h); a polygon list is a union, so
+    painting "polygons" back rebuilds an instance with its holes filled -- exact with ``fill_holes=True``, and "holes" carries what to
+    subtract without it.  ``False``: no launch more than before."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
+    polygons = _contours.contour_options(polygons, instances)
     split = _split.split_options(split, instances)
     match = _match.match_options(match, instances, gt_masks is not None)
     boundary = _boundary.boundary_options(boundary, match)
@@ -238,6 +244,8 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
                                                                                                         match, boundary)
         if rle:
             out["instance_rles"] = _rle.encode_instances(found["labels"])
+        if polygons:
+            out["instance_polygons"] = _contours.encode_instance_polygons(found["labels"], connectivity)
     if boundary is not None and gt is not None:
         out["boundary_iou"] = _boundary.boundary_iou(out["mask"], _positive(gt), boundary["distance"], boundary["ratio"])
     if refine is not None:
@@ -254,20 +262,21 @@ def detect_camouflage_batch(rg_model, images, gt_masks=None, n_segments=500, thr
 
 
 def detect_camouflage(rg_model, image, gt_mask=None, n_segments=500, threshold=0.5, device="cuda", cod_metrics=False, instances=False,
-                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None, split=False):
+                      min_area=0, fill_holes=False, connectivity=8, refine=None, *, match=None, rle=False, boundary=None, split=False,
+                      polygons=False):
     """The reference function's name: ``detect_camouflage_batch`` on one ``image`` [H, W, 3] (``gt_mask`` [H, W]); same dict."""
     img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image).to(torch.device(device))
     if img.dim() != 3:
         raise ValueError(f"need image [H, W, 3], got {tuple(img.shape)}")
     gt = None if gt_mask is None else (gt_mask if isinstance(gt_mask, torch.Tensor) else torch.as_tensor(gt_mask)).unsqueeze(0)
     return detect_camouflage_batch(rg_model, img.unsqueeze(0), gt, n_segments, threshold, device, cod_metrics, instances, min_area, fill_holes,
-                                   connectivity, refine, match=match, rle=rle, boundary=boundary, split=split)
+                                   connectivity, refine, match=match, rle=rle, boundary=boundary, split=split, polygons=polygons)
 
 
 @torch.no_grad()
 def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n_segments=500, threshold=0.5, device="cuda",
                              cod_metrics=False, evaluate_at="native", instances=False, min_area=0, fill_holes=False, connectivity=8, refine=None,
-                             *, match=None, rle=False, boundary=None, split=False):
+                             *, match=None, rle=False, boundary=None, split=False, polygons=False):
     """``detect_camouflage_batch`` for uint8 images of mixed sizes (``resize_batch``'s ``images``): resized to ``size`` (bilinear) on
     the device, detected there, and the mask probability resized back to every image's own size (bilinear).  Returns
     ``detect_camouflage_batch``'s dict (everything at ``size``) plus "prob_maps_native": the list of fp32 [H_i, W_i] maps (views of
@@ -299,10 +308,15 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
     ``split`` (``detect_camouflage_batch``'s; needs ``instances=True``) splits the NATIVE-size instances, maps of equal size sharing a
     call: "split_instances_native" (per image the records), "split_labels_native" (int32 [H_i, W_i]) and "split_counts_native"
     (int32 [4]); ``match``, ``boundary`` and ``rle`` then work on them.  With "merge" in ``split`` they are the merged ones, and
-    "split_merge_counts_native" (int32 [4] per image) is the one key more."""
+    "split_merge_counts_native" (int32 [4] per image) is the one key more.
+    ``polygons=True`` (needs ``instances=True``) adds "instance_polygons_native": per image {id: {"polygons", "holes", "area"}} of the
+    labels ``rle`` works on, in NATIVE coordinates (``contours.encode_instance_polygons`` with ``connectivity``; maps of equal size
+    share a call); painting "polygons" back rebuilds an instance with its holes filled, so the round trip is exact with
+    ``fill_holes=True`` and "holes" carries what to subtract without it."""
     if instances:
         _instances.check_arguments(threshold, connectivity, min_area)
     rle = _rle.rle_options(rle, instances)
+    polygons = _contours.contour_options(polygons, instances)
     split = _split.split_options(split, instances)
     match = _match.match_options(match, instances, gt_masks is not None and evaluate_at == "native")
     boundary = _boundary.boundary_options(boundary, match)
@@ -358,6 +372,8 @@ def detect_camouflage_ragged(rg_model, images, gt_masks=None, size=(256, 256), n
                 out["boundary_match"], out["boundary_match_tables"] = _native_boundary_matches(labels, tables, gt_labels, match, boundary)
         if rle:
             out["instance_rles_native"] = _by_size(labels, lambda idx, _: _rle.encode_instances(_stack(labels, idx)))
+        if polygons:
+            out["instance_polygons_native"] = _by_size(labels, lambda idx, _: _contours.encode_instance_polygons(_stack(labels, idx), connectivity))
     if boundary is not None and truth is not None:
         out["boundary_iou"] = _native_boundary_ious(out["mask_native"], truth, boundary)
     if refine is not None:
@@ -385,7 +401,8 @@ def _files_by_stem(folder):
     return {os.path.splitext(f)[0]: os.path.join(folder, f) for f in sorted(os.listdir(folder)) if f.lower().endswith(IMAGE_SUFFIXES)}
 
 
-def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None, batch_size=16, results_json=None, image_ids=None, **kw):
+def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None, batch_size=16, results_json=None, image_ids=None,
+                                annotations_json=None, **kw):
     """``detect_camouflage_ragged`` over the image files of ``image_dir`` (read with PIL, in sorted order, ``batch_size`` at a time;
     ``**kw`` goes to it).  With ``mask_dir`` every image needs a mask file of the same stem.  With ``out_dir`` every native-size mask
     probability is written there as ``<stem>.png``, 8 bits, quantised as include/camo_seg_measures.h quantises (``quantise_map``).
@@ -407,7 +424,13 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
     "boundary_ap": ``InstanceAP`` over them, which is Boundary AP; with masks scored at native size also "boundary_iou" per file and,
     with ``refine``, "refined_boundary_iou".
     With ``split`` (``detect_camouflage_ragged``'s; needs ``instances=True``) the instances matched, scored and written to
-    ``results_json`` are the split ones ("split_instances_native"), the merged ones with "merge" in ``split``."""
+    ``results_json`` are the split ones ("split_instances_native"), the merged ones with "merge" in ``split``.
+    ``annotations_json`` (a path; needs ``instances=True``, sets ``polygons=True``) writes the same instances as a COCO annotations
+    file {"images", "annotations", "categories": [{"id": 1, "name": "camouflaged"}]} with native-size polygons
+    (``contours.coco_annotations``): what ``polygons.coco_ground_truth`` and "gt_coco" read, so the detector's proposals can be
+    corrected in an annotation tool and fine-tuned from.  ``image_ids`` applies as for ``results_json``, and the two files may be asked
+    for together; the result also holds "annotations": the file's dict.  A polygon list is a union, so a reader rebuilds every instance
+    with its holes filled: the round trip is exact with ``fill_holes=True``, and "holes" carries what to subtract without it."""
     from PIL import Image
     refined = _refine.refine_options(kw.get("refine")) is not None
     found_key = "instances_native" if _split.split_options(kw.get("split", False), kw.get("instances", False)) is None else "split_instances_native"
@@ -419,8 +442,14 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         if not kw.get("instances", False):
             raise ValueError("results_json needs instances=True: the instances are what it writes")
         kw["rle"] = True
-    elif image_ids is not None:
-        raise ValueError("image_ids needs results_json")
+    if annotations_json is not None:
+        if not isinstance(annotations_json, (str, os.PathLike)):
+            raise ValueError(f"annotations_json must be a path, got {annotations_json!r}")
+        if not kw.get("instances", False):
+            raise ValueError("annotations_json needs instances=True: the instances are what it writes")
+        kw["polygons"] = True
+    if image_ids is not None and results_json is None and annotations_json is None:
+        raise ValueError("image_ids needs results_json or annotations_json")
     if image_ids is not None and not isinstance(image_ids, dict):
         raise ValueError(f"image_ids must be a dict from file stem to image id, got {type(image_ids).__name__}")
     cod = bool(kw.pop("cod_metrics", False))
@@ -448,13 +477,13 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         if coco is not None:
             truth = _polygons.coco_ground_truth(coco, stems)
             match["gt_segmentations"], coco_sizes = truth["segmentations"], truth["sizes"]
-            if results_json is not None and image_ids is None:
+            if (results_json is not None or annotations_json is not None) and image_ids is None:
                 image_ids = truth["image_ids"]
         _check_sources(match, len(stems), "files")      # (for the whole directory, before any file is read)
         source = next((key for key, _ in GT_SOURCES if match[key] is not None), None)
     if image_ids is not None and set(stems) - set(image_ids):
         raise ValueError(f"image_ids has no entry for {sorted(set(stems) - set(image_ids))[:5]}")
-    results = []
+    results, coco_images, coco_anns = [], [], []
     for at in range(0, len(stems), int(batch_size)):
         part = stems[at:at + int(batch_size)]
         arrays = [np.array(Image.open(images[s]).convert("RGB")) for s in part]
@@ -479,6 +508,10 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
                 bd_ap.add(out["boundary_match"], scores)
         if results_json is not None:
             results += _rle.coco_results(part, out[found_key], out["instance_rles_native"], image_ids)
+        if annotations_json is not None:
+            ims, anns = _contours.coco_annotations(part, [a.shape[:2] for a in arrays], out[found_key], out["instance_polygons_native"], image_ids)
+            coco_images += ims
+            coco_anns += [dict(a, id=len(coco_anns) + k + 1) for k, a in enumerate(anns)]      # (numbered over the whole directory)
         native = out["prob_maps_native_refined" if refined else "prob_maps_native"]
         if out_dir is not None:
             for s, p in zip(part, native):
@@ -513,4 +546,8 @@ def detect_camouflage_directory(rg_model, image_dir, mask_dir=None, out_dir=None
         with open(results_json, "w") as f:
             json.dump(results, f)
         result["results"] = results
+    if annotations_json is not None:
+        result["annotations"] = {"images": coco_images, "annotations": coco_anns, "categories": [{"id": 1, "name": "camouflaged"}]}
+        with open(annotations_json, "w") as f:
+            json.dump(result["annotations"], f)
     return result
